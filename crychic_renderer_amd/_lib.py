@@ -99,6 +99,9 @@ PROTOTYPES = {
     "crychic_deferred_light_points": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _P(_vp), _u32, _vp, _u32, _vp,
                                            _vp, _u32, _u32, _u32, _u32, _i, _f, _u32, _vp, _u32, _vp]),
     "crychic_draw_hot_path": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _vp]),
+    "crychic_deferred_light_spots": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _P(_vp), _u32, _vp, _u32, _vp,
+                                          _vp, _u32, _u32, _u32, _u32, _i, _f, _u32, _vp, _u32, _vp, _u32, _vp]),
+    "crychic_draw_hot_path_spots": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _vp, _u32, _vp]),
     "crychic_frustum_cull": (_i, [_P(Camera), _P(_f), _P(_f), _vp, _u32, _vp]),
     "crychic_ctx_set_profiling": (_i, [_vp, _i]),
     "crychic_ctx_last_pass_times": (_i, [_vp, _P(PassTimes)]),
@@ -115,6 +118,8 @@ PROTOTYPES = {
     "crychic_allgather_frame_all": (_i, [_P(_vp), _i, _P(_vp), _u32, _u32, _P(_u32), _P(_vp)]),
     "crychic_comm_barrier": (_i, [_vp, _vp]),
     "crychic_draw_hot_path_shared": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _P(_u32), _u32, _vp]),
+    "crychic_draw_hot_path_shared_spots": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _P(_u32), _u32, _vp, _u32,
+                                                _vp]),
     "crychic_create_box": (_i, [_f, _f, _f, _u32, _vp, _u32, _vp, _u32, _P(_u32)]),
     "crychic_create_grid": (_i, [_f, _f, _u32, _u32, _vp, _u32, _vp, _u32, _P(_u32)]),
     "crychic_load_mesh_text": (_i, [C.c_char_p, _vp, _u32, _vp, _u32, _P(_u32), _P(_u32)]),

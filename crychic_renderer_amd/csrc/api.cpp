@@ -166,6 +166,14 @@ int fill_light_params(cry::LightParams& P, const crychic_pass_constants* cb, con
     return 0;
 }
 
+// Spot lights (crychic_deferred_light_spots and the _spots hot paths): at most 1024, from a device buffer when there are any.
+int check_spot_lights(const crychic_light* spots, uint32_t n)
+{
+    if (n > cry::kMaxSpotLights || (n && !spots))
+        return fail(CRYCHIC_E_INVALID_ARG, "numSpotLights %u (max %u) / null spot light buffer", n, cry::kMaxSpotLights);
+    return 0;
+}
+
 // With a mip chain the level of detail comes from 2 x 2 pixel quads: a call's rows have to be whole quad rows.
 int check_chain_rows(const cry::LightParams& P, uint32_t row0, uint32_t rows, uint32_t H)
 {
@@ -304,6 +312,19 @@ int crychic_deferred_light_points(crychic_ctx* ctx, const crychic_pass_constants
                                   uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags,
                                   const crychic_light* point_lights_dev, uint32_t numPointLights, void* stream)
 {
+    return crychic_deferred_light_spots(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev, cubeDim,
+                                        out_rgba8_dev, radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags,
+                                        point_lights_dev, numPointLights, nullptr, 0u, stream);
+}
+
+int crychic_deferred_light_spots(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev,
+                                 const float* g2_dev, const uint32_t* depth_dev, const uint16_t* ambient_dev,
+                                 const uint32_t* const shadow_dev[4], uint32_t shadowDim, const uint8_t* cube_dev,
+                                 uint32_t cubeDim, uint8_t* out_rgba8_dev, float* radiance_out_dev, uint32_t W, uint32_t H,
+                                 uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags,
+                                 const crychic_light* point_lights_dev, uint32_t numPointLights,
+                                 const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream)
+{
     if (int rc = bind(ctx)) return rc;
     if (int rc = check_dims(W, H)) return rc;
     if (!cb || !g0_dev || !g1_dev || !g2_dev || !depth_dev || !shadow_dev || !cube_dev || !out_rgba8_dev)
@@ -311,13 +332,14 @@ int crychic_deferred_light_points(crychic_ctx* ctx, const crychic_pass_constants
     if (row0 > H || rows > H - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row frame", row0, rows, H);
     if (numPointLights > cry::kMaxPointLights || (numPointLights && !point_lights_dev))
         return fail(CRYCHIC_E_INVALID_ARG, "numPointLights %u (max %u) / null light buffer", numPointLights, cry::kMaxPointLights);
+    if (int rc = check_spot_lights(spot_lights_dev, numSpotLights)) return rc;
     cry::LightParams P;
     if (int rc = fill_light_params(P, cb, shadow_dev, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags)) return rc;
     P.pointLights = point_lights_dev;
     P.numPointLights = numPointLights;
     if (int rc = check_chain_rows(P, row0, rows, H)) return rc;
     CRY_HIP(cry::launch_light(P, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, cube_dev, out_rgba8_dev, radiance_out_dev,
-                              row0, rows, (hipStream_t)stream));
+                              row0, rows, (hipStream_t)stream, spot_lights_dev, numSpotLights));
     return 0;
 }
 
@@ -327,7 +349,8 @@ int crychic_deferred_light_points(crychic_ctx* ctx, const crychic_pass_constants
 // crychic_strip_rows cut of the strip's rows); after(user, part, row0, rows) runs behind part's launch -- comm.cpp hangs that
 // part's exchange there (crychic_draw_hot_path_shared).  nparts == 1, after == nullptr is crychic_draw_hot_path itself.
 int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
-                        const crychic_frame_desc* f, hipStream_t stream, uint32_t nparts, cry::PartHook after, void* user)
+                        const crychic_frame_desc* f, hipStream_t stream, uint32_t nparts, cry::PartHook after, void* user,
+                        const crychic_light* spots, uint32_t numSpots)
 {
     if (int rc = bind(ctx)) return rc;
     if (!ssaoCB || !passCB || !f) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
@@ -347,6 +370,7 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
         return fail(CRYCHIC_E_INVALID_ARG, "numPointLights %u (max %u) / null light buffer", f->numPointLights, cry::kMaxPointLights);
     P.pointLights = f->point_lights_dev;
     P.numPointLights = f->numPointLights;
+    if (int rc = check_spot_lights(spots, numSpots)) return rc;
     const bool prof = ctx->profiling;
     if (prof) { ctx->times_valid = false; CRY_HIP(hipEventRecord(ctx->ev[0], stream)); }
     if (ssaoOn) {
@@ -368,7 +392,7 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
         const uint32_t r1 = (p + 1u == nparts) ? f->row0 + f->rows : r0 + 2u * per;
         if (r1 > r0)
             CRY_HIP(cry::launch_light(P, f->g0_dev, f->g1_dev, f->g2_dev, f->depth_dev, ssaoOn ? f->ambient0_dev : nullptr,
-                                      f->cube_dev, f->out_rgba8_dev, nullptr, r0, r1 - r0, stream));
+                                      f->cube_dev, f->out_rgba8_dev, nullptr, r0, r1 - r0, stream, spots, numSpots));
         if (prof && p + 1u == nparts) { CRY_HIP(hipEventRecord(ctx->ev[3], stream)); ctx->times_valid = true; }
         if (after)
             if (int rc = after(user, p, r0, r1 - r0)) return rc;
@@ -382,6 +406,12 @@ int crychic_draw_hot_path(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB
                           const crychic_frame_desc* f, void* stream)
 {
     return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr);
+}
+
+int crychic_draw_hot_path_spots(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
+                                const crychic_frame_desc* f, const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream)
+{
+    return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr, spot_lights_dev, numSpotLights);
 }
 
 int crychic_ctx_set_profiling(crychic_ctx* ctx, int enabled)

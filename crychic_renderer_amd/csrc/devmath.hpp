@@ -247,8 +247,10 @@ CRY_HD float det_exp2(float x)
     if (x != x) return x;
     return det_exp2_clamped(clampf(x, -125.0f, 127.0f));
 }
-// HLSL pow(x, y) for 0 < y <= 1: below the smallest normal -> 0; negative or NaN -> NaN.  Branch-free:
-// the kernel runs on a safe stand-in and the specials are selected afterwards.
+// HLSL pow(x, y) = exp2(clamp(y * log2 x, -125, 127)): below the smallest normal -> 0; negative or NaN -> NaN.
+// Written for 0 < y <= 1; the same formula serves the spot lights' SpotPower (y = 0 gives exactly 1; relative error against
+// float64 for x in [0.001, 1], y <= 64: below 1e-5 while x^y >= 2^-125, tests/test_spot_lights.py).  Branch-free: the kernel runs on a safe stand-in and the
+// specials are selected afterwards.
 CRY_HD float det_pow(float x, float y)
 {
     const bool normal = x >= 1.17549435e-38f;

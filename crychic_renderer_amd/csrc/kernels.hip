@@ -525,15 +525,17 @@ __global__ __launch_bounds__(256) void light_kernel(LightParams P, const f4a* __
 // against the box (sphere of radius FalloffEnd vs AABB, conservatively inflated) and sets the light's bit in an LDS mask;
 // each pixel finally walks the set bits in ascending index order -- the accumulation order of the un-culled loop -- and
 // applies the exact per-pixel range test, so culling never changes a bit of the result.
-template <bool ZERO_RADIUS, bool MIPS = false>
-__global__ __launch_bounds__(256) void light_points_kernel(LightParams P, const f4a* __restrict__ g0, const f4a* __restrict__ g1,
-                                                           const f4a* __restrict__ g2, const uint32_t* __restrict__ depth,
-                                                           const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
-                                                           uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0,
-                                                           uint32_t row1)
+// SPOTS (light_spots_kernel): the spot lights of their own buffer are culled by the same sphere test in the same step into a
+// second mask, and walked after the point lights (the gLights order).  The cull stays spherical: a spot light contributes
+// outside its cone too (the 0.001 floor of PBR.hlsl:142), so only the range test is exact.
+template <bool ZERO_RADIUS, bool MIPS, bool SPOTS>
+__device__ __forceinline__ void light_local_tile(const LightParams& P, const f4a* __restrict__ g0, const f4a* __restrict__ g1,
+                                                 const f4a* __restrict__ g2, const uint32_t* __restrict__ depth,
+                                                 const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
+                                                 uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0, uint32_t row1,
+                                                 float (*s_box)[6], uint32_t* s_mask, const crychic_light* __restrict__ spots,
+                                                 uint32_t numSpots, uint32_t* s_spotMask)
 {
-    __shared__ float s_box[4][6];
-    __shared__ uint32_t s_mask[kMaxPointLights / 32];
     uint32_t bx, by;
     tile_origin<0>(bx, by);
     uint32_t x, y;
@@ -558,6 +560,7 @@ __global__ __launch_bounds__(256) void light_points_kernel(LightParams P, const 
     const uint32_t wave = threadIdx.x >> 6;
     if ((threadIdx.x & 63u) == 0) { for (int c = 0; c < 3; ++c) { s_box[wave][c] = lo[c]; s_box[wave][3 + c] = hi[c]; } }
     if (threadIdx.x < kMaxPointLights / 32) s_mask[threadIdx.x] = 0u;
+    if (SPOTS && threadIdx.x < kMaxSpotLights / 32) s_spotMask[threadIdx.x] = 0u;
     __syncthreads();
     float blo[3], bhi[3];
 #pragma unroll
@@ -566,20 +569,29 @@ __global__ __launch_bounds__(256) void light_points_kernel(LightParams P, const 
         bhi[c] = __builtin_fmaxf(__builtin_fmaxf(s_box[0][3 + c], s_box[1][3 + c]), __builtin_fmaxf(s_box[2][3 + c], s_box[3][3 + c]));
     }
     // 2. cull: light l touches the tile if dist(Position, box) <= FalloffEnd (inflated: the per-pixel test is the exact one)
+    auto touches = [&](const crychic_light& L) {
+        float d2 = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float p = L.Position[c];
+            const float e = __builtin_fmaxf(__builtin_fmaxf(blo[c] - p, p - bhi[c]), 0.0f);
+            d2 += e * e;
+        }
+        const float r = L.FalloffEnd * 1.0001f + 1.0e-3f;
+        return d2 <= r * r;
+    };
     const bool anyCovered = blo[0] <= bhi[0];
-    if (anyCovered)
+    if (anyCovered) {
         for (uint32_t l = threadIdx.x; l < P.numPointLights; l += 256u) {
             const crychic_light L = P.pointLights[l];
-            float d2 = 0.0f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float p = L.Position[c];
-                const float e = __builtin_fmaxf(__builtin_fmaxf(blo[c] - p, p - bhi[c]), 0.0f);
-                d2 += e * e;
-            }
-            const float r = L.FalloffEnd * 1.0001f + 1.0e-3f;
-            if (d2 <= r * r) atomicOr(&s_mask[l >> 5], 1u << (l & 31u));
+            if (touches(L)) atomicOr(&s_mask[l >> 5], 1u << (l & 31u));
         }
+        if (SPOTS)
+            for (uint32_t l = threadIdx.x; l < numSpots; l += 256u) {
+                const crychic_light L = spots[l];
+                if (touches(L)) atomicOr(&s_spotMask[l >> 5], 1u << (l & 31u));
+            }
+    }
     __syncthreads();
     float lod = 0.0f;
     f4a G2{ 0, 0, 0, 0 };
@@ -603,6 +615,17 @@ __global__ __launch_bounds__(256) void light_points_kernel(LightParams P, const 
                     pbr_point_light(P.pointLights[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
                 }
             }
+            if (SPOTS) {
+                const uint32_t spotWords = (numSpots + 31u) >> 5;
+                for (uint32_t w = 0; w < spotWords; ++w) {
+                    uint32_t m = s_spotMask[w];
+                    while (m) {
+                        const uint32_t b = (uint32_t)__builtin_ctz(m);
+                        m &= m - 1u;
+                        pbr_spot_light(spots[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
+                    }
+                }
+            }
         };
         if (MIPS) lit = light_pixel<ZERO_RADIUS, decltype(culled), true, CubeChain>(P, G0, g1[idx], G2, ambient, cube, culled, CubeChain{ lod, cube_chain_flat(lod) });
         else lit = light_pixel<ZERO_RADIUS, decltype(culled), true>(P, G0, g1[idx], g2[idx], ambient, cube, culled);
@@ -613,6 +636,33 @@ __global__ __launch_bounds__(256) void light_points_kernel(LightParams P, const 
     }
     if (radiance) radiance[idx] = f4a{ lit.x, lit.y, lit.z, lit.w };
     out[idx] = pack_rgba8(lit);
+}
+
+template <bool ZERO_RADIUS, bool MIPS = false>
+__global__ __launch_bounds__(256) void light_points_kernel(LightParams P, const f4a* __restrict__ g0, const f4a* __restrict__ g1,
+                                                           const f4a* __restrict__ g2, const uint32_t* __restrict__ depth,
+                                                           const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
+                                                           uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0,
+                                                           uint32_t row1)
+{
+    __shared__ float s_box[4][6];
+    __shared__ uint32_t s_mask[kMaxPointLights / 32];
+    light_local_tile<ZERO_RADIUS, MIPS, false>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask, nullptr, 0u, nullptr);
+}
+
+// The same pass with `numSpots` (1 .. 1024) spot lights after the point lights (crychic_deferred_light_spots); zero spot lights
+// take light_points_kernel / light_kernel, so this kernel is never the reference configuration's.
+template <bool ZERO_RADIUS, bool MIPS = false>
+__global__ __launch_bounds__(256) void light_spots_kernel(LightParams P, const f4a* __restrict__ g0, const f4a* __restrict__ g1,
+                                                          const f4a* __restrict__ g2, const uint32_t* __restrict__ depth,
+                                                          const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
+                                                          uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0,
+                                                          uint32_t row1, const crychic_light* __restrict__ spots, uint32_t numSpots)
+{
+    __shared__ float s_box[4][6];
+    __shared__ uint32_t s_mask[kMaxPointLights / 32];
+    __shared__ uint32_t s_spotMask[kMaxSpotLights / 32];
+    light_local_tile<ZERO_RADIUS, MIPS, true>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask, spots, numSpots, s_spotMask);
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------
@@ -767,12 +817,21 @@ hipError_t launch_blur_replay_chain(const crychic_ssao_constants& cb, const void
 
 hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, const float* g2,
                         const uint32_t* depth, const uint16_t* ambient, const uint8_t* cube, uint8_t* out,
-                        float* radiance, uint32_t row0, uint32_t rows, hipStream_t stream)
+                        float* radiance, uint32_t row0, uint32_t rows, hipStream_t stream, const crychic_light* spots,
+                        uint32_t numSpots)
 {
     if (rows == 0) return hipSuccess;
     const dim3 grid = grid_for(P.W, rows);
     const bool mips = P.cubeLevels > 1u;          // the chain: quads inside wavefronts (light_tile_pixel), so the rows must start a quad
     if (mips && (row0 & 1u)) return hipErrorInvalidValue;
+    if (numSpots) {
+#define CRY_LAUNCH_SPOTS(K) hipLaunchKernelGGL(K, grid, dim3(256), 0, stream, P, (const f4a*)g0, (const f4a*)g1, (const f4a*)g2, depth, ambient, \
+                                               (const uint32_t*)cube, (uint32_t*)out, (f4a*)radiance, row0, row0 + rows, spots, numSpots)
+        if (P.pcfSearchRadius == 0.0f) { if (mips) CRY_LAUNCH_SPOTS((light_spots_kernel<true, true>)); else CRY_LAUNCH_SPOTS((light_spots_kernel<true, false>)); }
+        else { if (mips) CRY_LAUNCH_SPOTS((light_spots_kernel<false, true>)); else CRY_LAUNCH_SPOTS((light_spots_kernel<false, false>)); }
+#undef CRY_LAUNCH_SPOTS
+        return hipGetLastError();
+    }
     if (P.numPointLights) {
 #define CRY_LAUNCH_POINTS(K) hipLaunchKernelGGL(K, grid, dim3(256), 0, stream, P, (const f4a*)g0, (const f4a*)g1, (const f4a*)g2, depth, ambient, \
                                                 (const uint32_t*)cube, (uint32_t*)out, (f4a*)radiance, row0, row0 + rows)

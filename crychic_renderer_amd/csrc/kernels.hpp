@@ -40,9 +40,11 @@ hipError_t launch_blur_replay(const crychic_ssao_constants& cb, const void* edge
 hipError_t launch_blur_replay_chain(const crychic_ssao_constants& cb, const void* edge_base, uint16_t* plane0, uint16_t* plane1, uint32_t W, uint32_t H,
                                     int blurCount, uint32_t row0, uint32_t rows, uint32_t stamp, hipStream_t stream);
 
+// spots / numSpots (<= 1024): spot lights after P's point lights (light_spots_kernel); 0 = the point-light or reference kernels.
 hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, const float* g2,
                         const uint32_t* depth, const uint16_t* ambient, const uint8_t* cube, uint8_t* out,
-                        float* radiance, uint32_t row0, uint32_t rows, hipStream_t stream);
+                        float* radiance, uint32_t row0, uint32_t rows, hipStream_t stream, const crychic_light* spots = nullptr,
+                        uint32_t numSpots = 0);
 
 
 // ---- producer passes (raster.hip) ----

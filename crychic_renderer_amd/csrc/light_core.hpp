@@ -48,6 +48,7 @@ CRY_HD void light_params_derive(LightParams& P)
 }
 
 constexpr uint32_t kMaxPointLights = 1024;   // tile masks live in LDS: 32 words
+constexpr uint32_t kMaxSpotLights = 1024;    // the same for the spot lights' mask
 
 // Common.hlsl:167-171 (noise is a scalar broadcast, so abs(noise.x + noise.y) * 0.5 == noise)
 CRY_HD float nrand(float u, float v)
@@ -323,6 +324,23 @@ CRY_HD void pbr_point_light(const crychic_light& L, f3 pos, f3 albedo, float rou
     const float rd = rcp(d);
     const f3 ln{ l.x * rd, l.y * rd, l.z * rd };
     const float att = saturate(divf(L.FalloffEnd - d, L.FalloffEnd - L.FalloffStart));
+    pbr_light<true>(ln, L.Strength, att, albedo, roughness, metalness, normal, view, 1.0f, result, fixQ3, fixQ4);
+}
+
+// Spot light, BUILD-DEFINED EXTENSION (crychic_hip.h crychic_deferred_light_spots): the reference's branch (PBR.hlsl:126-147) is
+// dead code as well; enabled like the point light with att *= pow(max(dot(-Direction, l), 0.001), SpotPower) -- det_pow, the
+// general pow, Direction used as given.  SpotPower = 0 makes the factor exactly 1: the point light's bits.
+CRY_HD void pbr_spot_light(const crychic_light& L, f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view,
+                           f3& result, bool fixQ3 = false, bool fixQ4 = false)
+{
+    const f3 l{ L.Position[0] - pos.x, L.Position[1] - pos.y, L.Position[2] - pos.z };
+    const float d = len_from_sq(dot3(l, l));
+    if (d > L.FalloffEnd) return;
+    const float rd = rcp(d);
+    const f3 ln{ l.x * rd, l.y * rd, l.z * rd };
+    float att = saturate(divf(L.FalloffEnd - d, L.FalloffEnd - L.FalloffStart));
+    const f3 spotDir{ -L.Direction[0], -L.Direction[1], -L.Direction[2] };                          // PBR.hlsl:128
+    att = att * det_pow(maxnn(dot3(spotDir, ln), 0.001f), L.SpotPower);                              // :142
     pbr_light<true>(ln, L.Strength, att, albedo, roughness, metalness, normal, view, 1.0f, result, fixQ3, fixQ4);
 }
 
@@ -700,6 +718,16 @@ struct AllPointLights {
     CRY_HD void operator()(f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view, f3& result, bool fixQ3, bool fixQ4) const
     {
         for (uint32_t i = 0; i < n; ++i) pbr_point_light(lights[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
+    }
+};
+// Every point light, then every spot light (the gLights order, Common.hlsl:102-105), un-culled: the host build's iteration.
+struct AllLocalLights {
+    const crychic_light* points; uint32_t nPoints;
+    const crychic_light* spots; uint32_t nSpots;
+    CRY_HD void operator()(f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view, f3& result, bool fixQ3, bool fixQ4) const
+    {
+        for (uint32_t i = 0; i < nPoints; ++i) pbr_point_light(points[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
+        for (uint32_t i = 0; i < nSpots; ++i) pbr_spot_light(spots[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
     }
 };
 

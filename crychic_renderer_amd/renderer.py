@@ -167,6 +167,7 @@ class Crychic:
         self.pcfSearchRadius = lib.crychic_pcf_search_radius(shadow_dim, 1)  # Common.hlsl:305 as written
         self.flags = 0
         self.mPointLights = None     # extension: torch uint8 tensor holding an array of Light structs (48 B each)
+        self.mSpotLights = None      # extension: the same for the spot lights (crychic_draw_hot_path_spots)
         self._desc = None
 
     def load_scene(self, planes):
@@ -218,7 +219,8 @@ class Crychic:
                self.mDeferred.mGBuffer[0].data_ptr(), self.mDeferred.mGBuffer[1].data_ptr(), self.mDeferred.mGBuffer[2].data_ptr(),
                sm.data_ptr(), int(sm.shape[-1]), self.mCubeMap.data_ptr(), int(self.mCubeMapSize or self.mCubeMap.shape[1]), int(self.mCubeMapLevels),
                self.blurCount, self.numDirLights, self.pcfSearchRadius, self.flags,
-               0 if self.mPointLights is None else self.mPointLights.data_ptr())
+               0 if self.mPointLights is None else self.mPointLights.data_ptr(),
+               0 if self.mSpotLights is None else self.mSpotLights.data_ptr())
         if self._desc is None:
             self._desc = {}
         f = self._desc.get(key)
@@ -226,6 +228,15 @@ class Crychic:
             if len(self._desc) > 16:
                 self._desc.clear()
             f = self._desc[key] = self.frame_desc(row0, rows)
+        if self.mSpotLights is not None:       # extension: the _spots entries, for the whole frame, a strip or the shared path
+            spots, n = _ptr(self.mSpotLights), self.mSpotLights.numel() // 48
+            if shared is not None:
+                check(lib.crychic_draw_hot_path_shared_spots(shared[0], C.byref(self.mSsaoCB), C.byref(self.mMainPassCB), C.byref(f), shared[1],
+                                                             int(shared[2]), spots, n, _stream(self.ctx.device)))
+                return
+            check(lib.crychic_draw_hot_path_spots(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(self.mMainPassCB), C.byref(f), spots, n,
+                                                  _stream(self.ctx.device)))
+            return
         if shared is not None:
             check(lib.crychic_draw_hot_path_shared(shared[0], C.byref(self.mSsaoCB), C.byref(self.mMainPassCB), C.byref(f), shared[1],
                                                    int(shared[2]), _stream(self.ctx.device)))
@@ -250,6 +261,17 @@ class Crychic:
             import numpy as np
             host = np.frombuffer(bytes(lights), dtype=np.uint8).copy()
             self.mPointLights = torch.from_numpy(host).to(self.ctx.device)
+        self._desc = None
+
+    def set_spot_lights(self, lights):
+        """Extension: `lights` is a ctypes array of Light (or None); copied to the device.  Spot lights are lit after the point
+        lights (include/crychic_hip.h crychic_deferred_light_spots); None or an empty array = none."""
+        if lights is None or len(lights) == 0:
+            self.mSpotLights = None
+        else:
+            import numpy as np
+            host = np.frombuffer(bytes(lights), dtype=np.uint8).copy()
+            self.mSpotLights = torch.from_numpy(host).to(self.ctx.device)
         self._desc = None
 
     def set_profiling(self, enabled):

@@ -297,3 +297,25 @@ def point_light_grid(n=8, y=3.0, falloff_start=1.0, falloff_end=10.0, strength=1
             L.Position[:] = (-extent + 2.0 * extent * i / (n - 1), y, -extent + 2.0 * extent * j / (n - 1))
             L.SpotPower = 64.0
     return arr
+
+
+def spot_light_ring(n=32, radius=14.0, y=8.0, target=(0.0, 0.0, 0.0), falloff_start=2.0, falloff_end=30.0, strength=2.0,
+                    spot_power=8.0):
+    """Extension: n spot lights evenly spaced on a horizontal ring of `radius` at height y, each aimed at `target` (Direction
+    normalised here: the product uses it as given), linear falloff start..end, white strength -- seed-free.  Returns a ctypes
+    array of Light."""
+    import math
+    from ._lib import Light
+    arr = (Light * n)()
+    for k in range(n):
+        a = 2.0 * math.pi * k / n
+        p = (radius * math.cos(a), y, radius * math.sin(a))
+        d = [target[c] - p[c] for c in range(3)]
+        inv = 1.0 / math.sqrt(sum(v * v for v in d))
+        L = arr[k]
+        L.Strength[:] = (strength, strength, strength)
+        L.FalloffStart, L.FalloffEnd = falloff_start, falloff_end
+        L.Direction[:] = tuple(v * inv for v in d)
+        L.Position[:] = p
+        L.SpotPower = spot_power
+    return arr

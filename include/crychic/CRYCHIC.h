@@ -223,17 +223,55 @@ public:
         // Several GPUs, one frame: the peers' strips arrive in place behind this strip's lighting pass (RCCL over xGMI), so the
         // back buffer that Present sees is complete on every GPU.  The reference has one GPU (NodeMask 0, CRYCHIC.cpp:96,105).
         // With SetExchangeParts(n > 1) the lighting pass runs in n row ranges and each range travels while the next is lit.
-        if (mComm)
+        // Local lights (SetLocalLights; an extension the reference's shader leaves dead): point lights ride in the frame descriptor,
+        // spot lights take the _spots entries.
+        if (mPointLights) { f.point_lights_dev = static_cast<const crychic_light*>(mPointLights->Data()); f.numPointLights = mNumPointLights; }
+        const crychic_light* spots = mSpotLights ? static_cast<const crychic_light*>(mSpotLights->Data()) : nullptr;
+        if (mComm && spots)
+            CrychicThrowIfFailed(crychic_draw_hot_path_shared_spots(mComm, reinterpret_cast<const crychic_ssao_constants*>(&scb),
+                                                                    reinterpret_cast<const crychic_pass_constants*>(&pcb), &f,
+                                                                    mStripBounds.empty() ? nullptr : mStripBounds.data(), mExchangeParts,
+                                                                    spots, mNumSpotLights, mCommandList->Stream()));
+        else if (mComm)
             CrychicThrowIfFailed(crychic_draw_hot_path_shared(mComm, reinterpret_cast<const crychic_ssao_constants*>(&scb),
                                                               reinterpret_cast<const crychic_pass_constants*>(&pcb), &f,
                                                               mStripBounds.empty() ? nullptr : mStripBounds.data(), mExchangeParts,
                                                               mCommandList->Stream()));
+        else if (spots)
+            CrychicThrowIfFailed(crychic_draw_hot_path_spots(md3dDevice->Ctx(), reinterpret_cast<const crychic_ssao_constants*>(&scb),
+                                                             reinterpret_cast<const crychic_pass_constants*>(&pcb), &f, spots, mNumSpotLights,
+                                                             mCommandList->Stream()));
         else
             CrychicThrowIfFailed(crychic_draw_hot_path(md3dDevice->Ctx(), reinterpret_cast<const crychic_ssao_constants*>(&scb),
                                                        reinterpret_cast<const crychic_pass_constants*>(&pcb), &f, mCommandList->Stream()));
         // :300-305: advance the fence and signal it behind this frame's commands
         mCurrFrameResource->Fence = ++mCurrentFence;
         CrychicHipThrowIfFailed(hipEventRecord(mCurrFrameResource->FenceEvent, mCommandList->Stream()));
+    }
+
+    // ---- local lights (extension: the reference's point and spot branches, PBR.hlsl:109-147, are dead code) -------------------
+    // Uploads both lists to device buffers this object owns (at most 1024 each); Draw lights them after the directional lights,
+    // point lights first, on the single-GPU and the shared path alike (include/crychic_hip.h crychic_deferred_light_spots).
+    // nullptr / 0 for a list removes it; both empty = the reference configuration.  Waits for the frames in flight first, which
+    // may still read the previous buffers.
+    void SetLocalLights(const Light* points, uint32_t nPoints, const Light* spots, uint32_t nSpots)
+    {
+        static_assert(sizeof(Light) == sizeof(crychic_light), "Light is crychic_light");
+        if (nPoints > 1024u || nSpots > 1024u || (nPoints && !points) || (nSpots && !spots))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetLocalLights (at most 1024 lights per list, non-null when non-empty)",
+                                   __FILE__, __LINE__);
+        mCommandList->Flush();
+        auto upload = [&](const Light* src, uint32_t n, std::unique_ptr<ID3D12Resource>& dst, uint32_t& count) {
+            dst.reset();
+            count = 0;
+            if (n == 0) return;
+            dst = std::make_unique<ID3D12Resource>((size_t)n * sizeof(Light), ID3D12Resource::DEFAULT_HEAP);
+            dst->Upload(src, (size_t)n * sizeof(Light), mCommandList->Stream());
+            count = n;
+        };
+        upload(points, nPoints, mPointLights, mNumPointLights);
+        upload(spots, nSpots, mSpotLights, mNumSpotLights);
+        mCommandList->Flush();                  // the caller's arrays may go once this returns
     }
 
     // ---- one frame on several GPUs (no counterpart in the single-GPU reference) ----------------------------------
@@ -640,6 +678,8 @@ private:
     UINT mExchangeParts = 1;                  // SetExchangeParts
     bool mWholeFrame = true;
     std::unique_ptr<ID3D12Resource> mDepthStencilBuffer, mBackBuffer, mCubeMap;
+    std::unique_ptr<ID3D12Resource> mPointLights, mSpotLights;   // SetLocalLights
+    uint32_t mNumPointLights = 0, mNumSpotLights = 0;
     UINT mCubeMapSize = 0, mCubeMapLevels = 1;
     UINT mClientWidth, mClientHeight;
     float mLightRotationAngle = 0.0f;

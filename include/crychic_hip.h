@@ -226,6 +226,28 @@ int crychic_deferred_light_points(crychic_ctx* ctx, const crychic_pass_constants
                                   int numDirLights, float pcfSearchRadius, uint32_t flags,
                                   const crychic_light* point_lights_dev, uint32_t numPointLights, void* stream);
 
+/* crychic_deferred_light_points plus `numSpotLights` (<= 1024) spot lights read from a second device array of crychic_light
+ * (all six fields).  BUILD-DEFINED EXTENSION like the point lights: the reference's NUM_SPOT_LIGHTS branch (PBR.hlsl:126-147)
+ * is dead code; parity is against this repo's checker only.  Definition -- after the directional and the point lights, spot
+ * lights in ascending index order (the gLights order, Common.hlsl:102-105), each one:
+ *   l = Position - pos;  d = |l|;  d > FalloffEnd: no contribution;  l *= rcp(d);
+ *   att = saturate((FalloffEnd - d) / (FalloffEnd - FalloffStart));
+ *   att = att * pow(max(dot(-Direction, l), 0.001), SpotPower)     (one rounding; pow = exp2(clamp(y * log2 x, -125, 127)))
+ *   lightStrength = Strength * nDotl * att;  result = fma(brdf, lightStrength, result)   (shadow factor 1)
+ * with the point lights' BRDF (CRYCHIC_FIX_Q3 / Q4 included).  Direction is used as given (not normalised).  SpotPower = 0
+ * gives a factor of exactly 1, i.e. the bits of a point light at the same position.  The 0.001 floor means a spot light never
+ * contributes exactly zero outside its cone, so tiles cull spot lights by their range sphere alone, exactly as point lights.
+ * numSpotLights == 0 is crychic_deferred_light_points, bit for bit.  numSpotLights > 1024, or a NULL spot_lights_dev with
+ * numSpotLights > 0, returns CRYCHIC_E_INVALID_ARG. */
+int crychic_deferred_light_spots(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev,
+                                 const float* g1_dev, const float* g2_dev, const uint32_t* depth_dev,
+                                 const uint16_t* ambient_dev, const uint32_t* const shadow_dev[4], uint32_t shadowDim,
+                                 const uint8_t* cube_dev, uint32_t cubeDim, uint8_t* out_rgba8_dev,
+                                 float* radiance_out_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                                 int numDirLights, float pcfSearchRadius, uint32_t flags,
+                                 const crychic_light* point_lights_dev, uint32_t numPointLights,
+                                 const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream);
+
 /* ---- whole hot path of CRYCHIC::Draw (CRYCHIC.cpp:220-221 + 238-279) -------------------------------------- */
 typedef struct crychic_frame_desc {
     uint32_t W, H;
@@ -256,6 +278,11 @@ typedef struct crychic_frame_desc {
 
 int crychic_draw_hot_path(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB,
                           const crychic_pass_constants* passCB, const crychic_frame_desc* frame, void* stream);
+/* crychic_draw_hot_path with `numSpotLights` spot lights after the frame's point lights (crychic_deferred_light_spots' definition
+ * and limits); numSpotLights == 0 is crychic_draw_hot_path, bit for bit. */
+int crychic_draw_hot_path_spots(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
+                                const crychic_frame_desc* frame, const crychic_light* spot_lights_dev, uint32_t numSpotLights,
+                                void* stream);
 
 /* Per-kernel timing of the last crychic_draw_hot_path issued with profiling enabled (HIP events recorded
  * on the caller's stream around each pass).  Times are milliseconds; blocks until the events complete. */
@@ -465,6 +492,10 @@ int crychic_allgather_frame_all(crychic_comm* const* comms, int nranks, uint8_t*
 #define CRYCHIC_MAX_EXCHANGE_PARTS 8
 int crychic_draw_hot_path_shared(crychic_comm* comm, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
                                  const crychic_frame_desc* frame, const uint32_t* bounds, uint32_t nparts, void* stream);
+/* The same with spot lights (crychic_draw_hot_path_spots); numSpotLights == 0 is crychic_draw_hot_path_shared. */
+int crychic_draw_hot_path_shared_spots(crychic_comm* comm, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
+                                       const crychic_frame_desc* frame, const uint32_t* bounds, uint32_t nparts,
+                                       const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream);
 /* Stream-ordered rendezvous of all ranks (a one-word ncclAllReduce): brackets timed regions; no host wait inside. */
 int crychic_comm_barrier(crychic_comm* comm, void* stream);
 
