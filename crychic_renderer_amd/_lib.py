@@ -64,6 +64,11 @@ class Texture(C.Structure):
     _fields_ = [("rgba8_dev", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("mipLevels", C.c_uint32)]
 
 
+class SpotShadows(C.Structure):
+    """crychic_spot_shadows: the first `count` spot lights read maps[k] through ShadowTransforms[4 + k] (extension)."""
+    _fields_ = [("count", C.c_uint32), ("dim", C.c_uint32), ("maps", C.c_void_p * 8)]
+
+
 class PassTimes(C.Structure):
     _fields_ = [("ssao_ms", C.c_float), ("blur_ms", C.c_float), ("light_ms", C.c_float), ("total_ms", C.c_float)]
 
@@ -85,6 +90,7 @@ PROTOTYPES = {
     "crychic_build_offset_vectors": (None, [_P(_u32), _P(C.c_float * 4)]),
     "crychic_build_random_vector_texture": (None, [_P(_u32), _i, _vp]),
     "crychic_update_cascade_shadow_transform": (_i, [_P(Camera), _P(_f), _u32, _vp, _vp, _vp]),
+    "crychic_update_spot_shadow_transform": (_i, [_P(Light), _f, _f, _vp, _vp, _vp]),
     "crychic_update_main_pass_cb": (_i, [_P(Camera), _u32, _u32, _vp, _vp, _P(PassConstants)]),
     "crychic_update_ssao_cb": (_i, [_P(Camera), _u32, _u32, _vp, _P(SsaoConstants)]),
     "crychic_pcf_search_radius": (_f, [_u32, _i]),
@@ -102,6 +108,11 @@ PROTOTYPES = {
     "crychic_deferred_light_spots": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _P(_vp), _u32, _vp, _u32, _vp,
                                           _vp, _u32, _u32, _u32, _u32, _i, _f, _u32, _vp, _u32, _vp, _u32, _vp]),
     "crychic_draw_hot_path_spots": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _vp, _u32, _vp]),
+    "crychic_deferred_light_spots_shadowed": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _P(_vp), _u32, _vp, _u32, _vp,
+                                                   _vp, _u32, _u32, _u32, _u32, _i, _f, _u32, _vp, _u32, _vp, _u32, _P(SpotShadows),
+                                                   _vp]),
+    "crychic_draw_hot_path_spots_shadowed": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _vp, _u32,
+                                                  _P(SpotShadows), _vp]),
     "crychic_frustum_cull": (_i, [_P(Camera), _P(_f), _P(_f), _vp, _u32, _vp]),
     "crychic_ctx_set_profiling": (_i, [_vp, _i]),
     "crychic_ctx_last_pass_times": (_i, [_vp, _P(PassTimes)]),
@@ -120,6 +131,8 @@ PROTOTYPES = {
     "crychic_draw_hot_path_shared": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _P(_u32), _u32, _vp]),
     "crychic_draw_hot_path_shared_spots": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _P(_u32), _u32, _vp, _u32,
                                                 _vp]),
+    "crychic_draw_hot_path_shared_spots_shadowed": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _P(_u32), _u32,
+                                                         _vp, _u32, _P(SpotShadows), _vp]),
     "crychic_create_box": (_i, [_f, _f, _f, _u32, _vp, _u32, _vp, _u32, _P(_u32)]),
     "crychic_create_grid": (_i, [_f, _f, _u32, _u32, _vp, _u32, _vp, _u32, _P(_u32)]),
     "crychic_load_mesh_text": (_i, [C.c_char_p, _vp, _u32, _vp, _u32, _P(_u32), _P(_u32)]),

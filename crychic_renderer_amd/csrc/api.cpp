@@ -174,6 +174,28 @@ int check_spot_lights(const crychic_light* spots, uint32_t n)
     return 0;
 }
 
+// Shadowed spot lights (the _spots_shadowed entries): the descriptor's first `count` maps and ShadowTransforms[4 + k] into S.
+// A NULL descriptor or count 0 leaves S.count = 0: the _spots entry's kernels.
+int fill_spot_shadows(cry::SpotShadows& S, const crychic_spot_shadows* d, const crychic_pass_constants* cb, uint32_t numSpots)
+{
+    std::memset(&S, 0, sizeof S);
+    if (!d || d->count == 0) return 0;
+    if (d->count > CRYCHIC_MAX_SPOT_SHADOWS || d->count > numSpots)
+        return fail(CRYCHIC_E_INVALID_ARG, "spot shadows: count %u (max %u, and at most numSpotLights %u)", d->count,
+                    (unsigned)CRYCHIC_MAX_SPOT_SHADOWS, numSpots);
+    if (d->dim < 2 || d->dim > CRYCHIC_MAX_SPOT_SHADOW_DIM)          // 2 texels at least, as the cascades: a footprint row is one pair
+        return fail(CRYCHIC_E_INVALID_ARG, "spot shadows: dim %u (2 .. %u)", d->dim, (unsigned)CRYCHIC_MAX_SPOT_SHADOW_DIM);
+    for (uint32_t k = 0; k < d->count; ++k) {
+        if (!d->maps[k]) return fail(CRYCHIC_E_INVALID_ARG, "spot shadows: null map %u of %u", k, d->count);
+        S.maps[k] = d->maps[k];
+        std::memcpy(S.T[k], cb->ShadowTransforms[4 + k], sizeof S.T[k]);
+    }
+    S.count = d->count;
+    S.dim = d->dim;
+    S.dx = 1.0f / (float)d->dim;                       // IEEE division on the host: correctly rounded
+    return 0;
+}
+
 // With a mip chain the level of detail comes from 2 x 2 pixel quads: a call's rows have to be whole quad rows.
 int check_chain_rows(const cry::LightParams& P, uint32_t row0, uint32_t rows, uint32_t H)
 {
@@ -325,6 +347,20 @@ int crychic_deferred_light_spots(crychic_ctx* ctx, const crychic_pass_constants*
                                  const crychic_light* point_lights_dev, uint32_t numPointLights,
                                  const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream)
 {
+    return crychic_deferred_light_spots_shadowed(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev,
+                                                 cubeDim, out_rgba8_dev, radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius,
+                                                 flags, point_lights_dev, numPointLights, spot_lights_dev, numSpotLights, nullptr, stream);
+}
+
+int crychic_deferred_light_spots_shadowed(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev,
+                                          const float* g2_dev, const uint32_t* depth_dev, const uint16_t* ambient_dev,
+                                          const uint32_t* const shadow_dev[4], uint32_t shadowDim, const uint8_t* cube_dev,
+                                          uint32_t cubeDim, uint8_t* out_rgba8_dev, float* radiance_out_dev, uint32_t W, uint32_t H,
+                                          uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags,
+                                          const crychic_light* point_lights_dev, uint32_t numPointLights,
+                                          const crychic_light* spot_lights_dev, uint32_t numSpotLights,
+                                          const crychic_spot_shadows* spotShadows, void* stream)
+{
     if (int rc = bind(ctx)) return rc;
     if (int rc = check_dims(W, H)) return rc;
     if (!cb || !g0_dev || !g1_dev || !g2_dev || !depth_dev || !shadow_dev || !cube_dev || !out_rgba8_dev)
@@ -333,13 +369,15 @@ int crychic_deferred_light_spots(crychic_ctx* ctx, const crychic_pass_constants*
     if (numPointLights > cry::kMaxPointLights || (numPointLights && !point_lights_dev))
         return fail(CRYCHIC_E_INVALID_ARG, "numPointLights %u (max %u) / null light buffer", numPointLights, cry::kMaxPointLights);
     if (int rc = check_spot_lights(spot_lights_dev, numSpotLights)) return rc;
+    cry::SpotShadows S;
+    if (int rc = fill_spot_shadows(S, spotShadows, cb, numSpotLights)) return rc;
     cry::LightParams P;
     if (int rc = fill_light_params(P, cb, shadow_dev, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags)) return rc;
     P.pointLights = point_lights_dev;
     P.numPointLights = numPointLights;
     if (int rc = check_chain_rows(P, row0, rows, H)) return rc;
     CRY_HIP(cry::launch_light(P, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, cube_dev, out_rgba8_dev, radiance_out_dev,
-                              row0, rows, (hipStream_t)stream, spot_lights_dev, numSpotLights));
+                              row0, rows, (hipStream_t)stream, spot_lights_dev, numSpotLights, &S));
     return 0;
 }
 
@@ -350,7 +388,7 @@ int crychic_deferred_light_spots(crychic_ctx* ctx, const crychic_pass_constants*
 // part's exchange there (crychic_draw_hot_path_shared).  nparts == 1, after == nullptr is crychic_draw_hot_path itself.
 int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
                         const crychic_frame_desc* f, hipStream_t stream, uint32_t nparts, cry::PartHook after, void* user,
-                        const crychic_light* spots, uint32_t numSpots)
+                        const crychic_light* spots, uint32_t numSpots, const crychic_spot_shadows* spotShadows)
 {
     if (int rc = bind(ctx)) return rc;
     if (!ssaoCB || !passCB || !f) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
@@ -371,6 +409,8 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
     P.pointLights = f->point_lights_dev;
     P.numPointLights = f->numPointLights;
     if (int rc = check_spot_lights(spots, numSpots)) return rc;
+    cry::SpotShadows S;
+    if (int rc = fill_spot_shadows(S, spotShadows, passCB, numSpots)) return rc;
     const bool prof = ctx->profiling;
     if (prof) { ctx->times_valid = false; CRY_HIP(hipEventRecord(ctx->ev[0], stream)); }
     if (ssaoOn) {
@@ -392,7 +432,7 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
         const uint32_t r1 = (p + 1u == nparts) ? f->row0 + f->rows : r0 + 2u * per;
         if (r1 > r0)
             CRY_HIP(cry::launch_light(P, f->g0_dev, f->g1_dev, f->g2_dev, f->depth_dev, ssaoOn ? f->ambient0_dev : nullptr,
-                                      f->cube_dev, f->out_rgba8_dev, nullptr, r0, r1 - r0, stream, spots, numSpots));
+                                      f->cube_dev, f->out_rgba8_dev, nullptr, r0, r1 - r0, stream, spots, numSpots, &S));
         if (prof && p + 1u == nparts) { CRY_HIP(hipEventRecord(ctx->ev[3], stream)); ctx->times_valid = true; }
         if (after)
             if (int rc = after(user, p, r0, r1 - r0)) return rc;
@@ -412,6 +452,13 @@ int crychic_draw_hot_path_spots(crychic_ctx* ctx, const crychic_ssao_constants* 
                                 const crychic_frame_desc* f, const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream)
 {
     return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr, spot_lights_dev, numSpotLights);
+}
+
+int crychic_draw_hot_path_spots_shadowed(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
+                                         const crychic_frame_desc* f, const crychic_light* spot_lights_dev, uint32_t numSpotLights,
+                                         const crychic_spot_shadows* spotShadows, void* stream)
+{
+    return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr, spot_lights_dev, numSpotLights, spotShadows);
 }
 
 int crychic_ctx_set_profiling(crychic_ctx* ctx, int enabled)
@@ -501,7 +548,19 @@ int crychic_draw_scene_to_shadow_maps(crychic_ctx* ctx, const crychic_pass_const
                                       uint32_t nItems, uint32_t* const* shadow_dev, uint32_t shadowDim, int depthBias, float slopeScaledDepthBias,
                                       void* workspace_dev, size_t workspaceBytes, void* stream)
 {
-    if (!passCBs || !shadow_dev || nCascades < 1u || nCascades > 4u) return fail(CRYCHIC_E_INVALID_ARG, "1..4 cascades with their pass constants and targets");
+    if (!passCBs || !shadow_dev || nCascades < 1u || nCascades > 12u)
+        return fail(CRYCHIC_E_INVALID_ARG, "1..12 cascades with their pass constants and targets");
+    if (nCascades > 4u) {          // gShadowMap[4..11] (the shadowed spot lights): consecutive fused passes of at most four targets
+        for (uint32_t c = 0; c < nCascades; ++c)
+            if (!shadow_dev[c]) return fail(CRYCHIC_E_INVALID_ARG, "shadow target %u is null", c);
+        for (uint32_t c0 = 0; c0 < nCascades; c0 += 4u) {
+            const uint32_t n = nCascades - c0 < 4u ? nCascades - c0 : 4u;
+            if (int rc = crychic_draw_scene_to_shadow_maps(ctx, passCBs + c0, n, items, nItems, shadow_dev + c0, shadowDim, depthBias,
+                                                           slopeScaledDepthBias, workspace_dev, workspaceBytes, stream))
+                return rc;
+        }
+        return 0;
+    }
     if (nCascades == 1u)
         return crychic_draw_scene_to_shadow_map(ctx, passCBs, items, nItems, shadow_dev[0], shadowDim, depthBias, slopeScaledDepthBias, workspace_dev,
                                                 workspaceBytes, stream);

@@ -276,6 +276,25 @@ int crychic_update_cascade_shadow_transform(const crychic_camera* cam, const flo
     return 0;
 }
 
+int crychic_update_spot_shadow_transform(const crychic_light* L, float fovY, float zNear, float lightView[16], float lightProj[16],
+                                         float shadowTransform[16])
+{
+    if (!L || !lightView || !lightProj || !shadowTransform) return CRYCHIC_E_INVALID_ARG;
+    const V3 pos{ L->Position[0], L->Position[1], L->Position[2] };
+    const V3 dir{ L->Direction[0], L->Direction[1], L->Direction[2] };
+    const float len = std::sqrt(dot(dir, dir));
+    if (!(len > 0.0f) || !std::isfinite(len)) return CRYCHIC_E_INVALID_ARG;
+    if (!(fovY > 0.0f && fovY < 3.14159265358979f) || !(zNear > 0.0f) || !(zNear < L->FalloffEnd)) return CRYCHIC_E_INVALID_ARG;
+    // up = +y unless the light looks (nearly) straight up or down, where the look-at basis would degenerate
+    const V3 up = std::fabs(dir.y) > 0.999f * len ? V3{ 0.0f, 0.0f, 1.0f } : V3{ 0.0f, 1.0f, 0.0f };
+    const Mat4 view = look_at_lh(pos, V3{ pos.x + dir.x, pos.y + dir.y, pos.z + dir.z }, up);
+    const Mat4 proj = perspective_fov_lh(fovY, 1.0f, zNear, L->FalloffEnd);
+    (view * proj * tex_matrix()).store(shadowTransform);
+    view.store(lightView);
+    proj.store(lightProj);
+    return 0;
+}
+
 int crychic_update_main_pass_cb(const crychic_camera* cam, uint32_t W, uint32_t H, const float shadowTransform[4][16],
                                 const float lightDirs[3][3], crychic_pass_constants* out)
 {

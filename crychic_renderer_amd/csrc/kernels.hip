@@ -528,13 +528,15 @@ __global__ __launch_bounds__(256) void light_kernel(LightParams P, const f4a* __
 // SPOTS (light_spots_kernel): the spot lights of their own buffer are culled by the same sphere test in the same step into a
 // second mask, and walked after the point lights (the gLights order).  The cull stays spherical: a spot light contributes
 // outside its cone too (the 0.001 floor of PBR.hlsl:142), so only the range test is exact.
-template <bool ZERO_RADIUS, bool MIPS, bool SPOTS>
+// SHADOWED (light_spots_shadowed_kernel): spot lights k < shadows->count take their shadow factor (spot_shadow_factor), evaluated
+// only where the term is (in range).  The cull is unchanged: a shadow can only scale a term it already admits.
+template <bool ZERO_RADIUS, bool MIPS, bool SPOTS, bool SHADOWED = false>
 __device__ __forceinline__ void light_local_tile(const LightParams& P, const f4a* __restrict__ g0, const f4a* __restrict__ g1,
                                                  const f4a* __restrict__ g2, const uint32_t* __restrict__ depth,
                                                  const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
                                                  uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0, uint32_t row1,
                                                  float (*s_box)[6], uint32_t* s_mask, const crychic_light* __restrict__ spots,
-                                                 uint32_t numSpots, uint32_t* s_spotMask)
+                                                 uint32_t numSpots, uint32_t* s_spotMask, const SpotShadows* shadows = nullptr)
 {
     uint32_t bx, by;
     tile_origin<0>(bx, by);
@@ -622,7 +624,11 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const f4a
                     while (m) {
                         const uint32_t b = (uint32_t)__builtin_ctz(m);
                         m &= m - 1u;
-                        pbr_spot_light(spots[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
+                        if (SHADOWED)
+                            pbr_spot_light(spots[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4,
+                                           SpotShadowOf{ shadows, pos, w * 32u + b });
+                        else
+                            pbr_spot_light(spots[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
                     }
                 }
             }
@@ -663,6 +669,23 @@ __global__ __launch_bounds__(256) void light_spots_kernel(LightParams P, const f
     __shared__ uint32_t s_mask[kMaxPointLights / 32];
     __shared__ uint32_t s_spotMask[kMaxSpotLights / 32];
     light_local_tile<ZERO_RADIUS, MIPS, true>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask, spots, numSpots, s_spotMask);
+}
+
+// The same pass with the first shadows.count (1 .. 8) spot lights shadowed (crychic_deferred_light_spots_shadowed); a count of 0
+// takes light_spots_kernel, so none of the instantiations above changes.
+template <bool ZERO_RADIUS, bool MIPS>
+__global__ __launch_bounds__(256) void light_spots_shadowed_kernel(LightParams P, const f4a* __restrict__ g0, const f4a* __restrict__ g1,
+                                                                   const f4a* __restrict__ g2, const uint32_t* __restrict__ depth,
+                                                                   const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
+                                                                   uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0,
+                                                                   uint32_t row1, const crychic_light* __restrict__ spots, uint32_t numSpots,
+                                                                   SpotShadows shadows)
+{
+    __shared__ float s_box[4][6];
+    __shared__ uint32_t s_mask[kMaxPointLights / 32];
+    __shared__ uint32_t s_spotMask[kMaxSpotLights / 32];
+    light_local_tile<ZERO_RADIUS, MIPS, true, true>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask, spots,
+                                                    numSpots, s_spotMask, &shadows);
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------
@@ -818,12 +841,20 @@ hipError_t launch_blur_replay_chain(const crychic_ssao_constants& cb, const void
 hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, const float* g2,
                         const uint32_t* depth, const uint16_t* ambient, const uint8_t* cube, uint8_t* out,
                         float* radiance, uint32_t row0, uint32_t rows, hipStream_t stream, const crychic_light* spots,
-                        uint32_t numSpots)
+                        uint32_t numSpots, const SpotShadows* shadows)
 {
     if (rows == 0) return hipSuccess;
     const dim3 grid = grid_for(P.W, rows);
     const bool mips = P.cubeLevels > 1u;          // the chain: quads inside wavefronts (light_tile_pixel), so the rows must start a quad
     if (mips && (row0 & 1u)) return hipErrorInvalidValue;
+    if (numSpots && shadows && shadows->count) {
+#define CRY_LAUNCH_SHADOWED(K) hipLaunchKernelGGL(K, grid, dim3(256), 0, stream, P, (const f4a*)g0, (const f4a*)g1, (const f4a*)g2, depth, ambient, \
+                                                  (const uint32_t*)cube, (uint32_t*)out, (f4a*)radiance, row0, row0 + rows, spots, numSpots, *shadows)
+        if (P.pcfSearchRadius == 0.0f) { if (mips) CRY_LAUNCH_SHADOWED((light_spots_shadowed_kernel<true, true>)); else CRY_LAUNCH_SHADOWED((light_spots_shadowed_kernel<true, false>)); }
+        else { if (mips) CRY_LAUNCH_SHADOWED((light_spots_shadowed_kernel<false, true>)); else CRY_LAUNCH_SHADOWED((light_spots_shadowed_kernel<false, false>)); }
+#undef CRY_LAUNCH_SHADOWED
+        return hipGetLastError();
+    }
     if (numSpots) {
 #define CRY_LAUNCH_SPOTS(K) hipLaunchKernelGGL(K, grid, dim3(256), 0, stream, P, (const f4a*)g0, (const f4a*)g1, (const f4a*)g2, depth, ambient, \
                                                (const uint32_t*)cube, (uint32_t*)out, (f4a*)radiance, row0, row0 + rows, spots, numSpots)

@@ -330,19 +330,60 @@ CRY_HD void pbr_point_light(const crychic_light& L, f3 pos, f3 albedo, float rou
 // Spot light, BUILD-DEFINED EXTENSION (crychic_hip.h crychic_deferred_light_spots): the reference's branch (PBR.hlsl:126-147) is
 // dead code as well; enabled like the point light with att *= pow(max(dot(-Direction, l), 0.001), SpotPower) -- det_pow, the
 // general pow, Direction used as given.  SpotPower = 0 makes the factor exactly 1: the point light's bits.
+// `shadow()` is the light's shadow factor, called only when the light is in range (crychic_deferred_light_spots_shadowed);
+// the unshadowed light passes UnitShadow, whose 1.0f gives the pinned `1.0f * brdf` exactly.
+struct UnitShadow { CRY_HD float operator()() const { return 1.0f; } };
+template <typename SHADOW = UnitShadow>
 CRY_HD void pbr_spot_light(const crychic_light& L, f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view,
-                           f3& result, bool fixQ3 = false, bool fixQ4 = false)
+                           f3& result, bool fixQ3 = false, bool fixQ4 = false, SHADOW shadow = SHADOW())
 {
     const f3 l{ L.Position[0] - pos.x, L.Position[1] - pos.y, L.Position[2] - pos.z };
     const float d = len_from_sq(dot3(l, l));
     if (d > L.FalloffEnd) return;
+    const float s = shadow();                                                                       // :145 shadowFactor[i]
     const float rd = rcp(d);
     const f3 ln{ l.x * rd, l.y * rd, l.z * rd };
     float att = saturate(divf(L.FalloffEnd - d, L.FalloffEnd - L.FalloffStart));
     const f3 spotDir{ -L.Direction[0], -L.Direction[1], -L.Direction[2] };                          // PBR.hlsl:128
     att = att * det_pow(maxnn(dot3(spotDir, ln), 0.001f), L.SpotPower);                              // :142
-    pbr_light<true>(ln, L.Strength, att, albedo, roughness, metalness, normal, view, 1.0f, result, fixQ3, fixQ4);
+    pbr_light<true>(ln, L.Strength, att, albedo, roughness, metalness, normal, view, s, result, fixQ3, fixQ4);
 }
+
+// Shadowed spot lights, BUILD-DEFINED EXTENSION (crychic_hip.h crychic_deferred_light_spots_shadowed): spot light k < count
+// reads map k with the transform the reference reserves as gShadowTransforms[4 + k] (Common.hlsl:46,91).
+constexpr uint32_t kMaxSpotShadows = 8;     // CRYCHIC_MAX_SPOT_SHADOWS: reference slots 4..11
+struct SpotShadows {
+    const uint32_t* maps[kMaxSpotShadows];
+    float T[kMaxSpotShadows][16];           // passCB->ShadowTransforms[4 + k], transposed like the cascades'
+    uint32_t count, dim;
+    float dx;                               // 1.0f / (float)dim, correctly rounded (on the host)
+};
+// CalcShadowFactor (Common.hlsl:135-165) with its gShadowMap[0] generalised to the light's own map: the perspective divide of
+// pcf_poisson (no w == 1 shortcut: the transform is perspective), then nine gsamShadow taps one texel apart in the order of
+// offsets[9] (:150-155, y outer, x inner), each coordinate one float add, summed from 0 and divided by 9 (IEEE quotient).
+CRY_HD float spot_shadow_factor(const uint32_t* __restrict__ map, uint32_t dim, float dx, const float* T, f3 pos)
+{
+    const float spx = mulcol1(pos.x, pos.y, pos.z, T), spy = mulcol1(pos.x, pos.y, pos.z, T + 4);
+    const float spz = mulcol1(pos.x, pos.y, pos.z, T + 8), spw = mulcol1(pos.x, pos.y, pos.z, T + 12);
+    const float rw = rcp(spw);
+    const float x = spx * rw, y = spy * rw, depth = spz * rw;
+    float percentLit = 0.0f;
+#pragma unroll
+    for (int j = -1; j <= 1; ++j) {
+        const float oy = j < 0 ? -dx : (j > 0 ? dx : 0.0f);
+#pragma unroll
+        for (int i = -1; i <= 1; ++i) {
+            const float ox = i < 0 ? -dx : (i > 0 ? dx : 0.0f);
+            percentLit += shadow_cmp_linear(map, dim, x + ox, y + oy, depth);
+        }
+    }
+    return percentLit / 9.0f;
+}
+// The shadow of spot light k when k < count, else factor 1 (the light is unshadowed).
+struct SpotShadowOf {
+    const SpotShadows* S; f3 pos; uint32_t k;
+    CRY_HD float operator()() const { return k < S->count ? spot_shadow_factor(S->maps[k], S->dim, S->dx, S->T[k], pos) : 1.0f; }
+};
 
 // TextureCube.Sample(gsamLinearWrap, r): D3D major-axis face selection (ties x >= y >= z), bilinear inside the
 // face with clamp-to-edge.  Faces +X,-X,+Y,-Y,+Z,-Z, RGBA8.
@@ -728,6 +769,18 @@ struct AllLocalLights {
     {
         for (uint32_t i = 0; i < nPoints; ++i) pbr_point_light(points[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
         for (uint32_t i = 0; i < nSpots; ++i) pbr_spot_light(spots[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
+    }
+};
+// AllLocalLights with the first shadows->count spot lights shadowed: the host build's iteration of the shadowed kernel.
+struct AllLocalLightsShadowed {
+    const crychic_light* points; uint32_t nPoints;
+    const crychic_light* spots; uint32_t nSpots;
+    const SpotShadows* shadows;
+    CRY_HD void operator()(f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view, f3& result, bool fixQ3, bool fixQ4) const
+    {
+        for (uint32_t i = 0; i < nPoints; ++i) pbr_point_light(points[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
+        for (uint32_t i = 0; i < nSpots; ++i)
+            pbr_spot_light(spots[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4, SpotShadowOf{ shadows, pos, i });
     }
 };
 

@@ -6,11 +6,12 @@ tensors that own HBM (PyTorch is used for device memory and streams only -- ever
 libcrychic_hip.so).
 """
 import ctypes as C
+import math
 
 import torch
 
 from . import _lib
-from ._lib import DrawItem, FrameDesc, PassConstants, PassTimes, SsaoConstants, Texture, check, lib
+from ._lib import CrychicError, DrawItem, FrameDesc, Light, PassConstants, PassTimes, SpotShadows, SsaoConstants, Texture, check, lib
 
 
 def _ptr(t):
@@ -168,6 +169,9 @@ class Crychic:
         self.flags = 0
         self.mPointLights = None     # extension: torch uint8 tensor holding an array of Light structs (48 B each)
         self.mSpotLights = None      # extension: the same for the spot lights (crychic_draw_hot_path_spots)
+        self.mSpotShadowMaps = None  # extension: (count, dim, dim) int32 D24 maps of the first spot lights (set_spot_shadows)
+        self._spotHost = None        # host copy of the spot lights (the shadow transforms are built from it)
+        self._spotShadow = None      # (SpotShadows descriptor, [transposed transform], [shadow pass constants], geometry)
         self._desc = None
 
     def load_scene(self, planes):
@@ -228,6 +232,21 @@ class Crychic:
             if len(self._desc) > 16:
                 self._desc.clear()
             f = self._desc[key] = self.frame_desc(row0, rows)
+        if self.mSpotLights is not None and self._spotShadow is not None:     # extension: the _spots_shadowed entries
+            spots, n = _ptr(self.mSpotLights), self.mSpotLights.numel() // 48
+            desc, T, cbs, geo = self._spotShadow
+            pcb = PassConstants.from_buffer_copy(self.mMainPassCB)          # mMainPassCB with the spot transforms in slots 4..11
+            for k, t in enumerate(T):
+                pcb.ShadowTransforms[4 + k][:] = t
+            if geo is not None:
+                self.DrawSpotShadowMaps()
+            if shared is not None:
+                check(lib.crychic_draw_hot_path_shared_spots_shadowed(shared[0], C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), shared[1],
+                                                                      int(shared[2]), spots, n, C.byref(desc), _stream(self.ctx.device)))
+                return
+            check(lib.crychic_draw_hot_path_spots_shadowed(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), spots, n, C.byref(desc),
+                                                           _stream(self.ctx.device)))
+            return
         if self.mSpotLights is not None:       # extension: the _spots entries, for the whole frame, a strip or the shared path
             spots, n = _ptr(self.mSpotLights), self.mSpotLights.numel() // 48
             if shared is not None:
@@ -265,14 +284,61 @@ class Crychic:
 
     def set_spot_lights(self, lights):
         """Extension: `lights` is a ctypes array of Light (or None); copied to the device.  Spot lights are lit after the point
-        lights (include/crychic_hip.h crychic_deferred_light_spots); None or an empty array = none."""
+        lights (include/crychic_hip.h crychic_deferred_light_spots); None or an empty array = none.  Shadows set with
+        set_spot_shadows are dropped (their transforms belong to the previous lights)."""
         if lights is None or len(lights) == 0:
             self.mSpotLights = None
+            self._spotHost = None
         else:
             import numpy as np
             host = np.frombuffer(bytes(lights), dtype=np.uint8).copy()
             self.mSpotLights = torch.from_numpy(host).to(self.ctx.device)
+            self._spotHost = (Light * len(lights)).from_buffer_copy(bytes(lights))
+        self.mSpotShadowMaps = None
+        self._spotShadow = None
         self._desc = None
+
+    def set_spot_shadows(self, count, dim=1024, fov_y=math.pi / 2, z_near=0.5, geometry=None):
+        """Extension: the first `count` (<= 8) spot lights cast shadows (include/crychic_hip.h crychic_deferred_light_spots_shadowed).
+        Allocates `count` dim x dim D24 maps, builds each light's transform (crychic_update_spot_shadow_transform: perspective, fov_y,
+        z_near .. FalloffEnd) and from then on writes it into ShadowTransforms[4 + k] and routes every Draw through the _shadowed
+        entries (mMainPassCB itself is not modified).  geometry (a SceneGeometry of the shadow casters): Draw renders the maps first,
+        in one DrawSceneToShadowMaps call, after whatever the caller drew for the cascades; without it the caller fills mSpotShadowMaps
+        (DrawSpotShadowMaps renders them on demand).  count 0 removes the shadows."""
+        if count == 0:
+            self.mSpotShadowMaps, self._spotShadow = None, None
+            return
+        n = 0 if self._spotHost is None else len(self._spotHost)
+        if not 0 < count <= 8 or count > n:
+            raise CrychicError(-1, "set_spot_shadows: count %d (1 .. 8, at most the %d spot lights)" % (count, n))
+        if not 2 <= dim <= 16384:
+            raise CrychicError(-1, "set_spot_shadows: dim %d (2 .. 16384)" % dim)
+        import numpy as np
+        T, cbs = [], []
+        for k in range(count):
+            lv, lp, st = ((C.c_float * 16)() for _ in range(3))
+            check(lib.crychic_update_spot_shadow_transform(C.byref(self._spotHost[k]), float(fov_y), float(z_near), lv, lp, st))
+            T.append(list(np.asarray(st[:], np.float32).reshape(4, 4).T.reshape(-1)))
+            cb = PassConstants()
+            vp = np.asarray(lv[:], np.float32).reshape(4, 4) @ np.asarray(lp[:], np.float32).reshape(4, 4)
+            cb.ViewProj[:] = list(vp.astype(np.float32).T.reshape(-1))
+            cbs.append(cb)
+        self.mSpotShadowMaps = torch.full((count, dim, dim), 0xFFFFFF, dtype=torch.int32, device=self.ctx.device)
+        desc = SpotShadows()
+        desc.count, desc.dim = count, dim
+        for k in range(count):
+            desc.maps[k] = self.mSpotShadowMaps[k].data_ptr()
+        self._spotShadow = (desc, T, cbs, geometry)
+
+    def spot_shadow_pass_constants(self):
+        """The shadow pass constants (ViewProj = lightView * lightProj) of the shadowed spot lights, in map order."""
+        return [] if self._spotShadow is None else list(self._spotShadow[2])
+
+    def DrawSpotShadowMaps(self, geometry=None):
+        """Renders every spot shadow map in one crychic_draw_scene_to_shadow_maps pass (the cascades' rasteriser and bias)."""
+        desc, T, cbs, geo = self._spotShadow
+        geo = geometry if geometry is not None else geo
+        geo.DrawSceneToShadowMaps(cbs, [self.mSpotShadowMaps[k] for k in range(len(cbs))])
 
     def set_profiling(self, enabled):
         check(lib.crychic_ctx_set_profiling(self.ctx.handle, 1 if enabled else 0))

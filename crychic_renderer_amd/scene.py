@@ -319,3 +319,30 @@ def spot_light_ring(n=32, radius=14.0, y=8.0, target=(0.0, 0.0, 0.0), falloff_st
         L.Position[:] = p
         L.SpotPower = spot_power
     return arr
+
+
+# boxes of the reference scene near the default camera (instance centres, _box_centres), in the order shadow_spot_lights aims at them
+_SHADOW_TARGETS = [(0.0, 0.8, -5.0), (5.0, 0.8, -5.0), (-5.0, 0.8, -5.0), (0.0, 0.8, 0.0), (5.0, 0.8, 0.0), (-5.0, 0.8, 0.0),
+                   (0.0, 0.8, 5.0), (5.0, 0.8, 5.0)]
+
+
+def shadow_spot_lights(n=1, offset=(-4.0, 6.0, -4.0), falloff_start=2.0, falloff_end=20.0, strength=3.0, spot_power=4.0):
+    """Extension: n (<= 8) spot lights, light k placed at `offset` from a box of the reference scene in front of the default camera
+    and aimed at that box's centre (Direction normalised here), so that the box's shadow falls on the grid behind it once the
+    light is shadowed (Crychic.set_spot_shadows).  Returns a ctypes array of Light."""
+    import math
+    from ._lib import Light
+    if not 0 < n <= len(_SHADOW_TARGETS):
+        raise ValueError("shadow_spot_lights: n %d (1 .. %d)" % (n, len(_SHADOW_TARGETS)))
+    arr = (Light * n)()
+    for k in range(n):
+        t = _SHADOW_TARGETS[k]
+        p = [t[c] + offset[c] for c in range(3)]
+        inv = 1.0 / math.sqrt(sum(v * v for v in offset))
+        L = arr[k]
+        L.Strength[:] = (strength, strength, strength)
+        L.FalloffStart, L.FalloffEnd = falloff_start, falloff_end
+        L.Direction[:] = tuple(-v * inv for v in offset)
+        L.Position[:] = p
+        L.SpotPower = spot_power
+    return arr

@@ -184,6 +184,7 @@ public:
         UpdateInstanceData(gt);                                                                     // :164
         UpdateMaterialBuffer(gt);                                                                   // :165
         UpdateCascadeShadowTransform(gt);
+        UpdateSpotShadowTransforms();
         UpdateMainPassCB(gt);
         UpdateShadowPassCB(gt);
         UpdateSsaoCB(gt);
@@ -227,7 +228,21 @@ public:
         // spot lights take the _spots entries.
         if (mPointLights) { f.point_lights_dev = static_cast<const crychic_light*>(mPointLights->Data()); f.numPointLights = mNumPointLights; }
         const crychic_light* spots = mSpotLights ? static_cast<const crychic_light*>(mSpotLights->Data()) : nullptr;
-        if (mComm && spots)
+        // Shadowed spot lights (SetSpotShadows): the first mSpotShadowCount spot lights read their maps through ShadowTransforms[4 + k]
+        crychic_spot_shadows sh = {};
+        sh.count = spots ? mSpotShadowCount : 0u;
+        sh.dim = mSpotShadowDim;
+        for (uint32_t k = 0; k < sh.count; ++k) sh.maps[k] = static_cast<const uint32_t*>(mSpotShadowMaps[k]->Data());
+        if (mComm && spots && sh.count)
+            CrychicThrowIfFailed(crychic_draw_hot_path_shared_spots_shadowed(mComm, reinterpret_cast<const crychic_ssao_constants*>(&scb),
+                                                                             reinterpret_cast<const crychic_pass_constants*>(&pcb), &f,
+                                                                             mStripBounds.empty() ? nullptr : mStripBounds.data(), mExchangeParts,
+                                                                             spots, mNumSpotLights, &sh, mCommandList->Stream()));
+        else if (spots && sh.count)
+            CrychicThrowIfFailed(crychic_draw_hot_path_spots_shadowed(md3dDevice->Ctx(), reinterpret_cast<const crychic_ssao_constants*>(&scb),
+                                                                      reinterpret_cast<const crychic_pass_constants*>(&pcb), &f, spots,
+                                                                      mNumSpotLights, &sh, mCommandList->Stream()));
+        else if (mComm && spots)
             CrychicThrowIfFailed(crychic_draw_hot_path_shared_spots(mComm, reinterpret_cast<const crychic_ssao_constants*>(&scb),
                                                                     reinterpret_cast<const crychic_pass_constants*>(&pcb), &f,
                                                                     mStripBounds.empty() ? nullptr : mStripBounds.data(), mExchangeParts,
@@ -271,8 +286,38 @@ public:
         };
         upload(points, nPoints, mPointLights, mNumPointLights);
         upload(spots, nSpots, mSpotLights, mNumSpotLights);
+        mSpotHost.assign(spots, spots + nSpots);    // the shadow transforms are built from these
+        if (mSpotShadowCount > nSpots) SetSpotShadows(0, 0, 0.0f, 0.0f);
         mCommandList->Flush();                  // the caller's arrays may go once this returns
     }
+
+    // ---- shadowed spot lights (extension: the reference reserves gShadowMap[4..11] / gShadowTransforms[4..11] and leaves them
+    // empty, Common.hlsl:46,91) -----------------------------------------------------------------------------------------------
+    // The first `count` (<= 8, at most the spot lights of SetLocalLights) spot lights cast shadows: each gets a dim x dim D24 map that
+    // DrawSceneToShadowMap renders after the four cascades (perspective, fovY, zNear .. FalloffEnd; crychic_update_spot_shadow_transform)
+    // and ShadowTransforms[4 + k]; Draw takes the _spots_shadowed entries (include/crychic_hip.h crychic_deferred_light_spots_shadowed).
+    // count 0 removes the shadows.  Waits for the frames in flight first, which may still read the previous maps.
+    void SetSpotShadows(uint32_t count, uint32_t dim, float fovY, float zNear)
+    {
+        mCommandList->Flush();
+        mSpotShadowMaps.clear();
+        mSpotShadowCount = 0;
+        if (count == 0) return;
+        if (count > CRYCHIC_MAX_SPOT_SHADOWS || count > mNumSpotLights || dim < 2 || dim > CRYCHIC_MAX_SPOT_SHADOW_DIM)
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetSpotShadows (count 1 .. 8 and at most the spot lights, dim 2 .. 16384)",
+                                   __FILE__, __LINE__);
+        float v[16], p[16], t[16];
+        for (uint32_t k = 0; k < count; ++k)       // fovY / zNear against every light's range, before anything changes
+            CrychicThrowIfFailed(crychic_update_spot_shadow_transform(reinterpret_cast<const crychic_light*>(&mSpotHost[k]), fovY, zNear, v, p, t));
+        for (uint32_t k = 0; k < count; ++k)
+            mSpotShadowMaps.push_back(std::make_unique<ID3D12Resource>((size_t)dim * dim * 4u, ID3D12Resource::DEFAULT_HEAP));
+        mSpotShadowCount = count;
+        mSpotShadowDim = dim;
+        mSpotShadowFovY = fovY;
+        mSpotShadowZNear = zNear;
+        UpdateSpotShadowTransforms();
+    }
+    ID3D12Resource* SpotShadowMap(uint32_t k) { return k < mSpotShadowCount ? mSpotShadowMaps[k].get() : nullptr; }
 
     // ---- one frame on several GPUs (no counterpart in the single-GPU reference) ----------------------------------
     // Rows [row0, row0 + rows) are this GPU's share of the hot path (row0 even).  An empty share is refused: a rank without rows
@@ -585,6 +630,22 @@ private:
         }
         CrychicThrowIfFailed(crychic_draw_scene_to_shadow_maps(md3dDevice->Ctx(), cbs, 4, items.data(), (uint32_t)items.size(), targets,
                                                                mShadowMap->Width(), 10000, 2.0f, ws, bytes, mCommandList->Stream()));  // bias: :1601-1603
+        if (mSpotShadowCount == 0) return;
+        // the shadowed spot lights' maps (slots 4..11): one more pass of the same rasteriser, ViewProj = lightView * lightProj
+        crychic_pass_constants scbs[CRYCHIC_MAX_SPOT_SHADOWS];
+        uint32_t* stargets[CRYCHIC_MAX_SPOT_SHADOWS];
+        for (uint32_t k = 0; k < mSpotShadowCount; ++k) {
+            std::memset(&scbs[k], 0, sizeof scbs[k]);
+            for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) {
+                float acc = 0.0f;
+                for (int q = 0; q < 4; ++q) acc += mLightViews[4 + k].m[r][q] * mLightProjs[4 + k].m[q][c];
+                scbs[k].ViewProj[4 * c + r] = acc;                                                  // stored transposed
+            }
+            stargets[k] = static_cast<uint32_t*>(mSpotShadowMaps[k]->Data());
+        }
+        void* sws = RasterWorkspace((uint64_t)mSpotShadowCount * mSceneTriangles, mSpotShadowDim, mSpotShadowDim, &bytes);
+        CrychicThrowIfFailed(crychic_draw_scene_to_shadow_maps(md3dDevice->Ctx(), scbs, mSpotShadowCount, items.data(), (uint32_t)items.size(),
+                                                               stargets, mSpotShadowDim, 10000, 2.0f, sws, bytes, mCommandList->Stream()));
     }
     void DrawNormalsAndDepth()  // CRYCHIC.cpp:2512-2543
     {
@@ -635,6 +696,15 @@ private:
             std::memcpy(&mLightViews[i], lv[i], 64); std::memcpy(&mLightProjs[i], lp[i], 64); std::memcpy(&mShadowTransforms[i], st[i], 64);
         }
     }
+    void UpdateSpotShadowTransforms()  // SetSpotShadows: the light, projection and shadow transform of slots 4 .. 4 + count - 1
+    {
+        for (uint32_t k = 0; k < mSpotShadowCount; ++k) {
+            float v[16], p[16], t[16];
+            CrychicThrowIfFailed(crychic_update_spot_shadow_transform(reinterpret_cast<const crychic_light*>(&mSpotHost[k]), mSpotShadowFovY,
+                                                                      mSpotShadowZNear, v, p, t));
+            std::memcpy(&mLightViews[4 + k], v, 64); std::memcpy(&mLightProjs[4 + k], p, 64); std::memcpy(&mShadowTransforms[4 + k], t, 64);
+        }
+    }
     void UpdateMainPassCB(const GameTimer& gt)  // CRYCHIC.cpp:817-868
     {
         float st[4][16], dirs[3][3];
@@ -642,6 +712,8 @@ private:
         for (int i = 0; i < 3; ++i) { dirs[i][0] = mRotatedLightDirections[i].x; dirs[i][1] = mRotatedLightDirections[i].y; dirs[i][2] = mRotatedLightDirections[i].z; }
         CrychicThrowIfFailed(crychic_update_main_pass_cb(&mCamera.Raw(), mClientWidth, mClientHeight, st, dirs,
                                                          reinterpret_cast<crychic_pass_constants*>(&mMainPassCB)));
+        for (uint32_t k = 0; k < mSpotShadowCount; ++k)                                             // slots 4..11, transposed like :826-830
+            for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) mMainPassCB.ShadowTransforms[4 + k].m[c][r] = mShadowTransforms[4 + k].m[r][c];
         mMainPassCB.TotalTime = gt.TotalTime();
         mMainPassCB.DeltaTime = gt.DeltaTime();
         mCurrFrameResource->PassCB->CopyData(0, mMainPassCB);                                       // :866-867
@@ -680,6 +752,10 @@ private:
     std::unique_ptr<ID3D12Resource> mDepthStencilBuffer, mBackBuffer, mCubeMap;
     std::unique_ptr<ID3D12Resource> mPointLights, mSpotLights;   // SetLocalLights
     uint32_t mNumPointLights = 0, mNumSpotLights = 0;
+    std::vector<Light> mSpotHost;                                         // SetLocalLights' spot list, for the shadow transforms
+    std::vector<std::unique_ptr<ID3D12Resource>> mSpotShadowMaps;         // SetSpotShadows
+    uint32_t mSpotShadowCount = 0, mSpotShadowDim = 0;
+    float mSpotShadowFovY = 0.0f, mSpotShadowZNear = 0.0f;
     UINT mCubeMapSize = 0, mCubeMapLevels = 1;
     UINT mClientWidth, mClientHeight;
     float mLightRotationAngle = 0.0f;

@@ -248,6 +248,59 @@ int crychic_deferred_light_spots(crychic_ctx* ctx, const crychic_pass_constants*
                                  const crychic_light* point_lights_dev, uint32_t numPointLights,
                                  const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream);
 
+/* ---- shadowed spot lights (BUILD-DEFINED EXTENSION; parity against this repo's checker, tests/spot_shadow_ref) ---------- *
+ * The reference declares gShadowMap[12] / gShadowTransforms[12] (Common.hlsl:46,91), of which the cascades use slots 0..3, and
+ * leaves the spot branch's `result += shadowFactor[i] * brdf * lightStrength` commented out (PBR.hlsl:145).  Here the first
+ * `count` (<= CRYCHIC_MAX_SPOT_SHADOWS) spot lights fill slots 4..11: spot light k < count reads
+ *   maps[k]: D24 in the low 24 bits of a uint32, square, side `dim` (the cascades' format), sampled with gsamShadow
+ *            (LESS_EQUAL, border 0);
+ *   passCB->ShadowTransforms[4 + k]: stored transposed like the cascade transforms (crychic_update_spot_shadow_transform).
+ * Spot lights k >= count keep shadow factor 1.  Shadow factor s -- CalcShadowFactor (Common.hlsl:135-165) with its hard-wired
+ * gShadowMap[0] generalised to the light's own map:
+ *   sp = mul(float4(posW, 1), T);  rw = rcp(sp.w);  x = sp.x * rw;  y = sp.y * rw;  depth = sp.z * rw   (as the cascades' PCF)
+ *   dx = 1.0f / (float)dim   (correctly rounded)
+ *   nine taps in the order of offsets[9] (:150-155: y outer, x inner, offsets -dx, 0, +dx), each
+ *       gsamShadow.SampleCmpLevelZero(map, float2(x + ox, y + oy), depth)   (each coordinate one float add, not an fma)
+ *   summed in that order from 0.0f;  s = percentLit / 9.0f   (correctly rounded)
+ * Non-finite coordinates address only border texels and give 0; positions behind the light (sp.w <= 0) are taken literally
+ * (no w == 1 shortcut: the transforms are perspective).  The spot term becomes result = fma(s * brdf, lightStrength, result):
+ * s == 1 gives the unshadowed bits, s == 0 leaves result unchanged for finite inputs.  s is evaluated only where the spot term
+ * is (d <= FalloffEnd); the tile cull stays spherical.
+ * A NULL descriptor or count == 0 is the matching _spots entry, bit for bit.  With count > 0: count > 8, count > numSpotLights,
+ * a NULL map among the first count, dim < 2 or dim > CRYCHIC_MAX_SPOT_SHADOW_DIM return CRYCHIC_E_INVALID_ARG (with a message)
+ * before anything is enqueued.  The maps are rendered by crychic_draw_scene_to_shadow_maps with passCBs[k].ViewProj = V * P of
+ * crychic_update_spot_shadow_transform. */
+#define CRYCHIC_MAX_SPOT_SHADOWS 8
+#define CRYCHIC_MAX_SPOT_SHADOW_DIM 16384
+typedef struct crychic_spot_shadows {
+    uint32_t count;
+    uint32_t dim;
+    const uint32_t* maps[CRYCHIC_MAX_SPOT_SHADOWS];
+} crychic_spot_shadows;
+
+/* crychic_deferred_light_spots with the first spotShadows->count spot lights shadowed (definition above). */
+int crychic_deferred_light_spots_shadowed(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev,
+                                          const float* g1_dev, const float* g2_dev, const uint32_t* depth_dev,
+                                          const uint16_t* ambient_dev, const uint32_t* const shadow_dev[4], uint32_t shadowDim,
+                                          const uint8_t* cube_dev, uint32_t cubeDim, uint8_t* out_rgba8_dev,
+                                          float* radiance_out_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                                          int numDirLights, float pcfSearchRadius, uint32_t flags,
+                                          const crychic_light* point_lights_dev, uint32_t numPointLights,
+                                          const crychic_light* spot_lights_dev, uint32_t numSpotLights,
+                                          const crychic_spot_shadows* spotShadows, void* stream);
+
+/* The light, projection and shadow transform of a shadowed spot light (host only; the counterpart of
+ * crychic_update_cascade_shadow_transform, whose storage it follows: untransposed row-vector matrices, copied TRANSPOSED
+ * into passCB->ShadowTransforms[4 + k]):
+ *   lightView = LookAtLH(Position, Position + Direction, up), up = (0, 1, 0), or (0, 0, 1) when
+ *               |dot(Direction, (0, 1, 0))| > 0.999 |Direction| (a light aimed straight up or down);
+ *   lightProj = PerspectiveFovLH(fovY, 1, zNear, FalloffEnd);
+ *   shadowTransform = lightView * lightProj * T, T the NDC -> texture matrix of the cascades (CRYCHIC.cpp:804-813).
+ * The shadow pass renders with ViewProj = lightView * lightProj.  CRYCHIC_E_INVALID_ARG for a NULL pointer, a zero Direction,
+ * fovY outside (0, pi), zNear <= 0 or zNear >= FalloffEnd. */
+int crychic_update_spot_shadow_transform(const crychic_light* L, float fovY, float zNear, float lightView[16], float lightProj[16],
+                                         float shadowTransform[16]);
+
 /* ---- whole hot path of CRYCHIC::Draw (CRYCHIC.cpp:220-221 + 238-279) -------------------------------------- */
 typedef struct crychic_frame_desc {
     uint32_t W, H;
@@ -283,6 +336,11 @@ int crychic_draw_hot_path(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB
 int crychic_draw_hot_path_spots(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
                                 const crychic_frame_desc* frame, const crychic_light* spot_lights_dev, uint32_t numSpotLights,
                                 void* stream);
+/* crychic_draw_hot_path_spots with shadowed spot lights (crychic_deferred_light_spots_shadowed's definition and limits); a NULL
+ * descriptor or count == 0 is crychic_draw_hot_path_spots, bit for bit. */
+int crychic_draw_hot_path_spots_shadowed(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
+                                         const crychic_frame_desc* frame, const crychic_light* spot_lights_dev, uint32_t numSpotLights,
+                                         const crychic_spot_shadows* spotShadows, void* stream);
 
 /* Per-kernel timing of the last crychic_draw_hot_path issued with profiling enabled (HIP events recorded
  * on the caller's stream around each pass).  Times are milliseconds; blocks until the events complete. */
@@ -411,7 +469,9 @@ int crychic_blur_chain_status(crychic_ctx* ctx, void* stream, uint32_t* timed_ou
 
 /* All cascades of CRYCHIC::DrawSceneToShadowMap (CRYCHIC.cpp:2477-2510 loops over four) in one pass: passCBs[c].ViewProj and
  * shadow_dev[c] per cascade, the same items for all.  Bit-identical to nCascades calls of crychic_draw_scene_to_shadow_map;
- * the workspace must hold crychic_raster_workspace_bytes(nCascades * triangles, shadowDim, shadowDim). */
+ * the workspace must hold crychic_raster_workspace_bytes(nCascades * triangles, shadowDim, shadowDim).  nCascades is 1 .. 12
+ * (gShadowMap[12], Common.hlsl:46: slots 4..11 hold the shadowed spot lights' maps); more than four targets run as consecutive
+ * fused passes of at most four on `stream`. */
 int crychic_draw_scene_to_shadow_maps(crychic_ctx* ctx, const crychic_pass_constants* passCBs, uint32_t nCascades,
                                       const crychic_draw_item* items, uint32_t nItems, uint32_t* const* shadow_dev, uint32_t shadowDim,
                                       int depthBias, float slopeScaledDepthBias, void* workspace_dev, size_t workspaceBytes, void* stream);
@@ -496,6 +556,11 @@ int crychic_draw_hot_path_shared(crychic_comm* comm, const crychic_ssao_constant
 int crychic_draw_hot_path_shared_spots(crychic_comm* comm, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
                                        const crychic_frame_desc* frame, const uint32_t* bounds, uint32_t nparts,
                                        const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream);
+/* The same with shadowed spot lights (crychic_draw_hot_path_spots_shadowed): each rank binds the maps it rendered. */
+int crychic_draw_hot_path_shared_spots_shadowed(crychic_comm* comm, const crychic_ssao_constants* ssaoCB,
+                                                const crychic_pass_constants* passCB, const crychic_frame_desc* frame,
+                                                const uint32_t* bounds, uint32_t nparts, const crychic_light* spot_lights_dev,
+                                                uint32_t numSpotLights, const crychic_spot_shadows* spotShadows, void* stream);
 /* Stream-ordered rendezvous of all ranks (a one-word ncclAllReduce): brackets timed regions; no host wait inside. */
 int crychic_comm_barrier(crychic_comm* comm, void* stream);
 
