@@ -155,8 +155,6 @@ int fill_light_params(cry::LightParams& P, const crychic_pass_constants* cb, con
     P.cubeLevels = (flags >> 16) & 15u;
     { uint32_t full = 1; for (uint32_t m = cubeDim; m > 1u; m >>= 1) ++full;
       if (P.cubeLevels > full) return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", P.cubeLevels, cubeDim, full); }
-    P.pointLights = nullptr;
-    P.numPointLights = 0;
     P.shadowWIsOne = cry::light_shadow_w_is_one(P.ShadowTransforms) ? 1u : 0u;
     P.darkLights = cry::light_dark_mask(P.Lights, numDirLights);
     P.unitLights = cry::light_dark_lengths_ok(P.Lights, numDirLights) ? 1u : 0u;
@@ -166,23 +164,23 @@ int fill_light_params(cry::LightParams& P, const crychic_pass_constants* cb, con
     return 0;
 }
 
-// Spot lights (crychic_deferred_light_spots and the _spots hot paths): at most 1024, from a device buffer when there are any.
-int check_spot_lights(const crychic_light* spots, uint32_t n)
+// The local lights of one lighting pass (every crychic_deferred_light* entry and the hot paths): at most 1024 point and 1024 spot
+// lights, each from a device buffer when there are any, into P; the descriptor's first `count` maps and ShadowTransforms[4 + k]
+// into S.  A NULL descriptor or count 0 leaves S.count = 0: the unshadowed kernels.  Touches neither P's other fields nor cb.
+int bind_local_lights(cry::LightParams& P, cry::SpotShadows& S, const crychic_pass_constants* cb, const crychic_light* points,
+                      uint32_t nPoints, const crychic_light* spots, uint32_t nSpots, const crychic_spot_shadows* d)
 {
-    if (n > cry::kMaxSpotLights || (n && !spots))
-        return fail(CRYCHIC_E_INVALID_ARG, "numSpotLights %u (max %u) / null spot light buffer", n, cry::kMaxSpotLights);
-    return 0;
-}
-
-// Shadowed spot lights (the _spots_shadowed entries): the descriptor's first `count` maps and ShadowTransforms[4 + k] into S.
-// A NULL descriptor or count 0 leaves S.count = 0: the _spots entry's kernels.
-int fill_spot_shadows(cry::SpotShadows& S, const crychic_spot_shadows* d, const crychic_pass_constants* cb, uint32_t numSpots)
-{
+    if (nPoints > cry::kMaxPointLights || (nPoints && !points))
+        return fail(CRYCHIC_E_INVALID_ARG, "numPointLights %u (max %u) / null light buffer", nPoints, cry::kMaxPointLights);
+    if (nSpots > cry::kMaxSpotLights || (nSpots && !spots))
+        return fail(CRYCHIC_E_INVALID_ARG, "numSpotLights %u (max %u) / null spot light buffer", nSpots, cry::kMaxSpotLights);
+    P.pointLights = points;
+    P.numPointLights = nPoints;
     std::memset(&S, 0, sizeof S);
     if (!d || d->count == 0) return 0;
-    if (d->count > CRYCHIC_MAX_SPOT_SHADOWS || d->count > numSpots)
+    if (d->count > CRYCHIC_MAX_SPOT_SHADOWS || d->count > nSpots)
         return fail(CRYCHIC_E_INVALID_ARG, "spot shadows: count %u (max %u, and at most numSpotLights %u)", d->count,
-                    (unsigned)CRYCHIC_MAX_SPOT_SHADOWS, numSpots);
+                    (unsigned)CRYCHIC_MAX_SPOT_SHADOWS, nSpots);
     if (d->dim < 2 || d->dim > CRYCHIC_MAX_SPOT_SHADOW_DIM)          // 2 texels at least, as the cascades: a footprint row is one pair
         return fail(CRYCHIC_E_INVALID_ARG, "spot shadows: dim %u (2 .. %u)", d->dim, (unsigned)CRYCHIC_MAX_SPOT_SHADOW_DIM);
     for (uint32_t k = 0; k < d->count; ++k) {
@@ -201,6 +199,29 @@ int check_chain_rows(const cry::LightParams& P, uint32_t row0, uint32_t rows, ui
 {
     if (P.cubeLevels > 1u && ((row0 & 1u) || ((rows & 1u) && row0 + rows != H)))
         return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u): with a cube map mip chain a call covers whole pixel quads (even row0; even rows unless they end the frame)", row0, rows);
+    return 0;
+}
+
+// Every crychic_deferred_light* entry: the lights the entry does not take are null / 0.
+int deferred_light_impl(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev, const float* g2_dev,
+                        const uint32_t* depth_dev, const uint16_t* ambient_dev, const uint32_t* const shadow_dev[4], uint32_t shadowDim,
+                        const uint8_t* cube_dev, uint32_t cubeDim, uint8_t* out_rgba8_dev, float* radiance_out_dev, uint32_t W, uint32_t H,
+                        uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags, const crychic_light* point_lights_dev,
+                        uint32_t numPointLights, const crychic_light* spot_lights_dev, uint32_t numSpotLights,
+                        const crychic_spot_shadows* spotShadows, void* stream)
+{
+    if (int rc = bind(ctx)) return rc;
+    if (int rc = check_dims(W, H)) return rc;
+    if (!cb || !g0_dev || !g1_dev || !g2_dev || !depth_dev || !shadow_dev || !cube_dev || !out_rgba8_dev)
+        return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (row0 > H || rows > H - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row frame", row0, rows, H);
+    cry::LightParams P;
+    cry::SpotShadows S;
+    if (int rc = bind_local_lights(P, S, cb, point_lights_dev, numPointLights, spot_lights_dev, numSpotLights, spotShadows)) return rc;
+    if (int rc = fill_light_params(P, cb, shadow_dev, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags)) return rc;
+    if (int rc = check_chain_rows(P, row0, rows, H)) return rc;
+    CRY_HIP(cry::launch_light(P, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, cube_dev, out_rgba8_dev, radiance_out_dev,
+                              row0, rows, (hipStream_t)stream, spot_lights_dev, numSpotLights, &S));
     return 0;
 }
 
@@ -314,17 +335,8 @@ int crychic_deferred_light(crychic_ctx* ctx, const crychic_pass_constants* cb, c
                            uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags,
                            void* stream)
 {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_dims(W, H)) return rc;
-    if (!cb || !g0_dev || !g1_dev || !g2_dev || !depth_dev || !shadow_dev || !cube_dev || !out_rgba8_dev)
-        return fail(CRYCHIC_E_INVALID_ARG, "null argument");
-    if (row0 > H || rows > H - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row frame", row0, rows, H);
-    cry::LightParams P;
-    if (int rc = fill_light_params(P, cb, shadow_dev, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags)) return rc;
-    if (int rc = check_chain_rows(P, row0, rows, H)) return rc;
-    CRY_HIP(cry::launch_light(P, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, cube_dev, out_rgba8_dev, radiance_out_dev,
-                              row0, rows, (hipStream_t)stream));
-    return 0;
+    return deferred_light_impl(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev, cubeDim, out_rgba8_dev,
+                               radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags, nullptr, 0u, nullptr, 0u, nullptr, stream);
 }
 
 int crychic_deferred_light_points(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev,
@@ -334,9 +346,9 @@ int crychic_deferred_light_points(crychic_ctx* ctx, const crychic_pass_constants
                                   uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags,
                                   const crychic_light* point_lights_dev, uint32_t numPointLights, void* stream)
 {
-    return crychic_deferred_light_spots(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev, cubeDim,
-                                        out_rgba8_dev, radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags,
-                                        point_lights_dev, numPointLights, nullptr, 0u, stream);
+    return deferred_light_impl(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev, cubeDim, out_rgba8_dev,
+                               radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags, point_lights_dev, numPointLights,
+                               nullptr, 0u, nullptr, stream);
 }
 
 int crychic_deferred_light_spots(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev,
@@ -347,9 +359,9 @@ int crychic_deferred_light_spots(crychic_ctx* ctx, const crychic_pass_constants*
                                  const crychic_light* point_lights_dev, uint32_t numPointLights,
                                  const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream)
 {
-    return crychic_deferred_light_spots_shadowed(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev,
-                                                 cubeDim, out_rgba8_dev, radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius,
-                                                 flags, point_lights_dev, numPointLights, spot_lights_dev, numSpotLights, nullptr, stream);
+    return deferred_light_impl(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev, cubeDim, out_rgba8_dev,
+                               radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags, point_lights_dev, numPointLights,
+                               spot_lights_dev, numSpotLights, nullptr, stream);
 }
 
 int crychic_deferred_light_spots_shadowed(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev,
@@ -361,24 +373,9 @@ int crychic_deferred_light_spots_shadowed(crychic_ctx* ctx, const crychic_pass_c
                                           const crychic_light* spot_lights_dev, uint32_t numSpotLights,
                                           const crychic_spot_shadows* spotShadows, void* stream)
 {
-    if (int rc = bind(ctx)) return rc;
-    if (int rc = check_dims(W, H)) return rc;
-    if (!cb || !g0_dev || !g1_dev || !g2_dev || !depth_dev || !shadow_dev || !cube_dev || !out_rgba8_dev)
-        return fail(CRYCHIC_E_INVALID_ARG, "null argument");
-    if (row0 > H || rows > H - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row frame", row0, rows, H);
-    if (numPointLights > cry::kMaxPointLights || (numPointLights && !point_lights_dev))
-        return fail(CRYCHIC_E_INVALID_ARG, "numPointLights %u (max %u) / null light buffer", numPointLights, cry::kMaxPointLights);
-    if (int rc = check_spot_lights(spot_lights_dev, numSpotLights)) return rc;
-    cry::SpotShadows S;
-    if (int rc = fill_spot_shadows(S, spotShadows, cb, numSpotLights)) return rc;
-    cry::LightParams P;
-    if (int rc = fill_light_params(P, cb, shadow_dev, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags)) return rc;
-    P.pointLights = point_lights_dev;
-    P.numPointLights = numPointLights;
-    if (int rc = check_chain_rows(P, row0, rows, H)) return rc;
-    CRY_HIP(cry::launch_light(P, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, cube_dev, out_rgba8_dev, radiance_out_dev,
-                              row0, rows, (hipStream_t)stream, spot_lights_dev, numSpotLights, &S));
-    return 0;
+    return deferred_light_impl(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev, cubeDim, out_rgba8_dev,
+                               radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags, point_lights_dev, numPointLights,
+                               spot_lights_dev, numSpotLights, spotShadows, stream);
 }
 
 }  // extern "C"
@@ -388,7 +385,7 @@ int crychic_deferred_light_spots_shadowed(crychic_ctx* ctx, const crychic_pass_c
 // part's exchange there (crychic_draw_hot_path_shared).  nparts == 1, after == nullptr is crychic_draw_hot_path itself.
 int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
                         const crychic_frame_desc* f, hipStream_t stream, uint32_t nparts, cry::PartHook after, void* user,
-                        const crychic_light* spots, uint32_t numSpots, const crychic_spot_shadows* spotShadows)
+                        const cry::SpotLightArgs& spots)
 {
     if (int rc = bind(ctx)) return rc;
     if (!ssaoCB || !passCB || !f) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
@@ -404,13 +401,8 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
     cry::LightParams P;
     if (int rc = fill_light_params(P, passCB, f->shadow_dev, f->shadowDim, f->cubeDim, W, H, f->numDirLights,
                                    f->pcfSearchRadius, f->flags)) return rc;
-    if (f->numPointLights > cry::kMaxPointLights || (f->numPointLights && !f->point_lights_dev))
-        return fail(CRYCHIC_E_INVALID_ARG, "numPointLights %u (max %u) / null light buffer", f->numPointLights, cry::kMaxPointLights);
-    P.pointLights = f->point_lights_dev;
-    P.numPointLights = f->numPointLights;
-    if (int rc = check_spot_lights(spots, numSpots)) return rc;
     cry::SpotShadows S;
-    if (int rc = fill_spot_shadows(S, spotShadows, passCB, numSpots)) return rc;
+    if (int rc = bind_local_lights(P, S, passCB, f->point_lights_dev, f->numPointLights, spots.lights, spots.count, spots.shadows)) return rc;
     const bool prof = ctx->profiling;
     if (prof) { ctx->times_valid = false; CRY_HIP(hipEventRecord(ctx->ev[0], stream)); }
     if (ssaoOn) {
@@ -432,7 +424,7 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
         const uint32_t r1 = (p + 1u == nparts) ? f->row0 + f->rows : r0 + 2u * per;
         if (r1 > r0)
             CRY_HIP(cry::launch_light(P, f->g0_dev, f->g1_dev, f->g2_dev, f->depth_dev, ssaoOn ? f->ambient0_dev : nullptr,
-                                      f->cube_dev, f->out_rgba8_dev, nullptr, r0, r1 - r0, stream, spots, numSpots, &S));
+                                      f->cube_dev, f->out_rgba8_dev, nullptr, r0, r1 - r0, stream, spots.lights, spots.count, &S));
         if (prof && p + 1u == nparts) { CRY_HIP(hipEventRecord(ctx->ev[3], stream)); ctx->times_valid = true; }
         if (after)
             if (int rc = after(user, p, r0, r1 - r0)) return rc;
@@ -445,20 +437,20 @@ extern "C" {
 int crychic_draw_hot_path(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
                           const crychic_frame_desc* f, void* stream)
 {
-    return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr);
+    return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr, {});
 }
 
 int crychic_draw_hot_path_spots(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
                                 const crychic_frame_desc* f, const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream)
 {
-    return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr, spot_lights_dev, numSpotLights);
+    return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr, { spot_lights_dev, numSpotLights, nullptr });
 }
 
 int crychic_draw_hot_path_spots_shadowed(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
                                          const crychic_frame_desc* f, const crychic_light* spot_lights_dev, uint32_t numSpotLights,
                                          const crychic_spot_shadows* spotShadows, void* stream)
 {
-    return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr, spot_lights_dev, numSpotLights, spotShadows);
+    return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr, { spot_lights_dev, numSpotLights, spotShadows });
 }
 
 int crychic_ctx_set_profiling(crychic_ctx* ctx, int enabled)

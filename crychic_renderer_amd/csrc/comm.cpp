@@ -373,8 +373,7 @@ int exchange_part(void* user, uint32_t p, uint32_t, uint32_t)
 
 namespace {
 int draw_shared(crychic_comm* c, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB, const crychic_frame_desc* f,
-                const uint32_t* bounds, uint32_t nparts, void* stream_, const crychic_light* spots, uint32_t numSpots,
-                const crychic_spot_shadows* spotShadows)
+                const uint32_t* bounds, uint32_t nparts, void* stream_, const cry::SpotLightArgs& spots)
 {
     if (!c || !c->nccl || !f) return fail(CRYCHIC_E_INVALID_ARG, "null communicator / frame descriptor");
     const Rccl* r = rccl();
@@ -387,7 +386,7 @@ int draw_shared(crychic_comm* c, const crychic_ssao_constants* ssaoCB, const cry
     if ((size_t)f->row0 * pitch != off[(size_t)c->rank] || (size_t)f->rows * pitch != len[(size_t)c->rank])
         return fail(CRYCHIC_E_INVALID_ARG, "the frame descriptor's strip [%u,+%u) is not rank %d's strip of the plan", f->row0, f->rows, c->rank);
     if (nparts == 1u) {                         // nothing to overlap: the strip, then the one-call exchange, on the caller's stream
-        if (int rc = cry::hot_path_parts(c->ctx, ssaoCB, passCB, f, stream, 1u, nullptr, nullptr, spots, numSpots, spotShadows)) return rc;
+        if (int rc = cry::hot_path_parts(c->ctx, ssaoCB, passCB, f, stream, 1u, nullptr, nullptr, spots)) return rc;
         return enqueue_gather(r, c, f->out_rgba8_dev, off, len, stream, false);
     }
     hipError_t he = hipSetDevice(c->ctx->device);
@@ -401,7 +400,7 @@ int draw_shared(crychic_comm* c, const crychic_ssao_constants* ssaoCB, const cry
     he = hipEventRecord(c->sideFree, stream);
     if (he == hipSuccess) he = hipStreamWaitEvent(c->side, c->sideFree, 0);
     if (he != hipSuccess) return fail(CRYCHIC_E_HIP, "ordering the exchange stream failed: %s", hipGetErrorString(he));
-    const int rc = cry::hot_path_parts(c->ctx, ssaoCB, passCB, f, stream, nparts, exchange_part, &d, spots, numSpots, spotShadows);
+    const int rc = cry::hot_path_parts(c->ctx, ssaoCB, passCB, f, stream, nparts, exchange_part, &d, spots);
     // whatever happened above, the caller's stream joins the side stream again: the frame is complete behind this call
     he = hipEventRecord(c->sideDone, c->side);
     if (he == hipSuccess) he = hipStreamWaitEvent(stream, c->sideDone, 0);
@@ -414,14 +413,14 @@ int draw_shared(crychic_comm* c, const crychic_ssao_constants* ssaoCB, const cry
 int crychic_draw_hot_path_shared(crychic_comm* c, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
                                  const crychic_frame_desc* f, const uint32_t* bounds, uint32_t nparts, void* stream)
 {
-    return draw_shared(c, ssaoCB, passCB, f, bounds, nparts, stream, nullptr, 0u, nullptr);
+    return draw_shared(c, ssaoCB, passCB, f, bounds, nparts, stream, {});
 }
 
 int crychic_draw_hot_path_shared_spots(crychic_comm* c, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
                                        const crychic_frame_desc* f, const uint32_t* bounds, uint32_t nparts,
                                        const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream)
 {
-    return draw_shared(c, ssaoCB, passCB, f, bounds, nparts, stream, spot_lights_dev, numSpotLights, nullptr);
+    return draw_shared(c, ssaoCB, passCB, f, bounds, nparts, stream, { spot_lights_dev, numSpotLights, nullptr });
 }
 
 int crychic_draw_hot_path_shared_spots_shadowed(crychic_comm* c, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
@@ -429,7 +428,7 @@ int crychic_draw_hot_path_shared_spots_shadowed(crychic_comm* c, const crychic_s
                                                 const crychic_light* spot_lights_dev, uint32_t numSpotLights,
                                                 const crychic_spot_shadows* spotShadows, void* stream)
 {
-    return draw_shared(c, ssaoCB, passCB, f, bounds, nparts, stream, spot_lights_dev, numSpotLights, spotShadows);
+    return draw_shared(c, ssaoCB, passCB, f, bounds, nparts, stream, { spot_lights_dev, numSpotLights, spotShadows });
 }
 
 int crychic_comm_barrier(crychic_comm* c, void* stream)

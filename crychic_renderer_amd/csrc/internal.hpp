@@ -18,11 +18,16 @@ namespace cry {
 // Stores the message crychic_last_error() returns (thread-local) and returns `code`.
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// The spot lights of a hot path (the point lights ride in crychic_frame_desc): `count` spot lights after the frame's point lights,
+// the first shadows->count of them shadowed.  {} = none; shadows == nullptr = unshadowed.
+struct SpotLightArgs {
+    const crychic_light* lights;
+    uint32_t count;
+    const crychic_spot_shadows* shadows;
+};
+
 // api.cpp: crychic_draw_hot_path with the lighting pass in `nparts` row ranges and a hook behind each (comm.cpp's overlapped exchange).
 typedef int (*PartHook)(void* user, uint32_t part, uint32_t row0, uint32_t rows);
-// spots / numSpots: spot lights after the frame's point lights (crychic_draw_hot_path_spots); nullptr / 0 = none.
-// spotShadows: the first spotShadows->count spot lights shadowed (crychic_draw_hot_path_spots_shadowed); nullptr = none.
 int hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
-                   const crychic_frame_desc* f, hipStream_t stream, uint32_t nparts, PartHook after, void* user,
-                   const crychic_light* spots = nullptr, uint32_t numSpots = 0, const crychic_spot_shadows* spotShadows = nullptr);
+                   const crychic_frame_desc* f, hipStream_t stream, uint32_t nparts, PartHook after, void* user, const SpotLightArgs& spots);
 }  // namespace cry

@@ -5,6 +5,7 @@
 // 8 B/lane on the fp16 normal plane and the depth row pairs), 4 rows per 256-thread workgroup.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <type_traits>
 #include "kernels.hpp"
 #include "ssao_core.hpp"
 #include "blur_tiles.hpp"
@@ -847,40 +848,29 @@ hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, 
     const dim3 grid = grid_for(P.W, rows);
     const bool mips = P.cubeLevels > 1u;          // the chain: quads inside wavefronts (light_tile_pixel), so the rows must start a quad
     if (mips && (row0 & 1u)) return hipErrorInvalidValue;
-    if (numSpots && shadows && shadows->count) {
-#define CRY_LAUNCH_SHADOWED(K) hipLaunchKernelGGL(K, grid, dim3(256), 0, stream, P, (const f4a*)g0, (const f4a*)g1, (const f4a*)g2, depth, ambient, \
-                                                  (const uint32_t*)cube, (uint32_t*)out, (f4a*)radiance, row0, row0 + rows, spots, numSpots, *shadows)
-        if (P.pcfSearchRadius == 0.0f) { if (mips) CRY_LAUNCH_SHADOWED((light_spots_shadowed_kernel<true, true>)); else CRY_LAUNCH_SHADOWED((light_spots_shadowed_kernel<true, false>)); }
-        else { if (mips) CRY_LAUNCH_SHADOWED((light_spots_shadowed_kernel<false, true>)); else CRY_LAUNCH_SHADOWED((light_spots_shadowed_kernel<false, false>)); }
-#undef CRY_LAUNCH_SHADOWED
+    // every family shares the kernel arguments up to row1; launch(kernel, extra...) appends the family's own
+    auto launch = [&](auto kernel, auto... extra) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, P, (const f4a*)g0, (const f4a*)g1, (const f4a*)g2, depth, ambient,
+                           (const uint32_t*)cube, (uint32_t*)out, (f4a*)radiance, row0, row0 + rows, extra...);
+    };
+    // by_radius(f) calls f(z) once and dispatch(family) calls family(z, m) once: z = <ZERO_RADIUS>, m = <MIPS>, as std::bool_constant
+    auto by_radius = [&](auto f) {
+        if (P.pcfSearchRadius == 0.0f) f(std::true_type{}); else f(std::false_type{});
         return hipGetLastError();
-    }
-    if (numSpots) {
-#define CRY_LAUNCH_SPOTS(K) hipLaunchKernelGGL(K, grid, dim3(256), 0, stream, P, (const f4a*)g0, (const f4a*)g1, (const f4a*)g2, depth, ambient, \
-                                               (const uint32_t*)cube, (uint32_t*)out, (f4a*)radiance, row0, row0 + rows, spots, numSpots)
-        if (P.pcfSearchRadius == 0.0f) { if (mips) CRY_LAUNCH_SPOTS((light_spots_kernel<true, true>)); else CRY_LAUNCH_SPOTS((light_spots_kernel<true, false>)); }
-        else { if (mips) CRY_LAUNCH_SPOTS((light_spots_kernel<false, true>)); else CRY_LAUNCH_SPOTS((light_spots_kernel<false, false>)); }
-#undef CRY_LAUNCH_SPOTS
-        return hipGetLastError();
-    }
-    if (P.numPointLights) {
-#define CRY_LAUNCH_POINTS(K) hipLaunchKernelGGL(K, grid, dim3(256), 0, stream, P, (const f4a*)g0, (const f4a*)g1, (const f4a*)g2, depth, ambient, \
-                                                (const uint32_t*)cube, (uint32_t*)out, (f4a*)radiance, row0, row0 + rows)
-        if (P.pcfSearchRadius == 0.0f) { if (mips) CRY_LAUNCH_POINTS((light_points_kernel<true, true>)); else CRY_LAUNCH_POINTS((light_points_kernel<true, false>)); }
-        else { if (mips) CRY_LAUNCH_POINTS((light_points_kernel<false, true>)); else CRY_LAUNCH_POINTS((light_points_kernel<false, false>)); }
-#undef CRY_LAUNCH_POINTS
-        return hipGetLastError();
-    }
+    };
+    auto dispatch = [&](auto family) {
+        return by_radius([&](auto z) { if (mips) family(z, std::true_type{}); else family(z, std::false_type{}); });
+    };
+    if (numSpots && shadows && shadows->count)
+        return dispatch([&](auto z, auto m) { launch(light_spots_shadowed_kernel<z, m>, spots, numSpots, *shadows); });
+    if (numSpots)
+        return dispatch([&](auto z, auto m) { launch(light_spots_kernel<z, m>, spots, numSpots); });
+    if (P.numPointLights)
+        return dispatch([&](auto z, auto m) { launch(light_points_kernel<z, m>); });
+    if (mips)                                     // FIX compiled in: the chain is not the benchmark's instantiation
+        return by_radius([&](auto z) { launch(light_kernel<z, true, true>); });
     const bool fix = (P.flags & (CRYCHIC_FIX_Q1 | CRYCHIC_FIX_Q3 | CRYCHIC_FIX_Q4)) != 0;
-#define CRY_LAUNCH_LIGHT(K) hipLaunchKernelGGL(K, grid, dim3(256), 0, stream, P, (const f4a*)g0, (const f4a*)g1, (const f4a*)g2, depth, ambient, \
-                                               (const uint32_t*)cube, (uint32_t*)out, (f4a*)radiance, row0, row0 + rows)
-    if (mips) {                                   // FIX compiled in: the chain is not the benchmark's instantiation
-        if (P.pcfSearchRadius == 0.0f) CRY_LAUNCH_LIGHT((light_kernel<true, true, true>)); else CRY_LAUNCH_LIGHT((light_kernel<false, true, true>));
-    }
-    else if (P.pcfSearchRadius == 0.0f) { if (fix) CRY_LAUNCH_LIGHT((light_kernel<true, true>)); else CRY_LAUNCH_LIGHT((light_kernel<true, false>)); }
-    else { if (fix) CRY_LAUNCH_LIGHT((light_kernel<false, true>)); else CRY_LAUNCH_LIGHT((light_kernel<false, false>)); }
-#undef CRY_LAUNCH_LIGHT
-    return hipGetLastError();
+    return by_radius([&](auto z) { if (fix) launch(light_kernel<z, true>); else launch(light_kernel<z, false>); });
 }
 
 }  // namespace cry

@@ -45,8 +45,8 @@ hipError_t launch_blur_replay_chain(const crychic_ssao_constants& cb, const void
 // shadows: the first shadows->count spot lights shadowed (light_spots_shadowed_kernel); nullptr or count 0 = none.
 hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, const float* g2,
                         const uint32_t* depth, const uint16_t* ambient, const uint8_t* cube, uint8_t* out,
-                        float* radiance, uint32_t row0, uint32_t rows, hipStream_t stream, const crychic_light* spots = nullptr,
-                        uint32_t numSpots = 0, const SpotShadows* shadows = nullptr);
+                        float* radiance, uint32_t row0, uint32_t rows, hipStream_t stream, const crychic_light* spots,
+                        uint32_t numSpots, const SpotShadows* shadows);
 
 
 // ---- producer passes (raster.hip) ----

@@ -753,36 +753,26 @@ CRY_HD bool light_dark_guard(f4a G0, f4a G1, f4a G2)
 struct NoPointLights {
     CRY_HD void operator()(f3, f3, float, float, f3, f3, f3&, bool, bool) const {}
 };
-// Iterates every point light of the buffer (what the oracle does); the tiled kernel substitutes a culled iteration.
-struct AllPointLights {
-    const crychic_light* lights; uint32_t n;
-    CRY_HD void operator()(f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view, f3& result, bool fixQ3, bool fixQ4) const
-    {
-        for (uint32_t i = 0; i < n; ++i) pbr_point_light(lights[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
-    }
-};
-// Every point light, then every spot light (the gLights order, Common.hlsl:102-105), un-culled: the host build's iteration.
+// Every point light, then every spot light (the gLights order, Common.hlsl:102-105), un-culled: the host build's iteration, where the
+// tiled kernels substitute a culled one.  shadows == nullptr models light_points_kernel / light_spots_kernel (UnitShadow), otherwise
+// the first shadows->count spot lights are shadowed as in light_spots_shadowed_kernel.
 struct AllLocalLights {
-    const crychic_light* points; uint32_t nPoints;
-    const crychic_light* spots; uint32_t nSpots;
-    CRY_HD void operator()(f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view, f3& result, bool fixQ3, bool fixQ4) const
-    {
-        for (uint32_t i = 0; i < nPoints; ++i) pbr_point_light(points[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
-        for (uint32_t i = 0; i < nSpots; ++i) pbr_spot_light(spots[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
-    }
-};
-// AllLocalLights with the first shadows->count spot lights shadowed: the host build's iteration of the shadowed kernel.
-struct AllLocalLightsShadowed {
     const crychic_light* points; uint32_t nPoints;
     const crychic_light* spots; uint32_t nSpots;
     const SpotShadows* shadows;
     CRY_HD void operator()(f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view, f3& result, bool fixQ3, bool fixQ4) const
     {
         for (uint32_t i = 0; i < nPoints; ++i) pbr_point_light(points[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
-        for (uint32_t i = 0; i < nSpots; ++i)
-            pbr_spot_light(spots[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4, SpotShadowOf{ shadows, pos, i });
+        for (uint32_t i = 0; i < nSpots; ++i) {
+            if (shadows) pbr_spot_light(spots[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4, SpotShadowOf{ shadows, pos, i });
+            else pbr_spot_light(spots[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
+        }
     }
 };
+// The names the point-light and shadowed-spot host builds were written against: the same functor, with the members they do not
+// initialise left null / 0 ({ points, n } = no spot lights; { points, nPoints, spots, nSpots, shadows } = all of them).
+using AllPointLights = AllLocalLights;
+using AllLocalLightsShadowed = AllLocalLights;
 
 // DeferredShading.hlsl:53-76: cascade selection and the (blended) shadow factor of the first light for one pixel.
 // `abs(distance - radius[j] < 5.0f)` is abs(bool) (Q1), true whenever distance < radius[j]: every pixel nearer than 80 blends

@@ -232,29 +232,23 @@ class Crychic:
             if len(self._desc) > 16:
                 self._desc.clear()
             f = self._desc[key] = self.frame_desc(row0, rows)
-        if self.mSpotLights is not None and self._spotShadow is not None:     # extension: the _spots_shadowed entries
+        if self.mSpotLights is not None:       # extension: the _spots_shadowed entries (no descriptor: unshadowed), frame, strip or shared
             spots, n = _ptr(self.mSpotLights), self.mSpotLights.numel() // 48
-            desc, T, cbs, geo = self._spotShadow
-            pcb = PassConstants.from_buffer_copy(self.mMainPassCB)          # mMainPassCB with the spot transforms in slots 4..11
-            for k, t in enumerate(T):
-                pcb.ShadowTransforms[4 + k][:] = t
-            if geo is not None:
-                self.DrawSpotShadowMaps()
+            pcb, desc = self.mMainPassCB, None
+            if self._spotShadow is not None:
+                d, T, cbs, geo = self._spotShadow
+                desc = C.byref(d)
+                pcb = PassConstants.from_buffer_copy(self.mMainPassCB)      # mMainPassCB with the spot transforms in slots 4..11
+                for k, t in enumerate(T):
+                    pcb.ShadowTransforms[4 + k][:] = t
+                if geo is not None:
+                    self.DrawSpotShadowMaps()
             if shared is not None:
                 check(lib.crychic_draw_hot_path_shared_spots_shadowed(shared[0], C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), shared[1],
-                                                                      int(shared[2]), spots, n, C.byref(desc), _stream(self.ctx.device)))
-                return
-            check(lib.crychic_draw_hot_path_spots_shadowed(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), spots, n, C.byref(desc),
-                                                           _stream(self.ctx.device)))
-            return
-        if self.mSpotLights is not None:       # extension: the _spots entries, for the whole frame, a strip or the shared path
-            spots, n = _ptr(self.mSpotLights), self.mSpotLights.numel() // 48
-            if shared is not None:
-                check(lib.crychic_draw_hot_path_shared_spots(shared[0], C.byref(self.mSsaoCB), C.byref(self.mMainPassCB), C.byref(f), shared[1],
-                                                             int(shared[2]), spots, n, _stream(self.ctx.device)))
-                return
-            check(lib.crychic_draw_hot_path_spots(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(self.mMainPassCB), C.byref(f), spots, n,
-                                                  _stream(self.ctx.device)))
+                                                                      int(shared[2]), spots, n, desc, _stream(self.ctx.device)))
+            else:
+                check(lib.crychic_draw_hot_path_spots_shadowed(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), spots, n, desc,
+                                                               _stream(self.ctx.device)))
             return
         if shared is not None:
             check(lib.crychic_draw_hot_path_shared(shared[0], C.byref(self.mSsaoCB), C.byref(self.mMainPassCB), C.byref(f), shared[1],

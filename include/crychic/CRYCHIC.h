@@ -225,7 +225,8 @@ public:
         // back buffer that Present sees is complete on every GPU.  The reference has one GPU (NodeMask 0, CRYCHIC.cpp:96,105).
         // With SetExchangeParts(n > 1) the lighting pass runs in n row ranges and each range travels while the next is lit.
         // Local lights (SetLocalLights; an extension the reference's shader leaves dead): point lights ride in the frame descriptor,
-        // spot lights take the _spots entries.
+        // spot lights and their shadows take the _spots_shadowed entries.  With no spot lights, or a shadow count of 0, those entries
+        // are crychic_draw_hot_path(_shared) / the _spots entries bit for bit (include/crychic_hip.h).
         if (mPointLights) { f.point_lights_dev = static_cast<const crychic_light*>(mPointLights->Data()); f.numPointLights = mNumPointLights; }
         const crychic_light* spots = mSpotLights ? static_cast<const crychic_light*>(mSpotLights->Data()) : nullptr;
         // Shadowed spot lights (SetSpotShadows): the first mSpotShadowCount spot lights read their maps through ShadowTransforms[4 + k]
@@ -233,32 +234,13 @@ public:
         sh.count = spots ? mSpotShadowCount : 0u;
         sh.dim = mSpotShadowDim;
         for (uint32_t k = 0; k < sh.count; ++k) sh.maps[k] = static_cast<const uint32_t*>(mSpotShadowMaps[k]->Data());
-        if (mComm && spots && sh.count)
-            CrychicThrowIfFailed(crychic_draw_hot_path_shared_spots_shadowed(mComm, reinterpret_cast<const crychic_ssao_constants*>(&scb),
-                                                                             reinterpret_cast<const crychic_pass_constants*>(&pcb), &f,
-                                                                             mStripBounds.empty() ? nullptr : mStripBounds.data(), mExchangeParts,
-                                                                             spots, mNumSpotLights, &sh, mCommandList->Stream()));
-        else if (spots && sh.count)
-            CrychicThrowIfFailed(crychic_draw_hot_path_spots_shadowed(md3dDevice->Ctx(), reinterpret_cast<const crychic_ssao_constants*>(&scb),
-                                                                      reinterpret_cast<const crychic_pass_constants*>(&pcb), &f, spots,
-                                                                      mNumSpotLights, &sh, mCommandList->Stream()));
-        else if (mComm && spots)
-            CrychicThrowIfFailed(crychic_draw_hot_path_shared_spots(mComm, reinterpret_cast<const crychic_ssao_constants*>(&scb),
-                                                                    reinterpret_cast<const crychic_pass_constants*>(&pcb), &f,
-                                                                    mStripBounds.empty() ? nullptr : mStripBounds.data(), mExchangeParts,
-                                                                    spots, mNumSpotLights, mCommandList->Stream()));
-        else if (mComm)
-            CrychicThrowIfFailed(crychic_draw_hot_path_shared(mComm, reinterpret_cast<const crychic_ssao_constants*>(&scb),
-                                                              reinterpret_cast<const crychic_pass_constants*>(&pcb), &f,
-                                                              mStripBounds.empty() ? nullptr : mStripBounds.data(), mExchangeParts,
-                                                              mCommandList->Stream()));
-        else if (spots)
-            CrychicThrowIfFailed(crychic_draw_hot_path_spots(md3dDevice->Ctx(), reinterpret_cast<const crychic_ssao_constants*>(&scb),
-                                                             reinterpret_cast<const crychic_pass_constants*>(&pcb), &f, spots, mNumSpotLights,
-                                                             mCommandList->Stream()));
+        const auto* ssaoCB = reinterpret_cast<const crychic_ssao_constants*>(&scb);
+        const auto* passCB = reinterpret_cast<const crychic_pass_constants*>(&pcb);
+        if (mComm)
+            CrychicThrowIfFailed(crychic_draw_hot_path_shared_spots_shadowed(mComm, ssaoCB, passCB, &f, mStripBounds.empty() ? nullptr : mStripBounds.data(),
+                                                                             mExchangeParts, spots, mNumSpotLights, &sh, mCommandList->Stream()));
         else
-            CrychicThrowIfFailed(crychic_draw_hot_path(md3dDevice->Ctx(), reinterpret_cast<const crychic_ssao_constants*>(&scb),
-                                                       reinterpret_cast<const crychic_pass_constants*>(&pcb), &f, mCommandList->Stream()));
+            CrychicThrowIfFailed(crychic_draw_hot_path_spots_shadowed(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, mNumSpotLights, &sh, mCommandList->Stream()));
         // :300-305: advance the fence and signal it behind this frame's commands
         mCurrFrameResource->Fence = ++mCurrentFence;
         CrychicHipThrowIfFailed(hipEventRecord(mCurrFrameResource->FenceEvent, mCommandList->Stream()));

@@ -248,7 +248,7 @@ int crychic_deferred_light_spots(crychic_ctx* ctx, const crychic_pass_constants*
                                  const crychic_light* point_lights_dev, uint32_t numPointLights,
                                  const crychic_light* spot_lights_dev, uint32_t numSpotLights, void* stream);
 
-/* ---- shadowed spot lights (BUILD-DEFINED EXTENSION; parity against this repo's checker, tests/spot_shadow_ref) ---------- *
+/* ---- shadowed spot lights (BUILD-DEFINED EXTENSION; parity against this repo's checker, tests/local_light_ref) --------- *
  * The reference declares gShadowMap[12] / gShadowTransforms[12] (Common.hlsl:46,91), of which the cascades use slots 0..3, and
  * leaves the spot branch's `result += shadowFactor[i] * brdf * lightStrength` commented out (PBR.hlsl:145).  Here the first
  * `count` (<= CRYCHIC_MAX_SPOT_SHADOWS) spot lights fill slots 4..11: spot light k < count reads

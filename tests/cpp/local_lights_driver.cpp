@@ -1,8 +1,13 @@
-// spot_shadow_driver.cpp -- the C++ veneer's shadowed spot lights: CRYCHIC::SetLocalLights + SetSpotShadows, then Update / Draw as a
-// reference call site would; frames go back for comparison with the Python path (tests/test_spot_shadows_veneer.py).
-// Usage: spot_shadow_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <numDirLights> <count> <dim>
-// <dir> holds the planes veneer_driver reads, spots.bin (an array of Light), spotmap<k>.bin (the first <count> maps, dim x dim D24)
-// and scene_spots.bin (the spot light of the built-in scene's run).
+// local_lights_driver.cpp -- the C++ veneer's local lights, as a reference call site would drive them (Update / Draw); frames go
+// back for comparison with the Python path (tests/test_spot_lights.py, tests/test_spot_shadows_veneer.py).  Three runs:
+//   1. CRYCHIC::SetLocalLights with point and spot lists: out.bin, then cleared to nothing: out_nolights.bin (pass_cb.bin, ssao_cb.bin);
+//   2. spot lights with SetSpotShadows(<count>, <dim>) and the caller's maps: out_shadowed.bin, then SetSpotShadows(0):
+//      out_noshadow.bin (pass_cb_shadowed.bin, ssao_cb_shadowed.bin);
+//   3. the built-in scene with its producer passes and one shadowed spot light: scene_shadowed.bin, scene_spotmap0.bin,
+//      scene_unshadowed.bin.
+// Usage: local_lights_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <numDirLights> <count> <dim>
+// <dir> holds the planes veneer_driver reads, points.bin and spots.bin (arrays of Light), randvec.bin (run 2's random-vector map),
+// spotmap<k>.bin (the first <count> maps, dim x dim D24) and scene_spots.bin (the spot light of run 3).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -66,14 +71,18 @@ int main(int argc, char** argv)
             app.CommandList()->Flush();
             dump(dir + "/" + name, out.data(), out.size());
         };
-        {
-            CRYCHIC app(0, W, H);
+        auto dump_cbs = [&](CRYCHIC& app, const std::string& suffix) {
+            dump(dir + "/pass_cb" + suffix + ".bin", &app.mCurrFrameResource->PassCB->Element(0), sizeof(PassConstants));
+            dump(dir + "/ssao_cb" + suffix + ".bin", &app.mCurrFrameResource->SsaoCB->Element(0), sizeof(SsaoConstants));
+        };
+        // an app over the planes of <dir> (no producer passes)
+        auto with_planes = [&](CRYCHIC& app) {
             app.mShadowMapSize = SD;
             app.mBlurCount = std::atoi(argv[6]);
             app.mNumDirLights = std::atoi(argv[7]);
             app.mSkyEnabled = true;
             app.mRunProducerPasses = false;
-            if (!app.Initialize()) return 3;
+            if (!app.Initialize()) return false;
             hipStream_t s = app.CommandList()->Stream();
             put(app.DepthStencilBuffer(), dir + "/depth.bin", s);
             put(app.mSsao->NormalMap(), dir + "/normal.bin", s);
@@ -82,8 +91,35 @@ int main(int argc, char** argv)
             auto cube = std::make_unique<ID3D12Resource>((size_t)6 * CD * CD * 4, ID3D12Resource::DEFAULT_HEAP);
             put(cube.get(), dir + "/cube.bin", s);
             app.SetCubeMap(std::move(cube), CD);
-
-            const std::vector<Light> spots = lights(dir + "/spots.bin");
+            return true;
+        };
+        const std::vector<Light> points = lights(dir + "/points.bin"), spots = lights(dir + "/spots.bin");
+        {
+            CRYCHIC app(0, W, H);
+            if (!with_planes(app)) return 3;
+            // errors throw CrychicException, as everywhere in the veneer
+            if (!throws_invalid([&] { app.SetLocalLights(nullptr, 1, nullptr, 0); })) {
+                std::fprintf(stderr, "SetLocalLights(nullptr, 1) did not throw\n");
+                return 4;
+            }
+            std::vector<Light> many(1025);
+            if (!throws_invalid([&] { app.SetLocalLights(nullptr, 0, many.data(), 1025); })) {
+                std::fprintf(stderr, "SetLocalLights(1025 spots) did not throw\n");
+                return 4;
+            }
+            app.SetLocalLights(points.data(), (uint32_t)points.size(), spots.data(), (uint32_t)spots.size());
+            frame(app, "out.bin");
+            app.SetLocalLights(nullptr, 0, nullptr, 0);     // today's behaviour again
+            frame(app, "out_nolights.bin");
+            dump_cbs(app, "");
+        }
+        {
+            CRYCHIC app(0, W, H);
+            if (!with_planes(app)) return 3;
+            hipStream_t s = app.CommandList()->Stream();
+            // the veneer draws its random-vector map from the process-wide rand() state (Ssao::RandState), which run 1 has advanced:
+            // this run takes the map a fresh process builds
+            put(app.mSsao->RandomVectorMap(), dir + "/randvec.bin", s);
             app.SetLocalLights(nullptr, 0, spots.data(), (uint32_t)spots.size());
             // errors throw CrychicException, as everywhere in the veneer, and leave the shadows as they were (none)
             const uint32_t n = (uint32_t)spots.size();
@@ -99,9 +135,8 @@ int main(int argc, char** argv)
 
             app.SetSpotShadows(count, dim, fovY, zNear);
             for (uint32_t k = 0; k < count; ++k) put(app.SpotShadowMap(k), dir + "/spotmap" + std::to_string(k) + ".bin", s);
-            frame(app, "out.bin");
-            dump(dir + "/pass_cb.bin", &app.mCurrFrameResource->PassCB->Element(0), sizeof(PassConstants));
-            dump(dir + "/ssao_cb.bin", &app.mCurrFrameResource->SsaoCB->Element(0), sizeof(SsaoConstants));
+            frame(app, "out_shadowed.bin");
+            dump_cbs(app, "_shadowed");
             app.SetSpotShadows(0, 0, 0.0f, 0.0f);          // the unshadowed spot lights again
             frame(app, "out_noshadow.bin");
         }
@@ -127,7 +162,7 @@ int main(int argc, char** argv)
             app.SetSpotShadows(0, 0, 0.0f, 0.0f);
             frame(app, "scene_unshadowed.bin");
         }
-        std::printf("spot shadow driver ok %ux%u\n", W, H);
+        std::printf("local lights driver ok %ux%u\n", W, H);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "exception: %s\n", e.what());
         return 1;

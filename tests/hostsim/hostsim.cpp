@@ -307,7 +307,7 @@ void hs_light(const crychic_pass_constants* cb, const float* g0, const float* g1
     P.cubeLevels = (flags >> 16) & 15u;                    // CRYCHIC_LIGHT_CUBE_LEVELS
     light_params_derive(P);
     const bool chain = P.cubeLevels > 1u;
-    const AllPointLights pl{ pointLights, numPointLights };
+    const AllLocalLights pl{ pointLights, numPointLights, nullptr, 0u, nullptr };
     const f4a* G0 = (const f4a*)g0; const f4a* G1 = (const f4a*)g1; const f4a* G2 = (const f4a*)g2;
     for (uint32_t y = row0; y < row0 + rows; ++y)
         for (uint32_t x = 0; x < W; ++x) {
@@ -323,14 +323,14 @@ void hs_light(const crychic_pass_constants* cb, const float* g0, const float* g1
                 if (shaded(x, y ^ 1u)) { const f3 n = reflection_dir(P, G0[(y ^ 1u) * W + x], G2[(y ^ 1u) * W + x]); ddy = (y & 1u) ? f3{ r.x - n.x, r.y - n.y, r.z - n.z } : f3{ n.x - r.x, n.y - r.y, n.z - r.z }; }
                 const float lod = cube_lod(P.cubeDim, P.cubeLevels, r, ddx, ddy);
                 const CubeChain cc{ lod, cube_chain_flat(lod) };
-                if (pcfSearchRadius == 0.0f) lit = light_pixel<true, AllPointLights, true, CubeChain>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl, cc);
-                else lit = light_pixel<false, AllPointLights, true, CubeChain>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl, cc);
+                if (pcfSearchRadius == 0.0f) lit = light_pixel<true, AllLocalLights, true, CubeChain>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl, cc);
+                else lit = light_pixel<false, AllLocalLights, true, CubeChain>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl, cc);
             }
             else if ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu) {
-                if (pcfSearchRadius == 0.0f) lit = fix ? light_pixel<true, AllPointLights, true>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl)
-                                                       : light_pixel<true, AllPointLights, false>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl);
-                else lit = fix ? light_pixel<false, AllPointLights, true>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl)
-                               : light_pixel<false, AllPointLights, false>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl);
+                if (pcfSearchRadius == 0.0f) lit = fix ? light_pixel<true, AllLocalLights, true>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl)
+                                                       : light_pixel<true, AllLocalLights, false>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl);
+                else lit = fix ? light_pixel<false, AllLocalLights, true>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl)
+                               : light_pixel<false, AllLocalLights, false>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl);
             }
             else if (flags & CRYCHIC_LIGHT_SKY) lit = chain ? sky_pixel_chain(P, (const uint32_t*)cube, x, y) : sky_pixel(P, (const uint32_t*)cube, x, y);
             else lit = f4{ 0.690196097f, 0.768627524f, 0.870588303f, 1.0f };

@@ -1,7 +1,8 @@
-// spot_shadow_host.cpp -- TEST HARNESS ONLY.  The shadowed spot-light kernel body (csrc/light_core.hpp light_pixel with the
-// AllLocalLightsShadowed functor: pbr_point_light, then pbr_spot_light with SpotShadowOf) compiled for the host CPU, so that the
-// CPU-only tier checks the definition bit for bit against tests/spot_shadow_ref/spot_shadow_ref.c before any GPU time is spent.
-// Modelled on tests/spot_ref/spot_host.cpp; the tiled kernel walks the culled lights in the same ascending order.
+// local_light_host.cpp -- TEST HARNESS ONLY.  The local-light kernel body (csrc/light_core.hpp light_pixel with the AllLocalLights
+// functor: pbr_point_light, then pbr_spot_light) compiled for the host CPU, so that the CPU-only tier checks the definition bit for
+// bit against tests/local_light_ref/local_light_ref.c before any GPU time is spent.  shadowCount 0 models light_spots_kernel
+// (UnitShadow), otherwise light_spots_shadowed_kernel (SpotShadowOf).  Modelled on tests/hostsim/hostsim.cpp's hs_light; the tiled
+// kernels walk the culled lights in the same ascending order as the un-culled iteration here.
 #include <cstring>
 #include "light_core.hpp"
 
@@ -12,7 +13,7 @@ extern "C" float shh_spot_shadow_factor(const uint32_t* map, uint32_t dim, const
     return spot_shadow_factor(map, dim, 1.0f / (float)dim, T, f3{ pos[0], pos[1], pos[2] });
 }
 
-extern "C" void shh_light_spots_shadowed(const crychic_pass_constants* cb, const float* g0, const float* g1, const float* g2,
+extern "C" void shh_light_local(const crychic_pass_constants* cb, const float* g0, const float* g1, const float* g2,
                                const uint32_t* depth, const uint16_t* ambient, const uint32_t* const shadow[4], uint32_t shadowDim,
                                const uint8_t* cube, uint32_t cubeDim, uint8_t* out, float* radiance, uint32_t W, uint32_t H,
                                uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags,
@@ -38,11 +39,11 @@ extern "C" void shh_light_spots_shadowed(const crychic_pass_constants* cb, const
     P.cubeLevels = (flags >> 16) & 15u;                    // CRYCHIC_LIGHT_CUBE_LEVELS
     light_params_derive(P);
     const bool chain = P.cubeLevels > 1u;
-    SpotShadows S;                                          // as api.cpp fill_spot_shadows builds it
+    SpotShadows S;                                          // as api.cpp bind_local_lights builds it
     std::memset(&S, 0, sizeof S);
     for (uint32_t k = 0; k < shadowCount; ++k) { S.maps[k] = shadowMaps[k]; std::memcpy(S.T[k], cb->ShadowTransforms[4 + k], sizeof S.T[k]); }
     S.count = shadowCount; S.dim = shadowMapDim; S.dx = shadowCount ? 1.0f / (float)shadowMapDim : 0.0f;
-    const AllLocalLightsShadowed ll{ pointLights, numPointLights, spotLights, numSpotLights, &S };
+    const AllLocalLights ll{ pointLights, numPointLights, spotLights, numSpotLights, shadowCount ? &S : nullptr };
     const f4a* G0 = (const f4a*)g0; const f4a* G1 = (const f4a*)g1; const f4a* G2 = (const f4a*)g2;
     auto shaded = [&](uint32_t xx, uint32_t yy) { return xx < W && yy < row0 + rows && (depth[yy * W + xx] & 0x00FFFFFFu) < 0x00FFFFFFu; };
     for (uint32_t y = row0; y < row0 + rows; ++y)
@@ -50,19 +51,19 @@ extern "C" void shh_light_spots_shadowed(const crychic_pass_constants* cb, const
             const uint32_t idx = y * W + x;
             f4 lit;
             if (shaded(x, y) && chain) {
-                // light_spots_shadowed_kernel<.., MIPS>: the quad neighbours' reflection vectors by lane exchange there, by recomputation here
+                // light_spots(_shadowed)_kernel<.., MIPS>: the quad neighbours' reflection vectors by lane exchange there, by recomputation here
                 const f3 r = reflection_dir(P, G0[idx], G2[idx]);
                 f3 ddx{ 0.0f, 0.0f, 0.0f }, ddy{ 0.0f, 0.0f, 0.0f };
                 if (shaded(x ^ 1u, y)) { const f3 n = reflection_dir(P, G0[y * W + (x ^ 1u)], G2[y * W + (x ^ 1u)]); ddx = (x & 1u) ? f3{ r.x - n.x, r.y - n.y, r.z - n.z } : f3{ n.x - r.x, n.y - r.y, n.z - r.z }; }
                 if (shaded(x, y ^ 1u)) { const f3 n = reflection_dir(P, G0[(y ^ 1u) * W + x], G2[(y ^ 1u) * W + x]); ddy = (y & 1u) ? f3{ r.x - n.x, r.y - n.y, r.z - n.z } : f3{ n.x - r.x, n.y - r.y, n.z - r.z }; }
                 const float lod = cube_lod(P.cubeDim, P.cubeLevels, r, ddx, ddy);
                 const CubeChain cc{ lod, cube_chain_flat(lod) };
-                if (pcfSearchRadius == 0.0f) lit = light_pixel<true, AllLocalLightsShadowed, true, CubeChain>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, ll, cc);
-                else lit = light_pixel<false, AllLocalLightsShadowed, true, CubeChain>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, ll, cc);
+                if (pcfSearchRadius == 0.0f) lit = light_pixel<true, AllLocalLights, true, CubeChain>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, ll, cc);
+                else lit = light_pixel<false, AllLocalLights, true, CubeChain>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, ll, cc);
             } else if (shaded(x, y)) {
-                // the shadowed kernel compiles FIX in, as the point-light kernel does
-                if (pcfSearchRadius == 0.0f) lit = light_pixel<true, AllLocalLightsShadowed, true>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, ll);
-                else lit = light_pixel<false, AllLocalLightsShadowed, true>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, ll);
+                // the spot kernels compile FIX in, as the point-light kernel does
+                if (pcfSearchRadius == 0.0f) lit = light_pixel<true, AllLocalLights, true>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, ll);
+                else lit = light_pixel<false, AllLocalLights, true>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, ll);
             }
             else if (flags & CRYCHIC_LIGHT_SKY) lit = chain ? sky_pixel_chain(P, (const uint32_t*)cube, x, y) : sky_pixel(P, (const uint32_t*)cube, x, y);
             else lit = f4{ 0.690196097f, 0.768627524f, 0.870588303f, 1.0f };

@@ -1,9 +1,9 @@
 /*
- * spot_shadow_ref.c -- TEST INFRASTRUCTURE: the checker of the shadowed spot lights (include/crychic_hip.h
+ * local_light_ref.c -- TEST INFRASTRUCTURE: the checker of the local lights (include/crychic_hip.h crychic_deferred_light_spots and
  * crychic_deferred_light_spots_shadowed).  The frozen oracle (oracle/or_light.c) is included unchanged, so its static BRDF,
  * sampler, PCF, cube and sky helpers are the ones used here; what is restated is the oracle's light_pixel with the spot loop
- * (tests/spot_ref/spot_ref.c) appended after the point loop, now with a shadow factor per spot light, and the frame loop around
- * it.  Built with the oracle's flags (tests/spot_shadow_lib.py).
+ * appended after the point loop, with a shadow factor per spot light (1 for the unshadowed ones), and the frame loop around it.
+ * Built with the oracle's flags (tests/local_light_lib.py).
  */
 #include "or_light.c"
 
@@ -168,7 +168,7 @@ static void spot_light_pixel(const or_pass_constants* cb, const float* g0, const
 }
 
 /* or_deferred_light_points plus the spot lights, the first shadowCount of them shadowed by maps[k] through
- * cb->ShadowTransforms[4 + k]; the same `sky` word (bit 0 sky, Q fixes, cube levels).  shadowCount 0 = tests/spot_ref. */
+ * cb->ShadowTransforms[4 + k]; the same `sky` word (bit 0 sky, Q fixes, cube levels).  shadowCount 0 = the unshadowed spot lights. */
 void ss_deferred_light_spots_shadowed(const or_pass_constants* cb, const float* g0, const float* g1, const float* g2,
                              const uint32_t* depth, const uint16_t* ambient, const uint32_t* const shadow[4],
                              uint32_t shadowDim, const uint8_t* cube, uint32_t cubeDim, uint8_t* out_rgba8,

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
-from test_point_lights import as_or_lights
+from local_lights_util import as_or_lights
 from test_textures import cube_header
 
 

@@ -7,12 +7,7 @@ import pytest
 
 import oracle_lib
 import scene_util
-
-
-def as_or_lights(lights):
-    arr = (oracle_lib.OrLight * len(lights))()
-    C.memmove(C.addressof(arr), C.addressof(lights), C.sizeof(arr))
-    return arr
+from local_lights_util import as_or_lights
 
 
 def lights_for_test():

@@ -1,62 +1,16 @@
 """Spot lights (extension, include/crychic_hip.h crychic_deferred_light_spots): the reference's NUM_SPOT_LIGHTS branch
-(PBR.hlsl:126-147) is dead code, so parity is against this repo's checker (tests/spot_ref/spot_ref.c, the frozen oracle's
-or_light.c with the spot loop appended), which is itself anchored to the oracle (SpotPower 0 = a point light) and to an
+(PBR.hlsl:126-147) is dead code, so parity is against this repo's checker (tests/local_light_ref/local_light_ref.c, the frozen
+oracle's or_light.c with the spot loop appended), which is itself anchored to the oracle (SpotPower 0 = a point light) and to an
 independent float64 restatement."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import local_light_lib
 import oracle_lib
-import scene_util
-import spot_lib
-
-FIX_ALL = 0x100 | 0x200 | 0x400          # CRYCHIC_FIX_Q1 | Q3 | Q4 (the oracle uses the same bits)
-
-
-def light_array(lights):
-    from crychic_renderer_amd._lib import Light
-    arr = (Light * len(lights))()
-    for k, L in enumerate(lights):
-        C.memmove(C.addressof(arr[k]), C.addressof(L), 48)
-    return arr
-
-
-def as_or_lights(lights):
-    arr = (oracle_lib.OrLight * len(lights))()
-    C.memmove(C.addressof(arr), C.addressof(lights), C.sizeof(arr))
-    return arr
-
-
-def spots_for_test(power=None):
-    """A ring aimed at the box field plus irregular members: an unnormalised direction, a light aimed away from everything,
-    one that reaches nothing, one that reaches everything.  power: override every SpotPower."""
-    from crychic_renderer_amd import scene
-    L = scene.spot_light_ring(12, radius=10.0, y=6.0, falloff_end=25.0, spot_power=8.0)
-    L[1].Direction[:] = [2.0 * v for v in L[1].Direction]          # used as given: a longer vector sharpens the cone
-    L[2].Direction[:] = (0.0, 1.0, 0.0)                             # aimed at the sky: only the 0.001 floor lights
-    L[3].Position[:] = (500.0, 500.0, 500.0)                        # reaches nothing
-    L[4].FalloffEnd = 300.0; L[4].SpotPower = 64.0                  # reaches everything, tight cone
-    L[5].Strength[:] = (3.0, 0.3, 0.2); L[5].SpotPower = 1.0
-    L[6].FalloffStart = 0.5; L[6].SpotPower = 200.0
-    if power is not None:
-        for k in range(len(L)):
-            L[k].SpotPower = power
-    return L
-
-
-def points_for_test():
-    from crychic_renderer_amd import scene
-    L = scene.point_light_grid(4)
-    L[2].Strength[:] = (0.2, 2.5, 0.3)
-    return L
-
-
-def _cpu(W, H):
-    pl = scene_util.cpu_scene(W, H, 256, 32)
-    p = scene_util.np_planes(pl)
-    c = pl["consts"]
-    return pl, p, c, oracle_lib.as_oracle_cb(c.pass_cb, oracle_lib.OrPassConstants)
+from local_lights_util import (FIX_ALL, _app, _cpu, _dev_lights, _device_scene, as_or_lights, light_array, points_for_test,
+                               run_local_lights_driver, spots_for_test)
 
 
 # ---- CPU tier -------------------------------------------------------------------------------------------------------------
@@ -74,7 +28,7 @@ def test_checker_at_power_zero_is_the_oracles_point_light(oracle, fixes, chain):
         p = dict(p, cube=cube)
         kw = dict(cube_dim=32)
         flags |= (levels & 15) << 16
-    sl = spot_lib.load()
+    sl = local_light_lib.load()
     spots, points = spots_for_test(power=0.0), points_for_test()
     # spots alone == the same lights as point lights
     got, grad = sl.checker(pcb, p, None, 3, 0.0, flags, spots=spots, **kw)
@@ -130,7 +84,7 @@ def test_checker_matches_float64_restatement():
     recovered from its radiance, is the float64 restatement's within 2e-3 relative (+1e-5 absolute)."""
     W, H = 64, 48
     _, p, c, pcb = _cpu(W, H)
-    sl = spot_lib.load()
+    sl = local_light_lib.load()
     spots = spots_for_test()
     assert sorted({s.SpotPower for s in spots}) == [1.0, 8.0, 64.0, 200.0]
     _, lit = sl.checker(pcb, p, None, 0, 0.0, 0, spots=spots)
@@ -179,7 +133,7 @@ def test_spot_kernel_body_matches_checker(built_lib, W, H):
     """The product's kernel body (light_core.hpp light_pixel with pbr_point_light then pbr_spot_light) on the host equals the
     checker bit for bit, mixed point and spot lists, with and without the Q fixes."""
     pl, p, c, pcb = _cpu(W, H)
-    sl = spot_lib.load()
+    sl = local_light_lib.load()
     points, spots = points_for_test(), spots_for_test()
     for fixes, ndl, radius in ((0, 1, 0.0), (FIX_ALL, 3, 0.01)):
         got, grad = sl.host(c.pass_cb, p, None, ndl, radius, fixes | 1, points=points, spots=spots)
@@ -190,23 +144,6 @@ def test_spot_kernel_body_matches_checker(built_lib, W, H):
 
 
 # ---- GPU tier -------------------------------------------------------------------------------------------------------------
-
-def _device_scene(ctx, W, H, SD=256, CD=32):
-    import torch
-    pl = scene_util.cpu_scene(W, H, SD, CD)
-    p = scene_util.np_planes(pl)
-    dev = {k: torch.from_numpy(np.ascontiguousarray(v).view(np.int32) if v.dtype == np.uint32 else np.ascontiguousarray(v)).to(ctx.device)
-           for k, v in p.items()}
-    return pl, p, dev
-
-
-def _dev_lights(ctx, lights):
-    import torch
-    if lights is None:
-        return None, 0
-    t = torch.from_numpy(np.frombuffer(bytes(lights), np.uint8).copy()).to(ctx.device)
-    return t, len(lights)
-
 
 def _light_spots(built_lib, ctx, c, dev, W, H, ambient, ndl, radius, flags, points, spots, row0=0, rows=None, out=None, rad=None,
                  cube=None, cube_dim=32):
@@ -239,7 +176,7 @@ def test_deferred_light_spots_on_device(built_lib, oracle, W, H):
     scb = oracle_lib.as_oracle_cb(c.ssao_cb, oracle_lib.OrSsaoConstants)
     ao = oracle.compute_ssao(scb, p["normal"], p["depth"], p["randvec"], 2)
     ao_dev = torch.from_numpy(ao.view(np.int16)).to(ctx.device)
-    sl = spot_lib.load()
+    sl = local_light_lib.load()
     points, spots = points_for_test(), spots_for_test()
     dp, ds = _dev_lights(ctx, points), _dev_lights(ctx, spots)
     cases = 0
@@ -281,24 +218,17 @@ def test_deferred_light_spots_cube_chain_row_ranges(built_lib, oracle):
     for r0, rn in ((0, 36), (36, 50), (86, 34)):
         built_lib.check(_light_spots(built_lib, ctx, c, dev, W, H, None, 3, 0.0, flags, dp, ds, r0, rn, out, rad, chain_dev)[0])
     torch.cuda.synchronize()
-    ref, rref = spot_lib.load().checker(pcb, dict(p, cube=chain), None, 3, 0.0, flags, points=points, spots=spots, cube_dim=32)
+    ref, rref = local_light_lib.load().checker(pcb, dict(p, cube=chain), None, 3, 0.0, flags, points=points, spots=spots, cube_dim=32)
     assert np.array_equal(out.cpu().numpy(), ref)
     assert np.array_equal(rad.cpu().numpy().view(np.uint32), rref.view(np.uint32))
     # spots alone through the chain
     rc, out1, _ = _light_spots(built_lib, ctx, c, dev, W, H, None, 1, 0.0, flags, (None, 0), ds, cube=chain_dev)
     built_lib.check(rc)
     torch.cuda.synchronize()
-    ref1, _ = spot_lib.load().checker(pcb, dict(p, cube=chain), None, 1, 0.0, flags, spots=spots, cube_dim=32)
+    ref1, _ = local_light_lib.load().checker(pcb, dict(p, cube=chain), None, 1, 0.0, flags, spots=spots, cube_dim=32)
     assert np.array_equal(out1.cpu().numpy(), ref1)
     ctx.close()
 
-
-def _app(ctx, W, H, dev, c, blur=3, ndl=3):
-    from crychic_renderer_amd import Crychic, LIGHT_SKY
-    app = Crychic(ctx, W, H, dev["randvec"], dev["cube"], shadow_dim=256)
-    app.load_scene({**dev, "consts": c})
-    app.blurCount, app.numDirLights, app.flags = blur, ndl, LIGHT_SKY
-    return app
 
 
 @pytest.mark.gpu
@@ -322,7 +252,7 @@ def test_hot_path_spots_whole_strips_and_shared(built_lib, oracle):
     full = app.mBackBuffer.cpu().numpy().copy()
     ao = oracle.compute_ssao(scb, p["normal"], p["depth"], p["randvec"], 3)
     assert np.array_equal(app.mSsao.mAmbientMap0.cpu().numpy().view(np.uint16), ao)
-    ref, _ = spot_lib.load().checker(pcb, p, ao, 3, app.pcfSearchRadius, 1, points=points, spots=spots)
+    ref, _ = local_light_lib.load().checker(pcb, p, ao, 3, app.pcfSearchRadius, 1, points=points, spots=spots)
     assert np.array_equal(full, ref)
     # strips
     app.mBackBuffer.zero_()
@@ -426,28 +356,14 @@ def test_spot_argument_errors(built_lib):
 
 @pytest.mark.gpu
 def test_veneer_set_local_lights(built_lib, tmp_path):
-    """tests/cpp/spot_driver.cpp renders through CRYCHIC::SetLocalLights; its frame equals the Python path's frame with the same
-    planes and lights (and SetLocalLights(nullptr, 0, nullptr, 0) gives back the frame without local lights)."""
-    import subprocess
+    """tests/cpp/local_lights_driver.cpp renders through CRYCHIC::SetLocalLights; its frame equals the Python path's frame with the
+    same planes and lights (and SetLocalLights(nullptr, 0, nullptr, 0) gives back the frame without local lights)."""
     import torch
-    import test_cpp_veneer
     from crychic_renderer_amd import Context
-    exe = test_cpp_veneer.build_driver("spot_driver")
-    W, H, SD, CD, BC, NL = 128, 96, 256, 32, 3, 3
-    pl = scene_util.cpu_scene(W, H, SD, CD)
-    p = scene_util.np_planes(pl)
+    from local_lights_util import DRIVER_FRAME as F
+    W, H, SD, CD, BC, NL = F["W"], F["H"], F["SD"], F["CD"], F["BC"], F["NL"]
     d = str(tmp_path)
-    p["depth"].tofile(d + "/depth.bin"); p["normal"].tofile(d + "/normal.bin"); p["cube"].tofile(d + "/cube.bin")
-    for i in range(3):
-        p["g%d" % i].tofile(d + "/g%d.bin" % i)
-    for i in range(4):
-        p["shadow"][i].tofile(d + "/shadow%d.bin" % i)
-    points, spots = points_for_test(), spots_for_test()
-    open(d + "/points.bin", "wb").write(bytes(points))
-    open(d + "/spots.bin", "wb").write(bytes(spots))
-    r = subprocess.run([exe, d, str(W), str(H), str(SD), str(CD), str(BC), str(NL)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "spot driver ok" in r.stdout
+    pl, _, points, spots, _ = run_local_lights_driver(d)
     out = np.fromfile(d + "/out.bin", dtype=np.uint8).reshape(H, W, 4)
     out0 = np.fromfile(d + "/out_nolights.bin", dtype=np.uint8).reshape(H, W, 4)
     ctx = Context(0)

@@ -1,19 +1,18 @@
 """Shadowed spot lights (extension, include/crychic_hip.h crychic_deferred_light_spots_shadowed): the reference declares
 gShadowMap[12] / gShadowTransforms[12] with slots 4..11 unused and leaves the spot branch's shadow factor commented out
-(PBR.hlsl:145), so parity is against this repo's checker (tests/spot_shadow_ref/spot_shadow_ref.c, the frozen oracle's
-or_light.c with the spot loop and a 9-tap CalcShadowFactor per light).  The checker is anchored to tests/spot_ref (count 0 and
-the s = 1 transform) and to a float64 restatement of the factor."""
+(PBR.hlsl:145), so parity is against this repo's checker (tests/local_light_ref/local_light_ref.c, the frozen oracle's
+or_light.c with the spot loop and a 9-tap CalcShadowFactor per light).  The checker is anchored to its own unshadowed frame (the
+s = 1 transform), whose anchors are in tests/test_spot_lights.py, and to a float64 restatement of the factor."""
 import ctypes as C
 import math
 
 import numpy as np
 import pytest
 
+import local_light_lib
 import oracle_lib
-import scene_util
-import spot_lib
-import spot_shadow_lib
-from test_spot_lights import FIX_ALL, light_array, points_for_test, spots_for_test
+from local_lights_util import (FIX_ALL, _app, _cpu, _dev_lights, _device_scene, light_array, points_for_test, random_maps,
+                               spot_transforms, spots_for_test, transposed, with_transforms)
 
 CENTRE_T = np.zeros(16, np.float32)                       # every position -> map centre (0.5, 0.5) at depth 0: s = 1
 CENTRE_T[3], CENTRE_T[7], CENTRE_T[15] = 0.5, 0.5, 1.0
@@ -21,49 +20,8 @@ FAR_T = CENTRE_T.copy()                                   # ... at depth 2: ever
 FAR_T[11] = 2.0
 
 
-def _cpu(W, H):
-    pl = scene_util.cpu_scene(W, H, 256, 32)
-    return pl, scene_util.np_planes(pl), pl["consts"]
-
-
-def spot_transforms(spots, count, fov_y=0.5 * math.pi, z_near=0.5):
-    """The product's crychic_update_spot_shadow_transform of the first `count` lights: (views, projs, transforms), untransposed."""
-    from crychic_renderer_amd import lib
-    out = []
-    for k in range(count):
-        lv, lp, st = ((C.c_float * 16)() for _ in range(3))
-        assert lib.crychic_update_spot_shadow_transform(C.byref(spots[k]), fov_y, z_near, lv, lp, st) == 0
-        out.append(tuple(np.asarray(m[:], np.float32).reshape(4, 4) for m in (lv, lp, st)))
-    return out
-
-
-def with_transforms(pass_cb, Ts):
-    """Copies of the product's pass constants (and the oracle's view of them) with ShadowTransforms[4 + k] = Ts[k] (stored
-    transposed: Ts are given as 16 floats already in that layout)."""
-    from crychic_renderer_amd._lib import PassConstants
-    cb = PassConstants.from_buffer_copy(pass_cb)
-    for k, T in enumerate(Ts):
-        cb.ShadowTransforms[4 + k][:] = [float(v) for v in np.asarray(T, np.float32).reshape(-1)]
-    return cb, oracle_lib.as_oracle_cb(cb, oracle_lib.OrPassConstants)
-
-
-def transposed(st):
-    return st.T.reshape(-1).copy()
-
-
-def random_maps(count, dim, seed):
-    """D24 maps with occluders: depths in [0.85, 1) with square blocks at 1 (lit) and at 0.5 (occluders in front)."""
-    rng = np.random.default_rng(seed)
-    m = (rng.uniform(0.85, 1.0, (count, dim, dim)) * 16777215.0).astype(np.uint32)
-    for k in range(count):
-        for _ in range(6):
-            x, y, s = rng.integers(0, dim, 3)
-            m[k, y:y + s // 3 + 1, x:x + s // 3 + 1] = rng.choice([0x00FFFFFF, 0x007FFFFF])
-    return m | (rng.integers(0, 256, m.shape, dtype=np.uint32) << 24)          # the X8 byte is ignored
-
-
 def _frame_setup(W, H, count, dim=64, seed=1):
-    pl, p, c = _cpu(W, H)
+    pl, p, c, _ = _cpu(W, H)
     spots = spots_for_test()
     T = [transposed(st) for _, _, st in spot_transforms(spots, count)]
     cb, pcb = with_transforms(c.pass_cb, T)
@@ -73,19 +31,17 @@ def _frame_setup(W, H, count, dim=64, seed=1):
 # ---- CPU tier: the checker's anchors -----------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("fixes", [0, FIX_ALL])
-def test_checker_count_zero_and_unit_transform_are_spot_ref(fixes):
-    """count 0, and a transform that sends every position to the map centre at depth 0 (s = 1 exactly), give tests/spot_ref's
-    frame bit for bit."""
+def test_checker_unit_transform_is_the_unshadowed_frame(fixes):
+    """Eight maps with a transform that sends every position to the map centre at depth 0 (s = 1 exactly) give the frame without
+    maps bit for bit."""
     W, H = 96, 64
-    _, p, c = _cpu(W, H)
+    _, p, c, _ = _cpu(W, H)
     spots, points = spots_for_test(), points_for_test()
-    sl, ssl = spot_lib.load(), spot_shadow_lib.load()
+    ll = local_light_lib.load()
     cb, pcb = with_transforms(c.pass_cb, [CENTRE_T] * 8)
-    ref, rref = sl.checker(pcb, p, None, 3, 0.0, 1 | fixes, points=points, spots=spots)
-    got, grad = ssl.checker(pcb, p, None, 3, 0.0, 1 | fixes, points=points, spots=spots)
-    assert np.array_equal(got, ref) and np.array_equal(grad.view(np.uint32), rref.view(np.uint32))
+    ref, rref = ll.checker(pcb, p, None, 3, 0.0, 1 | fixes, points=points, spots=spots)
     maps = random_maps(8, 32, 3)
-    got, grad = ssl.checker(pcb, p, None, 3, 0.0, 1 | fixes, points=points, spots=spots, maps=maps)
+    got, grad = ll.checker(pcb, p, None, 3, 0.0, 1 | fixes, points=points, spots=spots, maps=maps)
     assert np.array_equal(got, ref) and np.array_equal(grad.view(np.uint32), rref.view(np.uint32))
 
 
@@ -115,7 +71,7 @@ def test_checker_factor_matches_float64_restatement():
     """Random maps, perspective transforms and positions inside the light frusta: the checker's 9-tap factor is the float64
     CalcShadowFactor within 1e-5, and the product body's factor equals the checker's bit for bit."""
     rng = np.random.default_rng(7)
-    ssl = spot_shadow_lib.load()
+    ssl = local_light_lib.load()
     spots = spots_for_test()
     n, diffs = 0, []
     for k, (_, _, st) in enumerate(spot_transforms(spots, 8)):
@@ -144,7 +100,7 @@ def test_checker_factor_matches_float64_restatement():
 def test_factor_specials():
     """s == 1 at depth 0 and s == 0 at depth 2 for any map; a non-finite position addresses border texels only (s = 0: border
     0 fails LESS_EQUAL against a positive depth, and NaN fails it); positions behind the light are taken literally."""
-    ssl = spot_shadow_lib.load()
+    ssl = local_light_lib.load()
     m = random_maps(1, 32, 5)[0]
     for pos in ((1.0, 2.0, 3.0), (-7.5, 0.25, 40.0)):
         for which in ("ref", "host"):
@@ -177,7 +133,7 @@ def test_shadowed_kernel_body_matches_checker(built_lib, chain, count):
         cube, levels = g.cube_mip_chain(p["cube"])
         p = dict(p, cube=cube)
         kw, extra = dict(cube_dim=32), (levels & 15) << 16
-    ssl = spot_shadow_lib.load()
+    ssl = local_light_lib.load()
     points = points_for_test()
     for fixes, ndl, radius in ((0, 1, 0.0), (FIX_ALL, 3, 0.01)):
         flags = fixes | 1 | extra
@@ -250,20 +206,6 @@ def test_spot_shadow_transform_argument_errors(built_lib):
 
 # ---- GPU tier ---------------------------------------------------------------------------------------------------------------
 
-def _device_scene(ctx, W, H, SD=256, CD=32):
-    import torch
-    pl = scene_util.cpu_scene(W, H, SD, CD)
-    p = scene_util.np_planes(pl)
-    dev = {k: torch.from_numpy(np.ascontiguousarray(v).view(np.int32) if v.dtype == np.uint32 else np.ascontiguousarray(v)).to(ctx.device)
-           for k, v in p.items()}
-    return pl, p, dev
-
-
-def _dev_lights(ctx, lights):
-    import torch
-    if lights is None:
-        return None, 0
-    return torch.from_numpy(np.frombuffer(bytes(lights), np.uint8).copy()).to(ctx.device), len(lights)
 
 
 def _desc(dev_maps, count=None):
@@ -305,7 +247,7 @@ def test_deferred_light_spots_shadowed_on_device(built_lib, W, H):
     from crychic_renderer_amd import Context
     ctx = Context(0)
     pl, p, dev = _device_scene(ctx, W, H)
-    ssl = spot_shadow_lib.load()
+    ssl = local_light_lib.load()
     points, spots = points_for_test(), spots_for_test()
     dp, ds = _dev_lights(ctx, points), _dev_lights(ctx, spots)
     rng = np.random.default_rng(11)
@@ -356,7 +298,7 @@ def test_shadowed_cube_chain_row_ranges(built_lib):
         built_lib.check(_light(built_lib.lib, ctx, cb, dev, W, H, flags, (None, 0), ds, _desc(mdev), row0=r0, rows=rn, out=out, rad=rad,
                                cube=chain_dev)[0])
     torch.cuda.synchronize()
-    ref, rref = spot_shadow_lib.load().checker(pcb, dict(p, cube=chain), None, 3, 0.0, flags, spots=spots, maps=maps, cube_dim=32)
+    ref, rref = local_light_lib.load().checker(pcb, dict(p, cube=chain), None, 3, 0.0, flags, spots=spots, maps=maps, cube_dim=32)
     assert np.array_equal(out.cpu().numpy(), ref)
     assert np.array_equal(rad.cpu().numpy().view(np.uint32), rref.view(np.uint32))
     ctx.close()
@@ -401,13 +343,6 @@ def test_shadowed_identities(built_lib):
     ctx.close()
 
 
-def _app(ctx, W, H, dev, c, blur=3, ndl=3):
-    from crychic_renderer_amd import Crychic, LIGHT_SKY
-    app = Crychic(ctx, W, H, dev["randvec"], dev["cube"], shadow_dim=256)
-    app.load_scene({**dev, "consts": c})
-    app.blurCount, app.numDirLights, app.flags = blur, ndl, LIGHT_SKY
-    return app
-
 
 @pytest.mark.gpu
 def test_hot_path_spots_shadowed_whole_strips_and_shared(built_lib, oracle):
@@ -434,7 +369,7 @@ def test_hot_path_spots_shadowed_whole_strips_and_shared(built_lib, oracle):
     ao = oracle.compute_ssao(scb, p["normal"], p["depth"], p["randvec"], 3)
     T = [transposed(st) for _, _, st in spot_transforms(spots, 3)]
     _, pcb = with_transforms(c.pass_cb, T)
-    ref, _ = spot_shadow_lib.load().checker(pcb, p, ao, 3, app.pcfSearchRadius, 1, points=points, spots=spots, maps=maps)
+    ref, _ = local_light_lib.load().checker(pcb, p, ao, 3, app.pcfSearchRadius, 1, points=points, spots=spots, maps=maps)
     assert np.array_equal(full, ref)
     app.mBackBuffer.zero_()
     for rank in range(3):
@@ -611,7 +546,7 @@ def test_reference_scene_shadowed_spot_end_to_end(built_lib, oracle):
     ao = app.mSsao.mAmbientMap0.cpu().numpy().view(np.uint16)
     T = [transposed(st) for _, _, st in spot_transforms(lights, 1)]
     _, pcb = with_transforms(consts.pass_cb, T)
-    ssl = spot_shadow_lib.load()
+    ssl = local_light_lib.load()
     ref, lit1 = ssl.checker(pcb, p, ao, 1, app.pcfSearchRadius, 1, spots=lights, maps=maps)
     assert np.array_equal(rad[1], ref)
     _, lit0 = ssl.checker(pcb, p, ao, 1, app.pcfSearchRadius, 1, spots=lights)
