@@ -69,6 +69,11 @@ class SpotShadows(C.Structure):
     _fields_ = [("count", C.c_uint32), ("dim", C.c_uint32), ("maps", C.c_void_p * 8)]
 
 
+class PointShadows(C.Structure):
+    """crychic_point_shadows: the first `count` point lights read the six faces at maps[k] through shadowProj[k] (extension)."""
+    _fields_ = [("count", C.c_uint32), ("dim", C.c_uint32), ("maps", C.c_void_p * 4), ("shadowProj", (C.c_float * 16) * 4)]
+
+
 class PassTimes(C.Structure):
     _fields_ = [("ssao_ms", C.c_float), ("blur_ms", C.c_float), ("light_ms", C.c_float), ("total_ms", C.c_float)]
 
@@ -91,6 +96,7 @@ PROTOTYPES = {
     "crychic_build_random_vector_texture": (None, [_P(_u32), _i, _vp]),
     "crychic_update_cascade_shadow_transform": (_i, [_P(Camera), _P(_f), _u32, _vp, _vp, _vp]),
     "crychic_update_spot_shadow_transform": (_i, [_P(Light), _f, _f, _vp, _vp, _vp]),
+    "crychic_update_point_shadow_transforms": (_i, [_P(Light), _u32, _f, _vp, _vp, _vp]),
     "crychic_update_main_pass_cb": (_i, [_P(Camera), _u32, _u32, _vp, _vp, _P(PassConstants)]),
     "crychic_update_ssao_cb": (_i, [_P(Camera), _u32, _u32, _vp, _P(SsaoConstants)]),
     "crychic_pcf_search_radius": (_f, [_u32, _i]),
@@ -113,6 +119,11 @@ PROTOTYPES = {
                                                    _vp]),
     "crychic_draw_hot_path_spots_shadowed": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _vp, _u32,
                                                   _P(SpotShadows), _vp]),
+    "crychic_deferred_light_point_shadows": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _P(_vp), _u32, _vp, _u32, _vp,
+                                                  _vp, _u32, _u32, _u32, _u32, _i, _f, _u32, _vp, _u32, _vp, _u32, _P(SpotShadows),
+                                                  _P(PointShadows), _vp]),
+    "crychic_draw_hot_path_point_shadows": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _vp, _u32,
+                                                 _P(SpotShadows), _P(PointShadows), _vp]),
     "crychic_frustum_cull": (_i, [_P(Camera), _P(_f), _P(_f), _vp, _u32, _vp]),
     "crychic_ctx_set_profiling": (_i, [_vp, _i]),
     "crychic_ctx_last_pass_times": (_i, [_vp, _P(PassTimes)]),
@@ -133,6 +144,8 @@ PROTOTYPES = {
                                                 _vp]),
     "crychic_draw_hot_path_shared_spots_shadowed": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _P(_u32), _u32,
                                                          _vp, _u32, _P(SpotShadows), _vp]),
+    "crychic_draw_hot_path_shared_point_shadows": (_i, [_vp, _P(SsaoConstants), _P(PassConstants), _P(FrameDesc), _P(_u32), _u32,
+                                                        _vp, _u32, _P(SpotShadows), _P(PointShadows), _vp]),
     "crychic_create_box": (_i, [_f, _f, _f, _u32, _vp, _u32, _vp, _u32, _P(_u32)]),
     "crychic_create_grid": (_i, [_f, _f, _u32, _u32, _vp, _u32, _vp, _u32, _P(_u32)]),
     "crychic_load_mesh_text": (_i, [C.c_char_p, _vp, _u32, _vp, _u32, _P(_u32), _P(_u32)]),

@@ -164,11 +164,9 @@ int fill_light_params(cry::LightParams& P, const crychic_pass_constants* cb, con
     return 0;
 }
 
-// The local lights of one lighting pass (every crychic_deferred_light* entry and the hot paths): at most 1024 point and 1024 spot
-// lights, each from a device buffer when there are any, into P; the descriptor's first `count` maps and ShadowTransforms[4 + k]
-// into S.  A NULL descriptor or count 0 leaves S.count = 0: the unshadowed kernels.  Touches neither P's other fields nor cb.
-int bind_local_lights(cry::LightParams& P, cry::SpotShadows& S, const crychic_pass_constants* cb, const crychic_light* points,
-                      uint32_t nPoints, const crychic_light* spots, uint32_t nSpots, const crychic_spot_shadows* d)
+// bind_local_lights' point and spot lights and spot shadows.
+int bind_spot_lights(cry::LightParams& P, cry::SpotShadows& S, const crychic_pass_constants* cb, const crychic_light* points,
+                     uint32_t nPoints, const crychic_light* spots, uint32_t nSpots, const crychic_spot_shadows* d)
 {
     if (nPoints > cry::kMaxPointLights || (nPoints && !points))
         return fail(CRYCHIC_E_INVALID_ARG, "numPointLights %u (max %u) / null light buffer", nPoints, cry::kMaxPointLights);
@@ -194,6 +192,35 @@ int bind_local_lights(cry::LightParams& P, cry::SpotShadows& S, const crychic_pa
     return 0;
 }
 
+// The local lights of one lighting pass (every crychic_deferred_light* entry and the hot paths): at most 1024 point and 1024 spot
+// lights, each from a device buffer when there are any, into P; the descriptor's first `count` maps and ShadowTransforms[4 + k]
+// into S; the point descriptor's first `count` maps and transposed shadowProj into PS.  A NULL descriptor or count 0 leaves
+// S.count = 0 / PS.count = 0: the kernels without those shadows.  Touches neither P's other fields nor cb.
+int bind_local_lights(cry::LightParams& P, cry::SpotShadows& S, cry::PointShadows& PS, const crychic_pass_constants* cb,
+                      const crychic_light* points, uint32_t nPoints, const crychic_light* spots, uint32_t nSpots,
+                      const crychic_spot_shadows* d, const crychic_point_shadows* pd)
+{
+    if (int rc = bind_spot_lights(P, S, cb, points, nPoints, spots, nSpots, d)) return rc;
+    std::memset(&PS, 0, sizeof PS);
+    if (!pd || pd->count == 0) return 0;
+    if (pd->count > CRYCHIC_MAX_POINT_SHADOWS || pd->count > nPoints)
+        return fail(CRYCHIC_E_INVALID_ARG, "point shadows: count %u (max %u, and at most numPointLights %u)", pd->count,
+                    (unsigned)CRYCHIC_MAX_POINT_SHADOWS, nPoints);
+    if (pd->dim < CRYCHIC_MIN_POINT_SHADOW_DIM || pd->dim > CRYCHIC_MAX_SPOT_SHADOW_DIM)     // the widened faces need 2 texels of rim
+        return fail(CRYCHIC_E_INVALID_ARG, "point shadows: dim %u (%u .. %u)", pd->dim, (unsigned)CRYCHIC_MIN_POINT_SHADOW_DIM,
+                    (unsigned)CRYCHIC_MAX_SPOT_SHADOW_DIM);
+    for (uint32_t k = 0; k < pd->count; ++k) {
+        if (!pd->maps[k]) return fail(CRYCHIC_E_INVALID_ARG, "point shadows: null map %u of %u", k, pd->count);
+        PS.maps[k] = pd->maps[k];
+        for (int i = 0; i < 4; ++i)                        // transposed: row i of M = column i of shadowProj (as the spot T)
+            for (int j = 0; j < 4; ++j) PS.M[k][4 * i + j] = pd->shadowProj[k][4 * j + i];
+    }
+    PS.count = pd->count;
+    PS.dim = pd->dim;
+    PS.dx = 1.0f / (float)pd->dim;                     // IEEE division on the host: correctly rounded
+    return 0;
+}
+
 // With a mip chain the level of detail comes from 2 x 2 pixel quads: a call's rows have to be whole quad rows.
 int check_chain_rows(const cry::LightParams& P, uint32_t row0, uint32_t rows, uint32_t H)
 {
@@ -208,7 +235,7 @@ int deferred_light_impl(crychic_ctx* ctx, const crychic_pass_constants* cb, cons
                         const uint8_t* cube_dev, uint32_t cubeDim, uint8_t* out_rgba8_dev, float* radiance_out_dev, uint32_t W, uint32_t H,
                         uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags, const crychic_light* point_lights_dev,
                         uint32_t numPointLights, const crychic_light* spot_lights_dev, uint32_t numSpotLights,
-                        const crychic_spot_shadows* spotShadows, void* stream)
+                        const crychic_spot_shadows* spotShadows, const crychic_point_shadows* pointShadows, void* stream)
 {
     if (int rc = bind(ctx)) return rc;
     if (int rc = check_dims(W, H)) return rc;
@@ -217,11 +244,13 @@ int deferred_light_impl(crychic_ctx* ctx, const crychic_pass_constants* cb, cons
     if (row0 > H || rows > H - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row frame", row0, rows, H);
     cry::LightParams P;
     cry::SpotShadows S;
-    if (int rc = bind_local_lights(P, S, cb, point_lights_dev, numPointLights, spot_lights_dev, numSpotLights, spotShadows)) return rc;
+    cry::PointShadows PS;
+    if (int rc = bind_local_lights(P, S, PS, cb, point_lights_dev, numPointLights, spot_lights_dev, numSpotLights, spotShadows,
+                                   pointShadows)) return rc;
     if (int rc = fill_light_params(P, cb, shadow_dev, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags)) return rc;
     if (int rc = check_chain_rows(P, row0, rows, H)) return rc;
     CRY_HIP(cry::launch_light(P, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, cube_dev, out_rgba8_dev, radiance_out_dev,
-                              row0, rows, (hipStream_t)stream, spot_lights_dev, numSpotLights, &S));
+                              row0, rows, (hipStream_t)stream, spot_lights_dev, numSpotLights, &S, &PS));
     return 0;
 }
 
@@ -336,7 +365,7 @@ int crychic_deferred_light(crychic_ctx* ctx, const crychic_pass_constants* cb, c
                            void* stream)
 {
     return deferred_light_impl(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev, cubeDim, out_rgba8_dev,
-                               radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags, nullptr, 0u, nullptr, 0u, nullptr, stream);
+                               radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags, nullptr, 0u, nullptr, 0u, nullptr, nullptr, stream);
 }
 
 int crychic_deferred_light_points(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev,
@@ -348,7 +377,7 @@ int crychic_deferred_light_points(crychic_ctx* ctx, const crychic_pass_constants
 {
     return deferred_light_impl(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev, cubeDim, out_rgba8_dev,
                                radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags, point_lights_dev, numPointLights,
-                               nullptr, 0u, nullptr, stream);
+                               nullptr, 0u, nullptr, nullptr, stream);
 }
 
 int crychic_deferred_light_spots(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev,
@@ -361,7 +390,7 @@ int crychic_deferred_light_spots(crychic_ctx* ctx, const crychic_pass_constants*
 {
     return deferred_light_impl(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev, cubeDim, out_rgba8_dev,
                                radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags, point_lights_dev, numPointLights,
-                               spot_lights_dev, numSpotLights, nullptr, stream);
+                               spot_lights_dev, numSpotLights, nullptr, nullptr, stream);
 }
 
 int crychic_deferred_light_spots_shadowed(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev,
@@ -375,7 +404,21 @@ int crychic_deferred_light_spots_shadowed(crychic_ctx* ctx, const crychic_pass_c
 {
     return deferred_light_impl(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev, cubeDim, out_rgba8_dev,
                                radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags, point_lights_dev, numPointLights,
-                               spot_lights_dev, numSpotLights, spotShadows, stream);
+                               spot_lights_dev, numSpotLights, spotShadows, nullptr, stream);
+}
+
+int crychic_deferred_light_point_shadows(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev,
+                                         const float* g2_dev, const uint32_t* depth_dev, const uint16_t* ambient_dev,
+                                         const uint32_t* const shadow_dev[4], uint32_t shadowDim, const uint8_t* cube_dev,
+                                         uint32_t cubeDim, uint8_t* out_rgba8_dev, float* radiance_out_dev, uint32_t W, uint32_t H,
+                                         uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags,
+                                         const crychic_light* point_lights_dev, uint32_t numPointLights,
+                                         const crychic_light* spot_lights_dev, uint32_t numSpotLights,
+                                         const crychic_spot_shadows* spotShadows, const crychic_point_shadows* pointShadows, void* stream)
+{
+    return deferred_light_impl(ctx, cb, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, shadow_dev, shadowDim, cube_dev, cubeDim, out_rgba8_dev,
+                               radiance_out_dev, W, H, row0, rows, numDirLights, pcfSearchRadius, flags, point_lights_dev, numPointLights,
+                               spot_lights_dev, numSpotLights, spotShadows, pointShadows, stream);
 }
 
 }  // extern "C"
@@ -402,7 +445,9 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
     if (int rc = fill_light_params(P, passCB, f->shadow_dev, f->shadowDim, f->cubeDim, W, H, f->numDirLights,
                                    f->pcfSearchRadius, f->flags)) return rc;
     cry::SpotShadows S;
-    if (int rc = bind_local_lights(P, S, passCB, f->point_lights_dev, f->numPointLights, spots.lights, spots.count, spots.shadows)) return rc;
+    cry::PointShadows PS;
+    if (int rc = bind_local_lights(P, S, PS, passCB, f->point_lights_dev, f->numPointLights, spots.lights, spots.count, spots.shadows,
+                                   spots.pointShadows)) return rc;
     const bool prof = ctx->profiling;
     if (prof) { ctx->times_valid = false; CRY_HIP(hipEventRecord(ctx->ev[0], stream)); }
     if (ssaoOn) {
@@ -424,7 +469,7 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
         const uint32_t r1 = (p + 1u == nparts) ? f->row0 + f->rows : r0 + 2u * per;
         if (r1 > r0)
             CRY_HIP(cry::launch_light(P, f->g0_dev, f->g1_dev, f->g2_dev, f->depth_dev, ssaoOn ? f->ambient0_dev : nullptr,
-                                      f->cube_dev, f->out_rgba8_dev, nullptr, r0, r1 - r0, stream, spots.lights, spots.count, &S));
+                                      f->cube_dev, f->out_rgba8_dev, nullptr, r0, r1 - r0, stream, spots.lights, spots.count, &S, &PS));
         if (prof && p + 1u == nparts) { CRY_HIP(hipEventRecord(ctx->ev[3], stream)); ctx->times_valid = true; }
         if (after)
             if (int rc = after(user, p, r0, r1 - r0)) return rc;
@@ -451,6 +496,14 @@ int crychic_draw_hot_path_spots_shadowed(crychic_ctx* ctx, const crychic_ssao_co
                                          const crychic_spot_shadows* spotShadows, void* stream)
 {
     return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr, { spot_lights_dev, numSpotLights, spotShadows });
+}
+
+int crychic_draw_hot_path_point_shadows(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
+                                        const crychic_frame_desc* f, const crychic_light* spot_lights_dev, uint32_t numSpotLights,
+                                        const crychic_spot_shadows* spotShadows, const crychic_point_shadows* pointShadows, void* stream)
+{
+    return cry::hot_path_parts(ctx, ssaoCB, passCB, f, (hipStream_t)stream, 1u, nullptr, nullptr,
+                               { spot_lights_dev, numSpotLights, spotShadows, pointShadows });
 }
 
 int crychic_ctx_set_profiling(crychic_ctx* ctx, int enabled)

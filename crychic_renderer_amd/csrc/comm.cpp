@@ -431,6 +431,15 @@ int crychic_draw_hot_path_shared_spots_shadowed(crychic_comm* c, const crychic_s
     return draw_shared(c, ssaoCB, passCB, f, bounds, nparts, stream, { spot_lights_dev, numSpotLights, spotShadows });
 }
 
+int crychic_draw_hot_path_shared_point_shadows(crychic_comm* c, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
+                                               const crychic_frame_desc* f, const uint32_t* bounds, uint32_t nparts,
+                                               const crychic_light* spot_lights_dev, uint32_t numSpotLights,
+                                               const crychic_spot_shadows* spotShadows, const crychic_point_shadows* pointShadows,
+                                               void* stream)
+{
+    return draw_shared(c, ssaoCB, passCB, f, bounds, nparts, stream, { spot_lights_dev, numSpotLights, spotShadows, pointShadows });
+}
+
 int crychic_comm_barrier(crychic_comm* c, void* stream)
 {
     if (!c || !c->nccl) return fail(CRYCHIC_E_INVALID_ARG, "null or aborted communicator");

@@ -92,10 +92,10 @@ Mat4 perspective_fov_lh(float fovY, float aspect, float zn, float zf)
     r.m[3][2] = -range * zn;
     return r;
 }
-// XMMatrixLookAtLH (CRYCHIC.cpp:734)
-Mat4 look_at_lh(V3 eye, V3 at, V3 up)
+// XMMatrixLookToLH: the look-at basis for a direction
+Mat4 look_to_lh(V3 eye, V3 dir, V3 up)
 {
-    const V3 zaxis = normalize(at - eye);
+    const V3 zaxis = normalize(dir);
     const V3 xaxis = normalize(cross(up, zaxis));
     const V3 yaxis = cross(zaxis, xaxis);
     Mat4 r = Mat4::zero();
@@ -106,6 +106,8 @@ Mat4 look_at_lh(V3 eye, V3 at, V3 up)
     r.m[3][3] = 1.0f;
     return r;
 }
+// XMMatrixLookAtLH (CRYCHIC.cpp:734): LookToLH along at - eye
+Mat4 look_at_lh(V3 eye, V3 at, V3 up) { return look_to_lh(eye, at - eye, up); }
 // XMMatrixOrthographicOffCenterLH (CRYCHIC.cpp:804)
 Mat4 ortho_off_center_lh(float l, float r_, float b, float t, float zn, float zf)
 {
@@ -291,6 +293,33 @@ int crychic_update_spot_shadow_transform(const crychic_light* L, float fovY, flo
     const Mat4 proj = perspective_fov_lh(fovY, 1.0f, zNear, L->FalloffEnd);
     (view * proj * tex_matrix()).store(shadowTransform);
     view.store(lightView);
+    proj.store(lightProj);
+    return 0;
+}
+
+int crychic_update_point_shadow_transforms(const crychic_light* L, uint32_t dim, float zNear, float lightView[6][16],
+                                           float lightProj[16], float shadowProj[16])
+{
+    if (!L || !lightView || !lightProj || !shadowProj) return CRYCHIC_E_INVALID_ARG;
+    if (dim < CRYCHIC_MIN_POINT_SHADOW_DIM || dim > CRYCHIC_MAX_SPOT_SHADOW_DIM) return CRYCHIC_E_INVALID_ARG;
+    if (!(zNear > 0.0f) || !(zNear < L->FalloffEnd)) return CRYCHIC_E_INVALID_ARG;
+    const V3 pos{ L->Position[0], L->Position[1], L->Position[2] };
+    if (!std::isfinite(pos.x) || !std::isfinite(pos.y) || !std::isfinite(pos.z)) return CRYCHIC_E_INVALID_ARG;
+    // the faces +X, -X, +Y, -Y, +Z, -Z of a D3D cube map: axis and up vector (crychic_hip.h's face table)
+    static const V3 axis[6] = { { 1, 0, 0 }, { -1, 0, 0 }, { 0, 1, 0 }, { 0, -1, 0 }, { 0, 0, 1 }, { 0, 0, -1 } };
+    static const V3 up[6] = { { 0, 1, 0 }, { 0, 1, 0 }, { 0, 0, -1 }, { 0, 0, 1 }, { 0, 1, 0 }, { 0, 1, 0 } };
+    for (int f = 0; f < 6; ++f) look_to_lh(pos, axis[f], up[f]).store(lightView[f]);
+    // PerspectiveFovLH(2 atan(dim / (dim - 4)), 1, zNear, FalloffEnd) with its cot(fovY / 2) taken exactly as (dim - 4) / dim: the
+    // 90-degree region of a face maps to texel coordinates [2, dim - 2], so the 3 x 3 taps' footprints never leave the face
+    const float scale = (float)(dim - 4u) / (float)dim;
+    const float range = L->FalloffEnd / (L->FalloffEnd - zNear);
+    Mat4 proj = Mat4::zero();
+    proj.m[0][0] = scale;
+    proj.m[1][1] = scale;
+    proj.m[2][2] = range;
+    proj.m[2][3] = 1.0f;
+    proj.m[3][2] = -range * zNear;
+    (proj * tex_matrix()).store(shadowProj);
     proj.store(lightProj);
     return 0;
 }

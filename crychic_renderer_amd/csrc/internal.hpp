@@ -19,11 +19,13 @@ namespace cry {
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // The spot lights of a hot path (the point lights ride in crychic_frame_desc): `count` spot lights after the frame's point lights,
-// the first shadows->count of them shadowed.  {} = none; shadows == nullptr = unshadowed.
+// the first shadows->count of them shadowed, and the first pointShadows->count of the frame's point lights shadowed.  {} = none;
+// shadows / pointShadows == nullptr = unshadowed.
 struct SpotLightArgs {
     const crychic_light* lights;
     uint32_t count;
     const crychic_spot_shadows* shadows;
+    const crychic_point_shadows* pointShadows = nullptr;
 };
 
 // api.cpp: crychic_draw_hot_path with the lighting pass in `nparts` row ranges and a hook behind each (comm.cpp's overlapped exchange).

@@ -531,13 +531,17 @@ __global__ __launch_bounds__(256) void light_kernel(LightParams P, const f4a* __
 // outside its cone too (the 0.001 floor of PBR.hlsl:142), so only the range test is exact.
 // SHADOWED (light_spots_shadowed_kernel): spot lights k < shadows->count take their shadow factor (spot_shadow_factor), evaluated
 // only where the term is (in range).  The cull is unchanged: a shadow can only scale a term it already admits.
-template <bool ZERO_RADIUS, bool MIPS, bool SPOTS, bool SHADOWED = false>
+// POINT_SHADOWED (light_point_shadows_kernel): point lights k < pointShadows->count take their cube shadow (PointShadowOf) the same
+// way.  The mask word is read once per wavefront (readfirstlane: every lane reads the same LDS word), so the walk's light index is
+// scalar, and with it the light's projection and map; the face is per lane (point_face's selects).
+template <bool ZERO_RADIUS, bool MIPS, bool SPOTS, bool SHADOWED = false, bool POINT_SHADOWED = false>
 __device__ __forceinline__ void light_local_tile(const LightParams& P, const f4a* __restrict__ g0, const f4a* __restrict__ g1,
                                                  const f4a* __restrict__ g2, const uint32_t* __restrict__ depth,
                                                  const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
                                                  uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0, uint32_t row1,
                                                  float (*s_box)[6], uint32_t* s_mask, const crychic_light* __restrict__ spots,
-                                                 uint32_t numSpots, uint32_t* s_spotMask, const SpotShadows* shadows = nullptr)
+                                                 uint32_t numSpots, uint32_t* s_spotMask, const SpotShadows* shadows = nullptr,
+                                                 const PointShadows* pointShadows = nullptr)
 {
     uint32_t bx, by;
     tile_origin<0>(bx, by);
@@ -612,10 +616,15 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const f4a
             const uint32_t words = (P.numPointLights + 31u) >> 5;
             for (uint32_t w = 0; w < words; ++w) {
                 uint32_t m = s_mask[w];
+                if (POINT_SHADOWED) m = __builtin_amdgcn_readfirstlane(m);
                 while (m) {
                     const uint32_t b = (uint32_t)__builtin_ctz(m);
                     m &= m - 1u;
-                    pbr_point_light(P.pointLights[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
+                    if (POINT_SHADOWED)
+                        pbr_point_light(P.pointLights[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4,
+                                        PointShadowOf{ pointShadows, pos, &P.pointLights[w * 32u + b], w * 32u + b });
+                    else
+                        pbr_point_light(P.pointLights[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
                 }
             }
             if (SPOTS) {
@@ -688,6 +697,27 @@ __global__ __launch_bounds__(256) void light_spots_shadowed_kernel(LightParams P
     light_local_tile<ZERO_RADIUS, MIPS, true, true>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask, spots,
                                                     numSpots, s_spotMask, &shadows);
 }
+
+// The same pass with the first pointShadows.count (1 .. 4) point lights shadowed (crychic_deferred_light_point_shadows), spot lights
+// and their shadows as light_spots_shadowed_kernel: zero spot lights or a spot shadow count of 0 are settled at run time (SpotShadowOf
+// returns 1, the unshadowed bits).  A point shadow count of 0 takes the kernels above, so none of their instantiations changes.
+template <bool ZERO_RADIUS, bool MIPS>
+__global__ __launch_bounds__(256) void light_point_shadows_kernel(LightParams P, const f4a* __restrict__ g0, const f4a* __restrict__ g1,
+                                                                  const f4a* __restrict__ g2, const uint32_t* __restrict__ depth,
+                                                                  const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
+                                                                  uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0,
+                                                                  uint32_t row1, const crychic_light* __restrict__ spots, uint32_t numSpots,
+                                                                  SpotShadows shadows, PointShadows pointShadows)
+{
+    __shared__ float s_box[4][6];
+    __shared__ uint32_t s_mask[kMaxPointLights / 32];
+    __shared__ uint32_t s_spotMask[kMaxSpotLights / 32];
+    light_local_tile<ZERO_RADIUS, MIPS, true, true, true>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask,
+                                                          spots, numSpots, s_spotMask, &shadows, &pointShadows);
+}
+// Its kernel arguments, the largest of any kernel here: the usual HIP limit is 4 KiB.
+static_assert(sizeof(LightParams) + sizeof(SpotShadows) + sizeof(PointShadows) + 9 * sizeof(void*) + 3 * sizeof(uint32_t) <= 4096,
+              "light_point_shadows_kernel's arguments exceed 4 KiB");
 
 // ---- launchers ---------------------------------------------------------------------------------------------------
 // Margin (depth texel rows) of a row-limited depth pass around the rows of the call (ssao_core.hpp depth_pass_cell_rows).  Any value
@@ -842,7 +872,7 @@ hipError_t launch_blur_replay_chain(const crychic_ssao_constants& cb, const void
 hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, const float* g2,
                         const uint32_t* depth, const uint16_t* ambient, const uint8_t* cube, uint8_t* out,
                         float* radiance, uint32_t row0, uint32_t rows, hipStream_t stream, const crychic_light* spots,
-                        uint32_t numSpots, const SpotShadows* shadows)
+                        uint32_t numSpots, const SpotShadows* shadows, const PointShadows* pointShadows)
 {
     if (rows == 0) return hipSuccess;
     const dim3 grid = grid_for(P.W, rows);
@@ -861,6 +891,9 @@ hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, 
     auto dispatch = [&](auto family) {
         return by_radius([&](auto z) { if (mips) family(z, std::true_type{}); else family(z, std::false_type{}); });
     };
+    if (pointShadows && pointShadows->count)
+        return dispatch([&](auto z, auto m) { launch(light_point_shadows_kernel<z, m>, spots, numSpots, shadows ? *shadows : SpotShadows{},
+                                                     *pointShadows); });
     if (numSpots && shadows && shadows->count)
         return dispatch([&](auto z, auto m) { launch(light_spots_shadowed_kernel<z, m>, spots, numSpots, *shadows); });
     if (numSpots)

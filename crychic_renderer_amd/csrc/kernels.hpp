@@ -8,6 +8,7 @@ namespace cry {
 
 struct LightParams;
 struct SpotShadows;
+struct PointShadows;
 
 // D24 depth plane -> the decoded, BORDER-padded pairs plane inside the edge workspace (ssao_core.hpp "depth pairs") and the coarse
 // maps of the SSAO shortcuts, for the SSAO pass over half-res rows [row0, row0 + rows): those rows' texels and a margin (the whole
@@ -43,10 +44,12 @@ hipError_t launch_blur_replay_chain(const crychic_ssao_constants& cb, const void
 
 // spots / numSpots (<= 1024): spot lights after P's point lights (light_spots_kernel); 0 = the point-light or reference kernels.
 // shadows: the first shadows->count spot lights shadowed (light_spots_shadowed_kernel); nullptr or count 0 = none.
+// pointShadows: the first pointShadows->count point lights shadowed (light_point_shadows_kernel, which takes the spot lights and
+// their shadows as well); nullptr or count 0 = the kernels above.
 hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, const float* g2,
                         const uint32_t* depth, const uint16_t* ambient, const uint8_t* cube, uint8_t* out,
                         float* radiance, uint32_t row0, uint32_t rows, hipStream_t stream, const crychic_light* spots,
-                        uint32_t numSpots, const SpotShadows* shadows);
+                        uint32_t numSpots, const SpotShadows* shadows, const PointShadows* pointShadows);
 
 
 // ---- producer passes (raster.hip) ----

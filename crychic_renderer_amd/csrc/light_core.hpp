@@ -313,26 +313,30 @@ CRY_HD void pbr_dir_light(const crychic_light& L, f3 albedo, float roughness, fl
                               view, pow5(shadow), result, fixQ3, fixQ4);
 }
 
+// `shadow()` is a local light's shadow factor, called only when the light is in range (crychic_deferred_light_spots_shadowed,
+// crychic_deferred_light_point_shadows); an unshadowed light passes UnitShadow, whose 1.0f gives the pinned `1.0f * brdf` exactly.
+struct UnitShadow { CRY_HD float operator()() const { return 1.0f; } };
+
 // Point light, BUILD-DEFINED EXTENSION: the reference's branch (PBR.hlsl:109-124) is dead code; enabled as evidently
-// intended -- range test d > FalloffEnd (LightingUtil.hlsl:104-105), l /= d, linear attenuation, shadowFactor 1.
+// intended -- range test d > FalloffEnd (LightingUtil.hlsl:104-105), l /= d, linear attenuation, shadowFactor 1 (or the cube
+// shadow of PointShadowOf).
+template <typename SHADOW = UnitShadow>
 CRY_HD void pbr_point_light(const crychic_light& L, f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view,
-                            f3& result, bool fixQ3 = false, bool fixQ4 = false)
+                            f3& result, bool fixQ3 = false, bool fixQ4 = false, SHADOW shadow = SHADOW())
 {
     const f3 l{ L.Position[0] - pos.x, L.Position[1] - pos.y, L.Position[2] - pos.z };
     const float d = len_from_sq(dot3(l, l));
     if (d > L.FalloffEnd) return;
+    const float s = shadow();
     const float rd = rcp(d);
     const f3 ln{ l.x * rd, l.y * rd, l.z * rd };
     const float att = saturate(divf(L.FalloffEnd - d, L.FalloffEnd - L.FalloffStart));
-    pbr_light<true>(ln, L.Strength, att, albedo, roughness, metalness, normal, view, 1.0f, result, fixQ3, fixQ4);
+    pbr_light<true>(ln, L.Strength, att, albedo, roughness, metalness, normal, view, s, result, fixQ3, fixQ4);
 }
 
 // Spot light, BUILD-DEFINED EXTENSION (crychic_hip.h crychic_deferred_light_spots): the reference's branch (PBR.hlsl:126-147) is
 // dead code as well; enabled like the point light with att *= pow(max(dot(-Direction, l), 0.001), SpotPower) -- det_pow, the
 // general pow, Direction used as given.  SpotPower = 0 makes the factor exactly 1: the point light's bits.
-// `shadow()` is the light's shadow factor, called only when the light is in range (crychic_deferred_light_spots_shadowed);
-// the unshadowed light passes UnitShadow, whose 1.0f gives the pinned `1.0f * brdf` exactly.
-struct UnitShadow { CRY_HD float operator()() const { return 1.0f; } };
 template <typename SHADOW = UnitShadow>
 CRY_HD void pbr_spot_light(const crychic_light& L, f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view,
                            f3& result, bool fixQ3 = false, bool fixQ4 = false, SHADOW shadow = SHADOW())
@@ -383,6 +387,44 @@ CRY_HD float spot_shadow_factor(const uint32_t* __restrict__ map, uint32_t dim, 
 struct SpotShadowOf {
     const SpotShadows* S; f3 pos; uint32_t k;
     CRY_HD float operator()() const { return k < S->count ? spot_shadow_factor(S->maps[k], S->dim, S->dx, S->T[k], pos) : 1.0f; }
+};
+
+// Shadowed point lights, BUILD-DEFINED EXTENSION (crychic_hip.h crychic_deferred_light_point_shadows): point light k < count reads
+// the six faces at maps[k] through ONE projection per light; the face's view transform is an exact permutation of v (point_face).
+constexpr uint32_t kMaxPointShadows = 4;    // CRYCHIC_MAX_POINT_SHADOWS
+struct PointShadows {
+    const uint32_t* maps[kMaxPointShadows]; // six dim x dim faces back to back: +X, -X, +Y, -Y, +Z, -Z
+    float M[kMaxPointShadows][16];          // shadowProj[k] (lightProj * T), transposed like the spot lights' T
+    uint32_t count, dim;
+    float dx;                               // 1.0f / (float)dim, correctly rounded (on the host)
+};
+// The cube sampler's face of v = pos - Position (ties: x before y before z; positive when the component is >= 0) and the face's
+// view coordinates (a, b, c) = mul(float4(pos, 1), LookAtLH(Position, Position + axis, up)): sign flips and a permutation of v,
+// exact.  Chosen by selects -- the face is per lane.
+struct PointFace { f3 abc; uint32_t f; };
+CRY_HD PointFace point_face(f3 v)
+{
+    const float ax = __builtin_fabsf(v.x), ay = __builtin_fabsf(v.y), az = __builtin_fabsf(v.z);
+    const bool isX = (ax >= ay) & (ax >= az), isY = !isX & (ay >= az);
+    const float major = isX ? v.x : (isY ? v.y : v.z);
+    const bool pos = major >= 0.0f;
+    PointFace r;
+    r.f = (isX ? 0u : (isY ? 2u : 4u)) + (pos ? 0u : 1u);
+    // +X (-v.z, v.y, v.x)  -X (v.z, v.y, -v.x)  +Y (v.x, -v.z, v.y)  -Y (v.x, v.z, -v.y)  +Z (v.x, v.y, v.z)  -Z (-v.x, v.y, -v.z)
+    r.abc.x = isX ? (pos ? -v.z : v.z) : ((isY | pos) ? v.x : -v.x);
+    r.abc.y = isY ? (pos ? -v.z : v.z) : v.y;
+    r.abc.z = pos ? major : -major;
+    return r;
+}
+// The shadow of point light k when k < count, else factor 1: the spot lights' 9-tap factor on the face of v, at (a, b, c).
+struct PointShadowOf {
+    const PointShadows* S; f3 pos; const crychic_light* L; uint32_t k;
+    CRY_HD float operator()() const
+    {
+        if (k >= S->count) return 1.0f;
+        const PointFace pf = point_face(f3{ pos.x - L->Position[0], pos.y - L->Position[1], pos.z - L->Position[2] });
+        return spot_shadow_factor(S->maps[k] + (size_t)pf.f * S->dim * S->dim, S->dim, S->dx, S->M[k], pf.abc);
+    }
 };
 
 // TextureCube.Sample(gsamLinearWrap, r): D3D major-axis face selection (ties x >= y >= z), bilinear inside the
@@ -755,14 +797,20 @@ struct NoPointLights {
 };
 // Every point light, then every spot light (the gLights order, Common.hlsl:102-105), un-culled: the host build's iteration, where the
 // tiled kernels substitute a culled one.  shadows == nullptr models light_points_kernel / light_spots_kernel (UnitShadow), otherwise
-// the first shadows->count spot lights are shadowed as in light_spots_shadowed_kernel.
+// the first shadows->count spot lights are shadowed as in light_spots_shadowed_kernel; pointShadows != nullptr shadows the first
+// pointShadows->count point lights as in light_point_shadows_kernel.
 struct AllLocalLights {
     const crychic_light* points; uint32_t nPoints;
     const crychic_light* spots; uint32_t nSpots;
     const SpotShadows* shadows;
+    const PointShadows* pointShadows = nullptr;
     CRY_HD void operator()(f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view, f3& result, bool fixQ3, bool fixQ4) const
     {
-        for (uint32_t i = 0; i < nPoints; ++i) pbr_point_light(points[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
+        for (uint32_t i = 0; i < nPoints; ++i) {
+            if (pointShadows) pbr_point_light(points[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4,
+                                              PointShadowOf{ pointShadows, pos, &points[i], i });
+            else pbr_point_light(points[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
+        }
         for (uint32_t i = 0; i < nSpots; ++i) {
             if (shadows) pbr_spot_light(spots[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4, SpotShadowOf{ shadows, pos, i });
             else pbr_spot_light(spots[i], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);

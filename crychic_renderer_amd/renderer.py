@@ -11,7 +11,8 @@ import math
 import torch
 
 from . import _lib
-from ._lib import CrychicError, DrawItem, FrameDesc, Light, PassConstants, PassTimes, SpotShadows, SsaoConstants, Texture, check, lib
+from ._lib import (CrychicError, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+                   check, lib)
 
 
 def _ptr(t):
@@ -172,6 +173,9 @@ class Crychic:
         self.mSpotShadowMaps = None  # extension: (count, dim, dim) int32 D24 maps of the first spot lights (set_spot_shadows)
         self._spotHost = None        # host copy of the spot lights (the shadow transforms are built from it)
         self._spotShadow = None      # (SpotShadows descriptor, [transposed transform], [shadow pass constants], geometry)
+        self.mPointShadowMaps = None  # extension: (count, 6, dim, dim) int32 D24 cube faces of the first point lights (set_point_shadows)
+        self._pointHost = None       # host copy of the point lights (the face transforms are built from it)
+        self._pointShadow = None     # (PointShadows descriptor, [face pass constants, 6 per light], geometry)
         self._desc = None
 
     def load_scene(self, planes):
@@ -232,8 +236,10 @@ class Crychic:
             if len(self._desc) > 16:
                 self._desc.clear()
             f = self._desc[key] = self.frame_desc(row0, rows)
-        if self.mSpotLights is not None:       # extension: the _spots_shadowed entries (no descriptor: unshadowed), frame, strip or shared
-            spots, n = _ptr(self.mSpotLights), self.mSpotLights.numel() // 48
+        if self.mSpotLights is not None or self._pointShadow is not None:
+            # extension: the _spots_shadowed entries (no descriptor: unshadowed), or with point shadows the _point_shadows entries;
+            # frame, strip or shared
+            spots, n = (None, 0) if self.mSpotLights is None else (_ptr(self.mSpotLights), self.mSpotLights.numel() // 48)
             pcb, desc = self.mMainPassCB, None
             if self._spotShadow is not None:
                 d, T, cbs, geo = self._spotShadow
@@ -243,6 +249,17 @@ class Crychic:
                     pcb.ShadowTransforms[4 + k][:] = t
                 if geo is not None:
                     self.DrawSpotShadowMaps()
+            if self._pointShadow is not None:
+                pd, _, pgeo = self._pointShadow
+                if pgeo is not None:
+                    self.DrawPointShadowMaps()
+                if shared is not None:
+                    check(lib.crychic_draw_hot_path_shared_point_shadows(shared[0], C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), shared[1],
+                                                                         int(shared[2]), spots, n, desc, C.byref(pd), _stream(self.ctx.device)))
+                else:
+                    check(lib.crychic_draw_hot_path_point_shadows(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), spots, n, desc,
+                                                                  C.byref(pd), _stream(self.ctx.device)))
+                return
             if shared is not None:
                 check(lib.crychic_draw_hot_path_shared_spots_shadowed(shared[0], C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), shared[1],
                                                                       int(shared[2]), spots, n, desc, _stream(self.ctx.device)))
@@ -267,13 +284,18 @@ class Crychic:
         self._desc = None
 
     def set_point_lights(self, lights):
-        """Extension: `lights` is a ctypes array of Light (or None); copied to the device."""
+        """Extension: `lights` is a ctypes array of Light (or None); copied to the device.  Shadows set with set_point_shadows are
+        dropped (their transforms belong to the previous lights)."""
         if lights is None or len(lights) == 0:
             self.mPointLights = None
+            self._pointHost = None
         else:
             import numpy as np
             host = np.frombuffer(bytes(lights), dtype=np.uint8).copy()
             self.mPointLights = torch.from_numpy(host).to(self.ctx.device)
+            self._pointHost = (Light * len(lights)).from_buffer_copy(bytes(lights))
+        self.mPointShadowMaps = None
+        self._pointShadow = None
         self._desc = None
 
     def set_spot_lights(self, lights):
@@ -333,6 +355,52 @@ class Crychic:
         desc, T, cbs, geo = self._spotShadow
         geo = geometry if geometry is not None else geo
         geo.DrawSceneToShadowMaps(cbs, [self.mSpotShadowMaps[k] for k in range(len(cbs))])
+
+    def set_point_shadows(self, count, dim=512, z_near=0.5, geometry=None):
+        """Extension: the first `count` (<= 4) point lights cast cube shadows (include/crychic_hip.h crychic_deferred_light_point_shadows).
+        Allocates mPointShadowMaps, (count, 6, dim, dim) D24 faces cleared to 1.0, builds each light's face views and shadow projection
+        (crychic_update_point_shadow_transforms: widened 90-degree faces, z_near .. FalloffEnd) and from then on routes every Draw
+        through the _point_shadows entries.  geometry (a SceneGeometry of the shadow casters): Draw renders the faces first
+        (DrawPointShadowMaps); without it the caller fills mPointShadowMaps.  count 0 removes the shadows."""
+        if count == 0:
+            self.mPointShadowMaps, self._pointShadow = None, None
+            return
+        n = 0 if self._pointHost is None else len(self._pointHost)
+        if not 0 < count <= 4 or count > n:
+            raise CrychicError(-1, "set_point_shadows: count %d (1 .. 4, at most the %d point lights)" % (count, n))
+        if not 16 <= dim <= 16384:
+            raise CrychicError(-1, "set_point_shadows: dim %d (16 .. 16384)" % dim)
+        import numpy as np
+        desc = PointShadows()
+        desc.count, desc.dim = count, dim
+        cbs = []
+        for k in range(count):
+            lv, lp, sp = ((C.c_float * 16) * 6)(), (C.c_float * 16)(), (C.c_float * 16)()
+            check(lib.crychic_update_point_shadow_transforms(C.byref(self._pointHost[k]), int(dim), float(z_near), lv, lp, sp))
+            desc.shadowProj[k][:] = sp[:]
+            for f in range(6):
+                cb = PassConstants()
+                vp = np.asarray(lv[f][:], np.float32).reshape(4, 4) @ np.asarray(lp[:], np.float32).reshape(4, 4)
+                cb.ViewProj[:] = list(vp.astype(np.float32).T.reshape(-1))
+                cbs.append(cb)
+        self.mPointShadowMaps = torch.full((count, 6, dim, dim), 0xFFFFFF, dtype=torch.int32, device=self.ctx.device)
+        for k in range(count):
+            desc.maps[k] = self.mPointShadowMaps[k].data_ptr()
+        self._pointShadow = (desc, cbs, geometry)
+
+    def point_shadow_pass_constants(self):
+        """The shadow pass constants (ViewProj = lightView[f] * lightProj) of the shadowed point lights' faces: light-major, faces
+        +X, -X, +Y, -Y, +Z, -Z."""
+        return [] if self._pointShadow is None else list(self._pointShadow[1])
+
+    def DrawPointShadowMaps(self, geometry=None):
+        """Renders every point shadow face with crychic_draw_scene_to_shadow_maps (the cascades' rasteriser and bias), at most 12
+        faces (two lights) per call."""
+        desc, cbs, geo = self._pointShadow
+        geo = geometry if geometry is not None else geo
+        faces = [self.mPointShadowMaps[k, f] for k in range(len(cbs) // 6) for f in range(6)]
+        for i in range(0, len(cbs), 12):
+            geo.DrawSceneToShadowMaps(cbs[i:i + 12], faces[i:i + 12])
 
     def set_profiling(self, enabled):
         check(lib.crychic_ctx_set_profiling(self.ctx.handle, 1 if enabled else 0))

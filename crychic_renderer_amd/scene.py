@@ -346,3 +346,22 @@ def shadow_spot_lights(n=1, offset=(-4.0, 6.0, -4.0), falloff_start=2.0, falloff
         L.Position[:] = p
         L.SpotPower = spot_power
     return arr
+
+
+def shadow_point_lights(n=1, offset=(-1.0, 3.0, -1.0), falloff_start=1.0, falloff_end=12.0, strength=3.0):
+    """Extension: n (<= 4) point lights, light k placed at `offset` from a box of the reference scene in front of the default camera
+    (above it), so that once the light is shadowed (Crychic.set_point_shadows) the box's shadow falls on the grid around it.
+    Returns a ctypes array of Light."""
+    from ._lib import Light
+    if not 0 < n <= 4:
+        raise ValueError("shadow_point_lights: n %d (1 .. 4)" % n)
+    arr = (Light * n)()
+    for k in range(n):
+        t = _SHADOW_TARGETS[k]
+        L = arr[k]
+        L.Strength[:] = (strength, strength, strength)
+        L.FalloffStart, L.FalloffEnd = falloff_start, falloff_end
+        L.Direction[:] = (0.0, -1.0, 0.0)
+        L.Position[:] = [t[c] + offset[c] for c in range(3)]
+        L.SpotPower = 64.0
+    return arr

@@ -185,6 +185,7 @@ public:
         UpdateMaterialBuffer(gt);                                                                   // :165
         UpdateCascadeShadowTransform(gt);
         UpdateSpotShadowTransforms();
+        UpdatePointShadowTransforms();
         UpdateMainPassCB(gt);
         UpdateShadowPassCB(gt);
         UpdateSsaoCB(gt);
@@ -236,7 +237,22 @@ public:
         for (uint32_t k = 0; k < sh.count; ++k) sh.maps[k] = static_cast<const uint32_t*>(mSpotShadowMaps[k]->Data());
         const auto* ssaoCB = reinterpret_cast<const crychic_ssao_constants*>(&scb);
         const auto* passCB = reinterpret_cast<const crychic_pass_constants*>(&pcb);
-        if (mComm)
+        if (mPointShadowCount > 0) {
+            // Shadowed point lights (SetPointShadows): the first mPointShadowCount point lights read their six faces through shadowProj
+            crychic_point_shadows psh = {};
+            psh.count = mPointShadowCount;
+            psh.dim = mPointShadowDim;
+            for (uint32_t k = 0; k < psh.count; ++k) {
+                psh.maps[k] = static_cast<const uint32_t*>(mPointShadowMaps[k]->Data());
+                std::memcpy(psh.shadowProj[k], mPointShadowProjs[k], sizeof psh.shadowProj[k]);
+            }
+            if (mComm)
+                CrychicThrowIfFailed(crychic_draw_hot_path_shared_point_shadows(mComm, ssaoCB, passCB, &f, mStripBounds.empty() ? nullptr : mStripBounds.data(),
+                                                                                mExchangeParts, spots, mNumSpotLights, &sh, &psh, mCommandList->Stream()));
+            else
+                CrychicThrowIfFailed(crychic_draw_hot_path_point_shadows(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, mNumSpotLights, &sh, &psh,
+                                                                         mCommandList->Stream()));
+        } else if (mComm)
             CrychicThrowIfFailed(crychic_draw_hot_path_shared_spots_shadowed(mComm, ssaoCB, passCB, &f, mStripBounds.empty() ? nullptr : mStripBounds.data(),
                                                                              mExchangeParts, spots, mNumSpotLights, &sh, mCommandList->Stream()));
         else
@@ -269,7 +285,10 @@ public:
         upload(points, nPoints, mPointLights, mNumPointLights);
         upload(spots, nSpots, mSpotLights, mNumSpotLights);
         mSpotHost.assign(spots, spots + nSpots);    // the shadow transforms are built from these
+        mPointHost.assign(points, points + nPoints);
         if (mSpotShadowCount > nSpots) SetSpotShadows(0, 0, 0.0f, 0.0f);
+        if (mPointShadowCount > nPoints) SetPointShadows(0, 0, 0.0f);
+        UpdatePointShadowTransforms();          // the faces follow the lights that keep their shadows
         mCommandList->Flush();                  // the caller's arrays may go once this returns
     }
 
@@ -300,6 +319,33 @@ public:
         UpdateSpotShadowTransforms();
     }
     ID3D12Resource* SpotShadowMap(uint32_t k) { return k < mSpotShadowCount ? mSpotShadowMaps[k].get() : nullptr; }
+
+    // ---- shadowed point lights (extension: cube shadows, include/crychic_hip.h crychic_deferred_light_point_shadows) -------------
+    // The first `count` (<= 4, at most the point lights of SetLocalLights) point lights cast shadows: each gets six dim x dim D24 faces
+    // (+X, -X, +Y, -Y, +Z, -Z back to back) that DrawSceneToShadowMap renders after the spot lights' maps (widened 90-degree faces,
+    // zNear .. FalloffEnd; crychic_update_point_shadow_transforms); Draw takes the _point_shadows entries.  count 0 removes the shadows,
+    // and SetLocalLights drops them when fewer point lights remain.  Waits for the frames in flight first, which may still read the faces.
+    void SetPointShadows(uint32_t count, uint32_t dim, float zNear)
+    {
+        mCommandList->Flush();
+        mPointShadowMaps.clear();
+        mPointShadowCount = 0;
+        if (count == 0) return;
+        if (count > CRYCHIC_MAX_POINT_SHADOWS || count > mNumPointLights || dim < CRYCHIC_MIN_POINT_SHADOW_DIM || dim > CRYCHIC_MAX_SPOT_SHADOW_DIM)
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetPointShadows (count 1 .. 4 and at most the point lights, dim 16 .. 16384)",
+                                   __FILE__, __LINE__);
+        float v[6][16], p[16], t[16];
+        for (uint32_t k = 0; k < count; ++k)       // zNear against every light's range, before anything changes
+            CrychicThrowIfFailed(crychic_update_point_shadow_transforms(reinterpret_cast<const crychic_light*>(&mPointHost[k]), dim, zNear, v, p, t));
+        for (uint32_t k = 0; k < count; ++k)
+            mPointShadowMaps.push_back(std::make_unique<ID3D12Resource>((size_t)6 * dim * dim * 4u, ID3D12Resource::DEFAULT_HEAP));
+        mPointShadowCount = count;
+        mPointShadowDim = dim;
+        mPointShadowZNear = zNear;
+        UpdatePointShadowTransforms();
+    }
+    // The six faces of point light k, back to back (nullptr when it has none).
+    ID3D12Resource* PointShadowMap(uint32_t k) { return k < mPointShadowCount ? mPointShadowMaps[k].get() : nullptr; }
 
     // ---- one frame on several GPUs (no counterpart in the single-GPU reference) ----------------------------------
     // Rows [row0, row0 + rows) are this GPU's share of the hot path (row0 even).  An empty share is refused: a rank without rows
@@ -612,7 +658,12 @@ private:
         }
         CrychicThrowIfFailed(crychic_draw_scene_to_shadow_maps(md3dDevice->Ctx(), cbs, 4, items.data(), (uint32_t)items.size(), targets,
                                                                mShadowMap->Width(), 10000, 2.0f, ws, bytes, mCommandList->Stream()));  // bias: :1601-1603
-        if (mSpotShadowCount == 0) return;
+        if (mSpotShadowCount > 0) DrawSpotShadowMaps(items);
+        if (mPointShadowCount > 0) DrawPointShadowMaps(items);
+    }
+    void DrawSpotShadowMaps(const std::vector<crychic_draw_item>& items)
+    {
+        size_t bytes;
         // the shadowed spot lights' maps (slots 4..11): one more pass of the same rasteriser, ViewProj = lightView * lightProj
         crychic_pass_constants scbs[CRYCHIC_MAX_SPOT_SHADOWS];
         uint32_t* stargets[CRYCHIC_MAX_SPOT_SHADOWS];
@@ -628,6 +679,30 @@ private:
         void* sws = RasterWorkspace((uint64_t)mSpotShadowCount * mSceneTriangles, mSpotShadowDim, mSpotShadowDim, &bytes);
         CrychicThrowIfFailed(crychic_draw_scene_to_shadow_maps(md3dDevice->Ctx(), scbs, mSpotShadowCount, items.data(), (uint32_t)items.size(),
                                                                stargets, mSpotShadowDim, 10000, 2.0f, sws, bytes, mCommandList->Stream()));
+    }
+    void DrawPointShadowMaps(const std::vector<crychic_draw_item>& items)
+    {
+        // the shadowed point lights' faces: the same rasteriser, ViewProj = lightView[f] * lightProj, at most 12 faces (two lights) per call
+        size_t bytes;
+        const uint32_t nFaces = 6u * mPointShadowCount, perCall = 12u;
+        void* pws = RasterWorkspace((uint64_t)(nFaces < perCall ? nFaces : perCall) * mSceneTriangles, mPointShadowDim, mPointShadowDim, &bytes);
+        for (uint32_t first = 0; first < nFaces; first += perCall) {
+            const uint32_t n = nFaces - first < perCall ? nFaces - first : perCall;
+            crychic_pass_constants pcbs[12];
+            uint32_t* ptargets[12];
+            for (uint32_t i = 0; i < n; ++i) {
+                const uint32_t k = (first + i) / 6u, face = (first + i) % 6u;
+                std::memset(&pcbs[i], 0, sizeof pcbs[i]);
+                for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) {
+                    float acc = 0.0f;
+                    for (int q = 0; q < 4; ++q) acc += mPointViews[k][face][4 * r + q] * mPointProjs[k][4 * q + c];
+                    pcbs[i].ViewProj[4 * c + r] = acc;                                              // stored transposed
+                }
+                ptargets[i] = static_cast<uint32_t*>(mPointShadowMaps[k]->Data()) + (size_t)face * mPointShadowDim * mPointShadowDim;
+            }
+            CrychicThrowIfFailed(crychic_draw_scene_to_shadow_maps(md3dDevice->Ctx(), pcbs, n, items.data(), (uint32_t)items.size(), ptargets,
+                                                                   mPointShadowDim, 10000, 2.0f, pws, bytes, mCommandList->Stream()));
+        }
     }
     void DrawNormalsAndDepth()  // CRYCHIC.cpp:2512-2543
     {
@@ -687,6 +762,12 @@ private:
             std::memcpy(&mLightViews[4 + k], v, 64); std::memcpy(&mLightProjs[4 + k], p, 64); std::memcpy(&mShadowTransforms[4 + k], t, 64);
         }
     }
+    void UpdatePointShadowTransforms()  // SetPointShadows / SetLocalLights: the faces, projection and shadow projection of each shadowed point light
+    {
+        for (uint32_t k = 0; k < mPointShadowCount; ++k)
+            CrychicThrowIfFailed(crychic_update_point_shadow_transforms(reinterpret_cast<const crychic_light*>(&mPointHost[k]), mPointShadowDim,
+                                                                        mPointShadowZNear, mPointViews[k], mPointProjs[k], mPointShadowProjs[k]));
+    }
     void UpdateMainPassCB(const GameTimer& gt)  // CRYCHIC.cpp:817-868
     {
         float st[4][16], dirs[3][3];
@@ -738,6 +819,12 @@ private:
     std::vector<std::unique_ptr<ID3D12Resource>> mSpotShadowMaps;         // SetSpotShadows
     uint32_t mSpotShadowCount = 0, mSpotShadowDim = 0;
     float mSpotShadowFovY = 0.0f, mSpotShadowZNear = 0.0f;
+    std::vector<Light> mPointHost;                                        // SetLocalLights' point list, for the face transforms
+    std::vector<std::unique_ptr<ID3D12Resource>> mPointShadowMaps;        // SetPointShadows: six faces per light
+    uint32_t mPointShadowCount = 0, mPointShadowDim = 0;
+    float mPointShadowZNear = 0.0f;
+    float mPointViews[CRYCHIC_MAX_POINT_SHADOWS][6][16] = {}, mPointProjs[CRYCHIC_MAX_POINT_SHADOWS][16] = {};
+    float mPointShadowProjs[CRYCHIC_MAX_POINT_SHADOWS][16] = {};
     UINT mCubeMapSize = 0, mCubeMapLevels = 1;
     UINT mClientWidth, mClientHeight;
     float mLightRotationAngle = 0.0f;

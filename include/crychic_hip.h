@@ -301,6 +301,57 @@ int crychic_deferred_light_spots_shadowed(crychic_ctx* ctx, const crychic_pass_c
 int crychic_update_spot_shadow_transform(const crychic_light* L, float fovY, float zNear, float lightView[16], float lightProj[16],
                                          float shadowTransform[16]);
 
+/* ---- shadowed point lights (BUILD-DEFINED EXTENSION; parity against this repo's checker, tests/point_shadow_ref) ---------- *
+ * Omnidirectional (cube) shadows for the first `count` (<= CRYCHIC_MAX_POINT_SHADOWS) point lights.  Point light k < count reads
+ * six dim x dim D24 faces stored back to back at maps[k] (+X, -X, +Y, -Y, +Z, -Z; the spot maps' format) through one projection
+ * shadowProj[k] (untransposed, as crychic_update_point_shadow_transforms writes it).  Where the point term is evaluated
+ * (d <= FalloffEnd; the tile cull stays spherical):
+ *   v = pos - Position                                    (three float subtractions: -l of the point term)
+ *   ax, ay, az = |v|;  face axis X if ax >= ay && ax >= az, else Y if ay >= az, else Z;  positive when that component >= 0.0f
+ *   face view coordinates (a, b, c), exact sign flips and permutations of v (LookAtLH(Position, Position + axis, up)):
+ *     +X (-v.z, v.y, v.x)   -X (v.z, v.y, -v.x)   +Y (v.x, -v.z, v.y)   -Y (v.x, v.z, -v.y)   +Z (v.x, v.y, v.z)   -Z (-v.x, v.y, -v.z)
+ *     up = (0, 1, 0) for +-X and +-Z, (0, 0, -1) for +Y, (0, 0, 1) for -Y
+ *   s = the spot lights' 9-tap factor (crychic_deferred_light_spots_shadowed) on face f of maps[k] with T = shadowProj[k]
+ *       transposed, at the position (a, b, c): perspective divide, nine gsamShadow taps in offsets[9] order, / 9.0f
+ *   result = fma(s * brdf, lightStrength, result)         (s == 1: the unshadowed bits)
+ * Point lights k >= count keep shadow factor 1.  crychic_update_point_shadow_transforms widens each face so that every point of
+ * its 90-degree region lands at texel coordinates in [2, dim - 2]: all nine taps' footprints stay inside the face (no seams).
+ * A NULL descriptor or count == 0 is the matching _spots_shadowed entry, bit for bit.  With count > 0: count > 4,
+ * count > numPointLights, a NULL map among the first count, dim < 16 or dim > CRYCHIC_MAX_SPOT_SHADOW_DIM return
+ * CRYCHIC_E_INVALID_ARG (with a message) before anything is enqueued.  Face f is rendered by crychic_draw_scene_to_shadow_maps
+ * with passCBs[i].ViewProj = lightView[f] * lightProj (the cascades' bias, 10000 / 2.0; at most 12 faces, two lights, per call). */
+#define CRYCHIC_MAX_POINT_SHADOWS 4
+#define CRYCHIC_MIN_POINT_SHADOW_DIM 16            /* max: CRYCHIC_MAX_SPOT_SHADOW_DIM */
+typedef struct crychic_point_shadows {
+    uint32_t count;                                 /* point lights 0 .. count-1 are shadowed */
+    uint32_t dim;                                   /* face side */
+    const uint32_t* maps[CRYCHIC_MAX_POINT_SHADOWS];  /* six dim x dim D24 faces back to back: +X, -X, +Y, -Y, +Z, -Z */
+    float shadowProj[CRYCHIC_MAX_POINT_SHADOWS][16];  /* as crychic_update_point_shadow_transforms writes it (untransposed) */
+} crychic_point_shadows;
+
+/* crychic_deferred_light_spots_shadowed with the first pointShadows->count point lights shadowed (definition above). */
+int crychic_deferred_light_point_shadows(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev,
+                                         const float* g1_dev, const float* g2_dev, const uint32_t* depth_dev,
+                                         const uint16_t* ambient_dev, const uint32_t* const shadow_dev[4], uint32_t shadowDim,
+                                         const uint8_t* cube_dev, uint32_t cubeDim, uint8_t* out_rgba8_dev,
+                                         float* radiance_out_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                                         int numDirLights, float pcfSearchRadius, uint32_t flags,
+                                         const crychic_light* point_lights_dev, uint32_t numPointLights,
+                                         const crychic_light* spot_lights_dev, uint32_t numSpotLights,
+                                         const crychic_spot_shadows* spotShadows, const crychic_point_shadows* pointShadows,
+                                         void* stream);
+
+/* The six face views, the projection and the shadow projection of a shadowed point light (host only; the storage of
+ * crychic_update_spot_shadow_transform: untransposed row-vector matrices):
+ *   lightView[f] = LookAtLH(Position, Position + axis_f, up_f)   (the face table above; entries exactly 0, +-1 and -dot(axis, Position))
+ *   lightProj    = PerspectiveFovLH with aspect 1, zNear .. FalloffEnd and xScale = yScale = (dim - 4) / dim
+ *                  (fovY = 2 atan(dim / (dim - 4)): the widened face)
+ *   shadowProj   = lightProj * T, T the NDC -> texture matrix of the cascades; the descriptor's shadowProj[k].
+ * The shadow pass of face f renders with ViewProj = lightView[f] * lightProj.  CRYCHIC_E_INVALID_ARG for a NULL pointer, dim
+ * outside 16 .. 16384, zNear <= 0, zNear >= FalloffEnd or a non-finite Position. */
+int crychic_update_point_shadow_transforms(const crychic_light* L, uint32_t dim, float zNear, float lightView[6][16],
+                                           float lightProj[16], float shadowProj[16]);
+
 /* ---- whole hot path of CRYCHIC::Draw (CRYCHIC.cpp:220-221 + 238-279) -------------------------------------- */
 typedef struct crychic_frame_desc {
     uint32_t W, H;
@@ -341,6 +392,12 @@ int crychic_draw_hot_path_spots(crychic_ctx* ctx, const crychic_ssao_constants* 
 int crychic_draw_hot_path_spots_shadowed(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
                                          const crychic_frame_desc* frame, const crychic_light* spot_lights_dev, uint32_t numSpotLights,
                                          const crychic_spot_shadows* spotShadows, void* stream);
+/* crychic_draw_hot_path_spots_shadowed with shadowed point lights (crychic_deferred_light_point_shadows' definition and limits);
+ * a NULL point descriptor or count == 0 is crychic_draw_hot_path_spots_shadowed, bit for bit. */
+int crychic_draw_hot_path_point_shadows(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, const crychic_pass_constants* passCB,
+                                        const crychic_frame_desc* frame, const crychic_light* spot_lights_dev, uint32_t numSpotLights,
+                                        const crychic_spot_shadows* spotShadows, const crychic_point_shadows* pointShadows,
+                                        void* stream);
 
 /* Per-kernel timing of the last crychic_draw_hot_path issued with profiling enabled (HIP events recorded
  * on the caller's stream around each pass).  Times are milliseconds; blocks until the events complete. */
@@ -561,6 +618,12 @@ int crychic_draw_hot_path_shared_spots_shadowed(crychic_comm* comm, const crychi
                                                 const crychic_pass_constants* passCB, const crychic_frame_desc* frame,
                                                 const uint32_t* bounds, uint32_t nparts, const crychic_light* spot_lights_dev,
                                                 uint32_t numSpotLights, const crychic_spot_shadows* spotShadows, void* stream);
+/* The same with shadowed point lights (crychic_draw_hot_path_point_shadows): each rank binds the faces it rendered. */
+int crychic_draw_hot_path_shared_point_shadows(crychic_comm* comm, const crychic_ssao_constants* ssaoCB,
+                                               const crychic_pass_constants* passCB, const crychic_frame_desc* frame,
+                                               const uint32_t* bounds, uint32_t nparts, const crychic_light* spot_lights_dev,
+                                               uint32_t numSpotLights, const crychic_spot_shadows* spotShadows,
+                                               const crychic_point_shadows* pointShadows, void* stream);
 /* Stream-ordered rendezvous of all ranks (a one-word ncclAllReduce): brackets timed regions; no host wait inside. */
 int crychic_comm_barrier(crychic_comm* comm, void* stream);
 
