@@ -370,8 +370,9 @@ __global__ __launch_bounds__(512) void blur_replay_kernel(crychic_ssao_constants
 // per-iteration launches get from the kernel boundary -- iteration j reads what iteration j - 1 wrote, and may overwrite the plane
 // iteration j - 1 read -- is a per-tile dependency here: a tile's iteration j needs its own and its eight neighbours' iteration
 // j - 1 COMPLETE (their outputs are its apron; their inputs are the plane it writes).  Every tile publishes its count of completed
-// iterations, tagged with the frame stamp (a stale or uninitialised word never matches), with agent-scope release; a workgroup
-// polls its up to nine predecessors with agent-scope acquire before it stages.  Forward progress: workgroups are dispatched in
+// iterations, tagged with the frame stamp (a stale or uninitialised word never matches), after every wavefront of it has drained
+// its write-through stores; a workgroup polls its up to nine predecessors (relaxed) and executes one agent-scope acquire before it
+// stages (the hand-off's contract: DESIGN.md "Blur: one launch for the replayed iterations").  Forward progress: workgroups are dispatched in
 // increasing (z, y, x) order and a workgroup only ever waits for workgroups of the layer below, which were dispatched before it
 // and wait for nothing above them.  The poll is bounded all the same: a workgroup that gives up sets EdgePlane::progress's error
 // word and goes on (wrong pixels, never a hang).  Tiles the pair launch settled neither work nor publish nor are waited for.
@@ -404,8 +405,9 @@ __global__ __launch_bounds__(512) void blur_replay_chain_kernel(crychic_ssao_con
                 if (!(exitStamp != 0u && edge.tiles[n] == exitStamp)) {
                     bool ok = false;
                     for (int spin = 0; spin < (1 << 16) && !ok; ++spin) {
-                        // relaxed polls (a coherent load, no cache invalidation per poll: an acquire here flushed the caches under the
-                        // workgroups that were doing the work -- 14x slower); ONE acquire fence after the wait, below
+                        // relaxed polls (global_load_dwordx2 sc1: a coherent load, no cache invalidation per poll -- an acquire here
+                        // flushed the caches under the workgroups that were doing the work, 14x slower); the ONE acquire of the
+                        // hand-off follows the wait, below
                         const unsigned long long v = __hip_atomic_load(edge.progress + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         ok = (v >> 8) == (tag >> 8) && (v & 255ull) >= (unsigned long long)it;
                         if (!ok) __builtin_amdgcn_s_sleep(16);
@@ -413,8 +415,16 @@ __global__ __launch_bounds__(512) void blur_replay_chain_kernel(crychic_ssao_con
                     if (!ok) edge.progress[(size_t)ntx * blur_tiles_y(H)] = tag | 255ull;      // the error word (one past the tiles)
                 }
             }
+            // Consumer side of the hand-off, the acquire kept rather than one of the acquire-free forms measured safe (those need
+            // 4-byte or wider texels, or whole 128-byte lines per store instruction, which 2-byte texels on ragged widths are
+            // not): the polling wavefront, once every poll of it has matched, executes ONE agent-scope acquire (s_waitcnt
+            // vmcnt(0); buffer_inv sc1: this CU's L1 only) and waits for it (s_waitcnt vmcnt(0)) before it joins the barrier that
+            // lets the other wavefronts load.  Inside this branch, so that every path from the poll passes it.  The staging
+            // loads stay device-coherent (sc1) as well.
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        __syncthreads();          // the staging loads below are device-coherent themselves: nothing to invalidate
+        __syncthreads();
     }
     const uint32_t row0 = plan.row0[it], row1 = plan.row1[it];
     const bool mine = ty * (uint32_t)kBlurTileH < row1 && (ty + 1u) * (uint32_t)kBlurTileH > row0;
@@ -434,10 +444,13 @@ __global__ __launch_bounds__(512) void blur_replay_chain_kernel(crychic_ssao_con
         a.tileIndex = tile;
         blur_replay_tile(BlockDevT<true>{}, a, 0u, onesShortcut != 0, s_in, s_mask, s_mid, s_rows);
     }
-    // The tile's outputs were device-coherent stores: once every wavefront's stores are acknowledged (workgroup-scope release:
-    // s_waitcnt) they are visible to every XCD, and the count may be published -- no L2 write-back (an agent-scope release fence
-    // per workgroup writes back the XCD's whole L2: measured 390 us for the launch)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    // Producer side.  The tile's outputs were device-coherent (write-through, sc1) stores: once EVERY wavefront has seen its own
+    // stores acknowledged (s_waitcnt vmcnt(0), written as inline assembly: a workgroup-scope release fence emits no vmcnt wait
+    // here, and s_barrier waits for no counter) and has then reached the barrier, the texels are visible to every XCD and one
+    // lane may publish the count (a relaxed agent-scope store: global_store_dwordx2 sc1) -- no L2 write-back (an agent-scope
+    // release fence per workgroup writes back the XCD's whole L2: measured 390 us for the launch).
+    // tools/handoff_isa.py checks this order in the emitted assembly on every path (tests/test_chain_handoff_isa.py).
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) __hip_atomic_store(edge.progress + tile, tag | (unsigned long long)(it + 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

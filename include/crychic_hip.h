@@ -518,7 +518,11 @@ int crychic_raster_status(crychic_ctx* ctx, void* stream, uint32_t* flags);
 
 /* Ssao::ComputeSsao's blur iterations 1 .. blurCount - 1 run as ONE launch whose tiles wait for their neighbours' previous iteration
  * through per-tile counters in the edge workspace (Ssao.cpp:231-266 issues one draw per sweep and relies on the barrier between
- * draws).  The wait is bounded: a workgroup that gives up -- which would mean the device did not dispatch workgroups in grid order,
+ * draws).  The hand-off's contract ("Blur: one launch for the replayed iterations"): a tile's texels are stored
+ * write-through, every wavefront waits for its stores (s_waitcnt vmcnt(0)) and reaches the workgroup barrier before one lane
+ * publishes the counter; a waiting workgroup polls relaxed, then executes one agent-scope acquire, waits for it and passes a
+ * barrier before any wavefront loads a neighbour's texel.  tools/handoff_isa.py checks that order in the emitted assembly.
+ * The wait is bounded: a workgroup that gives up -- which would mean the device did not dispatch workgroups in grid order,
  * the assumption forward progress rests on -- records it and goes on.  This call synchronises `stream` and reports whether that
  * happened in the most recent chain issued on `ctx` (*timed_out = 1: that frame's ambient map is wrong).  Tests and bench.py
  * check it; CRYCHIC_BLUR_PER_ITERATION=1 in the environment selects one launch per iteration instead (the same pixels). */

@@ -153,6 +153,34 @@ def clear_cell_probe_case(seed):
     return W, H, c, scb, depth, normal, randvec
 
 
+def rough_wall_case(seed, W, H, sky_blocks):
+    """Frames for the blur chain's tile hand-off (tests/test_blur_chain_handoff.py): a "rough wall" -- view depth uniform in
+    [6.0, 6.6] per texel, normals (0.5 n1, 0.5 n2, -1) with n1, n2 standard normal, random randvec.  About 90 % of the texels
+    come out occluded, every texel changes under the blur and NO tile settles, so every tile of the chain takes part in the
+    hand-off and a stale apron read changes the result.  sky_blocks: rectangles of sky (clear depth, normal (0, 0, -1)) on a grid
+    of 256 x 96 full-res texels (2 x 3 blur tiles), each present with probability 1/2 -- tiles inside them settle and their
+    workgroups return at once, which makes the load uneven.  Returns (c, scb, depth, normal, randvec)."""
+    import oracle_lib
+    from crychic_renderer_amd import scene
+    rng = np.random.default_rng(seed)
+    c = scene.Constants(W, H, shadow_dim=64)
+    A, B = c.ssao_cb.Proj[10], c.ssao_cb.Proj[11]
+    vz = rng.uniform(6.0, 6.6, size=(H, W))
+    depth = np.clip(np.round((A + B / vz) * 16777215.0), 0, 0xFFFFFE).astype(np.uint32)
+    normal = np.zeros((H, W, 4), np.float16); normal[..., 2] = -1.0
+    normal[..., :2] = (0.5 * rng.standard_normal((H, W, 2))).astype(np.float16)
+    randvec = rng.integers(0, 256, size=(256, 256, 4), dtype=np.uint8)
+    if sky_blocks:
+        rng = np.random.default_rng(100 + seed)
+        for by in range(0, H, 96):
+            for bx in range(0, W, 256):
+                if rng.random() < 0.5:
+                    depth[by:by + 96, bx:bx + 256] = 0xFFFFFF
+                    normal[by:by + 96, bx:bx + 256, :3] = (0, 0, -1)
+    scb = oracle_lib.as_oracle_cb(c.ssao_cb, oracle_lib.OrSsaoConstants)
+    return c, scb, depth, normal, randvec
+
+
 def cull_probe_case(seed, W=256, H=160):
     """Frames for the SSAO tap culling (ssao_core.hpp): the reference scene -- open ground, where most taps are culled -- with what
     the nearest-depth bound must not miss: single near texels (spikes a fraction of a block wide), texels just in front of their
