@@ -12,6 +12,10 @@ LIB_PATH = os.environ.get("CRYCHIC_LIB") or os.path.join(HERE, "libcrychic_hip.s
 
 MAX_LIGHTS = 16
 LIGHT_SKY = 1
+# CRYCHIC_GBUFFER_G*_F16: that G-buffer plane holds half4 texels (the flags word of the lighting entries, FrameDesc.flags, and
+# crychic_draw_gbuffer_formats' gbufferFlags)
+GBUFFER_G0_F16, GBUFFER_G1_F16, GBUFFER_G2_F16 = 0x1000, 0x2000, 0x4000
+GBUFFER_F16_MASK = 0x7000
 COMM_ID_BYTES = 128
 
 
@@ -168,6 +172,9 @@ PROTOTYPES = {
                                        _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
     "crychic_draw_normals_depth_and_gbuffer_rows": (_i, [_vp, _P(PassConstants), _P(DrawItem), _u32, _vp, _u32, _P(Texture), _u32, _vp, _vp, _vp, _vp,
                                                         _vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
+    "crychic_gbuffer_plane_bytes": (_sz, [_u32, _u32, _u32, _i]),
+    "crychic_draw_gbuffer_formats": (_i, [_vp, _P(PassConstants), _P(DrawItem), _u32, _vp, _u32, _P(Texture), _u32, _vp, _vp, _vp, _vp,
+                                          _u32, _vp, _u32, _u32, _u32, _u32, _vp, _sz, _vp]),
 }
 
 

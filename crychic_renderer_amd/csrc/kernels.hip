@@ -10,33 +10,9 @@
 #include "ssao_core.hpp"
 #include "blur_tiles.hpp"
 #include "light_core.hpp"
+#include "light_tiles.hpp"
 
 namespace cry {
-
-// XCD-aware tile order.  Workgroups are dealt round-robin over the 8 XCDs (each with a private 4 MiB L2), so with
-// the natural order every XCD touches the whole frame: the SSAO depth taps then miss L2 eight times over
-// (measured: 362 MB fetched per 4K launch against 50 MB of planes).  The remap hands each XCD stripes of STRIPE
-// consecutive tile rows, interleaved over the frame with period 8*STRIPE: neighbouring tiles -- which share tap
-// footprints and blur aprons -- share an L2, while cheap (sky) and expensive (near geometry) regions still spread
-// over all XCDs (one contiguous band per XCD measured 1.8x SLOWER on the lighting pass: load imbalance).
-// Placement is a performance hint only: any dispatch order produces the same pixels.
-template <uint32_t STRIPE>
-__device__ __forceinline__ void tile_origin(uint32_t& bx, uint32_t& by)
-{
-    const uint32_t nbx = gridDim.x, n = nbx * gridDim.y;
-    uint32_t b = blockIdx.y * nbx + blockIdx.x;
-    if (STRIPE > 0) {
-        const uint32_t chunk = nbx * STRIPE;              // tiles per stripe
-        const uint32_t full = (n / (chunk * 8u)) * (chunk * 8u);   // tiles covered by whole 8-stripe groups
-        if (b < full) {
-            const uint32_t xcd = b & 7u, k = b >> 3;      // k-th tile this XCD receives
-            const uint32_t j = k / chunk, o = k - j * chunk;
-            b = (j * 8u + xcd) * chunk + o;
-        }                                                 // the tail keeps its ids (bijective)
-    }
-    by = b / nbx;
-    bx = b - by * nbx;
-}
 
 // Two-dimensional variant for the SSAO pass: the (padded) grid is cut into super-tiles of SX x SY workgroup tiles; whole
 // super-tiles are dealt to the XCDs, so the depth texels an XCD's taps reach form a compact block instead of a
@@ -455,39 +431,6 @@ __global__ __launch_bounds__(512) void blur_replay_chain_kernel(crychic_ssao_con
     if (threadIdx.x == 0) __hip_atomic_store(edge.progress + tile, tag | (unsigned long long)(it + 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// ---- deferred lighting -----------------------------------------------------------------------------------------
-// Shaders/DeferredShading.hlsl:23-101 as a full-screen pass over rows [row0, row1), masked by depth < 1.
-// MIPS (the cube map holds a mip chain, P.cubeLevels > 1): a wavefront covers 32 x 2 pixels instead of 64 x 1, so that every 2 x 2
-// quad of the frame lies inside one wavefront -- the x neighbour is lane ^ 1, the y neighbour lane ^ 32 -- and the level of detail of
-// the reflection lookup comes from the neighbours' reflection vectors without a second pass (light_core.hpp "TextureCube.Sample
-// with the mip chain bound").
-template <bool MIPS>
-__device__ __forceinline__ void light_tile_pixel(uint32_t bx, uint32_t by, uint32_t row0, uint32_t& x, uint32_t& y)
-{
-    if (MIPS) {
-        const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-        x = bx * 64u + (wave & 1u) * 32u + (lane & 31u);
-        y = row0 + by * 4u + (wave >> 1) * 2u + (lane >> 5);
-    } else {
-        x = bx * 64u + (threadIdx.x & 63u);
-        y = row0 + by * 4u + (threadIdx.x >> 6);
-    }
-}
-// The level of detail of this lane's reflection lookup; every lane of the wavefront calls it (converged).  `r` is the lane's
-// reflection vector when `covered`.  A neighbour the pass does not shade contributes a zero derivative (the oracle's definition).
-__device__ __forceinline__ float quad_reflection_lod(const LightParams& P, bool covered, f3 r, uint32_t x, uint32_t y)
-{
-    const unsigned long long mask = __builtin_amdgcn_ballot_w64(covered);
-    const uint32_t lane = threadIdx.x & 63u;
-    const f3 nx{ __shfl_xor(r.x, 1), __shfl_xor(r.y, 1), __shfl_xor(r.z, 1) };
-    const f3 ny{ __shfl_xor(r.x, 32), __shfl_xor(r.y, 32), __shfl_xor(r.z, 32) };
-    const bool hasX = (mask >> (lane ^ 1u)) & 1ull, hasY = (mask >> (lane ^ 32u)) & 1ull;
-    f3 ddx{ 0.0f, 0.0f, 0.0f }, ddy{ 0.0f, 0.0f, 0.0f };
-    if (hasX) ddx = (x & 1u) ? f3{ r.x - nx.x, r.y - nx.y, r.z - nx.z } : f3{ nx.x - r.x, nx.y - r.y, nx.z - r.z };
-    if (hasY) ddy = (y & 1u) ? f3{ r.x - ny.x, r.y - ny.y, r.z - ny.z } : f3{ ny.x - r.x, ny.y - r.y, ny.z - r.z };
-    return cube_lod(P.cubeDim, P.cubeLevels, r, ddx, ddy);
-}
-
 template <bool ZERO_RADIUS, bool FIX, bool MIPS = false>
 __global__ __launch_bounds__(256) void light_kernel(LightParams P, const f4a* __restrict__ g0,
                                                     const f4a* __restrict__ g1, const f4a* __restrict__ g2,
@@ -496,175 +439,7 @@ __global__ __launch_bounds__(256) void light_kernel(LightParams P, const f4a* __
                                                     const uint32_t* __restrict__ cube, uint32_t* __restrict__ out,
                                                     f4a* __restrict__ radiance, uint32_t row0, uint32_t row1)
 {
-    uint32_t bx, by;
-    tile_origin<0>(bx, by);
-    uint32_t x, y;
-    light_tile_pixel<MIPS>(bx, by, row0, x, y);
-    if (MIPS) {
-        const bool in = x < P.W && y < row1;
-        const uint32_t idx = in ? y * P.W + x : 0u;
-        const bool covered = in && (depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu;
-        f4a G0{ 0, 0, 0, 0 }, G2{ 0, 0, 0, 0 };
-        f3 r{ 0.0f, 0.0f, 0.0f };
-        if (covered) { G0 = g0[idx]; G2 = g2[idx]; r = reflection_dir(P, G0, G2); }
-        const float lod = quad_reflection_lod(P, covered, r, x, y);
-        if (!in) return;
-        f4 lit;
-        if (covered) lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX, CubeChain>(P, G0, g1[idx], G2, ambient, cube, NoPointLights(), CubeChain{ lod, cube_chain_flat(lod) });
-        else if (P.flags & CRYCHIC_LIGHT_SKY) lit = sky_pixel_chain(P, cube, x, y);
-        else lit = f4{ 0.690196097f, 0.768627524f, 0.870588303f, 1.0f };
-        if (radiance) radiance[idx] = f4a{ lit.x, lit.y, lit.z, lit.w };
-        out[idx] = pack_rgba8(lit);
-        return;
-    }
-    if (x >= P.W || y >= row1) return;
-    const uint32_t idx = y * P.W + x;
-    f4 lit;
-    // coverage: the reference re-rasterises the opaque items with LESS against depth cleared to 1.0
-    // (CRYCHIC.cpp:248,273) -- exactly the pixels whose normal/depth pass depth is below the clear value.
-    if ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu) {
-        lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX>(P, g0[idx], g1[idx], g2[idx], ambient, cube);
-    } else if (P.flags & CRYCHIC_LIGHT_SKY) {
-        lit = sky_pixel(P, cube, x, y);
-    } else {
-        lit = f4{ 0.690196097f, 0.768627524f, 0.870588303f, 1.0f };  // Colors::LightSteelBlue, CRYCHIC.cpp:247
-    }
-    if (radiance) radiance[idx] = f4a{ lit.x, lit.y, lit.z, lit.w };
-    out[idx] = pack_rgba8(lit);
-}
-
-// ---- deferred lighting with point lights (extension, BASELINE configs[4]) ------------------------------------------
-// Same pass plus NUM_POINT_LIGHTS point lights.  Tiled light culling in LDS: the 64 x 4-pixel tile of a workgroup
-// reduces the world-space bounding box of its covered pixels (wave shuffles, then LDS), every lane then tests lights
-// against the box (sphere of radius FalloffEnd vs AABB, conservatively inflated) and sets the light's bit in an LDS mask;
-// each pixel finally walks the set bits in ascending index order -- the accumulation order of the un-culled loop -- and
-// applies the exact per-pixel range test, so culling never changes a bit of the result.
-// SPOTS (light_spots_kernel): the spot lights of their own buffer are culled by the same sphere test in the same step into a
-// second mask, and walked after the point lights (the gLights order).  The cull stays spherical: a spot light contributes
-// outside its cone too (the 0.001 floor of PBR.hlsl:142), so only the range test is exact.
-// SHADOWED (light_spots_shadowed_kernel): spot lights k < shadows->count take their shadow factor (spot_shadow_factor), evaluated
-// only where the term is (in range).  The cull is unchanged: a shadow can only scale a term it already admits.
-// POINT_SHADOWED (light_point_shadows_kernel): point lights k < pointShadows->count take their cube shadow (PointShadowOf) the same
-// way.  The mask word is read once per wavefront (readfirstlane: every lane reads the same LDS word), so the walk's light index is
-// scalar, and with it the light's projection and map; the face is per lane (point_face's selects).
-template <bool ZERO_RADIUS, bool MIPS, bool SPOTS, bool SHADOWED = false, bool POINT_SHADOWED = false>
-__device__ __forceinline__ void light_local_tile(const LightParams& P, const f4a* __restrict__ g0, const f4a* __restrict__ g1,
-                                                 const f4a* __restrict__ g2, const uint32_t* __restrict__ depth,
-                                                 const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
-                                                 uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0, uint32_t row1,
-                                                 float (*s_box)[6], uint32_t* s_mask, const crychic_light* __restrict__ spots,
-                                                 uint32_t numSpots, uint32_t* s_spotMask, const SpotShadows* shadows = nullptr,
-                                                 const PointShadows* pointShadows = nullptr)
-{
-    uint32_t bx, by;
-    tile_origin<0>(bx, by);
-    uint32_t x, y;
-    light_tile_pixel<MIPS>(bx, by, row0, x, y);             // MIPS: 32 x 2 pixels per wavefront (quads inside a wavefront)
-    const bool inFrame = (x < P.W) && (y < row1);
-    const uint32_t idx = inFrame ? y * P.W + x : 0u;
-    const bool covered = inFrame && ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu);
-    f4a G0{ 0, 0, 0, 0 };
-    if (covered) G0 = g0[idx];
-
-    // 1. tile bounding box of the covered pixels' world positions
-    const float big = 3.0e38f;
-    float lo[3] = { covered ? G0.x : big, covered ? G0.y : big, covered ? G0.z : big };
-    float hi[3] = { covered ? G0.x : -big, covered ? G0.y : -big, covered ? G0.z : -big };
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            lo[c] = __builtin_fminf(lo[c], __shfl_xor(lo[c], off));
-            hi[c] = __builtin_fmaxf(hi[c], __shfl_xor(hi[c], off));
-        }
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0) { for (int c = 0; c < 3; ++c) { s_box[wave][c] = lo[c]; s_box[wave][3 + c] = hi[c]; } }
-    if (threadIdx.x < kMaxPointLights / 32) s_mask[threadIdx.x] = 0u;
-    if (SPOTS && threadIdx.x < kMaxSpotLights / 32) s_spotMask[threadIdx.x] = 0u;
-    __syncthreads();
-    float blo[3], bhi[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        blo[c] = __builtin_fminf(__builtin_fminf(s_box[0][c], s_box[1][c]), __builtin_fminf(s_box[2][c], s_box[3][c]));
-        bhi[c] = __builtin_fmaxf(__builtin_fmaxf(s_box[0][3 + c], s_box[1][3 + c]), __builtin_fmaxf(s_box[2][3 + c], s_box[3][3 + c]));
-    }
-    // 2. cull: light l touches the tile if dist(Position, box) <= FalloffEnd (inflated: the per-pixel test is the exact one)
-    auto touches = [&](const crychic_light& L) {
-        float d2 = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float p = L.Position[c];
-            const float e = __builtin_fmaxf(__builtin_fmaxf(blo[c] - p, p - bhi[c]), 0.0f);
-            d2 += e * e;
-        }
-        const float r = L.FalloffEnd * 1.0001f + 1.0e-3f;
-        return d2 <= r * r;
-    };
-    const bool anyCovered = blo[0] <= bhi[0];
-    if (anyCovered) {
-        for (uint32_t l = threadIdx.x; l < P.numPointLights; l += 256u) {
-            const crychic_light L = P.pointLights[l];
-            if (touches(L)) atomicOr(&s_mask[l >> 5], 1u << (l & 31u));
-        }
-        if (SPOTS)
-            for (uint32_t l = threadIdx.x; l < numSpots; l += 256u) {
-                const crychic_light L = spots[l];
-                if (touches(L)) atomicOr(&s_spotMask[l >> 5], 1u << (l & 31u));
-            }
-    }
-    __syncthreads();
-    float lod = 0.0f;
-    f4a G2{ 0, 0, 0, 0 };
-    if (MIPS) {                                              // every lane, converged: the quad neighbours' reflection vectors
-        f3 r{ 0.0f, 0.0f, 0.0f };
-        if (covered) { G2 = g2[idx]; r = reflection_dir(P, G0, G2); }
-        lod = quad_reflection_lod(P, covered, r, x, y);
-    }
-    if (!inFrame) return;
-
-    // 3. shade
-    f4 lit;
-    if (covered) {
-        auto culled = [&](f3 pos, f3 albedo, float roughness, float metalness, f3 normal, f3 view, f3& result, bool fixQ3, bool fixQ4) {
-            const uint32_t words = (P.numPointLights + 31u) >> 5;
-            for (uint32_t w = 0; w < words; ++w) {
-                uint32_t m = s_mask[w];
-                if (POINT_SHADOWED) m = __builtin_amdgcn_readfirstlane(m);
-                while (m) {
-                    const uint32_t b = (uint32_t)__builtin_ctz(m);
-                    m &= m - 1u;
-                    if (POINT_SHADOWED)
-                        pbr_point_light(P.pointLights[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4,
-                                        PointShadowOf{ pointShadows, pos, &P.pointLights[w * 32u + b], w * 32u + b });
-                    else
-                        pbr_point_light(P.pointLights[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
-                }
-            }
-            if (SPOTS) {
-                const uint32_t spotWords = (numSpots + 31u) >> 5;
-                for (uint32_t w = 0; w < spotWords; ++w) {
-                    uint32_t m = s_spotMask[w];
-                    while (m) {
-                        const uint32_t b = (uint32_t)__builtin_ctz(m);
-                        m &= m - 1u;
-                        if (SHADOWED)
-                            pbr_spot_light(spots[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4,
-                                           SpotShadowOf{ shadows, pos, w * 32u + b });
-                        else
-                            pbr_spot_light(spots[w * 32u + b], pos, albedo, roughness, metalness, normal, view, result, fixQ3, fixQ4);
-                    }
-                }
-            }
-        };
-        if (MIPS) lit = light_pixel<ZERO_RADIUS, decltype(culled), true, CubeChain>(P, G0, g1[idx], G2, ambient, cube, culled, CubeChain{ lod, cube_chain_flat(lod) });
-        else lit = light_pixel<ZERO_RADIUS, decltype(culled), true>(P, G0, g1[idx], g2[idx], ambient, cube, culled);
-    } else if (P.flags & CRYCHIC_LIGHT_SKY) {
-        lit = MIPS ? sky_pixel_chain(P, cube, x, y) : sky_pixel(P, cube, x, y);
-    } else {
-        lit = f4{ 0.690196097f, 0.768627524f, 0.870588303f, 1.0f };
-    }
-    if (radiance) radiance[idx] = f4a{ lit.x, lit.y, lit.z, lit.w };
-    out[idx] = pack_rgba8(lit);
+    light_frame_tile<ZERO_RADIUS, FIX, MIPS>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1);
 }
 
 template <bool ZERO_RADIUS, bool MIPS = false>
@@ -740,10 +515,6 @@ static int depth_margin()
 {
     static const int m = [] { const char* e = getenv("CRYCHIC_DEPTH_MARGIN"); return e ? atoi(e) : -1; }();
     return m;
-}
-static inline dim3 grid_for(uint32_t width, uint32_t rows, uint32_t rows_per_block = 4u)
-{
-    return dim3((width + 63u) / 64u, (rows + rows_per_block - 1u) / rows_per_block, 1);
 }
 
 hipError_t launch_depth_pairs(const crychic_ssao_constants& cb, const uint32_t* depth, void* edge_base, uint32_t W, uint32_t H, uint32_t stamp,
@@ -904,6 +675,9 @@ hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, 
     auto dispatch = [&](auto family) {
         return by_radius([&](auto z) { if (mips) family(z, std::true_type{}); else family(z, std::false_type{}); });
     };
+    // A half4 plane (CRYCHIC_GBUFFER_G*_F16): the format-aware kernels (light_formats.hip), which serve every light set
+    if (P.flags & CRYCHIC_GBUFFER_F16_MASK)
+        return launch_light_formats(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, rows, stream, spots, numSpots, shadows, pointShadows);
     if (pointShadows && pointShadows->count)
         return dispatch([&](auto z, auto m) { launch(light_point_shadows_kernel<z, m>, spots, numSpots, shadows ? *shadows : SpotShadows{},
                                                      *pointShadows); });

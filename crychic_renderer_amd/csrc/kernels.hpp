@@ -10,6 +10,12 @@ struct LightParams;
 struct SpotShadows;
 struct PointShadows;
 
+// Launch grid of the full-screen passes: a workgroup per 64 pixels x rows_per_block rows (shared by kernels.hip and light_formats.hip).
+inline dim3 grid_for(uint32_t width, uint32_t rows, uint32_t rows_per_block = 4u)
+{
+    return dim3((width + 63u) / 64u, (rows + rows_per_block - 1u) / rows_per_block, 1);
+}
+
 // D24 depth plane -> the decoded, BORDER-padded pairs plane inside the edge workspace (ssao_core.hpp "depth pairs") and the coarse
 // maps of the SSAO shortcuts, for the SSAO pass over half-res rows [row0, row0 + rows): those rows' texels and a margin (the whole
 // plane when the rows are the whole map; launch_ssao called with the same rows knows what was prepared).
@@ -46,11 +52,17 @@ hipError_t launch_blur_replay_chain(const crychic_ssao_constants& cb, const void
 // shadows: the first shadows->count spot lights shadowed (light_spots_shadowed_kernel); nullptr or count 0 = none.
 // pointShadows: the first pointShadows->count point lights shadowed (light_point_shadows_kernel, which takes the spot lights and
 // their shadows as well); nullptr or count 0 = the kernels above.
+// A CRYCHIC_GBUFFER_G*_F16 bit in P.flags: that plane's pointer addresses half4 texels, and the call goes to launch_light_formats.
 hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, const float* g2,
                         const uint32_t* depth, const uint16_t* ambient, const uint8_t* cube, uint8_t* out,
                         float* radiance, uint32_t row0, uint32_t rows, hipStream_t stream, const crychic_light* spots,
                         uint32_t numSpots, const SpotShadows* shadows, const PointShadows* pointShadows);
-
+// light_formats.hip: the same pass over planes of any format mix (P.flags' CRYCHIC_GBUFFER_G*_F16 bits) -- light_formats_kernel for
+// a frame without local lights, light_point_shadows_formats_kernel for every other.
+hipError_t launch_light_formats(const LightParams& P, const void* g0, const void* g1, const void* g2, const uint32_t* depth,
+                                const uint16_t* ambient, const uint8_t* cube, uint8_t* out, float* radiance, uint32_t row0, uint32_t rows,
+                                hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
+                                const PointShadows* pointShadows);
 
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
@@ -67,6 +79,7 @@ struct RasterPass {
     uint32_t* depth; void* normal; float* g0; float* g1; float* g2;
     void* workspace; size_t workspaceBytes;
     uint32_t gRow0, gRows;                  // G-buffer rows to render (a rank's strip); gRows == 0 = the whole target
+    uint32_t gbufferFlags;                  // CRYCHIC_GBUFFER_G*_F16: that plane's pointer (g0 / g1 / g2) addresses half4 texels
     const uint32_t* statusWord;             // OUT: device address of the pass's status word (bit 0: a vertex left the +-2^22 px
                                             // range and its triangle was dropped; bit 1: a vertex index outside the vertex buffer)
     // fused shadow pass (mode 0, nTargets 2..4): one ViewProj and one depth target per cascade, same items

@@ -791,6 +791,22 @@ CRY_HD bool light_dark_guard(f4a G0, f4a G1, f4a G2)
            (__builtin_fabsf(G2.x) < 3.0e38f) & (__builtin_fabsf(G2.y) < 3.0e38f) & (__builtin_fabsf(G2.z) < 3.0e38f);
 }
 
+// ---- G-buffer plane formats (crychic_hip.h CRYCHIC_GBUFFER_G*_F16) -----------------------------------
+// A plane is float4 texels or half4 texels (x in the low half of the first dword, the normal map's layout).  The format is storage
+// only: a half texel widens exactly (half_to_float, v_cvt_f32_f16: subnormals kept) and everything after the load is the fp32
+// arithmetic of light_pixel.  gbuffer_load decides by a branch on the plane's bit of P.flags -- a kernel argument, so the branch is
+// scalar -- and reads a half texel with one 8-byte load per lane (512 contiguous bytes per wavefront row).
+CRY_HD f4a gbuffer_widen(u2 t)
+{
+    return f4a{ half_to_float((uint16_t)(t.x & 0xFFFFu)), half_to_float((uint16_t)(t.x >> 16)),
+                half_to_float((uint16_t)(t.y & 0xFFFFu)), half_to_float((uint16_t)(t.y >> 16)) };
+}
+CRY_HD f4a gbuffer_load(const void* plane, uint32_t idx, uint32_t isHalf)
+{
+    if (isHalf) return gbuffer_widen(static_cast<const u2*>(plane)[idx]);
+    return static_cast<const f4a*>(plane)[idx];
+}
+
 // Point-light iteration policies of light_pixels (extension).
 struct NoPointLights {
     CRY_HD void operator()(f3, f3, float, float, f3, f3, f3&, bool, bool) const {}

@@ -192,6 +192,42 @@ __global__ __launch_bounds__(256) void resolve_kernel(int mode, const unsigned l
     }
 }
 
+// resolve_kernel with a format per G-buffer plane (RasterPass::gbufferFlags != 0): a half4 plane takes the same fp32 values through
+// float_to_half, four of them packed into one 8-byte store per lane (raster_core.hpp gbuffer_store); its clear value is zero bits.
+// Everything else as above.
+__global__ __launch_bounds__(256) void resolve_formats_kernel(int mode, const unsigned long long* __restrict__ vis, const SetupTri* __restrict__ tris,
+                                                              crychic_pass_constants_viewproj view, const crychic_material_data* __restrict__ materials,
+                                                              uint32_t nMaterials, const Texture* __restrict__ textures, uint32_t nTextures,
+                                                              uint32_t W, uint32_t H, uint32_t* __restrict__ depth, u2* __restrict__ normal,
+                                                              void* __restrict__ g0, void* __restrict__ g1, void* __restrict__ g2, uint32_t gLo,
+                                                              uint32_t gHi, uint32_t gbufferFlags)
+{
+    const uint32_t x = blockIdx.x * 64u + (threadIdx.x & 63u), y = blockIdx.y * 4u + (threadIdx.x >> 6);
+    if (x >= W || y >= H) return;
+    if (y < gLo || y >= gHi) { mode &= ~2; if (mode == 0) return; }
+    const uint32_t h0 = gbufferFlags & CRYCHIC_GBUFFER_G0_F16, h1 = gbufferFlags & CRYCHIC_GBUFFER_G1_F16, h2 = gbufferFlags & CRYCHIC_GBUFFER_G2_F16;
+    const uint32_t idx = y * W + x;
+    const uint64_t key = vis[idx];
+    const uint32_t serial = (uint32_t)(key & 0xFFFFFFFFull);
+    depth[idx] = (uint32_t)(key >> 32);
+    if (serial == 0) {
+        if (mode & 1) normal[idx] = u2{ 0u, 0x00003C00u };
+        if (mode & 2) {
+            const f4 zero{ 0.0f, 0.0f, 0.0f, 0.0f };
+            gbuffer_store(g0, idx, h0, zero); gbuffer_store(g1, idx, h1, zero); gbuffer_store(g2, idx, h2, zero);
+        }
+        return;
+    }
+    const ResolveOut r = resolve_pixel(mode, tris[serial - 1u], (int)x, (int)y, view.m, materials, nMaterials, textures, nTextures);
+    if (mode & 1)
+        normal[idx] = u2{ (uint32_t)float_to_half(r.normalV.x) | ((uint32_t)float_to_half(r.normalV.y) << 16), (uint32_t)float_to_half(r.normalV.z) };
+    if (mode & 2) {
+        gbuffer_store(g0, idx, h0, r.g0);
+        gbuffer_store(g1, idx, h1, r.g1);
+        gbuffer_store(g2, idx, h2, r.g2);
+    }
+}
+
 size_t raster_workspace_bytes(uint64_t triangles, uint32_t W, uint32_t H)
 {
     const uint64_t slots = triangles * (uint64_t)kSlotsPerTriangle;
@@ -264,9 +300,14 @@ hipError_t launch_raster_pass(RasterPass& p, hipStream_t stream)
 #undef CRY_RASTER
     }
     if (shadow) return hipGetLastError();
-    hipLaunchKernelGGL(resolve_kernel, dim3((p.W + 63u) / 64u, (p.H + 3u) / 4u), dim3(256), 0, stream, p.mode, vis, tris, view,
-                       p.materials, p.nMaterials, p.nTextures ? texDev : nullptr, p.nTextures, p.W, p.H, p.depth, (u2*)p.normal,
-                       (f4a*)p.g0, (f4a*)p.g1, (f4a*)p.g2, gLo, gHi);
+    if (p.gbufferFlags)
+        hipLaunchKernelGGL(resolve_formats_kernel, dim3((p.W + 63u) / 64u, (p.H + 3u) / 4u), dim3(256), 0, stream, p.mode, vis, tris, view,
+                           p.materials, p.nMaterials, p.nTextures ? texDev : nullptr, p.nTextures, p.W, p.H, p.depth, (u2*)p.normal,
+                           (void*)p.g0, (void*)p.g1, (void*)p.g2, gLo, gHi, p.gbufferFlags);
+    else
+        hipLaunchKernelGGL(resolve_kernel, dim3((p.W + 63u) / 64u, (p.H + 3u) / 4u), dim3(256), 0, stream, p.mode, vis, tris, view,
+                           p.materials, p.nMaterials, p.nTextures ? texDev : nullptr, p.nTextures, p.W, p.H, p.depth, (u2*)p.normal,
+                           (f4a*)p.g0, (f4a*)p.g1, (f4a*)p.g2, gLo, gHi);
     return hipGetLastError();
 }
 

@@ -221,6 +221,16 @@ CRY_HD uint16_t float_to_half(float f)
     return u;
 }
 
+// One texel of a G-buffer plane in the plane's format (crychic_hip.h CRYCHIC_GBUFFER_G*_F16): float4 as computed, or the same four
+// values through float_to_half packed into one 8-byte store (x in the low half of the first dword, the normal map's layout).
+CRY_HD void gbuffer_store(void* plane, uint32_t idx, uint32_t isHalf, f4 v)
+{
+    if (isHalf)
+        static_cast<u2*>(plane)[idx] = u2{ (uint32_t)float_to_half(v.x) | ((uint32_t)float_to_half(v.y) << 16),
+                                           (uint32_t)float_to_half(v.z) | ((uint32_t)float_to_half(v.w) << 16) };
+    else static_cast<f4a*>(plane)[idx] = f4a{ v.x, v.y, v.z, v.w };
+}
+
 // A material texture (gTextureMaps[], Common.hlsl:52): R8G8B8A8 levels stored back to back, level k = max(1, w >> k) x
 // max(1, h >> k) texels; mipLevels 0 or 1 = level 0 only.  Same layout as crychic_texture.
 struct Texture { const uint8_t* rgba8; uint32_t width, height, mipLevels; };

@@ -1,4 +1,4 @@
-"""python -m crychic_renderer_amd.demo [--size WxH] [--out frame.ppm] [--textures DIR] [--cube FILE.dds]
+"""python -m crychic_renderer_amd.demo [--size WxH] [--out frame.ppm] [--textures DIR] [--cube FILE.dds] [--gbuffer f32|mixed|f16]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present)."""
@@ -16,6 +16,8 @@ def main():
     ap.add_argument("--textures", default="", help="directory with the reference's DDS textures (else procedural stand-ins)")
     ap.add_argument("--cube", default="", help="a DDS cube map for the sky and the reflections, e.g. the reference's Textures/snowcube1024.dds "
                                                "(else a procedural one)")
+    ap.add_argument("--gbuffer", default="f32", choices=["f32", "mixed", "f16"],
+                    help="G-buffer plane formats: f32 = three float4 planes, mixed = G0 float4 with G1 and G2 half4, f16 = all three half4")
     a = ap.parse_args()
     W, H = (int(v) for v in a.size.lower().split("x"))
     import torch
@@ -27,7 +29,7 @@ def main():
     geo = SceneGeometry(ctx, g.cascade_scene_items(), g.reference_materials(), tex)
     sgeo = SceneGeometry(ctx, g.cascade_scene_items(shadow_layer=True))
     cube = scene.make_cubemap(256, ctx.device)
-    app = Crychic(ctx, W, H, torch.from_numpy(consts.randvec.copy()).to(ctx.device), cube, shadow_dim=a.shadow_dim)
+    app = Crychic(ctx, W, H, torch.from_numpy(consts.randvec.copy()).to(ctx.device), cube, shadow_dim=a.shadow_dim, gbuffer_formats=a.gbuffer)
     if a.cube:            # with the mip chain the file stores, as the reference binds it (CRYCHIC.cpp:1148-1151)
         chain, dim, levels = g.load_dds_cube_mips(a.cube)
         app.set_cube_map(torch.from_numpy(chain).to(ctx.device), dim=dim, levels=levels)

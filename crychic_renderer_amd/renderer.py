@@ -104,17 +104,48 @@ class Ssao:
                                     1 if horzBlur else 0, int(row0), int(rows), _stream(self.ctx.device)))
 
 
-class DeferredShading:
-    """DeferredShading.h:4-45: owns the G-buffer planes (R32G32B32A32_FLOAT, CRYCHIC.cpp:56-58).  The reference
-    allocates four; GBuffer3 carries no information (GBuffer.hlsl:29) and is not allocated here."""
+GBUFFER_FORMAT_NAMES = {"f32": ("f32", "f32", "f32"), "mixed": ("f32", "f16", "f16"), "f16": ("f16", "f16", "f16")}
+_GBUFFER_DTYPES = {"f32": torch.float32, "f16": torch.float16}
 
-    def __init__(self, ctx, width, height):
+
+def gbuffer_formats(formats):
+    """The per-plane formats ("f32" | "f16" for G0, G1, G2) of a name -- "f32", "mixed" (G0 float4, G1 + G2 half4: 32 bytes per
+    pixel) or "f16" (all three half4: 24 bytes, DXGI_FORMAT_R16G16B16A16_FLOAT) -- or of a sequence of three formats."""
+    if isinstance(formats, str):
+        formats = GBUFFER_FORMAT_NAMES.get(formats, (formats,))
+    formats = tuple(formats) if formats is not None else ()
+    if len(formats) != 3 or any(f not in _GBUFFER_DTYPES for f in formats):
+        raise CrychicError(-3, "G-buffer formats %r: 'f32', 'mixed', 'f16' or three of 'f32' / 'f16'" % (formats,))
+    return formats
+
+
+def gbuffer_flags(planes):
+    """The CRYCHIC_GBUFFER_G*_F16 bits of three G-buffer planes, from the tensors' dtypes."""
+    flags = 0
+    for k, g in enumerate(planes):
+        if g.dtype == torch.float16:
+            flags |= _lib.GBUFFER_G0_F16 << k
+        elif g.dtype != torch.float32:
+            raise CrychicError(-3, "G-buffer plane %d is %s: float32 or float16" % (k, g.dtype))
+    return flags
+
+
+class DeferredShading:
+    """DeferredShading.h:4-45: owns the G-buffer planes (R32G32B32A32_FLOAT in the reference, CRYCHIC.cpp:56-58).  The reference
+    allocates four; GBuffer3 carries no information (GBuffer.hlsl:29) and is not allocated here.  formats: each plane float4
+    ("f32") or half4 ("f16"), see gbuffer_formats; a plane is allocated at its own size."""
+
+    def __init__(self, ctx, width, height, formats=("f32", "f32", "f32")):
         self.ctx = ctx
+        self.mFormats = gbuffer_formats(formats)
         self.OnResize(width, height)
 
     def OnResize(self, newWidth, newHeight):  # DeferredShading.cpp:79-93
         self.mWidth, self.mHeight = newWidth, newHeight
-        self.mGBuffer = [torch.zeros((newHeight, newWidth, 4), device=self.ctx.device, dtype=torch.float32) for _ in range(3)]
+        self.mGBuffer = [torch.zeros((newHeight, newWidth, 4), device=self.ctx.device, dtype=_GBUFFER_DTYPES[f]) for f in self.mFormats]
+
+    def Format(self, plane):
+        return self.mFormats[plane]
 
     def Width(self):
         return self.mWidth
@@ -151,12 +182,12 @@ class Crychic:
     """Headless CRYCHIC (CRYCHIC.h:56-190): Draw() issues the hot part of CRYCHIC::Draw's deferred branch
     (CRYCHIC.cpp:220-221, 238-279) on this GPU's stream for the full-res rows [row0, row0 + rows)."""
 
-    def __init__(self, ctx, width, height, randvec, cube, shadow_dim=4096):
+    def __init__(self, ctx, width, height, randvec, cube, shadow_dim=4096, gbuffer_formats="f32"):
         self.ctx = ctx
         self.mClientWidth, self.mClientHeight = width, height
         self.mShadowMap = ShadowMap(ctx, shadow_dim, shadow_dim)
         self.mSsao = Ssao(ctx, width, height, randvec)
-        self.mDeferred = DeferredShading(ctx, width, height)
+        self.mDeferred = DeferredShading(ctx, width, height, gbuffer_formats)
         self.mCubeMap = cube
         self.mCubeMapLevels = 1      # set_cube_map: > 1 = mCubeMap is a flat mip chain (CRYCHIC_LIGHT_CUBE_LEVELS), mCubeMapSize its level-0 face size
         self.mCubeMapSize = None
@@ -178,11 +209,19 @@ class Crychic:
         self._pointShadow = None     # (PointShadows descriptor, [face pass constants, 6 per light], geometry)
         self._desc = None
 
+    def set_gbuffer_formats(self, formats):
+        """Re-allocates the G-buffer in the given formats (gbuffer_formats: "f32", "mixed", "f16" or three per-plane formats); its
+        contents are lost, as on a resize.  The producers and the lighting pass take each plane's format from its tensor."""
+        self.mDeferred = DeferredShading(self.ctx, self.mClientWidth, self.mClientHeight, formats)
+        self._desc = None
+
     def load_scene(self, planes):
-        """Install externally produced input planes (scene.make_scene) in place of the producer passes."""
+        """Install externally produced input planes (scene.make_scene) in place of the producer passes.  A G-buffer plane arrives in
+        float32 and is converted to its format here (torch's float32 -> float16: round to nearest even, subnormals kept, overflow to
+        infinity -- the producers' conversion); planes already in the format are installed as they are."""
         self.mDepthStencilBuffer = planes["depth"]
         self.mSsao.mNormalMap = planes["normal"]
-        self.mDeferred.mGBuffer = [planes["g0"], planes["g1"], planes["g2"]]
+        self.mDeferred.mGBuffer = [planes["g%d" % k].to(_GBUFFER_DTYPES[self.mDeferred.mFormats[k]]) for k in range(3)]
         self.mShadowMap.mShadowMap = planes["shadow"]
         self.mCubeMap = planes["cube"]
         self.mCubeMapLevels, self.mCubeMapSize = 1, None
@@ -197,6 +236,7 @@ class Crychic:
         f.W, f.H = W, H
         f.blurCount, f.numDirLights = int(self.blurCount), int(self.numDirLights)
         f.pcfSearchRadius, f.flags = float(self.pcfSearchRadius), int(self.flags) | ((int(self.mCubeMapLevels) & 15) << 16 if self.mCubeMapLevels > 1 else 0)
+        f.flags = (f.flags & ~_lib.GBUFFER_F16_MASK) | gbuffer_flags(self.mDeferred.mGBuffer)      # each plane's format: its tensor's dtype
         f.row0, f.rows = int(row0), int(H - row0 if rows is None else rows)
         f.normal_dev = self.mSsao.mNormalMap.data_ptr()
         f.depth_dev = self.mDepthStencilBuffer.data_ptr()
@@ -222,9 +262,10 @@ class Crychic:
         # per-frame host cost is one FFI call (matters once a strip takes tens of microseconds on 8 GPUs).  The key holds
         # every device pointer and size frame_desc() reads, so replacing any plane object invalidates the cached descriptor.
         ssao, sm = self.mSsao, self.mShadowMap.mShadowMap
+        g0, g1, g2 = self.mDeferred.mGBuffer
         key = (row0, rows, self.mBackBuffer.data_ptr(), ssao.mAmbientMap0.data_ptr(), ssao.mAmbientMap1.data_ptr(), ssao.mEdge.data_ptr(),
                ssao.mNormalMap.data_ptr(), ssao.mRandomVectorMap.data_ptr(), self.mDepthStencilBuffer.data_ptr(),
-               self.mDeferred.mGBuffer[0].data_ptr(), self.mDeferred.mGBuffer[1].data_ptr(), self.mDeferred.mGBuffer[2].data_ptr(),
+               g0.data_ptr(), g1.data_ptr(), g2.data_ptr(), g0.dtype, g1.dtype, g2.dtype,
                sm.data_ptr(), int(sm.shape[-1]), self.mCubeMap.data_ptr(), int(self.mCubeMapSize or self.mCubeMap.shape[1]), int(self.mCubeMapLevels),
                self.blurCount, self.numDirLights, self.pcfSearchRadius, self.flags,
                0 if self.mPointLights is None else self.mPointLights.data_ptr(),
@@ -491,6 +532,8 @@ class SceneGeometry:
         frame, G0..G2 for those rows only (crychic_draw_normals_depth_and_gbuffer_rows)."""
         H, W = int(depth.shape[0]), int(depth.shape[1])
         ws = self.workspace(W, H)
+        if gbuffer_flags(gbuffer):
+            return self._draw_gbuffer_formats(pass_cb, normal, gbuffer, depth, g_rows, ws)
         if g_rows is not None:
             check(lib.crychic_draw_normals_depth_and_gbuffer_rows(self.ctx.handle, C.byref(pass_cb), self.items, len(self.items), _ptr(self.materials),
                                                                   self.n_materials, self.textures, self.n_textures, _ptr(normal), _ptr(gbuffer[0]),
@@ -505,6 +548,8 @@ class SceneGeometry:
     def DrawGBuffer(self, pass_cb, gbuffer, depth, g_rows=None):  # CRYCHIC.cpp:2545-2571; g_rows = (row0, rows): scissored to a strip
         H, W = int(depth.shape[0]), int(depth.shape[1])
         ws = self.workspace(W, H)
+        if gbuffer_flags(gbuffer):
+            return self._draw_gbuffer_formats(pass_cb, None, gbuffer, depth, g_rows, ws)
         if g_rows is not None:
             check(lib.crychic_draw_gbuffer_rows(self.ctx.handle, C.byref(pass_cb), self.items, len(self.items), _ptr(self.materials), self.n_materials,
                                                 self.textures, self.n_textures, _ptr(gbuffer[0]), _ptr(gbuffer[1]), _ptr(gbuffer[2]), _ptr(depth), W, H,
@@ -513,3 +558,13 @@ class SceneGeometry:
         check(lib.crychic_draw_gbuffer(self.ctx.handle, C.byref(pass_cb), self.items, len(self.items), _ptr(self.materials), self.n_materials,
                                        self.textures, self.n_textures, _ptr(gbuffer[0]), _ptr(gbuffer[1]), _ptr(gbuffer[2]), _ptr(depth), W, H,
                                        _ptr(ws), ws.numel(), _stream(self.ctx.device)))
+
+    def _draw_gbuffer_formats(self, pass_cb, normal, gbuffer, depth, g_rows, ws):
+        """The G-buffer producers with a half4 plane among G0..G2 (each plane's format is its tensor's dtype): normal None = the
+        G-buffer pass alone, otherwise the fused pass."""
+        H, W = int(depth.shape[0]), int(depth.shape[1])
+        r0, rn = (0, 0) if g_rows is None else (int(g_rows[0]), int(g_rows[1]))
+        check(lib.crychic_draw_gbuffer_formats(self.ctx.handle, C.byref(pass_cb), self.items, len(self.items), _ptr(self.materials),
+                                               self.n_materials, self.textures, self.n_textures, _ptr(normal), _ptr(gbuffer[0]), _ptr(gbuffer[1]),
+                                               _ptr(gbuffer[2]), gbuffer_flags(gbuffer), _ptr(depth), W, H, r0, rn, _ptr(ws), ws.numel(),
+                                               _stream(self.ctx.device)))

@@ -168,6 +168,15 @@ public:
         if (mDeferred) { mDeferred->OnResize(mClientWidth, mClientHeight); mDeferred->BuildDescriptors(); }
     }
     void Resize(UINT w, UINT h) { mClientWidth = w; mClientHeight = h; OnResize(); }
+    // The G-buffer planes' formats (DeferredShading.h): re-creates mDeferred, its contents are lost as on a resize.  The default is
+    // the reference's, R32G32B32A32_FLOAT for all three; DrawGBuffer and Draw pass the formats on.
+    void SetGBufferFormat(DXGI_FORMAT g0, DXGI_FORMAT g1, DXGI_FORMAT g2)
+    {
+        const DXGI_FORMAT formats[3] = { g0, g1, g2 };
+        mCommandList->Flush();
+        mDeferred = std::make_unique<DeferredShading>(md3dDevice.get(), mClientWidth, mClientHeight, formats);
+        mDeferred->BuildDescriptors();
+    }
 
     void Update(const GameTimer& gt)  // CRYCHIC.cpp:130-170
     {
@@ -204,6 +213,7 @@ public:
         f.numDirLights = mNumDirLights;
         f.pcfSearchRadius = crychic_pcf_search_radius(mShadowMap->Width(), mPcfLiteral ? 1 : 0);
         f.flags = (mSkyEnabled ? CRYCHIC_LIGHT_SKY : 0u) | (mCubeMapLevels > 1 ? CRYCHIC_LIGHT_CUBE_LEVELS(mCubeMapLevels) : 0u);   // :278-279, :1148-1151
+        f.flags |= mDeferred->FormatFlags();                                                        // a half4 plane: its CRYCHIC_GBUFFER_G*_F16 bit
         f.row0 = mStripRow0; f.rows = mWholeFrame ? mClientHeight : mStripRows;                      // whole frame unless SetStrip / JoinNode
         f.normal_dev = mSsao->NormalMap()->Data();
         f.depth_dev = static_cast<const uint32_t*>(mDepthStencilBuffer->Data());
@@ -722,13 +732,21 @@ private:
         void* ws = RasterWorkspace(mSceneTriangles, mClientWidth, mClientHeight, &bytes);
         const PassConstants& cb = mCurrFrameResource->PassCB->Element(0);
         // the scissor rectangle of this pass (CRYCHIC.cpp:2547-2548) is this GPU's strip when the frame is shared (SetStrip / JoinNode)
-        CrychicThrowIfFailed(crychic_draw_gbuffer_rows(
-            md3dDevice->Ctx(), reinterpret_cast<const crychic_pass_constants*>(&cb), items.data(), (uint32_t)items.size(),
-            reinterpret_cast<const crychic_material_data*>(mCurrFrameResource->MaterialBuffer->Resource()->Data()), (uint32_t)mMaterials.size(),
-            mTextures.empty() ? nullptr : mTextures.data(), (uint32_t)mTextures.size(), static_cast<float*>(mDeferred->Resource(0)->Data()),
-            static_cast<float*>(mDeferred->Resource(1)->Data()), static_cast<float*>(mDeferred->Resource(2)->Data()),
-            static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth, mClientHeight, mStripRow0,
-            mWholeFrame ? mClientHeight : mStripRows, ws, bytes, mCommandList->Stream()));
+        const auto* passCB = reinterpret_cast<const crychic_pass_constants*>(&cb);
+        const auto* mats = reinterpret_cast<const crychic_material_data*>(mCurrFrameResource->MaterialBuffer->Resource()->Data());
+        const crychic_texture* tex = mTextures.empty() ? nullptr : mTextures.data();
+        void* g[3] = { mDeferred->Resource(0)->Data(), mDeferred->Resource(1)->Data(), mDeferred->Resource(2)->Data() };
+        const uint32_t rows = mWholeFrame ? mClientHeight : mStripRows;
+        if (mDeferred->FormatFlags())       // a half4 plane among G0..G2; float4 planes keep the entry (and its argument checks) they had
+            CrychicThrowIfFailed(crychic_draw_gbuffer_formats(md3dDevice->Ctx(), passCB, items.data(), (uint32_t)items.size(), mats, (uint32_t)mMaterials.size(),
+                                                              tex, (uint32_t)mTextures.size(), nullptr, g[0], g[1], g[2], mDeferred->FormatFlags(),
+                                                              static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth, mClientHeight, mStripRow0,
+                                                              rows, ws, bytes, mCommandList->Stream()));
+        else
+            CrychicThrowIfFailed(crychic_draw_gbuffer_rows(md3dDevice->Ctx(), passCB, items.data(), (uint32_t)items.size(), mats, (uint32_t)mMaterials.size(),
+                                                           tex, (uint32_t)mTextures.size(), static_cast<float*>(g[0]), static_cast<float*>(g[1]),
+                                                           static_cast<float*>(g[2]), static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth,
+                                                           mClientHeight, mStripRow0, rows, ws, bytes, mCommandList->Stream()));
     }
     void DrawNormalsDepthAndGBuffer()  // DrawNormalsAndDepth + DrawGBuffer: same items, same ViewProj, same visibility -> one rasterisation
     {
@@ -736,13 +754,21 @@ private:
         size_t bytes;
         void* ws = RasterWorkspace(mSceneTriangles, mClientWidth, mClientHeight, &bytes);
         const PassConstants& cb = mCurrFrameResource->PassCB->Element(0);
-        CrychicThrowIfFailed(crychic_draw_normals_depth_and_gbuffer_rows(
-            md3dDevice->Ctx(), reinterpret_cast<const crychic_pass_constants*>(&cb), items.data(), (uint32_t)items.size(),
-            reinterpret_cast<const crychic_material_data*>(mCurrFrameResource->MaterialBuffer->Resource()->Data()), (uint32_t)mMaterials.size(),
-            mTextures.empty() ? nullptr : mTextures.data(), (uint32_t)mTextures.size(), mSsao->NormalMap()->Data(),
-            static_cast<float*>(mDeferred->Resource(0)->Data()), static_cast<float*>(mDeferred->Resource(1)->Data()),
-            static_cast<float*>(mDeferred->Resource(2)->Data()), static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth, mClientHeight,
-            mStripRow0, mWholeFrame ? mClientHeight : mStripRows, ws, bytes, mCommandList->Stream()));
+        const auto* passCB = reinterpret_cast<const crychic_pass_constants*>(&cb);
+        const auto* mats = reinterpret_cast<const crychic_material_data*>(mCurrFrameResource->MaterialBuffer->Resource()->Data());
+        const crychic_texture* tex = mTextures.empty() ? nullptr : mTextures.data();
+        void* g[3] = { mDeferred->Resource(0)->Data(), mDeferred->Resource(1)->Data(), mDeferred->Resource(2)->Data() };
+        const uint32_t rows = mWholeFrame ? mClientHeight : mStripRows;
+        if (mDeferred->FormatFlags())       // a half4 plane among G0..G2; float4 planes keep the entry (and its argument checks) they had
+            CrychicThrowIfFailed(crychic_draw_gbuffer_formats(md3dDevice->Ctx(), passCB, items.data(), (uint32_t)items.size(), mats, (uint32_t)mMaterials.size(),
+                                                              tex, (uint32_t)mTextures.size(), mSsao->NormalMap()->Data(), g[0], g[1], g[2],
+                                                              mDeferred->FormatFlags(), static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth,
+                                                              mClientHeight, mStripRow0, rows, ws, bytes, mCommandList->Stream()));
+        else
+            CrychicThrowIfFailed(crychic_draw_normals_depth_and_gbuffer_rows(
+                md3dDevice->Ctx(), passCB, items.data(), (uint32_t)items.size(), mats, (uint32_t)mMaterials.size(), tex, (uint32_t)mTextures.size(),
+                mSsao->NormalMap()->Data(), static_cast<float*>(g[0]), static_cast<float*>(g[1]), static_cast<float*>(g[2]),
+                static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth, mClientHeight, mStripRow0, rows, ws, bytes, mCommandList->Stream()));
     }
     void UpdateCascadeShadowTransform(const GameTimer&)  // CRYCHIC.cpp:634-815
     {

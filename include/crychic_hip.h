@@ -201,6 +201,26 @@ int crychic_ssao_compute(crychic_ctx* ctx, const crychic_ssao_constants* cb, con
 #define CRYCHIC_FIX_Q1 0x100u
 #define CRYCHIC_FIX_Q3 0x200u
 #define CRYCHIC_FIX_Q4 0x400u
+/* The G-buffer plane formats.  Each of G0, G1 and G2 is, independently, float4 texels (16 bytes, the default) or
+ * half4 texels (8 bytes: IEEE binary16, x in the low half of the first dword -- DXGI_FORMAT_R16G16B16A16_FLOAT, the normal map's
+ * layout).  A set bit in `flags` (every crychic_deferred_light* entry, crychic_frame_desc.flags, crychic_draw_gbuffer_formats) says that
+ * the plane's pointer addresses half4 texels; the `const float*` / `float*` parameters keep their type and the caller casts.  All
+ * eight combinations are valid, flags without these bits is every earlier release's call.
+ * The format is STORAGE ONLY.  Write (producers): the fp32 value the pass computes is rounded to nearest even, subnormals kept,
+ * overflow (|x| > 65504 after rounding) to infinity -- the render-target conversion of the normal map; the clear value is all-zero
+ * bits.  Read (lighting): the texel widens exactly, and everything after the load is the fp32 arithmetic of the float4 path; there
+ * is no fp16 arithmetic anywhere.  So: light(planes in any mix) == light(those planes widened to float4) bit for bit, and
+ * producer(mix) == round_to_half(producer's float4 planes) bit for bit on the half planes, the other outputs unchanged.
+ * fp16 WORLD POSITIONS ARE COARSE: G0.xyz has an ulp of 1/64 unit at 16..32 units from the origin (1/8 at 128..256), which is what
+ * the format means in D3D too.  G0 float4 with G1 + G2 half4 (32 bytes per pixel instead of 48) is the practical mix; all three half4
+ * (24 bytes) is what DeferredShading(..., DXGI_FORMAT_R16G16B16A16_FLOAT) means. */
+#define CRYCHIC_GBUFFER_G0_F16 0x1000u
+#define CRYCHIC_GBUFFER_G1_F16 0x2000u
+#define CRYCHIC_GBUFFER_G2_F16 0x4000u
+#define CRYCHIC_GBUFFER_F16_MASK 0x7000u
+/* Bytes of plane `plane` (0, 1, 2 = G0, G1, G2) of a W x H G-buffer under `flags` (their CRYCHIC_GBUFFER_* bits); 0 for any other
+ * plane index.  Pure host arithmetic. */
+size_t crychic_gbuffer_plane_bytes(uint32_t W, uint32_t H, uint32_t flags, int plane);
 
 /* Full-screen replacement of the geometry re-draw at CRYCHIC.cpp:238-273 over full-res rows
  * [row0, row0+rows): pixels with depth < 1.0 are lit, the others get Colors::LightSteelBlue
@@ -563,6 +583,17 @@ int crychic_draw_normals_depth_and_gbuffer_rows(crychic_ctx* ctx, const crychic_
                                                 const crychic_texture* textures, uint32_t nTextures, void* normal_dev, float* g0_dev,
                                                 float* g1_dev, float* g2_dev, uint32_t* depth_dev, uint32_t W, uint32_t H,
                                                 uint32_t gRow0, uint32_t gRows, void* workspace_dev, size_t workspaceBytes, void* stream);
+
+/* The four G-buffer producers above with a format per plane: gbufferFlags = CRYCHIC_GBUFFER_G*_F16 bits (a set bit: that plane's
+ * pointer addresses half4 texels, sized by crychic_gbuffer_plane_bytes); any other bit is CRYCHIC_E_INVALID_ARG.  normal_dev == NULL is
+ * the G-buffer pass alone (crychic_draw_gbuffer_rows), otherwise the fused pass (crychic_draw_normals_depth_and_gbuffer_rows);
+ * gRows == 0 is the whole target.  With gbufferFlags == 0 every plane is bit-identical to those entries; a half4 plane holds the
+ * float4 plane's values rounded to nearest even (cleared texels: zero bits); depth, the normal map and float4 planes do not change. */
+int crychic_draw_gbuffer_formats(crychic_ctx* ctx, const crychic_pass_constants* passCB, const crychic_draw_item* items,
+                                 uint32_t nItems, const crychic_material_data* materials_dev, uint32_t nMaterials,
+                                 const crychic_texture* textures, uint32_t nTextures, void* normal_dev, void* g0_dev, void* g1_dev,
+                                 void* g2_dev, uint32_t gbufferFlags, uint32_t* depth_dev, uint32_t W, uint32_t H, uint32_t gRow0,
+                                 uint32_t gRows, void* workspace_dev, size_t workspaceBytes, void* stream);
 
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
