@@ -13,6 +13,7 @@
 #include "crychic_hip.h"
 #include "kernels.hpp"
 #include "light_core.hpp"
+#include "light_bind.hpp"
 #include "ssao_core.hpp"
 #include "blur_tiles.hpp"
 #include "raster_core.hpp"
@@ -133,34 +134,13 @@ int fill_light_params(cry::LightParams& P, const crychic_pass_constants* cb, con
     if (shadowDim < 2 || cubeDim < 2 || shadowDim > 16384 || cubeDim > 8192)
         return fail(CRYCHIC_E_INVALID_ARG, "shadowDim %u / cubeDim %u outside [2, 16384] / [2, 8192]", shadowDim, cubeDim);
     if (!(pcfSearchRadius >= 0.0f)) return fail(CRYCHIC_E_INVALID_ARG, "pcfSearchRadius must be >= 0");
-    memcpy(P.ViewProjTex, cb->ViewProjTex, sizeof P.ViewProjTex);
-    memcpy(P.ShadowTransforms, cb->ShadowTransforms, sizeof P.ShadowTransforms);  // cascades 0..3
-    memcpy(P.InvProj, cb->InvProj, sizeof P.InvProj);
-    memcpy(P.InvView, cb->InvView, sizeof P.InvView);
-    memcpy(P.EyePosW, cb->EyePosW, sizeof P.EyePosW);
-    P.pcfSearchRadius = pcfSearchRadius;
-    memcpy(P.AmbientLight, cb->AmbientLight, sizeof P.AmbientLight);
-    memcpy(P.Lights, cb->Lights, sizeof P.Lights);
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 4; ++i)
         if (!shadow[i]) return fail(CRYCHIC_E_INVALID_ARG, "shadow cascade %d is null", i);
-        P.shadow[i] = shadow[i];
-    }
-    P.shadowDim = shadowDim;
-    P.cubeDim = cubeDim;
-    P.W = W;
-    P.H = H;
-    P.numDirLights = numDirLights;
-    P.flags = flags;
-    // CRYCHIC_LIGHT_CUBE_LEVELS: the cube map's mip chain (0 / 1 = level 0 alone); a chain ends at 1 x 1 at the latest
-    P.cubeLevels = (flags >> 16) & 15u;
-    { uint32_t full = 1; for (uint32_t m = cubeDim; m > 1u; m >>= 1) ++full;
-      if (P.cubeLevels > full) return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", P.cubeLevels, cubeDim, full); }
-    P.shadowWIsOne = cry::light_shadow_w_is_one(P.ShadowTransforms) ? 1u : 0u;
-    P.darkLights = cry::light_dark_mask(P.Lights, numDirLights);
-    P.unitLights = cry::light_dark_lengths_ok(P.Lights, numDirLights) ? 1u : 0u;
-    P.rcpW = cry::rcp((float)W);          // sky_pixel's pixel-centre uv: (x + 0.5) * rcp(W), the reciprocal taken once
-    P.rcpH = cry::rcp((float)H);
-    cry::light_params_derive(P);
+    // CRYCHIC_LIGHT_CUBE_LEVELS: a chain ends at 1 x 1 at the latest
+    { const uint32_t levels = (flags >> 16) & 15u;
+      uint32_t full = 1; for (uint32_t m = cubeDim; m > 1u; m >>= 1) ++full;
+      if (levels > full) return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", levels, cubeDim, full); }
+    cry::bind_light_params(P, *cb, shadow, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags);
     return 0;
 }
 
@@ -172,23 +152,16 @@ int bind_spot_lights(cry::LightParams& P, cry::SpotShadows& S, const crychic_pas
         return fail(CRYCHIC_E_INVALID_ARG, "numPointLights %u (max %u) / null light buffer", nPoints, cry::kMaxPointLights);
     if (nSpots > cry::kMaxSpotLights || (nSpots && !spots))
         return fail(CRYCHIC_E_INVALID_ARG, "numSpotLights %u (max %u) / null spot light buffer", nSpots, cry::kMaxSpotLights);
-    P.pointLights = points;
-    P.numPointLights = nPoints;
-    std::memset(&S, 0, sizeof S);
-    if (!d || d->count == 0) return 0;
-    if (d->count > CRYCHIC_MAX_SPOT_SHADOWS || d->count > nSpots)
-        return fail(CRYCHIC_E_INVALID_ARG, "spot shadows: count %u (max %u, and at most numSpotLights %u)", d->count,
+    cry::bind_point_lights(P, points, nPoints);
+    const uint32_t count = d ? d->count : 0u;
+    if (count > CRYCHIC_MAX_SPOT_SHADOWS || count > nSpots)
+        return fail(CRYCHIC_E_INVALID_ARG, "spot shadows: count %u (max %u, and at most numSpotLights %u)", count,
                     (unsigned)CRYCHIC_MAX_SPOT_SHADOWS, nSpots);
-    if (d->dim < 2 || d->dim > CRYCHIC_MAX_SPOT_SHADOW_DIM)          // 2 texels at least, as the cascades: a footprint row is one pair
+    if (count && (d->dim < 2 || d->dim > CRYCHIC_MAX_SPOT_SHADOW_DIM))          // 2 texels at least, as the cascades: a footprint row is one pair
         return fail(CRYCHIC_E_INVALID_ARG, "spot shadows: dim %u (2 .. %u)", d->dim, (unsigned)CRYCHIC_MAX_SPOT_SHADOW_DIM);
-    for (uint32_t k = 0; k < d->count; ++k) {
-        if (!d->maps[k]) return fail(CRYCHIC_E_INVALID_ARG, "spot shadows: null map %u of %u", k, d->count);
-        S.maps[k] = d->maps[k];
-        std::memcpy(S.T[k], cb->ShadowTransforms[4 + k], sizeof S.T[k]);
-    }
-    S.count = d->count;
-    S.dim = d->dim;
-    S.dx = 1.0f / (float)d->dim;                       // IEEE division on the host: correctly rounded
+    for (uint32_t k = 0; k < count; ++k)
+        if (!d->maps[k]) return fail(CRYCHIC_E_INVALID_ARG, "spot shadows: null map %u of %u", k, count);
+    cry::bind_spot_shadows(S, *cb, d ? d->maps : nullptr, count, d ? d->dim : 0u);
     return 0;
 }
 
@@ -201,23 +174,16 @@ int bind_local_lights(cry::LightParams& P, cry::SpotShadows& S, cry::PointShadow
                       const crychic_spot_shadows* d, const crychic_point_shadows* pd)
 {
     if (int rc = bind_spot_lights(P, S, cb, points, nPoints, spots, nSpots, d)) return rc;
-    std::memset(&PS, 0, sizeof PS);
-    if (!pd || pd->count == 0) return 0;
-    if (pd->count > CRYCHIC_MAX_POINT_SHADOWS || pd->count > nPoints)
-        return fail(CRYCHIC_E_INVALID_ARG, "point shadows: count %u (max %u, and at most numPointLights %u)", pd->count,
+    const uint32_t count = pd ? pd->count : 0u;
+    if (count > CRYCHIC_MAX_POINT_SHADOWS || count > nPoints)
+        return fail(CRYCHIC_E_INVALID_ARG, "point shadows: count %u (max %u, and at most numPointLights %u)", count,
                     (unsigned)CRYCHIC_MAX_POINT_SHADOWS, nPoints);
-    if (pd->dim < CRYCHIC_MIN_POINT_SHADOW_DIM || pd->dim > CRYCHIC_MAX_SPOT_SHADOW_DIM)     // the widened faces need 2 texels of rim
+    if (count && (pd->dim < CRYCHIC_MIN_POINT_SHADOW_DIM || pd->dim > CRYCHIC_MAX_SPOT_SHADOW_DIM))     // the widened faces need 2 texels of rim
         return fail(CRYCHIC_E_INVALID_ARG, "point shadows: dim %u (%u .. %u)", pd->dim, (unsigned)CRYCHIC_MIN_POINT_SHADOW_DIM,
                     (unsigned)CRYCHIC_MAX_SPOT_SHADOW_DIM);
-    for (uint32_t k = 0; k < pd->count; ++k) {
-        if (!pd->maps[k]) return fail(CRYCHIC_E_INVALID_ARG, "point shadows: null map %u of %u", k, pd->count);
-        PS.maps[k] = pd->maps[k];
-        for (int i = 0; i < 4; ++i)                        // transposed: row i of M = column i of shadowProj (as the spot T)
-            for (int j = 0; j < 4; ++j) PS.M[k][4 * i + j] = pd->shadowProj[k][4 * j + i];
-    }
-    PS.count = pd->count;
-    PS.dim = pd->dim;
-    PS.dx = 1.0f / (float)pd->dim;                     // IEEE division on the host: correctly rounded
+    for (uint32_t k = 0; k < count; ++k)
+        if (!pd->maps[k]) return fail(CRYCHIC_E_INVALID_ARG, "point shadows: null map %u of %u", k, count);
+    cry::bind_point_shadows(PS, pd ? pd->maps : nullptr, pd ? &pd->shadowProj[0][0] : nullptr, count, pd ? pd->dim : 0u);
     return 0;
 }
 

@@ -10,6 +10,7 @@
 #include "ssao_core.hpp"
 #include "blur_tiles.hpp"
 #include "light_core.hpp"
+#include "light_bind.hpp"
 #include "light_tiles.hpp"
 
 namespace cry {
@@ -675,22 +676,28 @@ hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, 
     auto dispatch = [&](auto family) {
         return by_radius([&](auto z) { if (mips) family(z, std::true_type{}); else family(z, std::false_type{}); });
     };
-    // A half4 plane (CRYCHIC_GBUFFER_G*_F16): the format-aware kernels (light_formats.hip), which serve every light set
-    if (P.flags & CRYCHIC_GBUFFER_F16_MASK)
+    const LightFamily family = light_family(P.flags, P.numPointLights, numSpots, shadows ? shadows->count : 0u,
+                                            pointShadows ? pointShadows->count : 0u, P.cubeLevels);
+    switch (family) {
+    case LightFamily::FormatsFrame:
+    case LightFamily::FormatsLocal:               // a half4 plane: the format-aware kernels (light_formats.hip), which serve every light set
         return launch_light_formats(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, rows, stream, spots, numSpots, shadows, pointShadows);
-    if (pointShadows && pointShadows->count)
+    case LightFamily::PointShadows:
         return dispatch([&](auto z, auto m) { launch(light_point_shadows_kernel<z, m>, spots, numSpots, shadows ? *shadows : SpotShadows{},
                                                      *pointShadows); });
-    if (numSpots && shadows && shadows->count)
+    case LightFamily::SpotsShadowed:
         return dispatch([&](auto z, auto m) { launch(light_spots_shadowed_kernel<z, m>, spots, numSpots, *shadows); });
-    if (numSpots)
+    case LightFamily::Spots:
         return dispatch([&](auto z, auto m) { launch(light_spots_kernel<z, m>, spots, numSpots); });
-    if (P.numPointLights)
+    case LightFamily::Points:
         return dispatch([&](auto z, auto m) { launch(light_points_kernel<z, m>); });
-    if (mips)                                     // FIX compiled in: the chain is not the benchmark's instantiation
-        return by_radius([&](auto z) { launch(light_kernel<z, true, true>); });
-    const bool fix = (P.flags & (CRYCHIC_FIX_Q1 | CRYCHIC_FIX_Q3 | CRYCHIC_FIX_Q4)) != 0;
-    return by_radius([&](auto z) { if (fix) launch(light_kernel<z, true>); else launch(light_kernel<z, false>); });
+    case LightFamily::FrameFix:
+    case LightFamily::Frame:
+        if (mips)                                 // FrameFix: FIX compiled in, the chain is not the benchmark's instantiation
+            return by_radius([&](auto z) { launch(light_kernel<z, true, true>); });
+        return by_radius([&](auto z) { if (family == LightFamily::FrameFix) launch(light_kernel<z, true>); else launch(light_kernel<z, false>); });
+    }
+    return hipErrorInvalidValue;
 }
 
 }  // namespace cry

@@ -1,0 +1,117 @@
+// light_bind.hpp -- host side of one lighting call: what the kernels take by value (LightParams, SpotShadows, PointShadows) from the
+// caller's arguments, and which kernel family serves the call.  Plain C++: no HIP runtime call, nothing that can fail -- api.cpp
+// validates first and reports; the host build of the kernel bodies (tests/hostsim) binds through the same functions, so the CPU
+// tier executes the binding the library ships.
+#pragma once
+#include <cstring>
+#include "light_core.hpp"
+
+namespace cry {
+
+// The frame's constants and the four cascades into P, with everything the kernels expect precomputed on the host.  Leaves
+// P.pointLights / P.numPointLights alone (bind_point_lights).
+inline void bind_light_params(LightParams& P, const crychic_pass_constants& cb, const uint32_t* const shadow[4], uint32_t shadowDim,
+                              uint32_t cubeDim, uint32_t W, uint32_t H, int numDirLights, float pcfSearchRadius, uint32_t flags)
+{
+    std::memcpy(P.ViewProjTex, cb.ViewProjTex, sizeof P.ViewProjTex);
+    std::memcpy(P.ShadowTransforms, cb.ShadowTransforms, sizeof P.ShadowTransforms);  // cascades 0..3
+    std::memcpy(P.InvProj, cb.InvProj, sizeof P.InvProj);
+    std::memcpy(P.InvView, cb.InvView, sizeof P.InvView);
+    std::memcpy(P.EyePosW, cb.EyePosW, sizeof P.EyePosW);
+    P.pcfSearchRadius = pcfSearchRadius;
+    std::memcpy(P.AmbientLight, cb.AmbientLight, sizeof P.AmbientLight);
+    std::memcpy(P.Lights, cb.Lights, sizeof P.Lights);
+    for (int i = 0; i < 4; ++i) P.shadow[i] = shadow[i];
+    P.shadowDim = shadowDim;
+    P.cubeDim = cubeDim;
+    P.W = W;
+    P.H = H;
+    P.numDirLights = numDirLights;
+    P.flags = flags;
+    // CRYCHIC_LIGHT_CUBE_LEVELS: the cube map's mip chain (0 / 1 = level 0 alone); a chain ends at 1 x 1 at the latest
+    P.cubeLevels = (flags >> 16) & 15u;
+    P.shadowWIsOne = light_shadow_w_is_one(P.ShadowTransforms) ? 1u : 0u;
+    P.darkLights = light_dark_mask(P.Lights, numDirLights);
+    P.unitLights = light_dark_lengths_ok(P.Lights, numDirLights) ? 1u : 0u;
+    P.rcpW = rcp((float)W);          // sky_pixel's pixel-centre uv: (x + 0.5) * rcp(W), the reciprocal taken once
+    P.rcpH = rcp((float)H);
+    light_params_derive(P);
+}
+
+// The point lights of the pass (a device buffer when there are any).  Touches none of P's other fields.
+inline void bind_point_lights(LightParams& P, const crychic_light* points, uint32_t nPoints)
+{
+    P.pointLights = points;
+    P.numPointLights = nPoints;
+}
+
+// The first `count` spot shadow maps and cb.ShadowTransforms[4 + k] into S.  count 0 leaves S zeroed (S.count = 0): the kernels
+// without spot shadows.
+inline void bind_spot_shadows(SpotShadows& S, const crychic_pass_constants& cb, const uint32_t* const* maps, uint32_t count, uint32_t dim)
+{
+    std::memset(&S, 0, sizeof S);
+    if (count == 0) return;
+    for (uint32_t k = 0; k < count; ++k) {
+        S.maps[k] = maps[k];
+        std::memcpy(S.T[k], cb.ShadowTransforms[4 + k], sizeof S.T[k]);
+    }
+    S.count = count;
+    S.dim = dim;
+    S.dx = 1.0f / (float)dim;                          // IEEE division on the host: correctly rounded
+}
+
+// The first `count` cube shadow maps and their projections into PS.  shadowProj: 16 floats per light, untransposed
+// (crychic_update_point_shadow_transforms).  count 0 leaves PS zeroed: the kernels without point shadows.
+inline void bind_point_shadows(PointShadows& PS, const uint32_t* const* maps, const float* shadowProj, uint32_t count, uint32_t dim)
+{
+    std::memset(&PS, 0, sizeof PS);
+    if (count == 0) return;
+    for (uint32_t k = 0; k < count; ++k) {
+        PS.maps[k] = maps[k];
+        for (int i = 0; i < 4; ++i)                        // transposed: row i of M = column i of shadowProj (as the spot T)
+            for (int j = 0; j < 4; ++j) PS.M[k][4 * i + j] = shadowProj[16 * k + 4 * j + i];
+    }
+    PS.count = count;
+    PS.dim = dim;
+    PS.dx = 1.0f / (float)dim;                         // IEEE division on the host: correctly rounded
+}
+
+// ---- which kernels serve a lighting call -------------------------------------------------------------------------
+// One family per set of kernel arguments; ZERO_RADIUS and MIPS (P.cubeLevels > 1) select the instantiation inside every family.
+enum class LightFamily {
+    Frame,            // light_kernel<z, false>: no local light, no CRYCHIC_FIX_* bit, no chain -- the reference as written
+    FrameFix,         // light_kernel<z, true, mips>: FIX compiled in (the chain is not the benchmark's instantiation)
+    Points,           // light_points_kernel
+    Spots,            // light_spots_kernel: point lights, then spot lights
+    SpotsShadowed,    // light_spots_shadowed_kernel: SpotShadowOf on the spot lights
+    PointShadows,     // light_point_shadows_kernel: PointShadowOf on the point lights, and the spot lights with SpotShadowOf even at a
+                      // spot shadow count of 0 (factor 1)
+    FormatsFrame,     // light_formats_kernel: a half4 plane (CRYCHIC_GBUFFER_G*_F16), no local light
+    FormatsLocal,     // light_point_shadows_formats_kernel: a half4 plane and local lights of whatever kind; both shadow functors
+                      // whatever the counts
+};
+inline LightFamily light_family(uint32_t flags, uint32_t numPointLights, uint32_t numSpots, uint32_t spotShadowCount,
+                                uint32_t pointShadowCount, uint32_t cubeLevels)
+{
+    if (flags & CRYCHIC_GBUFFER_F16_MASK) return (numPointLights || numSpots) ? LightFamily::FormatsLocal : LightFamily::FormatsFrame;
+    if (pointShadowCount) return LightFamily::PointShadows;
+    if (numSpots && spotShadowCount) return LightFamily::SpotsShadowed;
+    if (numSpots) return LightFamily::Spots;
+    if (numPointLights) return LightFamily::Points;
+    const bool fix = (flags & (CRYCHIC_FIX_Q1 | CRYCHIC_FIX_Q3 | CRYCHIC_FIX_Q4)) != 0;
+    return (cubeLevels > 1u || fix) ? LightFamily::FrameFix : LightFamily::Frame;
+}
+// What a family's kernels compile in: every family but Frame instantiates light_pixel with FIX; the local families walk lights
+// (light_local_tile); SHADOWED / POINT_SHADOWED of light_local_tile.
+constexpr bool light_family_fix(LightFamily f) { return f != LightFamily::Frame; }
+constexpr bool light_family_local(LightFamily f)
+{
+    return f != LightFamily::Frame && f != LightFamily::FrameFix && f != LightFamily::FormatsFrame;
+}
+constexpr bool light_family_spot_shadows(LightFamily f)
+{
+    return f == LightFamily::SpotsShadowed || f == LightFamily::PointShadows || f == LightFamily::FormatsLocal;
+}
+constexpr bool light_family_point_shadows(LightFamily f) { return f == LightFamily::PointShadows || f == LightFamily::FormatsLocal; }
+
+}  // namespace cry

@@ -833,10 +833,6 @@ struct AllLocalLights {
         }
     }
 };
-// The names the point-light and shadowed-spot host builds were written against: the same functor, with the members they do not
-// initialise left null / 0 ({ points, n } = no spot lights; { points, nPoints, spots, nSpots, shadows } = all of them).
-using AllPointLights = AllLocalLights;
-using AllLocalLightsShadowed = AllLocalLights;
 
 // DeferredShading.hlsl:53-76: cascade selection and the (blended) shadow factor of the first light for one pixel.
 // `abs(distance - radius[j] < 5.0f)` is abs(bool) (Q1), true whenever distance < radius[j]: every pixel nearer than 80 blends

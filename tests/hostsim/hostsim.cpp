@@ -5,7 +5,9 @@
 #include "ssao_core.hpp"
 #include "blur_tiles.hpp"
 #include "light_core.hpp"
+#include "light_bind.hpp"
 #include "raster_core.hpp"
+#include <type_traits>
 #include <vector>
 
 using namespace cry;
@@ -16,6 +18,7 @@ float hs_d24_to_float(uint32_t v) { return d24_to_float(v); }
 float hs_unorm16_to_float(uint32_t v) { return unorm16_to_float(v); }
 float hs_unorm8_to_float(uint32_t v) { return unorm8_to_float(v); }
 float hs_half_to_float(uint16_t v) { return half_to_float(v); }
+uint16_t hs_float_to_half(float f) { return float_to_half(f); }
 float hs_det_sin(float x) { return det_sin(x); }
 float hs_det_cos(float x) { return det_cos(x); }
 float hs_det_log2(float x) { return det_log2(x); }
@@ -235,7 +238,7 @@ void hs_blur(const crychic_ssao_constants* cb, void* edge_base, const uint16_t* 
         }
 }
 
-// The blur chain of Ssao::ComputeSsao as api.cpp issues it: the launch plan of blur_tiles.hpp, every launch's tiles run one after
+// The blur chain of Ssao::ComputeSsao the way api.cpp issues it: the launch plan of blur_tiles.hpp, every launch's tiles run one after
 // the other through the very tile bodies the kernels instantiate (one sequential "thread" per tile).  planes[0] / planes[1] =
 // ambient0 / ambient1; the SSAO output is expected in planes[blur_chain_ssao_plane(blurCount)] for rows blur_chain_ssao_rows(..)
 // (hs_ssao_path with the same stamp wrote the unoccluded-wavefront map); the result is in planes[0], rows [row0, row0 + rows).
@@ -282,57 +285,95 @@ void hs_blur_chain(const crychic_ssao_constants* cb, void* edge_base, uint16_t* 
 int hs_blur_chain_ssao_plane(int blurCount) { return blur_chain_ssao_plane(blurCount); }
 void hs_blur_chain_ssao_rows(int blurCount, uint32_t row0, uint32_t rows, uint32_t h2, uint32_t* r0, uint32_t* rn) { blur_chain_ssao_rows(blurCount, row0, rows, h2, r0, rn); }
 
-void hs_light(const crychic_pass_constants* cb, const float* g0, const float* g1, const float* g2,
+// ---- one lighting call ---------------------------------------------------------------------------------------------
+// The scalar pieces the shadow tests probe on their own.
+float hs_spot_shadow_factor(const uint32_t* map, uint32_t dim, const float T[16], const float pos[3])
+{
+    return spot_shadow_factor(map, dim, 1.0f / (float)dim, T, f3{ pos[0], pos[1], pos[2] });
+}
+int hs_point_face(const float v[3], float abc[3])
+{
+    const PointFace pf = point_face(f3{ v[0], v[1], v[2] });
+    abc[0] = pf.abc.x; abc[1] = pf.abc.y; abc[2] = pf.abc.z;
+    return (int)pf.f;
+}
+// shadowProj: 16 floats, untransposed (crychic_update_point_shadow_transforms)
+float hs_point_shadow_factor(const uint32_t* faces, uint32_t dim, const float shadowProj[16], const float lightPos[3], const float pos[3])
+{
+    PointShadows S;
+    bind_point_shadows(S, &faces, shadowProj, 1u, dim);
+    crychic_light L;
+    std::memset(&L, 0, sizeof L);
+    std::memcpy(L.Position, lightPos, sizeof L.Position);
+    return PointShadowOf{ &S, f3{ pos[0], pos[1], pos[2] }, &L, 0u }();
+}
+
+}  // extern "C"
+
+// light_pixel as a kernel of the family instantiates it: MIPS kernels pass the quad's CubeChain, the others look level 0 up.
+template <bool ZERO_RADIUS, bool FIX, class Lights>
+static f4 hs_light_pixel(const LightParams& P, f4a G0, f4a G1, f4a G2, const uint16_t* ambient, const uint32_t* cube, Lights lights, const CubeChain* cc)
+{
+    return cc ? light_pixel<ZERO_RADIUS, Lights, FIX, CubeChain>(P, G0, G1, G2, ambient, cube, lights, *cc)
+              : light_pixel<ZERO_RADIUS, Lights, FIX>(P, G0, G1, G2, ambient, cube, lights);
+}
+
+extern "C" {
+
+// Every crychic_deferred_light* entry on the host: the arguments bound through the library's own light_bind.hpp, the kernel family
+// picked by its light_family(), and each pixel of rows [row0, row0 + rows) through the light_pixel instantiation that family's
+// kernels run.  g0 / g1 / g2: float4 or half4 texels by the CRYCHIC_GBUFFER_G*_F16 bits of flags (gbuffer_load; no bit: the plain
+// f4a load).  The local families iterate every light un-culled (AllLocalLights): the tiled kernels walk the culled lights in the
+// same ascending order.  A family's kernels carry a shadow functor or they do not, whatever the counts -- light_point_shadows_kernel
+// takes the spot lights with SpotShadowOf even at a spot shadow count of 0 (factor 1) -- and the descriptors handed to
+// AllLocalLights are non-null exactly for the functors the family compiles in.
+void hs_light(const crychic_pass_constants* cb, const void* g0, const void* g1, const void* g2,
               const uint32_t* depth, const uint16_t* ambient, const uint32_t* const shadow[4], uint32_t shadowDim,
               const uint8_t* cube, uint32_t cubeDim, uint8_t* out, float* radiance, uint32_t W, uint32_t H,
-              uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags, const crychic_light* pointLights,
-              uint32_t numPointLights)
+              uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags,
+              const crychic_light* pointLights, uint32_t numPointLights, const crychic_light* spotLights,
+              uint32_t numSpotLights, uint32_t shadowCount, uint32_t shadowMapDim, const uint32_t* const* shadowMaps,
+              uint32_t pointShadowCount, uint32_t pointShadowDim, const uint32_t* const* pointMaps, const float* shadowProj)
 {
     LightParams P;
-    std::memcpy(P.ViewProjTex, cb->ViewProjTex, sizeof P.ViewProjTex);
-    std::memcpy(P.ShadowTransforms, cb->ShadowTransforms, sizeof P.ShadowTransforms);
-    std::memcpy(P.InvProj, cb->InvProj, sizeof P.InvProj);
-    std::memcpy(P.InvView, cb->InvView, sizeof P.InvView);
-    std::memcpy(P.EyePosW, cb->EyePosW, sizeof P.EyePosW);
-    P.pcfSearchRadius = pcfSearchRadius;
-    std::memcpy(P.AmbientLight, cb->AmbientLight, sizeof P.AmbientLight);
-    std::memcpy(P.Lights, cb->Lights, sizeof P.Lights);
-    for (int i = 0; i < 4; ++i) P.shadow[i] = shadow[i];
-    P.shadowDim = shadowDim; P.cubeDim = cubeDim; P.W = W; P.H = H; P.numDirLights = numDirLights; P.flags = flags;
-    P.pointLights = pointLights; P.numPointLights = numPointLights;
-    P.shadowWIsOne = light_shadow_w_is_one(P.ShadowTransforms) ? 1u : 0u;
-    P.darkLights = light_dark_mask(P.Lights, numDirLights);
-    P.unitLights = light_dark_lengths_ok(P.Lights, numDirLights) ? 1u : 0u;
-    P.rcpW = rcp((float)W); P.rcpH = rcp((float)H);
-    P.cubeLevels = (flags >> 16) & 15u;                    // CRYCHIC_LIGHT_CUBE_LEVELS
-    light_params_derive(P);
-    const bool chain = P.cubeLevels > 1u;
-    const AllLocalLights pl{ pointLights, numPointLights, nullptr, 0u, nullptr };
-    const f4a* G0 = (const f4a*)g0; const f4a* G1 = (const f4a*)g1; const f4a* G2 = (const f4a*)g2;
+    SpotShadows S;
+    PointShadows PS;
+    bind_light_params(P, *cb, shadow, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags);
+    bind_point_lights(P, pointLights, numPointLights);
+    bind_spot_shadows(S, *cb, shadowMaps, shadowCount, shadowMapDim);
+    bind_point_shadows(PS, pointMaps, shadowProj, pointShadowCount, pointShadowDim);
+    const LightFamily family = light_family(P.flags, P.numPointLights, numSpotLights, S.count, PS.count, P.cubeLevels);
+    const bool chain = P.cubeLevels > 1u, zero = pcfSearchRadius == 0.0f;
+    const AllLocalLights ll{ pointLights, numPointLights, spotLights, numSpotLights, light_family_spot_shadows(family) ? &S : nullptr,
+                             light_family_point_shadows(family) ? &PS : nullptr };
+    const uint32_t h0 = flags & CRYCHIC_GBUFFER_G0_F16, h1 = flags & CRYCHIC_GBUFFER_G1_F16, h2 = flags & CRYCHIC_GBUFFER_G2_F16;
+    auto shaded = [&](uint32_t xx, uint32_t yy) { return xx < W && yy < row0 + rows && (depth[yy * W + xx] & 0x00FFFFFFu) < 0x00FFFFFFu; };
+    auto reflection = [&](uint32_t xx, uint32_t yy) { return reflection_dir(P, gbuffer_load(g0, yy * W + xx, h0), gbuffer_load(g2, yy * W + xx, h2)); };
+    const uint32_t* cubeTexels = (const uint32_t*)cube;
     for (uint32_t y = row0; y < row0 + rows; ++y)
         for (uint32_t x = 0; x < W; ++x) {
             const uint32_t idx = y * W + x;
             f4 lit;
-            const bool fix = (flags & (CRYCHIC_FIX_Q1 | CRYCHIC_FIX_Q3 | CRYCHIC_FIX_Q4)) != 0;     // as launch_light picks the instantiation
-            if (chain && (depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu) {
-                // light_kernel<.., MIPS>: the neighbours' reflection vectors arrive by lane exchange there, by recomputation here
-                auto shaded = [&](uint32_t xx, uint32_t yy) { return xx < W && yy < row0 + rows && (depth[yy * W + xx] & 0x00FFFFFFu) < 0x00FFFFFFu; };
-                const f3 r = reflection_dir(P, G0[idx], G2[idx]);
-                f3 ddx{ 0.0f, 0.0f, 0.0f }, ddy{ 0.0f, 0.0f, 0.0f };
-                if (shaded(x ^ 1u, y)) { const f3 n = reflection_dir(P, G0[y * W + (x ^ 1u)], G2[y * W + (x ^ 1u)]); ddx = (x & 1u) ? f3{ r.x - n.x, r.y - n.y, r.z - n.z } : f3{ n.x - r.x, n.y - r.y, n.z - r.z }; }
-                if (shaded(x, y ^ 1u)) { const f3 n = reflection_dir(P, G0[(y ^ 1u) * W + x], G2[(y ^ 1u) * W + x]); ddy = (y & 1u) ? f3{ r.x - n.x, r.y - n.y, r.z - n.z } : f3{ n.x - r.x, n.y - r.y, n.z - r.z }; }
-                const float lod = cube_lod(P.cubeDim, P.cubeLevels, r, ddx, ddy);
-                const CubeChain cc{ lod, cube_chain_flat(lod) };
-                if (pcfSearchRadius == 0.0f) lit = light_pixel<true, AllLocalLights, true, CubeChain>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl, cc);
-                else lit = light_pixel<false, AllLocalLights, true, CubeChain>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl, cc);
+            if (shaded(x, y)) {
+                const f4a G0 = gbuffer_load(g0, idx, h0), G1 = gbuffer_load(g1, idx, h1), G2 = gbuffer_load(g2, idx, h2);
+                CubeChain cc{ 0.0f, true };
+                if (chain) {        // <.., MIPS>: the quad neighbours' reflection vectors arrive by lane exchange there, by recomputation here
+                    const f3 r = reflection_dir(P, G0, G2);
+                    f3 ddx{ 0.0f, 0.0f, 0.0f }, ddy{ 0.0f, 0.0f, 0.0f };
+                    if (shaded(x ^ 1u, y)) { const f3 n = reflection(x ^ 1u, y); ddx = (x & 1u) ? f3{ r.x - n.x, r.y - n.y, r.z - n.z } : f3{ n.x - r.x, n.y - r.y, n.z - r.z }; }
+                    if (shaded(x, y ^ 1u)) { const f3 n = reflection(x, y ^ 1u); ddy = (y & 1u) ? f3{ r.x - n.x, r.y - n.y, r.z - n.z } : f3{ n.x - r.x, n.y - r.y, n.z - r.z }; }
+                    const float lod = cube_lod(P.cubeDim, P.cubeLevels, r, ddx, ddy);
+                    cc = CubeChain{ lod, cube_chain_flat(lod) };
+                }
+                auto pixel = [&](auto fix, auto lights) {
+                    return zero ? hs_light_pixel<true, decltype(fix)::value>(P, G0, G1, G2, ambient, cubeTexels, lights, chain ? &cc : nullptr)
+                                : hs_light_pixel<false, decltype(fix)::value>(P, G0, G1, G2, ambient, cubeTexels, lights, chain ? &cc : nullptr);
+                };
+                if (light_family_local(family)) lit = pixel(std::true_type{}, ll);           // every local family compiles FIX in
+                else if (light_family_fix(family)) lit = pixel(std::true_type{}, NoPointLights());
+                else lit = pixel(std::false_type{}, NoPointLights());
             }
-            else if ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu) {
-                if (pcfSearchRadius == 0.0f) lit = fix ? light_pixel<true, AllLocalLights, true>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl)
-                                                       : light_pixel<true, AllLocalLights, false>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl);
-                else lit = fix ? light_pixel<false, AllLocalLights, true>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl)
-                               : light_pixel<false, AllLocalLights, false>(P, G0[idx], G1[idx], G2[idx], ambient, (const uint32_t*)cube, pl);
-            }
-            else if (flags & CRYCHIC_LIGHT_SKY) lit = chain ? sky_pixel_chain(P, (const uint32_t*)cube, x, y) : sky_pixel(P, (const uint32_t*)cube, x, y);
+            else if (flags & CRYCHIC_LIGHT_SKY) lit = chain ? sky_pixel_chain(P, cubeTexels, x, y) : sky_pixel(P, cubeTexels, x, y);
             else lit = f4{ 0.690196097f, 0.768627524f, 0.870588303f, 1.0f };
             if (radiance) { radiance[4 * idx] = lit.x; radiance[4 * idx + 1] = lit.y; radiance[4 * idx + 2] = lit.z; radiance[4 * idx + 3] = lit.w; }
             ((uint32_t*)out)[idx] = pack_rgba8(lit);
@@ -340,11 +381,19 @@ void hs_light(const crychic_pass_constants* cb, const float* g0, const float* g1
 }
 
 // The producer passes executed sequentially on the host with the kernels' own bodies (raster_core.hpp): setup in draw
-// order into the same slot numbering as setup_kernel, coverage by min() on the 64-bit key, then the resolve stage.
-int hs_rasterize(int mode, const float* view, const float* viewProj, const crychic_draw_item* items, uint32_t nItems,
+// order into the same slot numbering as setup_kernel, coverage by min() on the 64-bit key, then the resolve stage
+// (resolve_formats_kernel's: G0..G2 stored through gbuffer_store in the formats of gbufferFlags, no bit = float4).
+// mode 0: depth alone (the shadow pass, with its bias); 1: depth and normals; 2: the G-buffer pass alone (depth and G0..G2 for rows
+// [gRow0, gRow0 + gRows) only); 3: the fused pass (depth and normals everywhere, G0..G2 in the rows).  gRows == 0: the whole
+// target.  Texels the pass does not write are left as they are.
+int hs_rasterize(int passMode, const float* view, const float* viewProj, const crychic_draw_item* items, uint32_t nItems,
                  const crychic_material_data* materials, uint32_t nMaterials, const crychic_texture* textures, uint32_t nTextures,
-                 uint32_t W, uint32_t H, int depthBias, float slopeBias, uint32_t* depth, uint16_t* normal, float* g0, float* g1, float* g2)
+                 uint32_t W, uint32_t H, int depthBias, float slopeBias, uint32_t* depth, uint16_t* normal, void* g0, void* g1, void* g2,
+                 uint32_t gbufferFlags, uint32_t gRow0, uint32_t gRows)
 {
+    const bool limited = (passMode & 2) && gRows;
+    const uint32_t gLo = limited ? gRow0 : 0u, gHi = limited ? gRow0 + gRows : H;
+    const uint32_t yLo = passMode == 2 ? gLo : 0u, yHi = passMode == 2 ? gHi : H;
     std::vector<SetupTri> tris;
     bool overflow = false;
     for (uint32_t it = 0; it < nItems; ++it) {
@@ -377,9 +426,9 @@ int hs_rasterize(int mode, const float* view, const float* viewProj, const crych
         const SetupTri& t = tris[slot];
         if (t.A2 <= 0) continue;
         ++live;
-        const PixelBox b = triangle_box(t, W, H);
+        const PixelBox b = triangle_box(t, W, yLo, yHi);
         const EdgeFlags e = triangle_edge_flags(t);
-        const double bias = mode == 0 ? triangle_depth_bias(t, depthBias, slopeBias) : 0.0;
+        const double bias = passMode == 0 ? triangle_depth_bias(t, depthBias, slopeBias) : 0.0;
         for (int y = b.y0; y <= b.y1; ++y)
             for (int x = b.x0; x <= b.x1; ++x) {
                 const uint64_t key = fragment_key(t, e, bias, x, y, (uint32_t)slot + 1u);
@@ -388,26 +437,27 @@ int hs_rasterize(int mode, const float* view, const float* viewProj, const crych
             }
     }
     const Texture* tex = reinterpret_cast<const Texture*>(textures);
+    const uint32_t h0 = gbufferFlags & CRYCHIC_GBUFFER_G0_F16, h1 = gbufferFlags & CRYCHIC_GBUFFER_G1_F16, h2 = gbufferFlags & CRYCHIC_GBUFFER_G2_F16;
     for (uint32_t y = 0; y < H; ++y)
         for (uint32_t x = 0; x < W; ++x) {
-            const size_t idx = (size_t)y * W + x;
+            int mode = passMode;
+            if (y < gLo || y >= gHi) { mode &= ~2; if (mode == 0) continue; }      // outside the rows: the G-buffer pass alone writes nothing
+            const uint32_t idx = y * W + x;
             const uint64_t key = vis[idx];
             const uint32_t serial = (uint32_t)(key & 0xFFFFFFFFull);
             depth[idx] = (uint32_t)(key >> 32);
             if (mode == 0) continue;
             if (serial == 0) {
-                if (mode == 1) { normal[idx * 4] = 0; normal[idx * 4 + 1] = 0; normal[idx * 4 + 2] = 0x3C00; normal[idx * 4 + 3] = 0; }
-                else for (int c = 0; c < 4; ++c) { g0[idx * 4 + c] = 0; g1[idx * 4 + c] = 0; g2[idx * 4 + c] = 0; }
+                if (mode & 1) { normal[idx * 4] = 0; normal[idx * 4 + 1] = 0; normal[idx * 4 + 2] = 0x3C00; normal[idx * 4 + 3] = 0; }
+                if (mode & 2) { const f4 zero{ 0.0f, 0.0f, 0.0f, 0.0f }; gbuffer_store(g0, idx, h0, zero); gbuffer_store(g1, idx, h1, zero); gbuffer_store(g2, idx, h2, zero); }
                 continue;
             }
             const ResolveOut r = resolve_pixel(mode, tris[serial - 1u], (int)x, (int)y, view, materials, nMaterials, tex, nTextures);
-            if (mode == 1) {
+            if (mode & 1) {
                 normal[idx * 4] = float_to_half(r.normalV.x); normal[idx * 4 + 1] = float_to_half(r.normalV.y);
                 normal[idx * 4 + 2] = float_to_half(r.normalV.z); normal[idx * 4 + 3] = 0;
-            } else {
-                const float a[12] = { r.g0.x, r.g0.y, r.g0.z, r.g0.w, r.g1.x, r.g1.y, r.g1.z, r.g1.w, r.g2.x, r.g2.y, r.g2.z, r.g2.w };
-                for (int c = 0; c < 4; ++c) { g0[idx * 4 + c] = a[c]; g1[idx * 4 + c] = a[4 + c]; g2[idx * 4 + c] = a[8 + c]; }
             }
+            if (mode & 2) { gbuffer_store(g0, idx, h0, r.g0); gbuffer_store(g1, idx, h1, r.g1); gbuffer_store(g2, idx, h2, r.g2); }
         }
     return live;
 }

@@ -6,6 +6,8 @@ import subprocess
 
 import numpy as np
 
+from gbuffer_f16_lib import F16_MASK, G0_F16, G1_F16, G2_F16
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "hostsim", "hostsim.cpp")
 LIB = os.path.join(ROOT, "tests", "hostsim", "libhostsim.so")
@@ -32,11 +34,63 @@ def build_sanitized(name, sources, extra=()):
 def build():
     if SANITIZE:
         return build_sanitized("libhostsim.so", [SRC])
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("devmath.hpp", "gamma_pow.inc", "ssao_core.hpp", "blur_tiles.hpp", "light_core.hpp", "raster_core.hpp")]
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ("devmath.hpp", "gamma_pow.inc", "ssao_core.hpp", "blur_tiles.hpp", "light_core.hpp", "light_bind.hpp", "raster_core.hpp")]
     if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
         subprocess.run([CLANG, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma",
                         "-I", os.path.join(ROOT, "include"), "-I", CSRC, SRC, "-o", LIB], check=True)
     return LIB
+
+
+G_F16 = (G0_F16, G1_F16, G2_F16)
+
+
+def _lights(lights):
+    return (C.addressof(lights), len(lights)) if lights is not None and len(lights) else (None, 0)
+
+
+# hs_light's arguments; the checkers' entry points (ss_deferred_light_spots_shadowed: the first 26, ps_deferred_light_point_shadows:
+# all 30) take the same leading ones, with flags as an int
+LIGHT_ARGTYPES = [C.c_void_p] * 7 + [C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + \
+    [C.c_int, C.c_float, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+     C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+
+
+def run_light(fn, cb, p, ambient, num_dir_lights, pcf_radius, flags=0, points=None, spots=None, maps=None, cubes=None, projs=None,
+              row0=0, rows=None, cube_dim=None, formats=False):
+    """One lighting call through fn, an entry point with (a prefix of) hs_light's arguments: the product's body on the host or a
+    checker.  p: the planes (g0..g2, depth, shadow, cube); points / spots: ctypes arrays of Light or None; maps: (count, dim, dim)
+    uint32 D24 maps of the first `count` spot lights; cubes: (count, 6, dim, dim) uint32 D24 faces of the first `count` point
+    lights, and projs, their (count, 16) untransposed shadow projections.  formats: G-buffer planes may be float16 arrays, and
+    their formats go into the flags word (the CRYCHIC_GBUFFER_G*_F16 bits); otherwise the planes are taken as float32.
+    Returns (RGBA8, radiance)."""
+    H, W = p["depth"].shape
+    rows = H - row0 if rows is None else rows
+    out = np.zeros((H, W, 4), np.uint8)
+    rad = np.zeros((H, W, 4), np.float32)
+    g = [np.ascontiguousarray(p[k], None if formats else np.float32) for k in ("g0", "g1", "g2")]
+    assert all(x.dtype in (np.float32, np.float16) for x in g)
+    flags = int(flags)
+    if formats:
+        flags = (flags & ~F16_MASK) | sum(bit for x, bit in zip(g, G_F16) if x.dtype == np.float16)
+    d = np.ascontiguousarray(p["depth"], np.uint32); s = np.ascontiguousarray(p["shadow"], np.uint32)
+    c = np.ascontiguousarray(p["cube"], np.uint8)
+    a = np.ascontiguousarray(ambient, np.uint16) if ambient is not None else None
+    sh = (C.c_void_p * 4)(*[s[k].ctypes.data for k in range(4)])
+    pp, pn = _lights(points)
+    sp, sn = _lights(spots)
+    m = None if maps is None or len(maps) == 0 else np.ascontiguousarray(maps, np.uint32)
+    count, dim = (0, 0) if m is None else (m.shape[0], m.shape[1])
+    mp = (C.c_void_p * 8)(*[m[k].ctypes.data for k in range(count)])
+    q = None if cubes is None or len(cubes) == 0 else np.ascontiguousarray(cubes, np.uint32)
+    pcount, pdim = (0, 0) if q is None else (q.shape[0], q.shape[2])
+    qp = (C.c_void_p * 4)(*[q[k].ctypes.data for k in range(pcount)])
+    T = np.ascontiguousarray(np.zeros((4, 16), np.float32) if projs is None else np.asarray(projs, np.float32).reshape(-1, 16))
+    args = (C.addressof(cb), g[0].ctypes.data, g[1].ctypes.data, g[2].ctypes.data, d.ctypes.data, a.ctypes.data if a is not None else None,
+            sh, s.shape[1], c.ctypes.data, int(cube_dim or c.shape[1]), out.ctypes.data, rad.ctypes.data, W, H, row0, rows,
+            num_dir_lights, pcf_radius, flags, pp, pn, sp, sn, count, dim, mp, pcount, pdim, qp, T.ctypes.data)
+    assert pcount == 0 or len(fn.argtypes) == len(args), "this entry point takes no point shadows"
+    fn(*args[:len(fn.argtypes)])
+    return out, rad
 
 
 class HostSim:
@@ -46,6 +100,7 @@ class HostSim:
         for n in ("hs_d24_to_float", "hs_unorm16_to_float", "hs_unorm8_to_float"):
             getattr(L, n).restype = f; getattr(L, n).argtypes = [u32]
         L.hs_half_to_float.restype = f; L.hs_half_to_float.argtypes = [C.c_uint16]
+        L.hs_float_to_half.restype = C.c_uint16; L.hs_float_to_half.argtypes = [f]
         for n in ("hs_det_sin", "hs_det_cos", "hs_det_log2", "hs_det_exp2"):
             getattr(L, n).restype = f; getattr(L, n).argtypes = [f]
         L.hs_det_pow.restype = f; L.hs_det_pow.argtypes = [f, f]
@@ -66,8 +121,11 @@ class HostSim:
         L.hs_set_prep_margin.argtypes = [i]
         L.hs_last_unprepared_rows.restype = u32
         L.hs_rasterize.restype = i
-        L.hs_rasterize.argtypes = [i, vp, vp, vp, u32, vp, u32, vp, u32, u32, u32, i, f, vp, vp, vp, vp, vp]
-        L.hs_light.argtypes = [vp, vp, vp, vp, vp, vp, vp, u32, vp, u32, vp, vp, u32, u32, u32, u32, i, f, u32, vp, u32]
+        L.hs_rasterize.argtypes = [i, vp, vp, vp, u32, vp, u32, vp, u32, u32, u32, i, f, vp, vp, vp, vp, vp, u32, u32, u32]
+        L.hs_light.argtypes = LIGHT_ARGTYPES
+        L.hs_spot_shadow_factor.restype = f; L.hs_spot_shadow_factor.argtypes = [vp, u32, vp, vp]
+        L.hs_point_shadow_factor.restype = f; L.hs_point_shadow_factor.argtypes = [vp, u32, vp, vp, vp]
+        L.hs_point_face.restype = i; L.hs_point_face.argtypes = [vp, vp]
 
     def eval_array(self, kind, a, b=None):
         a = np.ascontiguousarray(a); out = np.zeros(a.shape, dtype=np.float32)
@@ -101,7 +159,7 @@ class HostSim:
 
     def compute_ssao(self, cb, normal_f16, depth_u32, randvec_u8, edge_bytes, blur_count, row0=0, rows=None, use_exit=True, ones_margin=None,
                      edge=None, stamp=1, margin=-1):
-        """Ssao::ComputeSsao as api.cpp sequences it (SSAO pass, then the two-launch blur chain of blur_tiles.hpp through the
+        """Ssao::ComputeSsao the way api.cpp sequences it (SSAO pass, then the two-launch blur chain of blur_tiles.hpp through the
         kernels' own tile bodies).  Returns (ambient0, edge); rows [row0, row0 + rows) of ambient0 are the result.
         ones_margin: the reach the unoccluded-tile exit assumes (default: what api.cpp passes, 5 per iteration)."""
         H, W = depth_u32.shape
@@ -126,8 +184,14 @@ class HostSim:
                                1 if use_exit else 0, 5 * blur_count)
         return planes[0]
 
-    def rasterize(self, mode, view_t, viewproj_t, items, materials, textures, W, H, depth_bias=0, slope_bias=0.0):
+    def rasterize(self, mode, view_t, viewproj_t, items, materials, textures, W, H, depth_bias=0, slope_bias=0.0, *, mix=0,
+                  g_row0=0, g_rows=0, fill=0):
+        """The producer passes on the host.  mode 0: depth (the shadow pass, biased); 1: depth + normals; 2: the G-buffer pass;
+        3: the fused pass (crychic_draw_gbuffer_formats with normals).  mix: the CRYCHIC_GBUFFER_G*_F16 bits of G0..G2;
+        g_row0 / g_rows: the rows G0..G2 are written for (g_rows 0: the whole target).  Every output starts filled with the byte
+        `fill`, so texels the pass leaves untouched show.  Returns depth, normal (or None) and g0..g2 (or None)."""
         from crychic_renderer_amd._lib import DrawItem, Texture
+        from crychic_renderer_amd.geometry import texture_levels
         arr = (DrawItem * len(items))()
         keep = []
         for k, (v, idx, inst) in enumerate(items):
@@ -137,38 +201,68 @@ class HostSim:
         tex = (Texture * max(1, len(textures or [])))()
         for k, t in enumerate(textures or []):
             if t is not None:
-                from crychic_renderer_amd.geometry import texture_levels
                 flat, tw, th, levels = texture_levels(t); keep.append(flat)
                 tex[k] = Texture(flat.ctypes.data, tw, th, levels)
         mats = np.ascontiguousarray(materials) if materials is not None else None
-        depth = np.zeros((H, W), np.uint32)
-        normal = np.zeros((H, W, 4), np.uint16) if mode == 1 else None
-        g = [np.zeros((H, W, 4), np.float32) for _ in range(3)] if mode == 2 else [None] * 3
+        byte = np.uint8(fill)
+        depth = np.full((H, W, 4), byte, np.uint8).view(np.uint32).reshape(H, W)
+        normal = np.full((H, W, 8), byte, np.uint8).view(np.uint16) if mode & 1 else None
+        g = [np.full((H, W, 8 if mix & bit else 16), byte, np.uint8).view(np.float16 if mix & bit else np.float32) if mode & 2 else None
+             for bit in G_F16]
         view_t = np.ascontiguousarray(view_t, np.float32); viewproj_t = np.ascontiguousarray(viewproj_t, np.float32)
         n = self.lib.hs_rasterize(mode, view_t.ctypes.data, viewproj_t.ctypes.data, arr, len(items),
                                   mats.ctypes.data if mats is not None else None, len(mats) if mats is not None else 0,
                                   tex if textures else None, len(textures or []), W, H, depth_bias, slope_bias, depth.ctypes.data,
-                                  normal.ctypes.data if normal is not None else None, *[x.ctypes.data if x is not None else None for x in g])
+                                  normal.ctypes.data if normal is not None else None, *[x.ctypes.data if x is not None else None for x in g],
+                                  mix, g_row0, g_rows)
         if n < 0:
             raise RuntimeError("hs_rasterize failed (%d)" % n)
         return {"depth": depth, "normal": normal.view(np.float16) if normal is not None else None, "g0": g[0], "g1": g[1], "g2": g[2], "tris": n}
 
+    def float_to_half(self, x):
+        """raster_core.hpp float_to_half of every element of x (float32) -> uint16 bits."""
+        x = np.ascontiguousarray(x, np.float32)
+        return np.array([self.lib.hs_float_to_half(float(v)) for v in x.reshape(-1)], np.uint16).reshape(x.shape)
+
+    def half_to_float(self, h):
+        h = np.ascontiguousarray(h, np.uint16)
+        return np.array([self.lib.hs_half_to_float(int(v)) for v in h.reshape(-1)], np.float32).reshape(h.shape)
+
+    def light_frame(self, cb, p, ambient, num_dir_lights, pcf_radius, flags=0, **lights):
+        """One lighting call of the product's body on the host over the planes p (cb: the product's PassConstants; flags: the
+        product's word -- sky, CRYCHIC_FIX_Q*, CRYCHIC_LIGHT_CUBE_LEVELS; the plane formats come from the dtypes of g0..g2).
+        lights: points, spots, maps, cubes, projs, row0, rows, cube_dim as run_light takes them; which kernel family that models
+        is light_bind.hpp's choice, as in the library.  Returns (RGBA8, radiance)."""
+        return run_light(self.lib.hs_light, cb, p, ambient, num_dir_lights, pcf_radius, flags, formats=True, **lights)
+
     def light(self, cb, g0, g1, g2, depth_u32, ambient, shadow_u32, cube_u8, num_dir_lights, pcf_radius, flags=0,
-              want_radiance=False, point_lights=None, cube_dim=None, cube_levels=0):
-        H, W = depth_u32.shape
-        flags = int(flags) | ((int(cube_levels) & 15) << 16)
-        out = np.zeros((H, W, 4), dtype=np.uint8)
-        rad = np.zeros((H, W, 4), dtype=np.float32) if want_radiance else None
-        g0, g1, g2 = (np.ascontiguousarray(g) for g in (g0, g1, g2))
-        d = np.ascontiguousarray(depth_u32); s = np.ascontiguousarray(shadow_u32); c = np.ascontiguousarray(cube_u8)
-        a = np.ascontiguousarray(ambient) if ambient is not None else None
-        sh = (C.c_void_p * 4)(*[s[k].ctypes.data for k in range(4)])
-        self.lib.hs_light(C.addressof(cb), g0.ctypes.data, g1.ctypes.data, g2.ctypes.data, d.ctypes.data,
-                          a.ctypes.data if a is not None else None, sh, s.shape[1], c.ctypes.data, int(cube_dim or c.shape[1]),
-                          out.ctypes.data, rad.ctypes.data if rad is not None else None, W, H, 0, H, num_dir_lights,
-                          pcf_radius, flags, C.addressof(point_lights) if point_lights is not None else None,
-                          len(point_lights) if point_lights is not None else 0)
+              want_radiance=False, point_lights=None, cube_dim=None, cube_levels=0, **lights):
+        """light_frame over separate planes, with the chain's level count as an argument; RGBA8 alone unless want_radiance."""
+        p = {"g0": g0, "g1": g1, "g2": g2, "depth": depth_u32, "shadow": shadow_u32, "cube": cube_u8}
+        out, rad = self.light_frame(cb, p, ambient, num_dir_lights, pcf_radius, int(flags) | ((int(cube_levels) & 15) << 16),
+                                    points=point_lights, cube_dim=cube_dim, **lights)
         return (out, rad) if want_radiance else out
+
+    def spot_shadow_factor(self, m, T, pos):
+        """spot_shadow_factor of one position in the (dim, dim) D24 map m under the transposed transform T."""
+        m = np.ascontiguousarray(m, np.uint32)
+        T = np.ascontiguousarray(T, np.float32)
+        pos = np.ascontiguousarray(pos, np.float32)
+        return self.lib.hs_spot_shadow_factor(m.ctypes.data, m.shape[0], T.ctypes.data, pos.ctypes.data)
+
+    def point_shadow_factor(self, faces, proj, light_pos, pos):
+        """PointShadowOf of one position: faces (6, dim, dim), proj the light's untransposed shadow projection."""
+        faces = np.ascontiguousarray(faces, np.uint32)
+        proj = np.ascontiguousarray(proj, np.float32).reshape(16)
+        lp = np.ascontiguousarray(light_pos, np.float32)
+        pos = np.ascontiguousarray(pos, np.float32)
+        return self.lib.hs_point_shadow_factor(faces.ctypes.data, faces.shape[1], proj.ctypes.data, lp.ctypes.data, pos.ctypes.data)
+
+    def point_face(self, v):
+        """(f, (a, b, c)) of point_face."""
+        v = np.ascontiguousarray(v, np.float32)
+        abc = np.zeros(3, np.float32)
+        return self.lib.hs_point_face(v.ctypes.data, abc.ctypes.data), abc
 
 
 _HS = None

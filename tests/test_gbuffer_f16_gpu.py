@@ -10,6 +10,7 @@ import pytest
 
 import fuzz_util
 import gbuffer_f16_lib as gf
+import hostsim_lib
 import oracle_lib
 import point_shadow_lib
 import raster_util
@@ -152,7 +153,7 @@ def test_known_answers_round_trip_on_device(built_lib, oracle):
     pcb = oracle_lib.as_oracle_cb(cb, oracle_lib.OrPassConstants)
     shadow = torch.full((4, 16, 16), 0xFFFFFF, dtype=torch.int32, device=ctx.device)
     cube = torch.zeros((6, 2, 2, 4), dtype=torch.uint8, device=ctx.device)
-    lib = gf.load()
+    lib = hostsim_lib.load()
     seen_subnormal_light = 0
     for i in range(0, len(x), 5):
         v, w = x[i:i + 5], want[i:i + 5]
@@ -171,7 +172,7 @@ def test_known_answers_round_trip_on_device(built_lib, oracle):
         bits0, bits1 = g0.view(np.uint16), g1.view(np.uint16)
         assert (bits1[cov][:, :3] == w[:3]).all() and (bits1[cov][:, 3] == w[3]).all() and (bits0[cov][:, 3] == w[4]).all(), (v, w)
         assert not bits0[~cov].any() and not bits1[~cov].any() and not g2.view(np.uint16)[~cov].any()
-        host = lib.rasterize(np.array(cb.View, np.float32), np.array(cb.ViewProj, np.float32), items, mats, None, W, H, gf.ALL_F16)
+        host = lib.rasterize(2, np.array(cb.View, np.float32), np.array(cb.ViewProj, np.float32), items, mats, None, W, H, mix=gf.ALL_F16)
         for k, t in enumerate((g0, g1, g2)):
             assert np.array_equal(t.view(np.uint16), host["g%d" % k].view(np.uint16)), k
         dev = {"g0": gb[0], "g1": gb[1], "g2": gb[2], "depth": depth, "shadow": shadow, "cube": cube}
@@ -273,7 +274,7 @@ def test_draw_gbuffer_formats_matches_host_harness(built_lib, oracle):
     items, mats, tex = g.cascade_scene_items(), g.reference_materials(), g.procedural_textures(32)
     geo = SceneGeometry(ctx, items, mats, tex)
     view = np.array(cs.pass_cb.View, np.float32); vp = np.array(cs.pass_cb.ViewProj, np.float32)
-    host = gf.load()
+    host = hostsim_lib.load()
 
     def planes(mix, fill=0xCD):
         """G0..G2 in the formats of mix, depth and the normal map, every byte `fill`."""
@@ -295,7 +296,7 @@ def test_draw_gbuffer_formats_matches_host_harness(built_lib, oracle):
                     geo.DrawGBuffer(cs.pass_cb, gb, depth, g_rows=g_rows)
                 torch.cuda.synchronize()
                 r0, rn = g_rows or (0, 0)
-                ref = host.rasterize(view, vp, items, mats, tex, W, H, mix, with_normals=fused, g_row0=r0, g_rows=rn, fill=0xCD)
+                ref = host.rasterize(3 if fused else 2, view, vp, items, mats, tex, W, H, mix=mix, g_row0=r0, g_rows=rn, fill=0xCD)
                 what = (hex(mix), fused, g_rows)
                 for k in range(3):
                     assert gb[k].dtype == (torch.float16 if mix & (gf.G0_F16 << k) else torch.float32)

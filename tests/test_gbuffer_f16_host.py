@@ -2,7 +2,7 @@
 only, so the whole contract is two statements against code that is frozen:
   1. light(planes in any format mix) == checker light(those planes widened to fp32), RGBA8 and radiance bits;
   2. producer(format mix) == float_to_half(oracle rasteriser's fp32 planes) on the half planes; everything else unchanged.
-Here the product's bodies run on the host (tests/gbuffer_f16_ref/gbuffer_f16_host.cpp); tests/test_gbuffer_f16_gpu.py repeats the
+Here the product's bodies run on the host (tests/hostsim: hs_light, hs_rasterize); tests/test_gbuffer_f16_gpu.py repeats the
 statements on the device."""
 import ctypes as C
 
@@ -11,6 +11,7 @@ import pytest
 
 import fuzz_util
 import gbuffer_f16_lib as gf
+import hostsim_lib
 import oracle_lib
 import point_shadow_lib
 import raster_util
@@ -43,7 +44,7 @@ def known_answer_floats():
 def test_float_to_half_known_answers(built_lib):
     """raster_core.hpp float_to_half on the host: the hand-derived answers, numpy's conversion on them and on 20000 random floats
     around every interesting range; half_to_float is exact (numpy's widening) for all 65536 encodings, NaNs as NaNs."""
-    lib = gf.load()
+    lib = hostsim_lib.load()
     x, want = known_answer_floats()
     got = lib.float_to_half(x)
     assert got.tolist() == want.tolist(), [(float(a), hex(b), hex(c)) for a, b, c in zip(x, got, want) if b != c]
@@ -67,7 +68,7 @@ def test_torch_conversion_is_float_to_half(built_lib):
     rng = np.random.default_rng(2)
     r = np.concatenate([x] + [(rng.standard_normal(4000) * s).astype(np.float32) for s in (1.0, 1e-6, 3e4, 1e-4)])
     got = torch.from_numpy(r).to(torch.float16).numpy().view(np.uint16)
-    assert np.array_equal(got, gf.load().float_to_half(r))
+    assert np.array_equal(got, hostsim_lib.load().float_to_half(r))
     assert got[:len(want)].tolist() == want.tolist()
 
 
@@ -145,7 +146,7 @@ def test_host_body_matches_checker_on_widened_planes(built_lib, oracle, local, c
         kw = dict(cube_dim=32)
     rng = np.random.default_rng(3)
     ao = rng.integers(20000, 65535, (H // 2, W // 2), dtype=np.uint16)
-    lib, ps = gf.load(), point_shadow_lib.load()
+    lib, ps = hostsim_lib.load(), point_shadow_lib.load()
     changed = 0
     for mix in gf.MIXES:
         packed = gf.pack_planes(p, mix)
@@ -155,7 +156,7 @@ def test_host_body_matches_checker_on_widened_planes(built_lib, oracle, local, c
             for fixes, ndl, ambient in ((0, 1, None), (FIX_ALL, 3, ao)):
                 for sky in (1, 0):
                     flags = fixes | sky | ((levels & 15) << 16)
-                    got = lib.light(cb, packed, ambient, ndl, radius, flags, **lights, **kw)
+                    got = lib.light_frame(cb, packed, ambient, ndl, radius, flags, **lights, **kw)
                     if local:
                         ref = ps.checker(pcb, wide, ambient, ndl, radius, flags, **lights, **kw)
                     else:
@@ -163,7 +164,7 @@ def test_host_body_matches_checker_on_widened_planes(built_lib, oracle, local, c
                                                     ndl, radius, sky=bool(sky), want_radiance=True, fixes=fixes, cube_levels=levels, **kw)
                     assert _same(got, ref), (hex(mix), radius, fixes, sky)
         if mix:         # the format is not a no-op: the packed planes light differently from the fp32 ones
-            full = lib.light(cb, p, None, 1, 0.0, 1 | ((levels & 15) << 16), **lights, **kw)
+            full = lib.light_frame(cb, p, None, 1, 0.0, 1 | ((levels & 15) << 16), **lights, **kw)
             changed += not np.array_equal(full[1].view(np.uint32), got[1].view(np.uint32))
     assert changed == 7
 
@@ -177,18 +178,18 @@ def test_host_body_special_value_planes(built_lib, oracle, seed):
     W, H, planes, c, knobs = fuzz_util.random_case(100 + seed, built_lib, size=(66, 50))
     p = {k: planes[k] for k in ("g0", "g1", "g2", "depth", "shadow", "cube")}
     pcb = oracle_lib.as_oracle_cb(c.pass_cb, oracle_lib.OrPassConstants)
-    lib, ps = gf.load(), point_shadow_lib.load()
+    lib, ps = hostsim_lib.load(), point_shadow_lib.load()
     points, spots = points_for_test(), spots_for_test()
     fixes = FIX_ALL if seed & 1 else 0
     for mix in gf.MIXES:
         packed = gf.pack_planes(p, mix)
         wide = gf.widen_planes(packed)
         flags = fixes | knobs["sky"]
-        got = lib.light(c.pass_cb, packed, None, knobs["numDirLights"], knobs["pcfSearchRadius"], flags)
+        got = lib.light_frame(c.pass_cb, packed, None, knobs["numDirLights"], knobs["pcfSearchRadius"], flags)
         ref = oracle.deferred_light(pcb, wide["g0"], wide["g1"], wide["g2"], wide["depth"], None, wide["shadow"], wide["cube"],
                                     knobs["numDirLights"], knobs["pcfSearchRadius"], sky=bool(knobs["sky"]), want_radiance=True, fixes=fixes)
         assert _same(got, ref), (seed, hex(mix))
-        got = lib.light(c.pass_cb, packed, None, knobs["numDirLights"], knobs["pcfSearchRadius"], flags, points=points, spots=spots)
+        got = lib.light_frame(c.pass_cb, packed, None, knobs["numDirLights"], knobs["pcfSearchRadius"], flags, points=points, spots=spots)
         ref = ps.checker(pcb, wide, None, knobs["numDirLights"], knobs["pcfSearchRadius"], flags, points=points, spots=spots)
         assert _same(got, ref), (seed, hex(mix), "local")
 
@@ -198,9 +199,9 @@ def test_host_body_row_range(built_lib, oracle):
     W, H = 98, 66
     p, cb, pcb, lights = _local_case(W, H)
     packed = gf.pack_planes(p, gf.MIXED)
-    lib = gf.load()
-    whole = lib.light(cb, packed, None, 3, 0.0, 1, **lights)
-    part = lib.light(cb, packed, None, 3, 0.0, 1, row0=20, rows=30, **lights)
+    lib = hostsim_lib.load()
+    whole = lib.light_frame(cb, packed, None, 3, 0.0, 1, **lights)
+    part = lib.light_frame(cb, packed, None, 3, 0.0, 1, row0=20, rows=30, **lights)
     assert np.array_equal(part[0][20:50], whole[0][20:50]) and not part[0][:20].any() and not part[0][50:].any()
 
 
@@ -230,11 +231,11 @@ def test_resolve_matches_float_to_half_of_oracle_planes(built_lib, oracle, tmp_p
     nd = oracle_lib.rasterize(oracle, 1, view, vp, items, omats, tex, W, H)
     clear = (gb["depth"] & 0xFFFFFF) == 0xFFFFFF
     assert 0.02 < clear.mean() < 0.98
-    lib = gf.load()
+    lib = hostsim_lib.load()
     mixes = gf.MIXES if name == "reference" else [gf.MIXED, gf.ALL_F16]
     for mix in mixes:
         for fused in (False, True):
-            r = lib.rasterize(view, vp, items, mats, tex, W, H, mix, with_normals=fused)
+            r = lib.rasterize(3 if fused else 2, view, vp, items, mats, tex, W, H, mix=mix)
             assert np.array_equal(r["depth"], gb["depth"])
             if fused:
                 assert np.array_equal(r["normal"].view(np.uint16), nd["normal"].view(np.uint16))
@@ -249,7 +250,7 @@ def test_resolve_matches_float_to_half_of_oracle_planes(built_lib, oracle, tmp_p
     # rows [r0, r0 + rn): the G-buffer inside, the fill byte outside; the pass alone limits depth too, the fused pass does not
     r0, rn = 22, 40
     for fused in (False, True):
-        r = lib.rasterize(view, vp, items, mats, tex, W, H, gf.MIXED, with_normals=fused, g_row0=r0, g_rows=rn, fill=0xCD)
+        r = lib.rasterize(3 if fused else 2, view, vp, items, mats, tex, W, H, mix=gf.MIXED, g_row0=r0, g_rows=rn, fill=0xCD)
         for k in range(3):
             want = gb["g%d" % k] if k == 0 else gb["g%d" % k].astype(np.float16)
             raw, wraw = r["g%d" % k].view(np.uint8), np.ascontiguousarray(want).view(np.uint8)

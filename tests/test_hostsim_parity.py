@@ -263,7 +263,7 @@ def test_unoccluded_tile_exit_margin_bites(built_lib, oracle, hostsim):
 @pytest.mark.parametrize("blur_count", [2, 4])
 def test_recycled_workspace_cannot_settle_a_tile(built_lib, oracle, hostsim, blur_count):
     """The edge workspace is caller-owned and nothing clears it.  Render frame A, then a DIFFERENT frame B over the same,
-    uncleared workspace -- with a fresh stamp, as api.cpp draws one per frame, and, the worst case, with the very stamp frame A
+    uncleared workspace -- with a fresh stamp, the way api.cpp draws one per frame, and, the worst case, with the very stamp frame A
     ran with (a recycled allocation that served another context): every word of the unoccluded-wavefront map and every tile flag
     a frame looks at was written by that frame, so frame B equals the oracle either way."""
     import fuzz_util

@@ -9,6 +9,7 @@ import math
 import numpy as np
 import pytest
 
+import hostsim_lib
 import local_light_lib
 import oracle_lib
 import point_shadow_lib
@@ -74,8 +75,8 @@ def test_face_table_is_the_builders_look_at(built_lib):
             if trial % 5 == 0:                                      # exact ties between components
                 pos[1] = lp[1] + (pos[0] - lp[0]) * rng.choice([1, -1])
             v = (pos - lp).astype(np.float32)
-            f, abc = ps.face("ref", v)
-            fh, abch = ps.face("host", v)
+            f, abc = ps.face(v)
+            fh, abch = hostsim_lib.load().point_face(v)
             assert f == fh and abc.view(np.uint32).tolist() == abch.view(np.uint32).tolist()
             got = _mul_f32(pos, views[f])
             for c in range(3):
@@ -172,9 +173,9 @@ def test_no_seams_cleared_maps(built_lib, dim):
         narrow = sp.copy()
         narrow[0, 0], narrow[1, 1] = 0.5, -0.5                   # lightProj with xScale = yScale = 1, times T
         for pos in _edge_positions(lp, rng, lights[k].FalloffEnd):
-            assert ps.factor("ref", faces, sp, lp, pos) == 1.0, (dim, k, pos)
-            assert ps.factor("host", faces, sp, lp, pos) == 1.0, (dim, k, pos)
-            failed += ps.factor("ref", faces, narrow, lp, pos) < 1.0
+            assert ps.factor(faces, sp, lp, pos) == 1.0, (dim, k, pos)
+            assert hostsim_lib.load().point_shadow_factor(faces, sp, lp, pos) == 1.0, (dim, k, pos)
+            failed += ps.factor(faces, narrow, lp, pos) < 1.0
     assert failed > 0
 
 
@@ -186,8 +187,7 @@ def test_no_seams_frame(built_lib):
     points = shadowed_points()
     cubes = np.full((4, 6, 32, 32), 0xFFFFFF, np.uint32)
     projs = [sp.reshape(-1) for _, _, sp in point_transforms(points, 4, 32)]
-    for which, cb in (("checker", pcb), ("host", c.pass_cb)):
-        fn = getattr(ps, which)
+    for which, fn, cb in (("checker", ps.checker, pcb), ("host", hostsim_lib.load().light_frame, c.pass_cb)):
         base, rbase = fn(cb, p, None, 3, 0.0, 1, points=points)
         got, rgot = fn(cb, p, None, 3, 0.0, 1, points=points, cubes=cubes, projs=projs)
         assert np.array_equal(got, base) and np.array_equal(rgot.view(np.uint32), rbase.view(np.uint32)), which
@@ -247,7 +247,7 @@ def test_geometry_anchor_or_raster(built_lib, oracle):
             pos = np.array([x, 0.0, z], np.float32)
             if np.linalg.norm(pos - light) > 0.95 * L.FalloffEnd:
                 continue
-            f, abc = ps.face("ref", (pos - light.astype(np.float32)).astype(np.float32))
+            f, abc = ps.face((pos - light.astype(np.float32)).astype(np.float32))
             q = np.append(abc.astype(np.float64), 1.0) @ sp.astype(np.float64)
             tx, ty = q[0] / q[3] * dim, q[1] / q[3] * dim
             hits = set()
@@ -257,7 +257,7 @@ def test_geometry_anchor_or_raster(built_lib, oracle):
                     hits.add(None if gp is None else _segment_hits_box(gp, light, lo, hi))
             if len(hits) != 1 or None in hits:
                 continue
-            s = ps.factor("ref", faces, sp, light, pos)
+            s = ps.factor(faces, sp, light, pos)
             want = 0.0 if hits.pop() else 1.0
             assert s == want, (pos, f, s, want)
             counts[want] += 1
@@ -309,8 +309,8 @@ def test_checker_factor_matches_float64_restatement(built_lib):
             for _ in range(150):
                 d = rng.normal(size=3); d /= np.linalg.norm(d)
                 pos = (lp + d * rng.uniform(1.0, 0.9 * lights[k].FalloffEnd)).astype(np.float32)
-                s = ps.factor("ref", faces, sp, lp, pos)
-                assert np.float32(s).view(np.uint32) == np.float32(ps.factor("host", faces, sp, lp, pos)).view(np.uint32)
+                s = ps.factor(faces, sp, lp, pos)
+                assert np.float32(s).view(np.uint32) == np.float32(hostsim_lib.load().point_shadow_factor(faces, sp, lp, pos)).view(np.uint32)
                 ref = _factor_f64(faces, sp, lp, pos)
                 diffs.append(abs(s - ref))
                 if ref in (0.0, 1.0):
@@ -362,7 +362,7 @@ def test_kernel_body_matches_checker(built_lib, chain, count, spot_count):
     for fixes, ndl, radius in ((0, 1, 0.0), (FIX_ALL, 3, 0.01)):
         flags = fixes | 1 | extra
         args = dict(points=points, spots=spots, maps=maps, cubes=cubes, projs=projs, **kw)
-        got, grad = ps.host(cb, p, None, ndl, radius, flags, **args)
+        got, grad = hostsim_lib.load().light_frame(cb, p, None, ndl, radius, flags, **args)
         ref, rref = ps.checker(pcb, p, None, ndl, radius, flags, **args)
         assert np.array_equal(got, ref) and np.array_equal(grad.view(np.uint32), rref.view(np.uint32)), fixes
         base, _ = ps.checker(pcb, p, None, ndl, radius, flags, points=points, spots=spots, maps=maps, **kw)

@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import hostsim_lib
 import local_light_lib
 import oracle_lib
 from local_lights_util import (FIX_ALL, _app, _cpu, _dev_lights, _device_scene, as_or_lights, light_array, points_for_test,
@@ -136,7 +137,7 @@ def test_spot_kernel_body_matches_checker(built_lib, W, H):
     sl = local_light_lib.load()
     points, spots = points_for_test(), spots_for_test()
     for fixes, ndl, radius in ((0, 1, 0.0), (FIX_ALL, 3, 0.01)):
-        got, grad = sl.host(c.pass_cb, p, None, ndl, radius, fixes | 1, points=points, spots=spots)
+        got, grad = hostsim_lib.load().light_frame(c.pass_cb, p, None, ndl, radius, fixes | 1, points=points, spots=spots)
         ref, rref = sl.checker(pcb, p, None, ndl, radius, fixes | 1, points=points, spots=spots)
         assert np.array_equal(got, ref) and np.array_equal(grad.view(np.uint32), rref.view(np.uint32)), fixes
     base, _ = sl.checker(pcb, p, None, 1, 0.0, 1, points=points)

@@ -9,6 +9,7 @@ import math
 import numpy as np
 import pytest
 
+import hostsim_lib
 import local_light_lib
 import oracle_lib
 from local_lights_util import (FIX_ALL, _app, _cpu, _dev_lights, _device_scene, light_array, points_for_test, random_maps,
@@ -86,8 +87,8 @@ def test_checker_factor_matches_float64_restatement():
             d = np.asarray(L.Direction[:], np.float64); d /= np.linalg.norm(d)
             pos = np.asarray(L.Position[:], np.float64) + dist * d + rng.uniform(-0.3, 0.3, 3) * dist
             pos = pos.astype(np.float32)
-            s = ssl.factor("ref", m, T, pos)
-            assert np.float32(s).view(np.uint32) == np.float32(ssl.factor("host", m, T, pos)).view(np.uint32)
+            s = ssl.factor(m, T, pos)
+            assert np.float32(s).view(np.uint32) == np.float32(hostsim_lib.load().spot_shadow_factor(m, T, pos)).view(np.uint32)
             ref = _shadow_factor_f64(m, st.T.reshape(-1), pos.astype(np.float64))
             diffs.append(abs(s - ref))
             n += 1
@@ -103,18 +104,18 @@ def test_factor_specials():
     ssl = local_light_lib.load()
     m = random_maps(1, 32, 5)[0]
     for pos in ((1.0, 2.0, 3.0), (-7.5, 0.25, 40.0)):
-        for which in ("ref", "host"):
-            assert ssl.factor(which, m, CENTRE_T, pos) == 1.0
-            assert ssl.factor(which, m, FAR_T, pos) == 0.0
+        for factor in (ssl.factor, hostsim_lib.load().spot_shadow_factor):
+            assert factor(m, CENTRE_T, pos) == 1.0
+            assert factor(m, FAR_T, pos) == 0.0
     T = CENTRE_T.copy(); T[0] = 1.0; T[11] = 0.5                  # x = pos.x + 0.5, depth 0.5
     for pos in ((np.inf, 0.0, 0.0), (np.nan, 0.0, 0.0)):
-        assert ssl.factor("ref", m, T, pos) == 0.0 and ssl.factor("host", m, T, pos) == 0.0
+        assert ssl.factor(m, T, pos) == 0.0 and hostsim_lib.load().spot_shadow_factor(m, T, pos) == 0.0
     spots = spots_for_test()
     _, _, st = spot_transforms(spots, 1)[0]
     L = spots[0]
     behind = np.asarray(L.Position[:], np.float32) - 3.0 * np.asarray(L.Direction[:], np.float32)
     T = transposed(st)
-    a, b = ssl.factor("ref", m, T, behind), ssl.factor("host", m, T, behind)
+    a, b = ssl.factor(m, T, behind), hostsim_lib.load().spot_shadow_factor(m, T, behind)
     assert np.float32(a).view(np.uint32) == np.float32(b).view(np.uint32)
 
 
@@ -137,7 +138,7 @@ def test_shadowed_kernel_body_matches_checker(built_lib, chain, count):
     points = points_for_test()
     for fixes, ndl, radius in ((0, 1, 0.0), (FIX_ALL, 3, 0.01)):
         flags = fixes | 1 | extra
-        got, grad = ssl.host(cb, p, None, ndl, radius, flags, points=points, spots=spots, maps=maps, **kw)
+        got, grad = hostsim_lib.load().light_frame(cb, p, None, ndl, radius, flags, points=points, spots=spots, maps=maps, **kw)
         ref, rref = ssl.checker(pcb, p, None, ndl, radius, flags, points=points, spots=spots, maps=maps, **kw)
         assert np.array_equal(got, ref) and np.array_equal(grad.view(np.uint32), rref.view(np.uint32)), fixes
         base, _ = ssl.checker(pcb, p, None, ndl, radius, flags, points=points, spots=spots, **kw)
