@@ -12,6 +12,7 @@
 #include "light_core.hpp"
 #include "light_bind.hpp"
 #include "light_tiles.hpp"
+#include "dispatch_order.hpp"
 
 namespace cry {
 
@@ -35,8 +36,10 @@ __device__ __forceinline__ void tile_origin_2d(uint32_t& bx, uint32_t& by, uint3
         o = b - st * T;
     }
     const uint32_t sty = st / ncx, stx = st - sty * ncx, oy = o / SX, ox = o - oy * SX;
+    // which XCD a super-tile goes to is settled above; its row of the frame follows the band order of dispatch_order.hpp
+    // (measured best: bottom-up, so that a launch over ground under a sky ends on the short sky wavefronts)
     bx = stx * SX + ox;
-    by = sty * SY + oy;
+    by = launch_band(sty, gridDim.y / SY, CRY_SSAO_BAND_WAYS) * SY + oy;
 }
 
 // ---- SSAO ------------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "light_core.hpp"
+#include "dispatch_order.hpp"
 
 namespace cry {
 
@@ -83,6 +84,7 @@ __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLA
     const uint32_t h0 = P.flags & CRYCHIC_GBUFFER_G0_F16, h1 = P.flags & CRYCHIC_GBUFFER_G1_F16, h2 = P.flags & CRYCHIC_GBUFFER_G2_F16;
     uint32_t bx, by;
     tile_origin<0>(bx, by);
+    by = light_dispatch_row(by, gridDim.y);               // the band order of dispatch_order.hpp (measured best: the natural one)
     uint32_t x, y;
     light_tile_pixel<MIPS>(bx, by, row0, x, y);
     if (MIPS) {
@@ -143,6 +145,7 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLA
 {
     uint32_t bx, by;
     tile_origin<0>(bx, by);
+    by = light_dispatch_row(by, gridDim.y);               // the band order of dispatch_order.hpp (measured best: the natural one)
     uint32_t x, y;
     light_tile_pixel<MIPS>(bx, by, row0, x, y);             // MIPS: 32 x 2 pixels per wavefront (quads inside a wavefront)
     const bool inFrame = (x < P.W) && (y < row1);

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Wave-level statistics of the SSAO tap culling on the 4K benchmark frame (float64 restatement of Ssao.hlsl:141-191 in numpy):
 how many taps the nearest-depth cells cull, how many tap pairs a wavefront still executes, with 8-texel cells, 4-texel cells and a
-perfect test.  First: python tools/ssao_tap_stats.py --gen  (ray-casts the scene on the CPU, ~40 s, into /tmp/an/scene4k.npz)."""
+perfect test, for wavefront footprints of 64 x 1, 32 x 2, 16 x 4 and 8 x 8 pixels.  First: python tools/ssao_tap_stats.py --gen  (ray-casts the scene on the CPU, ~40 s, into /tmp/an/scene4k.npz)."""
 import os, sys
 import numpy as np
 if "--gen" in sys.argv:
@@ -79,12 +79,14 @@ for i in range(14):
 nsky=(~sky).sum()
 print('non-sky px',nsky,'of',sky.size)
 print('survive8 frac of taps', surv.sum()/(14*nsky), 'survive4', surv4.sum()/(14*nsky),'true occluding', true_occ.sum()/(14*nsky))
-# wave-level: waves = 64 px rows segments
-def wave(a): # a: (h2,w2) bool -> any over 64-lane segments
-    return a.reshape(h2,w2//64,64).any(-1)
-wsky=sky.reshape(h2,w2//64,64).all(-1)
-nw=(~wsky).sum(); print('non-sky waves',nw,'of',wsky.size)
-for name,S in (('cell8',surv),('cell4',surv4),('true',true_occ)):
-    pairs=sum(wave(S[i]|S[i+1]).sum() for i in range(0,14,2))
-    anyw=wave(S.any(0)).sum()
-    print(name,'pairs executed per non-sky wave',pairs/nw,' waves with any survivor',anyw/nw, ' lane-items per exec pair', S.sum()/max(pairs,1))
+# wave-level: the footprint of a wavefront is fh rows x fw pixels (64 x 1 is what ssao_kernel runs; the others answer whether a
+# squarer footprint would let more wavefronts skip a tap pair -- DESIGN.md section 8 item 3)
+for fh,fw in ((1,64),(2,32),(4,16),(8,8)):
+    def wave(a): # a: (h2,w2) bool -> any over the fh x fw blocks
+        return a.reshape(h2//fh,fh,w2//fw,fw).any(axis=(1,3))
+    wsky=~wave(~sky)
+    nw=(~wsky).sum(); print('footprint %dx%d: non-sky waves'%(fw,fh),nw,'of',wsky.size)
+    for name,S in (('cell8',surv),('cell4',surv4),('true',true_occ)):
+        pairs=sum(wave(S[i]|S[i+1]).sum() for i in range(0,14,2))
+        anyw=wave(S.any(0)).sum()
+        print(' ',name,'pairs executed per non-sky wave',pairs/nw,' waves with any survivor',anyw/nw, ' lane-items per exec pair', S.sum()/max(pairs,1))
