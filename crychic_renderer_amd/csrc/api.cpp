@@ -17,6 +17,7 @@
 #include "ssao_core.hpp"
 #include "blur_tiles.hpp"
 #include "raster_core.hpp"
+#include "cube_mips_core.hpp"
 #include "internal.hpp"
 
 namespace {
@@ -687,6 +688,28 @@ int crychic_draw_gbuffer_formats(crychic_ctx* ctx, const crychic_pass_constants*
     p.workspace = workspace_dev; p.workspaceBytes = workspaceBytes;
     p.gRow0 = gRow0; p.gRows = gRows;
     return raster_common(ctx, p, passCB, items, nItems, stream);
+}
+
+size_t crychic_cube_chain_bytes(uint32_t dim, uint32_t levels)
+{
+    size_t bytes = 0;
+    for (uint32_t k = 0; k < levels; ++k) bytes += cry::cube_level_texels(cry::cube_mip_dim(dim, k)) * 4u;
+    return bytes;
+}
+
+int crychic_generate_cube_mips(crychic_ctx* ctx, uint8_t* chain_dev, uint32_t dim, uint32_t levels, void* stream)
+{
+    if (int rc = bind(ctx)) return rc;
+    if (!chain_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (dim == 0) return fail(CRYCHIC_E_INVALID_ARG, "cube map face size 0");
+    if (dim > 32768u) return fail(CRYCHIC_E_UNSUPPORTED, "cube map face size %u exceeds 32768", dim);
+    // a chain ends at 1 x 1 at the latest, and CRYCHIC_LIGHT_CUBE_LEVELS announces at most 15 levels
+    const uint32_t full = cry::cube_full_levels(dim) < 15u ? cry::cube_full_levels(dim) : 15u;
+    if (levels == 0 || levels > full)
+        return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", levels, dim, full);
+    if (reinterpret_cast<uintptr_t>(chain_dev) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "cube map chain is not 4-byte aligned");
+    CRY_HIP(cry::launch_cube_mips(chain_dev, dim, levels, (hipStream_t)stream));
+    return 0;
 }
 
 int crychic_strip_rows(uint32_t H, int nranks, int rank, uint32_t* row0, uint32_t* rows)

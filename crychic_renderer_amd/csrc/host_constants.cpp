@@ -324,6 +324,26 @@ int crychic_update_point_shadow_transforms(const crychic_light* L, uint32_t dim,
     return 0;
 }
 
+int crychic_cube_capture_cameras(const float pos[3], float nearZ, float farZ, crychic_camera cams[6])
+{
+    if (!pos || !cams) return CRYCHIC_E_INVALID_ARG;
+    if (!std::isfinite(pos[0]) || !std::isfinite(pos[1]) || !std::isfinite(pos[2])) return CRYCHIC_E_INVALID_ARG;
+    if (!(nearZ > 0.0f) || !(nearZ < farZ) || !std::isfinite(farZ)) return CRYCHIC_E_INVALID_ARG;
+    // the axes and ups of crychic_update_point_shadow_transforms' faces (the cube sampler's convention), unwidened
+    static const float look[6][3] = { { 1, 0, 0 }, { -1, 0, 0 }, { 0, 1, 0 }, { 0, -1, 0 }, { 0, 0, 1 }, { 0, 0, -1 } };
+    static const float up[6][3] = { { 0, 1, 0 }, { 0, 1, 0 }, { 0, 0, -1 }, { 0, 0, 1 }, { 0, 1, 0 }, { 0, 1, 0 } };
+    for (int f = 0; f < 6; ++f) {
+        std::memcpy(cams[f].pos, pos, sizeof cams[f].pos);
+        std::memcpy(cams[f].look, look[f], sizeof cams[f].look);
+        std::memcpy(cams[f].up, up[f], sizeof cams[f].up);
+        cams[f].fovY = (float)(3.14159265358979323846 / 2.0);
+        cams[f].aspect = 1.0f;
+        cams[f].nearZ = nearZ;
+        cams[f].farZ = farZ;
+    }
+    return 0;
+}
+
 int crychic_update_main_pass_cb(const crychic_camera* cam, uint32_t W, uint32_t H, const float shadowTransform[4][16],
                                 const float lightDirs[3][3], crychic_pass_constants* out)
 {

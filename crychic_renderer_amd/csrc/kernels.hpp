@@ -64,6 +64,10 @@ hipError_t launch_light_formats(const LightParams& P, const void* g0, const void
                                 hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
                                 const PointShadows* pointShadows);
 
+// cube_mips.hip: levels 1 .. levels - 1 of an RGBA8 cube map's chain from its level 0, in place (cube_mips_core.hpp); one launch per
+// six levels on `stream`.  The caller has checked dim and levels.
+hipError_t launch_cube_mips(uint8_t* chain, uint32_t dim, uint32_t levels, hipStream_t stream);
+
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
 struct Texture;

@@ -1,7 +1,11 @@
 """python -m crychic_renderer_amd.demo [--size WxH] [--out frame.ppm] [--textures DIR] [--cube FILE.dds] [--gbuffer f32|mixed|f16]
+                                   [--capture-env X,Y,Z [--capture-dim N]]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
-(HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present)."""
+(HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
+--capture-env: before the frame, the scene is rendered into a cube map at X,Y,Z (Crychic.capture_environment: six faces of
+--capture-dim texels and their mip chain, built on the device) and the frame is rendered with that chain bound, so the boxes and the
+grid show up in the reflections."""
 import argparse
 import ctypes as C
 
@@ -18,6 +22,9 @@ def main():
                                                "(else a procedural one)")
     ap.add_argument("--gbuffer", default="f32", choices=["f32", "mixed", "f16"],
                     help="G-buffer plane formats: f32 = three float4 planes, mixed = G0 float4 with G1 and G2 half4, f16 = all three half4")
+    ap.add_argument("--capture-env", default="", metavar="X,Y,Z", help="capture the environment at this position before the frame and render "
+                                                                       "with the captured cube map bound")
+    ap.add_argument("--capture-dim", type=int, default=256, help="face size of the captured cube map (even)")
     a = ap.parse_args()
     W, H = (int(v) for v in a.size.lower().split("x"))
     import torch
@@ -41,6 +48,13 @@ def main():
     geo.DrawNormalsAndDepth(app.mMainPassCB, app.mSsao.mNormalMap, app.mDepthStencilBuffer)
     geo.DrawGBuffer(app.mMainPassCB, app.mDeferred.mGBuffer, app.mDepthStencilBuffer)
     app.blurCount, app.numDirLights, app.flags = 3, 1, LIGHT_SKY        # the reference's settings (CRYCHIC.cpp:221, Common.hlsl:6-8)
+    if a.capture_env:
+        pos = [float(v) for v in a.capture_env.split(",")]
+        if len(pos) != 3:
+            ap.error("--capture-env takes X,Y,Z")
+        chain, dim, levels = app.capture_environment(pos, geo, sgeo, dim=a.capture_dim)
+        app.set_cube_map(chain, dim, levels)
+        print("captured the environment at (%g, %g, %g): %d-texel faces, %d levels" % (pos[0], pos[1], pos[2], dim, levels))
     app.Draw()
     torch.cuda.synchronize()
     img = np.ascontiguousarray(app.mBackBuffer.cpu().numpy())

@@ -170,6 +170,25 @@ def cube_mip_chain(cube, levels=None):
     return np.concatenate([faces[f][k].reshape(-1) for k in range(n) for f in range(6)]), n
 
 
+def cube_full_levels(dim):
+    """The levels of a dim-texel cube map's chain down to 1 x 1, at most the 15 that CRYCHIC_LIGHT_CUBE_LEVELS announces."""
+    return min(15, int(dim).bit_length())
+
+
+def cube_chain_bytes(dim, levels):
+    """Bytes of the first `levels` levels of a dim-texel cube map's chain (crychic_cube_chain_bytes)."""
+    return int(lib.crychic_cube_chain_bytes(int(dim), int(levels)))
+
+
+def cube_capture_cameras(pos, z_near=0.5, z_far=100.0):
+    """The six face cameras (+X, -X, +Y, -Y, +Z, -Z) of an environment capture at `pos` (crychic_cube_capture_cameras): a ctypes
+    array of Camera with fovY = pi / 2 and aspect 1."""
+    from ._lib import Camera
+    cams = (Camera * 6)()
+    check(lib.crychic_cube_capture_cameras((C.c_float * 3)(*[float(v) for v in pos]), float(z_near), float(z_far), cams))
+    return cams
+
+
 def texture_levels(t):
     """(flat uint8 array of all levels back to back, width, height, mipLevels) for a texture given as one H x W x 4 array or as a
     list of level arrays (level k = max(1, W >> k) x max(1, H >> k))."""

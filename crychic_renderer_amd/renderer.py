@@ -198,7 +198,9 @@ class Crychic:
         self.blurCount = 3           # CRYCHIC.cpp:221
         self.numDirLights = 1        # NUM_DIR_LIGHTS of the deferred shader, Common.hlsl:6-8
         self.pcfSearchRadius = lib.crychic_pcf_search_radius(shadow_dim, 1)  # Common.hlsl:305 as written
+        self.pcfLiteral = 1          # capture_environment: the `literal` of crychic_pcf_search_radius for the capture's own shadow map
         self.flags = 0
+        self._probes = {}            # capture_environment: (dim, shadow_dim) -> the dim x dim probe renderer, kept across captures
         self.mPointLights = None     # extension: torch uint8 tensor holding an array of Light structs (48 B each)
         self.mSpotLights = None      # extension: the same for the spot lights (crychic_draw_hot_path_spots)
         self.mSpotShadowMaps = None  # extension: (count, dim, dim) int32 D24 maps of the first spot lights (set_spot_shadows)
@@ -323,6 +325,108 @@ class Crychic:
         self.mCubeMapLevels = int(levels)
         self.mCubeMapSize = int(dim) if dim is not None else None
         self._desc = None
+
+    def generate_cube_mips(self, chain, dim, levels=None):
+        """Extension: builds levels 1 .. levels - 1 of the cube map chain in the uint8 tensor `chain` from its level 0, on the device and
+        in place (crychic_generate_cube_mips; geometry.cube_mip_chain's bytes).  levels None = down to 1 x 1.  Returns `chain`."""
+        from .geometry import cube_full_levels
+        levels = cube_full_levels(dim) if levels is None else int(levels)
+        check(lib.crychic_generate_cube_mips(self.ctx.handle, _ptr(chain), int(dim), levels, _stream(self.ctx.device)))
+        return chain
+
+    def capture_environment(self, pos, geometry, shadow_geometry=None, dim=256, levels=None, z_near=0.5, z_far=None, shadow_dim=1024,
+                            out=None):
+        """Extension: renders the scene into a cube map at `pos` and builds its mip chain on the device (include/crychic_hip.h
+        "environment capture").  Face f of level 0 is the frame Draw produces at dim x dim for face camera f
+        (crychic_cube_capture_cameras) with CRYCHIC_LIGHT_SKY, written in place: `geometry` (a SceneGeometry) fills the normal map,
+        depth and G-buffer, `shadow_geometry` (default: `geometry`) the four cascades fitted to that camera, in a shadow map of
+        `shadow_dim` with pcfSearchRadius = crychic_pcf_search_radius(shadow_dim, self.pcfLiteral).  geometry None: no producer draws,
+        the planes are cleared and every face is sky.  Lights[], AmbientLight, TotalTime, blurCount, numDirLights, the Q-fix flags,
+        the point and spot lights with their shadow maps and ShadowTransforms[4..11], the SSAO offset vectors and the plane formats
+        are this object's; the cube map it has bound is the source (with its chain), so a capture never reflects itself and two
+        captures in a row give one bounce.  levels None = the full chain; z_far None = 100 (the reference's lens, CRYCHIC.cpp:114).
+        out: a uint8 tensor of at least geometry.cube_chain_bytes(dim, levels) bytes that must not overlap the bound cube map
+        (default: a new one).  The probe renderer is kept (release_capture_probes frees it), so a re-capture with `out` allocates nothing.  Returns (chain, dim, levels);
+        binding it is the caller's set_cube_map(chain, dim, levels)."""
+        import numpy as np
+        from .geometry import cube_capture_cameras, cube_chain_bytes, cube_full_levels
+        dim, shadow_dim = int(dim), int(shadow_dim)
+        if not 0 < dim <= 8192:
+            raise CrychicError(-1, "capture_environment: dim %d (a cube map the lighting pass binds has 2 .. 8192-texel faces)" % dim)
+        full = cube_full_levels(dim)
+        levels = full if levels is None else int(levels)
+        if not 1 <= levels <= full:
+            raise CrychicError(-1, "capture_environment: levels %d (1 .. %d for %d-texel faces)" % (levels, full, dim))
+        src = self.mCubeMap
+        probe = self._probes.get((dim, shadow_dim))
+        if probe is None:       # a dim x dim frame: an odd dim is refused as every frame size is (Ssao.OnResize)
+            probe = self._probes[(dim, shadow_dim)] = Crychic(self.ctx, dim, dim, self.mSsao.mRandomVectorMap, src, shadow_dim=shadow_dim,
+                                                              gbuffer_formats=self.mDeferred.mFormats)
+        nbytes = cube_chain_bytes(dim, levels)
+        if out is None:
+            out = torch.empty((nbytes,), device=self.ctx.device, dtype=torch.uint8)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < nbytes or out.device != self.mBackBuffer.device:
+            raise CrychicError(-1, "capture_environment: out must be a contiguous uint8 device tensor of at least %d bytes" % nbytes)
+        if out.data_ptr() < src.data_ptr() + src.numel() * src.element_size() and src.data_ptr() < out.data_ptr() + nbytes:
+            raise CrychicError(-1, "capture_environment: the destination aliases the bound cube map (a capture never reflects itself)")
+        if probe.mDeferred.mFormats != self.mDeferred.mFormats:
+            probe.set_gbuffer_formats(self.mDeferred.mFormats)
+        # the local lights' shadow maps are the main frame's: render them now if Draw has not yet
+        if self._spotShadow is not None and self._spotShadow[3] is not None:
+            self.DrawSpotShadowMaps()
+        if self._pointShadow is not None and self._pointShadow[2] is not None:
+            self.DrawPointShadowMaps()
+        probe.mSsao.mRandomVectorMap = self.mSsao.mRandomVectorMap
+        probe.mCubeMap, probe.mCubeMapLevels, probe.mCubeMapSize = src, self.mCubeMapLevels, self.mCubeMapSize
+        probe.blurCount, probe.numDirLights, probe.flags = self.blurCount, self.numDirLights, int(self.flags) | _lib.LIGHT_SKY
+        probe.pcfSearchRadius = lib.crychic_pcf_search_radius(shadow_dim, int(self.pcfLiteral))
+        probe.mPointLights, probe.mSpotLights = self.mPointLights, self.mSpotLights
+        probe._spotShadow = None if self._spotShadow is None else self._spotShadow[:3] + (None,)
+        probe._pointShadow = None if self._pointShadow is None else self._pointShadow[:2] + (None,)
+        if geometry is None:
+            probe.mDepthStencilBuffer.fill_(0xFFFFFF)
+            probe.mSsao.mNormalMap.zero_()
+            probe.mSsao.mNormalMap[..., 2] = 1.0
+            for g in probe.mDeferred.mGBuffer:
+                g.zero_()
+            probe.mShadowMap.mShadowMap.fill_(0xFFFFFF)
+        main = self.mMainPassCB
+        cams = cube_capture_cameras(pos, z_near, 100.0 if z_far is None else z_far)
+        light_dir = (C.c_float * 3)(*main.Lights[0].Direction)
+        dirs = np.array([list(main.Lights[i].Direction) for i in range(3)], np.float32)
+        lv, lp, st = (np.zeros((4, 4, 4), np.float32) for _ in range(3))
+        for f in range(6):
+            cam = cams[f]
+            check(lib.crychic_update_cascade_shadow_transform(C.byref(cam), light_dir, shadow_dim, lv.ctypes.data, lp.ctypes.data, st.ctypes.data))
+            pcb, scb = PassConstants(), SsaoConstants()
+            check(lib.crychic_update_main_pass_cb(C.byref(cam), dim, dim, st.ctypes.data, dirs.ctypes.data, C.byref(pcb)))
+            for i in range(_lib.MAX_LIGHTS):
+                pcb.Lights[i] = main.Lights[i]
+            pcb.AmbientLight[:] = main.AmbientLight[:]
+            pcb.TotalTime, pcb.DeltaTime = main.TotalTime, main.DeltaTime
+            for k in range(4, 12):
+                pcb.ShadowTransforms[k][:] = main.ShadowTransforms[k][:]
+            check(lib.crychic_update_ssao_cb(C.byref(cam), dim, dim, C.cast(self.mSsaoCB.OffsetVectors, C.c_void_p), C.byref(scb)))
+            if geometry is not None:
+                cbs = []
+                for k in range(4):
+                    vp = np.zeros((4, 4), np.float32)       # lightView * lightProj, summed term after term (UpdateShadowPassCB)
+                    for q in range(4):
+                        vp = vp + lv[k][:, q:q + 1] * lp[k][q:q + 1, :]
+                    cb = PassConstants()
+                    cb.ViewProj[:] = list(vp.T.reshape(-1))
+                    cbs.append(cb)
+                (shadow_geometry or geometry).DrawSceneToShadowMaps(cbs, [probe.mShadowMap.Resource(k) for k in range(4)])
+                geometry.DrawNormalsDepthAndGBuffer(pcb, probe.mSsao.mNormalMap, probe.mDeferred.mGBuffer, probe.mDepthStencilBuffer)
+            probe.mMainPassCB, probe.mSsaoCB = pcb, scb
+            probe.mBackBuffer = out[f * dim * dim * 4:(f + 1) * dim * dim * 4].view(dim, dim, 4)
+            probe.Draw()
+        self.generate_cube_mips(out, dim, levels)
+        return out, dim, levels
+
+    def release_capture_probes(self):
+        """Frees the probe renderers capture_environment keeps (one per (dim, shadow_dim) it was called with)."""
+        self._probes.clear()
 
     def set_point_lights(self, lights):
         """Extension: `lights` is a ctypes array of Light (or None); copied to the device.  Shadows set with set_point_shadows are

@@ -129,6 +129,7 @@ class CRYCHIC {
 public:
     CRYCHIC(int deviceOrdinal, UINT width, UINT height) : mClientWidth(width), mClientHeight(height)
     {
+        mDeviceOrdinal = deviceOrdinal;
         md3dDevice = std::make_unique<ID3D12Device>(deviceOrdinal);
         mCommandList = std::make_unique<ID3D12GraphicsCommandList>();
     }
@@ -190,6 +191,7 @@ public:
             const DirectX::XMFLOAT3 d = mBaseLightDirections[i];
             mRotatedLightDirections[i] = { d.x * c + d.z * s, d.y, -d.x * s + d.z * c };
         }
+        mLastTimer = gt;                                                                            // CaptureEnvironment's TotalTime
         UpdateInstanceData(gt);                                                                     // :164
         UpdateMaterialBuffer(gt);                                                                   // :165
         UpdateCascadeShadowTransform(gt);
@@ -207,12 +209,14 @@ public:
             if (mFuseCameraPasses) DrawNormalsDepthAndGBuffer();                                    // :214 + :236 on one rasterisation
             else { DrawNormalsAndDepth(); DrawGBuffer(); }
         }
+        // L: whose cube map, local lights and local-light shadow maps this frame reads -- a capture's probe reads its owner's
+        const CRYCHIC& L = mOwner ? *mOwner : *this;
         crychic_frame_desc f = {};
         f.W = mClientWidth; f.H = mClientHeight;
         f.blurCount = mBlurCount;                                                                   // :221
         f.numDirLights = mNumDirLights;
         f.pcfSearchRadius = crychic_pcf_search_radius(mShadowMap->Width(), mPcfLiteral ? 1 : 0);
-        f.flags = (mSkyEnabled ? CRYCHIC_LIGHT_SKY : 0u) | (mCubeMapLevels > 1 ? CRYCHIC_LIGHT_CUBE_LEVELS(mCubeMapLevels) : 0u);   // :278-279, :1148-1151
+        f.flags = (mSkyEnabled ? CRYCHIC_LIGHT_SKY : 0u) | (L.mCubeMapLevels > 1 ? CRYCHIC_LIGHT_CUBE_LEVELS(L.mCubeMapLevels) : 0u);   // :278-279, :1148-1151
         f.flags |= mDeferred->FormatFlags();                                                        // a half4 plane: its CRYCHIC_GBUFFER_G*_F16 bit
         f.row0 = mStripRow0; f.rows = mWholeFrame ? mClientHeight : mStripRows;                      // whole frame unless SetStrip / JoinNode
         f.normal_dev = mSsao->NormalMap()->Data();
@@ -223,13 +227,13 @@ public:
         f.g2_dev = static_cast<const float*>(mDeferred->Resource(2)->Data());
         for (int i = 0; i < 4; ++i) f.shadow_dev[i] = static_cast<const uint32_t*>(mShadowMap->Resource(i)->Data());
         f.shadowDim = mShadowMap->Width();
-        if (!mCubeMap) throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (no cube map set)", __FILE__, __LINE__);
-        f.cube_dev = static_cast<const uint8_t*>(mCubeMap->Data());
-        f.cubeDim = mCubeMapSize;
+        if (!L.mCubeMap) throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (no cube map set)", __FILE__, __LINE__);
+        f.cube_dev = static_cast<const uint8_t*>(L.mCubeMap->Data());
+        f.cubeDim = L.mCubeMapSize;
         f.ambient0_dev = static_cast<uint16_t*>(mSsao->AmbientMap()->Data());
         f.ambient1_dev = static_cast<uint16_t*>(mSsao->AmbientMap1()->Data());
         f.edge_dev = mSsao->EdgePlane()->Data();
-        f.out_rgba8_dev = static_cast<uint8_t*>(mBackBuffer->Data());
+        f.out_rgba8_dev = mRenderTarget ? mRenderTarget : static_cast<uint8_t*>(mBackBuffer->Data());   // mRenderTarget: a capture's face
         const SsaoConstants& scb = mCurrFrameResource->SsaoCB->Element(0);
         const PassConstants& pcb = mCurrFrameResource->PassCB->Element(0);
         // Several GPUs, one frame: the peers' strips arrive in place behind this strip's lighting pass (RCCL over xGMI), so the
@@ -238,35 +242,35 @@ public:
         // Local lights (SetLocalLights; an extension the reference's shader leaves dead): point lights ride in the frame descriptor,
         // spot lights and their shadows take the _spots_shadowed entries.  With no spot lights, or a shadow count of 0, those entries
         // are crychic_draw_hot_path(_shared) / the _spots entries bit for bit (include/crychic_hip.h).
-        if (mPointLights) { f.point_lights_dev = static_cast<const crychic_light*>(mPointLights->Data()); f.numPointLights = mNumPointLights; }
-        const crychic_light* spots = mSpotLights ? static_cast<const crychic_light*>(mSpotLights->Data()) : nullptr;
+        if (L.mPointLights) { f.point_lights_dev = static_cast<const crychic_light*>(L.mPointLights->Data()); f.numPointLights = L.mNumPointLights; }
+        const crychic_light* spots = L.mSpotLights ? static_cast<const crychic_light*>(L.mSpotLights->Data()) : nullptr;
         // Shadowed spot lights (SetSpotShadows): the first mSpotShadowCount spot lights read their maps through ShadowTransforms[4 + k]
         crychic_spot_shadows sh = {};
-        sh.count = spots ? mSpotShadowCount : 0u;
-        sh.dim = mSpotShadowDim;
-        for (uint32_t k = 0; k < sh.count; ++k) sh.maps[k] = static_cast<const uint32_t*>(mSpotShadowMaps[k]->Data());
+        sh.count = spots ? L.mSpotShadowCount : 0u;
+        sh.dim = L.mSpotShadowDim;
+        for (uint32_t k = 0; k < sh.count; ++k) sh.maps[k] = static_cast<const uint32_t*>(L.mSpotShadowMaps[k]->Data());
         const auto* ssaoCB = reinterpret_cast<const crychic_ssao_constants*>(&scb);
         const auto* passCB = reinterpret_cast<const crychic_pass_constants*>(&pcb);
-        if (mPointShadowCount > 0) {
+        if (L.mPointShadowCount > 0) {
             // Shadowed point lights (SetPointShadows): the first mPointShadowCount point lights read their six faces through shadowProj
             crychic_point_shadows psh = {};
-            psh.count = mPointShadowCount;
-            psh.dim = mPointShadowDim;
+            psh.count = L.mPointShadowCount;
+            psh.dim = L.mPointShadowDim;
             for (uint32_t k = 0; k < psh.count; ++k) {
-                psh.maps[k] = static_cast<const uint32_t*>(mPointShadowMaps[k]->Data());
-                std::memcpy(psh.shadowProj[k], mPointShadowProjs[k], sizeof psh.shadowProj[k]);
+                psh.maps[k] = static_cast<const uint32_t*>(L.mPointShadowMaps[k]->Data());
+                std::memcpy(psh.shadowProj[k], L.mPointShadowProjs[k], sizeof psh.shadowProj[k]);
             }
             if (mComm)
                 CrychicThrowIfFailed(crychic_draw_hot_path_shared_point_shadows(mComm, ssaoCB, passCB, &f, mStripBounds.empty() ? nullptr : mStripBounds.data(),
-                                                                                mExchangeParts, spots, mNumSpotLights, &sh, &psh, mCommandList->Stream()));
+                                                                                mExchangeParts, spots, L.mNumSpotLights, &sh, &psh, mCommandList->Stream()));
             else
-                CrychicThrowIfFailed(crychic_draw_hot_path_point_shadows(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, mNumSpotLights, &sh, &psh,
+                CrychicThrowIfFailed(crychic_draw_hot_path_point_shadows(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, L.mNumSpotLights, &sh, &psh,
                                                                          mCommandList->Stream()));
         } else if (mComm)
             CrychicThrowIfFailed(crychic_draw_hot_path_shared_spots_shadowed(mComm, ssaoCB, passCB, &f, mStripBounds.empty() ? nullptr : mStripBounds.data(),
-                                                                             mExchangeParts, spots, mNumSpotLights, &sh, mCommandList->Stream()));
+                                                                             mExchangeParts, spots, L.mNumSpotLights, &sh, mCommandList->Stream()));
         else
-            CrychicThrowIfFailed(crychic_draw_hot_path_spots_shadowed(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, mNumSpotLights, &sh, mCommandList->Stream()));
+            CrychicThrowIfFailed(crychic_draw_hot_path_spots_shadowed(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, L.mNumSpotLights, &sh, mCommandList->Stream()));
         // :300-305: advance the fence and signal it behind this frame's commands
         mCurrFrameResource->Fence = ++mCurrentFence;
         CrychicHipThrowIfFailed(hipEventRecord(mCurrFrameResource->FenceEvent, mCommandList->Stream()));
@@ -357,6 +361,72 @@ public:
     // The six faces of point light k, back to back (nullptr when it has none).
     ID3D12Resource* PointShadowMap(uint32_t k) { return k < mPointShadowCount ? mPointShadowMaps[k].get() : nullptr; }
 
+    // ---- environment capture (extension: include/crychic_hip.h "environment capture") -------------------------------------------
+    // Renders the built-in scene this object draws into a cube map at (x, y, z) and binds it: face f of level 0 is the frame Draw
+    // produces at dim x dim for face camera f (crychic_cube_capture_cameras; zNear 0.5, the main lens's far plane) with the sky on,
+    // written in place by a dim x dim probe this object keeps (its own planes and cascades of shadowDim, its own copy of the built-in
+    // scene); the local lights, their shadow maps (rendered here first when there are any: call Update before), the cube map, the
+    // G-buffer formats, the textures, blurCount and the timer are this object's, read in place.  crychic_generate_cube_mips then
+    // builds `levels` levels (0 = down to 1 x 1) and SetCubeMap binds the chain.  The cube map bound before is the source -- a capture
+    // never reflects itself, two captures in a row give one bounce -- and becomes the next capture's destination when its size fits,
+    // so a per-frame re-capture allocates nothing.  An object whose planes the caller fills (mRunProducerPasses == false) has no scene
+    // to capture and is refused.
+    void CaptureEnvironment(float x, float y, float z, UINT dim, UINT levels = 0, UINT shadowDim = 1024)
+    {
+        uint32_t full = 1;
+        for (UINT m = dim; m > 1u; m >>= 1) ++full;
+        if (full > 15u) full = 15u;
+        if (levels == 0) levels = full;
+        const bool localShadows = mSpotShadowCount > 0 || mPointShadowCount > 0;
+        if (!mCubeMap || !mRunProducerPasses || (localShadows && !mCurrFrameResource) || dim == 0 || (dim & 1u) || dim > 8192u ||
+            levels > full || shadowDim < 2u)
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::CaptureEnvironment (a cube map bound as the source; the producer passes on; "
+                                   "Update before it with shadowed local lights; dim even, 2 .. 8192; at most floor(log2 dim) + 1 levels)",
+                                   __FILE__, __LINE__);
+        if (localShadows) {                     // the probe reads this object's local-light shadow maps: as Draw would render them now
+            auto items = DrawItems(mRitemLayer[(int)RenderLayer::OpaqueShadow]);
+            if (mSpotShadowCount > 0) DrawSpotShadowMaps(items);
+            if (mPointShadowCount > 0) DrawPointShadowMaps(items);
+        }
+        mCommandList->Flush();                  // what the probe's stream reads is complete
+        if (!mProbe || mProbe->mClientWidth != dim || mProbe->mShadowMapSize != shadowDim) {
+            mProbe.reset();
+            mProbe = std::make_unique<CRYCHIC>(mDeviceOrdinal, dim, dim);
+            mProbe->mShadowMapSize = shadowDim;
+            mProbe->Initialize();
+            mProbe->mSsao->CopyNoiseFrom(*mSsao, mProbe->mCommandList.get());      // the SSAO noise is view-independent: this object's
+            mProbe->mOwner = this;
+        }
+        CRYCHIC& p = *mProbe;
+        p.mBlurCount = mBlurCount; p.mNumDirLights = mNumDirLights; p.mPcfLiteral = mPcfLiteral; p.mSkyEnabled = true;
+        p.mFrustumCullingEnabled = mFrustumCullingEnabled; p.mFuseCameraPasses = mFuseCameraPasses;
+        for (int i = 0; i < 3; ++i) p.mBaseLightDirections[i] = mBaseLightDirections[i];
+        p.mLightRotationAngle = mLightRotationAngle;
+        if (p.mDeferred->FormatFlags() != mDeferred->FormatFlags()) p.SetGBufferFormat(mDeferred->Format(0), mDeferred->Format(1), mDeferred->Format(2));
+        p.mTextures = mTextures;                // the device copies stay this object's (mTexturePlanes)
+        const size_t faceBytes = (size_t)dim * dim * 4u, chainBytes = crychic_cube_chain_bytes(dim, levels);
+        std::unique_ptr<ID3D12Resource> chain = std::move(mSpareCubeMap);          // the cube map the last capture replaced
+        if (!chain || chain->Bytes() != chainBytes) chain = std::make_unique<ID3D12Resource>(chainBytes, ID3D12Resource::DEFAULT_HEAP);
+        const float pos[3] = { x, y, z };
+        crychic_camera cams[6];
+        CrychicThrowIfFailed(crychic_cube_capture_cameras(pos, 0.5f, mCamera.GetFarZ(), cams));
+        for (int f = 0; f < 6; ++f) {
+            const crychic_camera& c = cams[f];
+            p.mCamera.SetPosition(c.pos[0], c.pos[1], c.pos[2]);
+            p.mCamera.LookTo(c.look[0], c.look[1], c.look[2], c.up[0], c.up[1], c.up[2]);
+            p.mCamera.SetLens(c.fovY, c.aspect, c.nearZ, c.farZ);
+            p.mRenderTarget = static_cast<uint8_t*>(chain->Data()) + (size_t)f * faceBytes;
+            p.Update(mLastTimer);
+            p.Draw(mLastTimer);
+        }
+        p.mCommandList->Flush();
+        p.mRenderTarget = nullptr;
+        CrychicThrowIfFailed(crychic_generate_cube_mips(md3dDevice->Ctx(), static_cast<uint8_t*>(chain->Data()), dim, levels, mCommandList->Stream()));
+        mCommandList->Flush();                  // frames in flight may still read the source, which the next capture overwrites
+        mSpareCubeMap = std::move(mCubeMap);
+        SetCubeMap(std::move(chain), dim, levels);
+    }
+
     // ---- one frame on several GPUs (no counterpart in the single-GPU reference) ----------------------------------
     // Rows [row0, row0 + rows) are this GPU's share of the hot path (row0 even).  An empty share is refused: a rank without rows
     // would have nothing to contribute to the gather (and "0 rows" must never come to mean "the whole frame").
@@ -406,6 +476,9 @@ public:
     ID3D12Resource* CurrentBackBuffer() { return mBackBuffer.get(); }
     // `levels` > 1: the resource holds the mip chain in crychic_load_dds_cube_rgba8_mips' layout (the reference binds every level,
     // CRYCHIC.cpp:1148-1151) and Draw announces it with CRYCHIC_LIGHT_CUBE_LEVELS
+    ID3D12Resource* CubeMap() { return mCubeMap.get(); }
+    UINT CubeMapSize() const { return mCubeMapSize; }
+    UINT CubeMapLevels() const { return mCubeMapLevels; }
     void SetCubeMap(std::unique_ptr<ID3D12Resource> cube, UINT dim, UINT levels = 1) { mCubeMap = std::move(cube); mCubeMapSize = dim; mCubeMapLevels = levels ? levels : 1; }
 
     // CRYCHIC::LoadTextures (CRYCHIC.cpp:939-973): the six material textures in heap order (= gTextureMaps indices, :954-959) with the
@@ -801,8 +874,9 @@ private:
         for (int i = 0; i < 3; ++i) { dirs[i][0] = mRotatedLightDirections[i].x; dirs[i][1] = mRotatedLightDirections[i].y; dirs[i][2] = mRotatedLightDirections[i].z; }
         CrychicThrowIfFailed(crychic_update_main_pass_cb(&mCamera.Raw(), mClientWidth, mClientHeight, st, dirs,
                                                          reinterpret_cast<crychic_pass_constants*>(&mMainPassCB)));
-        for (uint32_t k = 0; k < mSpotShadowCount; ++k)                                             // slots 4..11, transposed like :826-830
-            for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) mMainPassCB.ShadowTransforms[4 + k].m[c][r] = mShadowTransforms[4 + k].m[r][c];
+        const CRYCHIC& L = mOwner ? *mOwner : *this;                                                // a capture's probe: its owner's spot shadows
+        for (uint32_t k = 0; k < L.mSpotShadowCount; ++k)                                           // slots 4..11, transposed like :826-830
+            for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) mMainPassCB.ShadowTransforms[4 + k].m[c][r] = L.mShadowTransforms[4 + k].m[r][c];
         mMainPassCB.TotalTime = gt.TotalTime();
         mMainPassCB.DeltaTime = gt.DeltaTime();
         mCurrFrameResource->PassCB->CopyData(0, mMainPassCB);                                       // :866-867
@@ -856,4 +930,10 @@ private:
     float mLightRotationAngle = 0.0f;
     DirectX::XMFLOAT3 mBaseLightDirections[3] = { { 0.57735f, -0.57735f, 0.57735f }, { -0.57735f, -0.57735f, 0.57735f }, { 0.0f, -0.707f, -0.707f } };  // CRYCHIC.h:173-177
     DirectX::XMFLOAT3 mRotatedLightDirections[3];
+    int mDeviceOrdinal = 0;
+    GameTimer mLastTimer;                           // the timer of the last Update
+    const CRYCHIC* mOwner = nullptr;                // CaptureEnvironment, on the probe: whose cube map, local lights and shadow maps Draw reads
+    std::unique_ptr<ID3D12Resource> mSpareCubeMap;  // CaptureEnvironment: the cube map the last capture replaced, the next one's destination
+    uint8_t* mRenderTarget = nullptr;               // CaptureEnvironment, on the probe: the face the lighting pass writes (not owned)
+    std::unique_ptr<CRYCHIC> mProbe;                // CaptureEnvironment's dim x dim renderer, kept across captures; declared last: destroyed first
 };

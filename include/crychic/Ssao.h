@@ -89,6 +89,16 @@ public:
     // (tests/cpp/veneer_driver.cpp renders both).
     bool mLiteralSequence = false;
 
+    // A second Ssao of one application (the probe of CRYCHIC::CaptureEnvironment) samples the first one's noise: the process-wide
+    // rand() sequence has moved on by the time it is built, so the offset vectors and the random-vector texels are copied.
+    void CopyNoiseFrom(const Ssao& other, ID3D12GraphicsCommandList* cmdList)
+    {
+        for (int i = 0; i < 14; ++i) mOffsets[i] = other.mOffsets[i];
+        CrychicHipThrowIfFailed(hipMemcpyAsync(mRandomVectorMap->Data(), other.mRandomVectorMap->Data(), 256 * 256 * 4, hipMemcpyDeviceToDevice,
+                                               cmdList->Stream()));
+        cmdList->Flush();
+    }
+
     ID3D12Resource* AmbientMap1() { return mAmbientMap1.get(); }
     ID3D12Resource* RandomVectorMap() { return mRandomVectorMap.get(); }
     ID3D12Resource* EdgePlane() { return mEdgePlane.get(); }

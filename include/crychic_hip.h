@@ -595,6 +595,38 @@ int crychic_draw_gbuffer_formats(crychic_ctx* ctx, const crychic_pass_constants*
                                  void* g2_dev, uint32_t gbufferFlags, uint32_t* depth_dev, uint32_t W, uint32_t H, uint32_t gRow0,
                                  uint32_t gRows, void* workspace_dev, size_t workspaceBytes, void* stream);
 
+/* ---- environment capture (BUILD-DEFINED EXTENSION): the scene rendered into the cube map ------------- *
+ * The reference's cube map is a file (CRYCHIC.cpp:960,968).  Here the library can produce it: six frames of the hot path, one per
+ * face camera, written straight into level 0 of a chain whose further levels the device then builds.
+ *
+ * Mip chain.  The layout is crychic_load_dds_cube_rgba8_mips': level after level, each level the six faces (+X, -X, +Y, -Y, +Z, -Z)
+ * of d_k = max(dim >> k, 1) squared RGBA8 texels.  Level k+1, face f, texel (x, y), channel c is (a + b + c' + d + 2) >> 2 over the
+ * level-k texels (2x, 2y), (2x+1, 2y), (2x, 2y+1), (2x+1, 2y+1) of the same face, in integer arithmetic; when d_k is odd and
+ * greater than 1 its last row and column are not read; the chain ends at a 1 x 1 level; nothing is filtered across faces. */
+/* Bytes of the first `levels` levels of a dim-texel cube map's chain: the sum over k < levels of 6 * 4 * d_k^2.  Pure host
+ * arithmetic (levels past the 1 x 1 level count 24 bytes each). */
+size_t crychic_cube_chain_bytes(uint32_t dim, uint32_t levels);
+/* Builds levels 1 .. levels - 1 of the chain at chain_dev from its level 0, in place, on `stream`: level 0 is read and never
+ * written, no byte past level levels - 1 is touched, levels == 1 does nothing and succeeds.  ceil((levels - 1) / 6) launches.
+ * levels is 1 .. min(15, floor(log2 dim) + 1); a NULL pointer, dim == 0, levels == 0 or more levels than the face size allows
+ * return CRYCHIC_E_INVALID_ARG, dim > 32768 CRYCHIC_E_UNSUPPORTED.  chain_dev holds RGBA8 texels (4-byte aligned; 16-byte aligned
+ * chains of faces whose size is a multiple of 4 take the 16-byte loads). */
+int crychic_generate_cube_mips(crychic_ctx* ctx, uint8_t* chain_dev, uint32_t dim, uint32_t levels, void* stream);
+/* The six face cameras of a capture at `pos` (host only): camera f has pos, aspect = 1, fovY = (float)(pi / 2), nearZ, farZ and
+ *   face  +X        -X         +Y         -Y         +Z        -Z
+ *   look  (1,0,0)   (-1,0,0)   (0,1,0)    (0,-1,0)   (0,0,1)   (0,0,-1)
+ *   up    (0,1,0)   (0,1,0)    (0,0,-1)   (0,0,1)    (0,1,0)   (0,1,0)
+ * -- the axes and ups of crychic_update_point_shadow_transforms, without its widening.  The constants of a face are what
+ * crychic_update_main_pass_cb, crychic_update_ssao_cb and crychic_update_cascade_shadow_transform make of that camera at
+ * W = H = dim.  Known answer: with depth all clear and CRYCHIC_LIGHT_SKY, the frame of camera f over a one-level cube map of the
+ * frame's own dim is face f of that cube map, byte for byte (the sky pass of a face camera lands on texel centres).
+ * Capture (Crychic.capture_environment, CRYCHIC::CaptureEnvironment): face f of level 0 of the destination is the RGBA8 frame
+ * crychic_draw_hot_path* produces at dim x dim for camera f with CRYCHIC_LIGHT_SKY, out_rgba8_dev pointing at that face; planes and
+ * cascades come from the producers with that camera; everything view-independent and the bound cube map (the source, which the
+ * destination must not alias) are the main frame's; crychic_generate_cube_mips then builds the chain.
+ * CRYCHIC_E_INVALID_ARG for a NULL pointer, a non-finite position, nearZ <= 0 or nearZ >= farZ. */
+int crychic_cube_capture_cameras(const float pos[3], float nearZ, float farZ, crychic_camera cams[6]);
+
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
  * of 2 rows (half-res alignment); the last rank takes the remainder. */

@@ -15,4 +15,4 @@ LD_PRELOAD="$RT" python -m pytest -q -x -m "not gpu" -p no:cacheprovider \
     tests/test_oracle_kat.py tests/test_devmath_host.py tests/test_hostsim_parity.py tests/test_fuzz.py tests/test_golden.py \
     tests/test_numpy_restatements.py tests/test_raster_cpu.py tests/test_constants.py tests/test_culling.py tests/test_textures.py \
     tests/test_point_lights.py tests/test_spot_lights.py tests/test_spot_shadows.py tests/test_point_shadows.py \
-    tests/test_gbuffer_f16_host.py tests/test_cube_chain.py tests/test_sanitized_host.py "$@"
+    tests/test_gbuffer_f16_host.py tests/test_cube_chain.py tests/test_cube_mips_host.py tests/test_sanitized_host.py "$@"
