@@ -140,7 +140,9 @@ int fill_light_params(cry::LightParams& P, const crychic_pass_constants* cb, con
     // CRYCHIC_LIGHT_CUBE_LEVELS: a chain ends at 1 x 1 at the latest
     { const uint32_t levels = (flags >> 16) & 15u;
       uint32_t full = 1; for (uint32_t m = cubeDim; m > 1u; m >>= 1) ++full;
-      if (levels > full) return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", levels, cubeDim, full); }
+      if (levels > full) return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", levels, cubeDim, full);
+      if ((flags & CRYCHIC_LIGHT_CUBE_GLOSS) && levels < 2u)
+          return fail(CRYCHIC_E_INVALID_ARG, "CRYCHIC_LIGHT_CUBE_GLOSS needs a chain: CRYCHIC_LIGHT_CUBE_LEVELS(n) with n > 1"); }
     cry::bind_light_params(P, *cb, shadow, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags);
     return 0;
 }
@@ -188,10 +190,11 @@ int bind_local_lights(cry::LightParams& P, cry::SpotShadows& S, cry::PointShadow
     return 0;
 }
 
-// With a mip chain the level of detail comes from 2 x 2 pixel quads: a call's rows have to be whole quad rows.
+// With a mip chain the level of detail comes from 2 x 2 pixel quads: a call's rows have to be whole quad rows.  Not so with
+// CRYCHIC_LIGHT_CUBE_GLOSS, where it comes from the pixel's roughness.
 int check_chain_rows(const cry::LightParams& P, uint32_t row0, uint32_t rows, uint32_t H)
 {
-    if (P.cubeLevels > 1u && ((row0 & 1u) || ((rows & 1u) && row0 + rows != H)))
+    if (P.cubeLevels > 1u && !(P.flags & CRYCHIC_LIGHT_CUBE_GLOSS) && ((row0 & 1u) || ((rows & 1u) && row0 + rows != H)))
         return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u): with a cube map mip chain a call covers whole pixel quads (even row0; even rows unless they end the frame)", row0, rows);
     return 0;
 }
@@ -709,6 +712,25 @@ int crychic_generate_cube_mips(crychic_ctx* ctx, uint8_t* chain_dev, uint32_t di
         return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", levels, dim, full);
     if (reinterpret_cast<uintptr_t>(chain_dev) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "cube map chain is not 4-byte aligned");
     CRY_HIP(cry::launch_cube_mips(chain_dev, dim, levels, (hipStream_t)stream));
+    return 0;
+}
+
+int crychic_prefilter_cube_chain(crychic_ctx* ctx, const uint8_t* src_chain_dev, uint8_t* dst_chain_dev, uint32_t dim, uint32_t levels,
+                                 void* stream)
+{
+    if (int rc = bind(ctx)) return rc;
+    if (!src_chain_dev || !dst_chain_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (dim == 0) return fail(CRYCHIC_E_INVALID_ARG, "cube map face size 0");
+    // the chain sampler addresses texels by 32-bit byte offsets, as it does in the lighting pass (cubeDim <= 8192 there)
+    if (dim > 8192u) return fail(CRYCHIC_E_UNSUPPORTED, "cube map face size %u exceeds 8192", dim);
+    const uint32_t full = cry::cube_full_levels(dim) < 15u ? cry::cube_full_levels(dim) : 15u;
+    if (levels == 0 || levels > full)
+        return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", levels, dim, full);
+    const uintptr_t s = reinterpret_cast<uintptr_t>(src_chain_dev), d = reinterpret_cast<uintptr_t>(dst_chain_dev);
+    if ((s | d) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "cube map chain is not 4-byte aligned");
+    const size_t bytes = crychic_cube_chain_bytes(dim, levels);
+    if (s < d + bytes && d < s + bytes) return fail(CRYCHIC_E_INVALID_ARG, "the source and destination chains overlap");
+    CRY_HIP(cry::launch_cube_prefilter(src_chain_dev, dst_chain_dev, dim, levels, (hipStream_t)stream));
     return 0;
 }
 

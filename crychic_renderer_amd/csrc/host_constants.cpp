@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstring>
 #include "crychic_hip.h"
+#include "internal.hpp"
 
 namespace {
 
@@ -341,6 +342,50 @@ int crychic_cube_capture_cameras(const float pos[3], float nearZ, float farZ, cr
         cams[f].nearZ = nearZ;
         cams[f].farZ = farZ;
     }
+    return 0;
+}
+
+// The sample table of level `level` of a prefiltered chain (crychic_hip.h "sample table"): GGX importance samples of the lobe
+// a^2 = (level / (levels - 1))^2 around N = V = R, Hammersley points, all in double and stored as float.
+int crychic_cube_prefilter_samples(uint32_t dim, uint32_t levels, uint32_t level, float samples[32][4], uint32_t* count, float* rcpWeight)
+{
+    if (!samples || !count || !rcpWeight) return cry::fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (dim == 0) return cry::fail(CRYCHIC_E_INVALID_ARG, "cube map face size 0");
+    if (levels < 2 || levels > 15u) return cry::fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels: a prefiltered level needs a chain of 2 .. 15", levels);
+    if (level < 1 || level >= levels) return cry::fail(CRYCHIC_E_INVALID_ARG, "level %u outside 1 .. %u", level, levels - 1u);
+    const double pi = 3.14159265358979323846;
+    const double rho = (double)level / (double)(levels - 1u), a2 = rho * rho;
+    const double omegaP = 4.0 * pi / (6.0 * (double)dim * (double)dim);
+    const double top = (double)(levels - 1u);
+    uint32_t n = 0;
+    double sum = 0.0;
+    for (uint32_t i = 0; i < 32u; ++i) {
+        uint32_t b = i;                                  // base-2 radical inverse: the bits of i mirrored behind the point
+        b = (b << 16) | (b >> 16);
+        b = ((b & 0x00FF00FFu) << 8) | ((b & 0xFF00FF00u) >> 8);
+        b = ((b & 0x0F0F0F0Fu) << 4) | ((b & 0xF0F0F0F0u) >> 4);
+        b = ((b & 0x33333333u) << 2) | ((b & 0xCCCCCCCCu) >> 2);
+        b = ((b & 0x55555555u) << 1) | ((b & 0xAAAAAAAAu) >> 1);
+        const double xi1 = ((double)i + 0.5) / 32.0, xi2 = (double)b / 4294967296.0;
+        const double cos2 = (1.0 - xi1) / (1.0 + (a2 - 1.0) * xi1), phi = 2.0 * pi * xi2;
+        const double w = 2.0 * cos2 - 1.0;
+        if (!(w > 0.0)) continue;
+        const double cosT = std::sqrt(cos2), sinT = std::sqrt(1.0 - cos2);
+        const double t = (a2 - 1.0) * cos2 + 1.0;
+        const double D = a2 / (pi * t * t);
+        const double omegaS = 1.0 / (32.0 * D / 4.0);
+        double lod = 0.5 * std::log2(omegaS / omegaP) + 1.0;
+        lod = lod < 0.0 ? 0.0 : (lod > top ? top : lod);
+        samples[n][0] = (float)(2.0 * cosT * sinT * std::cos(phi));
+        samples[n][1] = (float)(2.0 * cosT * sinT * std::sin(phi));
+        samples[n][2] = (float)w;
+        samples[n][3] = (float)lod;
+        sum += w;
+        ++n;
+    }
+    for (uint32_t i = n; i < 32u; ++i) samples[i][0] = samples[i][1] = samples[i][2] = samples[i][3] = 0.0f;
+    *count = n;
+    *rcpWeight = (float)(1.0 / sum);
     return 0;
 }
 

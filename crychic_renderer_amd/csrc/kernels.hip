@@ -663,6 +663,8 @@ hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, 
                         uint32_t numSpots, const SpotShadows* shadows, const PointShadows* pointShadows)
 {
     if (rows == 0) return hipSuccess;
+    if (P.flags & CRYCHIC_LIGHT_CUBE_GLOSS)       // the level comes from the pixel's roughness: no quads, its own kernels (light_gloss.hip)
+        return launch_light_gloss(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, rows, stream, spots, numSpots, shadows, pointShadows);
     const dim3 grid = grid_for(P.W, rows);
     const bool mips = P.cubeLevels > 1u;          // the chain: quads inside wavefronts (light_tile_pixel), so the rows must start a quad
     if (mips && (row0 & 1u)) return hipErrorInvalidValue;

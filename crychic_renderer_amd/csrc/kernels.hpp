@@ -63,10 +63,20 @@ hipError_t launch_light_formats(const LightParams& P, const void* g0, const void
                                 const uint16_t* ambient, const uint8_t* cube, uint8_t* out, float* radiance, uint32_t row0, uint32_t rows,
                                 hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
                                 const PointShadows* pointShadows);
+// light_gloss.hip: the same pass with CRYCHIC_LIGHT_CUBE_GLOSS in P.flags (P.cubeLevels > 1) -- light_gloss_kernel for a frame without
+// local lights, light_gloss_local_kernel for every other; planes of any format mix.
+hipError_t launch_light_gloss(const LightParams& P, const void* g0, const void* g1, const void* g2, const uint32_t* depth,
+                              const uint16_t* ambient, const uint8_t* cube, uint8_t* out, float* radiance, uint32_t row0, uint32_t rows,
+                              hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
+                              const PointShadows* pointShadows);
 
 // cube_mips.hip: levels 1 .. levels - 1 of an RGBA8 cube map's chain from its level 0, in place (cube_mips_core.hpp); one launch per
 // six levels on `stream`.  The caller has checked dim and levels.
 hipError_t launch_cube_mips(uint8_t* chain, uint32_t dim, uint32_t levels, hipStream_t stream);
+
+// cube_prefilter.hip: level 0 of `src` copied to `dst` and levels 1 .. levels - 1 of `dst` prefiltered from the chain `src`
+// (cube_prefilter_core.hpp); one copy and one launch per level on `stream`.  The caller has checked dim, levels and the overlap.
+hipError_t launch_cube_prefilter(const uint8_t* src, uint8_t* dst, uint32_t dim, uint32_t levels, hipStream_t stream);
 
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment

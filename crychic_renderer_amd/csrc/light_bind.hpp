@@ -89,11 +89,13 @@ enum class LightFamily {
     FormatsFrame,     // light_formats_kernel: a half4 plane (CRYCHIC_GBUFFER_G*_F16), no local light
     FormatsLocal,     // light_point_shadows_formats_kernel: a half4 plane and local lights of whatever kind; both shadow functors
                       // whatever the counts
+    // CRYCHIC_LIGHT_CUBE_GLOSS maps onto these two as well: light_gloss_kernel and light_gloss_local_kernel (light_gloss.hip) compile
+    // in what they do -- planes of any format mix, FIX, both shadow functors -- with CubeGloss as the lookup.
 };
 inline LightFamily light_family(uint32_t flags, uint32_t numPointLights, uint32_t numSpots, uint32_t spotShadowCount,
                                 uint32_t pointShadowCount, uint32_t cubeLevels)
 {
-    if (flags & CRYCHIC_GBUFFER_F16_MASK) return (numPointLights || numSpots) ? LightFamily::FormatsLocal : LightFamily::FormatsFrame;
+    if (flags & (CRYCHIC_GBUFFER_F16_MASK | CRYCHIC_LIGHT_CUBE_GLOSS)) return (numPointLights || numSpots) ? LightFamily::FormatsLocal : LightFamily::FormatsFrame;
     if (pointShadowCount) return LightFamily::PointShadows;
     if (numSpots && spotShadowCount) return LightFamily::SpotsShadowed;
     if (numSpots) return LightFamily::Spots;

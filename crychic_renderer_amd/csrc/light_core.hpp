@@ -646,6 +646,42 @@ struct CubeChain {
         return cube_trilinear<false>(cube, P.cubeDim, P.cubeLevels, f.r, lod);
     }
 };
+// cube_trilinear in two halves, for a caller that has other loads to issue, or the next lookup to address, before it filters: the
+// addresses and the four pair loads of both levels, then the two filters and the mix -- the same arithmetic, bit for bit.
+struct CubeTrilinearFetch { CubeLevelAddr a0, a1; RawPair p00, p01, p10, p11; float frac; };
+CRY_HD CubeTrilinearFetch cube_trilinear_fetch(const uint32_t* __restrict__ chain, uint32_t dim, uint32_t levels, f3 r, float lod)
+{
+    const uint32_t l0 = (uint32_t)lod;
+    const uint32_t l1 = l0 + 1u < levels ? l0 + 1u : l0;
+    uint32_t off0 = 0;
+    for (uint32_t k = 0; k + 1u < levels; ++k) { const uint32_t d = cube_level_dim(dim, k); off0 += k < l0 ? 6u * d * d : 0u; }
+    const uint32_t d0 = cube_level_dim(dim, l0), d1 = cube_level_dim(dim, l1);
+    const uint32_t off1 = off0 + (l1 > l0 ? 6u * d0 * d0 : 0u);
+    CubeTrilinearFetch f;
+    f.frac = lod - (float)l0;
+    f.a0 = cube_level_address(off0, d0, r);
+    f.a1 = cube_level_address(off1, d1, r);
+    f.p00 = load_pair(chain, f.a0.t0); f.p01 = load_pair(chain, f.a0.t1);
+    f.p10 = load_pair(chain, f.a1.t0); f.p11 = load_pair(chain, f.a1.t1);
+    return f;
+}
+template <bool WANT_ALPHA>
+CRY_HD f4 cube_trilinear_resolve(const CubeTrilinearFetch& f)
+{
+    const f4 c0 = cube_resolve<WANT_ALPHA>(cube_level_pick(f.a0, f.p00, f.p01));
+    const f4 c1 = cube_resolve<WANT_ALPHA>(cube_level_pick(f.a1, f.p10, f.p11));
+    return f4{ fma(f.frac, c1.x - c0.x, c0.x), fma(f.frac, c1.y - c0.y, c0.y), fma(f.frac, c1.z - c0.z, c0.z), WANT_ALPHA ? fma(f.frac, c1.w - c0.w, c0.w) : 0.0f };
+}
+// ... or a chain prefiltered by roughness (CRYCHIC_LIGHT_CUBE_GLOSS) at the level of the pixel's own roughness,
+// lod = saturate(roughness) * (levels - 1) (NaN -> 0).  The level is known before the pixel's gathers are issued, so both levels'
+// pair loads travel with them: one round trip, no quad, no vote.
+struct CubeGloss {
+    float lod;
+    typedef CubeTrilinearFetch Fetch;
+    CRY_HD Fetch fetch(const LightParams& P, const uint32_t* __restrict__ cube, f3 r) const { return cube_trilinear_fetch(cube, P.cubeDim, P.cubeLevels, r, lod); }
+    CRY_HD f4 resolve(const LightParams&, const uint32_t* __restrict__, const Fetch& f) const { return cube_trilinear_resolve<false>(f); }
+};
+CRY_HD CubeGloss cube_gloss(const LightParams& P, float roughness) { return CubeGloss{ saturate(roughness) * (float)(P.cubeLevels - 1u) }; }
 // `flat` for a set of lanes: on the device a vote of the lanes that are active at the call, on the host the lane's own answer
 CRY_HD bool cube_chain_flat(float lod)
 {

@@ -75,7 +75,10 @@ __device__ __forceinline__ float quad_reflection_lod(const LightParams& P, bool 
 
 // PLANE: f4a = three float4 planes, void = each plane float4 or half4 by its CRYCHIC_GBUFFER_G*_F16 bit of P.flags (light_core.hpp
 // gbuffer_load); whatever consumes a texel -- the quad exchange of MIPS, the tile cull below -- consumes the widened value.
-template <bool ZERO_RADIUS, bool FIX, bool MIPS, class PLANE>
+// GLOSS (light_gloss.hip, never with MIPS): the reflection lookup takes the chain at the level of the pixel's roughness (CubeGloss);
+// the pixels keep the 64 x 1 footprint of a wavefront, and the sky reads level 0.  `if constexpr`: the other instantiations hold no
+// trace of it.
+template <bool ZERO_RADIUS, bool FIX, bool MIPS, class PLANE, bool GLOSS = false>
 __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLANE* __restrict__ g0, const PLANE* __restrict__ g1,
                                                  const PLANE* __restrict__ g2, const uint32_t* __restrict__ depth,
                                                  const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
@@ -110,6 +113,10 @@ __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLA
     // coverage: the reference re-rasterises the opaque items with LESS against depth cleared to 1.0
     // (CRYCHIC.cpp:248,273) -- exactly the pixels whose normal/depth pass depth is below the clear value.
     if ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu) {
+        if constexpr (GLOSS) {
+            const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
+            lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX, CubeGloss>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, NoPointLights(), cube_gloss(P, G1.w));
+        } else
         lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), CRY_GBUFFER_TEXEL(g1, idx, h1), CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube);
     } else if (P.flags & CRYCHIC_LIGHT_SKY) {
         lit = sky_pixel(P, cube, x, y);
@@ -134,7 +141,7 @@ __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLA
 // POINT_SHADOWED (light_point_shadows_kernel): point lights k < pointShadows->count take their cube shadow (PointShadowOf) the same
 // way.  The mask word is read once per wavefront (readfirstlane: every lane reads the same LDS word), so the walk's light index is
 // scalar, and with it the light's projection and map; the face is per lane (point_face's selects).
-template <bool ZERO_RADIUS, bool MIPS, bool SPOTS, bool SHADOWED = false, bool POINT_SHADOWED = false, class PLANE = f4a>
+template <bool ZERO_RADIUS, bool MIPS, bool SPOTS, bool SHADOWED = false, bool POINT_SHADOWED = false, class PLANE = f4a, bool GLOSS = false>
 __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLANE* __restrict__ g0, const PLANE* __restrict__ g1,
                                                  const PLANE* __restrict__ g2, const uint32_t* __restrict__ depth,
                                                  const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
@@ -245,6 +252,10 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLA
                 }
             }
         };
+        if constexpr (GLOSS) {
+            const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
+            lit = light_pixel<ZERO_RADIUS, decltype(culled), true, CubeGloss>(P, G0, G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, culled, cube_gloss(P, G1.w));
+        } else
         if (MIPS) lit = light_pixel<ZERO_RADIUS, decltype(culled), true, CubeChain>(P, G0, CRY_GBUFFER_TEXEL(g1, idx, h1), G2, ambient, cube, culled, CubeChain{ lod, cube_chain_flat(lod) });
         else lit = light_pixel<ZERO_RADIUS, decltype(culled), true>(P, G0, CRY_GBUFFER_TEXEL(g1, idx, h1), CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, culled);
     } else if (P.flags & CRYCHIC_LIGHT_SKY) {

@@ -1,11 +1,13 @@
 """python -m crychic_renderer_amd.demo [--size WxH] [--out frame.ppm] [--textures DIR] [--cube FILE.dds] [--gbuffer f32|mixed|f16]
-                                   [--capture-env X,Y,Z [--capture-dim N]]
+                                   [--capture-env X,Y,Z [--capture-dim N]] [--gloss]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
 --capture-env: before the frame, the scene is rendered into a cube map at X,Y,Z (Crychic.capture_environment: six faces of
 --capture-dim texels and their mip chain, built on the device) and the frame is rendered with that chain bound, so the boxes and the
-grid show up in the reflections."""
+grid show up in the reflections.
+--gloss (with --cube or --capture-env): the chain is prefiltered by roughness on the device (Crychic.prefilter_cube_map; a --cube file
+without a chain gets its box chain first) and bound with glossy reflections, so a rough surface shows a blurred environment."""
 import argparse
 import ctypes as C
 
@@ -25,7 +27,11 @@ def main():
     ap.add_argument("--capture-env", default="", metavar="X,Y,Z", help="capture the environment at this position before the frame and render "
                                                                        "with the captured cube map bound")
     ap.add_argument("--capture-dim", type=int, default=256, help="face size of the captured cube map (even)")
+    ap.add_argument("--gloss", action="store_true", help="prefilter the cube map chain by roughness and render glossy reflections "
+                                                         "(needs --cube or --capture-env)")
     a = ap.parse_args()
+    if a.gloss and not (a.cube or a.capture_env):
+        ap.error("--gloss needs --cube or --capture-env")
     W, H = (int(v) for v in a.size.lower().split("x"))
     import torch
     from . import Context, Crychic, LIGHT_SKY, SceneGeometry, check, geometry as g, lib, scene
@@ -39,7 +45,15 @@ def main():
     app = Crychic(ctx, W, H, torch.from_numpy(consts.randvec.copy()).to(ctx.device), cube, shadow_dim=a.shadow_dim, gbuffer_formats=a.gbuffer)
     if a.cube:            # with the mip chain the file stores, as the reference binds it (CRYCHIC.cpp:1148-1151)
         chain, dim, levels = g.load_dds_cube_mips(a.cube)
-        app.set_cube_map(torch.from_numpy(chain).to(ctx.device), dim=dim, levels=levels)
+        chain = torch.from_numpy(chain).to(ctx.device)
+        if a.gloss:
+            if levels < 2:        # the file stores level 0 alone: its box chain, built on the device
+                levels = g.cube_full_levels(dim)
+                full = torch.empty((g.cube_chain_bytes(dim, levels),), dtype=torch.uint8, device=ctx.device)
+                full[:chain.numel()] = chain
+                chain = app.generate_cube_mips(full, dim, levels)
+            chain = app.prefilter_cube_map(chain, dim, levels)
+        app.set_cube_map(chain, dim=dim, levels=levels, gloss=a.gloss and levels > 1)
     app.mMainPassCB, app.mSsaoCB = consts.pass_cb, consts.ssao_cb
     for k in range(4):
         cb = PassConstants()
@@ -52,8 +66,8 @@ def main():
         pos = [float(v) for v in a.capture_env.split(",")]
         if len(pos) != 3:
             ap.error("--capture-env takes X,Y,Z")
-        chain, dim, levels = app.capture_environment(pos, geo, sgeo, dim=a.capture_dim)
-        app.set_cube_map(chain, dim, levels)
+        chain, dim, levels = app.capture_environment(pos, geo, sgeo, dim=a.capture_dim, prefilter=a.gloss)
+        app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1)
         print("captured the environment at (%g, %g, %g): %d-texel faces, %d levels" % (pos[0], pos[1], pos[2], dim, levels))
     app.Draw()
     torch.cuda.synchronize()

@@ -189,6 +189,15 @@ def cube_capture_cameras(pos, z_near=0.5, z_far=100.0):
     return cams
 
 
+def cube_prefilter_samples(dim, levels, level):
+    """The sample table of level `level` of a prefiltered chain (crychic_cube_prefilter_samples): (samples, rcp_weight), samples a
+    (count, 4) float32 array of the kept entries { lx, ly, lz, lod } and rcp_weight the float32 1 / sum of their weights."""
+    s = np.zeros((32, 4), np.float32)
+    n, r = C.c_uint32(), C.c_float()
+    check(lib.crychic_cube_prefilter_samples(int(dim), int(levels), int(level), s.ctypes.data, C.byref(n), C.byref(r)))
+    return s[:n.value].copy(), np.float32(r.value)
+
+
 def texture_levels(t):
     """(flat uint8 array of all levels back to back, width, height, mipLevels) for a texture given as one H x W x 4 array or as a
     list of level arrays (level k = max(1, W >> k) x max(1, H >> k))."""

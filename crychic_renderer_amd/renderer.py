@@ -191,6 +191,7 @@ class Crychic:
         self.mCubeMap = cube
         self.mCubeMapLevels = 1      # set_cube_map: > 1 = mCubeMap is a flat mip chain (CRYCHIC_LIGHT_CUBE_LEVELS), mCubeMapSize its level-0 face size
         self.mCubeMapSize = None
+        self.mCubeMapGloss = False   # set_cube_map(gloss=True): the chain is prefiltered by roughness (CRYCHIC_LIGHT_CUBE_GLOSS)
         self.mDepthStencilBuffer = torch.full((height, width), 0xFFFFFF, device=ctx.device, dtype=torch.int32)
         self.mBackBuffer = torch.zeros((height, width, 4), device=ctx.device, dtype=torch.uint8)
         self.mMainPassCB = PassConstants()
@@ -201,6 +202,7 @@ class Crychic:
         self.pcfLiteral = 1          # capture_environment: the `literal` of crychic_pcf_search_radius for the capture's own shadow map
         self.flags = 0
         self._probes = {}            # capture_environment: (dim, shadow_dim) -> the dim x dim probe renderer, kept across captures
+        self._probe_chains = {}      # capture_environment(prefilter=True): (dim, levels) -> the scratch box chain
         self.mPointLights = None     # extension: torch uint8 tensor holding an array of Light structs (48 B each)
         self.mSpotLights = None      # extension: the same for the spot lights (crychic_draw_hot_path_spots)
         self.mSpotShadowMaps = None  # extension: (count, dim, dim) int32 D24 maps of the first spot lights (set_spot_shadows)
@@ -226,7 +228,7 @@ class Crychic:
         self.mDeferred.mGBuffer = [planes["g%d" % k].to(_GBUFFER_DTYPES[self.mDeferred.mFormats[k]]) for k in range(3)]
         self.mShadowMap.mShadowMap = planes["shadow"]
         self.mCubeMap = planes["cube"]
-        self.mCubeMapLevels, self.mCubeMapSize = 1, None
+        self.mCubeMapLevels, self.mCubeMapSize, self.mCubeMapGloss = 1, None, False
         self.mSsao.mRandomVectorMap = planes["randvec"]
         self.mMainPassCB = planes["consts"].pass_cb
         self.mSsaoCB = planes["consts"].ssao_cb
@@ -238,6 +240,8 @@ class Crychic:
         f.W, f.H = W, H
         f.blurCount, f.numDirLights = int(self.blurCount), int(self.numDirLights)
         f.pcfSearchRadius, f.flags = float(self.pcfSearchRadius), int(self.flags) | ((int(self.mCubeMapLevels) & 15) << 16 if self.mCubeMapLevels > 1 else 0)
+        if self.mCubeMapGloss:
+            f.flags |= _lib.LIGHT_CUBE_GLOSS
         f.flags = (f.flags & ~_lib.GBUFFER_F16_MASK) | gbuffer_flags(self.mDeferred.mGBuffer)      # each plane's format: its tensor's dtype
         f.row0, f.rows = int(row0), int(H - row0 if rows is None else rows)
         f.normal_dev = self.mSsao.mNormalMap.data_ptr()
@@ -269,7 +273,7 @@ class Crychic:
                ssao.mNormalMap.data_ptr(), ssao.mRandomVectorMap.data_ptr(), self.mDepthStencilBuffer.data_ptr(),
                g0.data_ptr(), g1.data_ptr(), g2.data_ptr(), g0.dtype, g1.dtype, g2.dtype,
                sm.data_ptr(), int(sm.shape[-1]), self.mCubeMap.data_ptr(), int(self.mCubeMapSize or self.mCubeMap.shape[1]), int(self.mCubeMapLevels),
-               self.blurCount, self.numDirLights, self.pcfSearchRadius, self.flags,
+               bool(self.mCubeMapGloss), self.blurCount, self.numDirLights, self.pcfSearchRadius, self.flags,
                0 if self.mPointLights is None else self.mPointLights.data_ptr(),
                0 if self.mSpotLights is None else self.mSpotLights.data_ptr())
         if self._desc is None:
@@ -317,10 +321,14 @@ class Crychic:
         check(lib.crychic_draw_hot_path(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(self.mMainPassCB), C.byref(f),
                                         _stream(self.ctx.device)))
 
-    def set_cube_map(self, cube, dim=None, levels=1):
+    def set_cube_map(self, cube, dim=None, levels=1, gloss=False):
         """The sky cube map: a 6 x dim x dim x 4 uint8 tensor (level 0 alone), or -- with `levels` > 1 -- the flat mip chain
         geometry.cube_mip_chain / load_dds_cube_mips produce (the reference binds the whole chain, CRYCHIC.cpp:1148-1151): the
-        reflection and sky lookups are then trilinear (CRYCHIC_LIGHT_CUBE_LEVELS)."""
+        reflection and sky lookups are then trilinear (CRYCHIC_LIGHT_CUBE_LEVELS).  gloss (needs levels > 1): the chain is one
+        prefilter_cube_map made, and the reflection lookup takes its level from the pixel's roughness (CRYCHIC_LIGHT_CUBE_GLOSS)."""
+        if gloss and int(levels) < 2:
+            raise CrychicError(-1, "set_cube_map: gloss needs a chain (levels > 1)")
+        self.mCubeMapGloss = bool(gloss)
         self.mCubeMap = cube
         self.mCubeMapLevels = int(levels)
         self.mCubeMapSize = int(dim) if dim is not None else None
@@ -334,8 +342,24 @@ class Crychic:
         check(lib.crychic_generate_cube_mips(self.ctx.handle, _ptr(chain), int(dim), levels, _stream(self.ctx.device)))
         return chain
 
+    def prefilter_cube_map(self, chain, dim, levels, out=None):
+        """Extension: the chain `chain` (a uint8 tensor: a box chain of generate_cube_mips or of a DDS file) prefiltered by roughness
+        (crychic_prefilter_cube_chain; include/crychic_hip.h "prefiltered chain"): level 0 copied, level k convolved with the GGX
+        lobe of roughness k / (levels - 1).  out: a uint8 tensor of at least geometry.cube_chain_bytes(dim, levels) bytes that does
+        not overlap `chain` (default: a new one).  Returns `out`."""
+        from .geometry import cube_chain_bytes
+        nbytes = cube_chain_bytes(dim, levels)
+        if out is None:
+            out = torch.empty((nbytes,), device=self.ctx.device, dtype=torch.uint8)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < nbytes or out.device != chain.device:
+            raise CrychicError(-1, "prefilter_cube_map: out must be a contiguous uint8 device tensor of at least %d bytes" % nbytes)
+        if chain.dtype != torch.uint8 or not chain.is_contiguous() or chain.numel() < nbytes:
+            raise CrychicError(-1, "prefilter_cube_map: chain must be a contiguous uint8 device tensor of at least %d bytes" % nbytes)
+        check(lib.crychic_prefilter_cube_chain(self.ctx.handle, _ptr(chain), _ptr(out), int(dim), int(levels), _stream(self.ctx.device)))
+        return out
+
     def capture_environment(self, pos, geometry, shadow_geometry=None, dim=256, levels=None, z_near=0.5, z_far=None, shadow_dim=1024,
-                            out=None):
+                            out=None, prefilter=False):
         """Extension: renders the scene into a cube map at `pos` and builds its mip chain on the device (include/crychic_hip.h
         "environment capture").  Face f of level 0 is the frame Draw produces at dim x dim for face camera f
         (crychic_cube_capture_cameras) with CRYCHIC_LIGHT_SKY, written in place: `geometry` (a SceneGeometry) fills the normal map,
@@ -347,7 +371,8 @@ class Crychic:
         captures in a row give one bounce.  levels None = the full chain; z_far None = 100 (the reference's lens, CRYCHIC.cpp:114).
         out: a uint8 tensor of at least geometry.cube_chain_bytes(dim, levels) bytes that must not overlap the bound cube map
         (default: a new one).  The probe renderer is kept (release_capture_probes frees it), so a re-capture with `out` allocates nothing.  Returns (chain, dim, levels);
-        binding it is the caller's set_cube_map(chain, dim, levels)."""
+        binding it is the caller's set_cube_map(chain, dim, levels) -- with gloss=True for a prefiltered one.  prefilter: the chain returned is the captured box chain
+        prefiltered by roughness (prefilter_cube_map); the box chain lives in a scratch tensor kept with the probes."""
         import numpy as np
         from .geometry import cube_capture_cameras, cube_chain_bytes, cube_full_levels
         dim, shadow_dim = int(dim), int(shadow_dim)
@@ -369,6 +394,11 @@ class Crychic:
             raise CrychicError(-1, "capture_environment: out must be a contiguous uint8 device tensor of at least %d bytes" % nbytes)
         if out.data_ptr() < src.data_ptr() + src.numel() * src.element_size() and src.data_ptr() < out.data_ptr() + nbytes:
             raise CrychicError(-1, "capture_environment: the destination aliases the bound cube map (a capture never reflects itself)")
+        final = out
+        if prefilter:           # the faces and their box chain go to the scratch chain, the prefiltered chain to `out`
+            out = self._probe_chains.get((dim, levels))
+            if out is None:
+                out = self._probe_chains[(dim, levels)] = torch.empty((nbytes,), device=self.ctx.device, dtype=torch.uint8)
         if probe.mDeferred.mFormats != self.mDeferred.mFormats:
             probe.set_gbuffer_formats(self.mDeferred.mFormats)
         # the local lights' shadow maps are the main frame's: render them now if Draw has not yet
@@ -378,6 +408,7 @@ class Crychic:
             self.DrawPointShadowMaps()
         probe.mSsao.mRandomVectorMap = self.mSsao.mRandomVectorMap
         probe.mCubeMap, probe.mCubeMapLevels, probe.mCubeMapSize = src, self.mCubeMapLevels, self.mCubeMapSize
+        probe.mCubeMapGloss = self.mCubeMapGloss        # a capture of a glossy scene is glossy
         probe.blurCount, probe.numDirLights, probe.flags = self.blurCount, self.numDirLights, int(self.flags) | _lib.LIGHT_SKY
         probe.pcfSearchRadius = lib.crychic_pcf_search_radius(shadow_dim, int(self.pcfLiteral))
         probe.mPointLights, probe.mSpotLights = self.mPointLights, self.mSpotLights
@@ -422,11 +453,14 @@ class Crychic:
             probe.mBackBuffer = out[f * dim * dim * 4:(f + 1) * dim * dim * 4].view(dim, dim, 4)
             probe.Draw()
         self.generate_cube_mips(out, dim, levels)
+        if prefilter:
+            out = self.prefilter_cube_map(out, dim, levels, out=final)
         return out, dim, levels
 
     def release_capture_probes(self):
         """Frees the probe renderers capture_environment keeps (one per (dim, shadow_dim) it was called with)."""
         self._probes.clear()
+        self._probe_chains.clear()
 
     def set_point_lights(self, lights):
         """Extension: `lights` is a ctypes array of Light (or None); copied to the device.  Shadows set with set_point_shadows are

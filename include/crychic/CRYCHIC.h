@@ -217,6 +217,7 @@ public:
         f.numDirLights = mNumDirLights;
         f.pcfSearchRadius = crychic_pcf_search_radius(mShadowMap->Width(), mPcfLiteral ? 1 : 0);
         f.flags = (mSkyEnabled ? CRYCHIC_LIGHT_SKY : 0u) | (L.mCubeMapLevels > 1 ? CRYCHIC_LIGHT_CUBE_LEVELS(L.mCubeMapLevels) : 0u);   // :278-279, :1148-1151
+        if (L.mGlossyReflections && L.mCubeMapLevels > 1) f.flags |= CRYCHIC_LIGHT_CUBE_GLOSS;      // the level from the pixel's roughness
         f.flags |= mDeferred->FormatFlags();                                                        // a half4 plane: its CRYCHIC_GBUFFER_G*_F16 bit
         f.row0 = mStripRow0; f.rows = mWholeFrame ? mClientHeight : mStripRows;                      // whole frame unless SetStrip / JoinNode
         f.normal_dev = mSsao->NormalMap()->Data();
@@ -370,7 +371,8 @@ public:
     // builds `levels` levels (0 = down to 1 x 1) and SetCubeMap binds the chain.  The cube map bound before is the source -- a capture
     // never reflects itself, two captures in a row give one bounce -- and becomes the next capture's destination when its size fits,
     // so a per-frame re-capture allocates nothing.  An object whose planes the caller fills (mRunProducerPasses == false) has no scene
-    // to capture and is refused.
+    // to capture and is refused.  With SetGlossyReflections(true) the faces and their box chain go to a scratch chain this object
+    // keeps, and the chain bound is crychic_prefilter_cube_chain's of it.
     void CaptureEnvironment(float x, float y, float z, UINT dim, UINT levels = 0, UINT shadowDim = 1024)
     {
         uint32_t full = 1;
@@ -407,6 +409,9 @@ public:
         const size_t faceBytes = (size_t)dim * dim * 4u, chainBytes = crychic_cube_chain_bytes(dim, levels);
         std::unique_ptr<ID3D12Resource> chain = std::move(mSpareCubeMap);          // the cube map the last capture replaced
         if (!chain || chain->Bytes() != chainBytes) chain = std::make_unique<ID3D12Resource>(chainBytes, ID3D12Resource::DEFAULT_HEAP);
+        if (mGlossyReflections && (!mCaptureBoxChain || mCaptureBoxChain->Bytes() != chainBytes))
+            mCaptureBoxChain = std::make_unique<ID3D12Resource>(chainBytes, ID3D12Resource::DEFAULT_HEAP);
+        ID3D12Resource* box = mGlossyReflections ? mCaptureBoxChain.get() : chain.get();         // where the faces are rendered
         const float pos[3] = { x, y, z };
         crychic_camera cams[6];
         CrychicThrowIfFailed(crychic_cube_capture_cameras(pos, 0.5f, mCamera.GetFarZ(), cams));
@@ -415,13 +420,16 @@ public:
             p.mCamera.SetPosition(c.pos[0], c.pos[1], c.pos[2]);
             p.mCamera.LookTo(c.look[0], c.look[1], c.look[2], c.up[0], c.up[1], c.up[2]);
             p.mCamera.SetLens(c.fovY, c.aspect, c.nearZ, c.farZ);
-            p.mRenderTarget = static_cast<uint8_t*>(chain->Data()) + (size_t)f * faceBytes;
+            p.mRenderTarget = static_cast<uint8_t*>(box->Data()) + (size_t)f * faceBytes;
             p.Update(mLastTimer);
             p.Draw(mLastTimer);
         }
         p.mCommandList->Flush();
         p.mRenderTarget = nullptr;
-        CrychicThrowIfFailed(crychic_generate_cube_mips(md3dDevice->Ctx(), static_cast<uint8_t*>(chain->Data()), dim, levels, mCommandList->Stream()));
+        CrychicThrowIfFailed(crychic_generate_cube_mips(md3dDevice->Ctx(), static_cast<uint8_t*>(box->Data()), dim, levels, mCommandList->Stream()));
+        if (mGlossyReflections)
+            CrychicThrowIfFailed(crychic_prefilter_cube_chain(md3dDevice->Ctx(), static_cast<const uint8_t*>(box->Data()),
+                                                              static_cast<uint8_t*>(chain->Data()), dim, levels, mCommandList->Stream()));
         mCommandList->Flush();                  // frames in flight may still read the source, which the next capture overwrites
         mSpareCubeMap = std::move(mCubeMap);
         SetCubeMap(std::move(chain), dim, levels);
@@ -480,6 +488,12 @@ public:
     UINT CubeMapSize() const { return mCubeMapSize; }
     UINT CubeMapLevels() const { return mCubeMapLevels; }
     void SetCubeMap(std::unique_ptr<ID3D12Resource> cube, UINT dim, UINT levels = 1) { mCubeMap = std::move(cube); mCubeMapSize = dim; mCubeMapLevels = levels ? levels : 1; }
+    // Glossy reflections (extension: include/crychic_hip.h CRYCHIC_LIGHT_CUBE_GLOSS): while on, CaptureEnvironment binds the captured
+    // chain prefiltered by roughness, and Draw -- this object's and its probe's -- looks a bound chain (more than one level) up at the
+    // level of the pixel's roughness.  The caller turns it on for a chain that is prefiltered: a capture made while it is on, or one
+    // it ran crychic_prefilter_cube_chain over.
+    void SetGlossyReflections(bool on) { mGlossyReflections = on; }
+    bool GlossyReflections() const { return mGlossyReflections; }
 
     // CRYCHIC::LoadTextures (CRYCHIC.cpp:939-973): the six material textures in heap order (= gTextureMaps indices, :954-959) with the
     // mip chains their files store, and the sky cube map, from `dir` (the reference opens "Textures/...").  The DDS decoding that
@@ -926,6 +940,8 @@ private:
     float mPointViews[CRYCHIC_MAX_POINT_SHADOWS][6][16] = {}, mPointProjs[CRYCHIC_MAX_POINT_SHADOWS][16] = {};
     float mPointShadowProjs[CRYCHIC_MAX_POINT_SHADOWS][16] = {};
     UINT mCubeMapSize = 0, mCubeMapLevels = 1;
+    bool mGlossyReflections = false;                // SetGlossyReflections
+    std::unique_ptr<ID3D12Resource> mCaptureBoxChain;   // CaptureEnvironment with glossy reflections: the captured box chain, kept
     UINT mClientWidth, mClientHeight;
     float mLightRotationAngle = 0.0f;
     DirectX::XMFLOAT3 mBaseLightDirections[3] = { { 0.57735f, -0.57735f, 0.57735f }, { -0.57735f, -0.57735f, 0.57735f }, { 0.0f, -0.707f, -0.707f } };  // CRYCHIC.h:173-177

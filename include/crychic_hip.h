@@ -198,6 +198,14 @@ int crychic_ssao_compute(crychic_ctx* ctx, const crychic_ssao_constants* cb, con
  * this repo's CPU checker.  n = 0 or 1: level 0 alone, the lookup of every earlier release.  With n > 1 a call's rows must be whole
  * quad rows (even row0; even rows unless they end the frame). */
 #define CRYCHIC_LIGHT_CUBE_LEVELS(n) (((uint32_t)(n) & 15u) << 16)
+/* Glossy reflections (BUILD-DEFINED EXTENSION).  CRYCHIC_LIGHT_CUBE_GLOSS, valid only together with
+ * CRYCHIC_LIGHT_CUBE_LEVELS(n), n > 1 (otherwise CRYCHIC_E_INVALID_ARG), says that cube_dev holds a chain prefiltered by roughness
+ * (crychic_prefilter_cube_chain below): the reflection lookup of DeferredShading.hlsl:95 is then trilinear at
+ * lod = saturate(roughness) * (n - 1) -- one multiply; roughness is the decoded G-buffer value the pixel's BRDF uses, NaN -> 0 --
+ * instead of the quad's derivatives; `shininess` and the Fresnel factor of :96-97 stay as written.  The sky reads level 0 alone,
+ * as without a chain.  No quad is involved, so the rows of a call need not be whole quad rows.  Accepted by every
+ * crychic_deferred_light* entry and in crychic_frame_desc.flags; without the flag every call is what it was, bit for bit. */
+#define CRYCHIC_LIGHT_CUBE_GLOSS 0x800u
 #define CRYCHIC_FIX_Q1 0x100u
 #define CRYCHIC_FIX_Q3 0x200u
 #define CRYCHIC_FIX_Q4 0x400u
@@ -626,6 +634,40 @@ int crychic_generate_cube_mips(crychic_ctx* ctx, uint8_t* chain_dev, uint32_t di
  * destination must not alias) are the main frame's; crychic_generate_cube_mips then builds the chain.
  * CRYCHIC_E_INVALID_ARG for a NULL pointer, a non-finite position, nearZ <= 0 or nearZ >= farZ. */
 int crychic_cube_capture_cameras(const float pos[3], float nearZ, float farZ, crychic_camera cams[6]);
+
+/* ---- cube map prefiltered by roughness (BUILD-DEFINED EXTENSION) --------------------------------------- *
+ * Level k of a prefiltered chain holds the environment convolved with the GGX lobe of roughness rho = k / (levels - 1): the first
+ * term of the split sum with N = V = R (Karis 2013), with the pass's own lobe (NDF_GGX is called with a = roughness: a^2 = rho^2).
+ *
+ * Sample table.  A pure function of (dim, levels, level k), 1 <= k < levels, computed on the host in double and stored as float.
+ * For i = 0 .. 31: xi1 = (i + 0.5) / 32, xi2 = the base-2 radical inverse of i; cos^2(theta) = (1 - xi1) / (1 + (a^2 - 1) xi1),
+ * phi = 2 pi xi2; the weight is w = 2 cos^2(theta) - 1 and a sample with w <= 0 is dropped.  A kept entry is { lx, ly, lz, lod }:
+ * (lx, ly, lz) = (2 cos sin cos(phi), 2 cos sin sin(phi), w), the light direction in tangent space (lz is also the weight), and
+ * lod = clamp(0.5 log2(Os / Op) + 1, 0, levels - 1) with Os = 1 / (32 D / 4), D = a^2 / (pi ((a^2 - 1) cos^2(theta) + 1)^2) and
+ * Op = 4 pi / (6 dim^2).  *count is the number of kept entries (16 at the last level, whose weights sum to exactly 8), entries
+ * past it are zero, and *rcpWeight = (float)(1 / sum of w), summed in double over the kept entries in index order.
+ * CRYCHIC_E_INVALID_ARG for a NULL pointer, dim == 0, levels outside 2 .. 15 or level outside 1 .. levels - 1. */
+int crychic_cube_prefilter_samples(uint32_t dim, uint32_t levels, uint32_t level, float samples[32][4], uint32_t* count,
+                                   float* rcpWeight);   /* host only */
+/* Prefiltered chain.  dst has the layout of src (crychic_cube_chain_bytes(dim, levels) bytes each); the two must not overlap.
+ * Level 0 of dst is level 0 of src, byte for byte.  Texel (x, y) of face f of level k >= 1 (d = max(dim >> k, 1)):
+ *   1. N = normalize of the direction of the texel centre: face coordinates (s, t) = ((2x + 1) / d - 1, (2y + 1) / d - 1) (the
+ *      quotient is a * rcp(d)), major axis 1, the inverse of the cube sampler's face table: +X (1, -t, -s), -X (-1, -t, s),
+ *      +Y (s, 1, t), -Y (s, -1, -t), +Z (s, -t, 1), -Z (-s, -t, -1);
+ *   2. up = (0, 0, 1) if |N.z| < 0.999, else (1, 0, 0); T = normalize(up x N), B = N x T, every cross component one
+ *      fma(a, b, -(c d));
+ *   3. for the kept samples of level k's table in index order: L = lx T + ly B + lz N (per component a product and two mads, x
+ *      then y then z), c = the trilinear chain lookup of src (all its levels) at direction L and level of detail lod_i, four
+ *      channels, exactly as the lighting pass samples a chain; acc = fma(lz_i, c, acc) per channel;
+ *   4. the texel is floor(saturate(acc * rcpWeight) * 255 + 0.5) per channel (one mad).
+ * Texels are finite and the directions never degenerate (|N| = |L| = 1, lz > 0), so there is no NaN case.  src is meant to be a
+ * box chain (crychic_generate_cube_mips or a DDS chain); any chain of the layout is accepted.  Nothing is filtered across faces.
+ * One copy and levels - 1 launches on `stream`, nothing allocated: the call can be captured into a graph.  levels == 1 copies
+ * level 0.  levels is 1 .. min(15, floor(log2 dim) + 1).  CRYCHIC_E_INVALID_ARG, before anything is enqueued, for a NULL pointer,
+ * dim == 0, a chain that is not 4-byte aligned, levels out of range or overlapping chains; dim > 8192 (the lighting pass's limit
+ * for a cube map it binds: the sampler's 32-bit offsets) CRYCHIC_E_UNSUPPORTED. */
+int crychic_prefilter_cube_chain(crychic_ctx* ctx, const uint8_t* src_chain_dev, uint8_t* dst_chain_dev, uint32_t dim,
+                                 uint32_t levels, void* stream);
 
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
