@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("CRYCHIC_LIB") or os.path.join(HERE, "libcrychic_hip.s
 MAX_LIGHTS = 16
 LIGHT_SKY = 1
 LIGHT_CUBE_GLOSS = 0x800      # CRYCHIC_LIGHT_CUBE_GLOSS: the bound chain is prefiltered by roughness
+LIGHT_AMBIENT_SH = 0x8000     # CRYCHIC_LIGHT_AMBIENT_SH: the ambient colour from the SH9 coefficients behind the cube map
+CUBE_SH_BYTES = 512           # CRYCHIC_CUBE_SH_BYTES: the environment tail (144 bytes of coefficients, then the projection's scratch)
 # CRYCHIC_GBUFFER_G*_F16: that G-buffer plane holds half4 texels (the flags word of the lighting entries, FrameDesc.flags, and
 # crychic_draw_gbuffer_formats' gbufferFlags)
 GBUFFER_G0_F16, GBUFFER_G1_F16, GBUFFER_G2_F16 = 0x1000, 0x2000, 0x4000
@@ -163,6 +165,9 @@ PROTOTYPES = {
     "crychic_cube_capture_cameras": (_i, [_P(_f), _f, _f, _P(Camera)]),
     "crychic_cube_prefilter_samples": (_i, [_u32, _u32, _u32, _vp, _P(_u32), _P(_f)]),
     "crychic_prefilter_cube_chain": (_i, [_vp, _vp, _vp, _u32, _u32, _vp]),
+    "crychic_cube_sh_offset": (_sz, [_u32, _u32]),
+    "crychic_cube_chain_sh_bytes": (_sz, [_u32, _u32]),
+    "crychic_project_cube_sh": (_i, [_vp, _vp, _u32, _vp, _vp]),
     "crychic_save_ppm": (_i, [C.c_char_p, _vp, _u32, _u32]),
     "crychic_raster_workspace_bytes": (_sz, [C.c_uint64, _u32, _u32]),
     "crychic_raster_status": (_i, [_vp, _vp, _P(_u32)]),

@@ -190,6 +190,20 @@ int bind_local_lights(cry::LightParams& P, cry::SpotShadows& S, cry::PointShadow
     return 0;
 }
 
+// CRYCHIC_LIGHT_AMBIENT_SH: the lookup it goes with and the environment tail behind the cube map, before anything is enqueued.
+int check_ambient_sh(uint32_t flags, const uint8_t* cube, uint32_t cubeDim)
+{
+    switch (cry::ambient_sh_check(flags, cube, cubeDim)) {
+    case cry::AmbientShCheck::DerivativeChain:
+        return fail(CRYCHIC_E_UNSUPPORTED, "CRYCHIC_LIGHT_AMBIENT_SH with a derivative-LOD chain: use no chain, or CRYCHIC_LIGHT_CUBE_LEVELS(n) with CRYCHIC_LIGHT_CUBE_GLOSS");
+    case cry::AmbientShCheck::NullCube: return fail(CRYCHIC_E_INVALID_ARG, "CRYCHIC_LIGHT_AMBIENT_SH: null cube map");
+    case cry::AmbientShCheck::MisalignedTail:
+        return fail(CRYCHIC_E_INVALID_ARG, "CRYCHIC_LIGHT_AMBIENT_SH: the environment tail at cube_dev + %zu is not 4-byte aligned",
+                    cry::ambient_sh_offset(cubeDim, (flags >> 16) & 15u));
+    default: return 0;
+    }
+}
+
 // With a mip chain the level of detail comes from 2 x 2 pixel quads: a call's rows have to be whole quad rows.  Not so with
 // CRYCHIC_LIGHT_CUBE_GLOSS, where it comes from the pixel's roughness.
 int check_chain_rows(const cry::LightParams& P, uint32_t row0, uint32_t rows, uint32_t H)
@@ -218,6 +232,7 @@ int deferred_light_impl(crychic_ctx* ctx, const crychic_pass_constants* cb, cons
     if (int rc = bind_local_lights(P, S, PS, cb, point_lights_dev, numPointLights, spot_lights_dev, numSpotLights, spotShadows,
                                    pointShadows)) return rc;
     if (int rc = fill_light_params(P, cb, shadow_dev, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags)) return rc;
+    if (int rc = check_ambient_sh(flags, cube_dev, cubeDim)) return rc;
     if (int rc = check_chain_rows(P, row0, rows, H)) return rc;
     CRY_HIP(cry::launch_light(P, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, cube_dev, out_rgba8_dev, radiance_out_dev,
                               row0, rows, (hipStream_t)stream, spot_lights_dev, numSpotLights, &S, &PS));
@@ -414,6 +429,7 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
     cry::LightParams P;
     if (int rc = fill_light_params(P, passCB, f->shadow_dev, f->shadowDim, f->cubeDim, W, H, f->numDirLights,
                                    f->pcfSearchRadius, f->flags)) return rc;
+    if (int rc = check_ambient_sh(f->flags, f->cube_dev, f->cubeDim)) return rc;
     cry::SpotShadows S;
     cry::PointShadows PS;
     if (int rc = bind_local_lights(P, S, PS, passCB, f->point_lights_dev, f->numPointLights, spots.lights, spots.count, spots.shadows,
@@ -731,6 +747,23 @@ int crychic_prefilter_cube_chain(crychic_ctx* ctx, const uint8_t* src_chain_dev,
     const size_t bytes = crychic_cube_chain_bytes(dim, levels);
     if (s < d + bytes && d < s + bytes) return fail(CRYCHIC_E_INVALID_ARG, "the source and destination chains overlap");
     CRY_HIP(cry::launch_cube_prefilter(src_chain_dev, dst_chain_dev, dim, levels, (hipStream_t)stream));
+    return 0;
+}
+
+size_t crychic_cube_sh_offset(uint32_t dim, uint32_t levels) { return cry::ambient_sh_offset(dim, levels); }
+size_t crychic_cube_chain_sh_bytes(uint32_t dim, uint32_t levels) { return cry::ambient_sh_offset(dim, levels) + CRYCHIC_CUBE_SH_BYTES; }
+
+int crychic_project_cube_sh(crychic_ctx* ctx, const uint8_t* level_dev, uint32_t d, void* tail_dev, void* stream)
+{
+    if (int rc = bind(ctx)) return rc;
+    if (!level_dev || !tail_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (d == 0 || d > 8192u) return fail(CRYCHIC_E_INVALID_ARG, "cube map face size %u outside 1 .. 8192", d);
+    const uintptr_t s = reinterpret_cast<uintptr_t>(level_dev), t = reinterpret_cast<uintptr_t>(tail_dev);
+    if (s & 3u) return fail(CRYCHIC_E_INVALID_ARG, "cube map level is not 4-byte aligned");
+    if (t & 7u) return fail(CRYCHIC_E_INVALID_ARG, "environment tail is not 8-byte aligned");
+    const size_t bytes = (size_t)6u * d * d * 4u;
+    if (s < t + CRYCHIC_CUBE_SH_BYTES && t < s + bytes) return fail(CRYCHIC_E_INVALID_ARG, "the environment tail overlaps the level");
+    CRY_HIP(cry::launch_cube_sh(level_dev, d, tail_dev, (hipStream_t)stream));
     return 0;
 }
 

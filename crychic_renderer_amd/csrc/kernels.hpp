@@ -69,6 +69,12 @@ hipError_t launch_light_gloss(const LightParams& P, const void* g0, const void* 
                               const uint16_t* ambient, const uint8_t* cube, uint8_t* out, float* radiance, uint32_t row0, uint32_t rows,
                               hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
                               const PointShadows* pointShadows);
+// light_env.hip: the same pass with CRYCHIC_LIGHT_AMBIENT_SH in P.flags -- light_env_kernel / light_env_local_kernel, each with the
+// level-0 or the gloss lookup; the coefficient block is read at cube + ambient_sh_offset(P.cubeDim, P.cubeLevels).
+hipError_t launch_light_env(const LightParams& P, const void* g0, const void* g1, const void* g2, const uint32_t* depth,
+                            const uint16_t* ambient, const uint8_t* cube, uint8_t* out, float* radiance, uint32_t row0, uint32_t rows,
+                            hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
+                            const PointShadows* pointShadows);
 
 // cube_mips.hip: levels 1 .. levels - 1 of an RGBA8 cube map's chain from its level 0, in place (cube_mips_core.hpp); one launch per
 // six levels on `stream`.  The caller has checked dim and levels.
@@ -77,6 +83,10 @@ hipError_t launch_cube_mips(uint8_t* chain, uint32_t dim, uint32_t levels, hipSt
 // cube_prefilter.hip: level 0 of `src` copied to `dst` and levels 1 .. levels - 1 of `dst` prefiltered from the chain `src`
 // (cube_prefilter_core.hpp); one copy and one launch per level on `stream`.  The caller has checked dim, levels and the overlap.
 hipError_t launch_cube_prefilter(const uint8_t* src, uint8_t* dst, uint32_t dim, uint32_t levels, hipStream_t stream);
+
+// cube_sh.hip: the SH9 irradiance coefficients of the six d x d faces at `level` into the environment tail `tail`
+// (cube_sh_core.hpp); three launches on `stream`.  The caller has checked d, the alignments and the overlap.
+hipError_t launch_cube_sh(const uint8_t* level, uint32_t d, void* tail, hipStream_t stream);
 
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment

@@ -76,6 +76,25 @@ inline void bind_point_shadows(PointShadows& PS, const uint32_t* const* maps, co
     PS.dx = 1.0f / (float)dim;                         // IEEE division on the host: correctly rounded
 }
 
+// CRYCHIC_LIGHT_AMBIENT_SH: what a call with the flag must satisfy before it is bound (api.cpp turns the answer into its error).
+enum class AmbientShCheck { Ok, DerivativeChain, NullCube, MisalignedTail };
+// Byte offset of the environment tail behind a cube map of `levels` levels (crychic_cube_sh_offset): the chain rounded up to 16.
+inline size_t ambient_sh_offset(uint32_t cubeDim, uint32_t levels)
+{
+    size_t n = 0;
+    for (uint32_t k = 0; k < (levels ? levels : 1u); ++k) { const size_t d = cube_level_dim(cubeDim, k); n += 6u * d * d * 4u; }
+    return (n + 15u) & ~(size_t)15u;
+}
+inline AmbientShCheck ambient_sh_check(uint32_t flags, const void* cube, uint32_t cubeDim)
+{
+    if (!(flags & CRYCHIC_LIGHT_AMBIENT_SH)) return AmbientShCheck::Ok;
+    const uint32_t levels = (flags >> 16) & 15u;
+    if (levels > 1u && !(flags & CRYCHIC_LIGHT_CUBE_GLOSS)) return AmbientShCheck::DerivativeChain;
+    if (!cube) return AmbientShCheck::NullCube;
+    if ((reinterpret_cast<uintptr_t>(cube) + ambient_sh_offset(cubeDim, levels)) & 3u) return AmbientShCheck::MisalignedTail;
+    return AmbientShCheck::Ok;
+}
+
 // ---- which kernels serve a lighting call -------------------------------------------------------------------------
 // One family per set of kernel arguments; ZERO_RADIUS and MIPS (P.cubeLevels > 1) select the instantiation inside every family.
 enum class LightFamily {
@@ -90,12 +109,13 @@ enum class LightFamily {
     FormatsLocal,     // light_point_shadows_formats_kernel: a half4 plane and local lights of whatever kind; both shadow functors
                       // whatever the counts
     // CRYCHIC_LIGHT_CUBE_GLOSS maps onto these two as well: light_gloss_kernel and light_gloss_local_kernel (light_gloss.hip) compile
-    // in what they do -- planes of any format mix, FIX, both shadow functors -- with CubeGloss as the lookup.
+    // in what they do -- planes of any format mix, FIX, both shadow functors -- with CubeGloss as the lookup.  So does
+    // CRYCHIC_LIGHT_AMBIENT_SH (light_env.hip: the same shapes with AmbientSH, level 0 or CubeGloss).
 };
 inline LightFamily light_family(uint32_t flags, uint32_t numPointLights, uint32_t numSpots, uint32_t spotShadowCount,
                                 uint32_t pointShadowCount, uint32_t cubeLevels)
 {
-    if (flags & (CRYCHIC_GBUFFER_F16_MASK | CRYCHIC_LIGHT_CUBE_GLOSS)) return (numPointLights || numSpots) ? LightFamily::FormatsLocal : LightFamily::FormatsFrame;
+    if (flags & (CRYCHIC_GBUFFER_F16_MASK | CRYCHIC_LIGHT_CUBE_GLOSS | CRYCHIC_LIGHT_AMBIENT_SH)) return (numPointLights || numSpots) ? LightFamily::FormatsLocal : LightFamily::FormatsFrame;
     if (pointShadowCount) return LightFamily::PointShadows;
     if (numSpots && spotShadowCount) return LightFamily::SpotsShadowed;
     if (numSpots) return LightFamily::Spots;

@@ -1061,9 +1061,47 @@ CRY_HD f3 reflection_dir(const LightParams& P, f4a G0, f4a G2)
     return reflect3(f3{ -view.x, -view.y, -view.z }, normalW);
 }
 
-template <bool ZERO_RADIUS, class PointLights = NoPointLights, bool FIX = false, class Cube = CubeLevel0>
+// Where light_pixel takes the colour of the ambient term of :44 from: the constant AmbientLight of the pass ...
+struct AmbientConst {
+    static constexpr bool kSH = false;
+    struct Coeffs {};
+    CRY_HD Coeffs load() const { return Coeffs{}; }
+    CRY_HD f3 ambient(const LightParams& P, const Coeffs&, f3, float ambientAccess, f3 albedo) const
+    {
+        return f3{ ambientAccess * P.AmbientLight[0] * albedo.x, ambientAccess * P.AmbientLight[1] * albedo.y,
+                   ambientAccess * P.AmbientLight[2] * albedo.z };  // :44
+    }
+};
+// ... or the SH9 irradiance of the environment along the pixel's normal (CRYCHIC_LIGHT_AMBIENT_SH): c points at
+// the coefficient block that follows the cube map (nine float4).  The address is the same for every lane -- a kernel argument plus
+// a kernel argument -- so the 27 loads are scalar loads, issued where load() is called: with the pixel's gathers.  Per channel
+// e = C_0; e = fma(C_m, b_m(n), e) for m = 1 .. 8; e = max(e, 0) (NaN -> 0).  AmbientLight is not read.
+struct AmbientSH {
+    static constexpr bool kSH = true;
+    const float* __restrict__ c;
+    struct Coeffs { float v[9][3]; };
+    CRY_HD Coeffs load() const
+    {
+        Coeffs k;
+#pragma unroll
+        for (int m = 0; m < 9; ++m) { k.v[m][0] = c[4 * m]; k.v[m][1] = c[4 * m + 1]; k.v[m][2] = c[4 * m + 2]; }
+        return k;
+    }
+    CRY_HD f3 ambient(const LightParams&, const Coeffs& k, f3 n, float ambientAccess, f3 albedo) const
+    {
+        const float b[9] = { 1.0f, n.y, n.z, n.x, n.x * n.y, n.y * n.z, fma(3.0f * n.z, n.z, -1.0f), n.x * n.z, fma(n.x, n.x, -(n.y * n.y)) };
+        float e[3] = { k.v[0][0], k.v[0][1], k.v[0][2] };
+#pragma unroll
+        for (int m = 1; m < 9; ++m) { e[0] = fma(k.v[m][0], b[m], e[0]); e[1] = fma(k.v[m][1], b[m], e[1]); e[2] = fma(k.v[m][2], b[m], e[2]); }
+        return f3{ ambientAccess * maxnn(e[0], 0.0f) * albedo.x, ambientAccess * maxnn(e[1], 0.0f) * albedo.y,
+                   ambientAccess * maxnn(e[2], 0.0f) * albedo.z };
+    }
+};
+
+template <bool ZERO_RADIUS, class PointLights = NoPointLights, bool FIX = false, class Cube = CubeLevel0, class Ambient = AmbientConst>
 CRY_HD f4 light_pixel(const LightParams& P, f4a G0, f4a G1, f4a G2, const uint16_t* __restrict__ ambient,
-                      const uint32_t* __restrict__ cube, PointLights pointLights = PointLights(), Cube cubeLookup = Cube())
+                      const uint32_t* __restrict__ cube, PointLights pointLights = PointLights(), Cube cubeLookup = Cube(),
+                      Ambient ambientTerm = Ambient())
 {
     const bool fixQ1 = FIX && (P.flags & CRYCHIC_FIX_Q1), fixQ3 = FIX && (P.flags & CRYCHIC_FIX_Q3), fixQ4 = FIX && (P.flags & CRYCHIC_FIX_Q4);
     const f3 posW{ G0.x, G0.y, G0.z };                         // GBuffer.hlsl:37-41
@@ -1090,6 +1128,7 @@ CRY_HD f4 light_pixel(const LightParams& P, f4a G0, f4a G1, f4a G2, const uint16
     const AmbientPairs af = ambient_fetch_projected(P, ambient, hasAO, (const uint16_t*)cube, posW);
     const f3 r = reflect3(f3{ -view.x, -view.y, -view.z }, normalW);  // :94
     const typename Cube::Fetch cf = cubeLookup.fetch(P, cube, r);   // :95
+    const typename Ambient::Coeffs shc = ambientTerm.load();         // AmbientSH: 27 scalar loads, in flight with the gathers
 
     CascadeTexels ct;
     if (packedCascades) {
@@ -1103,8 +1142,7 @@ CRY_HD f4 light_pixel(const LightParams& P, f4a G0, f4a G1, f4a G2, const uint16
     const f4 refl = cubeLookup.resolve(P, cube, cf);
     const float f0 = 1.0f - saturate(dot3(normalW, r));         // LightingUtil.hlsl:54-57
     const float f5 = f0 * f0 * f0 * f0 * f0;
-    const f3 amb{ ambientAccess * P.AmbientLight[0] * albedo.x, ambientAccess * P.AmbientLight[1] * albedo.y,
-                  ambientAccess * P.AmbientLight[2] * albedo.z };  // :44
+    const f3 amb = ambientTerm.ambient(P, shc, normalW, ambientAccess, albedo);   // :44
 
     const float shininess = (1.0f - roughness) * 1.0f;          // :84 (normalW.a == 1)
 

@@ -1,5 +1,5 @@
 """python -m crychic_renderer_amd.demo [--size WxH] [--out frame.ppm] [--textures DIR] [--cube FILE.dds] [--gbuffer f32|mixed|f16]
-                                   [--capture-env X,Y,Z [--capture-dim N]] [--gloss]
+                                   [--capture-env X,Y,Z [--capture-dim N]] [--gloss] [--env-ambient]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
@@ -7,7 +7,11 @@ Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow 
 --capture-dim texels and their mip chain, built on the device) and the frame is rendered with that chain bound, so the boxes and the
 grid show up in the reflections.
 --gloss (with --cube or --capture-env): the chain is prefiltered by roughness on the device (Crychic.prefilter_cube_map; a --cube file
-without a chain gets its box chain first) and bound with glossy reflections, so a rough surface shows a blurred environment."""
+without a chain gets its box chain first) and bound with glossy reflections, so a rough surface shows a blurred environment.
+--env-ambient (with --cube or --capture-env): level 0 of the cube map is projected onto SH9 irradiance coefficients on the device
+(Crychic.project_irradiance / capture_environment(irradiance=True)) and the ambient term takes its colour from them along the pixel's
+normal instead of the constant AmbientLight: a floor is tinted by the sky above it and by the box beside it.  Without --gloss the cube
+map is bound as level 0 alone (the derivative-LOD chain has no such kernels)."""
 import argparse
 import ctypes as C
 
@@ -29,9 +33,13 @@ def main():
     ap.add_argument("--capture-dim", type=int, default=256, help="face size of the captured cube map (even)")
     ap.add_argument("--gloss", action="store_true", help="prefilter the cube map chain by roughness and render glossy reflections "
                                                          "(needs --cube or --capture-env)")
+    ap.add_argument("--env-ambient", action="store_true", help="ambient light from the cube map's SH9 irradiance instead of the constant "
+                                                               "(needs --cube or --capture-env)")
     a = ap.parse_args()
     if a.gloss and not (a.cube or a.capture_env):
         ap.error("--gloss needs --cube or --capture-env")
+    if a.env_ambient and not (a.cube or a.capture_env):
+        ap.error("--env-ambient needs --cube or --capture-env")
     W, H = (int(v) for v in a.size.lower().split("x"))
     import torch
     from . import Context, Crychic, LIGHT_SKY, SceneGeometry, check, geometry as g, lib, scene
@@ -53,7 +61,13 @@ def main():
                 full[:chain.numel()] = chain
                 chain = app.generate_cube_mips(full, dim, levels)
             chain = app.prefilter_cube_map(chain, dim, levels)
-        app.set_cube_map(chain, dim=dim, levels=levels, gloss=a.gloss and levels > 1)
+        if a.env_ambient:
+            if not a.gloss:
+                levels = 1        # level 0 alone
+            full = torch.empty((g.cube_chain_sh_bytes(dim, levels),), dtype=torch.uint8, device=ctx.device)
+            full[:g.cube_chain_bytes(dim, levels)] = chain[:g.cube_chain_bytes(dim, levels)]
+            chain = app.project_irradiance(full, dim, levels)
+        app.set_cube_map(chain, dim=dim, levels=levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient)
     app.mMainPassCB, app.mSsaoCB = consts.pass_cb, consts.ssao_cb
     for k in range(4):
         cb = PassConstants()
@@ -66,8 +80,9 @@ def main():
         pos = [float(v) for v in a.capture_env.split(",")]
         if len(pos) != 3:
             ap.error("--capture-env takes X,Y,Z")
-        chain, dim, levels = app.capture_environment(pos, geo, sgeo, dim=a.capture_dim, prefilter=a.gloss)
-        app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1)
+        chain, dim, levels = app.capture_environment(pos, geo, sgeo, dim=a.capture_dim, prefilter=a.gloss, irradiance=a.env_ambient,
+                                                     levels=1 if a.env_ambient and not a.gloss else None)
+        app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient)
         print("captured the environment at (%g, %g, %g): %d-texel faces, %d levels" % (pos[0], pos[1], pos[2], dim, levels))
     app.Draw()
     torch.cuda.synchronize()

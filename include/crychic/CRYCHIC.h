@@ -218,6 +218,7 @@ public:
         f.pcfSearchRadius = crychic_pcf_search_radius(mShadowMap->Width(), mPcfLiteral ? 1 : 0);
         f.flags = (mSkyEnabled ? CRYCHIC_LIGHT_SKY : 0u) | (L.mCubeMapLevels > 1 ? CRYCHIC_LIGHT_CUBE_LEVELS(L.mCubeMapLevels) : 0u);   // :278-279, :1148-1151
         if (L.mGlossyReflections && L.mCubeMapLevels > 1) f.flags |= CRYCHIC_LIGHT_CUBE_GLOSS;      // the level from the pixel's roughness
+        if (L.mCubeMapHasTail) f.flags |= CRYCHIC_LIGHT_AMBIENT_SH;                                 // the ambient colour from the environment tail
         f.flags |= mDeferred->FormatFlags();                                                        // a half4 plane: its CRYCHIC_GBUFFER_G*_F16 bit
         f.row0 = mStripRow0; f.rows = mWholeFrame ? mClientHeight : mStripRows;                      // whole frame unless SetStrip / JoinNode
         f.normal_dev = mSsao->NormalMap()->Data();
@@ -372,7 +373,9 @@ public:
     // never reflects itself, two captures in a row give one bounce -- and becomes the next capture's destination when its size fits,
     // so a per-frame re-capture allocates nothing.  An object whose planes the caller fills (mRunProducerPasses == false) has no scene
     // to capture and is refused.  With SetGlossyReflections(true) the faces and their box chain go to a scratch chain this object
-    // keeps, and the chain bound is crychic_prefilter_cube_chain's of it.
+    // keeps, and the chain bound is crychic_prefilter_cube_chain's of it.  With SetEnvironmentAmbient(true) the chain is allocated with
+    // its environment tail (crychic_cube_chain_sh_bytes) and level 0 of the box chain is projected into it (crychic_project_cube_sh);
+    // a chain of more than one level then needs SetGlossyReflections(true) (the derivative-LOD chain has no such kernels).
     void CaptureEnvironment(float x, float y, float z, UINT dim, UINT levels = 0, UINT shadowDim = 1024)
     {
         uint32_t full = 1;
@@ -384,6 +387,9 @@ public:
             levels > full || shadowDim < 2u)
             throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::CaptureEnvironment (a cube map bound as the source; the producer passes on; "
                                    "Update before it with shadowed local lights; dim even, 2 .. 8192; at most floor(log2 dim) + 1 levels)",
+                                   __FILE__, __LINE__);
+        if (mEnvironmentAmbient && levels > 1u && !mGlossyReflections)
+            throw CrychicException(CRYCHIC_E_UNSUPPORTED, "CRYCHIC::CaptureEnvironment (environment ambient with a chain needs glossy reflections)",
                                    __FILE__, __LINE__);
         if (localShadows) {                     // the probe reads this object's local-light shadow maps: as Draw would render them now
             auto items = DrawItems(mRitemLayer[(int)RenderLayer::OpaqueShadow]);
@@ -407,8 +413,9 @@ public:
         if (p.mDeferred->FormatFlags() != mDeferred->FormatFlags()) p.SetGBufferFormat(mDeferred->Format(0), mDeferred->Format(1), mDeferred->Format(2));
         p.mTextures = mTextures;                // the device copies stay this object's (mTexturePlanes)
         const size_t faceBytes = (size_t)dim * dim * 4u, chainBytes = crychic_cube_chain_bytes(dim, levels);
+        const size_t boundBytes = mEnvironmentAmbient ? crychic_cube_chain_sh_bytes(dim, levels) : chainBytes;     // with the environment tail
         std::unique_ptr<ID3D12Resource> chain = std::move(mSpareCubeMap);          // the cube map the last capture replaced
-        if (!chain || chain->Bytes() != chainBytes) chain = std::make_unique<ID3D12Resource>(chainBytes, ID3D12Resource::DEFAULT_HEAP);
+        if (!chain || chain->Bytes() != boundBytes) chain = std::make_unique<ID3D12Resource>(boundBytes, ID3D12Resource::DEFAULT_HEAP);
         if (mGlossyReflections && (!mCaptureBoxChain || mCaptureBoxChain->Bytes() != chainBytes))
             mCaptureBoxChain = std::make_unique<ID3D12Resource>(chainBytes, ID3D12Resource::DEFAULT_HEAP);
         ID3D12Resource* box = mGlossyReflections ? mCaptureBoxChain.get() : chain.get();         // where the faces are rendered
@@ -427,12 +434,16 @@ public:
         p.mCommandList->Flush();
         p.mRenderTarget = nullptr;
         CrychicThrowIfFailed(crychic_generate_cube_mips(md3dDevice->Ctx(), static_cast<uint8_t*>(box->Data()), dim, levels, mCommandList->Stream()));
+        if (mEnvironmentAmbient)                // the box chain's level 0 (the prefiltered chain's level 0 is its copy) into the bound chain's tail
+            CrychicThrowIfFailed(crychic_project_cube_sh(md3dDevice->Ctx(), static_cast<const uint8_t*>(box->Data()), dim,
+                                                         static_cast<uint8_t*>(chain->Data()) + crychic_cube_sh_offset(dim, levels),
+                                                         mCommandList->Stream()));
         if (mGlossyReflections)
             CrychicThrowIfFailed(crychic_prefilter_cube_chain(md3dDevice->Ctx(), static_cast<const uint8_t*>(box->Data()),
                                                               static_cast<uint8_t*>(chain->Data()), dim, levels, mCommandList->Stream()));
         mCommandList->Flush();                  // frames in flight may still read the source, which the next capture overwrites
         mSpareCubeMap = std::move(mCubeMap);
-        SetCubeMap(std::move(chain), dim, levels);
+        SetCubeMap(std::move(chain), dim, levels, mEnvironmentAmbient);
     }
 
     // ---- one frame on several GPUs (no counterpart in the single-GPU reference) ----------------------------------
@@ -487,7 +498,18 @@ public:
     ID3D12Resource* CubeMap() { return mCubeMap.get(); }
     UINT CubeMapSize() const { return mCubeMapSize; }
     UINT CubeMapLevels() const { return mCubeMapLevels; }
-    void SetCubeMap(std::unique_ptr<ID3D12Resource> cube, UINT dim, UINT levels = 1) { mCubeMap = std::move(cube); mCubeMapSize = dim; mCubeMapLevels = levels ? levels : 1; }
+    // hasTail: the resource holds crychic_cube_chain_sh_bytes(dim, levels) bytes, the cube map and behind it the environment tail
+    // crychic_project_cube_sh filled; Draw then announces CRYCHIC_LIGHT_AMBIENT_SH.
+    void SetCubeMap(std::unique_ptr<ID3D12Resource> cube, UINT dim, UINT levels = 1, bool hasTail = false)
+    {
+        mCubeMap = std::move(cube); mCubeMapSize = dim; mCubeMapLevels = levels ? levels : 1; mCubeMapHasTail = hasTail;
+    }
+    bool CubeMapHasTail() const { return mCubeMapHasTail; }
+    // Ambient light from the environment (extension: include/crychic_hip.h CRYCHIC_LIGHT_AMBIENT_SH): while on, CaptureEnvironment
+    // allocates the chain with its environment tail and projects the captured level 0 onto the nine SH9 irradiance coefficients;
+    // Draw -- this object's and its probe's -- takes the ambient colour from the tail of a bound cube map that has one.
+    void SetEnvironmentAmbient(bool on) { mEnvironmentAmbient = on; }
+    bool EnvironmentAmbient() const { return mEnvironmentAmbient; }
     // Glossy reflections (extension: include/crychic_hip.h CRYCHIC_LIGHT_CUBE_GLOSS): while on, CaptureEnvironment binds the captured
     // chain prefiltered by roughness, and Draw -- this object's and its probe's -- looks a bound chain (more than one level) up at the
     // level of the pixel's roughness.  The caller turns it on for a chain that is prefiltered: a capture made while it is on, or one
@@ -941,6 +963,8 @@ private:
     float mPointShadowProjs[CRYCHIC_MAX_POINT_SHADOWS][16] = {};
     UINT mCubeMapSize = 0, mCubeMapLevels = 1;
     bool mGlossyReflections = false;                // SetGlossyReflections
+    bool mEnvironmentAmbient = false;               // SetEnvironmentAmbient
+    bool mCubeMapHasTail = false;                   // SetCubeMap(..., hasTail): the environment tail follows the bound cube map
     std::unique_ptr<ID3D12Resource> mCaptureBoxChain;   // CaptureEnvironment with glossy reflections: the captured box chain, kept
     UINT mClientWidth, mClientHeight;
     float mLightRotationAngle = 0.0f;

@@ -206,6 +206,14 @@ int crychic_ssao_compute(crychic_ctx* ctx, const crychic_ssao_constants* cb, con
  * as without a chain.  No quad is involved, so the rows of a call need not be whole quad rows.  Accepted by every
  * crychic_deferred_light* entry and in crychic_frame_desc.flags; without the flag every call is what it was, bit for bit. */
 #define CRYCHIC_LIGHT_CUBE_GLOSS 0x800u
+/* Ambient light from the cube map (BUILD-DEFINED EXTENSION; "SH9 irradiance" below).  With
+ * CRYCHIC_LIGHT_AMBIENT_SH the ambient term of DeferredShading.hlsl:44 takes its colour from the nine order-2 spherical-harmonics
+ * coefficients that follow the cube map in memory -- cube_dev + crychic_cube_sh_offset(cubeDim, levels) holds the environment tail --
+ * instead of AmbientLight, which is not read.  Valid with no chain (CRYCHIC_LIGHT_CUBE_LEVELS 0 or 1) and with
+ * CRYCHIC_LIGHT_CUBE_LEVELS(n > 1) | CRYCHIC_LIGHT_CUBE_GLOSS; with the derivative-LOD chain (n > 1 without gloss)
+ * CRYCHIC_E_UNSUPPORTED.  A tail that is not 4-byte aligned is CRYCHIC_E_INVALID_ARG, before anything is enqueued.  Accepted by every
+ * crychic_deferred_light* entry and in crychic_frame_desc.flags; without the flag every call is what it was, bit for bit. */
+#define CRYCHIC_LIGHT_AMBIENT_SH 0x8000u
 #define CRYCHIC_FIX_Q1 0x100u
 #define CRYCHIC_FIX_Q3 0x200u
 #define CRYCHIC_FIX_Q4 0x400u
@@ -668,6 +676,45 @@ int crychic_cube_prefilter_samples(uint32_t dim, uint32_t levels, uint32_t level
  * for a cube map it binds: the sampler's 32-bit offsets) CRYCHIC_E_UNSUPPORTED. */
 int crychic_prefilter_cube_chain(crychic_ctx* ctx, const uint8_t* src_chain_dev, uint8_t* dst_chain_dev, uint32_t dim,
                                  uint32_t levels, void* stream);
+
+/* ---- SH9 irradiance of a cube map (BUILD-DEFINED EXTENSION) --------------------------------------------- *
+ * Monomials of a unit vector n = (x, y, z), in this order: b0 = 1, b1 = y, b2 = z, b3 = x, b4 = x y, b5 = y z,
+ * b6 = fma(3 z, z, -1), b7 = x z, b8 = fma(x, x, -(y y)).  Constants K = { 1, 2, 2, 2, 15/4, 15/4, 5/16, 15/4, 15/16 } =
+ * 4 pi c_m^2 A_l, c_m the real SH normalisation of monomial m and A = (1, 2/3, 1/4) the cosine lobe over pi; all exact in binary, so
+ * a cube map of one colour c has ambient colour exactly c.
+ *
+ * Projection of one level (six faces of d x d RGBA8 texels, the chain's face order and layout).  For texel (x, y) of face f:
+ *   dir = the direction of the texel centre (the prefilter's table above, step 1), r2 = dot(dir, dir) = fma(z, z, fma(y, y, x x)),
+ *   n = dir * (1 / sqrt(r2)) (sqrt and reciprocal correctly rounded), w = 1 / (r2 * sqrt(r2)) -- the texel-centre solid angle up
+ *   to the factor 4 / d^2, which cancels;
+ *   q_m = the integer nearest to (w * b_m(n)) * 2^20 (one multiply, an exact scaling, ties to even), qw = the same of w * 2^20.
+ * Sums, in 64-bit integers over all 6 d^2 texels: S_w = sum of qw;  S_{m,c} = sum of q_m * texel_c for c = r, g, b, texel_c the
+ * byte 0 .. 255; alpha is ignored.  Integer sums are associative: the result depends on no lane, wave, workgroup or arrival order.
+ * |S| < 2^58 at d = 8192.
+ * Coefficient block: nine float4, 144 bytes, C_m = (r, g, b, 0),
+ *   C_{m,c} = (float)((double)S_{m,c} * K_m / ((double)S_w * 255.0))
+ * -- the conversions from int64 (exact below 2^53, correctly rounded above), one multiply, one multiply in the denominator, one
+ * divide and the conversion to binary32 are all correctly rounded, on the device as on a host.
+ *
+ * Lookup (CRYCHIC_LIGHT_AMBIENT_SH): with n = the pixel's normalW, per channel e = C_0; e = fma(C_m, b_m(n), e) for m = 1 .. 8 in
+ * index order; e = max(e, 0) (NaN -> 0: a zero-length normal has no ambient light);  amb_c = ambientAccess * e * albedo_c, the
+ * product order of DeferredShading.hlsl:44.  The sky, the tone map, the reflection term, shininess and Fresnel are unchanged.
+ *
+ * Environment tail: CRYCHIC_CUBE_SH_BYTES bytes at crychic_cube_sh_offset(dim, levels) =
+ * crychic_cube_chain_bytes(dim, max(levels, 1)) rounded up to 16, so a buffer of crychic_cube_chain_sh_bytes(dim, levels) = offset +
+ * CRYCHIC_CUBE_SH_BYTES bytes holds a chain and its tail.  Bytes [0, 144) of the tail are the coefficient block; bytes [144, 368)
+ * are the projection's 28 int64 accumulators (S_{m,c} at index 3 m + c, S_w at 27), scratch with no initialisation requirement;
+ * the rest is reserved.  Both size functions are pure host arithmetic. */
+#define CRYCHIC_CUBE_SH_BYTES 512u
+size_t crychic_cube_sh_offset(uint32_t dim, uint32_t levels);
+size_t crychic_cube_chain_sh_bytes(uint32_t dim, uint32_t levels);
+/* Projects the six d x d faces at level_dev -- any level of any chain: the caller adds crychic_cube_chain_bytes(dim, k) -- into the
+ * tail at tail_dev.  Three short launches on `stream` (zero the accumulators, accumulate with one 64-bit integer atomic add per
+ * quantity and workgroup, finalise), no allocation, no host read-back, no waiting between workgroups: capturable into a graph, and
+ * projecting twice gives the same bits whatever the tail held.  1 <= d <= 8192.  CRYCHIC_E_INVALID_ARG, before anything is
+ * enqueued, for a NULL pointer, d out of range, level_dev not 4-byte or tail_dev not 8-byte aligned, or a tail that overlaps the
+ * level. */
+int crychic_project_cube_sh(crychic_ctx* ctx, const uint8_t* level_dev, uint32_t d, void* tail_dev, void* stream);
 
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
