@@ -204,6 +204,14 @@ int check_ambient_sh(uint32_t flags, const uint8_t* cube, uint32_t cubeDim)
     }
 }
 
+// CRYCHIC_LIGHT_ENV_BRDF: the lookup it goes with and the table behind the environment tail, before anything is enqueued.
+int check_env_brdf(uint32_t flags, const uint8_t* cube, uint32_t cubeDim)
+{
+    const cry::EnvBrdfCheck c = cry::env_brdf_check(flags, cube, cubeDim);
+    if (c == cry::EnvBrdfCheck::Ok) return 0;
+    return fail(CRYCHIC_E_INVALID_ARG, cry::env_brdf_check_message(c), cry::env_brdf_offset(cubeDim, (flags >> 16) & 15u));
+}
+
 // With a mip chain the level of detail comes from 2 x 2 pixel quads: a call's rows have to be whole quad rows.  Not so with
 // CRYCHIC_LIGHT_CUBE_GLOSS, where it comes from the pixel's roughness.
 int check_chain_rows(const cry::LightParams& P, uint32_t row0, uint32_t rows, uint32_t H)
@@ -233,6 +241,7 @@ int deferred_light_impl(crychic_ctx* ctx, const crychic_pass_constants* cb, cons
                                    pointShadows)) return rc;
     if (int rc = fill_light_params(P, cb, shadow_dev, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags)) return rc;
     if (int rc = check_ambient_sh(flags, cube_dev, cubeDim)) return rc;
+    if (int rc = check_env_brdf(flags, cube_dev, cubeDim)) return rc;
     if (int rc = check_chain_rows(P, row0, rows, H)) return rc;
     CRY_HIP(cry::launch_light(P, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, cube_dev, out_rgba8_dev, radiance_out_dev,
                               row0, rows, (hipStream_t)stream, spot_lights_dev, numSpotLights, &S, &PS));
@@ -430,6 +439,7 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
     if (int rc = fill_light_params(P, passCB, f->shadow_dev, f->shadowDim, f->cubeDim, W, H, f->numDirLights,
                                    f->pcfSearchRadius, f->flags)) return rc;
     if (int rc = check_ambient_sh(f->flags, f->cube_dev, f->cubeDim)) return rc;
+    if (int rc = check_env_brdf(f->flags, f->cube_dev, f->cubeDim)) return rc;
     cry::SpotShadows S;
     cry::PointShadows PS;
     if (int rc = bind_local_lights(P, S, PS, passCB, f->point_lights_dev, f->numPointLights, spots.lights, spots.count, spots.shadows,
@@ -764,6 +774,18 @@ int crychic_project_cube_sh(crychic_ctx* ctx, const uint8_t* level_dev, uint32_t
     const size_t bytes = (size_t)6u * d * d * 4u;
     if (s < t + CRYCHIC_CUBE_SH_BYTES && t < s + bytes) return fail(CRYCHIC_E_INVALID_ARG, "the environment tail overlaps the level");
     CRY_HIP(cry::launch_cube_sh(level_dev, d, tail_dev, (hipStream_t)stream));
+    return 0;
+}
+
+size_t crychic_cube_env_brdf_offset(uint32_t dim, uint32_t levels) { return cry::env_brdf_offset(dim, levels); }
+size_t crychic_cube_chain_env_bytes(uint32_t dim, uint32_t levels) { return cry::env_brdf_offset(dim, levels) + CRYCHIC_ENV_BRDF_BYTES; }
+
+int crychic_build_env_brdf(crychic_ctx* ctx, void* table_dev, void* stream)
+{
+    if (int rc = bind(ctx)) return rc;
+    if (!table_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (reinterpret_cast<uintptr_t>(table_dev) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "environment BRDF table is not 4-byte aligned");
+    CRY_HIP(cry::launch_env_brdf(table_dev, (hipStream_t)stream));
     return 0;
 }
 

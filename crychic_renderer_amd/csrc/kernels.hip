@@ -663,6 +663,8 @@ hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, 
                         uint32_t numSpots, const SpotShadows* shadows, const PointShadows* pointShadows)
 {
     if (rows == 0) return hipSuccess;
+    if (P.flags & CRYCHIC_LIGHT_ENV_BRDF)         // the reflection weighed by the environment BRDF table: its own kernels (light_spec.hip)
+        return launch_light_spec(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, rows, stream, spots, numSpots, shadows, pointShadows);
     if (P.flags & CRYCHIC_LIGHT_AMBIENT_SH)       // the ambient colour from the coefficients behind the cube map: its own kernels (light_env.hip)
         return launch_light_env(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, rows, stream, spots, numSpots, shadows, pointShadows);
     if (P.flags & CRYCHIC_LIGHT_CUBE_GLOSS)       // the level comes from the pixel's roughness: no quads, its own kernels (light_gloss.hip)

@@ -75,6 +75,13 @@ hipError_t launch_light_env(const LightParams& P, const void* g0, const void* g1
                             const uint16_t* ambient, const uint8_t* cube, uint8_t* out, float* radiance, uint32_t row0, uint32_t rows,
                             hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
                             const PointShadows* pointShadows);
+// light_spec.hip: the same pass with CRYCHIC_LIGHT_ENV_BRDF in P.flags (always with CRYCHIC_LIGHT_CUBE_GLOSS) -- light_spec_kernel /
+// light_spec_local_kernel, each with the constant or the SH ambient term; the table is read at cube + env_brdf_offset(P.cubeDim,
+// P.cubeLevels).
+hipError_t launch_light_spec(const LightParams& P, const void* g0, const void* g1, const void* g2, const uint32_t* depth,
+                             const uint16_t* ambient, const uint8_t* cube, uint8_t* out, float* radiance, uint32_t row0, uint32_t rows,
+                             hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
+                             const PointShadows* pointShadows);
 
 // cube_mips.hip: levels 1 .. levels - 1 of an RGBA8 cube map's chain from its level 0, in place (cube_mips_core.hpp); one launch per
 // six levels on `stream`.  The caller has checked dim and levels.
@@ -87,6 +94,10 @@ hipError_t launch_cube_prefilter(const uint8_t* src, uint8_t* dst, uint32_t dim,
 // cube_sh.hip: the SH9 irradiance coefficients of the six d x d faces at `level` into the environment tail `tail`
 // (cube_sh_core.hpp); three launches on `stream`.  The caller has checked d, the alignments and the overlap.
 hipError_t launch_cube_sh(const uint8_t* level, uint32_t d, void* tail, hipStream_t stream);
+
+// env_brdf.hip: the 32 x 32 environment BRDF table (env_brdf_core.hpp) into the 4096 bytes at `table`; one launch on `stream`.  The
+// caller has checked the pointer and its alignment.
+hipError_t launch_env_brdf(void* table, hipStream_t stream);
 
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment

@@ -95,6 +95,31 @@ inline AmbientShCheck ambient_sh_check(uint32_t flags, const void* cube, uint32_
     return AmbientShCheck::Ok;
 }
 
+// CRYCHIC_LIGHT_ENV_BRDF: the same for the split-sum weight of the reflection.  The table follows the environment tail.
+enum class EnvBrdfCheck { Ok, NeedsGlossChain, NullCube, MisalignedTable };
+inline size_t env_brdf_offset(uint32_t cubeDim, uint32_t levels) { return ambient_sh_offset(cubeDim, levels) + CRYCHIC_CUBE_SH_BYTES; }
+inline EnvBrdfCheck env_brdf_check(uint32_t flags, const void* cube, uint32_t cubeDim)
+{
+    if (!(flags & CRYCHIC_LIGHT_ENV_BRDF)) return EnvBrdfCheck::Ok;
+    const uint32_t levels = (flags >> 16) & 15u;
+    if (levels < 2u || !(flags & CRYCHIC_LIGHT_CUBE_GLOSS)) return EnvBrdfCheck::NeedsGlossChain;
+    if (!cube) return EnvBrdfCheck::NullCube;
+    if ((reinterpret_cast<uintptr_t>(cube) + env_brdf_offset(cubeDim, levels)) & 3u) return EnvBrdfCheck::MisalignedTable;
+    return EnvBrdfCheck::Ok;
+}
+// The message api.cpp reports a refusal with (a printf format; MisalignedTable takes the table's offset as %zu), here so that the
+// host harness states the same text.
+inline const char* env_brdf_check_message(EnvBrdfCheck c)
+{
+    switch (c) {
+    case EnvBrdfCheck::NeedsGlossChain:
+        return "CRYCHIC_LIGHT_ENV_BRDF needs a prefiltered chain: CRYCHIC_LIGHT_CUBE_LEVELS(n) with n > 1 and CRYCHIC_LIGHT_CUBE_GLOSS";
+    case EnvBrdfCheck::NullCube: return "CRYCHIC_LIGHT_ENV_BRDF: null cube map";
+    case EnvBrdfCheck::MisalignedTable: return "CRYCHIC_LIGHT_ENV_BRDF: the table at cube_dev + %zu is not 4-byte aligned";
+    default: return "";
+    }
+}
+
 // ---- which kernels serve a lighting call -------------------------------------------------------------------------
 // One family per set of kernel arguments; ZERO_RADIUS and MIPS (P.cubeLevels > 1) select the instantiation inside every family.
 enum class LightFamily {
@@ -110,12 +135,13 @@ enum class LightFamily {
                       // whatever the counts
     // CRYCHIC_LIGHT_CUBE_GLOSS maps onto these two as well: light_gloss_kernel and light_gloss_local_kernel (light_gloss.hip) compile
     // in what they do -- planes of any format mix, FIX, both shadow functors -- with CubeGloss as the lookup.  So does
-    // CRYCHIC_LIGHT_AMBIENT_SH (light_env.hip: the same shapes with AmbientSH, level 0 or CubeGloss).
+    // CRYCHIC_LIGHT_AMBIENT_SH (light_env.hip: the same shapes with AmbientSH, level 0 or CubeGloss), and so does
+    // CRYCHIC_LIGHT_ENV_BRDF (light_spec.hip: the same shapes with SpecularSplitSum, always CubeGloss, either ambient term).
 };
 inline LightFamily light_family(uint32_t flags, uint32_t numPointLights, uint32_t numSpots, uint32_t spotShadowCount,
                                 uint32_t pointShadowCount, uint32_t cubeLevels)
 {
-    if (flags & (CRYCHIC_GBUFFER_F16_MASK | CRYCHIC_LIGHT_CUBE_GLOSS | CRYCHIC_LIGHT_AMBIENT_SH)) return (numPointLights || numSpots) ? LightFamily::FormatsLocal : LightFamily::FormatsFrame;
+    if (flags & (CRYCHIC_GBUFFER_F16_MASK | CRYCHIC_LIGHT_CUBE_GLOSS | CRYCHIC_LIGHT_AMBIENT_SH | CRYCHIC_LIGHT_ENV_BRDF)) return (numPointLights || numSpots) ? LightFamily::FormatsLocal : LightFamily::FormatsFrame;
     if (pointShadowCount) return LightFamily::PointShadows;
     if (numSpots && spotShadowCount) return LightFamily::SpotsShadowed;
     if (numSpots) return LightFamily::Spots;

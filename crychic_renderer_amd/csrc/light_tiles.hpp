@@ -79,12 +79,13 @@ __device__ __forceinline__ float quad_reflection_lod(const LightParams& P, bool 
 // the pixels keep the 64 x 1 footprint of a wavefront, and the sky reads level 0.  `if constexpr`: the other instantiations hold no
 // trace of it.
 // Ambient (light_env.hip, never with MIPS): AmbientSH takes the ambient colour from the coefficient block behind the cube map.
-template <bool ZERO_RADIUS, bool FIX, bool MIPS, class PLANE, bool GLOSS = false, class Ambient = AmbientConst>
+// Specular (light_spec.hip, always with GLOSS): SpecularSplitSum weighs the reflection by the table behind the environment tail.
+template <bool ZERO_RADIUS, bool FIX, bool MIPS, class PLANE, bool GLOSS = false, class Ambient = AmbientConst, class Specular = SpecularRef>
 __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLANE* __restrict__ g0, const PLANE* __restrict__ g1,
                                                  const PLANE* __restrict__ g2, const uint32_t* __restrict__ depth,
                                                  const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
                                                  uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0, uint32_t row1,
-                                                 Ambient ambientTerm = Ambient())
+                                                 Ambient ambientTerm = Ambient(), Specular specTerm = Specular())
 {
     const uint32_t h0 = P.flags & CRYCHIC_GBUFFER_G0_F16, h1 = P.flags & CRYCHIC_GBUFFER_G1_F16, h2 = P.flags & CRYCHIC_GBUFFER_G2_F16;
     uint32_t bx, by;
@@ -115,6 +116,11 @@ __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLA
     // coverage: the reference re-rasterises the opaque items with LESS against depth cleared to 1.0
     // (CRYCHIC.cpp:248,273) -- exactly the pixels whose normal/depth pass depth is below the clear value.
     if ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu) {
+        if constexpr (Specular::kSplitSum) {
+            static_assert(GLOSS, "the split-sum weight goes with the gloss lookup");
+            const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
+            lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX, CubeGloss, Ambient, Specular>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, NoPointLights(), cube_gloss(P, G1.w), ambientTerm, specTerm);
+        } else
         if constexpr (Ambient::kSH) {
             const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
             if constexpr (GLOSS) lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX, CubeGloss, Ambient>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, NoPointLights(), cube_gloss(P, G1.w), ambientTerm);
@@ -149,14 +155,15 @@ __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLA
 // way.  The mask word is read once per wavefront (readfirstlane: every lane reads the same LDS word), so the walk's light index is
 // scalar, and with it the light's projection and map; the face is per lane (point_face's selects).
 template <bool ZERO_RADIUS, bool MIPS, bool SPOTS, bool SHADOWED = false, bool POINT_SHADOWED = false, class PLANE = f4a, bool GLOSS = false,
-          class Ambient = AmbientConst>
+          class Ambient = AmbientConst, class Specular = SpecularRef>
 __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLANE* __restrict__ g0, const PLANE* __restrict__ g1,
                                                  const PLANE* __restrict__ g2, const uint32_t* __restrict__ depth,
                                                  const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
                                                  uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0, uint32_t row1,
                                                  float (*s_box)[6], uint32_t* s_mask, const crychic_light* __restrict__ spots,
                                                  uint32_t numSpots, uint32_t* s_spotMask, const SpotShadows* shadows = nullptr,
-                                                 const PointShadows* pointShadows = nullptr, Ambient ambientTerm = Ambient())
+                                                 const PointShadows* pointShadows = nullptr, Ambient ambientTerm = Ambient(),
+                                                 Specular specTerm = Specular())
 {
     uint32_t bx, by;
     tile_origin<0>(bx, by);
@@ -260,6 +267,11 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLA
                 }
             }
         };
+        if constexpr (Specular::kSplitSum) {
+            static_assert(GLOSS, "the split-sum weight goes with the gloss lookup");
+            const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
+            lit = light_pixel<ZERO_RADIUS, decltype(culled), true, CubeGloss, Ambient, Specular>(P, G0, G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, culled, cube_gloss(P, G1.w), ambientTerm, specTerm);
+        } else
         if constexpr (Ambient::kSH) {
             const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
             if constexpr (GLOSS) lit = light_pixel<ZERO_RADIUS, decltype(culled), true, CubeGloss, Ambient>(P, G0, G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, culled, cube_gloss(P, G1.w), ambientTerm);

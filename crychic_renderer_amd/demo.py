@@ -1,5 +1,5 @@
 """python -m crychic_renderer_amd.demo [--size WxH] [--out frame.ppm] [--textures DIR] [--cube FILE.dds] [--gbuffer f32|mixed|f16]
-                                   [--capture-env X,Y,Z [--capture-dim N]] [--gloss] [--env-ambient]
+                                   [--capture-env X,Y,Z [--capture-dim N]] [--gloss] [--env-ambient] [--env-specular]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
@@ -11,7 +11,11 @@ without a chain gets its box chain first) and bound with glossy reflections, so 
 --env-ambient (with --cube or --capture-env): level 0 of the cube map is projected onto SH9 irradiance coefficients on the device
 (Crychic.project_irradiance / capture_environment(irradiance=True)) and the ambient term takes its colour from them along the pixel's
 normal instead of the constant AmbientLight: a floor is tinted by the sky above it and by the box beside it.  Without --gloss the cube
-map is bound as level 0 alone (the derivative-LOD chain has no such kernels)."""
+map is bound as level 0 alone (the derivative-LOD chain has no such kernels).
+--env-specular (with --gloss): the environment BRDF table is built on the device behind the chain (Crychic.build_env_brdf /
+capture_environment(env_brdf=True)) and the glossy reflection is weighed by the split sum's second factor instead of
+(1 - roughness) times the mirror direction's Fresnel term: a rough metal keeps its brightness head-on, a rough dielectric its grazing
+sheen."""
 import argparse
 import ctypes as C
 
@@ -35,7 +39,10 @@ def main():
                                                          "(needs --cube or --capture-env)")
     ap.add_argument("--env-ambient", action="store_true", help="ambient light from the cube map's SH9 irradiance instead of the constant "
                                                                "(needs --cube or --capture-env)")
+    ap.add_argument("--env-specular", action="store_true", help="weigh the glossy reflection by the environment BRDF table (needs --gloss)")
     a = ap.parse_args()
+    if a.env_specular and not a.gloss:
+        ap.error("--env-specular needs --gloss")
     if a.gloss and not (a.cube or a.capture_env):
         ap.error("--gloss needs --cube or --capture-env")
     if a.env_ambient and not (a.cube or a.capture_env):
@@ -61,13 +68,18 @@ def main():
                 full[:chain.numel()] = chain
                 chain = app.generate_cube_mips(full, dim, levels)
             chain = app.prefilter_cube_map(chain, dim, levels)
-        if a.env_ambient:
+        if a.env_ambient or a.env_specular:
             if not a.gloss:
                 levels = 1        # level 0 alone
-            full = torch.empty((g.cube_chain_sh_bytes(dim, levels),), dtype=torch.uint8, device=ctx.device)
+            full = torch.empty(((g.cube_chain_env_bytes if a.env_specular else g.cube_chain_sh_bytes)(dim, levels),), dtype=torch.uint8,
+                               device=ctx.device)
             full[:g.cube_chain_bytes(dim, levels)] = chain[:g.cube_chain_bytes(dim, levels)]
-            chain = app.project_irradiance(full, dim, levels)
-        app.set_cube_map(chain, dim=dim, levels=levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient)
+            chain = full
+            if a.env_ambient:
+                app.project_irradiance(chain, dim, levels)
+            if a.env_specular:
+                app.build_env_brdf(chain, dim, levels)
+        app.set_cube_map(chain, dim=dim, levels=levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient, env_brdf=a.env_specular)
     app.mMainPassCB, app.mSsaoCB = consts.pass_cb, consts.ssao_cb
     for k in range(4):
         cb = PassConstants()
@@ -81,8 +93,8 @@ def main():
         if len(pos) != 3:
             ap.error("--capture-env takes X,Y,Z")
         chain, dim, levels = app.capture_environment(pos, geo, sgeo, dim=a.capture_dim, prefilter=a.gloss, irradiance=a.env_ambient,
-                                                     levels=1 if a.env_ambient and not a.gloss else None)
-        app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient)
+                                                     levels=1 if a.env_ambient and not a.gloss else None, env_brdf=a.env_specular)
+        app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient, env_brdf=a.env_specular)
         print("captured the environment at (%g, %g, %g): %d-texel faces, %d levels" % (pos[0], pos[1], pos[2], dim, levels))
     app.Draw()
     torch.cuda.synchronize()

@@ -191,6 +191,18 @@ def cube_chain_sh_bytes(dim, levels):
     return int(lib.crychic_cube_chain_sh_bytes(int(dim), int(levels)))
 
 
+def cube_env_brdf_offset(dim, levels):
+    """Byte offset of the environment BRDF table behind a cube map of `levels` levels (crychic_cube_env_brdf_offset): the
+    environment tail's offset plus its 512 bytes."""
+    return int(lib.crychic_cube_env_brdf_offset(int(dim), int(levels)))
+
+
+def cube_chain_env_bytes(dim, levels):
+    """Bytes of a cube map of `levels` levels with its environment tail and the environment BRDF table
+    (crychic_cube_chain_env_bytes)."""
+    return int(lib.crychic_cube_chain_env_bytes(int(dim), int(levels)))
+
+
 def cube_capture_cameras(pos, z_near=0.5, z_far=100.0):
     """The six face cameras (+X, -X, +Y, -Y, +Z, -Z) of an environment capture at `pos` (crychic_cube_capture_cameras): a ctypes
     array of Camera with fovY = pi / 2 and aspect 1."""

@@ -219,6 +219,7 @@ public:
         f.flags = (mSkyEnabled ? CRYCHIC_LIGHT_SKY : 0u) | (L.mCubeMapLevels > 1 ? CRYCHIC_LIGHT_CUBE_LEVELS(L.mCubeMapLevels) : 0u);   // :278-279, :1148-1151
         if (L.mGlossyReflections && L.mCubeMapLevels > 1) f.flags |= CRYCHIC_LIGHT_CUBE_GLOSS;      // the level from the pixel's roughness
         if (L.mCubeMapHasTail) f.flags |= CRYCHIC_LIGHT_AMBIENT_SH;                                 // the ambient colour from the environment tail
+        if (L.mCubeMapHasTable && (f.flags & CRYCHIC_LIGHT_CUBE_GLOSS)) f.flags |= CRYCHIC_LIGHT_ENV_BRDF;   // the reflection weighed by the table behind it
         f.flags |= mDeferred->FormatFlags();                                                        // a half4 plane: its CRYCHIC_GBUFFER_G*_F16 bit
         f.row0 = mStripRow0; f.rows = mWholeFrame ? mClientHeight : mStripRows;                      // whole frame unless SetStrip / JoinNode
         f.normal_dev = mSsao->NormalMap()->Data();
@@ -375,7 +376,10 @@ public:
     // to capture and is refused.  With SetGlossyReflections(true) the faces and their box chain go to a scratch chain this object
     // keeps, and the chain bound is crychic_prefilter_cube_chain's of it.  With SetEnvironmentAmbient(true) the chain is allocated with
     // its environment tail (crychic_cube_chain_sh_bytes) and level 0 of the box chain is projected into it (crychic_project_cube_sh);
-    // a chain of more than one level then needs SetGlossyReflections(true) (the derivative-LOD chain has no such kernels).
+    // a chain of more than one level then needs SetGlossyReflections(true) (the derivative-LOD chain has no such kernels).  With
+    // SetEnvironmentSpecular(true) -- which needs SetGlossyReflections(true) and more than one level -- the chain is allocated with the
+    // environment tail and the environment BRDF table (crychic_cube_chain_env_bytes) and the table is built behind the tail
+    // (crychic_build_env_brdf).
     void CaptureEnvironment(float x, float y, float z, UINT dim, UINT levels = 0, UINT shadowDim = 1024)
     {
         uint32_t full = 1;
@@ -390,6 +394,9 @@ public:
                                    __FILE__, __LINE__);
         if (mEnvironmentAmbient && levels > 1u && !mGlossyReflections)
             throw CrychicException(CRYCHIC_E_UNSUPPORTED, "CRYCHIC::CaptureEnvironment (environment ambient with a chain needs glossy reflections)",
+                                   __FILE__, __LINE__);
+        if (mEnvironmentSpecular && (levels < 2u || !mGlossyReflections))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::CaptureEnvironment (environment specular needs glossy reflections and a chain)",
                                    __FILE__, __LINE__);
         if (localShadows) {                     // the probe reads this object's local-light shadow maps: as Draw would render them now
             auto items = DrawItems(mRitemLayer[(int)RenderLayer::OpaqueShadow]);
@@ -413,7 +420,8 @@ public:
         if (p.mDeferred->FormatFlags() != mDeferred->FormatFlags()) p.SetGBufferFormat(mDeferred->Format(0), mDeferred->Format(1), mDeferred->Format(2));
         p.mTextures = mTextures;                // the device copies stay this object's (mTexturePlanes)
         const size_t faceBytes = (size_t)dim * dim * 4u, chainBytes = crychic_cube_chain_bytes(dim, levels);
-        const size_t boundBytes = mEnvironmentAmbient ? crychic_cube_chain_sh_bytes(dim, levels) : chainBytes;     // with the environment tail
+        const size_t boundBytes = mEnvironmentSpecular ? crychic_cube_chain_env_bytes(dim, levels)                  // with the tail and the table
+                                : mEnvironmentAmbient ? crychic_cube_chain_sh_bytes(dim, levels) : chainBytes;     // with the environment tail
         std::unique_ptr<ID3D12Resource> chain = std::move(mSpareCubeMap);          // the cube map the last capture replaced
         if (!chain || chain->Bytes() != boundBytes) chain = std::make_unique<ID3D12Resource>(boundBytes, ID3D12Resource::DEFAULT_HEAP);
         if (mGlossyReflections && (!mCaptureBoxChain || mCaptureBoxChain->Bytes() != chainBytes))
@@ -438,12 +446,15 @@ public:
             CrychicThrowIfFailed(crychic_project_cube_sh(md3dDevice->Ctx(), static_cast<const uint8_t*>(box->Data()), dim,
                                                          static_cast<uint8_t*>(chain->Data()) + crychic_cube_sh_offset(dim, levels),
                                                          mCommandList->Stream()));
+        if (mEnvironmentSpecular)               // the table depends on nothing but its definition: built where the bound chain keeps it
+            CrychicThrowIfFailed(crychic_build_env_brdf(md3dDevice->Ctx(), static_cast<uint8_t*>(chain->Data()) + crychic_cube_env_brdf_offset(dim, levels),
+                                                        mCommandList->Stream()));
         if (mGlossyReflections)
             CrychicThrowIfFailed(crychic_prefilter_cube_chain(md3dDevice->Ctx(), static_cast<const uint8_t*>(box->Data()),
                                                               static_cast<uint8_t*>(chain->Data()), dim, levels, mCommandList->Stream()));
         mCommandList->Flush();                  // frames in flight may still read the source, which the next capture overwrites
         mSpareCubeMap = std::move(mCubeMap);
-        SetCubeMap(std::move(chain), dim, levels, mEnvironmentAmbient);
+        SetCubeMap(std::move(chain), dim, levels, mEnvironmentAmbient, mEnvironmentSpecular);
     }
 
     // ---- one frame on several GPUs (no counterpart in the single-GPU reference) ----------------------------------
@@ -500,11 +511,21 @@ public:
     UINT CubeMapLevels() const { return mCubeMapLevels; }
     // hasTail: the resource holds crychic_cube_chain_sh_bytes(dim, levels) bytes, the cube map and behind it the environment tail
     // crychic_project_cube_sh filled; Draw then announces CRYCHIC_LIGHT_AMBIENT_SH.
-    void SetCubeMap(std::unique_ptr<ID3D12Resource> cube, UINT dim, UINT levels = 1, bool hasTail = false)
+    // hasTable: the resource holds crychic_cube_chain_env_bytes(dim, levels) bytes, and behind the environment tail (filled or not) the
+    // table crychic_build_env_brdf made; Draw then announces CRYCHIC_LIGHT_ENV_BRDF whenever it announces CRYCHIC_LIGHT_CUBE_GLOSS.
+    void SetCubeMap(std::unique_ptr<ID3D12Resource> cube, UINT dim, UINT levels = 1, bool hasTail = false, bool hasTable = false)
     {
         mCubeMap = std::move(cube); mCubeMapSize = dim; mCubeMapLevels = levels ? levels : 1; mCubeMapHasTail = hasTail;
+        mCubeMapHasTable = hasTable;
     }
     bool CubeMapHasTail() const { return mCubeMapHasTail; }
+    bool CubeMapHasTable() const { return mCubeMapHasTable; }
+    // Split-sum specular from the environment (extension: include/crychic_hip.h CRYCHIC_LIGHT_ENV_BRDF): while on, CaptureEnvironment
+    // (with glossy reflections on) allocates the chain with the environment BRDF table behind its environment tail and builds it;
+    // Draw -- this object's and its probe's -- weighs the glossy reflection of a bound chain that has a table by the split sum's
+    // second factor instead of shininess and the mirror direction's Fresnel term.
+    void SetEnvironmentSpecular(bool on) { mEnvironmentSpecular = on; }
+    bool EnvironmentSpecular() const { return mEnvironmentSpecular; }
     // Ambient light from the environment (extension: include/crychic_hip.h CRYCHIC_LIGHT_AMBIENT_SH): while on, CaptureEnvironment
     // allocates the chain with its environment tail and projects the captured level 0 onto the nine SH9 irradiance coefficients;
     // Draw -- this object's and its probe's -- takes the ambient colour from the tail of a bound cube map that has one.
@@ -965,6 +986,8 @@ private:
     bool mGlossyReflections = false;                // SetGlossyReflections
     bool mEnvironmentAmbient = false;               // SetEnvironmentAmbient
     bool mCubeMapHasTail = false;                   // SetCubeMap(..., hasTail): the environment tail follows the bound cube map
+    bool mEnvironmentSpecular = false;              // SetEnvironmentSpecular
+    bool mCubeMapHasTable = false;                  // SetCubeMap(..., hasTable): the environment BRDF table follows the environment tail
     std::unique_ptr<ID3D12Resource> mCaptureBoxChain;   // CaptureEnvironment with glossy reflections: the captured box chain, kept
     UINT mClientWidth, mClientHeight;
     float mLightRotationAngle = 0.0f;

@@ -214,6 +214,15 @@ int crychic_ssao_compute(crychic_ctx* ctx, const crychic_ssao_constants* cb, con
  * CRYCHIC_E_UNSUPPORTED.  A tail that is not 4-byte aligned is CRYCHIC_E_INVALID_ARG, before anything is enqueued.  Accepted by every
  * crychic_deferred_light* entry and in crychic_frame_desc.flags; without the flag every call is what it was, bit for bit. */
 #define CRYCHIC_LIGHT_AMBIENT_SH 0x8000u
+/* Split-sum specular from the environment (BUILD-DEFINED EXTENSION; "environment BRDF table" below).  With
+ * CRYCHIC_LIGHT_ENV_BRDF the reflection term of DeferredShading.hlsl:97 is weighed by the second factor of the split sum, filtered from
+ * the 32 x 32 table that follows the environment tail in memory -- cube_dev + crychic_cube_env_brdf_offset(cubeDim, levels) holds the
+ * table -- instead of shininess * SchlickFresnel(R0, normalW, r), which are not evaluated.  Valid only together with
+ * CRYCHIC_LIGHT_CUBE_LEVELS(n > 1) | CRYCHIC_LIGHT_CUBE_GLOSS, with and without CRYCHIC_LIGHT_AMBIENT_SH (the 512-byte tail before the
+ * table is read only under that flag); anything else, a NULL cube map or a table address that is not 4-byte aligned is
+ * CRYCHIC_E_INVALID_ARG with a message, before anything is enqueued.  Accepted by every crychic_deferred_light* entry (strips and the
+ * _shared entries included) and in crychic_frame_desc.flags; without the flag every call is what it was, bit for bit. */
+#define CRYCHIC_LIGHT_ENV_BRDF 0x100000u
 #define CRYCHIC_FIX_Q1 0x100u
 #define CRYCHIC_FIX_Q3 0x200u
 #define CRYCHIC_FIX_Q4 0x400u
@@ -715,6 +724,47 @@ size_t crychic_cube_chain_sh_bytes(uint32_t dim, uint32_t levels);
  * enqueued, for a NULL pointer, d out of range, level_dev not 4-byte or tail_dev not 8-byte aligned, or a tail that overlaps the
  * level. */
 int crychic_project_cube_sh(crychic_ctx* ctx, const uint8_t* level_dev, uint32_t d, void* tail_dev, void* stream);
+
+/* ---- environment BRDF table (BUILD-DEFINED EXTENSION) ----------------------------------------------------- *
+ * Level k of a prefiltered chain is the first factor of Karis' split sum; this table is the second: the integral of the pass's own
+ * specular BRDF over the pass's own lobe, as a factor A of R0 and an offset B.  CRYCHIC_ENV_BRDF_BYTES = 4096 bytes: 32 x 32 dwords,
+ * row-major; row j is roughness rho = (j + 0.5) / 32, column i is mu = N.V = (i + 0.5) / 32; each dword holds A | (B << 16), two R16
+ * UNORM values.  It depends on nothing but this definition.  Lobe and masking are the pass's: NDF_GGX with a^2 = rho^2
+ * (PBR.hlsl:4-14) and GeometrySmith with k = 0.125 (rho + 1) (rho + 1), that product order (PBR.hlsl:34).
+ *
+ * Quadrature: a product grid of 256 x 16 = 4096 samples per texel, xi_s = (s + 0.5) / 256 and phi_t = pi (t + 0.5) / 16 over the half
+ * circle (V lies in the xz-plane, so only cos(phi) enters).  The sixteen cosines are these binary32 constants, no libm involved:
+ * t = 0 .. 7: 0x3f7ec46d 0x3f74fa0b 0x3f61c598 0x3f45e403 0x3f226799 0x3ef15aea 0x3e94a031 0x3dc8bd36; t = 8 .. 15: the negations of
+ * t = 7 .. 0.  Arithmetic is binary32 with fma, rcp (correctly rounded, flush-to-zero reciprocal) and len_from_sq (correctly rounded
+ * square root of the argument clamped to [2^-100, 2^100]); nothing is fused unless written as fma.
+ *   per texel:  a2m1 = fma(rho, rho, -1); omk = 1 - k; vz = mu; vx = len_from_sq(fma(-mu, mu, 1)); gV = rcp(fma(vz, omk, k));
+ *   per s:      c2 = (1 - xi) * rcp(fma(a2m1, xi, 1)); c = len_from_sq(c2); sn = len_from_sq(1 - c2); rc = rcp(c);
+ *   per (s, t): voh = fma(vx, sn * cos_t, vz * c); lz = fma(2 * voh, c, -vz); a sample with !(lz > 0) contributes nothing; otherwise
+ *               gL = lz * rcp(fma(lz, omk, k)); gv = ((gV * gL) * voh) * rc; f = 1 - saturate(voh); fc = f f f f f, left to right;
+ *               tB = fc * gv; tA = (1 - fc) * gv; qA, qB = the integers nearest to tA * 2^24 and tB * 2^24 (exact scaling, ties to
+ *               even).
+ * S_A = sum of qA and S_B = sum of qB are 64-bit integers; integer sums are associative, so no reduction order is part of the
+ * definition.  A = float_to_unorm16((float)((double)S_A * 2^-36)), B alike: floor(saturate(x) * 65535 + 0.5) as one mad; both
+ * conversions are exact or correctly rounded.  Every term is below 19.5, so q < 2^29 and |S| < 2^42; A lies in [0.0102, 0.9955], B in
+ * [3.9e-8, 0.1441], and A + B <= 0.99548.  The quadrature's own error against a 2048 x 256 grid is at most 0.0024 in A (mean 0.0002;
+ * worst at grazing angles near rho = 0.1) and 0.0002 in B, about half an RGBA8 step.
+ *
+ * Lookup (CRYCHIC_LIGHT_ENV_BRDF), per covered pixel: u = saturate(dot3(normalW, view)); v = saturate(roughness), the decoded value
+ * the gloss lookup uses (NaN -> 0); (A, B) = the bilinear filter of the table at (u, v): t = fma(uv, 32, -0.5), floor and fraction,
+ * indices clamped to [0, 31], each texel's halves decoded as R16 UNORM, lerp as one mad, x then y; spec_c = fma(R0_c, A, B);
+ * lit_c = fma(spec_c, refl_c, tm_c) in place of DeferredShading.hlsl:97.  The sky, the tone map, the ambient term and the direct
+ * lights are unchanged.
+ *
+ * The table travels with the cube map, behind the environment tail: crychic_cube_env_brdf_offset(dim, levels) =
+ * crychic_cube_sh_offset(dim, levels) + CRYCHIC_CUBE_SH_BYTES, and a buffer of crychic_cube_chain_env_bytes(dim, levels) = that +
+ * CRYCHIC_ENV_BRDF_BYTES bytes holds a chain, its tail and the table.  Both size functions are pure host arithmetic. */
+#define CRYCHIC_ENV_BRDF_BYTES 4096u
+size_t crychic_cube_env_brdf_offset(uint32_t dim, uint32_t levels);
+size_t crychic_cube_chain_env_bytes(uint32_t dim, uint32_t levels);
+/* Builds the table into the 4096 bytes at table_dev.  One launch on `stream`, no allocation, no context-owned buffer, no host
+ * read-back: capturable into a graph, and building twice gives the same bits whatever the destination held.
+ * CRYCHIC_E_INVALID_ARG, before anything is enqueued, for a NULL pointer or one that is not 4-byte aligned. */
+int crychic_build_env_brdf(crychic_ctx* ctx, void* table_dev, void* stream);
 
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
