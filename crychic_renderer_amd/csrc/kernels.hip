@@ -443,7 +443,7 @@ __global__ __launch_bounds__(256) void light_kernel(LightParams P, const f4a* __
                                                     const uint32_t* __restrict__ cube, uint32_t* __restrict__ out,
                                                     f4a* __restrict__ radiance, uint32_t row0, uint32_t row1)
 {
-    light_frame_tile<ZERO_RADIUS, FIX, MIPS>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1);
+    light_frame_tile<ZERO_RADIUS, FIX, CubeOfMips<MIPS>>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1);
 }
 
 template <bool ZERO_RADIUS, bool MIPS = false>
@@ -455,7 +455,7 @@ __global__ __launch_bounds__(256) void light_points_kernel(LightParams P, const 
 {
     __shared__ float s_box[4][6];
     __shared__ uint32_t s_mask[kMaxPointLights / 32];
-    light_local_tile<ZERO_RADIUS, MIPS, false>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask, nullptr, 0u, nullptr);
+    light_local_tile<ZERO_RADIUS, CubeOfMips<MIPS>, false>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask, nullptr, 0u, nullptr);
 }
 
 // The same pass with `numSpots` (1 .. 1024) spot lights after the point lights (crychic_deferred_light_spots); zero spot lights
@@ -470,7 +470,7 @@ __global__ __launch_bounds__(256) void light_spots_kernel(LightParams P, const f
     __shared__ float s_box[4][6];
     __shared__ uint32_t s_mask[kMaxPointLights / 32];
     __shared__ uint32_t s_spotMask[kMaxSpotLights / 32];
-    light_local_tile<ZERO_RADIUS, MIPS, true>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask, spots, numSpots, s_spotMask);
+    light_local_tile<ZERO_RADIUS, CubeOfMips<MIPS>, true>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask, spots, numSpots, s_spotMask);
 }
 
 // The same pass with the first shadows.count (1 .. 8) spot lights shadowed (crychic_deferred_light_spots_shadowed); a count of 0
@@ -486,8 +486,8 @@ __global__ __launch_bounds__(256) void light_spots_shadowed_kernel(LightParams P
     __shared__ float s_box[4][6];
     __shared__ uint32_t s_mask[kMaxPointLights / 32];
     __shared__ uint32_t s_spotMask[kMaxSpotLights / 32];
-    light_local_tile<ZERO_RADIUS, MIPS, true, true>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask, spots,
-                                                    numSpots, s_spotMask, &shadows);
+    light_local_tile<ZERO_RADIUS, CubeOfMips<MIPS>, true, true>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask,
+                                                                spots, numSpots, s_spotMask, &shadows);
 }
 
 // The same pass with the first pointShadows.count (1 .. 4) point lights shadowed (crychic_deferred_light_point_shadows), spot lights
@@ -504,8 +504,8 @@ __global__ __launch_bounds__(256) void light_point_shadows_kernel(LightParams P,
     __shared__ float s_box[4][6];
     __shared__ uint32_t s_mask[kMaxPointLights / 32];
     __shared__ uint32_t s_spotMask[kMaxSpotLights / 32];
-    light_local_tile<ZERO_RADIUS, MIPS, true, true, true>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box, s_mask,
-                                                          spots, numSpots, s_spotMask, &shadows, &pointShadows);
+    light_local_tile<ZERO_RADIUS, CubeOfMips<MIPS>, true, true, true>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1, s_box,
+                                                                      s_mask, spots, numSpots, s_spotMask, &shadows, &pointShadows);
 }
 // Its kernel arguments, the largest of any kernel here: the usual HIP limit is 4 KiB.
 static_assert(sizeof(LightParams) + sizeof(SpotShadows) + sizeof(PointShadows) + 9 * sizeof(void*) + 3 * sizeof(uint32_t) <= 4096,
@@ -663,14 +663,9 @@ hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, 
                         uint32_t numSpots, const SpotShadows* shadows, const PointShadows* pointShadows)
 {
     if (rows == 0) return hipSuccess;
-    if (P.flags & CRYCHIC_LIGHT_ENV_BRDF)         // the reflection weighed by the environment BRDF table: its own kernels (light_spec.hip)
-        return launch_light_spec(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, rows, stream, spots, numSpots, shadows, pointShadows);
-    if (P.flags & CRYCHIC_LIGHT_AMBIENT_SH)       // the ambient colour from the coefficients behind the cube map: its own kernels (light_env.hip)
-        return launch_light_env(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, rows, stream, spots, numSpots, shadows, pointShadows);
-    if (P.flags & CRYCHIC_LIGHT_CUBE_GLOSS)       // the level comes from the pixel's roughness: no quads, its own kernels (light_gloss.hip)
-        return launch_light_gloss(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, rows, stream, spots, numSpots, shadows, pointShadows);
     const dim3 grid = grid_for(P.W, rows);
-    const bool mips = P.cubeLevels > 1u;          // the chain: quads inside wavefronts (light_tile_pixel), so the rows must start a quad
+    // the derivative chain: quads inside wavefronts (light_tile_pixel), so the rows must start a quad
+    const bool mips = light_variant(P.flags, P.cubeLevels).lookup == CubeLookup::DerivativeChain;
     if (mips && (row0 & 1u)) return hipErrorInvalidValue;
     // every family shares the kernel arguments up to row1; launch(kernel, extra...) appends the family's own
     auto launch = [&](auto kernel, auto... extra) {
@@ -689,8 +684,8 @@ hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, 
                                             pointShadows ? pointShadows->count : 0u, P.cubeLevels);
     switch (family) {
     case LightFamily::FormatsFrame:
-    case LightFamily::FormatsLocal:               // a half4 plane: the format-aware kernels (light_formats.hip), which serve every light set
-        return launch_light_formats(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, rows, stream, spots, numSpots, shadows, pointShadows);
+    case LightFamily::FormatsLocal:               // a half4 plane or a flagged lookup, ambient or specular term (light_general.hip)
+        return launch_light_general(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, rows, stream, spots, numSpots, shadows, pointShadows);
     case LightFamily::PointShadows:
         return dispatch([&](auto z, auto m) { launch(light_point_shadows_kernel<z, m>, spots, numSpots, shadows ? *shadows : SpotShadows{},
                                                      *pointShadows); });

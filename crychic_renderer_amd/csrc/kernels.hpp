@@ -10,7 +10,7 @@ struct LightParams;
 struct SpotShadows;
 struct PointShadows;
 
-// Launch grid of the full-screen passes: a workgroup per 64 pixels x rows_per_block rows (shared by kernels.hip and light_formats.hip).
+// Launch grid of the full-screen passes: a workgroup per 64 pixels x rows_per_block rows (shared by kernels.hip and light_general.hip).
 inline dim3 grid_for(uint32_t width, uint32_t rows, uint32_t rows_per_block = 4u)
 {
     return dim3((width + 63u) / 64u, (rows + rows_per_block - 1u) / rows_per_block, 1);
@@ -52,36 +52,19 @@ hipError_t launch_blur_replay_chain(const crychic_ssao_constants& cb, const void
 // shadows: the first shadows->count spot lights shadowed (light_spots_shadowed_kernel); nullptr or count 0 = none.
 // pointShadows: the first pointShadows->count point lights shadowed (light_point_shadows_kernel, which takes the spot lights and
 // their shadows as well); nullptr or count 0 = the kernels above.
-// A CRYCHIC_GBUFFER_G*_F16 bit in P.flags: that plane's pointer addresses half4 texels, and the call goes to launch_light_formats.
+// A CRYCHIC_GBUFFER_G*_F16 bit in P.flags: that plane's pointer addresses half4 texels, and the call goes to launch_light_general.
 hipError_t launch_light(const LightParams& P, const float* g0, const float* g1, const float* g2,
                         const uint32_t* depth, const uint16_t* ambient, const uint8_t* cube, uint8_t* out,
                         float* radiance, uint32_t row0, uint32_t rows, hipStream_t stream, const crychic_light* spots,
                         uint32_t numSpots, const SpotShadows* shadows, const PointShadows* pointShadows);
-// light_formats.hip: the same pass over planes of any format mix (P.flags' CRYCHIC_GBUFFER_G*_F16 bits) -- light_formats_kernel for
-// a frame without local lights, light_point_shadows_formats_kernel for every other.
-hipError_t launch_light_formats(const LightParams& P, const void* g0, const void* g1, const void* g2, const uint32_t* depth,
+// light_general.hip: the same pass for every call of the general family (light_bind.hpp: a CRYCHIC_GBUFFER_G*_F16 bit,
+// CRYCHIC_LIGHT_CUBE_GLOSS, CRYCHIC_LIGHT_AMBIENT_SH or CRYCHIC_LIGHT_ENV_BRDF in P.flags) -- light_general_kernel for a frame without
+// local lights, light_general_local_kernel for every other, instantiated by the call's LightVariant; planes of any format mix.  The
+// environment terms are read behind the cube map at light_variant_tail's offset.
+hipError_t launch_light_general(const LightParams& P, const void* g0, const void* g1, const void* g2, const uint32_t* depth,
                                 const uint16_t* ambient, const uint8_t* cube, uint8_t* out, float* radiance, uint32_t row0, uint32_t rows,
                                 hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
                                 const PointShadows* pointShadows);
-// light_gloss.hip: the same pass with CRYCHIC_LIGHT_CUBE_GLOSS in P.flags (P.cubeLevels > 1) -- light_gloss_kernel for a frame without
-// local lights, light_gloss_local_kernel for every other; planes of any format mix.
-hipError_t launch_light_gloss(const LightParams& P, const void* g0, const void* g1, const void* g2, const uint32_t* depth,
-                              const uint16_t* ambient, const uint8_t* cube, uint8_t* out, float* radiance, uint32_t row0, uint32_t rows,
-                              hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
-                              const PointShadows* pointShadows);
-// light_env.hip: the same pass with CRYCHIC_LIGHT_AMBIENT_SH in P.flags -- light_env_kernel / light_env_local_kernel, each with the
-// level-0 or the gloss lookup; the coefficient block is read at cube + ambient_sh_offset(P.cubeDim, P.cubeLevels).
-hipError_t launch_light_env(const LightParams& P, const void* g0, const void* g1, const void* g2, const uint32_t* depth,
-                            const uint16_t* ambient, const uint8_t* cube, uint8_t* out, float* radiance, uint32_t row0, uint32_t rows,
-                            hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
-                            const PointShadows* pointShadows);
-// light_spec.hip: the same pass with CRYCHIC_LIGHT_ENV_BRDF in P.flags (always with CRYCHIC_LIGHT_CUBE_GLOSS) -- light_spec_kernel /
-// light_spec_local_kernel, each with the constant or the SH ambient term; the table is read at cube + env_brdf_offset(P.cubeDim,
-// P.cubeLevels).
-hipError_t launch_light_spec(const LightParams& P, const void* g0, const void* g1, const void* g2, const uint32_t* depth,
-                             const uint16_t* ambient, const uint8_t* cube, uint8_t* out, float* radiance, uint32_t row0, uint32_t rows,
-                             hipStream_t stream, const crychic_light* spots, uint32_t numSpots, const SpotShadows* shadows,
-                             const PointShadows* pointShadows);
 
 // cube_mips.hip: levels 1 .. levels - 1 of an RGBA8 cube map's chain from its level 0, in place (cube_mips_core.hpp); one launch per
 // six levels on `stream`.  The caller has checked dim and levels.

@@ -1,5 +1,5 @@
 // light_bind.hpp -- host side of one lighting call: what the kernels take by value (LightParams, SpotShadows, PointShadows) from the
-// caller's arguments, and which kernel family serves the call.  Plain C++: no HIP runtime call, nothing that can fail -- api.cpp
+// caller's arguments, and which kernel family and instantiation serve the call.  Plain C++: no HIP runtime call, nothing that can fail -- api.cpp
 // validates first and reports; the host build of the kernel bodies (tests/hostsim) binds through the same functions, so the CPU
 // tier executes the binding the library ships.
 #pragma once
@@ -121,7 +121,7 @@ inline const char* env_brdf_check_message(EnvBrdfCheck c)
 }
 
 // ---- which kernels serve a lighting call -------------------------------------------------------------------------
-// One family per set of kernel arguments; ZERO_RADIUS and MIPS (P.cubeLevels > 1) select the instantiation inside every family.
+// One family per set of kernel arguments; ZERO_RADIUS and the LightVariant below select the instantiation inside every family.
 enum class LightFamily {
     Frame,            // light_kernel<z, false>: no local light, no CRYCHIC_FIX_* bit, no chain -- the reference as written
     FrameFix,         // light_kernel<z, true, mips>: FIX compiled in (the chain is not the benchmark's instantiation)
@@ -130,13 +130,11 @@ enum class LightFamily {
     SpotsShadowed,    // light_spots_shadowed_kernel: SpotShadowOf on the spot lights
     PointShadows,     // light_point_shadows_kernel: PointShadowOf on the point lights, and the spot lights with SpotShadowOf even at a
                       // spot shadow count of 0 (factor 1)
-    FormatsFrame,     // light_formats_kernel: a half4 plane (CRYCHIC_GBUFFER_G*_F16), no local light
-    FormatsLocal,     // light_point_shadows_formats_kernel: a half4 plane and local lights of whatever kind; both shadow functors
-                      // whatever the counts
-    // CRYCHIC_LIGHT_CUBE_GLOSS maps onto these two as well: light_gloss_kernel and light_gloss_local_kernel (light_gloss.hip) compile
-    // in what they do -- planes of any format mix, FIX, both shadow functors -- with CubeGloss as the lookup.  So does
-    // CRYCHIC_LIGHT_AMBIENT_SH (light_env.hip: the same shapes with AmbientSH, level 0 or CubeGloss), and so does
-    // CRYCHIC_LIGHT_ENV_BRDF (light_spec.hip: the same shapes with SpecularSplitSum, always CubeGloss, either ambient term).
+    // The general family (light_general.hip): every call with a half4 plane (CRYCHIC_GBUFFER_G*_F16),
+    // CRYCHIC_LIGHT_CUBE_GLOSS, CRYCHIC_LIGHT_AMBIENT_SH or CRYCHIC_LIGHT_ENV_BRDF.  Planes of any format mix and FIX compiled in;
+    // the LightVariant below picks the instantiation.
+    FormatsFrame,     // light_general_kernel: no local light
+    FormatsLocal,     // light_general_local_kernel: local lights of whatever kind; both shadow functors whatever the counts
 };
 inline LightFamily light_family(uint32_t flags, uint32_t numPointLights, uint32_t numSpots, uint32_t spotShadowCount,
                                 uint32_t pointShadowCount, uint32_t cubeLevels)
@@ -161,5 +159,50 @@ constexpr bool light_family_spot_shadows(LightFamily f)
     return f == LightFamily::SpotsShadowed || f == LightFamily::PointShadows || f == LightFamily::FormatsLocal;
 }
 constexpr bool light_family_point_shadows(LightFamily f) { return f == LightFamily::PointShadows || f == LightFamily::FormatsLocal; }
+
+// ---- which instantiation inside a family -------------------------------------------------------------------------
+// The policies a call's light_pixel is instantiated with (light_core.hpp): the one place that turns flags into them.  The kernels of
+// kernels.hip know the lookup alone (their MIPS parameter: DerivativeChain or Level0, no flag of the other two set); the general
+// family and the host build of the bodies (tests/hostsim/host_light.hpp) go through light_variant_visit.
+enum class CubeLookup { Level0, DerivativeChain, Gloss };      // CubeLevel0 / CubeChain / CubeGloss
+struct LightVariant {
+    CubeLookup lookup;
+    bool ambientSH;        // AmbientSH, else AmbientConst
+    bool splitSum;         // SpecularSplitSum, else SpecularRef
+};
+inline LightVariant light_variant(uint32_t flags, uint32_t cubeLevels)
+{
+    const CubeLookup lookup = (flags & CRYCHIC_LIGHT_CUBE_GLOSS) ? CubeLookup::Gloss : cubeLevels > 1u ? CubeLookup::DerivativeChain : CubeLookup::Level0;
+    return LightVariant{ lookup, (flags & CRYCHIC_LIGHT_AMBIENT_SH) != 0, (flags & CRYCHIC_LIGHT_ENV_BRDF) != 0 };
+}
+// Byte offset behind the cube map that the kernels of a variant with an environment term take after row1 (one argument, so that
+// the table and the coefficient block CRYCHIC_CUBE_SH_BYTES before it cost one address): the table's with the split sum, else the
+// coefficient block's.
+inline size_t light_variant_tail(const LightVariant& v, uint32_t cubeDim, uint32_t cubeLevels)
+{
+    return v.splitSum ? env_brdf_offset(cubeDim, cubeLevels) : ambient_sh_offset(cubeDim, cubeLevels);
+}
+// f(Cube(), Ambient(), Specular()) for the variant's policies (value-initialised tags: take their types), once; false and no call
+// for a combination no kernel exists for -- SH with the derivative chain, the split sum without the gloss lookup (the entries of
+// api.cpp refuse both: ambient_sh_check, env_brdf_check).  Seven combinations.
+template <class F>
+inline bool light_variant_visit(const LightVariant& v, F&& f)
+{
+    switch (v.lookup) {
+    case CubeLookup::Level0:
+        if (v.splitSum) return false;
+        if (v.ambientSH) f(CubeLevel0(), AmbientSH(), SpecularRef()); else f(CubeLevel0(), AmbientConst(), SpecularRef());
+        return true;
+    case CubeLookup::DerivativeChain:
+        if (v.ambientSH || v.splitSum) return false;
+        f(CubeChain(), AmbientConst(), SpecularRef());
+        return true;
+    case CubeLookup::Gloss:
+        if (v.splitSum) { if (v.ambientSH) f(CubeGloss(), AmbientSH(), SpecularSplitSum()); else f(CubeGloss(), AmbientConst(), SpecularSplitSum()); }
+        else { if (v.ambientSH) f(CubeGloss(), AmbientSH(), SpecularRef()); else f(CubeGloss(), AmbientConst(), SpecularRef()); }
+        return true;
+    }
+    return false;
+}
 
 }  // namespace cry

@@ -2,6 +2,7 @@
 // GBuffer.hlsl:33-43, PBR.hlsl:4-107, LightingUtil.hlsl:52-60 and the rotated-Poisson cascade PCF of
 // Common.hlsl:167-183,263-317.  The reference's quirks are reproduced, not fixed.
 #pragma once
+#include <type_traits>
 #include "devmath.hpp"
 #include "crychic_hip.h"
 
@@ -690,6 +691,15 @@ CRY_HD bool cube_chain_flat(float lod)
 #else
     return lod == 0.0f;
 #endif
+}
+// The lookup of a pixel as a kernel of that policy hands it to light_pixel: `roughness` picks CubeGloss's level, `lod` (the quad's
+// derivatives) CubeChain's; CubeLevel0 takes neither.
+template <class Cube>
+CRY_HD Cube lookup_for(const LightParams& P, float roughness, float lod = 0.0f)
+{
+    if constexpr (std::is_same_v<Cube, CubeGloss>) return cube_gloss(P, roughness);
+    else if constexpr (std::is_same_v<Cube, CubeChain>) return CubeChain{ lod, cube_chain_flat(lod) };
+    else return CubeLevel0();
 }
 
 // gsamLinearClamp on the half-res R16_UNORM ambient map  (CRYCHIC.cpp:2624-2629)

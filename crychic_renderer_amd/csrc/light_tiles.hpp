@@ -1,5 +1,6 @@
 // light_tiles.hpp -- the per-workgroup bodies of the deferred lighting kernels (device code), shared by the float4 kernels of
-// kernels.hip and the format-aware kernels of light_formats.hip (G-buffer planes of any format mix).
+// kernels.hip and the general family of light_general.hip (planes of any format mix and every flagged lookup, ambient and specular
+// term: DESIGN.md section 13).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
@@ -42,14 +43,18 @@ __device__ __forceinline__ void tile_origin(uint32_t& bx, uint32_t& by)
 
 // ---- deferred lighting -----------------------------------------------------------------------------------------
 // Shaders/DeferredShading.hlsl:23-101 as a full-screen pass over rows [row0, row1), masked by depth < 1.
-// MIPS (the cube map holds a mip chain, P.cubeLevels > 1): a wavefront covers 32 x 2 pixels instead of 64 x 1, so that every 2 x 2
-// quad of the frame lies inside one wavefront -- the x neighbour is lane ^ 1, the y neighbour lane ^ 32 -- and the level of detail of
-// the reflection lookup comes from the neighbours' reflection vectors without a second pass (light_core.hpp "TextureCube.Sample
-// with the mip chain bound").
-template <bool MIPS>
+// Cube, the lookup policy of light_core.hpp (CubeLevel0 / CubeChain / CubeGloss), decides the footprint.  CubeChain (the cube map
+// holds a mip chain sampled by derivatives, P.cubeLevels > 1 without CRYCHIC_LIGHT_CUBE_GLOSS): a wavefront covers 32 x 2 pixels
+// instead of 64 x 1, so that every 2 x 2 quad of the frame lies inside one wavefront -- the x neighbour is lane ^ 1, the y
+// neighbour lane ^ 32 -- and the level of detail of the reflection lookup comes from the neighbours' reflection vectors without a
+// second pass (light_core.hpp "TextureCube.Sample with the mip chain bound").  The kernels of kernels.hip spell the choice as
+// their MIPS parameter.
+template <bool MIPS> using CubeOfMips = std::conditional_t<MIPS, CubeChain, CubeLevel0>;
+template <class Cube> constexpr bool kQuads = std::is_same_v<Cube, CubeChain>;
+template <bool QUADS>
 __device__ __forceinline__ void light_tile_pixel(uint32_t bx, uint32_t by, uint32_t row0, uint32_t& x, uint32_t& y)
 {
-    if (MIPS) {
+    if (QUADS) {
         const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
         x = bx * 64u + (wave & 1u) * 32u + (lane & 31u);
         y = row0 + by * 4u + (wave >> 1) * 2u + (lane >> 5);
@@ -74,13 +79,13 @@ __device__ __forceinline__ float quad_reflection_lod(const LightParams& P, bool 
 }
 
 // PLANE: f4a = three float4 planes, void = each plane float4 or half4 by its CRYCHIC_GBUFFER_G*_F16 bit of P.flags (light_core.hpp
-// gbuffer_load); whatever consumes a texel -- the quad exchange of MIPS, the tile cull below -- consumes the widened value.
-// GLOSS (light_gloss.hip, never with MIPS): the reflection lookup takes the chain at the level of the pixel's roughness (CubeGloss);
-// the pixels keep the 64 x 1 footprint of a wavefront, and the sky reads level 0.  `if constexpr`: the other instantiations hold no
-// trace of it.
-// Ambient (light_env.hip, never with MIPS): AmbientSH takes the ambient colour from the coefficient block behind the cube map.
-// Specular (light_spec.hip, always with GLOSS): SpecularSplitSum weighs the reflection by the table behind the environment tail.
-template <bool ZERO_RADIUS, bool FIX, bool MIPS, class PLANE, bool GLOSS = false, class Ambient = AmbientConst, class Specular = SpecularRef>
+// gbuffer_load); whatever consumes a texel -- the quad exchange of CubeChain, the tile cull below -- consumes the widened value.
+// CubeGloss: the reflection lookup takes the chain at the level of the pixel's roughness; the pixels keep the 64 x 1 footprint of a
+// wavefront, and the sky reads level 0.
+// Ambient (never with CubeChain): AmbientSH takes the ambient colour from the coefficient block behind the cube map.
+// Specular (always with CubeGloss): SpecularSplitSum weighs the reflection by the table behind the environment tail.
+// light_bind.hpp's light_variant_visit lists the combinations that exist (light_general.hip instantiates them).
+template <bool ZERO_RADIUS, bool FIX, class Cube, class PLANE, class Ambient = AmbientConst, class Specular = SpecularRef>
 __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLANE* __restrict__ g0, const PLANE* __restrict__ g1,
                                                  const PLANE* __restrict__ g2, const uint32_t* __restrict__ depth,
                                                  const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
@@ -92,8 +97,8 @@ __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLA
     tile_origin<0>(bx, by);
     by = light_dispatch_row(by, gridDim.y);               // the band order of dispatch_order.hpp (measured best: the natural one)
     uint32_t x, y;
-    light_tile_pixel<MIPS>(bx, by, row0, x, y);
-    if (MIPS) {
+    light_tile_pixel<kQuads<Cube>>(bx, by, row0, x, y);
+    if (kQuads<Cube>) {
         const bool in = x < P.W && y < row1;
         const uint32_t idx = in ? y * P.W + x : 0u;
         const bool covered = in && (depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu;
@@ -116,21 +121,14 @@ __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLA
     // coverage: the reference re-rasterises the opaque items with LESS against depth cleared to 1.0
     // (CRYCHIC.cpp:248,273) -- exactly the pixels whose normal/depth pass depth is below the clear value.
     if ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu) {
-        if constexpr (Specular::kSplitSum) {
-            static_assert(GLOSS, "the split-sum weight goes with the gloss lookup");
+        static_assert(!Specular::kSplitSum || std::is_same_v<Cube, CubeGloss>, "the split-sum weight goes with the gloss lookup");
+        // the reference as written keeps its texel loads as argument expressions (see CRY_GBUFFER_TEXEL): naming G1 moves its code
+        if constexpr (std::is_same_v<Cube, CubeLevel0> && !Ambient::kSH && !Specular::kSplitSum) {
+            lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), CRY_GBUFFER_TEXEL(g1, idx, h1), CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube);
+        } else {
             const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
-            lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX, CubeGloss, Ambient, Specular>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, NoPointLights(), cube_gloss(P, G1.w), ambientTerm, specTerm);
-        } else
-        if constexpr (Ambient::kSH) {
-            const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
-            if constexpr (GLOSS) lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX, CubeGloss, Ambient>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, NoPointLights(), cube_gloss(P, G1.w), ambientTerm);
-            else lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX, CubeLevel0, Ambient>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, NoPointLights(), CubeLevel0(), ambientTerm);
-        } else
-        if constexpr (GLOSS) {
-            const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
-            lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX, CubeGloss>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, NoPointLights(), cube_gloss(P, G1.w));
-        } else
-        lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), CRY_GBUFFER_TEXEL(g1, idx, h1), CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube);
+            lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX, Cube, Ambient, Specular>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, NoPointLights(), lookup_for<Cube>(P, G1.w), ambientTerm, specTerm);
+        }
     } else if (P.flags & CRYCHIC_LIGHT_SKY) {
         lit = sky_pixel(P, cube, x, y);
     } else {
@@ -154,7 +152,7 @@ __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLA
 // POINT_SHADOWED (light_point_shadows_kernel): point lights k < pointShadows->count take their cube shadow (PointShadowOf) the same
 // way.  The mask word is read once per wavefront (readfirstlane: every lane reads the same LDS word), so the walk's light index is
 // scalar, and with it the light's projection and map; the face is per lane (point_face's selects).
-template <bool ZERO_RADIUS, bool MIPS, bool SPOTS, bool SHADOWED = false, bool POINT_SHADOWED = false, class PLANE = f4a, bool GLOSS = false,
+template <bool ZERO_RADIUS, class Cube, bool SPOTS, bool SHADOWED = false, bool POINT_SHADOWED = false, class PLANE = f4a,
           class Ambient = AmbientConst, class Specular = SpecularRef>
 __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLANE* __restrict__ g0, const PLANE* __restrict__ g1,
                                                  const PLANE* __restrict__ g2, const uint32_t* __restrict__ depth,
@@ -169,7 +167,7 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLA
     tile_origin<0>(bx, by);
     by = light_dispatch_row(by, gridDim.y);               // the band order of dispatch_order.hpp (measured best: the natural one)
     uint32_t x, y;
-    light_tile_pixel<MIPS>(bx, by, row0, x, y);             // MIPS: 32 x 2 pixels per wavefront (quads inside a wavefront)
+    light_tile_pixel<kQuads<Cube>>(bx, by, row0, x, y);     // CubeChain: 32 x 2 pixels per wavefront (quads inside a wavefront)
     const bool inFrame = (x < P.W) && (y < row1);
     const uint32_t idx = inFrame ? y * P.W + x : 0u;
     const bool covered = inFrame && ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu);
@@ -226,7 +224,7 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLA
     __syncthreads();
     float lod = 0.0f;
     f4a G2{ 0, 0, 0, 0 };
-    if (MIPS) {                                              // every lane, converged: the quad neighbours' reflection vectors
+    if (kQuads<Cube>) {                                      // every lane, converged: the quad neighbours' reflection vectors
         f3 r{ 0.0f, 0.0f, 0.0f };
         if (covered) { G2 = CRY_GBUFFER_TEXEL(g2, idx, h2); r = reflection_dir(P, G0, G2); }
         lod = quad_reflection_lod(P, covered, r, x, y);
@@ -267,24 +265,12 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLA
                 }
             }
         };
-        if constexpr (Specular::kSplitSum) {
-            static_assert(GLOSS, "the split-sum weight goes with the gloss lookup");
-            const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
-            lit = light_pixel<ZERO_RADIUS, decltype(culled), true, CubeGloss, Ambient, Specular>(P, G0, G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, culled, cube_gloss(P, G1.w), ambientTerm, specTerm);
-        } else
-        if constexpr (Ambient::kSH) {
-            const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
-            if constexpr (GLOSS) lit = light_pixel<ZERO_RADIUS, decltype(culled), true, CubeGloss, Ambient>(P, G0, G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, culled, cube_gloss(P, G1.w), ambientTerm);
-            else lit = light_pixel<ZERO_RADIUS, decltype(culled), true, CubeLevel0, Ambient>(P, G0, G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, culled, CubeLevel0(), ambientTerm);
-        } else
-        if constexpr (GLOSS) {
-            const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
-            lit = light_pixel<ZERO_RADIUS, decltype(culled), true, CubeGloss>(P, G0, G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, culled, cube_gloss(P, G1.w));
-        } else
-        if (MIPS) lit = light_pixel<ZERO_RADIUS, decltype(culled), true, CubeChain>(P, G0, CRY_GBUFFER_TEXEL(g1, idx, h1), G2, ambient, cube, culled, CubeChain{ lod, cube_chain_flat(lod) });
-        else lit = light_pixel<ZERO_RADIUS, decltype(culled), true>(P, G0, CRY_GBUFFER_TEXEL(g1, idx, h1), CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, culled);
+        static_assert(!Specular::kSplitSum || std::is_same_v<Cube, CubeGloss>, "the split-sum weight goes with the gloss lookup");
+        const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
+        if constexpr (!kQuads<Cube>) G2 = CRY_GBUFFER_TEXEL(g2, idx, h2);        // the quad exchange has loaded it already
+        lit = light_pixel<ZERO_RADIUS, decltype(culled), true, Cube, Ambient, Specular>(P, G0, G1, G2, ambient, cube, culled, lookup_for<Cube>(P, G1.w, lod), ambientTerm, specTerm);
     } else if (P.flags & CRYCHIC_LIGHT_SKY) {
-        lit = MIPS ? sky_pixel_chain(P, cube, x, y) : sky_pixel(P, cube, x, y);
+        lit = kQuads<Cube> ? sky_pixel_chain(P, cube, x, y) : sky_pixel(P, cube, x, y);
     } else {
         lit = f4{ 0.690196097f, 0.768627524f, 0.870588303f, 1.0f };
     }

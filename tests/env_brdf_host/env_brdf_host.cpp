@@ -1,11 +1,11 @@
 // env_brdf_host.cpp -- csrc/env_brdf_core.hpp and the SpecularSplitSum instantiations of light_pixel built for the host (TEST
-// INFRASTRUCTURE): the bodies of the kernels of env_brdf.hip and light_spec.hip, bound through light_bind.hpp as the library binds them.
+// INFRASTRUCTURE): the bodies of the kernels of env_brdf.hip and of the split-sum variants of light_general.hip, bound through
+// light_bind.hpp as the library binds them.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <type_traits>
 #include "env_brdf_core.hpp"
-#include "light_bind.hpp"
+#include "../hostsim/host_light.hpp"
 
 // The body's two sums of texel (row j, column i) over the sample rows listed in `rows` (each one xi with its sixteen phi), in the
 // order given, through env_brdf_accumulate.
@@ -52,9 +52,8 @@ extern "C" int bh_check_message(uint32_t flags, uintptr_t cube, uint32_t cubeDim
     return std::snprintf(out, cap, cry::env_brdf_check_message(c), cry::env_brdf_offset(cubeDim, (flags >> 16) & 15u));
 }
 
-// Every crychic_deferred_light* entry with CRYCHIC_LIGHT_ENV_BRDF on the host, as tests/env_sh_host's eh_light runs the SH calls: the
-// family picked by light_family() (the flag maps onto the format-aware families), each pixel of rows [row0, row0 + rows) through
-// light_pixel with CubeGloss, SpecularSplitSum and the ambient term the kernels of light_spec.hip instantiate.  -1: refused.
+// Every crychic_deferred_light* entry with CRYCHIC_LIGHT_ENV_BRDF on the host (tests/hostsim/host_light.hpp): the flag maps onto the
+// general family, with CubeGloss, SpecularSplitSum and either ambient term.  -1: refused.
 extern "C" int bh_light(const crychic_pass_constants* cb, const void* g0, const void* g1, const void* g2,
                         const uint32_t* depth, const uint16_t* ambient, const uint32_t* const shadow[4], uint32_t shadowDim,
                         const uint8_t* cube, uint32_t cubeDim, uint8_t* out, float* radiance, uint32_t W, uint32_t H,
@@ -66,40 +65,7 @@ extern "C" int bh_light(const crychic_pass_constants* cb, const void* g0, const 
     using namespace cry;
     if (!(flags & CRYCHIC_LIGHT_ENV_BRDF) || env_brdf_check(flags, cube, cubeDim) != EnvBrdfCheck::Ok ||
         ambient_sh_check(flags, cube, cubeDim) != AmbientShCheck::Ok) return -1;
-    LightParams P;
-    SpotShadows S;
-    PointShadows PS;
-    bind_light_params(P, *cb, shadow, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags);
-    bind_point_lights(P, pointLights, numPointLights);
-    bind_spot_shadows(S, *cb, shadowMaps, shadowCount, shadowMapDim);
-    bind_point_shadows(PS, pointMaps, shadowProj, pointShadowCount, pointShadowDim);
-    const LightFamily family = light_family(P.flags, P.numPointLights, numSpotLights, S.count, PS.count, P.cubeLevels);
-    if (family != LightFamily::FormatsFrame && family != LightFamily::FormatsLocal) return -1;
-    const bool zero = pcfSearchRadius == 0.0f, shAmbient = (flags & CRYCHIC_LIGHT_AMBIENT_SH) != 0;
-    const AllLocalLights ll{ pointLights, numPointLights, spotLights, numSpotLights, light_family_spot_shadows(family) ? &S : nullptr,
-                             light_family_point_shadows(family) ? &PS : nullptr };
-    const uint32_t h0 = flags & CRYCHIC_GBUFFER_G0_F16, h1 = flags & CRYCHIC_GBUFFER_G1_F16, h2 = flags & CRYCHIC_GBUFFER_G2_F16;
-    const uint32_t* cubeTexels = (const uint32_t*)cube;
-    const size_t tableOffset = env_brdf_offset(P.cubeDim, P.cubeLevels);
-    const AmbientSH sh{ reinterpret_cast<const float*>(cube + (tableOffset - CRYCHIC_CUBE_SH_BYTES)) };
-    const SpecularSplitSum spec{ reinterpret_cast<const uint32_t*>(cube + tableOffset) };
-    for (uint32_t y = row0; y < row0 + rows; ++y)
-        for (uint32_t x = 0; x < W; ++x) {
-            const uint32_t idx = y * W + x;
-            f4 lit;
-            if ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu) {
-                const f4a G0 = gbuffer_load(g0, idx, h0), G1 = gbuffer_load(g1, idx, h1), G2 = gbuffer_load(g2, idx, h2);
-                auto pixel = [&](auto lights, auto z) {
-                    if (shAmbient) return light_pixel<z, decltype(lights), true, CubeGloss, AmbientSH, SpecularSplitSum>(P, G0, G1, G2, ambient, cubeTexels, lights, cube_gloss(P, G1.w), sh, spec);
-                    return light_pixel<z, decltype(lights), true, CubeGloss, AmbientConst, SpecularSplitSum>(P, G0, G1, G2, ambient, cubeTexels, lights, cube_gloss(P, G1.w), AmbientConst(), spec);
-                };
-                auto by_radius = [&](auto lights) { return zero ? pixel(lights, std::true_type{}) : pixel(lights, std::false_type{}); };
-                lit = light_family_local(family) ? by_radius(ll) : by_radius(NoPointLights());
-            }
-            else if (flags & CRYCHIC_LIGHT_SKY) lit = sky_pixel(P, cubeTexels, x, y);
-            else lit = f4{ 0.690196097f, 0.768627524f, 0.870588303f, 1.0f };
-            if (radiance) { radiance[4 * idx] = lit.x; radiance[4 * idx + 1] = lit.y; radiance[4 * idx + 2] = lit.z; radiance[4 * idx + 3] = lit.w; }
-            ((uint32_t*)out)[idx] = pack_rgba8(lit);
-        }
-    return 0;
+    return host_light(cb, g0, g1, g2, depth, ambient, shadow, shadowDim, cube, cubeDim, out, radiance, W, H, row0, rows, numDirLights, pcfSearchRadius, flags,
+                      pointLights, numPointLights, spotLights, numSpotLights, shadowCount, shadowMapDim, shadowMaps, pointShadowCount,
+                      pointShadowDim, pointMaps, shadowProj) ? 0 : -1;
 }

@@ -1,11 +1,11 @@
 """Builds and loads the checker and the host harness of the environment BRDF table and of the lighting pass's split-sum reflection
 weight (TEST INFRASTRUCTURE ONLY): tests/env_brdf_ref/libenvbrdfref.so -- tests/env_sh_ref/env_sh_ref.c included unchanged, with the
 table and the lighting pixel restated, built with the oracle's flags -- and tests/env_brdf_host/libenvbrdfhost.so,
-csrc/env_brdf_core.hpp and the SpecularSplitSum instantiations of light_pixel (bound through light_bind.hpp) compiled for the host.
+csrc/env_brdf_core.hpp and the lighting call with SpecularSplitSum (tests/hostsim/host_light.hpp, bound through light_bind.hpp) compiled for
+the host.
 Both are rebuilt when a source is newer.  With CRYCHIC_SANITIZE=1 the harness is the ASan + UBSan build."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
@@ -13,7 +13,8 @@ import env_sh_lib
 import gloss_lib
 import local_light_lib
 import point_shadow_lib
-from hostsim_lib import CLANG, CSRC, LIGHT_ARGTYPES, ROOT, SANITIZE, build_sanitized, run_light
+import hostsim_lib
+from hostsim_lib import LIGHT_ARGTYPES, ROOT, run_light
 
 ENV_BRDF = 0x100000     # CRYCHIC_LIGHT_ENV_BRDF
 TABLE_BYTES = 4096      # CRYCHIC_ENV_BRDF_BYTES
@@ -30,13 +31,7 @@ def build_ref():
 
 
 def build_host():
-    if SANITIZE:
-        return build_sanitized("libenvbrdfhost.so", [HOST_SRC])
-    deps = [HOST_SRC] + [os.path.join(CSRC, f) for f in ("env_brdf_core.hpp", "light_core.hpp", "light_bind.hpp", "devmath.hpp", "gamma_pow.inc")]
-    if not os.path.exists(HOST_LIB) or any(os.path.getmtime(d) > os.path.getmtime(HOST_LIB) for d in deps):
-        subprocess.run([CLANG, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma",
-                        "-I", os.path.join(ROOT, "include"), "-I", CSRC, HOST_SRC, "-o", HOST_LIB], check=True)
-    return HOST_LIB
+    return hostsim_lib.build_host(HOST_LIB, HOST_SRC, ("env_brdf_core.hpp",))
 
 
 def build():

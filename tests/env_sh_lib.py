@@ -1,18 +1,18 @@
 """Builds and loads the checker and the host harness of the SH9 irradiance projection and of the lighting pass's ambient term from it
 (TEST INFRASTRUCTURE ONLY): tests/env_sh_ref/libenvshref.so -- tests/gloss_ref/gloss_ref.c included unchanged, with the projection
 and the lighting pixel restated, built with the oracle's flags -- and tests/env_sh_host/libenvshhost.so, csrc/cube_sh_core.hpp and
-the AmbientSH instantiations of light_pixel (bound through light_bind.hpp) compiled for the host.  Both are rebuilt when a source is
+the lighting call with AmbientSH (tests/hostsim/host_light.hpp, bound through light_bind.hpp) compiled for the host.  Both are rebuilt when a source is
 newer.  With CRYCHIC_SANITIZE=1 the harness is the ASan + UBSan build."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 import gloss_lib
 import local_light_lib
 import point_shadow_lib
-from hostsim_lib import CLANG, CSRC, LIGHT_ARGTYPES, ROOT, SANITIZE, build_sanitized, run_light
+import hostsim_lib
+from hostsim_lib import LIGHT_ARGTYPES, ROOT, run_light
 
 AMBIENT_SH = 0x8000     # CRYCHIC_LIGHT_AMBIENT_SH
 TAIL_BYTES = 512        # CRYCHIC_CUBE_SH_BYTES
@@ -28,14 +28,7 @@ def build_ref():
 
 
 def build_host():
-    if SANITIZE:
-        return build_sanitized("libenvshhost.so", [HOST_SRC])
-    deps = [HOST_SRC] + [os.path.join(CSRC, f) for f in ("cube_sh_core.hpp", "cube_prefilter_core.hpp", "light_core.hpp", "light_bind.hpp",
-                                                        "devmath.hpp", "gamma_pow.inc")]
-    if not os.path.exists(HOST_LIB) or any(os.path.getmtime(d) > os.path.getmtime(HOST_LIB) for d in deps):
-        subprocess.run([CLANG, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma",
-                        "-I", os.path.join(ROOT, "include"), "-I", CSRC, HOST_SRC, "-o", HOST_LIB], check=True)
-    return HOST_LIB
+    return hostsim_lib.build_host(HOST_LIB, HOST_SRC, ("cube_sh_core.hpp", "cube_prefilter_core.hpp"))
 
 
 def build():

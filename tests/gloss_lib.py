@@ -1,18 +1,18 @@
 """Builds and loads the checker and the host harness of the prefiltered cube map chain and the glossy reflection lookup (TEST
 INFRASTRUCTURE ONLY): tests/gloss_ref/libglossref.so -- tests/point_shadow_ref/point_shadow_ref.c included unchanged, with a sample
 table of its own, the prefilter and the lighting pixel restated with the gloss lookup, built with the oracle's flags -- and
-tests/gloss_host/libglosshost.so, csrc/cube_prefilter_core.hpp and the gloss instantiation of light_pixel (bound through
+tests/gloss_host/libglosshost.so, csrc/cube_prefilter_core.hpp and the gloss lighting call (tests/hostsim/host_light.hpp, bound through
 light_bind.hpp) compiled for the host.  Both are rebuilt when a source is newer.  With CRYCHIC_SANITIZE=1 the harness is the ASan +
 UBSan build."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
 import local_light_lib
 import point_shadow_lib
-from hostsim_lib import CLANG, CSRC, LIGHT_ARGTYPES, ROOT, SANITIZE, build_sanitized, run_light
+import hostsim_lib
+from hostsim_lib import LIGHT_ARGTYPES, ROOT, run_light
 
 GLOSS = 0x800       # CRYCHIC_LIGHT_CUBE_GLOSS
 
@@ -31,13 +31,7 @@ def build_ref():
 
 
 def build_host():
-    if SANITIZE:
-        return build_sanitized("libglosshost.so", [HOST_SRC])
-    deps = [HOST_SRC] + [os.path.join(CSRC, f) for f in ("cube_prefilter_core.hpp", "light_core.hpp", "light_bind.hpp", "devmath.hpp", "gamma_pow.inc")]
-    if not os.path.exists(HOST_LIB) or any(os.path.getmtime(d) > os.path.getmtime(HOST_LIB) for d in deps):
-        subprocess.run([CLANG, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma",
-                        "-I", os.path.join(ROOT, "include"), "-I", CSRC, HOST_SRC, "-o", HOST_LIB], check=True)
-    return HOST_LIB
+    return hostsim_lib.build_host(HOST_LIB, HOST_SRC, ("cube_prefilter_core.hpp",))
 
 
 def build():

@@ -7,6 +7,7 @@
 #include "light_core.hpp"
 #include "light_bind.hpp"
 #include "raster_core.hpp"
+#include "host_light.hpp"
 #include <type_traits>
 #include <vector>
 
@@ -310,23 +311,9 @@ float hs_point_shadow_factor(const uint32_t* faces, uint32_t dim, const float sh
 
 }  // extern "C"
 
-// light_pixel as a kernel of the family instantiates it: MIPS kernels pass the quad's CubeChain, the others look level 0 up.
-template <bool ZERO_RADIUS, bool FIX, class Lights>
-static f4 hs_light_pixel(const LightParams& P, f4a G0, f4a G1, f4a G2, const uint16_t* ambient, const uint32_t* cube, Lights lights, const CubeChain* cc)
-{
-    return cc ? light_pixel<ZERO_RADIUS, Lights, FIX, CubeChain>(P, G0, G1, G2, ambient, cube, lights, *cc)
-              : light_pixel<ZERO_RADIUS, Lights, FIX>(P, G0, G1, G2, ambient, cube, lights);
-}
-
 extern "C" {
 
-// Every crychic_deferred_light* entry on the host: the arguments bound through the library's own light_bind.hpp, the kernel family
-// picked by its light_family(), and each pixel of rows [row0, row0 + rows) through the light_pixel instantiation that family's
-// kernels run.  g0 / g1 / g2: float4 or half4 texels by the CRYCHIC_GBUFFER_G*_F16 bits of flags (gbuffer_load; no bit: the plain
-// f4a load).  The local families iterate every light un-culled (AllLocalLights): the tiled kernels walk the culled lights in the
-// same ascending order.  A family's kernels carry a shadow functor or they do not, whatever the counts -- light_point_shadows_kernel
-// takes the spot lights with SpotShadowOf even at a spot shadow count of 0 (factor 1) -- and the descriptors handed to
-// AllLocalLights are non-null exactly for the functors the family compiles in.
+// Every crychic_deferred_light* entry on the host (host_light.hpp).
 void hs_light(const crychic_pass_constants* cb, const void* g0, const void* g1, const void* g2,
               const uint32_t* depth, const uint16_t* ambient, const uint32_t* const shadow[4], uint32_t shadowDim,
               const uint8_t* cube, uint32_t cubeDim, uint8_t* out, float* radiance, uint32_t W, uint32_t H,
@@ -335,49 +322,9 @@ void hs_light(const crychic_pass_constants* cb, const void* g0, const void* g1, 
               uint32_t numSpotLights, uint32_t shadowCount, uint32_t shadowMapDim, const uint32_t* const* shadowMaps,
               uint32_t pointShadowCount, uint32_t pointShadowDim, const uint32_t* const* pointMaps, const float* shadowProj)
 {
-    LightParams P;
-    SpotShadows S;
-    PointShadows PS;
-    bind_light_params(P, *cb, shadow, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags);
-    bind_point_lights(P, pointLights, numPointLights);
-    bind_spot_shadows(S, *cb, shadowMaps, shadowCount, shadowMapDim);
-    bind_point_shadows(PS, pointMaps, shadowProj, pointShadowCount, pointShadowDim);
-    const LightFamily family = light_family(P.flags, P.numPointLights, numSpotLights, S.count, PS.count, P.cubeLevels);
-    const bool chain = P.cubeLevels > 1u, zero = pcfSearchRadius == 0.0f;
-    const AllLocalLights ll{ pointLights, numPointLights, spotLights, numSpotLights, light_family_spot_shadows(family) ? &S : nullptr,
-                             light_family_point_shadows(family) ? &PS : nullptr };
-    const uint32_t h0 = flags & CRYCHIC_GBUFFER_G0_F16, h1 = flags & CRYCHIC_GBUFFER_G1_F16, h2 = flags & CRYCHIC_GBUFFER_G2_F16;
-    auto shaded = [&](uint32_t xx, uint32_t yy) { return xx < W && yy < row0 + rows && (depth[yy * W + xx] & 0x00FFFFFFu) < 0x00FFFFFFu; };
-    auto reflection = [&](uint32_t xx, uint32_t yy) { return reflection_dir(P, gbuffer_load(g0, yy * W + xx, h0), gbuffer_load(g2, yy * W + xx, h2)); };
-    const uint32_t* cubeTexels = (const uint32_t*)cube;
-    for (uint32_t y = row0; y < row0 + rows; ++y)
-        for (uint32_t x = 0; x < W; ++x) {
-            const uint32_t idx = y * W + x;
-            f4 lit;
-            if (shaded(x, y)) {
-                const f4a G0 = gbuffer_load(g0, idx, h0), G1 = gbuffer_load(g1, idx, h1), G2 = gbuffer_load(g2, idx, h2);
-                CubeChain cc{ 0.0f, true };
-                if (chain) {        // <.., MIPS>: the quad neighbours' reflection vectors arrive by lane exchange there, by recomputation here
-                    const f3 r = reflection_dir(P, G0, G2);
-                    f3 ddx{ 0.0f, 0.0f, 0.0f }, ddy{ 0.0f, 0.0f, 0.0f };
-                    if (shaded(x ^ 1u, y)) { const f3 n = reflection(x ^ 1u, y); ddx = (x & 1u) ? f3{ r.x - n.x, r.y - n.y, r.z - n.z } : f3{ n.x - r.x, n.y - r.y, n.z - r.z }; }
-                    if (shaded(x, y ^ 1u)) { const f3 n = reflection(x, y ^ 1u); ddy = (y & 1u) ? f3{ r.x - n.x, r.y - n.y, r.z - n.z } : f3{ n.x - r.x, n.y - r.y, n.z - r.z }; }
-                    const float lod = cube_lod(P.cubeDim, P.cubeLevels, r, ddx, ddy);
-                    cc = CubeChain{ lod, cube_chain_flat(lod) };
-                }
-                auto pixel = [&](auto fix, auto lights) {
-                    return zero ? hs_light_pixel<true, decltype(fix)::value>(P, G0, G1, G2, ambient, cubeTexels, lights, chain ? &cc : nullptr)
-                                : hs_light_pixel<false, decltype(fix)::value>(P, G0, G1, G2, ambient, cubeTexels, lights, chain ? &cc : nullptr);
-                };
-                if (light_family_local(family)) lit = pixel(std::true_type{}, ll);           // every local family compiles FIX in
-                else if (light_family_fix(family)) lit = pixel(std::true_type{}, NoPointLights());
-                else lit = pixel(std::false_type{}, NoPointLights());
-            }
-            else if (flags & CRYCHIC_LIGHT_SKY) lit = chain ? sky_pixel_chain(P, cubeTexels, x, y) : sky_pixel(P, cubeTexels, x, y);
-            else lit = f4{ 0.690196097f, 0.768627524f, 0.870588303f, 1.0f };
-            if (radiance) { radiance[4 * idx] = lit.x; radiance[4 * idx + 1] = lit.y; radiance[4 * idx + 2] = lit.z; radiance[4 * idx + 3] = lit.w; }
-            ((uint32_t*)out)[idx] = pack_rgba8(lit);
-        }
+    host_light(cb, g0, g1, g2, depth, ambient, shadow, shadowDim, cube, cubeDim, out, radiance, W, H, row0, rows, numDirLights, pcfSearchRadius, flags,
+               pointLights, numPointLights, spotLights, numSpotLights, shadowCount, shadowMapDim, shadowMaps, pointShadowCount,
+               pointShadowDim, pointMaps, shadowProj);
 }
 
 // The producer passes executed sequentially on the host with the kernels' own bodies (raster_core.hpp): setup in draw

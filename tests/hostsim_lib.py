@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "hostsim", "hostsim.cpp")
 LIB = os.path.join(ROOT, "tests", "hostsim", "libhostsim.so")
 CSRC = os.path.join(ROOT, "crychic_renderer_amd", "csrc")
+HOST_LIGHT = os.path.join(ROOT, "tests", "hostsim", "host_light.hpp")      # the lighting call every host harness shares
 CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 
 
@@ -24,21 +25,27 @@ def build_sanitized(name, sources, extra=()):
     """clang ASan + UBSan shared object under tests/hostsim/_san (loaded with the sanitizer runtime preloaded: tools/sanitize.sh)."""
     os.makedirs(SAN_DIR, exist_ok=True)
     out = os.path.join(SAN_DIR, name)
-    deps = list(sources) + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(ROOT, "include", "crychic_hip.h")]
+    deps = list(sources) + [HOST_LIGHT] + [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".hpp")] + [os.path.join(ROOT, "include", "crychic_hip.h")]
     if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         subprocess.run([CLANG, "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma"] + SAN_FLAGS + list(extra) +
                        ["-I", os.path.join(ROOT, "include"), "-I", CSRC] + list(sources) + ["-o", out], check=True)
     return out
 
 
-def build():
+def build_host(lib, src, headers):
+    """The host harness `lib` from its one source `src`, rebuilt when the source, host_light.hpp or one of csrc's `headers` (besides
+    the ones every harness includes) is newer; with CRYCHIC_SANITIZE=1 its ASan + UBSan build instead."""
     if SANITIZE:
-        return build_sanitized("libhostsim.so", [SRC])
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("devmath.hpp", "gamma_pow.inc", "ssao_core.hpp", "blur_tiles.hpp", "light_core.hpp", "light_bind.hpp", "raster_core.hpp")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
+        return build_sanitized(os.path.basename(lib), [src])
+    deps = [src, HOST_LIGHT] + [os.path.join(CSRC, f) for f in ("devmath.hpp", "gamma_pow.inc", "light_core.hpp", "light_bind.hpp") + tuple(headers)]
+    if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         subprocess.run([CLANG, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma",
-                        "-I", os.path.join(ROOT, "include"), "-I", CSRC, SRC, "-o", LIB], check=True)
-    return LIB
+                        "-I", os.path.join(ROOT, "include"), "-I", CSRC, src, "-o", lib], check=True)
+    return lib
+
+
+def build():
+    return build_host(LIB, SRC, ("ssao_core.hpp", "blur_tiles.hpp", "raster_core.hpp"))
 
 
 G_F16 = (G0_F16, G1_F16, G2_F16)

@@ -234,8 +234,8 @@ def test_every_entry_every_mix(built_lib, oracle, entry):
 def test_1080p_whole_frame_and_strips(built_lib, oracle, mix):
     """1920 x 1080 through crychic_deferred_light_point_shadows with every kind of local light and shadow, and through
     crychic_deferred_light without any: the whole frame == the checker on the widened planes, and two strips == the whole frame.
-    These two entries are the two format-aware kernels (launch_light_formats): the _points, _spots and _spots_shadowed entries launch
-    the very light_point_shadows_formats_kernel that _point_shadows does, with counts of 0, and all five entries are held against the
+    These two entries are the two kernels of the general family (launch_light_general): the _points, _spots and _spots_shadowed entries
+    launch the very light_general_local_kernel that _point_shadows does, with counts of 0, and all five entries are held against the
     checker at 322 x 190 (test_every_entry_every_mix); at this size the other six mixes are left to that test too."""
     import torch
     from crychic_renderer_amd import Context

@@ -10,7 +10,7 @@ if [ "$mode" = build ]; then
   name=$1; defs=$2
   mkdir -p tools/_probe
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -shared --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -fno-slp-vectorize -Wno-unused-function $defs \
-    -I include -I crychic_renderer_amd/csrc $(for s in kernels.hip light_formats.hip raster.hip api.cpp comm.cpp host_constants.cpp host_geometry.cpp host_textures.cpp; do echo -x hip crychic_renderer_amd/csrc/$s; done) \
+    -I include -I crychic_renderer_amd/csrc $(for s in kernels.hip light_general.hip raster.hip api.cpp comm.cpp host_constants.cpp host_geometry.cpp host_textures.cpp; do echo -x hip crychic_renderer_amd/csrc/$s; done) \
     -ldl -o tools/_probe/lib_$name.so && echo "built tools/_probe/lib_$name.so"
   exit $?
 fi
