@@ -152,24 +152,50 @@ __global__ __launch_bounds__(256) void ssao_kernel(crychic_ssao_constants cb, co
 
     const DepthPairs dp{ edge.pairs, depth_pairs_pitch(W) };
     const DepthD24 dd{ depth, W, H };
+    // ---- the wavefront's one batch of loads: nothing in it waits for anything else in it ----
     // the pixel's own depth comes from the D24 plane (coalesced): its pairs entry may be one the depth pass did not write
-    const SsaoCentre c = ssao_centre(cb, normal, depth, W, H, (int)x, (int)y);
+    const SsaoCentreRaw cr = ssao_centre_fetch(normal, depth, W, H, (int)x, (int)y);
+    // the random-vector texels of the tap loop: their addresses depend on (x, y) alone
+    RandvecRaw rv{};
+    if (EMIT_AO) rv = ssao_pixel_randvec_fetch(randvec, x, y, hs);
+    // the cells of the geometry map the sky shortcut may ask for, one per lane: the rectangle depends on the wavefront's position
+    // and the kernel's arguments alone, so it is addressed (on wave-uniform values: x0 and the row are the same in every lane)
+    // and fetched before anyone knows whether the wavefront is sky
+    const bool skyMaps = EMIT_AO && MAPS && sky.enabled;
+    const uint32_t x0 = bx * 64u, n = (w2 - x0) < 64u ? (w2 - x0) : 64u;
+    GeoCells g{};
+    uint32_t cellWord = 0u;
+    if (skyMaps) {
+        g = ssao_sky_cells(sky, W, H, x0, n, (uint32_t)__builtin_amdgcn_readfirstlane((int)y));
+        cellWord = edge.geo[ssao_sky_cell_of_lane(g, geo_map_cols(W), threadIdx.x & 63u)];
+    }
+    // the border texels of the edge workspace, under their lane predicates
+    u2 gcolTexel{}, growTexel{};
+    if (edge.nrm) {
+        if (x == 0) gcolTexel = normal[(2u * y + 1u) * W];      // texel (0, 2y+1)
+        if (y == row0) growTexel = normal[2u * x + 1u];         // texel (2x+1, 0)
+    }
+    // ---- the batch is in flight ----
+    const SsaoCentre c = ssao_centre_resolve(cb, cr);
     if (edge.nrm) {
         const uint32_t idx = y * w2 + x;
         edge.nrm[idx] = c.nrm_bits;
         edge.vz[idx] = c.vz;
-        if (x == 0) edge.gcol[y] = normal[(2u * y + 1u) * W];   // texel (0, 2y+1)
-        if (y == row0) edge.grow[x] = normal[2u * x + 1u];      // texel (2x+1, 0)
+        if (x == 0) edge.gcol[y] = gcolTexel;
+        if (y == row0) edge.grow[x] = growTexel;
     }
     // Sky shortcut (ssao_core.hpp): every live lane of this wave is a sky pixel and no cell its taps can reach holds geometry
-    if (EMIT_AO && MAPS && sky.enabled && __builtin_amdgcn_ballot_w64(!c.sky) == 0) {
-        const uint32_t x0 = bx * 64u, n = (w2 - x0) < 64u ? (w2 - x0) : 64u;
-        const GeoCells g = ssao_sky_cells(sky, W, H, x0, n, y);
+    if (skyMaps && __builtin_amdgcn_ballot_w64(!c.sky) == 0) {
         const uint32_t ncx = g.cx1 - g.cx0 + 1u, ncells = ncx * (g.cy1 - g.cy0 + 1u), pitch = geo_map_cols(W);
-        bool geometry = false;
-        for (uint32_t k = threadIdx.x & 63u; k < ncells; k += n) {          // the wave's n live lanes (0 .. n-1) share the cells
-            const uint32_t cy = k / ncx, cx = k - cy * ncx;
-            geometry |= edge.geo[(g.cy0 + cy) * pitch + g.cx0 + cx] == stamp;
+        bool geometry = cellWord == stamp;                                    // lanes 0 .. ncells-1 hold the cells: enough when ncells <= n
+        if (ncells > n) {
+            // a rectangle of more cells than the wave has live lanes (more than 64 cells, or a short wave at the frame's edge
+            // with a wide reach): the n live lanes (0 .. n-1) share the cells in a loop
+            geometry = false;
+            for (uint32_t k = threadIdx.x & 63u; k < ncells; k += n) {
+                const uint32_t cy = k / ncx, cx = k - cy * ncx;
+                geometry |= edge.geo[(g.cy0 + cy) * pitch + g.cx0 + cx] == stamp;
+            }
         }
         if (g.known && __builtin_amdgcn_ballot_w64(geometry) == 0) {
             ambient[y * w2 + x] = (uint16_t)0xFFFFu;
@@ -182,17 +208,17 @@ __global__ __launch_bounds__(256) void ssao_kernel(crychic_ssao_constants cb, co
         const ZminMap zm{ edge.zcull, zmin_map_cols(W) };
         if (ROWS && PAIRS) {      // && MAPS
             const DepthPairsRows dr{ dp, dd, prep.j0lo, prep.nj };
-            if (cullEnabled) v = ssao_pixel(cb, c, dr, randvec, W, H, x, y, hs, sparseProjTex != 0, ZminMapRows{ zm, prep.j0lo, prep.nj });
-            else v = ssao_pixel(cb, c, dr, randvec, W, H, x, y, hs, sparseProjTex != 0);
+            if (cullEnabled) v = ssao_pixel_fetched(cb, c, dr, rv, W, H, x, y, hs, sparseProjTex != 0, ZminMapRows{ zm, prep.j0lo, prep.nj });
+            else v = ssao_pixel_fetched(cb, c, dr, rv, W, H, x, y, hs, sparseProjTex != 0);
         }
         else if (ROWS) {          // MAPS without the pairs plane: the taps gather from the raw plane, the culling map is the strip's
-            if (cullEnabled) v = ssao_pixel(cb, c, dd, randvec, W, H, x, y, hs, sparseProjTex != 0, ZminMapRows{ zm, prep.j0lo, prep.nj });
-            else v = ssao_pixel(cb, c, dd, randvec, W, H, x, y, hs, sparseProjTex != 0);
+            if (cullEnabled) v = ssao_pixel_fetched(cb, c, dd, rv, W, H, x, y, hs, sparseProjTex != 0, ZminMapRows{ zm, prep.j0lo, prep.nj });
+            else v = ssao_pixel_fetched(cb, c, dd, rv, W, H, x, y, hs, sparseProjTex != 0);
         }
-        else if (PAIRS && MAPS && cullEnabled) v = ssao_pixel(cb, c, dp, randvec, W, H, x, y, hs, sparseProjTex != 0, zm);
-        else if (PAIRS) v = ssao_pixel(cb, c, dp, randvec, W, H, x, y, hs, sparseProjTex != 0);
-        else if (MAPS && cullEnabled) v = ssao_pixel(cb, c, dd, randvec, W, H, x, y, hs, sparseProjTex != 0, zm);
-        else v = ssao_pixel(cb, c, dd, randvec, W, H, x, y, hs, sparseProjTex != 0);
+        else if (PAIRS && MAPS && cullEnabled) v = ssao_pixel_fetched(cb, c, dp, rv, W, H, x, y, hs, sparseProjTex != 0, zm);
+        else if (PAIRS) v = ssao_pixel_fetched(cb, c, dp, rv, W, H, x, y, hs, sparseProjTex != 0);
+        else if (MAPS && cullEnabled) v = ssao_pixel_fetched(cb, c, dd, rv, W, H, x, y, hs, sparseProjTex != 0, zm);
+        else v = ssao_pixel_fetched(cb, c, dd, rv, W, H, x, y, hs, sparseProjTex != 0);
         ambient[y * w2 + x] = (uint16_t)v;
         // unoccluded-wavefront map (ssao_core.hpp "unoccluded tiles"): lane 0 is live whenever the wave is (x = 64 bx < w2).  The
         // word is written by EVERY wavefront that emits ambient values -- the stamp or 0 -- so no word of a row computed this

@@ -194,16 +194,28 @@ CRY_HD void depth_tap(const DepthPairsRows& d, bool culled, int i0, int j0, floa
 
 // The same sampler at the centre of half-res pixel (xi, yi) (even W, H): texels 2xi..2xi+1 x 2yi..2yi+1 with
 // weights 1/2; a pixel outside the half-res map only ever addresses border texels.
+// In two halves -- issue the loads, decode them -- so that a caller can put the loads into one batch with others before it waits
+// for any of them (ssao_kernel's prologue).
+struct HalfPixelRaw { RawPair p0, p1; bool in; };
+CRY_HD HalfPixelRaw depth_at_half_pixel_fetch(const uint32_t* __restrict__ depth, uint32_t W, uint32_t H, int xi, int yi)
+{
+    HalfPixelRaw r;
+    r.in = ((uint32_t)(2 * xi) < W) & ((uint32_t)(2 * yi) < H);   // even sizes: all four in or all four out
+    const uint32_t cx = (uint32_t)clampi(2 * xi, 0, (int)W - 2), cy = (uint32_t)clampi(2 * yi, 0, (int)H - 2);
+    const uint32_t t0 = mul24(cy, W) + cx;
+    r.p0 = load_pair(depth, t0);
+    r.p1 = load_pair(depth, t0 + W);
+    return r;
+}
+CRY_HD void depth_at_half_pixel_resolve(const HalfPixelRaw& r, float& t00, float& t10, float& t01, float& t11)
+{
+    t00 = d24_to_float(r.in ? r.p0.lo : 0x00FFFFFFu); t10 = d24_to_float(r.in ? r.p0.hi : 0x00FFFFFFu);
+    t01 = d24_to_float(r.in ? r.p1.lo : 0x00FFFFFFu); t11 = d24_to_float(r.in ? r.p1.hi : 0x00FFFFFFu);
+}
 CRY_HD void depth_at_half_pixel(const uint32_t* __restrict__ depth, uint32_t W, uint32_t H, int xi, int yi, float& t00, float& t10, float& t01,
                                 float& t11)
 {
-    const bool in = ((uint32_t)(2 * xi) < W) & ((uint32_t)(2 * yi) < H);   // even sizes: all four in or all four out
-    const uint32_t cx = (uint32_t)clampi(2 * xi, 0, (int)W - 2), cy = (uint32_t)clampi(2 * yi, 0, (int)H - 2);
-    const uint32_t t0 = mul24(cy, W) + cx;
-    const RawPair p0 = load_pair(depth, t0);
-    const RawPair p1 = load_pair(depth, t0 + W);
-    t00 = d24_to_float(in ? p0.lo : 0x00FFFFFFu); t10 = d24_to_float(in ? p0.hi : 0x00FFFFFFu);
-    t01 = d24_to_float(in ? p1.lo : 0x00FFFFFFu); t11 = d24_to_float(in ? p1.hi : 0x00FFFFFFu);
+    depth_at_half_pixel_resolve(depth_at_half_pixel_fetch(depth, W, H, xi, yi), t00, t10, t01, t11);
 }
 CRY_HD float depth_at_half_pixel(const uint32_t* __restrict__ depth, uint32_t W, uint32_t H, int xi, int yi)
 {
@@ -222,22 +234,36 @@ CRY_HD u2 normal_texel_bits(const u2* __restrict__ normal, uint32_t W, uint32_t 
 }
 
 // gsamLinearWrap on the 256x256 RGBA8 random-vector map  (CRYCHIC.cpp:1068-1073)
-CRY_HD f3 randvec_linear_wrap(const uint32_t* __restrict__ rv, float u, float v)
+// In two halves (issue, then filter): the texel addresses depend on the pixel's position alone, so ssao_kernel issues the four
+// loads with its first batch.  The four texels and the two fractions are carried to the resolve half.
+struct RandvecRaw { uint32_t t00, t10, t01, t11; float fx, fy; };
+CRY_HD RandvecRaw randvec_fetch(const uint32_t* __restrict__ rv, float u, float v)
 {
     float uw = u - __builtin_floorf(u), vw = v - __builtin_floorf(v);
     Bilin b = bilinear_setup(uw, vw, 256, 256);
     uint32_t x0 = (uint32_t)b.i0 & 255u, x1 = (uint32_t)(b.i0 + 1) & 255u;
     uint32_t y0 = (uint32_t)b.j0 & 255u, y1 = (uint32_t)(b.j0 + 1) & 255u;
-    const uint32_t t00 = load_at<uint32_t>(rv, (y0 * 256u + x0) * 4u), t10 = load_at<uint32_t>(rv, (y0 * 256u + x1) * 4u);
-    const uint32_t t01 = load_at<uint32_t>(rv, (y1 * 256u + x0) * 4u), t11 = load_at<uint32_t>(rv, (y1 * 256u + x1) * 4u);
+    RandvecRaw r;
+    r.t00 = load_at<uint32_t>(rv, (y0 * 256u + x0) * 4u); r.t10 = load_at<uint32_t>(rv, (y0 * 256u + x1) * 4u);
+    r.t01 = load_at<uint32_t>(rv, (y1 * 256u + x0) * 4u); r.t11 = load_at<uint32_t>(rv, (y1 * 256u + x1) * 4u);
+    r.fx = b.fx; r.fy = b.fy;
+    return r;
+}
+CRY_HD f3 randvec_resolve(const RandvecRaw& r)
+{
+    const uint32_t t00 = r.t00, t10 = r.t10, t01 = r.t01, t11 = r.t11;
     f3 o;
     o.x = bilerp(unorm8_to_float(t00 & 255u), unorm8_to_float(t10 & 255u), unorm8_to_float(t01 & 255u),
-                 unorm8_to_float(t11 & 255u), b.fx, b.fy);
+                 unorm8_to_float(t11 & 255u), r.fx, r.fy);
     o.y = bilerp(unorm8_to_float((t00 >> 8) & 255u), unorm8_to_float((t10 >> 8) & 255u),
-                 unorm8_to_float((t01 >> 8) & 255u), unorm8_to_float((t11 >> 8) & 255u), b.fx, b.fy);
+                 unorm8_to_float((t01 >> 8) & 255u), unorm8_to_float((t11 >> 8) & 255u), r.fx, r.fy);
     o.z = bilerp(unorm8_to_float((t00 >> 16) & 255u), unorm8_to_float((t10 >> 16) & 255u),
-                 unorm8_to_float((t01 >> 16) & 255u), unorm8_to_float((t11 >> 16) & 255u), b.fx, b.fy);
+                 unorm8_to_float((t01 >> 16) & 255u), unorm8_to_float((t11 >> 16) & 255u), r.fx, r.fy);
     return o;
+}
+CRY_HD f3 randvec_linear_wrap(const uint32_t* __restrict__ rv, float u, float v)
+{
+    return randvec_resolve(randvec_fetch(rv, u, v));
 }
 
 // gProjTex = Proj * T (CRYCHIC.cpp:828-834,918) has seven structural zeros and a one for every perspective projection:
@@ -333,6 +359,21 @@ CRY_HD GeoCells ssao_sky_cells(const SkyReach& r, uint32_t W, uint32_t H, uint32
     const int cellsEnd = 32 * (int)g.cy1 + 32 < (int)H ? 32 * (int)g.cy1 + 32 : (int)H;      // texel rows [32 cy0, cellsEnd) belong to the cells
     g.known = 32 * (int)g.cy0 >= r.y0 && cellsEnd <= r.y1;
     return g;
+}
+
+// The cell of the rectangle that lane `lane` of a wavefront looks at when the rectangle's cells are dealt one per lane: cell
+// k = min(lane, ncells - 1) in row-major order, as an index into the map of `pitch` columns.  Needs ncells <= 64.  The row
+// k / ncx comes from a reciprocal taken once on wave-uniform values instead of an integer division per lane:
+// floor((k + 0.5) * rcp(ncx)) -- (k + 0.5) / ncx is at least 1 / (2 ncx) >= 2^-7 away from every integer, and with k < 64 the
+// binary32 product is off by less than 64 * 2 * 2^-24 < 2^-17 (k + 0.5 is exact, the reciprocal of 1 <= ncx <= 64 and the product
+// are rounded once each), so the floor is the exact quotient, on the device and on the host.  Lanes past the last cell repeat
+// it: harmless to a vote.  Every index lies inside the rectangle, hence inside the map.
+CRY_HD uint32_t ssao_sky_cell_of_lane(const GeoCells& g, uint32_t pitch, uint32_t lane)
+{
+    const uint32_t ncx = g.cx1 - g.cx0 + 1u, ncells = ncx * (g.cy1 - g.cy0 + 1u);
+    const uint32_t k = lane < ncells ? lane : ncells - 1u;
+    const uint32_t cy = (uint32_t)(((float)k + 0.5f) * rcp_normal((float)ncx)), cx = k - cy * ncx;
+    return (g.cy0 + cy) * pitch + g.cx0 + cx;
 }
 
 // Cell rows of the nearest-depth map [*c0, *c0 + *cn) that the depth pass visits for an SSAO pass over half-res rows
@@ -434,16 +475,28 @@ struct SsaoCentre {
     bool sky;        // ssao_sky_lane(): candidate for the sky shortcut (pairs path only)
 };
 
-CRY_HD SsaoCentre ssao_centre(const crychic_ssao_constants& cb, const u2* __restrict__ normal,
-                              const uint32_t* __restrict__ depth, uint32_t W, uint32_t H, int x, int y)
+struct SsaoCentreRaw { u2 nrm_bits; HalfPixelRaw depth; };
+CRY_HD SsaoCentreRaw ssao_centre_fetch(const u2* __restrict__ normal, const uint32_t* __restrict__ depth, uint32_t W, uint32_t H, int x, int y)
+{
+    SsaoCentreRaw r;
+    r.nrm_bits = normal_texel_bits(normal, W, H, x, y);
+    r.depth = depth_at_half_pixel_fetch(depth, W, H, x, y);
+    return r;
+}
+CRY_HD SsaoCentre ssao_centre_resolve(const crychic_ssao_constants& cb, const SsaoCentreRaw& r)
 {
     SsaoCentre c;
-    c.nrm_bits = normal_texel_bits(normal, W, H, x, y);
+    c.nrm_bits = r.nrm_bits;
     float t00, t10, t01, t11;
-    depth_at_half_pixel(depth, W, H, x, y, t00, t10, t01, t11);
+    depth_at_half_pixel_resolve(r.depth, t00, t10, t01, t11);
     c.vz = ndc_to_view(cb, bilerp(t00, t10, t01, t11, 0.5f, 0.5f));
     c.sky = ssao_sky_lane(t00, t10, t01, t11, c.nrm_bits);
     return c;
+}
+CRY_HD SsaoCentre ssao_centre(const crychic_ssao_constants& cb, const u2* __restrict__ normal,
+                              const uint32_t* __restrict__ depth, uint32_t W, uint32_t H, int x, int y)
+{
+    return ssao_centre_resolve(cb, ssao_centre_fetch(normal, depth, W, H, x, y));
 }
 // Ssao.hlsl:117-199 for half-res pixel (x, y); returns the R16_UNORM ambient value.  `sparseProjTex` = ssao_projtex_is_sparse(cb).
 // `cull`: NoCull, or the ZminMap of the tap culling.  `culledTaps` (host builds only, may be null): three words -- [0] += the number
@@ -454,12 +507,24 @@ CRY_HD SsaoCentre ssao_centre(const crychic_ssao_constants& cb, const u2* __rest
 struct HalfResScale { float rw2, rh2; };
 CRY_HD HalfResScale half_res_scale(uint32_t W, uint32_t H) { return HalfResScale{ rcp((float)(W / 2)), rcp((float)(H / 2)) }; }
 
-template <class Depth, class Cull = NoCull>
-CRY_HD uint32_t ssao_pixel(const crychic_ssao_constants& cb, const SsaoCentre& c,
-                           const Depth depth, const uint32_t* __restrict__ randvec, uint32_t W,
-                           uint32_t H, uint32_t x, uint32_t y, const HalfResScale hs, bool sparseProjTex, const Cull cull = Cull(),
-                           uint32_t* culledTaps = nullptr)
+// The random-vector texels of pixel (x, y), issued (ssao_pixel_randvec_fetch) ahead of the body that filters them
+// (ssao_pixel_fetched): the kernel puts them into its first batch of loads, ssao_pixel() is the two back to back.
+CRY_HD RandvecRaw ssao_pixel_randvec_fetch(const uint32_t* __restrict__ randvec, uint32_t x, uint32_t y, const HalfResScale hs)
 {
+    const float u = ((float)x + 0.5f) * hs.rw2;
+    const float v = ((float)y + 0.5f) * hs.rh2;
+    return randvec_fetch(randvec, 4.0f * u, 4.0f * v);  // :138
+}
+template <class Depth, class Cull = NoCull>
+CRY_HD uint32_t ssao_pixel_fetched(const crychic_ssao_constants& cb, const SsaoCentre& c,
+                                   const Depth depth, const RandvecRaw& rvRaw, uint32_t W,
+                                   uint32_t H, uint32_t x, uint32_t y, const HalfResScale hs, bool sparseProjTex, const Cull cull = Cull(),
+                                   uint32_t* culledTaps = nullptr)
+{
+    // first, so that the fetched texels and fractions are dead before the pressure of the tap loop's setup builds up
+    const f3 rv = randvec_resolve(rvRaw);  // :138
+    const f3 randVec{ fma(2.0f, rv.x, -1.0f), fma(2.0f, rv.y, -1.0f), fma(2.0f, rv.z, -1.0f) };
+
     const float u = ((float)x + 0.5f) * hs.rw2;
     const float v = ((float)y + 0.5f) * hs.rh2;
 
@@ -479,8 +544,6 @@ CRY_HD uint32_t ssao_pixel(const crychic_ssao_constants& cb, const SsaoCentre& c
     const f3 p{ t * PosV.x, t * PosV.y, t * PosV.z };
     const float pzEps = Cull::active ? ssao_cull_threshold(nRaw, p, cb.SurfaceEpsilon) : 0.0f;   // "tap culling"
 
-    const f3 rv = randvec_linear_wrap(randvec, 4.0f * u, 4.0f * v);  // :138
-    const f3 randVec{ fma(2.0f, rv.x, -1.0f), fma(2.0f, rv.y, -1.0f), fma(2.0f, rv.z, -1.0f) };
 
     const float eps = cb.SurfaceEpsilon, fadeEnd = cb.OcclusionFadeEnd;
     const float rFadeLength = rcp(cb.OcclusionFadeEnd - cb.OcclusionFadeStart);  // :100,104: one reciprocal for all taps
@@ -589,6 +652,14 @@ CRY_HD uint32_t ssao_pixel(const crychic_ssao_constants& cb, const SsaoCentre& c
     const float access = 1.0f - occlusionSum;                                    // :195
     const float a2 = access * access, a4 = a2 * a2;                              // :198 pow(access, 6)
     return float_to_unorm16(a4 * a2);
+}
+template <class Depth, class Cull = NoCull>
+CRY_HD uint32_t ssao_pixel(const crychic_ssao_constants& cb, const SsaoCentre& c,
+                           const Depth depth, const uint32_t* __restrict__ randvec, uint32_t W,
+                           uint32_t H, uint32_t x, uint32_t y, const HalfResScale hs, bool sparseProjTex, const Cull cull = Cull(),
+                           uint32_t* culledTaps = nullptr)
+{
+    return ssao_pixel_fetched(cb, c, depth, ssao_pixel_randvec_fetch(randvec, x, y, hs), W, H, x, y, hs, sparseProjTex, cull, culledTaps);
 }
 
 // ---- unoccluded tiles --------------------------------------------------------------------------------------------------
