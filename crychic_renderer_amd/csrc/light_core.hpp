@@ -880,6 +880,56 @@ struct AllLocalLights {
     }
 };
 
+// ---- the tile cull of the local lights ------------------------------------------------------------------------------------------
+// The arithmetic of light_tiles.hpp's light_local_tile, here so that the host build of the bodies (tests/hostsim/host_light.hpp's
+// tiled mode) culls with the kernels' own code.  A tile's box is the merge of its pixels' boxes; a light is admitted when its sphere
+// of radius FalloffEnd, inflated, touches the box.  The guarantee: the cull admits every light whose range test (pbr_point_light,
+// pbr_spot_light: `d > FalloffEnd` skips, so a NaN d or a NaN FalloffEnd does not) some covered pixel of the tile passes.  For finite
+// positions and lights that is the geometry; the rest is stated case by case below.
+struct TileBox { float lo[3], hi[3]; };
+// One pixel's box.  Not covered: empty (lo > hi, the neutral element of the merge).  A covered position with a NaN or an infinite
+// component is all of space: its d is NaN for some lights whatever they are (NaN - p, inf - inf), which no box states, so the tile
+// admits every light and the range test decides per pixel.  No NaN ever enters a box.
+CRY_HD TileBox tile_box_pixel(bool covered, f4a G0)
+{
+    const float big = 3.0e38f, inf = __builtin_inff();
+    const bool finite = __builtin_fabsf(G0.x) < inf && __builtin_fabsf(G0.y) < inf && __builtin_fabsf(G0.z) < inf;
+    const float p[3] = { G0.x, G0.y, G0.z };
+    TileBox b;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        b.lo[c] = covered ? (finite ? p[c] : -inf) : big;
+        b.hi[c] = covered ? (finite ? p[c] : inf) : -big;
+    }
+    return b;
+}
+CRY_HD TileBox tile_box_merge(const TileBox& a, const TileBox& b)
+{
+    TileBox m;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { m.lo[c] = __builtin_fminf(a.lo[c], b.lo[c]); m.hi[c] = __builtin_fmaxf(a.hi[c], b.hi[c]); }
+    return m;
+}
+// Does the box hold a covered pixel?  A tile without one admits nothing.
+CRY_HD bool tile_box_any_covered(const TileBox& b) { return b.lo[0] <= b.hi[0]; }
+// dist(Position, box) <= FalloffEnd, inflated (the per-pixel test is the exact one), with both compares written so that a NaN admits:
+// the selects keep the NaN of a NaN Position component (fmaxf would drop it) and of inf - inf against the box of all space, and
+// !(d2 > r * r) holds for a NaN FalloffEnd.  For finite operands these are max(max(lo - p, p - hi), 0) and d2 <= r * r.
+CRY_HD bool tile_light_touches(const crychic_light& L, const TileBox& b)
+{
+    float d2 = 0.0f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float p = L.Position[c];
+        const float below = b.lo[c] - p, above = p - b.hi[c];
+        float e = below > above ? below : above;
+        e = e < 0.0f ? 0.0f : e;
+        d2 += e * e;
+    }
+    const float r = L.FalloffEnd * 1.0001f + 1.0e-3f;
+    return !(d2 > r * r);
+}
+
 // DeferredShading.hlsl:53-76: cascade selection and the (blended) shadow factor of the first light for one pixel.
 // `abs(distance - radius[j] < 5.0f)` is abs(bool) (Q1), true whenever distance < radius[j]: every pixel nearer than 80 blends
 // cascades j and j+1.

@@ -144,6 +144,13 @@ __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLA
 // against the box (sphere of radius FalloffEnd vs AABB, conservatively inflated) and sets the light's bit in an LDS mask;
 // each pixel finally walks the set bits in ascending index order -- the accumulation order of the un-culled loop -- and
 // applies the exact per-pixel range test, so culling never changes a bit of the result.
+// What that takes (the arithmetic is light_core.hpp's tile_box_* / tile_light_touches, which tests/hostsim runs on the host as
+// well): the cull admits every light whose range test some covered pixel of the tile passes, and the range test skips only on
+// `d > FalloffEnd`, which a NaN on either side does not satisfy.  So a covered position with a NaN or an infinite component makes
+// its tile's box all of space (the tile admits every light; a tile whose covered positions are all NaN is not empty), a light with
+// a NaN FalloffEnd or a NaN Position component is admitted by every tile that covers anything, and +-inf in a light's Position or
+// FalloffEnd goes through the compares as it does per pixel.  Tiles of finite positions cull exactly as they would without these
+// cases; there is one cull pass per tile and no un-culled walk.
 // SPOTS (light_spots_kernel): the spot lights of their own buffer are culled by the same sphere test in the same step into a
 // second mask, and walked after the point lights (the gLights order).  The cull stays spherical: a spot light contributes
 // outside its cone too (the 0.001 floor of PBR.hlsl:142), so only the range test is exact.
@@ -175,50 +182,33 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLA
     f4a G0{ 0, 0, 0, 0 };
     if (covered) G0 = CRY_GBUFFER_TEXEL(g0, idx, h0);
 
-    // 1. tile bounding box of the covered pixels' world positions
-    const float big = 3.0e38f;
-    float lo[3] = { covered ? G0.x : big, covered ? G0.y : big, covered ? G0.z : big };
-    float hi[3] = { covered ? G0.x : -big, covered ? G0.y : -big, covered ? G0.z : -big };
+    // 1. tile bounding box of the covered pixels' world positions (tile_box_pixel: all of space for a non-finite one)
+    TileBox wbox = tile_box_pixel(covered, G0);
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
+    for (int off = 32; off > 0; off >>= 1) {
+        TileBox other;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            lo[c] = __builtin_fminf(lo[c], __shfl_xor(lo[c], off));
-            hi[c] = __builtin_fmaxf(hi[c], __shfl_xor(hi[c], off));
-        }
+        for (int c = 0; c < 3; ++c) { other.lo[c] = __shfl_xor(wbox.lo[c], off); other.hi[c] = __shfl_xor(wbox.hi[c], off); }
+        wbox = tile_box_merge(wbox, other);
+    }
     const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63u) == 0) { for (int c = 0; c < 3; ++c) { s_box[wave][c] = lo[c]; s_box[wave][3 + c] = hi[c]; } }
+    if ((threadIdx.x & 63u) == 0) { for (int c = 0; c < 3; ++c) { s_box[wave][c] = wbox.lo[c]; s_box[wave][3 + c] = wbox.hi[c]; } }
     if (threadIdx.x < kMaxPointLights / 32) s_mask[threadIdx.x] = 0u;
     if (SPOTS && threadIdx.x < kMaxSpotLights / 32) s_spotMask[threadIdx.x] = 0u;
     __syncthreads();
-    float blo[3], bhi[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        blo[c] = __builtin_fminf(__builtin_fminf(s_box[0][c], s_box[1][c]), __builtin_fminf(s_box[2][c], s_box[3][c]));
-        bhi[c] = __builtin_fmaxf(__builtin_fmaxf(s_box[0][3 + c], s_box[1][3 + c]), __builtin_fmaxf(s_box[2][3 + c], s_box[3][3 + c]));
-    }
-    // 2. cull: light l touches the tile if dist(Position, box) <= FalloffEnd (inflated: the per-pixel test is the exact one)
-    auto touches = [&](const crychic_light& L) {
-        float d2 = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float p = L.Position[c];
-            const float e = __builtin_fmaxf(__builtin_fmaxf(blo[c] - p, p - bhi[c]), 0.0f);
-            d2 += e * e;
-        }
-        const float r = L.FalloffEnd * 1.0001f + 1.0e-3f;
-        return d2 <= r * r;
-    };
-    const bool anyCovered = blo[0] <= bhi[0];
-    if (anyCovered) {
+    auto waveBox = [&](int w) { return TileBox{ { s_box[w][0], s_box[w][1], s_box[w][2] }, { s_box[w][3], s_box[w][4], s_box[w][5] } }; };
+    const TileBox box = tile_box_merge(tile_box_merge(waveBox(0), waveBox(1)), tile_box_merge(waveBox(2), waveBox(3)));
+    // 2. cull: light l touches the tile if dist(Position, box) <= FalloffEnd (inflated: the per-pixel test is the exact one; a NaN
+    // on either side admits, as it passes the per-pixel test: tile_light_touches)
+    if (tile_box_any_covered(box)) {
         for (uint32_t l = threadIdx.x; l < P.numPointLights; l += 256u) {
             const crychic_light L = P.pointLights[l];
-            if (touches(L)) atomicOr(&s_mask[l >> 5], 1u << (l & 31u));
+            if (tile_light_touches(L, box)) atomicOr(&s_mask[l >> 5], 1u << (l & 31u));
         }
         if (SPOTS)
             for (uint32_t l = threadIdx.x; l < numSpots; l += 256u) {
                 const crychic_light L = spots[l];
-                if (touches(L)) atomicOr(&s_spotMask[l >> 5], 1u << (l & 31u));
+                if (tile_light_touches(L, box)) atomicOr(&s_spotMask[l >> 5], 1u << (l & 31u));
             }
     }
     __syncthreads();

@@ -207,3 +207,101 @@ def cull_probe_case(seed, W=256, H=160):
         normal[rng.integers(0, H, 40), rng.integers(0, W, 40), 0] = np.nan
         c.ssao_cb.SurfaceEpsilon = float([0.05, 0.0, 0.5, 0.05, 1e-4, 0.05][seed % 6])
     return W, H, c, depth, normal, p["randvec"]
+
+
+# ---- frames for the tiled cull of the local lights (tests/test_light_cull_host.py, tests/test_light_cull_gpu.py) ------------------
+LIGHT_DT = np.dtype([("Strength", "<f4", 3), ("FalloffStart", "<f4"), ("Direction", "<f4", 3), ("FalloffEnd", "<f4"),
+                     ("Position", "<f4", 3), ("SpotPower", "<f4")])        # crychic_light
+CULL_W, CULL_H = 130, 70            # three tile columns (the last 2 pixels wide), a last tile row of 2 rows
+CULL_ROW_RANGES = ((0, 36), (36, 22), (58, 12))      # the third is not anchored on a multiple of the tile height
+CULL_FALLOFF_END = np.array([0.5, 2.0, 4.0, 10.0, 30.0, 0.0, -1.0, np.nan, np.inf], np.float32)
+CULL_FALLOFF_END_P = np.array([0.22, 0.2, 0.15, 0.13, 0.08, 0.05, 0.05, 0.06, 0.06])
+
+
+def lights_from_records(rec):
+    """A ctypes array of the product's Light from a LIGHT_DT record array."""
+    from crychic_renderer_amd._lib import Light
+    rec = np.ascontiguousarray(rec, LIGHT_DT)
+    return (Light * len(rec)).from_buffer_copy(rec.tobytes())
+
+
+def cull_lights(rng, n, eye, far, regular, infinite_end=True):
+    """n local lights: positions half N(0, 20) and half spread along the coherent plane of random_case, FalloffEnd from
+    CULL_FALLOFF_END (infinite_end False: 0.5 in the place of +inf, and no infinite position with a NaN FalloffEnd), FalloffStart from {0, 1, FalloffEnd}, SpotPower from {0, 1, 8, 64}, un-normalised directions, about 1 % of
+    the positions with a NaN component and 1 % with an infinite one.  The first `regular` lights are finite with FalloffEnd 10 or
+    30 and FalloffStart 1 (what the shadow transform builders accept)."""
+    L = np.zeros(n, LIGHT_DT)
+    pos = (rng.standard_normal((n, 3)) * 20.0).astype(np.float32)
+    plane = rng.random(n) < 0.5
+    along = np.stack([eye[0] + rng.uniform(-3.0, 3.0, n), eye[1] - 1.0 + rng.standard_normal(n) * 0.5, eye[2] + 2.0 + rng.random(n) * far], 1)
+    pos[plane] = along[plane].astype(np.float32)
+    L["FalloffEnd"] = rng.choice(CULL_FALLOFF_END, n, p=CULL_FALLOFF_END_P)
+    start = rng.integers(0, 3, n)
+    L["FalloffStart"] = np.where(start == 0, np.float32(0.0), np.where(start == 1, np.float32(1.0), L["FalloffEnd"]))
+    L["Strength"] = rng.choice(np.array([0.0, 0.1, 1.0, 2.4], np.float32), (n, 3))
+    L["Direction"] = (rng.standard_normal((n, 3)) * rng.uniform(0.2, 3.0, (n, 1))).astype(np.float32)
+    L["SpotPower"] = rng.choice(np.array([0.0, 1.0, 8.0, 64.0], np.float32), n)
+    odd = rng.random(n)
+    comp = rng.integers(0, 3, n)
+    for k in np.nonzero(odd < 0.02)[0]:
+        pos[k, comp[k]] = np.nan if odd[k] < 0.01 else (np.inf if odd[k] < 0.015 else -np.inf)
+    if not infinite_end:          # no light that is in range everywhere with a NaN term (light_cull_case)
+        L["FalloffEnd"][np.isinf(L["FalloffEnd"])] = 0.5
+        L["FalloffEnd"][np.isinf(pos).any(1) & np.isnan(L["FalloffEnd"])] = 4.0
+    m = min(regular, n)
+    pos[:m] = along[:m].astype(np.float32)
+    L["FalloffEnd"][:m] = rng.choice(np.array([10.0, 30.0], np.float32), m)
+    L["FalloffStart"][:m] = 1.0
+    L["Position"] = pos
+    return L
+
+
+def light_cull_case(seed, built_lib, n_points=1024, n_spots=1024):
+    """A 130 x 70 frame for the tiled cull: random_case's planes and constants (same seed) with the world positions redrawn -- even
+    seeds coherent (random_case's tilted plane), odd seeds incoherent (N(0, 20) per pixel) -- and non-finite positions put in by
+    tile of the whole frame's 64 x 4 grid: most tiles none, some exactly one, some a few, some all of their covered positions (and
+    one such tile at least per frame); a non-finite position is a NaN in one component, in all three, or +-inf in one.
+    A light with FalloffEnd = +inf is in range everywhere with an attenuation of NaN ((inf - d) / (inf - FalloffStart)), and so is
+    one at an infinite position whose FalloffEnd is NaN (l / d = inf * 0): either turns the radiance of about half of the frame's
+    pixels into NaN -- equal to any NaN, so blind to everything else.  Seeds with seed % 4 in (1, 2) draw such lights (one frame of
+    every (2k, 2k + 1) pair); the others keep about 98 % of their pixels finite.
+    Returns (planes, constants, knobs, point light records, spot light records)."""
+    W, H = CULL_W, CULL_H
+    _, _, planes, c, knobs = random_case(seed, built_lib, size=(W, H))
+    rng = np.random.default_rng(50000 + seed)
+    eye = np.array(list(c.cam.pos), dtype=np.float32)
+    far = float(rng.choice([25.0, 60.0, 120.0]))
+    g0 = planes["g0"].copy()
+    if seed % 2 == 0:
+        yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+        g0[..., 0] = eye[0] + (xx / W - 0.5) * 6.0
+        g0[..., 1] = eye[1] - 1.0 + rng.standard_normal((H, W)).astype(np.float32) * 0.05
+        g0[..., 2] = eye[2] + 2.0 + (1.0 - yy / H) * far
+    else:
+        g0[..., :3] = (rng.standard_normal((H, W, 3)) * 20.0).astype(np.float32)
+    covered = (planes["depth"] & 0xFFFFFF) < 0xFFFFFF
+
+    def spoil(y, x):
+        kind = int(rng.integers(0, 6))
+        if kind < 3:
+            g0[y, x, kind] = np.nan
+        elif kind == 3:
+            g0[y, x, :3] = np.nan
+        else:
+            g0[y, x, int(rng.integers(0, 3))] = np.inf if kind == 4 else -np.inf
+
+    tiles = [(ty, tx) for ty in range((H + 3) // 4) for tx in range((W + 63) // 64) if covered[4 * ty:4 * ty + 4, 64 * tx:64 * tx + 64].any()]
+    forced = {tiles[int(k)]: mode for k, mode in zip(rng.choice(len(tiles), 3, replace=False), ("all", "one", "one"))}
+    for ty, tx in tiles:
+        ys, xs = np.nonzero(covered[4 * ty:4 * ty + 4, 64 * tx:64 * tx + 64])
+        r = rng.random()
+        mode = forced.get((ty, tx)) or ("one" if r < 0.14 else "few" if r < 0.25 else "all" if r < 0.30 else None)
+        if mode == "all":
+            g0[4 * ty + ys, 64 * tx + xs, int(rng.integers(0, 3))] = np.nan
+        elif mode is not None:
+            for k in rng.choice(len(ys), min(len(ys), 1 if mode == "one" else int(rng.integers(2, 7))), replace=False):
+                spoil(4 * ty + ys[k], 64 * tx + xs[k])
+    planes = dict(planes, g0=g0)
+    points = cull_lights(rng, n_points, eye, far, 4, seed % 4 in (1, 2))
+    spots = cull_lights(rng, n_spots, eye, far, 8, seed % 4 in (1, 2))
+    return planes, c, knobs, points, spots

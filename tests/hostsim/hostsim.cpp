@@ -327,6 +327,22 @@ void hs_light(const crychic_pass_constants* cb, const void* g0, const void* g1, 
                pointShadowDim, pointMaps, shadowProj);
 }
 
+// hs_light in host_light.hpp's tiled mode: the local lights culled per 64 x 4 tile with light_local_tile's own arithmetic.
+// tileMasks: ((rows + 3) / 4) * ((W + 63) / 64) tiles, 64 words each (the point lights' mask, then the spot lights').
+void hs_light_tiled(const crychic_pass_constants* cb, const void* g0, const void* g1, const void* g2,
+                    const uint32_t* depth, const uint16_t* ambient, const uint32_t* const shadow[4], uint32_t shadowDim,
+                    const uint8_t* cube, uint32_t cubeDim, uint8_t* out, float* radiance, uint32_t W, uint32_t H,
+                    uint32_t row0, uint32_t rows, int numDirLights, float pcfSearchRadius, uint32_t flags,
+                    const crychic_light* pointLights, uint32_t numPointLights, const crychic_light* spotLights,
+                    uint32_t numSpotLights, uint32_t shadowCount, uint32_t shadowMapDim, const uint32_t* const* shadowMaps,
+                    uint32_t pointShadowCount, uint32_t pointShadowDim, const uint32_t* const* pointMaps, const float* shadowProj,
+                    uint32_t* tileMasks)
+{
+    host_light(cb, g0, g1, g2, depth, ambient, shadow, shadowDim, cube, cubeDim, out, radiance, W, H, row0, rows, numDirLights, pcfSearchRadius, flags,
+               pointLights, numPointLights, spotLights, numSpotLights, shadowCount, shadowMapDim, shadowMaps, pointShadowCount,
+               pointShadowDim, pointMaps, shadowProj, tileMasks);
+}
+
 // The producer passes executed sequentially on the host with the kernels' own bodies (raster_core.hpp): setup in draw
 // order into the same slot numbering as setup_kernel, coverage by min() on the 64-bit key, then the resolve stage
 // (resolve_formats_kernel's: G0..G2 stored through gbuffer_store in the formats of gbufferFlags, no bit = float4).

@@ -130,6 +130,7 @@ class HostSim:
         L.hs_rasterize.restype = i
         L.hs_rasterize.argtypes = [i, vp, vp, vp, u32, vp, u32, vp, u32, u32, u32, i, f, vp, vp, vp, vp, vp, u32, u32, u32]
         L.hs_light.argtypes = LIGHT_ARGTYPES
+        L.hs_light_tiled.argtypes = LIGHT_ARGTYPES + [vp]
         L.hs_spot_shadow_factor.restype = f; L.hs_spot_shadow_factor.argtypes = [vp, u32, vp, vp]
         L.hs_point_shadow_factor.restype = f; L.hs_point_shadow_factor.argtypes = [vp, u32, vp, vp, vp]
         L.hs_point_face.restype = i; L.hs_point_face.argtypes = [vp, vp]
@@ -241,6 +242,22 @@ class HostSim:
         lights: points, spots, maps, cubes, projs, row0, rows, cube_dim as run_light takes them; which kernel family that models
         is light_bind.hpp's choice, as in the library.  Returns (RGBA8, radiance)."""
         return run_light(self.lib.hs_light, cb, p, ambient, num_dir_lights, pcf_radius, flags, formats=True, **lights)
+
+    def light_frame_tiled(self, cb, p, ambient, num_dir_lights, pcf_radius, flags=0, **lights):
+        """light_frame with the local lights culled per 64 x 4 tile as the kernels cull them (host_light.hpp's tiled mode: tiles
+        anchored at row0, box and admitted lights from light_core.hpp's tile_box_* / tile_light_touches).  Returns (RGBA8, radiance,
+        masks): masks[ty, tx, 0] are the 32 words of tile (tx, ty)'s point-light mask and masks[ty, tx, 1] the spot lights', bit
+        l & 31 of word l >> 5 set = light l admitted; ty counts from row0."""
+        H, W = p["depth"].shape
+        row0 = lights.get("row0", 0)
+        rows = H - row0 if lights.get("rows") is None else lights["rows"]
+        masks = np.zeros(((rows + 3) // 4, (W + 63) // 64, 2, 32), np.uint32)
+
+        def fn(*args):
+            self.lib.hs_light_tiled(*args, masks.ctypes.data)
+        fn.argtypes = LIGHT_ARGTYPES
+        out, rad = run_light(fn, cb, p, ambient, num_dir_lights, pcf_radius, flags, formats=True, **lights)
+        return out, rad, masks
 
     def light(self, cb, g0, g1, g2, depth_u32, ambient, shadow_u32, cube_u8, num_dir_lights, pcf_radius, flags=0,
               want_radiance=False, point_lights=None, cube_dim=None, cube_levels=0, **lights):

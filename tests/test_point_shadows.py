@@ -395,18 +395,22 @@ def _point_desc(dev_cubes, projs=None, count=None):
 
 
 def _light(lib, ctx, cb, dev, W, H, flags, points, spots, sdesc, pdesc, ndl=3, radius=0.0, ambient=None, row0=0, rows=None, out=None,
-           rad=None, cube=None, entry="point_shadows"):
+           rad=None, cube=None, entry="point_shadows", shadow_dim=256, cube_dim=32):
+    """One crychic_deferred_light_point_shadows / _spots_shadowed / _spots call (entry "point_shadows" / "spots_shadowed" / "spots")
+    on the planes of dev; shadow_dim / cube_dim: the sizes of dev's cascades and cube map."""
     import torch
     from crychic_renderer_amd.renderer import _ptr, _stream
     rows = H - row0 if rows is None else rows
     out = torch.zeros((H, W, 4), dtype=torch.uint8, device=dev["g0"].device) if out is None else out
     rad = torch.zeros((H, W, 4), dtype=torch.float32, device=dev["g0"].device) if rad is None else rad
     sh = (C.c_void_p * 4)(*[dev["shadow"][k].data_ptr() for k in range(4)])
-    args = [ctx.handle, C.byref(cb), _ptr(dev["g0"]), _ptr(dev["g1"]), _ptr(dev["g2"]), _ptr(dev["depth"]), _ptr(ambient), sh, 256,
-            _ptr(cube if cube is not None else dev["cube"]), 32, _ptr(out), _ptr(rad), W, H, row0, rows, ndl, radius, flags,
+    args = [ctx.handle, C.byref(cb), _ptr(dev["g0"]), _ptr(dev["g1"]), _ptr(dev["g2"]), _ptr(dev["depth"]), _ptr(ambient), sh, shadow_dim,
+            _ptr(cube if cube is not None else dev["cube"]), cube_dim, _ptr(out), _ptr(rad), W, H, row0, rows, ndl, radius, flags,
             _ptr(points[0]), points[1], _ptr(spots[0]), spots[1], None if sdesc is None else C.byref(sdesc)]
     if entry == "point_shadows":
         rc = lib.crychic_deferred_light_point_shadows(*args, None if pdesc is None else C.byref(pdesc), _stream(ctx.device))
+    elif entry == "spots":
+        rc = lib.crychic_deferred_light_spots(*args[:-1], _stream(ctx.device))
     else:
         rc = lib.crychic_deferred_light_spots_shadowed(*args, _stream(ctx.device))
     return rc, out, rad
