@@ -15,6 +15,8 @@ LIGHT_SKY = 1
 LIGHT_CUBE_GLOSS = 0x800      # CRYCHIC_LIGHT_CUBE_GLOSS: the bound chain is prefiltered by roughness
 LIGHT_AMBIENT_SH = 0x8000     # CRYCHIC_LIGHT_AMBIENT_SH: the ambient colour from the SH9 coefficients behind the cube map
 LIGHT_ENV_BRDF = 0x100000     # CRYCHIC_LIGHT_ENV_BRDF: the reflection weighed by the environment BRDF table behind the environment tail
+LIGHT_CUBE_PARALLAX = 0x200000    # CRYCHIC_LIGHT_CUBE_PARALLAX: the reflection lookup box-projected through the probe volume in the environment tail
+CUBE_PROBE_OFFSET, CUBE_PROBE_BYTES = 368, 48     # CRYCHIC_CUBE_PROBE_OFFSET / _BYTES: the probe volume inside the environment tail
 ENV_BRDF_BYTES = 4096         # CRYCHIC_ENV_BRDF_BYTES: 32 x 32 dwords A | B << 16
 CUBE_SH_BYTES = 512           # CRYCHIC_CUBE_SH_BYTES: the environment tail (144 bytes of coefficients, then the projection's scratch)
 # CRYCHIC_GBUFFER_G*_F16: that G-buffer plane holds half4 texels (the flags word of the lighting entries, FrameDesc.flags, and
@@ -173,6 +175,8 @@ PROTOTYPES = {
     "crychic_cube_env_brdf_offset": (_sz, [_u32, _u32]),
     "crychic_cube_chain_env_bytes": (_sz, [_u32, _u32]),
     "crychic_build_env_brdf": (_i, [_vp, _vp, _vp]),
+    "crychic_cube_probe_offset": (_sz, [_u32, _u32]),
+    "crychic_set_cube_probe_volume": (_i, [_vp, _vp, _P(_f), _P(_f), _P(_f), _vp]),
     "crychic_save_ppm": (_i, [C.c_char_p, _vp, _u32, _u32]),
     "crychic_raster_workspace_bytes": (_sz, [C.c_uint64, _u32, _u32]),
     "crychic_raster_status": (_i, [_vp, _vp, _P(_u32)]),

@@ -212,6 +212,14 @@ int check_env_brdf(uint32_t flags, const uint8_t* cube, uint32_t cubeDim)
     return fail(CRYCHIC_E_INVALID_ARG, cry::env_brdf_check_message(c), cry::env_brdf_offset(cubeDim, (flags >> 16) & 15u));
 }
 
+// CRYCHIC_LIGHT_CUBE_PARALLAX: the lookup it goes with and the probe volume in the environment tail, before anything is enqueued.
+int check_parallax(uint32_t flags, const uint8_t* cube, uint32_t cubeDim)
+{
+    const cry::ParallaxCheck c = cry::parallax_check(flags, cube, cubeDim);
+    if (c == cry::ParallaxCheck::Ok) return 0;
+    return fail(CRYCHIC_E_INVALID_ARG, cry::parallax_check_message(c), cry::parallax_probe_offset(cubeDim, (flags >> 16) & 15u));
+}
+
 // With a mip chain the level of detail comes from 2 x 2 pixel quads: a call's rows have to be whole quad rows.  Not so with
 // CRYCHIC_LIGHT_CUBE_GLOSS, where it comes from the pixel's roughness.
 int check_chain_rows(const cry::LightParams& P, uint32_t row0, uint32_t rows, uint32_t H)
@@ -242,6 +250,7 @@ int deferred_light_impl(crychic_ctx* ctx, const crychic_pass_constants* cb, cons
     if (int rc = fill_light_params(P, cb, shadow_dev, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags)) return rc;
     if (int rc = check_ambient_sh(flags, cube_dev, cubeDim)) return rc;
     if (int rc = check_env_brdf(flags, cube_dev, cubeDim)) return rc;
+    if (int rc = check_parallax(flags, cube_dev, cubeDim)) return rc;
     if (int rc = check_chain_rows(P, row0, rows, H)) return rc;
     CRY_HIP(cry::launch_light(P, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, cube_dev, out_rgba8_dev, radiance_out_dev,
                               row0, rows, (hipStream_t)stream, spot_lights_dev, numSpotLights, &S, &PS));
@@ -440,6 +449,7 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
                                    f->pcfSearchRadius, f->flags)) return rc;
     if (int rc = check_ambient_sh(f->flags, f->cube_dev, f->cubeDim)) return rc;
     if (int rc = check_env_brdf(f->flags, f->cube_dev, f->cubeDim)) return rc;
+    if (int rc = check_parallax(f->flags, f->cube_dev, f->cubeDim)) return rc;
     cry::SpotShadows S;
     cry::PointShadows PS;
     if (int rc = bind_local_lights(P, S, PS, passCB, f->point_lights_dev, f->numPointLights, spots.lights, spots.count, spots.shadows,
@@ -786,6 +796,20 @@ int crychic_build_env_brdf(crychic_ctx* ctx, void* table_dev, void* stream)
     if (!table_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
     if (reinterpret_cast<uintptr_t>(table_dev) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "environment BRDF table is not 4-byte aligned");
     CRY_HIP(cry::launch_env_brdf(table_dev, (hipStream_t)stream));
+    return 0;
+}
+
+size_t crychic_cube_probe_offset(uint32_t dim, uint32_t levels) { return cry::parallax_probe_offset(dim, levels); }
+
+int crychic_set_cube_probe_volume(crychic_ctx* ctx, void* tail_dev, const float pos[3], const float boxMin[3], const float boxMax[3],
+                                  void* stream)
+{
+    if (int rc = bind(ctx)) return rc;
+    if (!tail_dev || !pos || !boxMin || !boxMax) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (reinterpret_cast<uintptr_t>(tail_dev) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "environment tail is not 4-byte aligned");
+    if (!cry::probe_volume_valid(pos, boxMin, boxMax))
+        return fail(CRYCHIC_E_INVALID_ARG, "probe volume: every value finite and boxMin < pos < boxMax in every component");
+    CRY_HIP(cry::launch_cube_probe_volume(tail_dev, pos, boxMin, boxMax, (hipStream_t)stream));
     return 0;
 }
 

@@ -69,4 +69,28 @@ hipError_t launch_cube_sh(const uint8_t* level, uint32_t d, void* tail, hipStrea
     return hipGetLastError();
 }
 
+// crychic_set_cube_probe_volume: the probe volume of the box-projected reflection lookup into tail bytes
+// [CRYCHIC_CUBE_PROBE_OFFSET, + CRYCHIC_CUBE_PROBE_BYTES).  The twelve floats arrive by value in the kernel's arguments; lane k < 12
+// stores dword k with an ordinary vector store.
+struct ProbeVolumeArgs { float v[12]; };
+__global__ __launch_bounds__(64) void cube_probe_volume_kernel(float* __restrict__ probe, ProbeVolumeArgs a)
+{
+    if (threadIdx.x < 12u) {
+        float x = a.v[0];
+#pragma unroll
+        for (uint32_t k = 1; k < 12u; ++k) x = threadIdx.x == k ? a.v[k] : x;      // selects: the arguments stay in scalar registers
+        probe[threadIdx.x] = x;
+    }
+}
+
+hipError_t launch_cube_probe_volume(void* tail, const float pos[3], const float boxMin[3], const float boxMax[3], hipStream_t stream)
+{
+    ProbeVolumeArgs a;
+    for (int k = 0; k < 3; ++k) { a.v[k] = pos[k]; a.v[4 + k] = boxMin[k]; a.v[8 + k] = boxMax[k]; }
+    a.v[3] = a.v[7] = a.v[11] = 0.0f;
+    float* probe = reinterpret_cast<float*>(static_cast<uint8_t*>(tail) + CRYCHIC_CUBE_PROBE_OFFSET);
+    hipLaunchKernelGGL(cube_probe_volume_kernel, dim3(1), dim3(64), 0, stream, probe, a);
+    return hipGetLastError();
+}
+
 }  // namespace cry

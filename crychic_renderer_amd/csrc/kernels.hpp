@@ -77,6 +77,9 @@ hipError_t launch_cube_prefilter(const uint8_t* src, uint8_t* dst, uint32_t dim,
 // cube_sh.hip: the SH9 irradiance coefficients of the six d x d faces at `level` into the environment tail `tail`
 // (cube_sh_core.hpp); three launches on `stream`.  The caller has checked d, the alignments and the overlap.
 hipError_t launch_cube_sh(const uint8_t* level, uint32_t d, void* tail, hipStream_t stream);
+// ... and the probe volume of the box-projected reflection lookup (pos, boxMin, boxMax as three float4) into bytes [368, 416) of
+// the environment tail `tail`; one launch on `stream`.  The caller has checked the pointers, the alignment and the values.
+hipError_t launch_cube_probe_volume(void* tail, const float pos[3], const float boxMin[3], const float boxMax[3], hipStream_t stream);
 
 // env_brdf.hip: the 32 x 32 environment BRDF table (env_brdf_core.hpp) into the 4096 bytes at `table`; one launch on `stream`.  The
 // caller has checked the pointer and its alignment.

@@ -120,6 +120,38 @@ inline const char* env_brdf_check_message(EnvBrdfCheck c)
     }
 }
 
+// CRYCHIC_LIGHT_CUBE_PARALLAX: the same for the box-projected reflection lookup.  The probe volume sits in the environment tail.
+enum class ParallaxCheck { Ok, NeedsGlossChain, NullCube, MisalignedProbe };
+inline size_t parallax_probe_offset(uint32_t cubeDim, uint32_t levels) { return ambient_sh_offset(cubeDim, levels) + CRYCHIC_CUBE_PROBE_OFFSET; }
+inline ParallaxCheck parallax_check(uint32_t flags, const void* cube, uint32_t cubeDim)
+{
+    if (!(flags & CRYCHIC_LIGHT_CUBE_PARALLAX)) return ParallaxCheck::Ok;
+    const uint32_t levels = (flags >> 16) & 15u;
+    if (levels < 2u || !(flags & CRYCHIC_LIGHT_CUBE_GLOSS)) return ParallaxCheck::NeedsGlossChain;
+    if (!cube) return ParallaxCheck::NullCube;
+    if ((reinterpret_cast<uintptr_t>(cube) + parallax_probe_offset(cubeDim, levels)) & 3u) return ParallaxCheck::MisalignedProbe;
+    return ParallaxCheck::Ok;
+}
+// The message of a refusal (a printf format; MisalignedProbe takes the probe volume's offset as %zu), shared with the host harness.
+inline const char* parallax_check_message(ParallaxCheck c)
+{
+    switch (c) {
+    case ParallaxCheck::NeedsGlossChain:
+        return "CRYCHIC_LIGHT_CUBE_PARALLAX needs a prefiltered chain: CRYCHIC_LIGHT_CUBE_LEVELS(n) with n > 1 and CRYCHIC_LIGHT_CUBE_GLOSS";
+    case ParallaxCheck::NullCube: return "CRYCHIC_LIGHT_CUBE_PARALLAX: null cube map";
+    case ParallaxCheck::MisalignedProbe: return "CRYCHIC_LIGHT_CUBE_PARALLAX: the probe volume at cube_dev + %zu is not 4-byte aligned";
+    default: return "";
+    }
+}
+// crychic_set_cube_probe_volume's arguments: finite, and boxMin < pos < boxMax strictly in every component (a NaN fails).
+inline bool probe_volume_valid(const float pos[3], const float boxMin[3], const float boxMax[3])
+{
+    const float inf = __builtin_inff();
+    for (int k = 0; k < 3; ++k)
+        if (!(__builtin_fabsf(boxMin[k]) < inf && __builtin_fabsf(boxMax[k]) < inf && boxMin[k] < pos[k] && pos[k] < boxMax[k])) return false;
+    return true;
+}
+
 // ---- which kernels serve a lighting call -------------------------------------------------------------------------
 // One family per set of kernel arguments; ZERO_RADIUS and the LightVariant below select the instantiation inside every family.
 enum class LightFamily {
@@ -131,7 +163,8 @@ enum class LightFamily {
     PointShadows,     // light_point_shadows_kernel: PointShadowOf on the point lights, and the spot lights with SpotShadowOf even at a
                       // spot shadow count of 0 (factor 1)
     // The general family (light_general.hip): every call with a half4 plane (CRYCHIC_GBUFFER_G*_F16),
-    // CRYCHIC_LIGHT_CUBE_GLOSS, CRYCHIC_LIGHT_AMBIENT_SH or CRYCHIC_LIGHT_ENV_BRDF.  Planes of any format mix and FIX compiled in;
+    // CRYCHIC_LIGHT_CUBE_GLOSS, CRYCHIC_LIGHT_AMBIENT_SH or CRYCHIC_LIGHT_ENV_BRDF (CRYCHIC_LIGHT_CUBE_PARALLAX comes with the gloss
+    // flag).  Planes of any format mix and FIX compiled in;
     // the LightVariant below picks the instantiation.
     FormatsFrame,     // light_general_kernel: no local light
     FormatsLocal,     // light_general_local_kernel: local lights of whatever kind; both shadow functors whatever the counts
@@ -164,16 +197,17 @@ constexpr bool light_family_point_shadows(LightFamily f) { return f == LightFami
 // The policies a call's light_pixel is instantiated with (light_core.hpp): the one place that turns flags into them.  The kernels of
 // kernels.hip know the lookup alone (their MIPS parameter: DerivativeChain or Level0, no flag of the other two set); the general
 // family and the host build of the bodies (tests/hostsim/host_light.hpp) go through light_variant_visit.
-enum class CubeLookup { Level0, DerivativeChain, Gloss };      // CubeLevel0 / CubeChain / CubeGloss
+enum class CubeLookup { Level0, DerivativeChain, Gloss };      // CubeLevel0 / CubeChain / CubeGloss (with parallax: CubeGlossBox)
 struct LightVariant {
     CubeLookup lookup;
     bool ambientSH;        // AmbientSH, else AmbientConst
     bool splitSum;         // SpecularSplitSum, else SpecularRef
+    bool parallax;         // CubeGlossBox in place of CubeGloss (CRYCHIC_LIGHT_CUBE_PARALLAX)
 };
 inline LightVariant light_variant(uint32_t flags, uint32_t cubeLevels)
 {
     const CubeLookup lookup = (flags & CRYCHIC_LIGHT_CUBE_GLOSS) ? CubeLookup::Gloss : cubeLevels > 1u ? CubeLookup::DerivativeChain : CubeLookup::Level0;
-    return LightVariant{ lookup, (flags & CRYCHIC_LIGHT_AMBIENT_SH) != 0, (flags & CRYCHIC_LIGHT_ENV_BRDF) != 0 };
+    return LightVariant{ lookup, (flags & CRYCHIC_LIGHT_AMBIENT_SH) != 0, (flags & CRYCHIC_LIGHT_ENV_BRDF) != 0, (flags & CRYCHIC_LIGHT_CUBE_PARALLAX) != 0 };
 }
 // Byte offset behind the cube map that the kernels of a variant with an environment term take after row1 (one argument, so that
 // the table and the coefficient block CRYCHIC_CUBE_SH_BYTES before it cost one address): the table's with the split sum, else the
@@ -183,26 +217,37 @@ inline size_t light_variant_tail(const LightVariant& v, uint32_t cubeDim, uint32
     return v.splitSum ? env_brdf_offset(cubeDim, cubeLevels) : ambient_sh_offset(cubeDim, cubeLevels);
 }
 // f(Cube(), Ambient(), Specular()) for the variant's policies (value-initialised tags: take their types), once; false and no call
-// for a combination no kernel exists for -- SH with the derivative chain, the split sum without the gloss lookup (the entries of
-// api.cpp refuse both: ambient_sh_check, env_brdf_check).  Seven combinations.
+// for a combination no kernel exists for -- SH with the derivative chain, the split sum or the box projection without the gloss
+// lookup (the entries of api.cpp refuse them: ambient_sh_check, env_brdf_check, parallax_check).  Eleven combinations: the seven
+// without the box projection, and gloss x {const, SH} x {ref, split sum} with it (CubeGlossBox).  The one switch.
 template <class F>
-inline bool light_variant_visit(const LightVariant& v, F&& f)
+inline bool light_variant_visit_all(const LightVariant& v, F&& f)
 {
+    auto gloss = [&](auto c) {
+        if (v.splitSum) { if (v.ambientSH) f(c, AmbientSH(), SpecularSplitSum()); else f(c, AmbientConst(), SpecularSplitSum()); }
+        else { if (v.ambientSH) f(c, AmbientSH(), SpecularRef()); else f(c, AmbientConst(), SpecularRef()); }
+    };
     switch (v.lookup) {
     case CubeLookup::Level0:
-        if (v.splitSum) return false;
+        if (v.splitSum || v.parallax) return false;
         if (v.ambientSH) f(CubeLevel0(), AmbientSH(), SpecularRef()); else f(CubeLevel0(), AmbientConst(), SpecularRef());
         return true;
     case CubeLookup::DerivativeChain:
-        if (v.ambientSH || v.splitSum) return false;
+        if (v.ambientSH || v.splitSum || v.parallax) return false;
         f(CubeChain(), AmbientConst(), SpecularRef());
         return true;
     case CubeLookup::Gloss:
-        if (v.splitSum) { if (v.ambientSH) f(CubeGloss(), AmbientSH(), SpecularSplitSum()); else f(CubeGloss(), AmbientConst(), SpecularSplitSum()); }
-        else { if (v.ambientSH) f(CubeGloss(), AmbientSH(), SpecularRef()); else f(CubeGloss(), AmbientConst(), SpecularRef()); }
+        if (v.parallax) gloss(CubeGlossBox()); else gloss(CubeGloss());
         return true;
     }
     return false;
+}
+// The seven combinations without the box projection, for a caller that cannot hand a probe volume over (tests/hostsim/host_light.hpp):
+// false and no call for a parallax variant.
+template <class F>
+inline bool light_variant_visit(const LightVariant& v, F&& f)
+{
+    return !v.parallax && light_variant_visit_all(v, static_cast<F&&>(f));
 }
 
 }  // namespace cry

@@ -683,6 +683,54 @@ struct CubeGloss {
     CRY_HD f4 resolve(const LightParams&, const uint32_t* __restrict__, const Fetch& f) const { return cube_trilinear_resolve<false>(f); }
 };
 CRY_HD CubeGloss cube_gloss(const LightParams& P, float roughness) { return CubeGloss{ saturate(roughness) * (float)(P.cubeLevels - 1u) }; }
+// ... or that chain looked up along the box-projected direction (CRYCHIC_LIGHT_CUBE_PARALLAX): the reflection
+// ray from the pixel's own position is cut with the probe volume's box, and the lookup takes the direction from the capture position
+// to the hit point.  The volume is the twelve floats at tail offset CRYCHIC_CUBE_PROBE_OFFSET behind the cube map -- the same address
+// for every lane, so probe_load's loads are scalar loads; the tile bodies issue them before the depth and G-buffer loads
+// (light_tiles.hpp), so that they are back long before the gathers they feed.
+struct ProbeVolume { f3 c, bmin, bmax; };
+CRY_HD ProbeVolume probe_load(const float* __restrict__ v)
+{
+    return ProbeVolume{ f3{ v[0], v[1], v[2] }, f3{ v[4], v[5], v[6] }, f3{ v[8], v[9], v[10] } };
+}
+// Where the volume has to have arrived: an empty statement that reads the nine values as scalar registers.  Placed behind the issue
+// of the depth load, it keeps the scalar loads from sinking to their use in front of the cube gathers (where their round trip
+// would be exposed); the wait it costs runs inside the depth load's own, much longer one.
+CRY_HD void probe_pin(ProbeVolume& v)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+s"(v.c.x), "+s"(v.c.y), "+s"(v.c.z), "+s"(v.bmin.x), "+s"(v.bmin.y), "+s"(v.bmin.z), "+s"(v.bmax.x), "+s"(v.bmax.y), "+s"(v.bmax.z));
+#else
+    (void)v;
+#endif
+}
+// The correction (crychic_hip.h "probe volume"): t = the nearest exit through the face each usable component heads for, clamped to
+// 0; a component that is zero, subnormal or NaN is skipped, a NaN t_k loses, and with nothing usable the direction stays r.
+CRY_HD f3 probe_project(const ProbeVolume& v, f3 p, f3 r)
+{
+    const float inf = __builtin_inff(), tiny = u2f(0x00800000u);        // 2^-126
+    const float tx = ((r.x < 0.0f ? v.bmin.x : v.bmax.x) - p.x) * rcp(r.x);
+    const float ty = ((r.y < 0.0f ? v.bmin.y : v.bmax.y) - p.y) * rcp(r.y);
+    const float tz = ((r.z < 0.0f ? v.bmin.z : v.bmax.z) - p.z) * rcp(r.z);
+    float t = inf;
+    t = ((__builtin_fabsf(r.x) >= tiny) & (tx < t)) ? tx : t;
+    t = ((__builtin_fabsf(r.y) >= tiny) & (ty < t)) ? ty : t;
+    t = ((__builtin_fabsf(r.z) >= tiny) & (tz < t)) ? tz : t;
+    t = maxnn(t, 0.0f);
+    const f3 h{ fma(r.x, t, p.x), fma(r.y, t, p.y), fma(r.z, t, p.z) };
+    const bool usable = t < inf;
+    return f3{ usable ? h.x - v.c.x : r.x, usable ? h.y - v.c.y : r.y, usable ? h.z - v.c.z : r.z };
+}
+struct CubeGlossBox {
+    float lod;
+    ProbeVolume probe;
+    typedef CubeTrilinearFetch Fetch;
+    CRY_HD f3 direction(f3 posW, f3 r) const { return probe_project(probe, posW, r); }
+    CRY_HD Fetch fetch(const LightParams& P, const uint32_t* __restrict__ cube, f3 r) const { return cube_trilinear_fetch(cube, P.cubeDim, P.cubeLevels, r, lod); }
+    CRY_HD f4 resolve(const LightParams&, const uint32_t* __restrict__, const Fetch& f) const { return cube_trilinear_resolve<false>(f); }
+};
+// Both lookups of a prefiltered chain: what the split-sum weight goes with.
+template <class Cube> constexpr bool kGlossLookup = std::is_same_v<Cube, CubeGloss> || std::is_same_v<Cube, CubeGlossBox>;
 // `flat` for a set of lanes: on the device a vote of the lanes that are active at the call, on the host the lane's own answer
 CRY_HD bool cube_chain_flat(float lod)
 {
@@ -693,11 +741,12 @@ CRY_HD bool cube_chain_flat(float lod)
 #endif
 }
 // The lookup of a pixel as a kernel of that policy hands it to light_pixel: `roughness` picks CubeGloss's level, `lod` (the quad's
-// derivatives) CubeChain's; CubeLevel0 takes neither.
+// derivatives) CubeChain's; CubeLevel0 takes neither.  `probe`: the volume CubeGlossBox projects with, loaded by the caller.
 template <class Cube>
-CRY_HD Cube lookup_for(const LightParams& P, float roughness, float lod = 0.0f)
+CRY_HD Cube lookup_for(const LightParams& P, float roughness, float lod = 0.0f, const ProbeVolume& probe = ProbeVolume())
 {
     if constexpr (std::is_same_v<Cube, CubeGloss>) return cube_gloss(P, roughness);
+    else if constexpr (std::is_same_v<Cube, CubeGlossBox>) return CubeGlossBox{ cube_gloss(P, roughness).lod, probe };
     else if constexpr (std::is_same_v<Cube, CubeChain>) return CubeChain{ lod, cube_chain_flat(lod) };
     else return CubeLevel0();
 }
@@ -1237,7 +1286,9 @@ CRY_HD f4 light_pixel(const LightParams& P, f4a G0, f4a G1, f4a G2, const uint16
     const bool hasAO = ambient != nullptr;
     const AmbientPairs af = ambient_fetch_projected(P, ambient, hasAO, (const uint16_t*)cube, posW);
     const f3 r = reflect3(f3{ -view.x, -view.y, -view.z }, normalW);  // :94
-    const typename Cube::Fetch cf = cubeLookup.fetch(P, cube, r);   // :95
+    f3 rl = r;                                                       // CubeGlossBox: the lookup alone takes the projected direction
+    if constexpr (std::is_same_v<Cube, CubeGlossBox>) rl = cubeLookup.direction(posW, r);
+    const typename Cube::Fetch cf = cubeLookup.fetch(P, cube, rl);  // :95
     const typename Ambient::Coeffs shc = ambientTerm.load();         // AmbientSH: 27 scalar loads, in flight with the gathers
     [[maybe_unused]] typename Specular::Fetch sf{};
     if constexpr (Specular::kSplitSum) sf = specTerm.fetch(dot3(normalW, view), roughness);   // two 8-byte loads, in flight with the gathers

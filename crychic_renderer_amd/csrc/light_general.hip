@@ -1,10 +1,11 @@
 // light_general.hip -- the general family of the deferred lighting kernels: light_tiles.hpp's bodies over
 // `const void*` planes of any format mix (each plane's format is a scalar branch on a bit of P.flags at the load: light_core.hpp
 // gbuffer_load; no format bit: float4), FIX compiled in, and for a call with local lights both shadow functors whatever the counts.
-// Every call with a CRYCHIC_GBUFFER_G*_F16 bit, CRYCHIC_LIGHT_CUBE_GLOSS, CRYCHIC_LIGHT_AMBIENT_SH or CRYCHIC_LIGHT_ENV_BRDF comes
-// here (light_bind.hpp light_family), so no kernel of kernels.hip carries a trace of them.  What distinguishes the instantiations is
+// Every call with a CRYCHIC_GBUFFER_G*_F16 bit, CRYCHIC_LIGHT_CUBE_GLOSS (with or without CRYCHIC_LIGHT_CUBE_PARALLAX),
+// CRYCHIC_LIGHT_AMBIENT_SH or CRYCHIC_LIGHT_ENV_BRDF comes here (light_bind.hpp light_family), so no kernel of kernels.hip carries a trace of them.  What distinguishes the instantiations is
 // the LightVariant of light_bind.hpp: the cube lookup, the ambient term and the weight of the reflection.  Seven variants x
-// ZERO_RADIUS x (frame | local) = 28 kernels.
+// ZERO_RADIUS x (frame | local) = 28 kernels, and four more variants with the box-projected lookup (CRYCHIC_LIGHT_CUBE_PARALLAX,
+// DESIGN.md section 18): 16 kernels.
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "kernels.hpp"
@@ -33,6 +34,17 @@ __device__ __forceinline__ Specular split_sum_at(const uint32_t* __restrict__ cu
         return SpecularRef{};
 }
 
+// CubeGlossBox: the probe volume sits CRYCHIC_CUBE_PROBE_OFFSET into the environment tail, which starts where the coefficient block
+// does; every box variant takes the Tail argument, whatever its ambient term and weight.
+template <class Cube, class Specular>
+__device__ __forceinline__ const float* probe_at(const uint32_t* __restrict__ cube, size_t tail = 0)
+{
+    if constexpr (std::is_same_v<Cube, CubeGlossBox>)
+        return reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(cube) + (Specular::kSplitSum ? tail - CRYCHIC_CUBE_SH_BYTES : tail) + CRYCHIC_CUBE_PROBE_OFFSET);
+    else
+        return nullptr;
+}
+
 // A frame without local lights.  Never the benchmark's kernel.
 template <bool ZERO_RADIUS, class Cube, class Ambient, class Specular, class... Tail>
 __global__ __launch_bounds__(256) void light_general_kernel(LightParams P, const void* __restrict__ g0,
@@ -44,7 +56,7 @@ __global__ __launch_bounds__(256) void light_general_kernel(LightParams P, const
 {
     light_frame_tile<ZERO_RADIUS, true, Cube, void, Ambient, Specular>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1,
                                                                        ambient_at<Ambient, Specular>(cube, tail...),
-                                                                       split_sum_at<Specular>(cube, tail...));
+                                                                       split_sum_at<Specular>(cube, tail...), probe_at<Cube, Specular>(cube, tail...));
 }
 
 // Every frame with local lights of whatever kind: counts of 0 are settled at run time (no spot lights: an empty mask; no shadows:
@@ -63,7 +75,7 @@ __global__ __launch_bounds__(256) void light_general_local_kernel(LightParams P,
     light_local_tile<ZERO_RADIUS, Cube, true, true, true, void, Ambient, Specular>(P, g0, g1, g2, depth, ambient, cube, out, radiance, row0, row1,
                                                                                    s_box, s_mask, spots, numSpots, s_spotMask, &shadows,
                                                                                    &pointShadows, ambient_at<Ambient, Specular>(cube, tail...),
-                                                                                   split_sum_at<Specular>(cube, tail...));
+                                                                                   split_sum_at<Specular>(cube, tail...), probe_at<Cube, Specular>(cube, tail...));
 }
 static_assert(sizeof(LightParams) + sizeof(SpotShadows) + sizeof(PointShadows) + 10 * sizeof(void*) + 3 * sizeof(uint32_t) <= 4096,
               "light_general_local_kernel's arguments exceed 4 KiB");
@@ -80,7 +92,7 @@ hipError_t launch_light_general(const LightParams& P, const void* g0, const void
     if (v.lookup == CubeLookup::Gloss && P.cubeLevels < 2u) return hipErrorInvalidValue;
     if (v.lookup == CubeLookup::DerivativeChain && (row0 & 1u)) return hipErrorInvalidValue;
     const size_t tail = light_variant_tail(v, P.cubeDim, P.cubeLevels);
-    if ((v.ambientSH || v.splitSum) && ((reinterpret_cast<uintptr_t>(cube) + tail) & 3u)) return hipErrorInvalidValue;
+    if ((v.ambientSH || v.splitSum || v.parallax) && ((reinterpret_cast<uintptr_t>(cube) + tail) & 3u)) return hipErrorInvalidValue;
     const dim3 grid = grid_for(P.W, rows);
     const bool local = P.numPointLights || numSpots;
     // one kernel of <z, Cube, Ambient, Specular, decltype(t)...>: the frame's or the local one, whose own arguments follow the tail
@@ -93,11 +105,11 @@ hipError_t launch_light_general(const LightParams& P, const void* g0, const void
             hipLaunchKernelGGL((light_general_kernel<z, decltype(c), decltype(a), decltype(s), decltype(t)...>), grid, dim3(256), 0, stream, P,
                                g0, g1, g2, depth, ambient, (const uint32_t*)cube, (uint32_t*)out, (f4a*)radiance, row0, row0 + rows, t...);
     };
-    const bool served = light_variant_visit(v, [&](auto c, auto a, auto s) {
+    const bool served = light_variant_visit_all(v, [&](auto c, auto a, auto s) {
         auto by_radius = [&](auto... t) {
             if (P.pcfSearchRadius == 0.0f) launch(std::true_type{}, c, a, s, t...); else launch(std::false_type{}, c, a, s, t...);
         };
-        if constexpr (decltype(a)::kSH || decltype(s)::kSplitSum) by_radius(tail); else by_radius();
+        if constexpr (decltype(a)::kSH || decltype(s)::kSplitSum || std::is_same_v<decltype(c), CubeGlossBox>) by_radius(tail); else by_radius();
     });
     return served ? hipGetLastError() : hipErrorInvalidValue;
 }

@@ -83,15 +83,21 @@ __device__ __forceinline__ float quad_reflection_lod(const LightParams& P, bool 
 // CubeGloss: the reflection lookup takes the chain at the level of the pixel's roughness; the pixels keep the 64 x 1 footprint of a
 // wavefront, and the sky reads level 0.
 // Ambient (never with CubeChain): AmbientSH takes the ambient colour from the coefficient block behind the cube map.
-// Specular (always with CubeGloss): SpecularSplitSum weighs the reflection by the table behind the environment tail.
+// Specular (always with CubeGloss or CubeGlossBox): SpecularSplitSum weighs the reflection by the table behind the environment tail.
+// CubeGlossBox: CubeGloss along the direction projected through the probe volume at probeVolume (twelve floats behind the tail).
 // light_bind.hpp's light_variant_visit lists the combinations that exist (light_general.hip instantiates them).
 template <bool ZERO_RADIUS, bool FIX, class Cube, class PLANE, class Ambient = AmbientConst, class Specular = SpecularRef>
 __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLANE* __restrict__ g0, const PLANE* __restrict__ g1,
                                                  const PLANE* __restrict__ g2, const uint32_t* __restrict__ depth,
                                                  const uint16_t* __restrict__ ambient, const uint32_t* __restrict__ cube,
                                                  uint32_t* __restrict__ out, f4a* __restrict__ radiance, uint32_t row0, uint32_t row1,
-                                                 Ambient ambientTerm = Ambient(), Specular specTerm = Specular())
+                                                 Ambient ambientTerm = Ambient(), Specular specTerm = Specular(),
+                                                 const float* __restrict__ probeVolume = nullptr)
 {
+    // CubeGlossBox: the volume's scalar loads go out first and are pinned behind the issue of the depth load, whose round trip they
+    // overlap (probe_pin)
+    [[maybe_unused]] ProbeVolume probe{};
+    if constexpr (std::is_same_v<Cube, CubeGlossBox>) probe = probe_load(probeVolume);
     const uint32_t h0 = P.flags & CRYCHIC_GBUFFER_G0_F16, h1 = P.flags & CRYCHIC_GBUFFER_G1_F16, h2 = P.flags & CRYCHIC_GBUFFER_G2_F16;
     uint32_t bx, by;
     tile_origin<0>(bx, by);
@@ -120,14 +126,22 @@ __device__ __forceinline__ void light_frame_tile(const LightParams& P, const PLA
     f4 lit;
     // coverage: the reference re-rasterises the opaque items with LESS against depth cleared to 1.0
     // (CRYCHIC.cpp:248,273) -- exactly the pixels whose normal/depth pass depth is below the clear value.
-    if ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu) {
-        static_assert(!Specular::kSplitSum || std::is_same_v<Cube, CubeGloss>, "the split-sum weight goes with the gloss lookup");
+    bool coveredPixel;
+    if constexpr (std::is_same_v<Cube, CubeGlossBox>) {
+        const uint32_t z = depth[idx];
+        probe_pin(probe);
+        coveredPixel = (z & 0x00FFFFFFu) < 0x00FFFFFFu;
+    } else {
+        coveredPixel = (depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu;
+    }
+    if (coveredPixel) {
+        static_assert(!Specular::kSplitSum || kGlossLookup<Cube>, "the split-sum weight goes with the gloss lookup");
         // the reference as written keeps its texel loads as argument expressions (see CRY_GBUFFER_TEXEL): naming G1 moves its code
         if constexpr (std::is_same_v<Cube, CubeLevel0> && !Ambient::kSH && !Specular::kSplitSum) {
             lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), CRY_GBUFFER_TEXEL(g1, idx, h1), CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube);
         } else {
             const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
-            lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX, Cube, Ambient, Specular>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, NoPointLights(), lookup_for<Cube>(P, G1.w), ambientTerm, specTerm);
+            lit = light_pixel<ZERO_RADIUS, NoPointLights, FIX, Cube, Ambient, Specular>(P, CRY_GBUFFER_TEXEL(g0, idx, h0), G1, CRY_GBUFFER_TEXEL(g2, idx, h2), ambient, cube, NoPointLights(), lookup_for<Cube>(P, G1.w, 0.0f, probe), ambientTerm, specTerm);
         }
     } else if (P.flags & CRYCHIC_LIGHT_SKY) {
         lit = sky_pixel(P, cube, x, y);
@@ -168,8 +182,10 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLA
                                                  float (*s_box)[6], uint32_t* s_mask, const crychic_light* __restrict__ spots,
                                                  uint32_t numSpots, uint32_t* s_spotMask, const SpotShadows* shadows = nullptr,
                                                  const PointShadows* pointShadows = nullptr, Ambient ambientTerm = Ambient(),
-                                                 Specular specTerm = Specular())
+                                                 Specular specTerm = Specular(), const float* __restrict__ probeVolume = nullptr)
 {
+    [[maybe_unused]] ProbeVolume probe{};                  // CubeGlossBox: as in light_frame_tile, ahead of the depth load and the cull
+    if constexpr (std::is_same_v<Cube, CubeGlossBox>) probe = probe_load(probeVolume);
     uint32_t bx, by;
     tile_origin<0>(bx, by);
     by = light_dispatch_row(by, gridDim.y);               // the band order of dispatch_order.hpp (measured best: the natural one)
@@ -177,7 +193,14 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLA
     light_tile_pixel<kQuads<Cube>>(bx, by, row0, x, y);     // CubeChain: 32 x 2 pixels per wavefront (quads inside a wavefront)
     const bool inFrame = (x < P.W) && (y < row1);
     const uint32_t idx = inFrame ? y * P.W + x : 0u;
-    const bool covered = inFrame && ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu);
+    bool covered;
+    if constexpr (std::is_same_v<Cube, CubeGlossBox>) {
+        const uint32_t z = depth[idx];
+        probe_pin(probe);
+        covered = inFrame && ((z & 0x00FFFFFFu) < 0x00FFFFFFu);
+    } else {
+        covered = inFrame && ((depth[idx] & 0x00FFFFFFu) < 0x00FFFFFFu);
+    }
     const uint32_t h0 = P.flags & CRYCHIC_GBUFFER_G0_F16, h1 = P.flags & CRYCHIC_GBUFFER_G1_F16, h2 = P.flags & CRYCHIC_GBUFFER_G2_F16;
     f4a G0{ 0, 0, 0, 0 };
     if (covered) G0 = CRY_GBUFFER_TEXEL(g0, idx, h0);
@@ -255,10 +278,10 @@ __device__ __forceinline__ void light_local_tile(const LightParams& P, const PLA
                 }
             }
         };
-        static_assert(!Specular::kSplitSum || std::is_same_v<Cube, CubeGloss>, "the split-sum weight goes with the gloss lookup");
+        static_assert(!Specular::kSplitSum || kGlossLookup<Cube>, "the split-sum weight goes with the gloss lookup");
         const f4a G1 = CRY_GBUFFER_TEXEL(g1, idx, h1);
         if constexpr (!kQuads<Cube>) G2 = CRY_GBUFFER_TEXEL(g2, idx, h2);        // the quad exchange has loaded it already
-        lit = light_pixel<ZERO_RADIUS, decltype(culled), true, Cube, Ambient, Specular>(P, G0, G1, G2, ambient, cube, culled, lookup_for<Cube>(P, G1.w, lod), ambientTerm, specTerm);
+        lit = light_pixel<ZERO_RADIUS, decltype(culled), true, Cube, Ambient, Specular>(P, G0, G1, G2, ambient, cube, culled, lookup_for<Cube>(P, G1.w, lod, probe), ambientTerm, specTerm);
     } else if (P.flags & CRYCHIC_LIGHT_SKY) {
         lit = kQuads<Cube> ? sky_pixel_chain(P, cube, x, y) : sky_pixel(P, cube, x, y);
     } else {

@@ -1,5 +1,6 @@
 """python -m crychic_renderer_amd.demo [--size WxH] [--out frame.ppm] [--textures DIR] [--cube FILE.dds] [--gbuffer f32|mixed|f16]
                                    [--capture-env X,Y,Z [--capture-dim N]] [--gloss] [--env-ambient] [--env-specular]
+                                   [--probe-box X0,Y0,Z0,X1,Y1,Z1]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
@@ -15,7 +16,11 @@ map is bound as level 0 alone (the derivative-LOD chain has no such kernels).
 --env-specular (with --gloss): the environment BRDF table is built on the device behind the chain (Crychic.build_env_brdf /
 capture_environment(env_brdf=True)) and the glossy reflection is weighed by the split sum's second factor instead of
 (1 - roughness) times the mirror direction's Fresnel term: a rough metal keeps its brightness head-on, a rough dielectric its grazing
-sheen."""
+sheen.
+--probe-box (with --capture-env and --gloss): the axis-aligned proxy box of the captured surroundings.  The capture writes its
+position and the box into the chain's environment tail (capture_environment(probe_box=...)) and the reflection lookup is box-projected
+through it (set_cube_map(parallax=True)): a box's reflection in the floor meets the box at its foot instead of sliding with the
+camera."""
 import argparse
 import ctypes as C
 
@@ -40,7 +45,17 @@ def main():
     ap.add_argument("--env-ambient", action="store_true", help="ambient light from the cube map's SH9 irradiance instead of the constant "
                                                                "(needs --cube or --capture-env)")
     ap.add_argument("--env-specular", action="store_true", help="weigh the glossy reflection by the environment BRDF table (needs --gloss)")
+    ap.add_argument("--probe-box", default="", metavar="X0,Y0,Z0,X1,Y1,Z1", help="box-project the captured reflections through this box around "
+                                                                                 "the capture position (needs --capture-env and --gloss)")
     a = ap.parse_args()
+    box = None
+    if a.probe_box:
+        if not (a.capture_env and a.gloss):
+            ap.error("--probe-box needs --capture-env and --gloss")
+        v = [float(x) for x in a.probe_box.split(",")]
+        if len(v) != 6:
+            ap.error("--probe-box takes X0,Y0,Z0,X1,Y1,Z1")
+        box = (v[:3], v[3:])
     if a.env_specular and not a.gloss:
         ap.error("--env-specular needs --gloss")
     if a.gloss and not (a.cube or a.capture_env):
@@ -93,8 +108,9 @@ def main():
         if len(pos) != 3:
             ap.error("--capture-env takes X,Y,Z")
         chain, dim, levels = app.capture_environment(pos, geo, sgeo, dim=a.capture_dim, prefilter=a.gloss, irradiance=a.env_ambient,
-                                                     levels=1 if a.env_ambient and not a.gloss else None, env_brdf=a.env_specular)
-        app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient, env_brdf=a.env_specular)
+                                                     levels=1 if a.env_ambient and not a.gloss else None, env_brdf=a.env_specular, probe_box=box)
+        app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient, env_brdf=a.env_specular,
+                         parallax=box is not None)
         print("captured the environment at (%g, %g, %g): %d-texel faces, %d levels" % (pos[0], pos[1], pos[2], dim, levels))
     app.Draw()
     torch.cuda.synchronize()

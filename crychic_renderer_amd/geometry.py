@@ -203,6 +203,12 @@ def cube_chain_env_bytes(dim, levels):
     return int(lib.crychic_cube_chain_env_bytes(int(dim), int(levels)))
 
 
+def cube_probe_offset(dim, levels):
+    """Byte offset of the probe volume of the box-projected reflection lookup behind a cube map of `levels` levels
+    (crychic_cube_probe_offset): 368 bytes into the environment tail."""
+    return int(lib.crychic_cube_probe_offset(int(dim), int(levels)))
+
+
 def cube_capture_cameras(pos, z_near=0.5, z_far=100.0):
     """The six face cameras (+X, -X, +Y, -Y, +Z, -Z) of an environment capture at `pos` (crychic_cube_capture_cameras): a ctypes
     array of Camera with fovY = pi / 2 and aspect 1."""

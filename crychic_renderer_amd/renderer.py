@@ -194,6 +194,7 @@ class Crychic:
         self.mCubeMapGloss = False   # set_cube_map(gloss=True): the chain is prefiltered by roughness (CRYCHIC_LIGHT_CUBE_GLOSS)
         self.mCubeMapEnvBrdf = False     # set_cube_map(env_brdf=True): the environment BRDF table follows the environment tail (CRYCHIC_LIGHT_ENV_BRDF)
         self.mCubeMapAmbientSH = False   # set_cube_map(ambient_sh=True): the environment tail follows the cube map (CRYCHIC_LIGHT_AMBIENT_SH)
+        self.mCubeMapParallax = False    # set_cube_map(parallax=True): the probe volume in the environment tail corrects the reflection lookup (CRYCHIC_LIGHT_CUBE_PARALLAX)
         self.mDepthStencilBuffer = torch.full((height, width), 0xFFFFFF, device=ctx.device, dtype=torch.int32)
         self.mBackBuffer = torch.zeros((height, width, 4), device=ctx.device, dtype=torch.uint8)
         self.mMainPassCB = PassConstants()
@@ -231,6 +232,7 @@ class Crychic:
         self.mShadowMap.mShadowMap = planes["shadow"]
         self.mCubeMap = planes["cube"]
         self.mCubeMapLevels, self.mCubeMapSize, self.mCubeMapGloss, self.mCubeMapAmbientSH, self.mCubeMapEnvBrdf = 1, None, False, False, False
+        self.mCubeMapParallax = False
         self.mSsao.mRandomVectorMap = planes["randvec"]
         self.mMainPassCB = planes["consts"].pass_cb
         self.mSsaoCB = planes["consts"].ssao_cb
@@ -248,6 +250,8 @@ class Crychic:
             f.flags |= _lib.LIGHT_AMBIENT_SH
         if self.mCubeMapEnvBrdf:
             f.flags |= _lib.LIGHT_ENV_BRDF
+        if self.mCubeMapParallax:
+            f.flags |= _lib.LIGHT_CUBE_PARALLAX
         f.flags = (f.flags & ~_lib.GBUFFER_F16_MASK) | gbuffer_flags(self.mDeferred.mGBuffer)      # each plane's format: its tensor's dtype
         f.row0, f.rows = int(row0), int(H - row0 if rows is None else rows)
         f.normal_dev = self.mSsao.mNormalMap.data_ptr()
@@ -279,7 +283,7 @@ class Crychic:
                ssao.mNormalMap.data_ptr(), ssao.mRandomVectorMap.data_ptr(), self.mDepthStencilBuffer.data_ptr(),
                g0.data_ptr(), g1.data_ptr(), g2.data_ptr(), g0.dtype, g1.dtype, g2.dtype,
                sm.data_ptr(), int(sm.shape[-1]), self.mCubeMap.data_ptr(), int(self.mCubeMapSize or self.mCubeMap.shape[1]), int(self.mCubeMapLevels),
-               bool(self.mCubeMapGloss), bool(self.mCubeMapAmbientSH), bool(self.mCubeMapEnvBrdf), self.blurCount, self.numDirLights, self.pcfSearchRadius, self.flags,
+               bool(self.mCubeMapGloss), bool(self.mCubeMapAmbientSH), bool(self.mCubeMapEnvBrdf), bool(self.mCubeMapParallax), self.blurCount, self.numDirLights, self.pcfSearchRadius, self.flags,
                0 if self.mPointLights is None else self.mPointLights.data_ptr(),
                0 if self.mSpotLights is None else self.mSpotLights.data_ptr())
         if self._desc is None:
@@ -327,7 +331,7 @@ class Crychic:
         check(lib.crychic_draw_hot_path(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(self.mMainPassCB), C.byref(f),
                                         _stream(self.ctx.device)))
 
-    def set_cube_map(self, cube, dim=None, levels=1, gloss=False, ambient_sh=False, env_brdf=False):
+    def set_cube_map(self, cube, dim=None, levels=1, gloss=False, ambient_sh=False, env_brdf=False, parallax=False):
         """The sky cube map: a 6 x dim x dim x 4 uint8 tensor (level 0 alone), or -- with `levels` > 1 -- the flat mip chain
         geometry.cube_mip_chain / load_dds_cube_mips produce (the reference binds the whole chain, CRYCHIC.cpp:1148-1151): the
         reflection and sky lookups are then trilinear (CRYCHIC_LIGHT_CUBE_LEVELS).  gloss (needs levels > 1): the chain is one
@@ -337,9 +341,19 @@ class Crychic:
         pixel's normal instead of AmbientLight (CRYCHIC_LIGHT_AMBIENT_SH).  env_brdf (needs gloss): the tensor holds
         geometry.cube_chain_env_bytes(dim, levels) bytes, the chain, the environment tail and behind it the table build_env_brdf
         made; the reflection is then weighed by the split sum's second factor instead of shininess and the mirror direction's
-        Fresnel term (CRYCHIC_LIGHT_ENV_BRDF)."""
+        Fresnel term (CRYCHIC_LIGHT_ENV_BRDF).  parallax (needs gloss): the tensor holds at least
+        geometry.cube_chain_sh_bytes(dim, levels) bytes and set_probe_volume (or capture_environment(probe_box=...)) wrote the probe
+        volume into its environment tail; the reflection lookup is then box-projected through it (CRYCHIC_LIGHT_CUBE_PARALLAX)."""
         if gloss and int(levels) < 2:
             raise CrychicError(-1, "set_cube_map: gloss needs a chain (levels > 1)")
+        if parallax:
+            from .geometry import cube_chain_sh_bytes
+            if not gloss:
+                raise CrychicError(-1, "set_cube_map: parallax needs a prefiltered chain (levels > 1 and gloss=True)")
+            d = int(dim) if dim is not None else int(cube.shape[1])
+            if cube.numel() * cube.element_size() < cube_chain_sh_bytes(d, levels):
+                raise CrychicError(-1, "set_cube_map: parallax needs a tensor of %d bytes (the chain and its environment tail)"
+                                   % cube_chain_sh_bytes(d, levels))
         if env_brdf:
             from .geometry import cube_chain_env_bytes
             if not gloss:
@@ -359,6 +373,7 @@ class Crychic:
         self.mCubeMapGloss = bool(gloss)
         self.mCubeMapAmbientSH = bool(ambient_sh)
         self.mCubeMapEnvBrdf = bool(env_brdf)
+        self.mCubeMapParallax = bool(parallax)
         self.mCubeMap = cube
         self.mCubeMapLevels = int(levels)
         self.mCubeMapSize = int(dim) if dim is not None else None
@@ -419,8 +434,24 @@ class Crychic:
                                          _stream(self.ctx.device)))
         return chain
 
+    def set_probe_volume(self, chain, dim, levels, pos, box_min, box_max):
+        """Extension: writes the probe volume of the box-projected reflection lookup -- the capture position `pos` and the proxy box
+        [box_min, box_max], three floats each, box_min < pos < box_max -- into the environment tail of `chain` (a uint8 tensor of at
+        least geometry.cube_chain_sh_bytes(dim, levels) bytes), at geometry.cube_probe_offset(dim, levels)
+        (crychic_set_cube_probe_volume; include/crychic_hip.h "probe volume").  Returns `chain`;
+        set_cube_map(chain, dim, levels, gloss=True, parallax=True) binds it."""
+        from .geometry import cube_chain_sh_bytes, cube_sh_offset
+        dim, levels = int(dim), int(levels)
+        if chain.dtype != torch.uint8 or not chain.is_contiguous() or chain.numel() < cube_chain_sh_bytes(dim, levels):
+            raise CrychicError(-1, "set_probe_volume: chain must be a contiguous uint8 device tensor of at least %d bytes"
+                               % cube_chain_sh_bytes(dim, levels))
+        v = [(C.c_float * 3)(*[float(x) for x in a]) for a in (pos, box_min, box_max)]
+        check(lib.crychic_set_cube_probe_volume(self.ctx.handle, C.c_void_p(chain.data_ptr() + cube_sh_offset(dim, levels)), v[0], v[1], v[2],
+                                                _stream(self.ctx.device)))
+        return chain
+
     def capture_environment(self, pos, geometry, shadow_geometry=None, dim=256, levels=None, z_near=0.5, z_far=None, shadow_dim=1024,
-                            out=None, prefilter=False, irradiance=False, env_brdf=False):
+                            out=None, prefilter=False, irradiance=False, env_brdf=False, probe_box=None):
         """Extension: renders the scene into a cube map at `pos` and builds its mip chain on the device (include/crychic_hip.h
         "environment capture").  Face f of level 0 is the frame Draw produces at dim x dim for face camera f
         (crychic_cube_capture_cameras) with CRYCHIC_LIGHT_SKY, written in place: `geometry` (a SceneGeometry) fills the normal map,
@@ -437,12 +468,18 @@ class Crychic:
         tensor returned has geometry.cube_chain_sh_bytes(dim, levels) bytes (so must `out`), and level 0 of the captured box chain is
         projected into its environment tail (project_irradiance) -- bind it with ambient_sh=True.  env_brdf (needs prefilter=True and
         more than one level): the tensor returned has geometry.cube_chain_env_bytes(dim, levels) bytes (so must `out`) and the
-        environment BRDF table is built behind its environment tail (build_env_brdf) -- bind it with gloss=True, env_brdf=True."""
+        environment BRDF table is built behind its environment tail (build_env_brdf) -- bind it with gloss=True, env_brdf=True.
+        probe_box = (box_min, box_max) (needs prefilter=True and more than one level): the tensor returned has at least
+        geometry.cube_chain_sh_bytes(dim, levels) bytes (so must `out`) and the probe volume -- this capture's `pos` and the box -- is
+        written into the environment tail of the chain returned, the prefiltered one (set_probe_volume) -- bind it with gloss=True,
+        parallax=True."""
         import numpy as np
         from .geometry import (cube_capture_cameras, cube_chain_bytes, cube_chain_env_bytes, cube_chain_sh_bytes, cube_env_brdf_offset,
                                cube_full_levels, cube_sh_offset)
         if env_brdf and not prefilter:
             raise CrychicError(-1, "capture_environment: env_brdf needs prefilter=True (the table weighs a prefiltered chain)")
+        if probe_box is not None and not prefilter:
+            raise CrychicError(-1, "capture_environment: probe_box needs prefilter=True (the box-projected lookup reads a prefiltered chain)")
         dim, shadow_dim = int(dim), int(shadow_dim)
         if not 0 < dim <= 8192:
             raise CrychicError(-1, "capture_environment: dim %d (a cube map the lighting pass binds has 2 .. 8192-texel faces)" % dim)
@@ -452,13 +489,15 @@ class Crychic:
             raise CrychicError(-1, "capture_environment: levels %d (1 .. %d for %d-texel faces)" % (levels, full, dim))
         if env_brdf and levels < 2:
             raise CrychicError(-1, "capture_environment: env_brdf needs a chain (levels > 1)")
+        if probe_box is not None and levels < 2:
+            raise CrychicError(-1, "capture_environment: probe_box needs a chain (levels > 1)")
         src = self.mCubeMap
         probe = self._probes.get((dim, shadow_dim))
         if probe is None:       # a dim x dim frame: an odd dim is refused as every frame size is (Ssao.OnResize)
             probe = self._probes[(dim, shadow_dim)] = Crychic(self.ctx, dim, dim, self.mSsao.mRandomVectorMap, src, shadow_dim=shadow_dim,
                                                               gbuffer_formats=self.mDeferred.mFormats)
         chain_bytes = cube_chain_bytes(dim, levels)
-        nbytes = cube_chain_env_bytes(dim, levels) if env_brdf else cube_chain_sh_bytes(dim, levels) if irradiance else chain_bytes
+        nbytes = cube_chain_env_bytes(dim, levels) if env_brdf else cube_chain_sh_bytes(dim, levels) if irradiance or probe_box is not None else chain_bytes
         if out is None:
             out = torch.empty((nbytes,), device=self.ctx.device, dtype=torch.uint8)
         elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < nbytes or out.device != self.mBackBuffer.device:
@@ -482,6 +521,7 @@ class Crychic:
         probe.mCubeMapGloss = self.mCubeMapGloss        # a capture of a glossy scene is glossy
         probe.mCubeMapAmbientSH = self.mCubeMapAmbientSH  # ... and one lit by its environment is lit by it
         probe.mCubeMapEnvBrdf = self.mCubeMapEnvBrdf      # ... with the reflection weight the owner uses
+        probe.mCubeMapParallax = self.mCubeMapParallax    # ... and the bound map's probe volume: it is stated in world space
         probe.blurCount, probe.numDirLights, probe.flags = self.blurCount, self.numDirLights, int(self.flags) | _lib.LIGHT_SKY
         probe.pcfSearchRadius = lib.crychic_pcf_search_radius(shadow_dim, int(self.pcfLiteral))
         probe.mPointLights, probe.mSpotLights = self.mPointLights, self.mSpotLights
@@ -534,6 +574,8 @@ class Crychic:
                                              _stream(self.ctx.device)))
         if prefilter:
             out = self.prefilter_cube_map(out, dim, levels, out=final)
+        if probe_box is not None:       # into the chain that is bound later: the prefiltered one
+            self.set_probe_volume(final, dim, levels, pos, probe_box[0], probe_box[1])
         return out, dim, levels
 
     def release_capture_probes(self):

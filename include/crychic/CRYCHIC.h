@@ -220,6 +220,7 @@ public:
         if (L.mGlossyReflections && L.mCubeMapLevels > 1) f.flags |= CRYCHIC_LIGHT_CUBE_GLOSS;      // the level from the pixel's roughness
         if (L.mCubeMapHasTail) f.flags |= CRYCHIC_LIGHT_AMBIENT_SH;                                 // the ambient colour from the environment tail
         if (L.mCubeMapHasTable && (f.flags & CRYCHIC_LIGHT_CUBE_GLOSS)) f.flags |= CRYCHIC_LIGHT_ENV_BRDF;   // the reflection weighed by the table behind it
+        if (L.mCubeMapHasProbe && L.mProbeBoxSet && (f.flags & CRYCHIC_LIGHT_CUBE_GLOSS)) f.flags |= CRYCHIC_LIGHT_CUBE_PARALLAX;   // the lookup box-projected through the probe volume in its tail
         f.flags |= mDeferred->FormatFlags();                                                        // a half4 plane: its CRYCHIC_GBUFFER_G*_F16 bit
         f.row0 = mStripRow0; f.rows = mWholeFrame ? mClientHeight : mStripRows;                      // whole frame unless SetStrip / JoinNode
         f.normal_dev = mSsao->NormalMap()->Data();
@@ -379,7 +380,10 @@ public:
     // a chain of more than one level then needs SetGlossyReflections(true) (the derivative-LOD chain has no such kernels).  With
     // SetEnvironmentSpecular(true) -- which needs SetGlossyReflections(true) and more than one level -- the chain is allocated with the
     // environment tail and the environment BRDF table (crychic_cube_chain_env_bytes) and the table is built behind the tail
-    // (crychic_build_env_brdf).
+    // (crychic_build_env_brdf).  The capture position is remembered; with SetReflectionProbeBox's box set and glossy reflections on over
+    // more than one level the chain is allocated with its environment tail at least, and the probe volume -- (x, y, z) and the box --
+    // is written into the tail of the chain that is bound (crychic_set_cube_probe_volume; a box that does not hold the position
+    // strictly inside is refused before anything is rendered).
     void CaptureEnvironment(float x, float y, float z, UINT dim, UINT levels = 0, UINT shadowDim = 1024)
     {
         uint32_t full = 1;
@@ -420,14 +424,18 @@ public:
         if (p.mDeferred->FormatFlags() != mDeferred->FormatFlags()) p.SetGBufferFormat(mDeferred->Format(0), mDeferred->Format(1), mDeferred->Format(2));
         p.mTextures = mTextures;                // the device copies stay this object's (mTexturePlanes)
         const size_t faceBytes = (size_t)dim * dim * 4u, chainBytes = crychic_cube_chain_bytes(dim, levels);
+        const bool withProbe = mProbeBoxSet && mGlossyReflections && levels > 1u;                                  // the probe volume lives in the tail
         const size_t boundBytes = mEnvironmentSpecular ? crychic_cube_chain_env_bytes(dim, levels)                  // with the tail and the table
-                                : mEnvironmentAmbient ? crychic_cube_chain_sh_bytes(dim, levels) : chainBytes;     // with the environment tail
+                                : (mEnvironmentAmbient || withProbe) ? crychic_cube_chain_sh_bytes(dim, levels) : chainBytes;     // with the environment tail
         std::unique_ptr<ID3D12Resource> chain = std::move(mSpareCubeMap);          // the cube map the last capture replaced
         if (!chain || chain->Bytes() != boundBytes) chain = std::make_unique<ID3D12Resource>(boundBytes, ID3D12Resource::DEFAULT_HEAP);
         if (mGlossyReflections && (!mCaptureBoxChain || mCaptureBoxChain->Bytes() != chainBytes))
             mCaptureBoxChain = std::make_unique<ID3D12Resource>(chainBytes, ID3D12Resource::DEFAULT_HEAP);
         ID3D12Resource* box = mGlossyReflections ? mCaptureBoxChain.get() : chain.get();         // where the faces are rendered
         const float pos[3] = { x, y, z };
+        if (withProbe)                          // the prefilter and the projection leave tail bytes [368, 416) alone
+            CrychicThrowIfFailed(crychic_set_cube_probe_volume(md3dDevice->Ctx(), static_cast<uint8_t*>(chain->Data()) + crychic_cube_sh_offset(dim, levels),
+                                                               pos, mProbeBoxMin, mProbeBoxMax, mCommandList->Stream()));
         crychic_camera cams[6];
         CrychicThrowIfFailed(crychic_cube_capture_cameras(pos, 0.5f, mCamera.GetFarZ(), cams));
         for (int f = 0; f < 6; ++f) {
@@ -455,6 +463,8 @@ public:
         mCommandList->Flush();                  // frames in flight may still read the source, which the next capture overwrites
         mSpareCubeMap = std::move(mCubeMap);
         SetCubeMap(std::move(chain), dim, levels, mEnvironmentAmbient, mEnvironmentSpecular);
+        mCubeMapHasProbe = withProbe;
+        mCapturePos[0] = x; mCapturePos[1] = y; mCapturePos[2] = z; mHaveCapturePos = true;
     }
 
     // ---- one frame on several GPUs (no counterpart in the single-GPU reference) ----------------------------------
@@ -517,6 +527,8 @@ public:
     {
         mCubeMap = std::move(cube); mCubeMapSize = dim; mCubeMapLevels = levels ? levels : 1; mCubeMapHasTail = hasTail;
         mCubeMapHasTable = hasTable;
+        mCubeMapHasProbe = false;               // CaptureEnvironment and SetReflectionProbeBox write the volume and say so
+        mHaveCapturePos = false;
     }
     bool CubeMapHasTail() const { return mCubeMapHasTail; }
     bool CubeMapHasTable() const { return mCubeMapHasTable; }
@@ -531,6 +543,25 @@ public:
     // Draw -- this object's and its probe's -- takes the ambient colour from the tail of a bound cube map that has one.
     void SetEnvironmentAmbient(bool on) { mEnvironmentAmbient = on; }
     bool EnvironmentAmbient() const { return mEnvironmentAmbient; }
+    // Parallax-corrected reflections (extension: include/crychic_hip.h CRYCHIC_LIGHT_CUBE_PARALLAX): the axis-aligned proxy box of the
+    // captured surroundings.  While a box is set, CaptureEnvironment (with glossy reflections on) writes the probe volume -- its own
+    // position and the box -- into the environment tail of the chain it binds, and Draw -- this object's and its probe's -- looks a
+    // glossy chain that has the volume up along the box-projected direction.  Set after a capture whose chain has a tail, the volume
+    // is written at once with the remembered capture position.  ClearReflectionProbeBox clears the flag: the distant lookup again.
+    void SetReflectionProbeBox(const float boxMin[3], const float boxMax[3])
+    {
+        for (int k = 0; k < 3; ++k) { mProbeBoxMin[k] = boxMin[k]; mProbeBoxMax[k] = boxMax[k]; }
+        mProbeBoxSet = true;
+        if (mHaveCapturePos && mCubeMap && mCubeMapLevels > 1 && mCubeMap->Bytes() >= crychic_cube_chain_sh_bytes(mCubeMapSize, mCubeMapLevels)) {
+            mCommandList->Flush();              // frames in flight read the volume that is there
+            CrychicThrowIfFailed(crychic_set_cube_probe_volume(md3dDevice->Ctx(), static_cast<uint8_t*>(mCubeMap->Data()) + crychic_cube_sh_offset(mCubeMapSize, mCubeMapLevels),
+                                                               mCapturePos, mProbeBoxMin, mProbeBoxMax, mCommandList->Stream()));
+            mCubeMapHasProbe = true;
+        }
+    }
+    void ClearReflectionProbeBox() { mProbeBoxSet = false; }
+    bool ReflectionProbeBox() const { return mProbeBoxSet; }
+    bool CubeMapHasProbe() const { return mCubeMapHasProbe; }
     // Glossy reflections (extension: include/crychic_hip.h CRYCHIC_LIGHT_CUBE_GLOSS): while on, CaptureEnvironment binds the captured
     // chain prefiltered by roughness, and Draw -- this object's and its probe's -- looks a bound chain (more than one level) up at the
     // level of the pixel's roughness.  The caller turns it on for a chain that is prefiltered: a capture made while it is on, or one
@@ -988,6 +1019,10 @@ private:
     bool mCubeMapHasTail = false;                   // SetCubeMap(..., hasTail): the environment tail follows the bound cube map
     bool mEnvironmentSpecular = false;              // SetEnvironmentSpecular
     bool mCubeMapHasTable = false;                  // SetCubeMap(..., hasTable): the environment BRDF table follows the environment tail
+    bool mProbeBoxSet = false;                      // SetReflectionProbeBox / ClearReflectionProbeBox
+    bool mCubeMapHasProbe = false;                  // the bound cube map's environment tail holds the probe volume
+    bool mHaveCapturePos = false;                   // the bound cube map is CaptureEnvironment's, taken at mCapturePos
+    float mProbeBoxMin[3] = {}, mProbeBoxMax[3] = {}, mCapturePos[3] = {};
     std::unique_ptr<ID3D12Resource> mCaptureBoxChain;   // CaptureEnvironment with glossy reflections: the captured box chain, kept
     UINT mClientWidth, mClientHeight;
     float mLightRotationAngle = 0.0f;

@@ -223,6 +223,15 @@ int crychic_ssao_compute(crychic_ctx* ctx, const crychic_ssao_constants* cb, con
  * CRYCHIC_E_INVALID_ARG with a message, before anything is enqueued.  Accepted by every crychic_deferred_light* entry (strips and the
  * _shared entries included) and in crychic_frame_desc.flags; without the flag every call is what it was, bit for bit. */
 #define CRYCHIC_LIGHT_ENV_BRDF 0x100000u
+/* Parallax-corrected reflections (BUILD-DEFINED EXTENSION; "probe volume" below).  With
+ * CRYCHIC_LIGHT_CUBE_PARALLAX the reflection lookup of DeferredShading.hlsl:95 takes, in place of the reflection vector, the direction
+ * from the capture position to the point where the reflection ray from the pixel's own world position leaves the probe volume's box
+ * -- the twelve floats at cube_dev + crychic_cube_probe_offset(cubeDim, levels), inside the environment tail.  Valid only together with
+ * CRYCHIC_LIGHT_CUBE_LEVELS(n > 1) | CRYCHIC_LIGHT_CUBE_GLOSS, with and without CRYCHIC_LIGHT_AMBIENT_SH and CRYCHIC_LIGHT_ENV_BRDF and
+ * with any G-buffer format mix; any other combination, a NULL cube map or a probe volume address that is not 4-byte aligned is
+ * CRYCHIC_E_INVALID_ARG with a message, before anything is enqueued.  Accepted by every crychic_deferred_light* entry (strips and the
+ * _shared entries included) and in crychic_frame_desc.flags; without the flag every call is what it was, bit for bit. */
+#define CRYCHIC_LIGHT_CUBE_PARALLAX 0x200000u
 #define CRYCHIC_FIX_Q1 0x100u
 #define CRYCHIC_FIX_Q3 0x200u
 #define CRYCHIC_FIX_Q4 0x400u
@@ -713,7 +722,8 @@ int crychic_prefilter_cube_chain(crychic_ctx* ctx, const uint8_t* src_chain_dev,
  * crychic_cube_chain_bytes(dim, max(levels, 1)) rounded up to 16, so a buffer of crychic_cube_chain_sh_bytes(dim, levels) = offset +
  * CRYCHIC_CUBE_SH_BYTES bytes holds a chain and its tail.  Bytes [0, 144) of the tail are the coefficient block; bytes [144, 368)
  * are the projection's 28 int64 accumulators (S_{m,c} at index 3 m + c, S_w at 27), scratch with no initialisation requirement;
- * the rest is reserved.  Both size functions are pure host arithmetic. */
+ * bytes [368, 416) are the probe volume ("probe volume" below), which the projection leaves alone; the rest is reserved.  Both size
+ * functions are pure host arithmetic. */
 #define CRYCHIC_CUBE_SH_BYTES 512u
 size_t crychic_cube_sh_offset(uint32_t dim, uint32_t levels);
 size_t crychic_cube_chain_sh_bytes(uint32_t dim, uint32_t levels);
@@ -765,6 +775,39 @@ size_t crychic_cube_chain_env_bytes(uint32_t dim, uint32_t levels);
  * read-back: capturable into a graph, and building twice gives the same bits whatever the destination held.
  * CRYCHIC_E_INVALID_ARG, before anything is enqueued, for a NULL pointer or one that is not 4-byte aligned. */
 int crychic_build_env_brdf(crychic_ctx* ctx, void* table_dev, void* stream);
+
+/* ---- probe volume: box-projected reflections (BUILD-DEFINED EXTENSION) ---------------------------------- *
+ * A capture taken at a position is looked up as if it were infinitely far away; box projection corrects that for one axis-aligned
+ * proxy box around the capture.  A build definition: parity is against this repo's CPU checker (tests/parallax_ref).
+ *
+ * Probe volume: CRYCHIC_CUBE_PROBE_BYTES = 48 bytes of the environment tail's reserved area, at tail offset
+ * CRYCHIC_CUBE_PROBE_OFFSET = 368: three float4, c = (cx, cy, cz, 0) the capture position, bmin = (.., 0) and bmax = (.., 0) the box.
+ * Its address is cube_dev + crychic_cube_probe_offset(dim, levels) = cube_dev + crychic_cube_sh_offset(dim, levels) + 368 (pure host
+ * arithmetic); a buffer of crychic_cube_chain_sh_bytes holds it, and so does one of crychic_cube_chain_env_bytes.  Tail bytes
+ * [416, 512) stay reserved.  crychic_project_cube_sh writes tail bytes [0, 368) only.
+ *
+ * Correction (CRYCHIC_LIGHT_CUBE_PARALLAX), per covered pixel, in binary32 with rcp (above); nothing is fused unless written as fma.
+ * p = posW, r = the reflection vector of DeferredShading.hlsl:94.
+ *   for k = x, y, z: if |r_k| >= 2^-126 (false for NaN): e_k = (r_k < 0 ? bmin_k : bmax_k) - p_k, t_k = e_k * rcp(r_k); otherwise the
+ *     component is skipped;
+ *   t = +inf, then for k in order t = (t_k < t) ? t_k : t (a NaN t_k loses);  t = max(t, 0) (the clamp of HLSL's max);
+ *   if !(t < +inf): r' = r -- nothing usable, the distant lookup;  otherwise h_k = fma(r_k, t, p_k), r'_k = h_k - c_k.
+ * r' replaces r as the argument of the cube lookup alone (the trilinear fetch of the gloss chain).  The level from roughness,
+ * f0 = 1 - saturate(dot(normalW, r)) and the whole reference weight, the split-sum (A, B) lookup, the ambient term, the sky, the
+ * direct lights and the tone map stay on r, normalW, view and roughness as they are.  A zero or non-finite r' goes to the sampler
+ * like any other direction.  There is no inside-the-box test, on purpose: rasterised floor positions sit an ulp either side of a box
+ * face, and the clamp t >= 0 makes such a pixel reflect from its own position instead of flickering between two rules.
+ * Known answers (exact), c = 0, bmin = (-4, -2, -4), bmax = (4, 6, 4): p = (1, -2, 1), r = (0.5, 0.5, 0) gives t = 6, r' = (4, 1, 1),
+ * and so does r = (0.5, 0.5, -0.0f); r = (0, 0, 0) gives r' = r; p = (1, -2.5, 1), r = (0, -1, 0) clamps t to 0, r' = p - c. */
+#define CRYCHIC_CUBE_PROBE_OFFSET 368u
+#define CRYCHIC_CUBE_PROBE_BYTES 48u
+size_t crychic_cube_probe_offset(uint32_t dim, uint32_t levels);
+/* Writes the probe volume into the environment tail at tail_dev (cube_dev + crychic_cube_sh_offset(dim, levels)): bytes
+ * [368, 416) of the tail and nothing else.  One tiny launch on `stream`: the twelve floats travel by value with the kernel's
+ * arguments; no allocation, no host copy, capturable into a graph.  CRYCHIC_E_INVALID_ARG, before anything is enqueued, for a NULL
+ * pointer, a tail_dev that is not 4-byte aligned, a non-finite value, or any component without boxMin < pos < boxMax strictly. */
+int crychic_set_cube_probe_volume(crychic_ctx* ctx, void* tail_dev, const float pos[3], const float boxMin[3], const float boxMax[3],
+                                  void* stream);
 
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples

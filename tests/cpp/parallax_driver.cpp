@@ -1,0 +1,89 @@
+// parallax_driver.cpp -- the C++ veneer's parallax-corrected reflections (include/crychic/CRYCHIC.h SetReflectionProbeBox), as a
+// reference call site would drive it; the captured chain with the probe volume in its tail and the frames rendered with it go back for
+// comparison with the Python path (tests/test_parallax_veneer.py).  The built-in scene with its producer passes, frustum culling off
+// (the Python path draws every instance): SetGlossyReflections(true), SetEnvironmentSpecular(true), SetReflectionProbeBox(min, max);
+// one frame, CaptureEnvironment(x, y, z, dim, 0, captureShadowDim), chain.bin (the bound chain, its tail and the table), a frame with
+// it bound: out.bin, pass_cb.bin, ssao_cb.bin; then ClearReflectionProbeBox and the same frame again: out_cleared.bin.
+// Usage: parallax_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <dim> <captureShadowDim> <x> <y> <z> <x0> <y0> <z0> <x1> <y1> <z1>
+// <dir> holds cube.bin, the one-level source cube map of <cubeDim>.
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <string>
+#include <vector>
+#include "crychic/CRYCHIC.h"
+
+static std::vector<char> slurp(const std::string& p)
+{
+    std::ifstream f(p, std::ios::binary);
+    if (!f) { std::fprintf(stderr, "cannot open %s\n", p.c_str()); std::exit(2); }
+    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+}
+static void dump(const std::string& p, const void* d, size_t n)
+{
+    std::ofstream f(p, std::ios::binary);
+    f.write(static_cast<const char*>(d), (std::streamsize)n);
+}
+
+int main(int argc, char** argv)
+{
+    if (argc < 18) { std::fprintf(stderr, "usage\n"); return 2; }
+    const std::string dir = argv[1];
+    const UINT W = std::atoi(argv[2]), H = std::atoi(argv[3]), SD = std::atoi(argv[4]), CD = std::atoi(argv[5]);
+    const UINT dim = std::atoi(argv[7]), captureSD = std::atoi(argv[8]);
+    const float x = (float)std::atof(argv[9]), y = (float)std::atof(argv[10]), z = (float)std::atof(argv[11]);
+    float lo[3], hi[3];
+    for (int k = 0; k < 3; ++k) { lo[k] = (float)std::atof(argv[12 + k]); hi[k] = (float)std::atof(argv[15 + k]); }
+    try {
+        GameTimer gt;
+        CRYCHIC app(0, W, H);
+        app.mShadowMapSize = SD;
+        app.mBlurCount = std::atoi(argv[6]);
+        app.mNumDirLights = 1;
+        app.mSkyEnabled = true;
+        app.mFrustumCullingEnabled = false;
+        if (!app.Initialize()) return 3;
+        hipStream_t s = app.CommandList()->Stream();
+        auto cube = std::make_unique<ID3D12Resource>((size_t)6 * CD * CD * 4, ID3D12Resource::DEFAULT_HEAP);
+        auto b = slurp(dir + "/cube.bin");
+        if (b.size() != cube->Bytes()) { std::fprintf(stderr, "cube.bin: %zu bytes, expected %zu\n", b.size(), cube->Bytes()); return 2; }
+        cube->Upload(b.data(), b.size(), s);
+        app.CommandList()->Flush();
+        app.SetCubeMap(std::move(cube), CD);
+        app.SetGlossyReflections(true);
+        app.SetEnvironmentSpecular(true);
+        app.SetReflectionProbeBox(lo, hi);      // nothing captured yet: the box is kept for the capture
+        if (!app.ReflectionProbeBox() || app.CubeMapHasProbe()) return 4;
+        auto frame = [&](const char* name) {
+            app.Update(gt);
+            app.Draw(gt);
+            app.CommandList()->Flush();
+            if (!name) return;
+            std::vector<uint8_t> out((size_t)W * H * 4);
+            app.CurrentBackBuffer()->Download(out.data(), out.size(), s);
+            app.CommandList()->Flush();
+            dump(dir + "/" + name, out.data(), out.size());
+        };
+        gt.Tick(1.0f / 60.0f);
+        frame(nullptr);                         // before the capture the bound cube map has no volume: the distant lookup
+        app.CaptureEnvironment(x, y, z, dim, 0, captureSD);
+        if (!app.CubeMapHasProbe() || !app.CubeMapHasTable() || app.CubeMap()->Bytes() != crychic_cube_chain_env_bytes(dim, app.CubeMapLevels())) return 5;
+        std::vector<uint8_t> chain(app.CubeMap()->Bytes());
+        app.CubeMap()->Download(chain.data(), chain.size(), s);
+        app.CommandList()->Flush();
+        dump(dir + "/chain.bin", chain.data(), chain.size());
+        gt.Tick(1.0f / 60.0f);
+        frame("out.bin");
+        dump(dir + "/pass_cb.bin", &app.mCurrFrameResource->PassCB->Element(0), sizeof(PassConstants));
+        dump(dir + "/ssao_cb.bin", &app.mCurrFrameResource->SsaoCB->Element(0), sizeof(SsaoConstants));
+        app.ClearReflectionProbeBox();          // the flag goes with the box: the same frame without the correction
+        frame("out_cleared.bin");
+        app.SetReflectionProbeBox(lo, hi);      // set again after the capture: written at once with the remembered position
+        frame("out_again.bin");
+        std::printf("parallax driver ok dim %u levels %u\n", dim, app.CubeMapLevels());
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "exception: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
