@@ -21,8 +21,9 @@ namespace cry {
 constexpr int kLargeBox = 2048;   // pixel-box area above which a triangle gets a whole workgroup
 struct RasterCounters { uint32_t nlive; uint32_t overflow; uint32_t nlarge; uint32_t pad; };
 
-// Clears: 16-byte stores (two visibility keys / four depth texels per lane); the planes come from hipMalloc / torch and are
-// 16-byte aligned, odd tails are finished with scalar stores by the last lanes.
+// Clears: 16-byte stores (two visibility keys / four depth texels per lane), odd tails finished with single stores by the last
+// lanes.  The visibility buffer opens the workspace and is 16-byte aligned with it; a depth plane is the caller's and may be only
+// 4-byte aligned, so its clear also writes the texels before the first 16-byte boundary one by one.
 __global__ __launch_bounds__(256) void clear_vis_kernel(uint64_t* __restrict__ vis, uint32_t n, RasterCounters* c)
 {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -236,7 +237,10 @@ size_t raster_workspace_bytes(uint64_t triangles, uint32_t W, uint32_t H)
 
 hipError_t launch_raster_pass(RasterPass& p, hipStream_t stream)
 {
-    // carve the workspace: vis | tris | live | textures | counters (all 16-byte aligned)
+    // carve the workspace: vis | tris | live | textures | counters.  vis starts at the workspace's own (16-byte) alignment, which its
+    // clear relies on (16-byte stores).  The regions behind it are only 8-byte aligned when W * H is odd: enough for SetupTri and
+    // Texture (alignof 8, all the compiler may assume; wide global and scalar loads need dword alignment only) and for the 32-bit
+    // words of live and the counters.
     uint64_t total = 0;
     for (uint32_t i = 0; i < p.nItems; ++i) total += (uint64_t)(p.items[i].indexCount / 3u) * p.items[i].instanceCount;
     const bool shadow = p.mode == 0;

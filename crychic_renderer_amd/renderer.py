@@ -729,13 +729,30 @@ class SceneGeometry:
         self._keep = []
         self.items = (DrawItem * len(items))()
         self.triangles = 0
-        for k, (v, idx, inst) in enumerate(items):
-            tv = torch.from_numpy(np.ascontiguousarray(v).view(np.uint8).copy()).to(dev)
-            ti = torch.from_numpy(np.ascontiguousarray(idx).view(np.int32).copy()).to(dev)
-            tn = torch.from_numpy(np.ascontiguousarray(inst).view(np.uint8).copy()).to(dev)
-            self._keep += [tv, ti, tn]
-            self.items[k] = DrawItem(tv.data_ptr(), len(v), ti.data_ptr(), len(idx), 0, 0, tn.data_ptr(), len(inst))
-            self.triangles += (len(idx) // 3) * len(inst)
+        uploads = {}
+
+        def upload(a, as_type):
+            # None or an empty array: a null buffer.  An array object that several items pass (a shared vertex buffer) is uploaded
+            # once: the key is the caller's own object, which `uploads` keeps alive, never a temporary copy.
+            if a is None or len(a) == 0:
+                return None
+            if id(a) not in uploads:
+                t = torch.from_numpy(np.ascontiguousarray(a).view(as_type).copy()).to(dev)
+                uploads[id(a)] = (a, t)
+                self._keep.append(t)
+            return uploads[id(a)][1]
+
+        for k, item in enumerate(items):
+            # (vertices, indices, instances) or (vertices, indices, instances, startIndexLocation, baseVertexLocation): with the two
+            # locations the item draws the indices from startIndexLocation to the end of the array it is given
+            v, idx, inst = item[:3]
+            start, base = (int(item[3]), int(item[4])) if len(item) == 5 else (0, 0)
+            count = (len(idx) if idx is not None else 0) - start
+            tv, ti, tn = upload(v, np.uint8), upload(idx, np.int32), upload(inst, np.uint8)
+            self.items[k] = DrawItem(tv.data_ptr() if tv is not None else None, len(v) if v is not None else 0,
+                                     ti.data_ptr() if ti is not None else None, count, start, base,
+                                     tn.data_ptr() if tn is not None else None, len(inst) if inst is not None else 0)
+            self.triangles += (count // 3) * (len(inst) if inst is not None else 0)
         self.materials = None
         self.n_materials = 0
         if materials is not None:

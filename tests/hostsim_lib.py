@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 
 from gbuffer_f16_lib import F16_MASK, G0_F16, G1_F16, G2_F16
+from oracle_lib import draw_item_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "hostsim", "hostsim.cpp")
@@ -202,10 +203,8 @@ class HostSim:
         from crychic_renderer_amd.geometry import texture_levels
         arr = (DrawItem * len(items))()
         keep = []
-        for k, (v, idx, inst) in enumerate(items):
-            v = np.ascontiguousarray(v); idx = np.ascontiguousarray(idx); inst = np.ascontiguousarray(inst)
-            keep += [v, idx, inst]
-            arr[k] = DrawItem(v.ctypes.data, len(v), idx.ctypes.data, len(idx), 0, 0, inst.ctypes.data, len(inst))
+        for k, item in enumerate(items):                     # 3-tuples, or 5-tuples with the two locations (oracle_lib.draw_item_fields)
+            arr[k] = DrawItem(*draw_item_fields(item, keep))
         tex = (Texture * max(1, len(textures or [])))()
         for k, t in enumerate(textures or []):
             if t is not None:

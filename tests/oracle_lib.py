@@ -228,15 +228,32 @@ def load_mesh_text(orc, path):
     return v, idx
 
 
+def draw_item_fields(item, keep):
+    """The eight fields of a draw item record (crychic_draw_item's order, host pointers) for (vertices, indices, instances) or
+    (vertices, indices, instances, startIndexLocation, baseVertexLocation).  With the two locations the item draws the indices from
+    startIndexLocation to the end of the array it is given, so items that draw ranges of one shared buffer pass views of it that
+    start at its first element; None or an empty array is a null buffer.  The arrays are appended to `keep`."""
+    v, idx, inst = item[:3]
+    start, base = (int(item[3]), int(item[4])) if len(item) == 5 else (0, 0)
+
+    def buf(a):
+        if a is None or len(a) == 0:
+            return None, 0
+        a = np.ascontiguousarray(a); keep.append(a)
+        return a.ctypes.data, len(a)
+    (pv, nv), (pi, ni), (pn, nn) = buf(v), buf(idx), buf(inst)
+    assert 0 <= start <= ni
+    return pv, nv, pi, ni - start, start, base, pn, nn
+
+
 def rasterize(orc, mode, view_t, viewproj_t, items, materials, textures, W, H, depth_bias=0, slope_bias=0.0):
-    """items: list of (vertices, indices, instances) numpy arrays; textures: list of HxWx4 uint8 arrays (or None)."""
+    """items: list of (vertices, indices, instances) numpy arrays, or of 5-tuples with startIndexLocation and baseVertexLocation
+    (draw_item_fields); textures: list of HxWx4 uint8 arrays (or None)."""
     _raster_protos(orc.lib)
     arr = (OrDrawItem * len(items))()
     keep = []
-    for k, (v, idx, inst) in enumerate(items):
-        v = np.ascontiguousarray(v); idx = np.ascontiguousarray(idx); inst = np.ascontiguousarray(inst)
-        keep += [v, idx, inst]
-        arr[k] = OrDrawItem(v.ctypes.data, len(v), idx.ctypes.data, len(idx), 0, 0, inst.ctypes.data, len(inst))
+    for k, item in enumerate(items):
+        arr[k] = OrDrawItem(*draw_item_fields(item, keep))
     tex = (OrTexture * max(1, len(textures or [])))()
     for k, t in enumerate(textures or []):
         if t is not None:
