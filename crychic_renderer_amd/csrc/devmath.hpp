@@ -8,6 +8,21 @@
 // equal to the definitions for EVERY binary32 input by tools/exact_math_probe.hip (tests/test_gpu_exact_math.py runs it);
 // on the host (tests/hostsim) they are the definitions themselves.  Transcendentals follow fixed polynomial recurrences,
 // so results do not depend on a vendor math library.
+//
+// Three tiers hold every primitive here to its definition, bit for bit (any NaN equal to any NaN), DESIGN.md 3:
+//   1. the definition on the CPU: the test oracle's own function for the primitive, IEEE division and explicit compares;
+//   2. the host build of this header, its `#else` branches (tests/hostsim hs_eval_array; tests/test_devmath_lattice_host.py);
+//   3. the device build, with the product's flag set (tests/devmath_dev; tests/test_devmath_gpu.py) -- the only tier that compiles
+//      the `__HIP_DEVICE_COMPILE__` branches.
+// Exhaustive: half_to_float, unorm16_to_float, unorm8_to_float, d24_to_float (every value of the format, tiers 2 and 3); rcp,
+// len_from_sq, inv_len_from_sq, rcp2, inv_len_from_sq2 (all 2^32 patterns) and rcp_normal, rcp_normal2 (every pattern of their
+// domain) on the device by tools/exact_math_probe.hip.  Lattice-checked (every upper half-word x 256 lower ones, plus each
+// algorithm's breakpoints +- 8 ulp): everything else -- det_sin / det_cos, det_log2, det_exp2, det_pow, pow_inv_gamma(2), divf,
+// clamp_len2, sqrt_clamped, saturate, maxnn, sign1, signf, lerpf, float_to_unorm8 / 16, texel_index, bilinear_setup, mul24.
+// Stated domains (what a caller must guarantee; outside them the device returns something else than the host build):
+//   rcp_normal, rcp_normal2: 2^-126 <= |b| <= 2^126;  sqrt_clamped: [2^-100, 2^100];  mul24: operands below 2^24;
+//   clamp_len2 (and the length functions through it), texel_index: no signaling NaN -- they are v_med3_f32 on the device, and
+//   their arguments are arithmetic results; tests/test_snan_frames_*.py put signaling NaNs into every plane to hold callers to it.
 #pragma once
 #include <stdint.h>
 

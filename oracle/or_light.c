@@ -380,26 +380,67 @@ float or_det_log2f(float x) { return or_det_log2f_(x); }
 float or_det_exp2f(float x) { return or_det_exp2f_(x); }
 float or_det_powf(float x, float y) { return or_det_powf_(x, y); }
 
-/* Batch evaluation of the scalar definitions (unit tests compare them with the product's device math compiled
- * for the host).  kind: 0 sin, 1 cos, 2 log2, 3 exp2, 4 pow(in, in2), 5 nrand(in, in2), 6 d24 decode (in = bits),
- * 7 unorm16 decode, 8 unorm8 decode, 9 half decode, 10 pow(in, 1/2.2) of the tone map. */
-void or_eval_array(int kind, size_t n, const float* in, const float* in2, float* out)
+/* Batch evaluation of the scalar definitions (unit tests compare them with the product's device math compiled for the host,
+ * tests/hostsim hs_eval_array, and run on the device, tests/devmath_dev: the same kind numbers in all three places).
+ * in / in2 are float arrays whose BITS are the argument where the argument is an integer; an integer result is returned as bits.
+ *    0 sin   1 cos   2 log2   3 exp2   4 pow(in, in2)   5 nrand(in, in2)   6 d24 decode   7 unorm16 decode   8 unorm8 decode
+ *    9 half decode   10, 11 pow(in, 1/2.2) of the tone map (11: the product's packed form, second lane)
+ *   12 rcp   13 rcp (the product's rcp_normal, 2^-126 <= |in| <= 2^126)   14 in / in2   15 clamp_len2   16 sqrt (the product's
+ *   sqrt_clamped, [2^-100, 2^100])   17 length from the squared length   18 inverse length
+ *   19 .. 24 rcp, rcp, inverse length of in (the product's packed forms: rcp2 .x .y, rcp_normal2 .x .y, inv_len_from_sq2 .x .y with
+ *   in2 in the other lane)   25 pow(in, 1/2.2) (packed form, first lane)
+ *   26 saturate   27 max(in, in2)   28, 29 sign (the product's sign1, signf)   30 lerp(in, in2, 0.37)   31 lerp(0.04, in2, in)
+ *   32 UNORM8 write   33 UNORM16 write   34 texel index of the floored coordinate in, dim = bits of in2
+ *   35 + 4 s + o: output o (i0, j0, fx, fy) of the bilinear set-up of (in, in2) on a w x h texture, (w, h) = or_eval_sizes[s]
+ *   51 the product of the bits of in and in2 (both below 2^24), low 32 bits */
+static const uint32_t or_eval_sizes[4][2] = { { 2u, 16u }, { 16u, 130u }, { 130u, 16384u }, { 16384u, 2u } };
+static inline float eval_one(int kind, float a, float b)
 {
-    const uint32_t* bits = (const uint32_t*)in;
-    for (size_t i = 0; i < n; ++i) {
-        switch (kind) {
-        case 0: out[i] = or_det_sinf_(in[i]); break;
-        case 1: out[i] = or_det_cosf_(in[i]); break;
-        case 2: out[i] = or_det_log2f_(in[i]); break;
-        case 3: out[i] = or_det_exp2f_(in[i]); break;
-        case 4: out[i] = or_det_powf_(in[i], in2[i]); break;
-        case 5: out[i] = nrand(in[i], in2[i]); break;
-        case 6: out[i] = or_d24(bits[i]); break;
-        case 7: out[i] = or_unorm16((uint16_t)bits[i]); break;
-        case 8: out[i] = or_unorm8((uint8_t)bits[i]); break;
-        case 9: out[i] = or_half_bits_to_float((uint16_t)bits[i]); break;
-        case 10: out[i] = or_pow_inv_gamma(in[i]); break;
-        default: out[i] = 0.0f;
+    const uint32_t ua = or_float_to_bits(a), ub = or_float_to_bits(b);
+    switch (kind) {
+    case 0: return or_det_sinf_(a);
+    case 1: return or_det_cosf_(a);
+    case 2: return or_det_log2f_(a);
+    case 3: return or_det_exp2f_(a);
+    case 4: return or_det_powf_(a, b);
+    case 5: return nrand(a, b);
+    case 6: return or_d24(ua);
+    case 7: return or_unorm16((uint16_t)ua);
+    case 8: return or_unorm8((uint8_t)ua);
+    case 9: return or_half_bits_to_float((uint16_t)ua);
+    case 10: case 11: case 25: return or_pow_inv_gamma(a);
+    case 12: case 13: case 19: case 20: case 21: case 22: return or_rcp(a);
+    case 14: return or_div(a, b);
+    case 15: return or_clamp_len2(a);
+    case 16: return sqrtf(a);
+    case 17: return or_len(a);
+    case 18: case 23: case 24: return or_inv_len(a);
+    case 26: return or_saturate(a);
+    case 27: return or_max0(a, b);
+    case 28: case 29: return or_sign(a);
+    case 30: return or_lerp(a, b, 0.37f);
+    case 31: return or_lerp(0.04f, b, a);
+    case 32: return or_bits_to_float((uint32_t)or_to_unorm8(a));
+    case 33: return or_bits_to_float((uint32_t)or_to_unorm16(a));
+    case 34: return or_bits_to_float((uint32_t)or_texel_index(a, ub));
+    case 51: return or_bits_to_float(ua * ub);
+    default: break;
+    }
+    if (kind >= 35 && kind < 51) {
+        const uint32_t* wh = or_eval_sizes[(kind - 35) >> 2];
+        const or_bilin s = or_bilinear_setup(a, b, wh[0], wh[1]);
+        switch ((kind - 35) & 3) {
+        case 0: return or_bits_to_float((uint32_t)s.i0);
+        case 1: return or_bits_to_float((uint32_t)s.j0);
+        case 2: return s.fx;
+        default: return s.fy;
         }
     }
+    return 0.0f;
+}
+void or_eval_array(int kind, size_t n, const float* in, const float* in2, float* out)
+{
+    uint32_t* obits = (uint32_t*)out;
+#pragma omp parallel for schedule(static) if (n >= 65536)
+    for (long long i = 0; i < (long long)n; ++i) obits[i] = or_float_to_bits(eval_one(kind, in[i], in2[i]));
 }

@@ -24,12 +24,13 @@ typedef struct or_bilin {
     float fx, fy; /* weights of the +1 texels */
 } or_bilin;
 
-/* Clamp the (already floored) coordinate into [-2, dim+1] so the int conversion is defined; anything
- * non-finite maps to -2 (fully out of range). */
+/* Clamp the (already floored) coordinate into [-2, dim] so the int conversion is defined; NaN maps to -2.  A footprint
+ * whose top-left texel is -2 or dim consists of out-of-range texels only, like the one it stands in for (until the
+ * device tier compared the index on its own this bound was dim + 1, the kernels' dim; no sampler can tell the two apart). */
 static inline int or_texel_index(float fl, uint32_t dim)
 {
     if (!(fl >= -2.0f)) return -2;
-    if (fl > (float)dim + 1.0f) return (int)dim + 1;
+    if (fl > (float)dim) return (int)dim;
     return (int)fl;
 }
 

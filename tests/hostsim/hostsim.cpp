@@ -8,6 +8,7 @@
 #include "light_bind.hpp"
 #include "raster_core.hpp"
 #include "host_light.hpp"
+#include "devmath_eval.hpp"
 #include <type_traits>
 #include <vector>
 
@@ -53,28 +54,12 @@ uint32_t hs_check_d24_threshold(void)
     return bad;
 }
 
-// kind: 0 sin, 1 cos, 2 log2, 3 exp2, 4 pow, 5 nrand, 6 d24, 7 unorm16, 8 unorm8, 9 half, 10 pow(., 1/2.2) (same numbering as or_eval_array);
-// 11: pow(., 1/2.2) through the packed form
+// The kinds of or_eval_array (oracle/or_light.c lists them), each through the product's primitive: devmath_eval.hpp, which the
+// device harness (tests/devmath_dev) compiles as well; 5, nrand, is light_core.hpp's and has no device kind.
 void hs_eval_array(int kind, size_t n, const float* in, const float* in2, float* out)
 {
-    const uint32_t* bits = (const uint32_t*)in;
-    for (size_t i = 0; i < n; ++i) {
-        switch (kind) {
-        case 0: out[i] = det_sin(in[i]); break;
-        case 1: out[i] = det_cos(in[i]); break;
-        case 2: out[i] = det_log2(in[i]); break;
-        case 3: out[i] = det_exp2(in[i]); break;
-        case 4: out[i] = det_pow(in[i], in2[i]); break;
-        case 5: out[i] = nrand(in[i], in2[i]); break;
-        case 6: out[i] = d24_to_float(bits[i]); break;
-        case 7: out[i] = unorm16_to_float(bits[i]); break;
-        case 8: out[i] = unorm8_to_float(bits[i]); break;
-        case 9: out[i] = half_to_float((uint16_t)bits[i]); break;
-        case 10: out[i] = pow_inv_gamma(in[i]); break;
-        case 11: out[i] = pow_inv_gamma2(v2f{ in2[i], in[i] }).y; break;      // the packed form's second lane
-        default: out[i] = 0.0f;
-        }
-    }
+    uint32_t* obits = (uint32_t*)out;
+    for (size_t i = 0; i < n; ++i) obits[i] = kind == 5 ? f2u(nrand(in[i], in2[i])) : devmath_eval(kind, in[i], in2[i]);
 }
 
 static uint32_t g_sky_waves = 0;     // wavefronts the last hs_ssao_path call resolved through the sky shortcut

@@ -45,7 +45,14 @@ def build_host(lib, src, headers):
     return lib
 
 
+DEVMATH_EVAL = os.path.join(ROOT, "tests", "hostsim", "devmath_eval.hpp")      # hs_eval_array's kinds (shared with tests/devmath_dev)
+
+
 def build():
+    # a dependency build_host does not know: a library older than it is built again
+    for lib in (LIB, os.path.join(SAN_DIR, os.path.basename(LIB))):
+        if os.path.exists(lib) and os.path.getmtime(DEVMATH_EVAL) > os.path.getmtime(lib):
+            os.remove(lib)
     return build_host(LIB, SRC, ("ssao_core.hpp", "blur_tiles.hpp", "raster_core.hpp"))
 
 

@@ -5,7 +5,7 @@
 //   rsqrt(x) := (float)(1.0 / sqrt((double)x)) (the oracle's definition; fp64 here, IEEE on the GPU as well)
 // The reference value of each is computed on the GPU by the compiler's IEEE expansions (fp32 division / sqrt with
 // -fhip-fp32-correctly-rounded-divide-sqrt, the default; fp64 for rsqrt).  Prints, per candidate, the number of inputs
-// whose bits differ and the first few of them.  Build: hipcc -O2 --offload-arch=gfx950 -ffp-contract=off
+// whose bits differ and the first few of them.  Build: the product's flag set without -shared (tests/devmath_dev_lib.py build_probe)
 #include <hip/hip_runtime.h>
 #include "../crychic_renderer_amd/csrc/devmath.hpp"
 #include <cstdint>
@@ -146,7 +146,9 @@ __global__ __launch_bounds__(256) void sweep(Tally* t, uint64_t lo, uint64_t hi)
         float x = u2f((uint32_t)u);
         // The length primitives only ever see an arithmetic result (a dot product), and the hardware never produces a signaling
         // NaN: v_med3_f32 treats the two NaN kinds differently, so the sweep quiets them as any preceding mad would.
-        if (WHICH >= 14 && x != x) x = u2f(f2u(x) | 0x00400000u);
+        if ((WHICH == 14 || WHICH == 15 || WHICH == 21 || WHICH == 22) && x != x) x = u2f(f2u(x) | 0x00400000u);
+        // the packed forms: the value under test in one lane, a rotated pattern of it (any class of number) in the other
+        const float o = u2f((((uint32_t)u << 13) | ((uint32_t)u >> 19)) ^ 0x5A5A5A5Au);
         float got, ref;
         if (WHICH == 0) { got = rcp_hw(x); ref = ref_rcp(x); }
         else if (WHICH == 1) { got = rcp_nr1(x); ref = ref_rcp(x); }
@@ -163,7 +165,14 @@ __global__ __launch_bounds__(256) void sweep(Tally* t, uint64_t lo, uint64_t hi)
         else if (WHICH == 12) { got = invsqrt_total(x); ref = def_invsqrt(x); }
         else if (WHICH == 13) { got = cry::rcp(x); ref = def_rcp(x); }                    // the shipped text (csrc/devmath.hpp)
         else if (WHICH == 14) { got = cry::len_from_sq(x); ref = def_len(x); }
-        else { got = cry::inv_len_from_sq(x); ref = def_inv_len(x); }
+        else if (WHICH == 15) { got = cry::inv_len_from_sq(x); ref = def_inv_len(x); }
+        else if (WHICH == 16) { got = cry::rcp_normal(x); ref = def_rcp(x); }            // on its domain (the ranges main() passes)
+        else if (WHICH == 17) { got = cry::rcp2(cry::v2f{ x, o }).x; ref = def_rcp(x); }
+        else if (WHICH == 18) { got = cry::rcp2(cry::v2f{ o, x }).y; ref = def_rcp(x); }
+        else if (WHICH == 19) { got = cry::rcp_normal2(cry::v2f{ x, o }).x; ref = def_rcp(x); }
+        else if (WHICH == 20) { got = cry::rcp_normal2(cry::v2f{ o, x }).y; ref = def_rcp(x); }
+        else if (WHICH == 21) { got = cry::inv_len_from_sq2(cry::v2f{ x, o }).x; ref = def_inv_len(x); }
+        else { got = cry::inv_len_from_sq2(cry::v2f{ o, x }).y; ref = def_inv_len(x); }
         uint32_t a = f2u(got), b = f2u(ref);
         if (got != got) a = 0x7FC00000u;       // any NaN == any NaN
         if (ref != ref) b = 0x7FC00000u;
@@ -203,9 +212,26 @@ int main(int argc, char** argv)
             if (run<13>("rcp (devmath.hpp) vs or_rcp", c[0], c[1], d)) return 1;
             if (run<14>("len_from_sq vs or_len", c[0], c[1], d)) return 1;
             if (run<15>("inv_len_from_sq vs or_inv_len", c[0], c[1], d)) return 1;
+            if (run<17>("rcp2.x vs or_rcp", c[0], c[1], d)) return 1;
+            if (run<18>("rcp2.y vs or_rcp", c[0], c[1], d)) return 1;
+            if (run<21>("inv_len_from_sq2.x vs or_inv_len", c[0], c[1], d)) return 1;
+            if (run<22>("inv_len_from_sq2.y vs or_inv_len", c[0], c[1], d)) return 1;
+        }
+        // rcp_normal and its packed form promise 2^-126 <= |b| <= 2^126 (0x00800000 .. 0x7E800000 and the same with the sign bit): every pattern of that domain
+        const uint32_t dom[2][2] = { { 0x00800000u, 0x7E800001u }, { 0x80800000u, 0xFE800001u } };
+        for (auto& c : dom) {
+            if (run<16>("rcp_normal vs or_rcp", c[0], c[1], d)) return 1;
+            if (run<19>("rcp_normal2.x vs or_rcp", c[0], c[1], d)) return 1;
+            if (run<20>("rcp_normal2.y vs or_rcp", c[0], c[1], d)) return 1;
         }
         // 0xFFFFFFFF itself (a NaN): the half-open ranges above stop just short of it
         if (run<13>("rcp (devmath.hpp) vs or_rcp", 0xFFFFFFFFull, 0x100000000ull, d)) return 1;
+        if (run<14>("len_from_sq vs or_len", 0xFFFFFFFFull, 0x100000000ull, d)) return 1;
+        if (run<15>("inv_len_from_sq vs or_inv_len", 0xFFFFFFFFull, 0x100000000ull, d)) return 1;
+        if (run<17>("rcp2.x vs or_rcp", 0xFFFFFFFFull, 0x100000000ull, d)) return 1;
+        if (run<18>("rcp2.y vs or_rcp", 0xFFFFFFFFull, 0x100000000ull, d)) return 1;
+        if (run<21>("inv_len_from_sq2.x vs or_inv_len", 0xFFFFFFFFull, 0x100000000ull, d)) return 1;
+        if (run<22>("inv_len_from_sq2.y vs or_inv_len", 0xFFFFFFFFull, 0x100000000ull, d)) return 1;
         CHK(hipFree(d));
         return 0;
     }
