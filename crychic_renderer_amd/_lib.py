@@ -24,6 +24,7 @@ CUBE_SH_BYTES = 512           # CRYCHIC_CUBE_SH_BYTES: the environment tail (144
 GBUFFER_G0_F16, GBUFFER_G1_F16, GBUFFER_G2_F16 = 0x1000, 0x2000, 0x4000
 GBUFFER_F16_MASK = 0x7000
 COMM_ID_BYTES = 128
+AA_MAX_SEARCH = 16            # CRYCHIC_AA_MAX_SEARCH: the longest end search of crychic_antialias, in pixels
 
 
 class Light(C.Structure):
@@ -83,6 +84,19 @@ class SpotShadows(C.Structure):
 class PointShadows(C.Structure):
     """crychic_point_shadows: the first `count` point lights read the six faces at maps[k] through shadowProj[k] (extension)."""
     _fields_ = [("count", C.c_uint32), ("dim", C.c_uint32), ("maps", C.c_void_p * 4), ("shadowProj", (C.c_float * 16) * 4)]
+
+
+class AAParams(C.Structure):
+    """crychic_aa_params: the knobs of crychic_antialias (extension); AAParams.default() = crychic_aa_default_params."""
+    _fields_ = [("absMin", C.c_uint32), ("relShift", C.c_uint32), ("searchSteps", C.c_uint32), ("subpix", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **fields):
+        p = cls()
+        check(lib.crychic_aa_default_params(C.byref(p)))
+        for k, v in fields.items():
+            setattr(p, k, int(v))
+        return p
 
 
 class PassTimes(C.Structure):
@@ -177,6 +191,8 @@ PROTOTYPES = {
     "crychic_build_env_brdf": (_i, [_vp, _vp, _vp]),
     "crychic_cube_probe_offset": (_sz, [_u32, _u32]),
     "crychic_set_cube_probe_volume": (_i, [_vp, _vp, _P(_f), _P(_f), _P(_f), _vp]),
+    "crychic_aa_default_params": (_i, [_P(AAParams)]),
+    "crychic_antialias": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(AAParams), _vp]),
     "crychic_save_ppm": (_i, [C.c_char_p, _vp, _u32, _u32]),
     "crychic_raster_workspace_bytes": (_sz, [C.c_uint64, _u32, _u32]),
     "crychic_raster_status": (_i, [_vp, _vp, _P(_u32)]),

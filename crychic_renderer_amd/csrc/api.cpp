@@ -18,6 +18,7 @@
 #include "blur_tiles.hpp"
 #include "raster_core.hpp"
 #include "cube_mips_core.hpp"
+#include "post_aa_core.hpp"
 #include "internal.hpp"
 
 namespace {
@@ -767,6 +768,42 @@ int crychic_prefilter_cube_chain(crychic_ctx* ctx, const uint8_t* src_chain_dev,
     const size_t bytes = crychic_cube_chain_bytes(dim, levels);
     if (s < d + bytes && d < s + bytes) return fail(CRYCHIC_E_INVALID_ARG, "the source and destination chains overlap");
     CRY_HIP(cry::launch_cube_prefilter(src_chain_dev, dst_chain_dev, dim, levels, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(CRYCHIC_AA_MAX_SEARCH == cry::kAaMaxSearch && sizeof(crychic_aa_params) == sizeof(cry::PostAaParams), "post_aa_core.hpp mirrors the ABI");
+
+int crychic_aa_default_params(crychic_aa_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    out->absMin = 2048u; out->relShift = 3u; out->searchSteps = 12u; out->subpix = 192u;
+    return 0;
+}
+
+int crychic_antialias(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0,
+                      uint32_t rows, const crychic_aa_params* params, void* stream)
+{
+    // every argument is checked before the context is looked at: a refusal needs no device
+    if (!in_rgba8_dev || !out_rgba8_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
+    // 2^28 pixels: 32-bit texel coordinates and plane offsets below 2^30; 32 rows per workgroup row, grid.y <= 65535
+    if ((uint64_t)W * H > (1ull << 28) || H > 32u * 65535u)
+        return fail(CRYCHIC_E_UNSUPPORTED, "frame %ux%u exceeds 2^28 pixels or 2097120 rows", W, H);
+    if (row0 > H || rows > H - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row frame", row0, rows, H);
+    crychic_aa_params p;
+    crychic_aa_default_params(&p);
+    if (params) p = *params;
+    if (p.relShift > 31u) return fail(CRYCHIC_E_INVALID_ARG, "anti-aliasing relShift %u outside 0 .. 31", p.relShift);
+    if (p.searchSteps == 0 || p.searchSteps > CRYCHIC_AA_MAX_SEARCH)
+        return fail(CRYCHIC_E_INVALID_ARG, "anti-aliasing searchSteps %u outside 1 .. %d", p.searchSteps, CRYCHIC_AA_MAX_SEARCH);
+    if (p.subpix > 256u) return fail(CRYCHIC_E_INVALID_ARG, "anti-aliasing subpix %u outside 0 .. 256", p.subpix);
+    const uintptr_t s = reinterpret_cast<uintptr_t>(in_rgba8_dev), d = reinterpret_cast<uintptr_t>(out_rgba8_dev);
+    if ((s | d) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "anti-aliasing planes are not 4-byte aligned");
+    const size_t bytes = (size_t)W * H * 4u;
+    if (s < d + bytes && d < s + bytes) return fail(CRYCHIC_E_INVALID_ARG, "the anti-aliasing input and output planes overlap (the pass cannot run in place)");
+    if (int rc = bind(ctx)) return rc;
+    const cry::PostAaParams q = { p.absMin, p.relShift, p.searchSteps, p.subpix };
+    CRY_HIP(cry::launch_post_aa(in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, q, (hipStream_t)stream));
     return 0;
 }
 

@@ -85,6 +85,12 @@ hipError_t launch_cube_probe_volume(void* tail, const float pos[3], const float 
 // caller has checked the pointer and its alignment.
 hipError_t launch_env_brdf(void* table, hipStream_t stream);
 
+// post_aa.hip: rows [row0, row0 + rows) of the anti-aliased W x H RGBA8 frame `out` from `in` (post_aa_core.hpp); one launch on
+// `stream`, none for rows == 0.  The caller has checked the pointers, their alignment and overlap, the sizes, the rows and `p`.
+struct PostAaParams;
+hipError_t launch_post_aa(const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const PostAaParams& p,
+                          hipStream_t stream);
+
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
 struct Texture;

@@ -1,6 +1,6 @@
 """python -m crychic_renderer_amd.demo [--size WxH] [--out frame.ppm] [--textures DIR] [--cube FILE.dds] [--gbuffer f32|mixed|f16]
                                    [--capture-env X,Y,Z [--capture-dim N]] [--gloss] [--env-ambient] [--env-specular]
-                                   [--probe-box X0,Y0,Z0,X1,Y1,Z1]
+                                   [--probe-box X0,Y0,Z0,X1,Y1,Z1] [--aa]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
@@ -20,7 +20,9 @@ sheen.
 --probe-box (with --capture-env and --gloss): the axis-aligned proxy box of the captured surroundings.  The capture writes its
 position and the box into the chain's environment tail (capture_environment(probe_box=...)) and the reflection lookup is box-projected
 through it (set_cube_map(parallax=True)): a box's reflection in the floor meets the box at its foot instead of sliding with the
-camera."""
+camera.
+--aa: the finished frame goes through the post-process anti-aliasing pass (Crychic.antiAliasing = True: crychic_antialias after the
+lighting pass, the deferred path's stand-in for the framework's 4x MSAA switch) and the anti-aliased buffer is what is written."""
 import argparse
 import ctypes as C
 
@@ -47,6 +49,7 @@ def main():
     ap.add_argument("--env-specular", action="store_true", help="weigh the glossy reflection by the environment BRDF table (needs --gloss)")
     ap.add_argument("--probe-box", default="", metavar="X0,Y0,Z0,X1,Y1,Z1", help="box-project the captured reflections through this box around "
                                                                                  "the capture position (needs --capture-env and --gloss)")
+    ap.add_argument("--aa", action="store_true", help="anti-alias the finished frame (post-process pass) and write the anti-aliased buffer")
     a = ap.parse_args()
     box = None
     if a.probe_box:
@@ -112,11 +115,13 @@ def main():
         app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient, env_brdf=a.env_specular,
                          parallax=box is not None)
         print("captured the environment at (%g, %g, %g): %d-texel faces, %d levels" % (pos[0], pos[1], pos[2], dim, levels))
+    if a.aa:
+        app.antiAliasing = True
     app.Draw()
     torch.cuda.synchronize()
-    img = np.ascontiguousarray(app.mBackBuffer.cpu().numpy())
+    img = np.ascontiguousarray((app.mBackBufferAA if a.aa else app.mBackBuffer).cpu().numpy())
     check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, W, H))
-    print("wrote %s (%dx%d) on %s" % (a.out, W, H, ctx.device_name))
+    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, ", anti-aliased" if a.aa else "", ctx.device_name))
 
 
 if __name__ == "__main__":

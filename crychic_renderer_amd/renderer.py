@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (CrychicError, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -215,6 +215,8 @@ class Crychic:
         self._pointHost = None       # host copy of the point lights (the face transforms are built from it)
         self._pointShadow = None     # (PointShadows descriptor, [face pass constants, 6 per light], geometry)
         self._desc = None
+        self.antiAliasing = None     # extension: None | True | AAParams -- Draw() of a whole frame runs crychic_antialias into mBackBufferAA
+        self.mBackBufferAA = None    # the anti-aliased frame, allocated by the first antialias() that needs it
 
     def set_gbuffer_formats(self, formats):
         """Re-allocates the G-buffer in the given formats (gbuffer_formats: "f32", "mixed", "f16" or three per-plane formats); its
@@ -273,7 +275,11 @@ class Crychic:
 
     def Draw(self, row0=0, rows=None, shared=None):  # CRYCHIC.cpp:172-306 (hot part)
         """shared = (communicator handle, bounds array or None, parts): crychic_draw_hot_path_shared -- the strip AND its exchange,
-        the lighting pass in `parts` row ranges that travel while the next is lit (sharding.StripExchange.draw)."""
+        the lighting pass in `parts` row ranges that travel while the next is lit (sharding.StripExchange.draw).
+        antiAliasing = True or an AAParams (extension): a whole frame, then crychic_antialias over it into mBackBufferAA; mBackBuffer is
+        the frame without it.  A strip or a shared draw then raises CrychicError."""
+        if self.antiAliasing:
+            return self._draw_antialiased(row0, rows, shared)
         # The descriptor only changes when a plane is re-allocated or a knob is turned: keep it across frames so the
         # per-frame host cost is one FFI call (matters once a strip takes tens of microseconds on 8 GPUs).  The key holds
         # every device pointer and size frame_desc() reads, so replacing any plane object invalidates the cached descriptor.
@@ -330,6 +336,35 @@ class Crychic:
             return
         check(lib.crychic_draw_hot_path(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(self.mMainPassCB), C.byref(f),
                                         _stream(self.ctx.device)))
+
+    def _draw_antialiased(self, row0, rows, shared):
+        """Draw() with antiAliasing set: the frame as Draw() issues it without, then the pass over it into mBackBufferAA."""
+        if shared is not None or row0 != 0 or (rows is not None and rows != self.mClientHeight):
+            raise CrychicError(-1, "antiAliasing is set: Draw() takes the whole frame on one GPU (the pass is not sharded and does not run "
+                               "behind the exchange)")
+        aa, self.antiAliasing = self.antiAliasing, None
+        try:
+            self.Draw()
+        finally:
+            self.antiAliasing = aa
+        self.antialias(params=aa if isinstance(aa, AAParams) else None)
+
+    def antialias(self, src=None, out=None, row0=0, rows=None, params=None):
+        """crychic_antialias on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferAA, allocated on first
+        use) from `src` (default: mBackBuffer), both (H, W, 4) uint8 tensors; params: an AAParams, None = the defaults.  The pass reads
+        rows [row0 - 16, row0 + rows + 16) of `src` and writes no other byte of `out`.  Returns `out`."""
+        src = self.mBackBuffer if src is None else src
+        if out is None:
+            if self.mBackBufferAA is None or self.mBackBufferAA.shape != src.shape or self.mBackBufferAA.device != src.device:
+                self.mBackBufferAA = torch.zeros_like(src)
+            out = self.mBackBufferAA
+        H, W = int(src.shape[0]), int(src.shape[1])
+        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
+                or not src.is_contiguous() or not out.is_contiguous():
+            raise CrychicError(-1, "antialias takes contiguous (H, W, 4) uint8 tensors of one shape")
+        check(lib.crychic_antialias(self.ctx.handle, _ptr(src), _ptr(out), W, H, int(row0), int(H - row0 if rows is None else rows),
+                                    None if params is None else C.byref(params), _stream(self.ctx.device)))
+        return out
 
     def set_cube_map(self, cube, dim=None, levels=1, gloss=False, ambient_sh=False, env_brdf=False, parallax=False):
         """The sky cube map: a 6 x dim x dim x 4 uint8 tensor (level 0 alone), or -- with `levels` > 1 -- the flat mip chain

@@ -164,6 +164,7 @@ public:
         mDepthStencilBuffer = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
         CrychicHipThrowIfFailed(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(mDepthStencilBuffer->Data()), 0x00FFFFFF, n));
         mBackBuffer = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
+        if (mAntiAliasing) mBackBufferAA = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
         mCamera.SetLens(0.25f * 3.1415926535f, AspectRatio(), 1.0f, 100.0f);                       // :114
         if (mSsao) { mSsao->OnResize(mClientWidth, mClientHeight); mSsao->RebuildDescriptors(mDepthStencilBuffer.get()); }
         if (mDeferred) { mDeferred->OnResize(mClientWidth, mClientHeight); mDeferred->BuildDescriptors(); }
@@ -204,6 +205,9 @@ public:
 
     void Draw(const GameTimer&)  // CRYCHIC.cpp:172-306, deferred branch
     {
+        if (mAntiAliasing && (!mWholeFrame || mComm))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (anti-aliasing takes the whole frame on one GPU: no SetStrip / JoinNode)",
+                                   __FILE__, __LINE__);
         if (mRunProducerPasses) {
             DrawSceneToShadowMap();                                                                 // :208
             if (mFuseCameraPasses) DrawNormalsDepthAndGBuffer();                                    // :214 + :236 on one rasterisation
@@ -275,10 +279,38 @@ public:
                                                                              mExchangeParts, spots, L.mNumSpotLights, &sh, mCommandList->Stream()));
         else
             CrychicThrowIfFailed(crychic_draw_hot_path_spots_shadowed(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, L.mNumSpotLights, &sh, mCommandList->Stream()));
+        // SetAntiAliasing: the finished frame through the post-process pass into the second back buffer, behind the lighting pass
+        if (mAntiAliasing)
+            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), static_cast<const uint8_t*>(mBackBuffer->Data()),
+                                                   static_cast<uint8_t*>(mBackBufferAA->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
+                                                   &mAAParams, mCommandList->Stream()));
         // :300-305: advance the fence and signal it behind this frame's commands
         mCurrFrameResource->Fence = ++mCurrentFence;
         CrychicHipThrowIfFailed(hipEventRecord(mCurrFrameResource->FenceEvent, mCommandList->Stream()));
     }
+
+    // ---- anti-aliasing (extension) ----------------------------------------------------------------------------------------------
+    // The deferred path's stand-in for the framework's Set4xMsaaState (Common/d3dApp.cpp:60-70, F2 at :367): MSAA does not compose
+    // with a G-buffer, so edges are smoothed by a post-process pass over the finished frame (include/crychic_hip.h
+    // crychic_antialias).  On: Draw issues the pass after the lighting pass of a whole frame, into a second back buffer that OnResize
+    // re-creates, and Present writes that buffer; CurrentBackBuffer stays the frame without it.  p == nullptr: the default
+    // parameters.  With it on, SetStrip / JoinNode make Draw throw (the pass is not sharded).  Off (the default): nothing changes.
+    void SetAntiAliasing(bool on, const crychic_aa_params* p = nullptr)
+    {
+        crychic_aa_params q;
+        CrychicThrowIfFailed(crychic_aa_default_params(&q));
+        if (p) q = *p;
+        if (q.relShift > 31u || q.searchSteps == 0 || q.searchSteps > CRYCHIC_AA_MAX_SEARCH || q.subpix > 256u)
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetAntiAliasing (relShift 0 .. 31, searchSteps 1 .. 16, subpix 0 .. 256)",
+                                   __FILE__, __LINE__);
+        mCommandList->Flush();                                  // a frame in flight may still write the buffer released below
+        mAntiAliasing = on;
+        mAAParams = q;
+        if (on) mBackBufferAA = std::make_unique<ID3D12Resource>((size_t)mClientWidth * mClientHeight * 4, ID3D12Resource::DEFAULT_HEAP);
+        else mBackBufferAA.reset();
+    }
+    bool AntiAliasing() const { return mAntiAliasing; }
+    ID3D12Resource* AntiAliasedBackBuffer() { return mBackBufferAA.get(); }
 
     // ---- local lights (extension: the reference's point and spot branches, PBR.hlsl:109-147, are dead code) -------------------
     // Uploads both lists to device buffers this object owns (at most 1024 each); Draw lights them after the directional lights,
@@ -502,11 +534,12 @@ public:
         SetWholeFrame();
     }
 
-    // mSwapChain->Present (CRYCHIC.cpp:294-297) for a headless build: read the back buffer back and write it as PPM.
+    // mSwapChain->Present (CRYCHIC.cpp:294-297) for a headless build: read the back buffer back and write it as PPM (with
+    // SetAntiAliasing on: the anti-aliased one).
     void Present(const std::string& path)
     {
         std::vector<uint8_t> host((size_t)mClientWidth * mClientHeight * 4);
-        mBackBuffer->Download(host.data(), host.size(), mCommandList->Stream());
+        (mAntiAliasing ? mBackBufferAA : mBackBuffer)->Download(host.data(), host.size(), mCommandList->Stream());
         mCommandList->Flush();
         CrychicThrowIfFailed(crychic_save_ppm(path.c_str(), host.data(), mClientWidth, mClientHeight));
     }
@@ -1000,6 +1033,9 @@ private:
     UINT mStripRow0 = 0, mStripRows = 0;      // this GPU's rows when the frame is shared
     UINT mExchangeParts = 1;                  // SetExchangeParts
     bool mWholeFrame = true;
+    bool mAntiAliasing = false;               // SetAntiAliasing
+    crychic_aa_params mAAParams = {};
+    std::unique_ptr<ID3D12Resource> mBackBufferAA;   // the anti-aliased frame, while mAntiAliasing
     std::unique_ptr<ID3D12Resource> mDepthStencilBuffer, mBackBuffer, mCubeMap;
     std::unique_ptr<ID3D12Resource> mPointLights, mSpotLights;   // SetLocalLights
     uint32_t mNumPointLights = 0, mNumSpotLights = 0;

@@ -809,6 +809,47 @@ size_t crychic_cube_probe_offset(uint32_t dim, uint32_t levels);
 int crychic_set_cube_probe_volume(crychic_ctx* ctx, void* tail_dev, const float pos[3], const float boxMin[3], const float boxMax[3],
                                   void* stream);
 
+/* ---- post-process anti-aliasing of the back buffer (extension) ------------------------------------------
+ * The reference's framework smooths edges with 4x MSAA (Common/d3dApp.cpp:190-191, :367, :518), which does not compose with a
+ * deferred G-buffer; this is the deferred path's stand-in: one pass over the finished RGBA8 frame, a separate call after the
+ * lighting pass.  FXAA-class, and defined entirely in 32-bit integer arithmetic, so the device, a host build and the checker
+ * (tests/post_aa_ref) agree bit for bit.  A build definition: nothing of it is the reference's.
+ *
+ * in and out are RGBA8 planes, W x H, W and H >= 1 (odd sizes are valid: no half-resolution map is involved).  Every coordinate
+ * clamps to the frame edge, never to the row range of a call.  Luma of a texel: L = 77 R + 150 G + 29 B (0 .. 65280).
+ * For pixel (x, y), with M, N, S, E, W and NW, NE, SW, SE the lumas of its 3 x 3 neighbourhood:
+ *   1 early copy    hi / lo = max / min of M, N, S, E, W; range = hi - lo.  If range == 0 or range < max(absMin, hi >> relShift):
+ *                   out = in for this pixel (all four channels).
+ *   2 orientation   horz = |NW - 2W + SW| + 2 |N - 2M + S| + |NE - 2E + SE|,  vert = |NW - 2N + NE| + 2 |W - 2M + E| + |SW - 2S + SE|;
+ *                   the edge is horizontal iff horz >= vert.
+ *   3 side          (a, b) = (N, S) if horizontal, else (W, E); gA = |a - M|, gB = |b - M|; the across-neighbour is the a side iff
+ *                   gA >= gB; g = max(gA, gB); nb = the across-neighbour's luma; Lp = M + nb.
+ *   4 end search    in each of the two directions along the edge, for i = 1 .. K: q = the pixel i steps along, q' = its neighbour on
+ *                   the chosen side, d = L(q) + L(q') - Lp; stop at the first i with 2 |d| >= g.  The distance is that i, or K if no
+ *                   step stopped; the end delta is the last d computed: (dn, en) for the negative direction, (dp, ep) for the positive.
+ *   5 edge weight   (dmin, e) = (dn, en) if dn <= dp, else (dp, ep);  wE = 128 - (256 dmin) / (dn + dp) (integer division) if
+ *                   (e < 0) != (M - nb < 0), else 0.
+ *   6 sub-pixel     s = 2 (N + S + E + W) + NW + NE + SW + SE;  t = |s - 12 M|;  r = min(256, (256 t) / (12 range));
+ *                   r2 = (r r (768 - 2 r)) >> 16;  wS = (((r2 r2) >> 8) subpix) >> 8.
+ *   7 blend         w = max(wE, wS) (0 .. 256); per channel c: out_c = (in_c(x, y) (256 - w) + in_c(across-neighbour) w + 128) >> 8.
+ * No intermediate exceeds 2^32.  Known answers: a uniform frame, or one whose ranges stay below the threshold, comes back unchanged;
+ * a straight axis-aligned black / white edge changes only the two pixel columns (rows) beside it, each by w = 12 under the defaults.
+ *
+ * Parameters: absMin (default 2048, any value), relShift (3; 0 .. 31), searchSteps = K (12; 1 .. CRYCHIC_AA_MAX_SEARCH) and subpix
+ * (192; 0 .. 256).  crychic_aa_default_params fills the defaults (pure host code; CRYCHIC_E_INVALID_ARG for NULL). */
+#define CRYCHIC_AA_MAX_SEARCH 16
+typedef struct crychic_aa_params { uint32_t absMin, relShift, searchSteps, subpix; } crychic_aa_params;   /* 16 bytes */
+int crychic_aa_default_params(crychic_aa_params* out);
+/* Writes output rows [row0, row0 + rows) of out_rgba8_dev and no other byte of it; in_rgba8_dev must hold valid pixels for rows
+ * [row0 - 16, row0 + rows + 16) cut to [0, H), and no other row of it is read.  Stitched row ranges therefore equal the whole-frame
+ * call byte for byte, for any row0 and rows.  params == NULL = the defaults.  One launch on `stream`: no allocation, no
+ * synchronisation, no host read-back; capturable into a graph.  Planes are 4-byte aligned; with W a multiple of 4 and both planes
+ * 16-byte aligned the pass moves 16 bytes per lane.  CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and
+ * before anything is enqueued: a NULL pointer, a misaligned plane, W or H of 0, a row range outside the frame, a parameter outside
+ * its range, in and out overlapping within W * H * 4 bytes.  More than 2^28 pixels or 2097120 rows: CRYCHIC_E_UNSUPPORTED. */
+int crychic_antialias(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H,
+                      uint32_t row0, uint32_t rows, const crychic_aa_params* params /* NULL = defaults */, void* stream);
+
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
  * of 2 rows (half-res alignment); the last rank takes the remainder. */
