@@ -647,6 +647,10 @@ public:
     ID3D12GraphicsCommandList* CommandList() { return mCommandList.get(); }
     ID3D12Device* Device() { return md3dDevice.get(); }
     float AspectRatio() const { return (float)mClientWidth / (float)mClientHeight; }
+    // The built scene, for a caller that edits it between Initialize() and the first Update(): item k of a layer (nullptr past the
+    // end) and a material by name (nullptr if there is none).  After changing a material set its NumFramesDirty = gNumFrameResources.
+    RenderItem* LayerItem(RenderLayer layer, size_t k) { auto& l = mRitemLayer[(int)layer]; return k < l.size() ? l[k] : nullptr; }
+    Material* FindMaterial(const std::string& name) { auto it = mMaterials.find(name); return it == mMaterials.end() ? nullptr : it->second.get(); }
 
     bool mRunProducerPasses = true;   // false: the caller fills the input planes itself (tests, external producers)
     std::unique_ptr<ShadowMap> mShadowMap;

@@ -1,9 +1,11 @@
 // veneer_driver.cpp -- exercises the C++ veneer (include/crychic/*.h) exactly as reference call sites would:
 // CRYCHIC::Initialize / Update / Draw, UploadBuffer::CopyData, Ssao::ComputeSsao ...  Input planes come from raw
 // files written by the pytest side (tests/test_cpp_veneer.py); outputs go back as raw files for comparison with
-// the oracle.  Usage: veneer_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <numDirLights> [scene]
+// the oracle.  Usage: veneer_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <numDirLights> [scene | transforms] [textureDir]
 // With the trailing word `scene` the application also runs its own producer passes on its built-in scene (100 boxes +
-// grid) instead of loading depth / normal / G-buffer / shadow planes from <dir>.
+// grid) instead of loading depth / normal / G-buffer / shadow planes from <dir>.  `transforms` is `scene` with the grid of the
+// camera layer under a World with a rotation and a non-symmetric TexTransform, and its material under a non-symmetric
+// MatTransform (tests/test_cpp_veneer.py holds the same numbers): what UpdateInstanceData and UpdateMaterialBuffer transpose.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -41,10 +43,20 @@ int main(int argc, char** argv)
         app.mBlurCount = std::atoi(argv[6]);
         app.mNumDirLights = std::atoi(argv[7]);
         app.mSkyEnabled = true;
-        const bool sceneMode = argc > 8 && std::string(argv[8]) == "scene";
+        const bool transforms = argc > 8 && std::string(argv[8]) == "transforms";
+        const bool sceneMode = transforms || (argc > 8 && std::string(argv[8]) == "scene");
         app.mRunProducerPasses = sceneMode;
         if (!app.Initialize()) return 3;
         hipStream_t s = app.CommandList()->Stream();
+        if (transforms) {   // row-vector convention, as DirectXMath builds them: v' = v . M
+            RenderItem* grid = app.LayerItem(RenderLayer::Opaque, 1);
+            Material* mat = app.FindMaterial("skullMat");
+            if (!grid || grid->Instances.size() != 1 || !mat || grid->Instances[0].MaterialIndex != (UINT)mat->MatCBIndex) return 7;
+            grid->Instances[0].World = DirectX::XMFLOAT4X4{ { { 2.4f, 0, -1.8f, 0 }, { 0, 3, 0, 0 }, { 1.8f, 0, 2.4f, 0 }, { 0.5f, 0.125f, -0.25f, 1 } } };
+            grid->Instances[0].TexTransform = DirectX::XMFLOAT4X4{ { { 2, 0.5f, 0, 0 }, { -0.25f, 1.5f, 0, 0 }, { 0, 0, 1, 0 }, { 0.125f, 0.375f, 0, 1 } } };
+            mat->MatTransform = DirectX::XMFLOAT4X4{ { { 1.25f, -0.5f, 0, 0 }, { 0.75f, 0.5f, 0, 0 }, { 0, 0, 1, 0 }, { 0.25f, 0.0625f, 0, 1 } } };
+            mat->NumFramesDirty = gNumFrameResources;
+        }
         if (!sceneMode) {
             put(app.DepthStencilBuffer(), dir + "/depth.bin", s);
             put(app.mSsao->NormalMap(), dir + "/normal.bin", s);

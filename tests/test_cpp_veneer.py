@@ -152,3 +152,66 @@ def test_veneer_load_textures(built_lib, oracle, tmp_path, cube_levels):
     flat = raster_util.oracle_frame(oracle, consts, items, shadow_items, g.reference_materials(), None, W, H, SD, cube, BC, NL,
                                     built_lib.lib.crychic_pcf_search_radius(SD, 1), **chain_kw)
     assert not np.array_equal(flat["g1"], ref["g1"])
+
+
+@pytest.mark.gpu
+def test_veneer_transposes_world_and_texture_transforms(built_lib, oracle, tmp_path):
+    """UpdateInstanceData and UpdateMaterialBuffer store World, TexTransform and MatTransform transposed (CRYCHIC.cpp:546-547, 582).
+    The live scene never shows it: its World matrices are symmetric in their 3 x 3 and both texture transforms are identity.  The
+    driver's `transforms` mode puts the grid under a World with a rotation (3 . RotationY with cos 0.8, sin 0.6, plus a
+    translation) and a non-symmetric TexTransform, and its material under a non-symmetric MatTransform; the oracle gets the same
+    scene with the records built here, transposed by hand.  Depth, the normal plane and G0 - G2 are equal bit for bit."""
+    import ctypes as C
+    import raster_util
+    from test_textures import cube_header, mip_header, oracle_cube, oracle_load_mips
+    from crychic_renderer_amd import geometry as g, scene
+    exe = build_driver()
+    W, H, SD, CD, BC, NL = 160, 120, 256, 16, 2, 1
+    d = str(tmp_path)
+    tdir = tmp_path / "Textures"
+    tdir.mkdir()
+    names = ["bricks2.dds", "bricks2_nmap.dds", "tile.dds", "tile_nmap.dds", "white1x1.dds", "default_nmap.dds"]
+    rng = np.random.default_rng(11)
+    masks = (0xFF0000, 0xFF00, 0xFF, 0xFF000000)                      # A8R8G8B8: memory order B, G, R, A
+    for name in names:                                                # noise: a wrong texture coordinate shows at every pixel
+        levels = g.box_mips(rng.integers(0, 256, (32, 32, 4), dtype=np.uint8))
+        (tdir / name).write_bytes(mip_header(32, 32, len(levels), None, masks) + b"".join(np.ascontiguousarray(l[..., [2, 1, 0, 3]]).tobytes() for l in levels))
+    faces = rng.integers(0, 256, (6, CD, CD, 4), dtype=np.uint8)
+    (tdir / "snowcube1024.dds").write_bytes(cube_header(CD, 1, None, masks) + faces.tobytes())
+    np.zeros((6, CD, CD, 4), np.uint8).tofile(d + "/cube.bin")
+    r = subprocess.run([exe, d, str(W), str(H), str(SD), str(CD), str(BC), str(NL), "transforms", str(tdir)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    consts = raster_util.frame_constants(W, H, SD)
+    C.memmove(C.addressof(consts.pass_cb), open(d + "/pass_cb.bin", "rb").read(), C.sizeof(consts.pass_cb))
+    # the driver's matrices as DirectXMath writes them (rows of v' = v . M); a record holds the transpose
+    world = [[2.4, 0, -1.8, 0], [0, 3, 0, 0], [1.8, 0, 2.4, 0], [0.5, 0.125, -0.25, 1]]
+    tex_t = [[2, 0.5, 0, 0], [-0.25, 1.5, 0, 0], [0, 0, 1, 0], [0.125, 0.375, 0, 1]]
+    mat_t = [[1.25, -0.5, 0, 0], [0.75, 0.5, 0, 0], [0, 0, 1, 0], [0.25, 0.0625, 0, 1]]
+    stored = lambda m: np.array([[m[j][i] for j in range(4)] for i in range(4)], np.float32).reshape(16)
+    items = g.cascade_scene_items(cull_camera=scene.default_camera(W, H))
+    grid_inst = items[1][2].copy()
+    assert len(grid_inst) == 1 and grid_inst[0]["MaterialIndex"] == 3
+    grid_inst[0]["World"] = stored(world); grid_inst[0]["TexTransform"] = stored(tex_t)
+    assert len(g.frustum_cull(scene.default_camera(W, H), items[1][0], grid_inst)) == 1       # still in view under its new World
+    items[1] = (items[1][0], items[1][1], grid_inst)
+    mats = g.reference_materials().view(oracle_lib.MATERIAL_DT).copy()
+    mats[3]["MatTransform"] = stored(mat_t)
+    tex = [oracle_load_mips(oracle, str(tdir / n)) for n in names]
+    view, vp = np.array(consts.pass_cb.View, np.float32), np.array(consts.pass_cb.ViewProj, np.float32)
+    nd = oracle_lib.rasterize(oracle, 1, view, vp, items, mats, tex, W, H)
+    gb = oracle_lib.rasterize(oracle, 2, view, vp, items, mats, tex, W, H)
+    grid_px = (gb["depth"] < 0xFFFFFF) & (gb["g1"][..., 3] == mats[3]["Roughness"])
+    assert grid_px.mean() > 0.1                                        # the grid fills a good part of the frame
+    assert np.array_equal(np.fromfile(d + "/depth_out.bin", np.uint32).reshape(H, W), gb["depth"])
+    assert np.array_equal(np.fromfile(d + "/normal_out.bin", np.uint16).reshape(H, W, 4), nd["normal"].view(np.uint16))
+    for i, k in enumerate(("g0", "g1", "g2")):
+        assert np.array_equal(np.fromfile(d + "/g%d_out.bin" % i, np.uint32).reshape(H, W, 4), gb[k].view(np.uint32)), k
+    # each of the three matrices matters: with any one of them left untransposed the oracle renders another image
+    for which in ("World", "TexTransform", "MatTransform"):
+        inst2, mats2 = grid_inst.copy(), mats.copy()
+        if which == "MatTransform":
+            mats2[3]["MatTransform"] = np.array(mat_t, np.float32).reshape(16)
+        else:
+            inst2[0][which] = np.array(world if which == "World" else tex_t, np.float32).reshape(16)
+        other = oracle_lib.rasterize(oracle, 2, view, vp, [items[0], (items[1][0], items[1][1], inst2)], mats2, tex, W, H)
+        assert not all(np.array_equal(other[k], gb[k]) for k in ("g0", "g1", "g2")), which
