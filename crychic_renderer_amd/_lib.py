@@ -25,6 +25,7 @@ GBUFFER_G0_F16, GBUFFER_G1_F16, GBUFFER_G2_F16 = 0x1000, 0x2000, 0x4000
 GBUFFER_F16_MASK = 0x7000
 COMM_ID_BYTES = 128
 AA_MAX_SEARCH = 16            # CRYCHIC_AA_MAX_SEARCH: the longest end search of crychic_antialias, in pixels
+FOG_MAX_STEPS = 64            # CRYCHIC_FOG_MAX_STEPS: the most samples crychic_fog takes along a view ray
 
 
 class Light(C.Structure):
@@ -96,6 +97,26 @@ class AAParams(C.Structure):
         check(lib.crychic_aa_default_params(C.byref(p)))
         for k, v in fields.items():
             setattr(p, k, int(v))
+        return p
+
+
+class FogParams(C.Structure):
+    """crychic_fog_params: the knobs of crychic_fog (extension); FogParams.default() = crychic_fog_default_params.  ambient and sun
+    take an (R, G, B) sequence."""
+    _fields_ = [("density", C.c_float), ("maxDistance", C.c_float), ("steps", C.c_uint32), ("ambient", C.c_uint8 * 4), ("sun", C.c_uint8 * 4),
+                ("reserved", C.c_uint32 * 3)]
+
+    @classmethod
+    def default(cls, **fields):
+        p = cls()
+        check(lib.crychic_fog_default_params(C.byref(p)))
+        for k, v in fields.items():
+            if k in ("ambient", "sun"):
+                setattr(p, k, (C.c_uint8 * 4)(*[int(c) for c in tuple(v)[:3]]))
+            elif k == "steps":
+                p.steps = int(v)
+            else:
+                setattr(p, k, float(v))
         return p
 
 
@@ -193,6 +214,8 @@ PROTOTYPES = {
     "crychic_set_cube_probe_volume": (_i, [_vp, _vp, _P(_f), _P(_f), _P(_f), _vp]),
     "crychic_aa_default_params": (_i, [_P(AAParams)]),
     "crychic_antialias": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(AAParams), _vp]),
+    "crychic_fog_default_params": (_i, [_P(FogParams)]),
+    "crychic_fog": (_i, [_vp, _P(PassConstants), _vp, _P(_vp), _u32, _vp, _vp, _u32, _u32, _u32, _u32, _P(FogParams), _vp]),
     "crychic_save_ppm": (_i, [C.c_char_p, _vp, _u32, _u32]),
     "crychic_raster_workspace_bytes": (_sz, [C.c_uint64, _u32, _u32]),
     "crychic_raster_status": (_i, [_vp, _vp, _P(_u32)]),

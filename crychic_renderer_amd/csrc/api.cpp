@@ -19,6 +19,7 @@
 #include "raster_core.hpp"
 #include "cube_mips_core.hpp"
 #include "post_aa_core.hpp"
+#include "fog_core.hpp"
 #include "internal.hpp"
 
 namespace {
@@ -804,6 +805,64 @@ int crychic_antialias(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* ou
     if (int rc = bind(ctx)) return rc;
     const cry::PostAaParams q = { p.absMin, p.relShift, p.searchSteps, p.subpix };
     CRY_HIP(cry::launch_post_aa(in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, q, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(CRYCHIC_FOG_MAX_STEPS == cry::kFogMaxSteps && sizeof(crychic_fog_params) == 32 && sizeof(crychic_fog_params) == sizeof(cry::FogParams),
+              "fog_core.hpp mirrors the ABI");
+
+int crychic_fog_default_params(crychic_fog_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    *out = crychic_fog_params{};
+    out->density = 0.02f; out->maxDistance = 100.0f; out->steps = 16u;
+    out->ambient[0] = 70; out->ambient[1] = 80; out->ambient[2] = 100;
+    out->sun[0] = 150; out->sun[1] = 140; out->sun[2] = 110;
+    return 0;
+}
+
+int crychic_fog(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32_t* depth_dev, const uint32_t* const shadow_dev[4],
+                uint32_t shadowDim, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                const crychic_fog_params* params, void* stream)
+{
+    // every argument is checked before the context is looked at: a refusal needs no device
+    if (!cb || !depth_dev || !shadow_dev || !in_rgba8_dev || !out_rgba8_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    uintptr_t align = reinterpret_cast<uintptr_t>(depth_dev) | reinterpret_cast<uintptr_t>(in_rgba8_dev) | reinterpret_cast<uintptr_t>(out_rgba8_dev);
+    for (int j = 0; j < 4; ++j) {
+        if (!shadow_dev[j]) return fail(CRYCHIC_E_INVALID_ARG, "null argument (cascade map %d)", j);
+        align |= reinterpret_cast<uintptr_t>(shadow_dev[j]);
+    }
+    if (align & 3u) return fail(CRYCHIC_E_INVALID_ARG, "fog planes and maps are not 4-byte aligned");
+    if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
+    // 2^28 pixels: 32-bit texel indices and plane offsets below 2^30; the grid is one-dimensional, at most 2^27 workgroups
+    if ((uint64_t)W * H > (1ull << 28)) return fail(CRYCHIC_E_UNSUPPORTED, "frame %ux%u exceeds 2^28 pixels", W, H);
+    if (row0 > H || rows > H - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row frame", row0, rows, H);
+    if (shadowDim == 0 || shadowDim > CRYCHIC_MAX_SPOT_SHADOW_DIM)
+        return fail(CRYCHIC_E_INVALID_ARG, "fog shadowDim %u outside 1 .. %d", shadowDim, CRYCHIC_MAX_SPOT_SHADOW_DIM);
+    crychic_fog_params p;
+    crychic_fog_default_params(&p);
+    if (params) p = *params;
+    if (!(p.density >= 0.0f && p.density <= 16.0f)) return fail(CRYCHIC_E_INVALID_ARG, "fog density %g outside 0 .. 16", (double)p.density);
+    if (!(p.maxDistance > 0.0f && p.maxDistance <= 3.40282347e38f))
+        return fail(CRYCHIC_E_INVALID_ARG, "fog maxDistance %g is not a finite positive number", (double)p.maxDistance);
+    if (p.steps == 0 || p.steps > CRYCHIC_FOG_MAX_STEPS) return fail(CRYCHIC_E_INVALID_ARG, "fog steps %u outside 1 .. %d", p.steps, CRYCHIC_FOG_MAX_STEPS);
+    if (p.reserved[0] | p.reserved[1] | p.reserved[2]) return fail(CRYCHIC_E_INVALID_ARG, "fog reserved words must be 0");
+    // the march takes the shadow coordinates as linear along the ray: exact only for an affine transform
+    for (int j = 0; j < 4; ++j) {
+        const float* w = cb->ShadowTransforms[j] + 12;
+        if (!(w[0] == 0.0f && w[1] == 0.0f && w[2] == 0.0f && w[3] == 1.0f))
+            return fail(CRYCHIC_E_INVALID_ARG, "ShadowTransforms[%d] is not affine (last column %g %g %g %g, not 0 0 0 1)", j, (double)w[0], (double)w[1],
+                        (double)w[2], (double)w[3]);
+    }
+    const uintptr_t s = reinterpret_cast<uintptr_t>(in_rgba8_dev), d = reinterpret_cast<uintptr_t>(out_rgba8_dev);
+    const size_t bytes = (size_t)W * H * 4u;
+    if (s != d && s < d + bytes && d < s + bytes)
+        return fail(CRYCHIC_E_INVALID_ARG, "the fog input and output planes overlap (in place takes the same address)");
+    if (int rc = bind(ctx)) return rc;
+    cry::FogParams q;
+    std::memcpy(&q, &p, sizeof q);
+    CRY_HIP(cry::launch_fog(cb->InvViewProj, cb->EyePosW, cb->ShadowTransforms, depth_dev, shadow_dev, shadowDim, in_rgba8_dev, out_rgba8_dev, W, H,
+                            row0, rows, q, (hipStream_t)stream));
     return 0;
 }
 

@@ -91,6 +91,15 @@ struct PostAaParams;
 hipError_t launch_post_aa(const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const PostAaParams& p,
                           hipStream_t stream);
 
+// fog.hip: rows [row0, row0 + rows) of the fogged W x H RGBA8 frame `out` from `in`, the D24 plane `depth` and the four dim x dim
+// cascade maps (fog_core.hpp); invViewProj, eye and shadowTransforms are the pass constants' fields, read before the call returns.
+// One launch on `stream`, none for rows == 0.  The caller has checked the pointers, their alignment and overlap, the sizes, the rows,
+// the transforms and `p`.
+struct FogParams;
+hipError_t launch_fog(const float* invViewProj, const float* eye, const float (*shadowTransforms)[16], const uint32_t* depth,
+                      const uint32_t* const* maps, uint32_t dim, const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0,
+                      uint32_t rows, const FogParams& p, hipStream_t stream);
+
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
 struct Texture;

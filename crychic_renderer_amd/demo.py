@@ -1,6 +1,7 @@
 """python -m crychic_renderer_amd.demo [--size WxH] [--out frame.ppm] [--textures DIR] [--cube FILE.dds] [--gbuffer f32|mixed|f16]
                                    [--capture-env X,Y,Z [--capture-dim N]] [--gloss] [--env-ambient] [--env-specular]
                                    [--probe-box X0,Y0,Z0,X1,Y1,Z1] [--aa]
+                                   [--fog [--fog-density X] [--fog-steps N]]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
@@ -22,7 +23,9 @@ position and the box into the chain's environment tail (capture_environment(prob
 through it (set_cube_map(parallax=True)): a box's reflection in the floor meets the box at its foot instead of sliding with the
 camera.
 --aa: the finished frame goes through the post-process anti-aliasing pass (Crychic.antiAliasing = True: crychic_antialias after the
-lighting pass, the deferred path's stand-in for the framework's 4x MSAA switch) and the anti-aliased buffer is what is written."""
+lighting pass, the deferred path's stand-in for the framework's 4x MSAA switch) and the anti-aliased buffer is what is written.
+--fog: volumetric fog with sun shafts through the cascade maps (Crychic.fog: crychic_fog after the lighting pass, in place on the back
+buffer, in front of --aa); --fog-density (default 0.02) and --fog-steps (default 16, at most 64) set its parameters."""
 import argparse
 import ctypes as C
 
@@ -50,7 +53,12 @@ def main():
     ap.add_argument("--probe-box", default="", metavar="X0,Y0,Z0,X1,Y1,Z1", help="box-project the captured reflections through this box around "
                                                                                  "the capture position (needs --capture-env and --gloss)")
     ap.add_argument("--aa", action="store_true", help="anti-alias the finished frame (post-process pass) and write the anti-aliased buffer")
+    ap.add_argument("--fog", action="store_true", help="volumetric fog with sun shafts through the cascades, after the lighting pass")
+    ap.add_argument("--fog-density", type=float, default=None, metavar="X", help="fog density, 0 .. 16 (default 0.02; needs --fog)")
+    ap.add_argument("--fog-steps", type=int, default=None, metavar="N", help="samples along each view ray, 1 .. 64 (default 16; needs --fog)")
     a = ap.parse_args()
+    if (a.fog_density is not None or a.fog_steps is not None) and not a.fog:
+        ap.error("--fog-density and --fog-steps need --fog")
     box = None
     if a.probe_box:
         if not (a.capture_env and a.gloss):
@@ -68,7 +76,7 @@ def main():
     W, H = (int(v) for v in a.size.lower().split("x"))
     import torch
     from . import Context, Crychic, LIGHT_SKY, SceneGeometry, check, geometry as g, lib, scene
-    from ._lib import PassConstants
+    from ._lib import FogParams, PassConstants
     ctx = Context(0)
     consts = scene.Constants(W, H, a.shadow_dim)
     tex = g.reference_textures(a.textures) if a.textures else g.procedural_textures(64)
@@ -115,13 +123,16 @@ def main():
         app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient, env_brdf=a.env_specular,
                          parallax=box is not None)
         print("captured the environment at (%g, %g, %g): %d-texel faces, %d levels" % (pos[0], pos[1], pos[2], dim, levels))
+    if a.fog:
+        knobs = {k: v for k, v in (("density", a.fog_density), ("steps", a.fog_steps)) if v is not None}
+        app.fog = FogParams.default(**knobs) if knobs else True
     if a.aa:
         app.antiAliasing = True
     app.Draw()
     torch.cuda.synchronize()
     img = np.ascontiguousarray((app.mBackBufferAA if a.aa else app.mBackBuffer).cpu().numpy())
     check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, W, H))
-    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, ", anti-aliased" if a.aa else "", ctx.device_name))
+    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, (", fog" if a.fog else "") + (", anti-aliased" if a.aa else ""), ctx.device_name))
 
 
 if __name__ == "__main__":

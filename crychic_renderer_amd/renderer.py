@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (AAParams, CrychicError, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, FogParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -217,6 +217,7 @@ class Crychic:
         self._desc = None
         self.antiAliasing = None     # extension: None | True | AAParams -- Draw() of a whole frame runs crychic_antialias into mBackBufferAA
         self.mBackBufferAA = None    # the anti-aliased frame, allocated by the first antialias() that needs it
+        self.fog = None              # extension: None | True | FogParams -- Draw() of a whole frame runs crychic_fog in place on mBackBuffer
 
     def set_gbuffer_formats(self, formats):
         """Re-allocates the G-buffer in the given formats (gbuffer_formats: "f32", "mixed", "f16" or three per-plane formats); its
@@ -277,7 +278,11 @@ class Crychic:
         """shared = (communicator handle, bounds array or None, parts): crychic_draw_hot_path_shared -- the strip AND its exchange,
         the lighting pass in `parts` row ranges that travel while the next is lit (sharding.StripExchange.draw).
         antiAliasing = True or an AAParams (extension): a whole frame, then crychic_antialias over it into mBackBufferAA; mBackBuffer is
-        the frame without it.  A strip or a shared draw then raises CrychicError."""
+        the frame without it.  A strip or a shared draw then raises CrychicError.
+        fog = True or a FogParams (extension): a whole frame, then crychic_fog in place on mBackBuffer (in front of the anti-aliasing
+        if that is set too).  A strip or a shared draw then raises CrychicError."""
+        if self.fog:
+            return self._draw_fogged(row0, rows, shared)
         if self.antiAliasing:
             return self._draw_antialiased(row0, rows, shared)
         # The descriptor only changes when a plane is re-allocated or a knob is turned: keep it across frames so the
@@ -348,6 +353,38 @@ class Crychic:
         finally:
             self.antiAliasing = aa
         self.antialias(params=aa if isinstance(aa, AAParams) else None)
+
+    def _draw_fogged(self, row0, rows, shared):
+        """Draw() with fog set: the frame as Draw() issues it without, the fog pass in place on mBackBuffer, then the anti-aliasing if
+        that is set."""
+        if shared is not None or row0 != 0 or (rows is not None and rows != self.mClientHeight):
+            raise CrychicError(-1, "fog is set: Draw() takes the whole frame on one GPU (the pass is not sharded and does not run behind the "
+                               "exchange)")
+        fog, aa, self.fog, self.antiAliasing = self.fog, self.antiAliasing, None, None
+        try:
+            self.Draw()
+        finally:
+            self.fog, self.antiAliasing = fog, aa
+        self.apply_fog(params=fog if isinstance(fog, FogParams) else None)
+        if aa:
+            self.antialias(params=aa if isinstance(aa, AAParams) else None)
+
+    def apply_fog(self, src=None, out=None, row0=0, rows=None, params=None):
+        """crychic_fog on the context's stream: rows [row0, row0 + rows) of `out` from `src`, both (H, W, 4) uint8 tensors (default:
+        mBackBuffer, in place; `out` alone given: from mBackBuffer into it; `src` alone given: in place on it), with this frame's depth
+        plane, pass constants and cascade maps; params: a FogParams, None = the defaults.  Writes no other byte of `out`.  Returns
+        `out`."""
+        src = self.mBackBuffer if src is None else src
+        out = src if out is None else out
+        H, W = int(src.shape[0]), int(src.shape[1])
+        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
+                or not src.is_contiguous() or not out.is_contiguous() or (H, W) != (self.mClientHeight, self.mClientWidth):
+            raise CrychicError(-1, "apply_fog takes contiguous (H, W, 4) uint8 tensors of the frame's size")
+        maps = (C.c_void_p * 4)(*[self.mShadowMap.mShadowMap[i].data_ptr() for i in range(4)])
+        check(lib.crychic_fog(self.ctx.handle, C.byref(self.mMainPassCB), self.mDepthStencilBuffer.data_ptr(), maps, self.mShadowMap.Width(),
+                              _ptr(src), _ptr(out), W, H, int(row0), int(H - row0 if rows is None else rows),
+                              None if params is None else C.byref(params), _stream(self.ctx.device)))
+        return out
 
     def antialias(self, src=None, out=None, row0=0, rows=None, params=None):
         """crychic_antialias on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferAA, allocated on first

@@ -208,6 +208,9 @@ public:
         if (mAntiAliasing && (!mWholeFrame || mComm))
             throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (anti-aliasing takes the whole frame on one GPU: no SetStrip / JoinNode)",
                                    __FILE__, __LINE__);
+        if (mFog && (!mWholeFrame || mComm))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (fog takes the whole frame on one GPU: no SetStrip / JoinNode)", __FILE__,
+                                   __LINE__);
         if (mRunProducerPasses) {
             DrawSceneToShadowMap();                                                                 // :208
             if (mFuseCameraPasses) DrawNormalsDepthAndGBuffer();                                    // :214 + :236 on one rasterisation
@@ -279,6 +282,10 @@ public:
                                                                              mExchangeParts, spots, L.mNumSpotLights, &sh, mCommandList->Stream()));
         else
             CrychicThrowIfFailed(crychic_draw_hot_path_spots_shadowed(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, L.mNumSpotLights, &sh, mCommandList->Stream()));
+        // SetFog: the finished frame through the fog pass, in place, behind the lighting pass and in front of the anti-aliasing
+        if (mFog)
+            CrychicThrowIfFailed(crychic_fog(md3dDevice->Ctx(), passCB, f.depth_dev, f.shadow_dev, f.shadowDim, f.out_rgba8_dev, f.out_rgba8_dev,
+                                             mClientWidth, mClientHeight, 0, mClientHeight, &mFogParams, mCommandList->Stream()));
         // SetAntiAliasing: the finished frame through the post-process pass into the second back buffer, behind the lighting pass
         if (mAntiAliasing)
             CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), static_cast<const uint8_t*>(mBackBuffer->Data()),
@@ -311,6 +318,24 @@ public:
     }
     bool AntiAliasing() const { return mAntiAliasing; }
     ID3D12Resource* AntiAliasedBackBuffer() { return mBackBufferAA.get(); }
+
+    // ---- fog (extension) ----------------------------------------------------------------------------------------------------------
+    // Volumetric fog with sun shafts through the cascade maps (include/crychic_hip.h crychic_fog).  On: Draw issues the pass after the
+    // lighting pass of a whole frame, in place on the back buffer, in front of the anti-aliasing if that is on too.  p == nullptr: the
+    // default parameters.  With it on, SetStrip / JoinNode make Draw throw (the pass is not sharded).  Off (the default): nothing changes.
+    void SetFog(bool on, const crychic_fog_params* p = nullptr)
+    {
+        crychic_fog_params q;
+        CrychicThrowIfFailed(crychic_fog_default_params(&q));
+        if (p) q = *p;
+        if (!(q.density >= 0.0f && q.density <= 16.0f) || !(q.maxDistance > 0.0f && q.maxDistance <= 3.40282347e38f) || q.steps == 0 ||
+            q.steps > CRYCHIC_FOG_MAX_STEPS || (q.reserved[0] | q.reserved[1] | q.reserved[2]))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetFog (density 0 .. 16, maxDistance finite and > 0, steps 1 .. 64, reserved 0)",
+                                   __FILE__, __LINE__);
+        mFog = on;
+        mFogParams = q;
+    }
+    bool Fog() const { return mFog; }
 
     // ---- local lights (extension: the reference's point and spot branches, PBR.hlsl:109-147, are dead code) -------------------
     // Uploads both lists to device buffers this object owns (at most 1024 each); Draw lights them after the directional lights,
@@ -1037,6 +1062,8 @@ private:
     UINT mStripRow0 = 0, mStripRows = 0;      // this GPU's rows when the frame is shared
     UINT mExchangeParts = 1;                  // SetExchangeParts
     bool mWholeFrame = true;
+    bool mFog = false;                        // SetFog
+    crychic_fog_params mFogParams = {};
     bool mAntiAliasing = false;               // SetAntiAliasing
     crychic_aa_params mAAParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferAA;   // the anti-aliased frame, while mAntiAliasing

@@ -850,6 +850,81 @@ int crychic_aa_default_params(crychic_aa_params* out);
 int crychic_antialias(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H,
                       uint32_t row0, uint32_t rows, const crychic_aa_params* params /* NULL = defaults */, void* stream);
 
+/* ---- volumetric fog with sun shafts through the cascades (extension) ------------------------------------
+ * One pass over the finished RGBA8 frame, a separate call after the lighting pass and before the anti-aliasing: every pixel is
+ * attenuated by the fog between the eye and its surface (the far plane for sky), an ambient in-scatter term is added, and a sun
+ * in-scatter term that counts only the samples of the view ray which the cascade maps say are lit.  Everything behind the lighting
+ * pass is display-referred here (the tone map sits inside it), so the pass composes on RGBA8.  A build definition: nothing of it is
+ * the reference's.  The device, a host build and the checker (tests/fog_ref) agree bit for bit.
+ *
+ * Float operations are IEEE binary32, each rounded once, in the order written; fma(a, b, c) is the fused a b + c and nothing else
+ * is fused.  The named ones are the project's:
+ *   rcp(b)          the correctly rounded 1 / b; |b| < 2^-126 gives +-inf, |b| > 2^126 gives +-0, NaN gives NaN
+ *   len_from_sq(x)  the correctly rounded square root of x clamped to [2^-100, 2^100], NaN taken as 2^-100
+ *   dot3(u, v)      fma(u.z, v.z, fma(u.y, v.y, u.x v.x))
+ *   mulcol(x, y, z, w, m) = fma(w, m[3], fma(z, m[2], fma(y, m[1], x m[0])));   mulcol1(x, y, z, m) = fma(z, m[2], fma(y, m[1], x m[0])) + m[3]
+ *   d24_to_float(u) with v = (float)(u & 0xFFFFFF): fma(v, C_hi, v C_lo), C_hi = 0x33800001 and C_lo = 0xA77FFFFF as bit patterns
+ *                   (equal to the IEEE quotient v / 16777215 for every v)
+ *   det_exp2(z)     for z not NaN: z clamped to [-125, 127], n = z rounded to the nearest integer (ties to even), f = z - n,
+ *                   p = Horner in f with one fma per step over 0.00015406982856802642, 0.0013400138122960925, 0.009618260897696018,
+ *                   0.05550328269600868, 0.24022649228572845, 0.6931471824645996, 1.0 (highest power first); the result is p 2^n
+ * A matrix of the pass constants is stored transposed (column c of the row-vector matrix at floats 4c .. 4c + 3), as everywhere here.
+ *
+ * Host-side constants, once per call, with N = steps:  invN = 1.0f / (float)N;  c = -(density * 1.44269504f) * invN;
+ * sx = 2.0f / (float)W;  sy = 2.0f / (float)H;  dimf = (float)shadowDim;  and for cascade j = 0 .. 3 and c in {x, y, z}:
+ * a[j][c] = mulcol1(EyePosW, ShadowTransforms[j] + 4c).
+ * Per pixel (px, py), Eye = EyePosW:
+ *   1  d = d24_to_float(depth[py W + px])  (the top byte of the texel is ignored)
+ *   2  nx = fma((float)px + 0.5f, sx, -1.0f);  ny = fma((float)py + 0.5f, -sy, 1.0f)
+ *   3  h[c] = mulcol(nx, ny, d, 1.0f, InvViewProj + 4c), c = 0 .. 3;  rw = rcp(h[3]);  P = (h[0] rw, h[1] rw, h[2] rw).  A sky pixel
+ *      (depth 1) is no special case: it reconstructs to the far plane.
+ *   4  r = P - Eye;  L = len_from_sq(dot3(r, r)), in [2^-50, 2^50], never 0 or NaN;  Lc = fminf(L, maxDistance);  invL = rcp(L)
+ *   5  q = det_exp2(c Lc);  qi = (uint32_t)fma(q, 65536.0f, 0.5f), in 0 .. 65536
+ *   6  stepLen = Lc invN;  jit = ((float)B[py & 3][px & 3] + 0.5f) / 16.0f (exact), B the 4 x 4 Bayer matrix
+ *      { 0, 8, 2, 10;  12, 4, 14, 6;  3, 11, 1, 9;  15, 7, 13, 5 }.  From here on everything but the sample coordinates is 32 / 64-bit
+ *      integer arithmetic.
+ *   7  T_0 = 65536, S = 0;  for i = 0 .. N - 1:  T_(i+1) = (T_i qi + 32768) >> 16 (the product in 64 bits);  w = T_i - T_(i+1) (>= 0);
+ *      t = ((float)i + jit) stepLen;  S += lit(t) ? w : 0
+ *   8  lit(t): the cascade is the lighting pass's own by distance from the eye: j = 0 if t < 30, 1 if t < 50, 2 if t < 80, 3 if
+ *      t < 100, otherwise the sample is lit.  f = t invL;  for c in {x, y, z}, with m = ShadowTransforms[j] + 4c:
+ *      b[c] = fma(r.z, m[2], fma(r.y, m[1], r.x m[0])),  s[c] = fma(b[c], f, a[j][c]);  fx = s.x dimf, fy = s.y dimf.  The sample is
+ *      inside iff fx >= 0 && fx < dimf && fy >= 0 && fy < dimf (false for NaN).  A sample that is not inside is lit; one that is, is
+ *      lit iff s.z <= d24_to_float(map[j][(uint32_t)fy shadowDim + (uint32_t)fx]).  One point compare: no filter, no bias (the
+ *      samples are in open air), no blend between cascades.
+ *   9  Tend = T_N;  for R, G, B:  o = (in Tend + ambient (65536 - Tend) + sun S + 32768) >> 16,  out = min(o, 255);  alpha is copied.
+ * The sample's shadow coordinates are linear in f only because the cascade transforms are affine, so a ShadowTransforms[j], j < 4,
+ * whose floats 12 .. 15 are not exactly (0, 0, 0, 1) is refused; crychic_update_cascade_shadow_transform followed by
+ * crychic_update_main_pass_cb produces exactly that.
+ * Known answers: density 0 gives qi = 65536 and out == in byte for byte.  N = 1, maxDistance = 0.5 (below the near plane's distance
+ * of a camera with nearZ = 1), density such that c Lc == -1, maps full of 0xFFFFFF: q = 0.5, Tend = S = 32768 for every pixel,
+ * out = min((in 32768 + (ambient + sun) 32768 + 32768) >> 16, 255); with maps full of 0, S = 0 and the sun term is gone.
+ *
+ * Parameters: density (default 0.02; finite, 0 .. 16), maxDistance (100; finite, > 0), steps = N (16; 1 .. CRYCHIC_FOG_MAX_STEPS),
+ * ambient and sun (R, G, B in bytes 0 .. 2, byte 3 ignored; (70, 80, 100) and (150, 140, 110)), reserved (must be 0).
+ * crychic_fog_default_params fills the defaults (pure host code; CRYCHIC_E_INVALID_ARG for NULL). */
+#define CRYCHIC_FOG_MAX_STEPS 64
+typedef struct crychic_fog_params {
+    float density;
+    float maxDistance;
+    uint32_t steps;
+    uint8_t ambient[4];
+    uint8_t sun[4];
+    uint32_t reserved[3];
+} crychic_fog_params;   /* 32 bytes */
+int crychic_fog_default_params(crychic_fog_params* out);
+/* Writes rows [row0, row0 + rows) of out_rgba8_dev and no other byte; reads the same rows of in_rgba8_dev and depth_dev (W x H, D24 in
+ * the low 24 bits), any texel of the four shadowDim x shadowDim maps, and InvViewProj, EyePosW and ShadowTransforms[0 .. 3] of cb (a
+ * host pointer, read during the call).  Stitched row ranges therefore equal the whole-frame call byte for byte, for any row0 and
+ * rows; rows == 0 launches nothing.  in == out (the same address) is valid: a pixel reads only its own texel.  params == NULL = the
+ * defaults.  One launch on `stream`: no allocation, no synchronisation, no host read-back; capturable into a graph.
+ * CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and before anything is enqueued: a NULL plane, map or cb, a
+ * plane or map that is not 4-byte aligned, W or H of 0, a row range outside the frame, shadowDim outside 1 ..
+ * CRYCHIC_MAX_SPOT_SHADOW_DIM, a parameter outside its range or a non-zero reserved word, a cascade transform that is not affine, in and
+ * out overlapping within W * H * 4 bytes other than in == out.  More than 2^28 pixels: CRYCHIC_E_UNSUPPORTED. */
+int crychic_fog(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32_t* depth_dev, const uint32_t* const shadow_dev[4],
+                uint32_t shadowDim, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0,
+                uint32_t rows, const crychic_fog_params* params /* NULL = defaults */, void* stream);
+
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
  * of 2 rows (half-res alignment); the last rank takes the remainder. */
