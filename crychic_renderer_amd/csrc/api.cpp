@@ -47,15 +47,43 @@ using cry::fail;
         if (e_ != hipSuccess) return fail(CRYCHIC_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// The size bound of every pass: 2^28 pixels (32-bit texel indices, plane offsets below 2^30), fewer than 2^20 columns where
+// `columns`, and at most maxRows rows (a pass's pixel rows per workgroup row x 65535, grid.y <= 65535; 0: no such limit).
+int check_extent(const char* what, uint32_t W, uint32_t H, bool columns, uint32_t maxRows)
+{
+    if ((uint64_t)W * H <= (1ull << 28) && !(columns && W >= (1u << 20)) && !(maxRows && H > maxRows)) return 0;
+    char limits[48] = "";
+    if (maxRows) snprintf(limits, sizeof limits, columns ? ", 2^20 columns or %u rows" : " or %u rows", maxRows);
+    return fail(CRYCHIC_E_UNSUPPORTED, "%s %ux%u exceeds 2^28 pixels%s", what, W, H, limits);
+}
+
 int check_dims(uint32_t W, uint32_t H)
 {
     if (W == 0 || H == 0 || (W & 1u) || (H & 1u))
         return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero and even (half-res maps are W/2 x H/2)", W, H);
-    // 2^28 pixels: 32-bit plane offsets; 4 * 65535 rows: one workgroup row of the lighting pass per 4 pixel rows, grid.y <= 65535
-    if ((uint64_t)W * H > (1ull << 28) || W >= (1u << 20) || H > 4u * 65535u)
-        return fail(CRYCHIC_E_UNSUPPORTED, "frame %ux%u exceeds 2^28 pixels, 2^20 columns or 262140 rows", W, H);
+    return check_extent("frame", W, H, true, 4u * 65535u);      // the lighting pass: 4 pixel rows per workgroup row
+}
+
+// Rows [row0, row0 + rows) inside `limit` rows, and at least minRows of them; `fmt` names what they are rows of.
+constexpr const char* kAmbientRows = "rows [%u,+%u) outside the %u-row ambient map";
+constexpr const char* kFrameRows = "rows [%u,+%u) outside the %u-row frame";
+constexpr const char* kTargetRows = "G-buffer rows [%u,+%u) outside the %u-row target";
+int check_rows(const char* fmt, uint32_t row0, uint32_t rows, uint32_t limit, uint32_t minRows = 0u)
+{
+    if (rows < minRows || row0 > limit || rows > limit - row0) return fail(CRYCHIC_E_INVALID_ARG, fmt, row0, rows, limit);
     return 0;
 }
+
+// CRYCHIC_LIGHT_CUBE_LEVELS announces at most 15 levels, and a chain ends at 1 x 1 at the latest.
+int check_cube_levels(uint32_t levels, uint32_t dim, uint32_t minLevels)
+{
+    const uint32_t full = cry::cube_full_levels(dim) < 15u ? cry::cube_full_levels(dim) : 15u;
+    if (levels < minLevels || levels > full)
+        return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", levels, dim, full);
+    return 0;
+}
+
+bool ranges_overlap(uintptr_t a, size_t aBytes, uintptr_t b, size_t bBytes) { return a < b + bBytes && b < a + aBytes; }
 
 }  // namespace
 
@@ -86,7 +114,7 @@ int ssao_compute_impl(const crychic_ssao_constants* cb, const void* normal, cons
                       uint32_t H, int blurCount, uint32_t row0, uint32_t rows, hipStream_t stream, hipEvent_t afterSsao, crychic_ctx* ctx)
 {
     const uint32_t h2 = H / 2;
-    if (row0 > h2 || rows > h2 - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row ambient map", row0, rows, h2);
+    if (int rc = check_rows(kAmbientRows, row0, rows, h2)) return rc;
     if (blurCount < 0) return fail(CRYCHIC_E_INVALID_ARG, "blurCount %d < 0", blurCount);
     if (blurCount > 0 && (!ambient1 || !edge)) return fail(CRYCHIC_E_INVALID_ARG, "blurCount > 0 needs ambient1 and the edge workspace");
     // rows, planes and launches: blur_tiles.hpp "the launch plan"
@@ -139,12 +167,10 @@ int fill_light_params(cry::LightParams& P, const crychic_pass_constants* cb, con
     if (!(pcfSearchRadius >= 0.0f)) return fail(CRYCHIC_E_INVALID_ARG, "pcfSearchRadius must be >= 0");
     for (int i = 0; i < 4; ++i)
         if (!shadow[i]) return fail(CRYCHIC_E_INVALID_ARG, "shadow cascade %d is null", i);
-    // CRYCHIC_LIGHT_CUBE_LEVELS: a chain ends at 1 x 1 at the latest
-    { const uint32_t levels = (flags >> 16) & 15u;
-      uint32_t full = 1; for (uint32_t m = cubeDim; m > 1u; m >>= 1) ++full;
-      if (levels > full) return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", levels, cubeDim, full);
-      if ((flags & CRYCHIC_LIGHT_CUBE_GLOSS) && levels < 2u)
-          return fail(CRYCHIC_E_INVALID_ARG, "CRYCHIC_LIGHT_CUBE_GLOSS needs a chain: CRYCHIC_LIGHT_CUBE_LEVELS(n) with n > 1"); }
+    const uint32_t levels = (flags >> 16) & 15u;          // CRYCHIC_LIGHT_CUBE_LEVELS; 0: no chain
+    if (int rc = check_cube_levels(levels, cubeDim, 0u)) return rc;
+    if ((flags & CRYCHIC_LIGHT_CUBE_GLOSS) && levels < 2u)
+        return fail(CRYCHIC_E_INVALID_ARG, "CRYCHIC_LIGHT_CUBE_GLOSS needs a chain: CRYCHIC_LIGHT_CUBE_LEVELS(n) with n > 1");
     cry::bind_light_params(P, *cb, shadow, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags);
     return 0;
 }
@@ -222,6 +248,14 @@ int check_parallax(uint32_t flags, const uint8_t* cube, uint32_t cubeDim)
     return fail(CRYCHIC_E_INVALID_ARG, cry::parallax_check_message(c), cry::parallax_probe_offset(cubeDim, (flags >> 16) & 15u));
 }
 
+// The three lookups behind the cube map, in the order their refusals take precedence.
+int check_environment(uint32_t flags, const uint8_t* cube, uint32_t cubeDim)
+{
+    if (int rc = check_ambient_sh(flags, cube, cubeDim)) return rc;
+    if (int rc = check_env_brdf(flags, cube, cubeDim)) return rc;
+    return check_parallax(flags, cube, cubeDim);
+}
+
 // With a mip chain the level of detail comes from 2 x 2 pixel quads: a call's rows have to be whole quad rows.  Not so with
 // CRYCHIC_LIGHT_CUBE_GLOSS, where it comes from the pixel's roughness.
 int check_chain_rows(const cry::LightParams& P, uint32_t row0, uint32_t rows, uint32_t H)
@@ -243,16 +277,14 @@ int deferred_light_impl(crychic_ctx* ctx, const crychic_pass_constants* cb, cons
     if (int rc = check_dims(W, H)) return rc;
     if (!cb || !g0_dev || !g1_dev || !g2_dev || !depth_dev || !shadow_dev || !cube_dev || !out_rgba8_dev)
         return fail(CRYCHIC_E_INVALID_ARG, "null argument");
-    if (row0 > H || rows > H - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row frame", row0, rows, H);
+    if (int rc = check_rows(kFrameRows, row0, rows, H)) return rc;
     cry::LightParams P;
     cry::SpotShadows S;
     cry::PointShadows PS;
     if (int rc = bind_local_lights(P, S, PS, cb, point_lights_dev, numPointLights, spot_lights_dev, numSpotLights, spotShadows,
                                    pointShadows)) return rc;
     if (int rc = fill_light_params(P, cb, shadow_dev, shadowDim, cubeDim, W, H, numDirLights, pcfSearchRadius, flags)) return rc;
-    if (int rc = check_ambient_sh(flags, cube_dev, cubeDim)) return rc;
-    if (int rc = check_env_brdf(flags, cube_dev, cubeDim)) return rc;
-    if (int rc = check_parallax(flags, cube_dev, cubeDim)) return rc;
+    if (int rc = check_environment(flags, cube_dev, cubeDim)) return rc;
     if (int rc = check_chain_rows(P, row0, rows, H)) return rc;
     CRY_HIP(cry::launch_light(P, g0_dev, g1_dev, g2_dev, depth_dev, ambient_dev, cube_dev, out_rgba8_dev, radiance_out_dev,
                               row0, rows, (hipStream_t)stream, spot_lights_dev, numSpotLights, &S, &PS));
@@ -316,7 +348,7 @@ int crychic_ssao(crychic_ctx* ctx, const crychic_ssao_constants* cb, const void*
     if (int rc = bind(ctx)) return rc;
     if (int rc = check_dims(W, H)) return rc;
     if (!cb || !normal_dev || !depth_dev || !randvec_dev || !ambient_out_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
-    if (row0 > H / 2 || rows > H / 2 - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row ambient map", row0, rows, H / 2);
+    if (int rc = check_rows(kAmbientRows, row0, rows, H / 2)) return rc;
     const uint32_t stamp = next_stamp();
     const bool usePairs = edge_dev != nullptr;
     if (edge_dev) CRY_HIP(cry::launch_depth_pairs(*cb, depth_dev, edge_dev, W, H, stamp, usePairs, row0, rows, (hipStream_t)stream));
@@ -332,7 +364,7 @@ int crychic_ssao_edges(crychic_ctx* ctx, const crychic_ssao_constants* cb, const
     if (int rc = bind(ctx)) return rc;
     if (int rc = check_dims(W, H)) return rc;
     if (!cb || !normal_dev || !depth_dev || !edge_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
-    if (row0 > H / 2 || rows > H / 2 - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row ambient map", row0, rows, H / 2);
+    if (int rc = check_rows(kAmbientRows, row0, rows, H / 2)) return rc;
     CRY_HIP(cry::launch_ssao(*cb, normal_dev, depth_dev, nullptr, nullptr, edge_dev, W, H, row0, rows, false, false, 0u, (hipStream_t)stream));
     return 0;
 }
@@ -345,7 +377,7 @@ int crychic_ssao_blur(crychic_ctx* ctx, const crychic_ssao_constants* cb, const 
     if (int rc = check_dims(W, H)) return rc;
     if (!cb || !edge_dev || !ambient_in_dev || !ambient_out_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
     if (ambient_in_dev == ambient_out_dev) return fail(CRYCHIC_E_INVALID_ARG, "blur cannot run in place (the reference ping-pongs, Ssao.cpp:253-266)");
-    if (row0 > H / 2 || rows > H / 2 - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row ambient map", row0, rows, H / 2);
+    if (int rc = check_rows(kAmbientRows, row0, rows, H / 2)) return rc;
     CRY_HIP(cry::launch_blur(*cb, edge_dev, ambient_in_dev, ambient_out_dev, W, H, horizontal != 0, row0, rows, (hipStream_t)stream));
     return 0;
 }
@@ -449,9 +481,7 @@ int cry::hot_path_parts(crychic_ctx* ctx, const crychic_ssao_constants* ssaoCB, 
     cry::LightParams P;
     if (int rc = fill_light_params(P, passCB, f->shadow_dev, f->shadowDim, f->cubeDim, W, H, f->numDirLights,
                                    f->pcfSearchRadius, f->flags)) return rc;
-    if (int rc = check_ambient_sh(f->flags, f->cube_dev, f->cubeDim)) return rc;
-    if (int rc = check_env_brdf(f->flags, f->cube_dev, f->cubeDim)) return rc;
-    if (int rc = check_parallax(f->flags, f->cube_dev, f->cubeDim)) return rc;
+    if (int rc = check_environment(f->flags, f->cube_dev, f->cubeDim)) return rc;
     cry::SpotShadows S;
     cry::PointShadows PS;
     if (int rc = bind_local_lights(P, S, PS, passCB, f->point_lights_dev, f->numPointLights, spots.lights, spots.count, spots.shadows,
@@ -543,9 +573,7 @@ static int raster_common(crychic_ctx* ctx, cry::RasterPass& p, const crychic_pas
     if (int rc = bind(ctx)) return rc;
     if (!passCB || (!items && nItems) || (!p.depth && p.nTargets < 2u) || !p.workspace) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
     if (p.W == 0 || p.H == 0) return fail(CRYCHIC_E_INVALID_ARG, "bad target size %ux%u", p.W, p.H);
-    // the same bounds as the full-screen passes: 32-bit plane offsets, and one workgroup row of the resolve pass per 4 pixel rows
-    if ((uint64_t)p.W * p.H > (1ull << 28) || p.W >= (1u << 20) || p.H > 4u * 65535u)
-        return fail(CRYCHIC_E_UNSUPPORTED, "target %ux%u exceeds 2^28 pixels, 2^20 columns or 262140 rows", p.W, p.H);
+    if (int rc = check_extent("target", p.W, p.H, true, 4u * 65535u)) return rc;      // the resolve pass: 4 pixel rows per workgroup row
     for (uint32_t i = 0; i < nItems; ++i) {
         const crychic_draw_item& d = items[i];
         if (d.indexCount % 3u) return fail(CRYCHIC_E_INVALID_ARG, "item %u: indexCount %u is not a triangle list", i, d.indexCount);
@@ -587,13 +615,27 @@ int crychic_blur_chain_status(crychic_ctx* ctx, void* stream, uint32_t* timed_ou
     return 0;
 }
 
+// What every producer entry fills in alike: the mode (kernels.hpp), the target's size and depth plane, the workspace.
+static cry::RasterPass raster_pass(int mode, uint32_t W, uint32_t H, uint32_t* depth_dev, void* workspace_dev, size_t workspaceBytes)
+{
+    cry::RasterPass p = {};
+    p.mode = mode; p.W = W; p.H = H; p.depth = depth_dev; p.workspace = workspace_dev; p.workspaceBytes = workspaceBytes;
+    return p;
+}
+
+static cry::RasterPass shadow_pass(uint32_t shadowDim, int depthBias, float slopeScaledDepthBias, uint32_t* shadow_dev, void* workspace_dev,
+                                   size_t workspaceBytes)
+{
+    cry::RasterPass p = raster_pass(0, shadowDim, shadowDim, shadow_dev, workspace_dev, workspaceBytes);
+    p.depthBias = depthBias; p.slopeScaledDepthBias = slopeScaledDepthBias;
+    return p;
+}
+
 int crychic_draw_scene_to_shadow_map(crychic_ctx* ctx, const crychic_pass_constants* passCB, const crychic_draw_item* items,
                                      uint32_t nItems, uint32_t* shadow_dev, uint32_t shadowDim, int depthBias,
                                      float slopeScaledDepthBias, void* workspace_dev, size_t workspaceBytes, void* stream)
 {
-    cry::RasterPass p = {};
-    p.mode = 0; p.W = shadowDim; p.H = shadowDim; p.depthBias = depthBias; p.slopeScaledDepthBias = slopeScaledDepthBias;
-    p.depth = shadow_dev; p.workspace = workspace_dev; p.workspaceBytes = workspaceBytes;
+    cry::RasterPass p = shadow_pass(shadowDim, depthBias, slopeScaledDepthBias, shadow_dev, workspace_dev, workspaceBytes);
     return raster_common(ctx, p, passCB, items, nItems, stream);
 }
 
@@ -617,9 +659,7 @@ int crychic_draw_scene_to_shadow_maps(crychic_ctx* ctx, const crychic_pass_const
     if (nCascades == 1u)
         return crychic_draw_scene_to_shadow_map(ctx, passCBs, items, nItems, shadow_dev[0], shadowDim, depthBias, slopeScaledDepthBias, workspace_dev,
                                                 workspaceBytes, stream);
-    cry::RasterPass p = {};
-    p.mode = 0; p.W = shadowDim; p.H = shadowDim; p.depthBias = depthBias; p.slopeScaledDepthBias = slopeScaledDepthBias;
-    p.workspace = workspace_dev; p.workspaceBytes = workspaceBytes;
+    cry::RasterPass p = shadow_pass(shadowDim, depthBias, slopeScaledDepthBias, nullptr, workspace_dev, workspaceBytes);
     p.nTargets = nCascades;
     for (uint32_t c = 0; c < nCascades; ++c) {
         if (!shadow_dev[c]) return fail(CRYCHIC_E_INVALID_ARG, "shadow target %u is null", c);
@@ -634,8 +674,29 @@ int crychic_draw_normals_and_depth(crychic_ctx* ctx, const crychic_pass_constant
                                    void* workspace_dev, size_t workspaceBytes, void* stream)
 {
     if (!normal_dev) return fail(CRYCHIC_E_INVALID_ARG, "null normal target");
-    cry::RasterPass p = {};
-    p.mode = 1; p.W = W; p.H = H; p.depth = depth_dev; p.normal = normal_dev; p.workspace = workspace_dev; p.workspaceBytes = workspaceBytes;
+    cry::RasterPass p = raster_pass(1, W, H, depth_dev, workspace_dev, workspaceBytes);
+    p.normal = normal_dev;
+    return raster_common(ctx, p, passCB, items, nItems, stream);
+}
+
+// The camera's G-buffer pass behind the five entries below.  `fused`: the entry takes a normal map of its own, which may then not
+// be null; with a normal map the pass writes it too (mode 3).  minRows 1: gRows == 0 is refused, not read as the whole target.
+static int gbuffer_pass(crychic_ctx* ctx, const crychic_pass_constants* passCB, const crychic_draw_item* items, uint32_t nItems,
+                        const crychic_material_data* materials_dev, uint32_t nMaterials, const crychic_texture* textures, uint32_t nTextures,
+                        bool fused, void* normal_dev, void* g0_dev, void* g1_dev, void* g2_dev, uint32_t gbufferFlags, uint32_t* depth_dev,
+                        uint32_t W, uint32_t H, uint32_t gRow0, uint32_t gRows, uint32_t minRows, void* workspace_dev, size_t workspaceBytes,
+                        void* stream)
+{
+    if ((fused && !normal_dev) || !g0_dev || !g1_dev || !g2_dev)
+        return fail(CRYCHIC_E_INVALID_ARG, fused ? "null normal / G-buffer target" : "null G-buffer target");
+    if (nTextures && !textures) return fail(CRYCHIC_E_INVALID_ARG, "null texture table");
+    if (int rc = check_rows(kTargetRows, gRow0, gRows, H, minRows)) return rc;
+    cry::RasterPass p = raster_pass(normal_dev ? 3 : 2, W, H, depth_dev, workspace_dev, workspaceBytes);
+    p.normal = normal_dev;
+    p.g0 = (float*)g0_dev; p.g1 = (float*)g1_dev; p.g2 = (float*)g2_dev; p.gbufferFlags = gbufferFlags;
+    p.materials = materials_dev; p.nMaterials = nMaterials;
+    p.textures = reinterpret_cast<const cry::Texture*>(textures); p.nTextures = nTextures;
+    p.gRow0 = gRow0; p.gRows = gRows;
     return raster_common(ctx, p, passCB, items, nItems, stream);
 }
 
@@ -644,14 +705,8 @@ int crychic_draw_gbuffer(crychic_ctx* ctx, const crychic_pass_constants* passCB,
                          uint32_t nTextures, float* g0_dev, float* g1_dev, float* g2_dev, uint32_t* depth_dev, uint32_t W, uint32_t H,
                          void* workspace_dev, size_t workspaceBytes, void* stream)
 {
-    if (!g0_dev || !g1_dev || !g2_dev) return fail(CRYCHIC_E_INVALID_ARG, "null G-buffer target");
-    if (nTextures && !textures) return fail(CRYCHIC_E_INVALID_ARG, "null texture table");
-    cry::RasterPass p = {};
-    p.mode = 2; p.W = W; p.H = H; p.depth = depth_dev; p.g0 = g0_dev; p.g1 = g1_dev; p.g2 = g2_dev;
-    p.materials = materials_dev; p.nMaterials = nMaterials;
-    p.textures = reinterpret_cast<const cry::Texture*>(textures); p.nTextures = nTextures;
-    p.workspace = workspace_dev; p.workspaceBytes = workspaceBytes;
-    return raster_common(ctx, p, passCB, items, nItems, stream);
+    return gbuffer_pass(ctx, passCB, items, nItems, materials_dev, nMaterials, textures, nTextures, false, nullptr, g0_dev, g1_dev, g2_dev, 0u,
+                        depth_dev, W, H, 0u, 0u, 0u, workspace_dev, workspaceBytes, stream);
 }
 
 int crychic_draw_normals_depth_and_gbuffer(crychic_ctx* ctx, const crychic_pass_constants* passCB, const crychic_draw_item* items, uint32_t nItems,
@@ -659,14 +714,8 @@ int crychic_draw_normals_depth_and_gbuffer(crychic_ctx* ctx, const crychic_pass_
                                            uint32_t nTextures, void* normal_dev, float* g0_dev, float* g1_dev, float* g2_dev, uint32_t* depth_dev,
                                            uint32_t W, uint32_t H, void* workspace_dev, size_t workspaceBytes, void* stream)
 {
-    if (!normal_dev || !g0_dev || !g1_dev || !g2_dev) return fail(CRYCHIC_E_INVALID_ARG, "null normal / G-buffer target");
-    if (nTextures && !textures) return fail(CRYCHIC_E_INVALID_ARG, "null texture table");
-    cry::RasterPass p = {};
-    p.mode = 3; p.W = W; p.H = H; p.depth = depth_dev; p.normal = normal_dev; p.g0 = g0_dev; p.g1 = g1_dev; p.g2 = g2_dev;
-    p.materials = materials_dev; p.nMaterials = nMaterials;
-    p.textures = reinterpret_cast<const cry::Texture*>(textures); p.nTextures = nTextures;
-    p.workspace = workspace_dev; p.workspaceBytes = workspaceBytes;
-    return raster_common(ctx, p, passCB, items, nItems, stream);
+    return gbuffer_pass(ctx, passCB, items, nItems, materials_dev, nMaterials, textures, nTextures, true, normal_dev, g0_dev, g1_dev, g2_dev, 0u,
+                        depth_dev, W, H, 0u, 0u, 0u, workspace_dev, workspaceBytes, stream);
 }
 
 int crychic_draw_gbuffer_rows(crychic_ctx* ctx, const crychic_pass_constants* passCB, const crychic_draw_item* items, uint32_t nItems,
@@ -674,16 +723,8 @@ int crychic_draw_gbuffer_rows(crychic_ctx* ctx, const crychic_pass_constants* pa
                               uint32_t nTextures, float* g0_dev, float* g1_dev, float* g2_dev, uint32_t* depth_dev, uint32_t W, uint32_t H,
                               uint32_t gRow0, uint32_t gRows, void* workspace_dev, size_t workspaceBytes, void* stream)
 {
-    if (!g0_dev || !g1_dev || !g2_dev) return fail(CRYCHIC_E_INVALID_ARG, "null G-buffer target");
-    if (nTextures && !textures) return fail(CRYCHIC_E_INVALID_ARG, "null texture table");
-    if (gRows == 0 || gRow0 > H || gRows > H - gRow0) return fail(CRYCHIC_E_INVALID_ARG, "G-buffer rows [%u,+%u) outside the %u-row target", gRow0, gRows, H);
-    cry::RasterPass p = {};
-    p.mode = 2; p.W = W; p.H = H; p.depth = depth_dev; p.g0 = g0_dev; p.g1 = g1_dev; p.g2 = g2_dev;
-    p.materials = materials_dev; p.nMaterials = nMaterials;
-    p.textures = reinterpret_cast<const cry::Texture*>(textures); p.nTextures = nTextures;
-    p.workspace = workspace_dev; p.workspaceBytes = workspaceBytes;
-    p.gRow0 = gRow0; p.gRows = gRows;
-    return raster_common(ctx, p, passCB, items, nItems, stream);
+    return gbuffer_pass(ctx, passCB, items, nItems, materials_dev, nMaterials, textures, nTextures, false, nullptr, g0_dev, g1_dev, g2_dev, 0u,
+                        depth_dev, W, H, gRow0, gRows, 1u, workspace_dev, workspaceBytes, stream);
 }
 
 int crychic_draw_normals_depth_and_gbuffer_rows(crychic_ctx* ctx, const crychic_pass_constants* passCB, const crychic_draw_item* items, uint32_t nItems,
@@ -692,16 +733,8 @@ int crychic_draw_normals_depth_and_gbuffer_rows(crychic_ctx* ctx, const crychic_
                                                 uint32_t W, uint32_t H, uint32_t gRow0, uint32_t gRows, void* workspace_dev, size_t workspaceBytes,
                                                 void* stream)
 {
-    if (!normal_dev || !g0_dev || !g1_dev || !g2_dev) return fail(CRYCHIC_E_INVALID_ARG, "null normal / G-buffer target");
-    if (nTextures && !textures) return fail(CRYCHIC_E_INVALID_ARG, "null texture table");
-    if (gRows == 0 || gRow0 > H || gRows > H - gRow0) return fail(CRYCHIC_E_INVALID_ARG, "G-buffer rows [%u,+%u) outside the %u-row target", gRow0, gRows, H);
-    cry::RasterPass p = {};
-    p.mode = 3; p.W = W; p.H = H; p.depth = depth_dev; p.normal = normal_dev; p.g0 = g0_dev; p.g1 = g1_dev; p.g2 = g2_dev;
-    p.materials = materials_dev; p.nMaterials = nMaterials;
-    p.textures = reinterpret_cast<const cry::Texture*>(textures); p.nTextures = nTextures;
-    p.workspace = workspace_dev; p.workspaceBytes = workspaceBytes;
-    p.gRow0 = gRow0; p.gRows = gRows;
-    return raster_common(ctx, p, passCB, items, nItems, stream);
+    return gbuffer_pass(ctx, passCB, items, nItems, materials_dev, nMaterials, textures, nTextures, true, normal_dev, g0_dev, g1_dev, g2_dev, 0u,
+                        depth_dev, W, H, gRow0, gRows, 1u, workspace_dev, workspaceBytes, stream);
 }
 
 size_t crychic_gbuffer_plane_bytes(uint32_t W, uint32_t H, uint32_t flags, int plane)
@@ -718,17 +751,8 @@ int crychic_draw_gbuffer_formats(crychic_ctx* ctx, const crychic_pass_constants*
 {
     if (gbufferFlags & ~CRYCHIC_GBUFFER_F16_MASK)
         return fail(CRYCHIC_E_INVALID_ARG, "gbufferFlags 0x%x: bits outside CRYCHIC_GBUFFER_G0_F16 | G1_F16 | G2_F16", gbufferFlags);
-    if (!g0_dev || !g1_dev || !g2_dev) return fail(CRYCHIC_E_INVALID_ARG, "null G-buffer target");
-    if (nTextures && !textures) return fail(CRYCHIC_E_INVALID_ARG, "null texture table");
-    if (gRow0 > H || gRows > H - gRow0) return fail(CRYCHIC_E_INVALID_ARG, "G-buffer rows [%u,+%u) outside the %u-row target", gRow0, gRows, H);
-    cry::RasterPass p = {};
-    p.mode = normal_dev ? 3 : 2; p.W = W; p.H = H; p.depth = depth_dev; p.normal = normal_dev;
-    p.g0 = (float*)g0_dev; p.g1 = (float*)g1_dev; p.g2 = (float*)g2_dev; p.gbufferFlags = gbufferFlags;
-    p.materials = materials_dev; p.nMaterials = nMaterials;
-    p.textures = reinterpret_cast<const cry::Texture*>(textures); p.nTextures = nTextures;
-    p.workspace = workspace_dev; p.workspaceBytes = workspaceBytes;
-    p.gRow0 = gRow0; p.gRows = gRows;
-    return raster_common(ctx, p, passCB, items, nItems, stream);
+    return gbuffer_pass(ctx, passCB, items, nItems, materials_dev, nMaterials, textures, nTextures, false, normal_dev, g0_dev, g1_dev, g2_dev,
+                        gbufferFlags, depth_dev, W, H, gRow0, gRows, 0u, workspace_dev, workspaceBytes, stream);
 }
 
 size_t crychic_cube_chain_bytes(uint32_t dim, uint32_t levels)
@@ -744,10 +768,7 @@ int crychic_generate_cube_mips(crychic_ctx* ctx, uint8_t* chain_dev, uint32_t di
     if (!chain_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
     if (dim == 0) return fail(CRYCHIC_E_INVALID_ARG, "cube map face size 0");
     if (dim > 32768u) return fail(CRYCHIC_E_UNSUPPORTED, "cube map face size %u exceeds 32768", dim);
-    // a chain ends at 1 x 1 at the latest, and CRYCHIC_LIGHT_CUBE_LEVELS announces at most 15 levels
-    const uint32_t full = cry::cube_full_levels(dim) < 15u ? cry::cube_full_levels(dim) : 15u;
-    if (levels == 0 || levels > full)
-        return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", levels, dim, full);
+    if (int rc = check_cube_levels(levels, dim, 1u)) return rc;
     if (reinterpret_cast<uintptr_t>(chain_dev) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "cube map chain is not 4-byte aligned");
     CRY_HIP(cry::launch_cube_mips(chain_dev, dim, levels, (hipStream_t)stream));
     return 0;
@@ -761,13 +782,11 @@ int crychic_prefilter_cube_chain(crychic_ctx* ctx, const uint8_t* src_chain_dev,
     if (dim == 0) return fail(CRYCHIC_E_INVALID_ARG, "cube map face size 0");
     // the chain sampler addresses texels by 32-bit byte offsets, as it does in the lighting pass (cubeDim <= 8192 there)
     if (dim > 8192u) return fail(CRYCHIC_E_UNSUPPORTED, "cube map face size %u exceeds 8192", dim);
-    const uint32_t full = cry::cube_full_levels(dim) < 15u ? cry::cube_full_levels(dim) : 15u;
-    if (levels == 0 || levels > full)
-        return fail(CRYCHIC_E_INVALID_ARG, "%u cube map levels, a %u-texel face has at most %u", levels, dim, full);
+    if (int rc = check_cube_levels(levels, dim, 1u)) return rc;
     const uintptr_t s = reinterpret_cast<uintptr_t>(src_chain_dev), d = reinterpret_cast<uintptr_t>(dst_chain_dev);
     if ((s | d) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "cube map chain is not 4-byte aligned");
     const size_t bytes = crychic_cube_chain_bytes(dim, levels);
-    if (s < d + bytes && d < s + bytes) return fail(CRYCHIC_E_INVALID_ARG, "the source and destination chains overlap");
+    if (ranges_overlap(s, bytes, d, bytes)) return fail(CRYCHIC_E_INVALID_ARG, "the source and destination chains overlap");
     CRY_HIP(cry::launch_cube_prefilter(src_chain_dev, dst_chain_dev, dim, levels, (hipStream_t)stream));
     return 0;
 }
@@ -787,10 +806,8 @@ int crychic_antialias(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* ou
     // every argument is checked before the context is looked at: a refusal needs no device
     if (!in_rgba8_dev || !out_rgba8_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
     if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
-    // 2^28 pixels: 32-bit texel coordinates and plane offsets below 2^30; 32 rows per workgroup row, grid.y <= 65535
-    if ((uint64_t)W * H > (1ull << 28) || H > 32u * 65535u)
-        return fail(CRYCHIC_E_UNSUPPORTED, "frame %ux%u exceeds 2^28 pixels or 2097120 rows", W, H);
-    if (row0 > H || rows > H - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row frame", row0, rows, H);
+    if (int rc = check_extent("frame", W, H, false, 32u * 65535u)) return rc;         // 32 pixel rows per workgroup row
+    if (int rc = check_rows(kFrameRows, row0, rows, H)) return rc;
     crychic_aa_params p;
     crychic_aa_default_params(&p);
     if (params) p = *params;
@@ -801,7 +818,7 @@ int crychic_antialias(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* ou
     const uintptr_t s = reinterpret_cast<uintptr_t>(in_rgba8_dev), d = reinterpret_cast<uintptr_t>(out_rgba8_dev);
     if ((s | d) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "anti-aliasing planes are not 4-byte aligned");
     const size_t bytes = (size_t)W * H * 4u;
-    if (s < d + bytes && d < s + bytes) return fail(CRYCHIC_E_INVALID_ARG, "the anti-aliasing input and output planes overlap (the pass cannot run in place)");
+    if (ranges_overlap(s, bytes, d, bytes)) return fail(CRYCHIC_E_INVALID_ARG, "the anti-aliasing input and output planes overlap (the pass cannot run in place)");
     if (int rc = bind(ctx)) return rc;
     const cry::PostAaParams q = { p.absMin, p.relShift, p.searchSteps, p.subpix };
     CRY_HIP(cry::launch_post_aa(in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, q, (hipStream_t)stream));
@@ -834,9 +851,8 @@ int crychic_fog(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32
     }
     if (align & 3u) return fail(CRYCHIC_E_INVALID_ARG, "fog planes and maps are not 4-byte aligned");
     if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
-    // 2^28 pixels: 32-bit texel indices and plane offsets below 2^30; the grid is one-dimensional, at most 2^27 workgroups
-    if ((uint64_t)W * H > (1ull << 28)) return fail(CRYCHIC_E_UNSUPPORTED, "frame %ux%u exceeds 2^28 pixels", W, H);
-    if (row0 > H || rows > H - row0) return fail(CRYCHIC_E_INVALID_ARG, "rows [%u,+%u) outside the %u-row frame", row0, rows, H);
+    if (int rc = check_extent("frame", W, H, false, 0u)) return rc;                   // a one-dimensional grid, at most 2^27 workgroups
+    if (int rc = check_rows(kFrameRows, row0, rows, H)) return rc;
     if (shadowDim == 0 || shadowDim > CRYCHIC_MAX_SPOT_SHADOW_DIM)
         return fail(CRYCHIC_E_INVALID_ARG, "fog shadowDim %u outside 1 .. %d", shadowDim, CRYCHIC_MAX_SPOT_SHADOW_DIM);
     crychic_fog_params p;
@@ -856,7 +872,7 @@ int crychic_fog(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32
     }
     const uintptr_t s = reinterpret_cast<uintptr_t>(in_rgba8_dev), d = reinterpret_cast<uintptr_t>(out_rgba8_dev);
     const size_t bytes = (size_t)W * H * 4u;
-    if (s != d && s < d + bytes && d < s + bytes)
+    if (s != d && ranges_overlap(s, bytes, d, bytes))
         return fail(CRYCHIC_E_INVALID_ARG, "the fog input and output planes overlap (in place takes the same address)");
     if (int rc = bind(ctx)) return rc;
     cry::FogParams q;
@@ -878,7 +894,7 @@ int crychic_project_cube_sh(crychic_ctx* ctx, const uint8_t* level_dev, uint32_t
     if (s & 3u) return fail(CRYCHIC_E_INVALID_ARG, "cube map level is not 4-byte aligned");
     if (t & 7u) return fail(CRYCHIC_E_INVALID_ARG, "environment tail is not 8-byte aligned");
     const size_t bytes = (size_t)6u * d * d * 4u;
-    if (s < t + CRYCHIC_CUBE_SH_BYTES && t < s + bytes) return fail(CRYCHIC_E_INVALID_ARG, "the environment tail overlaps the level");
+    if (ranges_overlap(s, bytes, t, CRYCHIC_CUBE_SH_BYTES)) return fail(CRYCHIC_E_INVALID_ARG, "the environment tail overlaps the level");
     CRY_HIP(cry::launch_cube_sh(level_dev, d, tail_dev, (hipStream_t)stream));
     return 0;
 }

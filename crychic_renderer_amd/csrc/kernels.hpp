@@ -104,7 +104,7 @@ hipError_t launch_fog(const float* invViewProj, const float* eye, const float (*
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
 struct Texture;
 struct RasterPass {
-    int mode;                               // 0 shadow depth, 1 view normals + depth, 2 G-buffer + depth
+    int mode;                               // 0 shadow depth, 1 view normals + depth, 2 G-buffer + depth, 3 normals + G-buffer + depth
     const float* view;                      // PassConstants.View (transposed storage)
     const float* viewProj;                  // PassConstants.ViewProj
     const crychic_draw_item* items; uint32_t nItems;     // host array, device pointers inside

@@ -19,6 +19,11 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(None)
 
 
+def _check_chain(who, chain, nbytes):
+    if chain.dtype != torch.uint8 or not chain.is_contiguous() or chain.numel() < nbytes:
+        raise CrychicError(-1, "%s: chain must be a contiguous uint8 device tensor of at least %d bytes" % (who, nbytes))
+
+
 def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -207,7 +212,7 @@ class Crychic:
         self._probes = {}            # capture_environment: (dim, shadow_dim) -> the dim x dim probe renderer, kept across captures
         self._probe_chains = {}      # capture_environment(prefilter=True): (dim, levels) -> the scratch box chain
         self.mPointLights = None     # extension: torch uint8 tensor holding an array of Light structs (48 B each)
-        self.mSpotLights = None      # extension: the same for the spot lights (crychic_draw_hot_path_spots)
+        self.mSpotLights = None      # extension: the same for the spot lights (the hot path's spot list)
         self.mSpotShadowMaps = None  # extension: (count, dim, dim) int32 D24 maps of the first spot lights (set_spot_shadows)
         self._spotHost = None        # host copy of the spot lights (the shadow transforms are built from it)
         self._spotShadow = None      # (SpotShadows descriptor, [transposed transform], [shadow pass constants], geometry)
@@ -275,7 +280,7 @@ class Crychic:
         return f
 
     def Draw(self, row0=0, rows=None, shared=None):  # CRYCHIC.cpp:172-306 (hot part)
-        """shared = (communicator handle, bounds array or None, parts): crychic_draw_hot_path_shared -- the strip AND its exchange,
+        """shared = (communicator handle, bounds array or None, parts): the _shared entry -- the strip AND its exchange,
         the lighting pass in `parts` row ranges that travel while the next is lit (sharding.StripExchange.draw).
         antiAliasing = True or an AAParams (extension): a whole frame, then crychic_antialias over it into mBackBufferAA; mBackBuffer is
         the frame without it.  A strip or a shared draw then raises CrychicError.
@@ -294,59 +299,49 @@ class Crychic:
                ssao.mNormalMap.data_ptr(), ssao.mRandomVectorMap.data_ptr(), self.mDepthStencilBuffer.data_ptr(),
                g0.data_ptr(), g1.data_ptr(), g2.data_ptr(), g0.dtype, g1.dtype, g2.dtype,
                sm.data_ptr(), int(sm.shape[-1]), self.mCubeMap.data_ptr(), int(self.mCubeMapSize or self.mCubeMap.shape[1]), int(self.mCubeMapLevels),
-               bool(self.mCubeMapGloss), bool(self.mCubeMapAmbientSH), bool(self.mCubeMapEnvBrdf), bool(self.mCubeMapParallax), self.blurCount, self.numDirLights, self.pcfSearchRadius, self.flags,
+               self.mCubeMapGloss, self.mCubeMapAmbientSH, self.mCubeMapEnvBrdf, self.mCubeMapParallax, self.blurCount, self.numDirLights, self.pcfSearchRadius, self.flags,
                0 if self.mPointLights is None else self.mPointLights.data_ptr(),
                0 if self.mSpotLights is None else self.mSpotLights.data_ptr())
         if self._desc is None:
             self._desc = {}
-        f = self._desc.get(key)
+        f = self._desc.get(key)          # the descriptor's reference, as the entries take it
         if f is None:
             if len(self._desc) > 16:
                 self._desc.clear()
-            f = self._desc[key] = self.frame_desc(row0, rows)
-        if self.mSpotLights is not None or self._pointShadow is not None:
-            # extension: the _spots_shadowed entries (no descriptor: unshadowed), or with point shadows the _point_shadows entries;
-            # frame, strip or shared
-            spots, n = (None, 0) if self.mSpotLights is None else (_ptr(self.mSpotLights), self.mSpotLights.numel() // 48)
-            pcb, desc = self.mMainPassCB, None
-            if self._spotShadow is not None:
-                d, T, cbs, geo = self._spotShadow
-                desc = C.byref(d)
-                pcb = PassConstants.from_buffer_copy(self.mMainPassCB)      # mMainPassCB with the spot transforms in slots 4..11
-                for k, t in enumerate(T):
-                    pcb.ShadowTransforms[4 + k][:] = t
-                if geo is not None:
-                    self.DrawSpotShadowMaps()
-            if self._pointShadow is not None:
-                pd, _, pgeo = self._pointShadow
-                if pgeo is not None:
-                    self.DrawPointShadowMaps()
-                if shared is not None:
-                    check(lib.crychic_draw_hot_path_shared_point_shadows(shared[0], C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), shared[1],
-                                                                         int(shared[2]), spots, n, desc, C.byref(pd), _stream(self.ctx.device)))
-                else:
-                    check(lib.crychic_draw_hot_path_point_shadows(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), spots, n, desc,
-                                                                  C.byref(pd), _stream(self.ctx.device)))
-                return
-            if shared is not None:
-                check(lib.crychic_draw_hot_path_shared_spots_shadowed(shared[0], C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), shared[1],
-                                                                      int(shared[2]), spots, n, desc, _stream(self.ctx.device)))
-            else:
-                check(lib.crychic_draw_hot_path_spots_shadowed(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(pcb), C.byref(f), spots, n, desc,
-                                                               _stream(self.ctx.device)))
-            return
+            f = self._desc[key] = C.byref(self.frame_desc(row0, rows))
+        # One entry, frame, strip or shared: the local lights' lists and shadow descriptors (extensions) are None where there are
+        # none, which the library serves as the narrower entries do, bit for bit (include/crychic_hip.h).
+        spots, n = (None, 0) if self.mSpotLights is None else (_ptr(self.mSpotLights), self.mSpotLights.numel() // 48)
+        pcb, desc, pdesc = self.mMainPassCB, None, None
+        if self._spotShadow is not None:
+            d, T, cbs, geo = self._spotShadow
+            desc = C.byref(d)
+            pcb = PassConstants.from_buffer_copy(self.mMainPassCB)      # mMainPassCB with the spot transforms in slots 4..11
+            for k, t in enumerate(T):
+                pcb.ShadowTransforms[4 + k][:] = t
+            if geo is not None:
+                self.DrawSpotShadowMaps()
+        if self._pointShadow is not None:
+            pd, _, pgeo = self._pointShadow
+            pdesc = C.byref(pd)
+            if pgeo is not None:
+                self.DrawPointShadowMaps()
         if shared is not None:
-            check(lib.crychic_draw_hot_path_shared(shared[0], C.byref(self.mSsaoCB), C.byref(self.mMainPassCB), C.byref(f), shared[1],
-                                                   int(shared[2]), _stream(self.ctx.device)))
-            return
-        check(lib.crychic_draw_hot_path(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(self.mMainPassCB), C.byref(f),
-                                        _stream(self.ctx.device)))
+            check(lib.crychic_draw_hot_path_shared_point_shadows(shared[0], C.byref(self.mSsaoCB), C.byref(pcb), f, shared[1],
+                                                                 int(shared[2]), spots, n, desc, pdesc, _stream(self.ctx.device)))
+        else:
+            check(lib.crychic_draw_hot_path_point_shadows(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(pcb), f, spots, n, desc,
+                                                          pdesc, _stream(self.ctx.device)))
+
+    def _whole_frame_only(self, what, row0, rows, shared):
+        """The guard of the passes that are not sharded and do not run behind the exchange."""
+        if shared is not None or row0 != 0 or (rows is not None and rows != self.mClientHeight):
+            raise CrychicError(-1, "%s is set: Draw() takes the whole frame on one GPU (the pass is not sharded and does not run behind the "
+                               "exchange)" % what)
 
     def _draw_antialiased(self, row0, rows, shared):
         """Draw() with antiAliasing set: the frame as Draw() issues it without, then the pass over it into mBackBufferAA."""
-        if shared is not None or row0 != 0 or (rows is not None and rows != self.mClientHeight):
-            raise CrychicError(-1, "antiAliasing is set: Draw() takes the whole frame on one GPU (the pass is not sharded and does not run "
-                               "behind the exchange)")
+        self._whole_frame_only("antiAliasing", row0, rows, shared)
         aa, self.antiAliasing = self.antiAliasing, None
         try:
             self.Draw()
@@ -357,9 +352,7 @@ class Crychic:
     def _draw_fogged(self, row0, rows, shared):
         """Draw() with fog set: the frame as Draw() issues it without, the fog pass in place on mBackBuffer, then the anti-aliasing if
         that is set."""
-        if shared is not None or row0 != 0 or (rows is not None and rows != self.mClientHeight):
-            raise CrychicError(-1, "fog is set: Draw() takes the whole frame on one GPU (the pass is not sharded and does not run behind the "
-                               "exchange)")
+        self._whole_frame_only("fog", row0, rows, shared)
         fog, aa, self.fog, self.antiAliasing = self.fog, self.antiAliasing, None, None
         try:
             self.Draw()
@@ -418,30 +411,24 @@ class Crychic:
         volume into its environment tail; the reflection lookup is then box-projected through it (CRYCHIC_LIGHT_CUBE_PARALLAX)."""
         if gloss and int(levels) < 2:
             raise CrychicError(-1, "set_cube_map: gloss needs a chain (levels > 1)")
+        from .geometry import cube_chain_env_bytes, cube_chain_sh_bytes
+
+        def holds(option, nbytes, what):
+            need = nbytes(int(dim) if dim is not None else int(cube.shape[1]), levels)
+            if cube.numel() * cube.element_size() < need:
+                raise CrychicError(-1, "set_cube_map: %s needs a tensor of %d bytes (%s)" % (option, need, what))
         if parallax:
-            from .geometry import cube_chain_sh_bytes
             if not gloss:
                 raise CrychicError(-1, "set_cube_map: parallax needs a prefiltered chain (levels > 1 and gloss=True)")
-            d = int(dim) if dim is not None else int(cube.shape[1])
-            if cube.numel() * cube.element_size() < cube_chain_sh_bytes(d, levels):
-                raise CrychicError(-1, "set_cube_map: parallax needs a tensor of %d bytes (the chain and its environment tail)"
-                                   % cube_chain_sh_bytes(d, levels))
+            holds("parallax", cube_chain_sh_bytes, "the chain and its environment tail")
         if env_brdf:
-            from .geometry import cube_chain_env_bytes
             if not gloss:
                 raise CrychicError(-1, "set_cube_map: env_brdf needs a prefiltered chain (levels > 1 and gloss=True)")
-            d = int(dim) if dim is not None else int(cube.shape[1])
-            if cube.numel() * cube.element_size() < cube_chain_env_bytes(d, levels):
-                raise CrychicError(-1, "set_cube_map: env_brdf needs a tensor of %d bytes (the chain, its environment tail and the table)"
-                                   % cube_chain_env_bytes(d, levels))
+            holds("env_brdf", cube_chain_env_bytes, "the chain, its environment tail and the table")
         if ambient_sh:
-            from .geometry import cube_chain_sh_bytes
             if int(levels) > 1 and not gloss:
                 raise CrychicError(-4, "set_cube_map: ambient_sh with a derivative-LOD chain is not supported (no chain, or gloss=True)")
-            d = int(dim) if dim is not None else int(cube.shape[1])
-            if cube.numel() * cube.element_size() < cube_chain_sh_bytes(d, levels):
-                raise CrychicError(-1, "set_cube_map: ambient_sh needs a tensor of %d bytes (the cube map and its environment tail)"
-                                   % cube_chain_sh_bytes(d, levels))
+            holds("ambient_sh", cube_chain_sh_bytes, "the cube map and its environment tail")
         self.mCubeMapGloss = bool(gloss)
         self.mCubeMapAmbientSH = bool(ambient_sh)
         self.mCubeMapEnvBrdf = bool(env_brdf)
@@ -470,8 +457,7 @@ class Crychic:
             out = torch.empty((nbytes,), device=self.ctx.device, dtype=torch.uint8)
         elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < nbytes or out.device != chain.device:
             raise CrychicError(-1, "prefilter_cube_map: out must be a contiguous uint8 device tensor of at least %d bytes" % nbytes)
-        if chain.dtype != torch.uint8 or not chain.is_contiguous() or chain.numel() < nbytes:
-            raise CrychicError(-1, "prefilter_cube_map: chain must be a contiguous uint8 device tensor of at least %d bytes" % nbytes)
+        _check_chain("prefilter_cube_map", chain, nbytes)
         check(lib.crychic_prefilter_cube_chain(self.ctx.handle, _ptr(chain), _ptr(out), int(dim), int(levels), _stream(self.ctx.device)))
         return out
 
@@ -482,9 +468,7 @@ class Crychic:
         `chain`; set_cube_map(chain, dim, levels, ambient_sh=True) binds it."""
         from .geometry import cube_chain_bytes, cube_chain_sh_bytes, cube_sh_offset
         dim, levels, level = int(dim), int(levels), int(level)
-        if chain.dtype != torch.uint8 or not chain.is_contiguous() or chain.numel() < cube_chain_sh_bytes(dim, levels):
-            raise CrychicError(-1, "project_irradiance: chain must be a contiguous uint8 device tensor of at least %d bytes"
-                               % cube_chain_sh_bytes(dim, levels))
+        _check_chain("project_irradiance", chain, cube_chain_sh_bytes(dim, levels))
         if not 0 <= level < max(levels, 1):
             raise CrychicError(-1, "project_irradiance: level %d outside 0 .. %d" % (level, max(levels, 1) - 1))
         base = chain.data_ptr()
@@ -499,9 +483,7 @@ class Crychic:
         Returns `chain`; set_cube_map(chain, dim, levels, gloss=True, env_brdf=True) binds it."""
         from .geometry import cube_chain_env_bytes, cube_env_brdf_offset
         dim, levels = int(dim), int(levels)
-        if chain.dtype != torch.uint8 or not chain.is_contiguous() or chain.numel() < cube_chain_env_bytes(dim, levels):
-            raise CrychicError(-1, "build_env_brdf: chain must be a contiguous uint8 device tensor of at least %d bytes"
-                               % cube_chain_env_bytes(dim, levels))
+        _check_chain("build_env_brdf", chain, cube_chain_env_bytes(dim, levels))
         check(lib.crychic_build_env_brdf(self.ctx.handle, C.c_void_p(chain.data_ptr() + cube_env_brdf_offset(dim, levels)),
                                          _stream(self.ctx.device)))
         return chain
@@ -514,9 +496,7 @@ class Crychic:
         set_cube_map(chain, dim, levels, gloss=True, parallax=True) binds it."""
         from .geometry import cube_chain_sh_bytes, cube_sh_offset
         dim, levels = int(dim), int(levels)
-        if chain.dtype != torch.uint8 or not chain.is_contiguous() or chain.numel() < cube_chain_sh_bytes(dim, levels):
-            raise CrychicError(-1, "set_probe_volume: chain must be a contiguous uint8 device tensor of at least %d bytes"
-                               % cube_chain_sh_bytes(dim, levels))
+        _check_chain("set_probe_volume", chain, cube_chain_sh_bytes(dim, levels))
         v = [(C.c_float * 3)(*[float(x) for x in a]) for a in (pos, box_min, box_max)]
         check(lib.crychic_set_cube_probe_volume(self.ctx.handle, C.c_void_p(chain.data_ptr() + cube_sh_offset(dim, levels)), v[0], v[1], v[2],
                                                 _stream(self.ctx.device)))
@@ -689,8 +669,8 @@ class Crychic:
     def set_spot_shadows(self, count, dim=1024, fov_y=math.pi / 2, z_near=0.5, geometry=None):
         """Extension: the first `count` (<= 8) spot lights cast shadows (include/crychic_hip.h crychic_deferred_light_spots_shadowed).
         Allocates `count` dim x dim D24 maps, builds each light's transform (crychic_update_spot_shadow_transform: perspective, fov_y,
-        z_near .. FalloffEnd) and from then on writes it into ShadowTransforms[4 + k] and routes every Draw through the _shadowed
-        entries (mMainPassCB itself is not modified).  geometry (a SceneGeometry of the shadow casters): Draw renders the maps first,
+        z_near .. FalloffEnd) and from then on every Draw writes it into ShadowTransforms[4 + k] and passes the
+        maps' descriptor (mMainPassCB itself is not modified).  geometry (a SceneGeometry of the shadow casters): Draw renders the maps first,
         in one DrawSceneToShadowMaps call, after whatever the caller drew for the cascades; without it the caller fills mSpotShadowMaps
         (DrawSpotShadowMaps renders them on demand).  count 0 removes the shadows."""
         if count == 0:
@@ -731,8 +711,8 @@ class Crychic:
     def set_point_shadows(self, count, dim=512, z_near=0.5, geometry=None):
         """Extension: the first `count` (<= 4) point lights cast cube shadows (include/crychic_hip.h crychic_deferred_light_point_shadows).
         Allocates mPointShadowMaps, (count, 6, dim, dim) D24 faces cleared to 1.0, builds each light's face views and shadow projection
-        (crychic_update_point_shadow_transforms: widened 90-degree faces, z_near .. FalloffEnd) and from then on routes every Draw
-        through the _point_shadows entries.  geometry (a SceneGeometry of the shadow casters): Draw renders the faces first
+        (crychic_update_point_shadow_transforms: widened 90-degree faces, z_near .. FalloffEnd) and from then on every Draw
+        passes their descriptor.  geometry (a SceneGeometry of the shadow casters): Draw renders the faces first
         (DrawPointShadowMaps); without it the caller fills mPointShadowMaps.  count 0 removes the shadows."""
         if count == 0:
             self.mPointShadowMaps, self._pointShadow = None, None
@@ -877,41 +857,23 @@ class SceneGeometry:
     def DrawNormalsDepthAndGBuffer(self, pass_cb, normal, gbuffer, depth, g_rows=None):
         """DrawNormalsAndDepth + DrawGBuffer on one rasterisation (same items, same ViewProj => same visibility); every plane is
         bit-identical to the two separate passes.  g_rows = (row0, rows): a rank's strip -- depth and normals for the whole
-        frame, G0..G2 for those rows only (crychic_draw_normals_depth_and_gbuffer_rows)."""
-        H, W = int(depth.shape[0]), int(depth.shape[1])
-        ws = self.workspace(W, H)
-        if gbuffer_flags(gbuffer):
-            return self._draw_gbuffer_formats(pass_cb, normal, gbuffer, depth, g_rows, ws)
-        if g_rows is not None:
-            check(lib.crychic_draw_normals_depth_and_gbuffer_rows(self.ctx.handle, C.byref(pass_cb), self.items, len(self.items), _ptr(self.materials),
-                                                                  self.n_materials, self.textures, self.n_textures, _ptr(normal), _ptr(gbuffer[0]),
-                                                                  _ptr(gbuffer[1]), _ptr(gbuffer[2]), _ptr(depth), W, H, int(g_rows[0]), int(g_rows[1]),
-                                                                  _ptr(ws), ws.numel(), _stream(self.ctx.device)))
-            return
-        check(lib.crychic_draw_normals_depth_and_gbuffer(self.ctx.handle, C.byref(pass_cb), self.items, len(self.items), _ptr(self.materials),
-                                                         self.n_materials, self.textures, self.n_textures, _ptr(normal), _ptr(gbuffer[0]),
-                                                         _ptr(gbuffer[1]), _ptr(gbuffer[2]), _ptr(depth), W, H, _ptr(ws), ws.numel(),
-                                                         _stream(self.ctx.device)))
+        frame, G0..G2 for those rows only."""
+        if normal is None:      # the library would take it for the G-buffer pass alone
+            raise CrychicError(-1, "null normal / G-buffer target")
+        self._draw_camera_pass(pass_cb, normal, gbuffer, depth, g_rows)
 
     def DrawGBuffer(self, pass_cb, gbuffer, depth, g_rows=None):  # CRYCHIC.cpp:2545-2571; g_rows = (row0, rows): scissored to a strip
-        H, W = int(depth.shape[0]), int(depth.shape[1])
-        ws = self.workspace(W, H)
-        if gbuffer_flags(gbuffer):
-            return self._draw_gbuffer_formats(pass_cb, None, gbuffer, depth, g_rows, ws)
-        if g_rows is not None:
-            check(lib.crychic_draw_gbuffer_rows(self.ctx.handle, C.byref(pass_cb), self.items, len(self.items), _ptr(self.materials), self.n_materials,
-                                                self.textures, self.n_textures, _ptr(gbuffer[0]), _ptr(gbuffer[1]), _ptr(gbuffer[2]), _ptr(depth), W, H,
-                                                int(g_rows[0]), int(g_rows[1]), _ptr(ws), ws.numel(), _stream(self.ctx.device)))
-            return
-        check(lib.crychic_draw_gbuffer(self.ctx.handle, C.byref(pass_cb), self.items, len(self.items), _ptr(self.materials), self.n_materials,
-                                       self.textures, self.n_textures, _ptr(gbuffer[0]), _ptr(gbuffer[1]), _ptr(gbuffer[2]), _ptr(depth), W, H,
-                                       _ptr(ws), ws.numel(), _stream(self.ctx.device)))
+        self._draw_camera_pass(pass_cb, None, gbuffer, depth, g_rows)
 
-    def _draw_gbuffer_formats(self, pass_cb, normal, gbuffer, depth, g_rows, ws):
-        """The G-buffer producers with a half4 plane among G0..G2 (each plane's format is its tensor's dtype): normal None = the
-        G-buffer pass alone, otherwise the fused pass."""
+    def _draw_camera_pass(self, pass_cb, normal, gbuffer, depth, g_rows):
+        """crychic_draw_gbuffer_formats, the G-buffer producers in one: normal None = the G-buffer pass alone, otherwise the fused
+        pass; each plane's format is its tensor's dtype.  The entry reads 0 rows as the whole target, so an explicit g_rows with 0
+        rows is refused here, as the _rows entries refuse it."""
         H, W = int(depth.shape[0]), int(depth.shape[1])
         r0, rn = (0, 0) if g_rows is None else (int(g_rows[0]), int(g_rows[1]))
+        if g_rows is not None and rn == 0:
+            raise CrychicError(-1, "G-buffer rows [%u,+%u) outside the %u-row target" % (r0, rn, H))
+        ws = self.workspace(W, H)
         check(lib.crychic_draw_gbuffer_formats(self.ctx.handle, C.byref(pass_cb), self.items, len(self.items), _ptr(self.materials),
                                                self.n_materials, self.textures, self.n_textures, _ptr(normal), _ptr(gbuffer[0]), _ptr(gbuffer[1]),
                                                _ptr(gbuffer[2]), gbuffer_flags(gbuffer), _ptr(depth), W, H, r0, rn, _ptr(ws), ws.numel(),

@@ -251,8 +251,8 @@ public:
         // back buffer that Present sees is complete on every GPU.  The reference has one GPU (NodeMask 0, CRYCHIC.cpp:96,105).
         // With SetExchangeParts(n > 1) the lighting pass runs in n row ranges and each range travels while the next is lit.
         // Local lights (SetLocalLights; an extension the reference's shader leaves dead): point lights ride in the frame descriptor,
-        // spot lights and their shadows take the _spots_shadowed entries.  With no spot lights, or a shadow count of 0, those entries
-        // are crychic_draw_hot_path(_shared) / the _spots entries bit for bit (include/crychic_hip.h).
+        // spot lights and both kinds of shadow take the _point_shadows entries.  With no spot lights, or a shadow count of 0, those
+        // entries are the narrower ones bit for bit (include/crychic_hip.h).
         if (L.mPointLights) { f.point_lights_dev = static_cast<const crychic_light*>(L.mPointLights->Data()); f.numPointLights = L.mNumPointLights; }
         const crychic_light* spots = L.mSpotLights ? static_cast<const crychic_light*>(L.mSpotLights->Data()) : nullptr;
         // Shadowed spot lights (SetSpotShadows): the first mSpotShadowCount spot lights read their maps through ShadowTransforms[4 + k]
@@ -262,26 +262,20 @@ public:
         for (uint32_t k = 0; k < sh.count; ++k) sh.maps[k] = static_cast<const uint32_t*>(L.mSpotShadowMaps[k]->Data());
         const auto* ssaoCB = reinterpret_cast<const crychic_ssao_constants*>(&scb);
         const auto* passCB = reinterpret_cast<const crychic_pass_constants*>(&pcb);
-        if (L.mPointShadowCount > 0) {
-            // Shadowed point lights (SetPointShadows): the first mPointShadowCount point lights read their six faces through shadowProj
-            crychic_point_shadows psh = {};
-            psh.count = L.mPointShadowCount;
-            psh.dim = L.mPointShadowDim;
-            for (uint32_t k = 0; k < psh.count; ++k) {
-                psh.maps[k] = static_cast<const uint32_t*>(L.mPointShadowMaps[k]->Data());
-                std::memcpy(psh.shadowProj[k], L.mPointShadowProjs[k], sizeof psh.shadowProj[k]);
-            }
-            if (mComm)
-                CrychicThrowIfFailed(crychic_draw_hot_path_shared_point_shadows(mComm, ssaoCB, passCB, &f, mStripBounds.empty() ? nullptr : mStripBounds.data(),
-                                                                                mExchangeParts, spots, L.mNumSpotLights, &sh, &psh, mCommandList->Stream()));
-            else
-                CrychicThrowIfFailed(crychic_draw_hot_path_point_shadows(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, L.mNumSpotLights, &sh, &psh,
-                                                                         mCommandList->Stream()));
-        } else if (mComm)
-            CrychicThrowIfFailed(crychic_draw_hot_path_shared_spots_shadowed(mComm, ssaoCB, passCB, &f, mStripBounds.empty() ? nullptr : mStripBounds.data(),
-                                                                             mExchangeParts, spots, L.mNumSpotLights, &sh, mCommandList->Stream()));
+        // Shadowed point lights (SetPointShadows): the first mPointShadowCount point lights read their six faces through shadowProj
+        crychic_point_shadows psh = {};
+        psh.count = L.mPointShadowCount;
+        psh.dim = L.mPointShadowDim;
+        for (uint32_t k = 0; k < psh.count; ++k) {
+            psh.maps[k] = static_cast<const uint32_t*>(L.mPointShadowMaps[k]->Data());
+            std::memcpy(psh.shadowProj[k], L.mPointShadowProjs[k], sizeof psh.shadowProj[k]);
+        }
+        if (mComm)
+            CrychicThrowIfFailed(crychic_draw_hot_path_shared_point_shadows(mComm, ssaoCB, passCB, &f, mStripBounds.empty() ? nullptr : mStripBounds.data(),
+                                                                            mExchangeParts, spots, L.mNumSpotLights, &sh, &psh, mCommandList->Stream()));
         else
-            CrychicThrowIfFailed(crychic_draw_hot_path_spots_shadowed(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, L.mNumSpotLights, &sh, mCommandList->Stream()));
+            CrychicThrowIfFailed(crychic_draw_hot_path_point_shadows(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, L.mNumSpotLights, &sh, &psh,
+                                                                     mCommandList->Stream()));
         // SetFog: the finished frame through the fog pass, in place, behind the lighting pass and in front of the anti-aliasing
         if (mFog)
             CrychicThrowIfFailed(crychic_fog(md3dDevice->Ctx(), passCB, f.depth_dev, f.shadow_dev, f.shadowDim, f.out_rgba8_dev, f.out_rgba8_dev,
@@ -371,7 +365,7 @@ public:
     // empty, Common.hlsl:46,91) -----------------------------------------------------------------------------------------------
     // The first `count` (<= 8, at most the spot lights of SetLocalLights) spot lights cast shadows: each gets a dim x dim D24 map that
     // DrawSceneToShadowMap renders after the four cascades (perspective, fovY, zNear .. FalloffEnd; crychic_update_spot_shadow_transform)
-    // and ShadowTransforms[4 + k]; Draw takes the _spots_shadowed entries (include/crychic_hip.h crychic_deferred_light_spots_shadowed).
+    // and ShadowTransforms[4 + k]; Draw hands them to the lighting pass (include/crychic_hip.h crychic_deferred_light_spots_shadowed).
     // count 0 removes the shadows.  Waits for the frames in flight first, which may still read the previous maps.
     void SetSpotShadows(uint32_t count, uint32_t dim, float fovY, float zNear)
     {
@@ -546,7 +540,7 @@ public:
         else { r0 = bounds.at(2 * (size_t)rank); rn = bounds.at(2 * (size_t)rank + 1); }
         SetStrip(r0, rn);
     }
-    // 1 (default): the strip, then one exchange.  n > 1: crychic_draw_hot_path_shared's overlapped exchange in n parts.
+    // 1 (default): the strip, then one exchange.  n > 1: the shared hot path's overlapped exchange in n parts.
     void SetExchangeParts(UINT n)
     {
         if (n == 0 || n > CRYCHIC_MAX_EXCHANGE_PARTS) throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetExchangeParts", __FILE__, __LINE__);
@@ -655,9 +649,7 @@ public:
         uint32_t dim = 0, cubeLevels = 0;
         const int rc = crychic_load_dds_cube_rgba8_mips(cubePath.c_str(), nullptr, 0, &dim, &cubeLevels);      // :1148-1151: the whole chain
         if (rc == 0) {
-            size_t bytes = 0;
-            for (uint32_t k = 0; k < cubeLevels; ++k) { const size_t d = (dim >> k) ? (dim >> k) : 1; bytes += 6 * d * d * 4; }
-            host.resize(bytes);
+            host.resize(crychic_cube_chain_bytes(dim, cubeLevels));
             CrychicThrowIfFailed(crychic_load_dds_cube_rgba8_mips(cubePath.c_str(), host.data(), host.size(), &dim, &cubeLevels));
             auto cube = std::make_unique<ID3D12Resource>(host.size(), ID3D12Resource::DEFAULT_HEAP);
             cube->Upload(host.data(), host.size(), s);
@@ -840,13 +832,8 @@ private:
     {
         for (int i = 0; i < 4; ++i) {
             PassConstants cb;
-            float vp[4][4];
-            for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) {
-                float acc = 0.0f;
-                for (int k = 0; k < 4; ++k) acc += mLightViews[i].m[r][k] * mLightProjs[i].m[k][c];
-                vp[r][c] = acc;
-            }
-            for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { cb.ViewProj.m[c][r] = vp[r][c]; cb.View.m[c][r] = mLightViews[i].m[r][c]; cb.Proj.m[c][r] = mLightProjs[i].m[r][c]; }
+            ViewProjTransposed(&mLightViews[i].m[0][0], &mLightProjs[i].m[0][0], &cb.ViewProj.m[0][0]);
+            for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { cb.View.m[c][r] = mLightViews[i].m[r][c]; cb.Proj.m[c][r] = mLightProjs[i].m[r][c]; }
             cb.RenderTargetSize = { (float)mShadowMap->Width(), (float)mShadowMap->Height() };
             cb.InvRenderTargetSize = { 1.0f / mShadowMap->Width(), 1.0f / mShadowMap->Height() };
             mCurrFrameResource->PassCB->CopyData(1 + i, cb);                                          // :897-898
@@ -854,6 +841,16 @@ private:
     }
 
     // ---- producer passes --------------------------------------------------------------------------------------------
+    // view * proj (row-major 4 x 4 each), stored transposed as the pass constants hold it.  The shadow maps are compared bit for
+    // bit: the sum runs over k = 0 .. 3 in this order.
+    static void ViewProjTransposed(const float* view, const float* proj, float* out)
+    {
+        for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) {
+            float acc = 0.0f;
+            for (int k = 0; k < 4; ++k) acc += view[4 * r + k] * proj[4 * k + c];
+            out[4 * c + r] = acc;
+        }
+    }
     std::vector<crychic_draw_item> DrawItems(const std::vector<RenderItem*>& ritems)  // CRYCHIC::DrawRenderItems, CRYCHIC.cpp:2438-2475
     {
         std::vector<crychic_draw_item> out;
@@ -902,11 +899,7 @@ private:
         uint32_t* stargets[CRYCHIC_MAX_SPOT_SHADOWS];
         for (uint32_t k = 0; k < mSpotShadowCount; ++k) {
             std::memset(&scbs[k], 0, sizeof scbs[k]);
-            for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) {
-                float acc = 0.0f;
-                for (int q = 0; q < 4; ++q) acc += mLightViews[4 + k].m[r][q] * mLightProjs[4 + k].m[q][c];
-                scbs[k].ViewProj[4 * c + r] = acc;                                                  // stored transposed
-            }
+            ViewProjTransposed(&mLightViews[4 + k].m[0][0], &mLightProjs[4 + k].m[0][0], scbs[k].ViewProj);
             stargets[k] = static_cast<uint32_t*>(mSpotShadowMaps[k]->Data());
         }
         void* sws = RasterWorkspace((uint64_t)mSpotShadowCount * mSceneTriangles, mSpotShadowDim, mSpotShadowDim, &bytes);
@@ -926,11 +919,7 @@ private:
             for (uint32_t i = 0; i < n; ++i) {
                 const uint32_t k = (first + i) / 6u, face = (first + i) % 6u;
                 std::memset(&pcbs[i], 0, sizeof pcbs[i]);
-                for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) {
-                    float acc = 0.0f;
-                    for (int q = 0; q < 4; ++q) acc += mPointViews[k][face][4 * r + q] * mPointProjs[k][4 * q + c];
-                    pcbs[i].ViewProj[4 * c + r] = acc;                                              // stored transposed
-                }
+                ViewProjTransposed(mPointViews[k][face], mPointProjs[k], pcbs[i].ViewProj);
                 ptargets[i] = static_cast<uint32_t*>(mPointShadowMaps[k]->Data()) + (size_t)face * mPointShadowDim * mPointShadowDim;
             }
             CrychicThrowIfFailed(crychic_draw_scene_to_shadow_maps(md3dDevice->Ctx(), pcbs, n, items.data(), (uint32_t)items.size(), ptargets,
@@ -948,50 +937,25 @@ private:
                                                             static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth, mClientHeight, ws, bytes,
                                                             mCommandList->Stream()));
     }
-    void DrawGBuffer()  // CRYCHIC.cpp:2545-2571
+    void DrawGBuffer() { DrawCameraPass(nullptr); }  // CRYCHIC.cpp:2545-2571
+    // DrawNormalsAndDepth + DrawGBuffer: same items, same ViewProj, same visibility -> one rasterisation
+    void DrawNormalsDepthAndGBuffer() { DrawCameraPass(mSsao->NormalMap()->Data()); }
+    void DrawCameraPass(void* normalMap)  // the G-buffer and depth, with the view normals too when there is a map for them
     {
         auto items = DrawItems(mRitemLayer[(int)RenderLayer::Opaque]);
         size_t bytes;
         void* ws = RasterWorkspace(mSceneTriangles, mClientWidth, mClientHeight, &bytes);
         const PassConstants& cb = mCurrFrameResource->PassCB->Element(0);
-        // the scissor rectangle of this pass (CRYCHIC.cpp:2547-2548) is this GPU's strip when the frame is shared (SetStrip / JoinNode)
-        const auto* passCB = reinterpret_cast<const crychic_pass_constants*>(&cb);
         const auto* mats = reinterpret_cast<const crychic_material_data*>(mCurrFrameResource->MaterialBuffer->Resource()->Data());
-        const crychic_texture* tex = mTextures.empty() ? nullptr : mTextures.data();
-        void* g[3] = { mDeferred->Resource(0)->Data(), mDeferred->Resource(1)->Data(), mDeferred->Resource(2)->Data() };
-        const uint32_t rows = mWholeFrame ? mClientHeight : mStripRows;
-        if (mDeferred->FormatFlags())       // a half4 plane among G0..G2; float4 planes keep the entry (and its argument checks) they had
-            CrychicThrowIfFailed(crychic_draw_gbuffer_formats(md3dDevice->Ctx(), passCB, items.data(), (uint32_t)items.size(), mats, (uint32_t)mMaterials.size(),
-                                                              tex, (uint32_t)mTextures.size(), nullptr, g[0], g[1], g[2], mDeferred->FormatFlags(),
-                                                              static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth, mClientHeight, mStripRow0,
-                                                              rows, ws, bytes, mCommandList->Stream()));
-        else
-            CrychicThrowIfFailed(crychic_draw_gbuffer_rows(md3dDevice->Ctx(), passCB, items.data(), (uint32_t)items.size(), mats, (uint32_t)mMaterials.size(),
-                                                           tex, (uint32_t)mTextures.size(), static_cast<float*>(g[0]), static_cast<float*>(g[1]),
-                                                           static_cast<float*>(g[2]), static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth,
-                                                           mClientHeight, mStripRow0, rows, ws, bytes, mCommandList->Stream()));
-    }
-    void DrawNormalsDepthAndGBuffer()  // DrawNormalsAndDepth + DrawGBuffer: same items, same ViewProj, same visibility -> one rasterisation
-    {
-        auto items = DrawItems(mRitemLayer[(int)RenderLayer::Opaque]);
-        size_t bytes;
-        void* ws = RasterWorkspace(mSceneTriangles, mClientWidth, mClientHeight, &bytes);
-        const PassConstants& cb = mCurrFrameResource->PassCB->Element(0);
-        const auto* passCB = reinterpret_cast<const crychic_pass_constants*>(&cb);
-        const auto* mats = reinterpret_cast<const crychic_material_data*>(mCurrFrameResource->MaterialBuffer->Resource()->Data());
-        const crychic_texture* tex = mTextures.empty() ? nullptr : mTextures.data();
-        void* g[3] = { mDeferred->Resource(0)->Data(), mDeferred->Resource(1)->Data(), mDeferred->Resource(2)->Data() };
-        const uint32_t rows = mWholeFrame ? mClientHeight : mStripRows;
-        if (mDeferred->FormatFlags())       // a half4 plane among G0..G2; float4 planes keep the entry (and its argument checks) they had
-            CrychicThrowIfFailed(crychic_draw_gbuffer_formats(md3dDevice->Ctx(), passCB, items.data(), (uint32_t)items.size(), mats, (uint32_t)mMaterials.size(),
-                                                              tex, (uint32_t)mTextures.size(), mSsao->NormalMap()->Data(), g[0], g[1], g[2],
-                                                              mDeferred->FormatFlags(), static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth,
-                                                              mClientHeight, mStripRow0, rows, ws, bytes, mCommandList->Stream()));
-        else
-            CrychicThrowIfFailed(crychic_draw_normals_depth_and_gbuffer_rows(
-                md3dDevice->Ctx(), passCB, items.data(), (uint32_t)items.size(), mats, (uint32_t)mMaterials.size(), tex, (uint32_t)mTextures.size(),
-                mSsao->NormalMap()->Data(), static_cast<float*>(g[0]), static_cast<float*>(g[1]), static_cast<float*>(g[2]),
-                static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth, mClientHeight, mStripRow0, rows, ws, bytes, mCommandList->Stream()));
+        // the scissor rectangle of this pass (CRYCHIC.cpp:2547-2548) is this GPU's strip when the frame is shared (SetStrip / JoinNode,
+        // which refuse an empty one); FormatFlags() marks the half4 planes among G0..G2, 0 = float4 throughout
+        CrychicThrowIfFailed(crychic_draw_gbuffer_formats(md3dDevice->Ctx(), reinterpret_cast<const crychic_pass_constants*>(&cb), items.data(),
+                                                          (uint32_t)items.size(), mats, (uint32_t)mMaterials.size(),
+                                                          mTextures.empty() ? nullptr : mTextures.data(), (uint32_t)mTextures.size(), normalMap,
+                                                          mDeferred->Resource(0)->Data(), mDeferred->Resource(1)->Data(), mDeferred->Resource(2)->Data(),
+                                                          mDeferred->FormatFlags(), static_cast<uint32_t*>(mDepthStencilBuffer->Data()), mClientWidth,
+                                                          mClientHeight, mStripRow0, mWholeFrame ? mClientHeight : mStripRows, ws, bytes,
+                                                          mCommandList->Stream()));
     }
     void UpdateCascadeShadowTransform(const GameTimer&)  // CRYCHIC.cpp:634-815
     {

@@ -316,7 +316,8 @@ def test_refusals_of_the_binding_and_the_size_function(built_lib, px):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     api = open(os.path.join(root, "crychic_renderer_amd", "csrc", "api.cpp")).read()
     assert "fail(CRYCHIC_E_INVALID_ARG, cry::parallax_check_message(c), cry::parallax_probe_offset(cubeDim, (flags >> 16) & 15u))" in api
-    assert api.count("check_parallax(") == 3 and '"CRYCHIC_LIGHT_CUBE_PARALLAX' not in api
+    # its definition and its one call, in check_environment; that one is defined once and called by both lighting paths
+    assert api.count("check_parallax(") == 2 and api.count("check_environment(") == 3 and '"CRYCHIC_LIGHT_CUBE_PARALLAX' not in api
     assert built_lib.LIGHT_CUBE_PARALLAX == PARALLAX == 0x200000
     assert PARALLAX & (0xF0000 | 0xFFFF | ENV_BRDF) == 0          # clear of the level count and of every other flag
     from crychic_renderer_amd import geometry as g
