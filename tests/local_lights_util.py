@@ -112,6 +112,9 @@ def _dev_lights(ctx, lights):
     return torch.from_numpy(np.frombuffer(bytes(lights), np.uint8).copy()).to(ctx.device), len(lights)
 
 
+dev_lights = _dev_lights          # for library modules
+
+
 def _app(ctx, W, H, dev, c, blur=3, ndl=3):
     from crychic_renderer_amd import Crychic, LIGHT_SKY
     app = Crychic(ctx, W, H, dev["randvec"], dev["cube"], shadow_dim=256)

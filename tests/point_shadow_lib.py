@@ -7,6 +7,7 @@ import os
 import numpy as np
 
 import local_light_lib
+import local_lights_util
 from hostsim_lib import LIGHT_ARGTYPES, ROOT, run_light
 
 DIR = os.path.join(ROOT, "tests", "point_shadow_ref")
@@ -45,6 +46,45 @@ class PointShadowLib:
         v = np.ascontiguousarray(v, np.float32)
         abc = np.zeros(3, np.float32)
         return self._ref.ps_point_face(v.ctypes.data, abc.ctypes.data), abc
+
+# ---- what the tests of the family share: transforms, faces and the descriptors of a device call -----------------------------------
+def point_transforms(lights, count, dim, z_near=0.5):
+    """crychic_update_point_shadow_transforms of the first `count` lights: [(views (6, 4, 4), proj (4, 4), shadowProj (4, 4))]."""
+    from crychic_renderer_amd import lib
+    out = []
+    for k in range(count):
+        lv, lp, sp = ((C.c_float * 16) * 6)(), (C.c_float * 16)(), (C.c_float * 16)()
+        assert lib.crychic_update_point_shadow_transforms(C.byref(lights[k]), dim, z_near, lv, lp, sp) == 0
+        out.append((np.array([lv[f][:] for f in range(6)], np.float32).reshape(6, 4, 4), np.asarray(lp[:], np.float32).reshape(4, 4),
+                    np.asarray(sp[:], np.float32).reshape(4, 4)))
+    return out
+
+
+def random_cubes(count, dim, seed):
+    return local_lights_util.random_maps(count * 6, dim, seed).reshape(count, 6, dim, dim)
+
+
+def spot_desc(dev_maps, count=None):
+    from crychic_renderer_amd._lib import SpotShadows
+    d = SpotShadows()
+    if dev_maps is not None:
+        d.count = dev_maps.shape[0] if count is None else count
+        d.dim = dev_maps.shape[1]
+        for k in range(dev_maps.shape[0]):
+            d.maps[k] = dev_maps[k].data_ptr()
+    return d
+
+
+def point_desc(dev_cubes, projs=None, count=None):
+    from crychic_renderer_amd._lib import PointShadows
+    d = PointShadows()
+    if dev_cubes is not None:
+        d.count = dev_cubes.shape[0] if count is None else count
+        d.dim = dev_cubes.shape[2]
+        for k in range(dev_cubes.shape[0]):
+            d.maps[k] = dev_cubes[k].data_ptr()
+            d.shadowProj[k][:] = [float(v) for v in np.asarray(projs[k], np.float32).reshape(-1)]
+    return d
 
 
 _LIB = None

@@ -13,6 +13,7 @@ import hostsim_lib
 import local_light_lib
 import oracle_lib
 import point_shadow_lib
+from point_shadow_lib import point_desc as _point_desc, point_transforms, random_cubes, spot_desc as _spot_desc  # noqa: F401 (other test modules import them from here)
 from local_lights_util import (FIX_ALL, _app, _cpu, _dev_lights, _device_scene, light_array, points_for_test, random_maps,
                                spot_transforms, spots_for_test, transposed, with_transforms)
 
@@ -20,22 +21,6 @@ CENTRE_P = np.zeros(16, np.float32)          # untransposed: every position -> f
 CENTRE_P[12], CENTRE_P[13], CENTRE_P[15] = 0.5, 0.5, 1.0
 AXES = np.array([[1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0], [0, 0, 1], [0, 0, -1]], np.float64)
 UPS = np.array([[0, 1, 0], [0, 1, 0], [0, 0, -1], [0, 0, 1], [0, 1, 0], [0, 1, 0]], np.float64)
-
-
-def point_transforms(lights, count, dim, z_near=0.5):
-    """crychic_update_point_shadow_transforms of the first `count` lights: [(views (6, 4, 4), proj (4, 4), shadowProj (4, 4))]."""
-    from crychic_renderer_amd import lib
-    out = []
-    for k in range(count):
-        lv, lp, sp = ((C.c_float * 16) * 6)(), (C.c_float * 16)(), (C.c_float * 16)()
-        assert lib.crychic_update_point_shadow_transforms(C.byref(lights[k]), dim, z_near, lv, lp, sp) == 0
-        out.append((np.array([lv[f][:] for f in range(6)], np.float32).reshape(6, 4, 4), np.asarray(lp[:], np.float32).reshape(4, 4),
-                    np.asarray(sp[:], np.float32).reshape(4, 4)))
-    return out
-
-
-def random_cubes(count, dim, seed):
-    return random_maps(count * 6, dim, seed).reshape(count, 6, dim, dim)
 
 
 def shadowed_points():
@@ -370,29 +355,6 @@ def test_kernel_body_matches_checker(built_lib, chain, count, spot_count):
 
 
 # ---- GPU tier ---------------------------------------------------------------------------------------------------------------
-
-def _spot_desc(dev_maps, count=None):
-    from crychic_renderer_amd._lib import SpotShadows
-    d = SpotShadows()
-    if dev_maps is not None:
-        d.count = dev_maps.shape[0] if count is None else count
-        d.dim = dev_maps.shape[1]
-        for k in range(dev_maps.shape[0]):
-            d.maps[k] = dev_maps[k].data_ptr()
-    return d
-
-
-def _point_desc(dev_cubes, projs=None, count=None):
-    from crychic_renderer_amd._lib import PointShadows
-    d = PointShadows()
-    if dev_cubes is not None:
-        d.count = dev_cubes.shape[0] if count is None else count
-        d.dim = dev_cubes.shape[2]
-        for k in range(dev_cubes.shape[0]):
-            d.maps[k] = dev_cubes[k].data_ptr()
-            d.shadowProj[k][:] = [float(v) for v in np.asarray(projs[k], np.float32).reshape(-1)]
-    return d
-
 
 def _light(lib, ctx, cb, dev, W, H, flags, points, spots, sdesc, pdesc, ndl=3, radius=0.0, ambient=None, row0=0, rows=None, out=None,
            rad=None, cube=None, entry="point_shadows", shadow_dim=256, cube_dim=32):
