@@ -26,6 +26,7 @@ GBUFFER_F16_MASK = 0x7000
 COMM_ID_BYTES = 128
 AA_MAX_SEARCH = 16            # CRYCHIC_AA_MAX_SEARCH: the longest end search of crychic_antialias, in pixels
 FOG_MAX_STEPS = 64            # CRYCHIC_FOG_MAX_STEPS: the most samples crychic_fog takes along a view ray
+DOF_MAX_RADIUS = 8            # CRYCHIC_DOF_MAX_RADIUS: the largest gather radius of crychic_dof, in pixels
 
 
 class Light(C.Structure):
@@ -117,6 +118,24 @@ class FogParams(C.Structure):
                 p.steps = int(v)
             else:
                 setattr(p, k, float(v))
+        return p
+
+
+class DofParams(C.Structure):
+    """crychic_dof_params: the knobs of crychic_dof (extension); DofParams.default() = crychic_dof_default_params, with focus, aperture
+    and radius as short names of focusDistance, aperture and maxRadius."""
+    _fields_ = [("focusDistance", C.c_float), ("aperture", C.c_float), ("maxRadius", C.c_uint32), ("reserved", C.c_uint32 * 5)]
+
+    @classmethod
+    def default(cls, focus=None, aperture=None, radius=None):
+        p = cls()
+        check(lib.crychic_dof_default_params(C.byref(p)))
+        if focus is not None:
+            p.focusDistance = float(focus)
+        if aperture is not None:
+            p.aperture = float(aperture)
+        if radius is not None:
+            p.maxRadius = int(radius)
         return p
 
 
@@ -216,6 +235,8 @@ PROTOTYPES = {
     "crychic_antialias": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(AAParams), _vp]),
     "crychic_fog_default_params": (_i, [_P(FogParams)]),
     "crychic_fog": (_i, [_vp, _P(PassConstants), _vp, _P(_vp), _u32, _vp, _vp, _u32, _u32, _u32, _u32, _P(FogParams), _vp]),
+    "crychic_dof_default_params": (_i, [_P(DofParams)]),
+    "crychic_dof": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(DofParams), _vp]),
     "crychic_save_ppm": (_i, [C.c_char_p, _vp, _u32, _u32]),
     "crychic_raster_workspace_bytes": (_sz, [C.c_uint64, _u32, _u32]),
     "crychic_raster_status": (_i, [_vp, _vp, _P(_u32)]),

@@ -20,6 +20,7 @@
 #include "cube_mips_core.hpp"
 #include "post_aa_core.hpp"
 #include "fog_core.hpp"
+#include "dof_core.hpp"
 #include "internal.hpp"
 
 namespace {
@@ -879,6 +880,52 @@ int crychic_fog(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32
     std::memcpy(&q, &p, sizeof q);
     CRY_HIP(cry::launch_fog(cb->InvViewProj, cb->EyePosW, cb->ShadowTransforms, depth_dev, shadow_dev, shadowDim, in_rgba8_dev, out_rgba8_dev, W, H,
                             row0, rows, q, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(CRYCHIC_DOF_MAX_RADIUS == cry::kDofMaxRadius && sizeof(crychic_dof_params) == 32 && sizeof(crychic_dof_params) == sizeof(cry::DofParams),
+              "dof_core.hpp mirrors the ABI");
+
+int crychic_dof_default_params(crychic_dof_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    *out = crychic_dof_params{};
+    out->focusDistance = 15.0f; out->aperture = 6.0f; out->maxRadius = CRYCHIC_DOF_MAX_RADIUS;
+    return 0;
+}
+
+int crychic_dof(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev,
+                uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const crychic_dof_params* params, void* stream)
+{
+    // every argument is checked before the context is looked at: a refusal needs no device
+    if (!cb || !depth_dev || !in_rgba8_dev || !out_rgba8_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    const uintptr_t s = reinterpret_cast<uintptr_t>(in_rgba8_dev), d = reinterpret_cast<uintptr_t>(out_rgba8_dev);
+    if ((reinterpret_cast<uintptr_t>(depth_dev) | s | d) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "depth-of-field planes are not 4-byte aligned");
+    if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
+    if (int rc = check_extent("frame", W, H, false, 0u)) return rc;                   // a one-dimensional grid, at most 2^24 workgroups
+    if (int rc = check_rows(kFrameRows, row0, rows, H)) return rc;
+    crychic_dof_params p;
+    crychic_dof_default_params(&p);
+    if (params) p = *params;
+    if (!(p.focusDistance > 0.0f && p.focusDistance <= 3.40282347e38f))
+        return fail(CRYCHIC_E_INVALID_ARG, "depth-of-field focusDistance %g is not a finite positive number", (double)p.focusDistance);
+    if (!(p.aperture >= 0.0f && p.aperture <= 64.0f)) return fail(CRYCHIC_E_INVALID_ARG, "depth-of-field aperture %g outside 0 .. 64", (double)p.aperture);
+    if (p.maxRadius == 0 || p.maxRadius > CRYCHIC_DOF_MAX_RADIUS)
+        return fail(CRYCHIC_E_INVALID_ARG, "depth-of-field maxRadius %u outside 1 .. %d", p.maxRadius, CRYCHIC_DOF_MAX_RADIUS);
+    if (p.reserved[0] | p.reserved[1] | p.reserved[2] | p.reserved[3] | p.reserved[4])
+        return fail(CRYCHIC_E_INVALID_ARG, "depth-of-field reserved words must be 0");
+    const float A = cb->Proj[10], B = cb->Proj[11];
+    const float big = 3.40282347e38f;
+    if (!(A >= -big && A <= big && B >= -big && B <= big) || B == 0.0f)
+        return fail(CRYCHIC_E_INVALID_ARG, "Proj[10] = %g and Proj[11] = %g must be finite and Proj[11] not 0 (viewZ = Proj[11] / (d - Proj[10]))",
+                    (double)A, (double)B);
+    const size_t bytes = (size_t)W * H * 4u;
+    if (ranges_overlap(s, bytes, d, bytes))
+        return fail(CRYCHIC_E_INVALID_ARG, "the depth-of-field input and output planes overlap (the pass cannot run in place)");
+    if (int rc = bind(ctx)) return rc;
+    cry::DofParams q;
+    std::memcpy(&q, &p, sizeof q);
+    CRY_HIP(cry::launch_dof(cb->Proj, depth_dev, in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, q, (hipStream_t)stream));
     return 0;
 }
 

@@ -100,6 +100,13 @@ hipError_t launch_fog(const float* invViewProj, const float* eye, const float (*
                       const uint32_t* const* maps, uint32_t dim, const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0,
                       uint32_t rows, const FogParams& p, hipStream_t stream);
 
+// dof.hip: rows [row0, row0 + rows) of the W x H RGBA8 frame `out`: `in` blurred by the circle of confusion of the D24 plane `depth`
+// (dof_core.hpp); proj is the pass constants' Proj, read before the call returns.  One launch on `stream`, none for rows == 0.  The
+// caller has checked the pointers, their alignment and overlap, the sizes, the rows, proj and `p`.
+struct DofParams;
+hipError_t launch_dof(const float* proj, const uint32_t* depth, const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0,
+                      uint32_t rows, const DofParams& p, hipStream_t stream);
+
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
 struct Texture;

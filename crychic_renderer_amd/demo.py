@@ -2,6 +2,7 @@
                                    [--capture-env X,Y,Z [--capture-dim N]] [--gloss] [--env-ambient] [--env-specular]
                                    [--probe-box X0,Y0,Z0,X1,Y1,Z1] [--aa]
                                    [--fog [--fog-density X] [--fog-steps N]]
+                                   [--dof [--dof-focus X] [--dof-aperture X] [--dof-radius N]]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
@@ -25,7 +26,10 @@ camera.
 --aa: the finished frame goes through the post-process anti-aliasing pass (Crychic.antiAliasing = True: crychic_antialias after the
 lighting pass, the deferred path's stand-in for the framework's 4x MSAA switch) and the anti-aliased buffer is what is written.
 --fog: volumetric fog with sun shafts through the cascade maps (Crychic.fog: crychic_fog after the lighting pass, in place on the back
-buffer, in front of --aa); --fog-density (default 0.02) and --fog-steps (default 16, at most 64) set its parameters."""
+buffer, in front of --aa); --fog-density (default 0.02) and --fog-steps (default 16, at most 64) set its parameters.
+--dof: depth of field from the depth plane (Crychic.depthOfField: crychic_dof after the lighting pass and the fog, in front of --aa);
+--dof-focus (the distance in focus, default 15), --dof-aperture (the blur radius in pixels of a point at infinity, default 6, at most
+64) and --dof-radius (the gather radius in pixels, default 8, at most 8) set its parameters.  The PPM is the last stage's output."""
 import argparse
 import ctypes as C
 
@@ -56,7 +60,14 @@ def main():
     ap.add_argument("--fog", action="store_true", help="volumetric fog with sun shafts through the cascades, after the lighting pass")
     ap.add_argument("--fog-density", type=float, default=None, metavar="X", help="fog density, 0 .. 16 (default 0.02; needs --fog)")
     ap.add_argument("--fog-steps", type=int, default=None, metavar="N", help="samples along each view ray, 1 .. 64 (default 16; needs --fog)")
+    ap.add_argument("--dof", action="store_true", help="depth of field from the depth plane, after the lighting pass and the fog")
+    ap.add_argument("--dof-focus", type=float, default=None, metavar="X", help="view-space distance in focus (default 15; needs --dof)")
+    ap.add_argument("--dof-aperture", type=float, default=None, metavar="X", help="circle-of-confusion radius in pixels of a point at infinity, "
+                                                                                  "0 .. 64 (default 6; needs --dof)")
+    ap.add_argument("--dof-radius", type=int, default=None, metavar="N", help="gather radius in pixels, 1 .. 8 (default 8; needs --dof)")
     a = ap.parse_args()
+    if (a.dof_focus is not None or a.dof_aperture is not None or a.dof_radius is not None) and not a.dof:
+        ap.error("--dof-focus, --dof-aperture and --dof-radius need --dof")
     if (a.fog_density is not None or a.fog_steps is not None) and not a.fog:
         ap.error("--fog-density and --fog-steps need --fog")
     box = None
@@ -76,7 +87,7 @@ def main():
     W, H = (int(v) for v in a.size.lower().split("x"))
     import torch
     from . import Context, Crychic, LIGHT_SKY, SceneGeometry, check, geometry as g, lib, scene
-    from ._lib import FogParams, PassConstants
+    from ._lib import DofParams, FogParams, PassConstants
     ctx = Context(0)
     consts = scene.Constants(W, H, a.shadow_dim)
     tex = g.reference_textures(a.textures) if a.textures else g.procedural_textures(64)
@@ -126,13 +137,15 @@ def main():
     if a.fog:
         knobs = {k: v for k, v in (("density", a.fog_density), ("steps", a.fog_steps)) if v is not None}
         app.fog = FogParams.default(**knobs) if knobs else True
+    if a.dof:
+        app.depthOfField = DofParams.default(focus=a.dof_focus, aperture=a.dof_aperture, radius=a.dof_radius)
     if a.aa:
         app.antiAliasing = True
     app.Draw()
     torch.cuda.synchronize()
-    img = np.ascontiguousarray((app.mBackBufferAA if a.aa else app.mBackBuffer).cpu().numpy())
+    img = np.ascontiguousarray((app.mBackBufferAA if a.aa else (app.mBackBufferDoF if a.dof else app.mBackBuffer)).cpu().numpy())
     check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, W, H))
-    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, (", fog" if a.fog else "") + (", anti-aliased" if a.aa else ""), ctx.device_name))
+    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, (", fog" if a.fog else "") + (", depth of field" if a.dof else "") + (", anti-aliased" if a.aa else ""), ctx.device_name))
 
 
 if __name__ == "__main__":

@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (AAParams, CrychicError, FogParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, FogParams, DofParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -220,9 +220,28 @@ class Crychic:
         self._pointHost = None       # host copy of the point lights (the face transforms are built from it)
         self._pointShadow = None     # (PointShadows descriptor, [face pass constants, 6 per light], geometry)
         self._desc = None
-        self.antiAliasing = None     # extension: None | True | AAParams -- Draw() of a whole frame runs crychic_antialias into mBackBufferAA
+        # The switches of the passes behind the lighting pass (the properties below): Draw() looks at _post alone, so a frame with none
+        # of them set pays one test however many passes there are.
+        self._post = False
+        self._antiAliasing = None    # antiAliasing, extension: None | True | AAParams -- Draw() of a whole frame runs crychic_antialias into mBackBufferAA
         self.mBackBufferAA = None    # the anti-aliased frame, allocated by the first antialias() that needs it
-        self.fog = None              # extension: None | True | FogParams -- Draw() of a whole frame runs crychic_fog in place on mBackBuffer
+        self._fog = None             # fog, extension: None | True | FogParams -- Draw() of a whole frame runs crychic_fog in place on mBackBuffer
+        self._depthOfField = None    # depthOfField, extension: None | True | DofParams -- Draw() of a whole frame runs crychic_dof into mBackBufferDoF
+        self.mBackBufferDoF = None   # the frame behind the depth-of-field pass, allocated by the first depth_of_field() that needs it
+
+    def _post_switch(name):          # noqa: N805 -- a class-body helper: the property of one switch
+        def get(self):
+            return getattr(self, name)
+
+        def put(self, value):
+            setattr(self, name, value)
+            self._post = bool(self._fog or self._antiAliasing or self._depthOfField)
+        return property(get, put)
+
+    antiAliasing = _post_switch("_antiAliasing")
+    fog = _post_switch("_fog")
+    depthOfField = _post_switch("_depthOfField")
+    del _post_switch
 
     def set_gbuffer_formats(self, formats):
         """Re-allocates the G-buffer in the given formats (gbuffer_formats: "f32", "mixed", "f16" or three per-plane formats); its
@@ -285,10 +304,14 @@ class Crychic:
         antiAliasing = True or an AAParams (extension): a whole frame, then crychic_antialias over it into mBackBufferAA; mBackBuffer is
         the frame without it.  A strip or a shared draw then raises CrychicError.
         fog = True or a FogParams (extension): a whole frame, then crychic_fog in place on mBackBuffer (in front of the anti-aliasing
-        if that is set too).  A strip or a shared draw then raises CrychicError."""
-        if self.fog:
-            return self._draw_fogged(row0, rows, shared)
-        if self.antiAliasing:
+        if that is set too).  A strip or a shared draw then raises CrychicError.
+        depthOfField = True or a DofParams (extension): a whole frame (fogged if fog is set), then crychic_dof from mBackBuffer into
+        mBackBufferDoF; the anti-aliasing, if set too, then reads mBackBufferDoF.  A strip or a shared draw then raises CrychicError."""
+        if self._post:
+            if self._depthOfField:
+                return self._draw_with_depth_of_field(row0, rows, shared)
+            if self._fog:
+                return self._draw_fogged(row0, rows, shared)
             return self._draw_antialiased(row0, rows, shared)
         # The descriptor only changes when a plane is re-allocated or a knob is turned: keep it across frames so the
         # per-frame host cost is one FFI call (matters once a strip takes tens of microseconds on 8 GPUs).  The key holds
@@ -361,6 +384,38 @@ class Crychic:
         self.apply_fog(params=fog if isinstance(fog, FogParams) else None)
         if aa:
             self.antialias(params=aa if isinstance(aa, AAParams) else None)
+
+    def _draw_with_depth_of_field(self, row0, rows, shared):
+        """Draw() with depthOfField set: the frame as Draw() issues it without (fogged in place if fog is set), the depth-of-field
+        pass from mBackBuffer into mBackBufferDoF, then the anti-aliasing of mBackBufferDoF if that is set."""
+        self._whole_frame_only("depthOfField", row0, rows, shared)
+        dof, aa, self.depthOfField, self.antiAliasing = self.depthOfField, self.antiAliasing, None, None
+        try:
+            self.Draw()
+        finally:
+            self.depthOfField, self.antiAliasing = dof, aa
+        self.depth_of_field(params=dof if isinstance(dof, DofParams) else None)
+        if aa:
+            self.antialias(src=self.mBackBufferDoF, params=aa if isinstance(aa, AAParams) else None)
+
+    def depth_of_field(self, src=None, out=None, row0=0, rows=None, params=None):
+        """crychic_dof on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferDoF, allocated on first use)
+        from `src` (default: mBackBuffer), both (H, W, 4) uint8 tensors of the frame's size, with this frame's depth plane and pass
+        constants; params: a DofParams, None = the defaults.  The pass reads rows [row0 - R, row0 + rows + R) of `src` and of the
+        depth plane and writes no other byte of `out`; `src` and `out` must not overlap.  Returns `out`."""
+        src = self.mBackBuffer if src is None else src
+        if out is None:
+            if self.mBackBufferDoF is None or self.mBackBufferDoF.shape != src.shape or self.mBackBufferDoF.device != src.device:
+                self.mBackBufferDoF = torch.zeros_like(src)
+            out = self.mBackBufferDoF
+        H, W = int(src.shape[0]), int(src.shape[1])
+        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
+                or not src.is_contiguous() or not out.is_contiguous() or (H, W) != (self.mClientHeight, self.mClientWidth):
+            raise CrychicError(-1, "depth_of_field takes contiguous (H, W, 4) uint8 tensors of the frame's size")
+        check(lib.crychic_dof(self.ctx.handle, C.byref(self.mMainPassCB), self.mDepthStencilBuffer.data_ptr(), _ptr(src), _ptr(out), W, H,
+                              int(row0), int(H - row0 if rows is None else rows), None if params is None else C.byref(params),
+                              _stream(self.ctx.device)))
+        return out
 
     def apply_fog(self, src=None, out=None, row0=0, rows=None, params=None):
         """crychic_fog on the context's stream: rows [row0, row0 + rows) of `out` from `src`, both (H, W, 4) uint8 tensors (default:

@@ -165,6 +165,7 @@ public:
         CrychicHipThrowIfFailed(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(mDepthStencilBuffer->Data()), 0x00FFFFFF, n));
         mBackBuffer = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
         if (mAntiAliasing) mBackBufferAA = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
+        if (mDepthOfField) mBackBufferDoF = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
         mCamera.SetLens(0.25f * 3.1415926535f, AspectRatio(), 1.0f, 100.0f);                       // :114
         if (mSsao) { mSsao->OnResize(mClientWidth, mClientHeight); mSsao->RebuildDescriptors(mDepthStencilBuffer.get()); }
         if (mDeferred) { mDeferred->OnResize(mClientWidth, mClientHeight); mDeferred->BuildDescriptors(); }
@@ -211,6 +212,9 @@ public:
         if (mFog && (!mWholeFrame || mComm))
             throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (fog takes the whole frame on one GPU: no SetStrip / JoinNode)", __FILE__,
                                    __LINE__);
+        if (mDepthOfField && (!mWholeFrame || mComm))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (depth of field takes the whole frame on one GPU: no SetStrip / JoinNode)",
+                                   __FILE__, __LINE__);
         if (mRunProducerPasses) {
             DrawSceneToShadowMap();                                                                 // :208
             if (mFuseCameraPasses) DrawNormalsDepthAndGBuffer();                                    // :214 + :236 on one rasterisation
@@ -280,9 +284,13 @@ public:
         if (mFog)
             CrychicThrowIfFailed(crychic_fog(md3dDevice->Ctx(), passCB, f.depth_dev, f.shadow_dev, f.shadowDim, f.out_rgba8_dev, f.out_rgba8_dev,
                                              mClientWidth, mClientHeight, 0, mClientHeight, &mFogParams, mCommandList->Stream()));
+        // SetDepthOfField: the finished (and fogged) frame through the lens blur into its own back buffer, in front of the anti-aliasing
+        if (mDepthOfField)
+            CrychicThrowIfFailed(crychic_dof(md3dDevice->Ctx(), passCB, f.depth_dev, f.out_rgba8_dev, static_cast<uint8_t*>(mBackBufferDoF->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
+                                             &mDofParams, mCommandList->Stream()));
         // SetAntiAliasing: the finished frame through the post-process pass into the second back buffer, behind the lighting pass
         if (mAntiAliasing)
-            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), static_cast<const uint8_t*>(mBackBuffer->Data()),
+            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), static_cast<const uint8_t*>((mDepthOfField ? mBackBufferDoF : mBackBuffer)->Data()),
                                                    static_cast<uint8_t*>(mBackBufferAA->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
                                                    &mAAParams, mCommandList->Stream()));
         // :300-305: advance the fence and signal it behind this frame's commands
@@ -330,6 +338,31 @@ public:
         mFogParams = q;
     }
     bool Fog() const { return mFog; }
+
+    // ---- depth of field (extension) -------------------------------------------------------------------------------------------------
+    // A thin-lens blur from the depth plane (include/crychic_hip.h crychic_dof).  On: Draw issues the pass after the lighting pass of a
+    // whole frame (and after the fog, if that is on), from the back buffer into a buffer of its own that OnResize re-creates; the
+    // anti-aliasing, if on too, then reads that buffer, and Present writes the last stage's output.  CurrentBackBuffer stays the frame
+    // without it.  p == nullptr: the default parameters.  With it on, SetStrip / JoinNode make Draw throw (the pass is not sharded).
+    // Off (the default): nothing changes.
+    void SetDepthOfField(bool on, const crychic_dof_params* p = nullptr)
+    {
+        crychic_dof_params q;
+        CrychicThrowIfFailed(crychic_dof_default_params(&q));
+        if (p) q = *p;
+        if (!(q.focusDistance > 0.0f && q.focusDistance <= 3.40282347e38f) || !(q.aperture >= 0.0f && q.aperture <= 64.0f) || q.maxRadius == 0 ||
+            q.maxRadius > CRYCHIC_DOF_MAX_RADIUS || (q.reserved[0] | q.reserved[1] | q.reserved[2] | q.reserved[3] | q.reserved[4]))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG,
+                                   "CRYCHIC::SetDepthOfField (focusDistance finite and > 0, aperture 0 .. 64, maxRadius 1 .. 8, reserved 0)", __FILE__,
+                                   __LINE__);
+        mCommandList->Flush();                                  // a frame in flight may still write the buffer released below
+        mDepthOfField = on;
+        mDofParams = q;
+        if (on) mBackBufferDoF = std::make_unique<ID3D12Resource>((size_t)mClientWidth * mClientHeight * 4, ID3D12Resource::DEFAULT_HEAP);
+        else mBackBufferDoF.reset();
+    }
+    bool DepthOfField() const { return mDepthOfField; }
+    ID3D12Resource* DepthOfFieldBackBuffer() { return mBackBufferDoF.get(); }
 
     // ---- local lights (extension: the reference's point and spot branches, PBR.hlsl:109-147, are dead code) -------------------
     // Uploads both lists to device buffers this object owns (at most 1024 each); Draw lights them after the directional lights,
@@ -558,7 +591,7 @@ public:
     void Present(const std::string& path)
     {
         std::vector<uint8_t> host((size_t)mClientWidth * mClientHeight * 4);
-        (mAntiAliasing ? mBackBufferAA : mBackBuffer)->Download(host.data(), host.size(), mCommandList->Stream());
+        (mAntiAliasing ? mBackBufferAA : (mDepthOfField ? mBackBufferDoF : mBackBuffer))->Download(host.data(), host.size(), mCommandList->Stream());
         mCommandList->Flush();
         CrychicThrowIfFailed(crychic_save_ppm(path.c_str(), host.data(), mClientWidth, mClientHeight));
     }
@@ -1028,6 +1061,9 @@ private:
     bool mWholeFrame = true;
     bool mFog = false;                        // SetFog
     crychic_fog_params mFogParams = {};
+    bool mDepthOfField = false;               // SetDepthOfField
+    crychic_dof_params mDofParams = {};
+    std::unique_ptr<ID3D12Resource> mBackBufferDoF;  // the frame behind the depth-of-field pass, while mDepthOfField
     bool mAntiAliasing = false;               // SetAntiAliasing
     crychic_aa_params mAAParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferAA;   // the anti-aliased frame, while mAntiAliasing

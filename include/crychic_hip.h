@@ -925,6 +925,66 @@ int crychic_fog(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32
                 uint32_t shadowDim, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0,
                 uint32_t rows, const crychic_fog_params* params /* NULL = defaults */, void* stream);
 
+/* ---- depth of field from the depth plane (extension) -------------------------------------------------------
+ * One pass over the finished RGBA8 frame, a separate call after the lighting pass (and the fog) and before the anti-aliasing: a
+ * thin-lens blur.  Every texel has a circle of confusion from its depth; every output pixel gathers the texels of a disc of radius R
+ * around it, each weighed by how far its own circle reaches, with the rule that a sample behind the pixel cannot spread over it
+ * further than the pixel itself is blurred (a sharp foreground stays sharp in front of a blurred background) while a sample in front
+ * spreads with its own circle (a blurred foreground bleeds over what is behind it).  A build definition: nothing of it is the
+ * reference's.  The device, a host build and the checker (tests/dof_ref) agree bit for bit.
+ *
+ * Float operations are IEEE binary32, each rounded once, in the order written; nothing is fused except inside d24_to_float (see
+ * crychic_fog above: fma(v, C_hi, v C_lo) with v = (float)(u & 0xFFFFFF), the IEEE quotient v / 16777215; the top byte is ignored).
+ * clampf(x, lo, hi) = fminf(fmaxf(x, lo), hi), so a NaN gives lo.
+ *
+ * Host side, once per call:  A = cb->Proj[10], B = cb->Proj[11] in memory order (the two numbers of the SSAO pass's ndc_to_view:
+ * viewZ = B / (d - A)), both finite and B != 0;  g = focusDistance / B (IEEE division);  ap16 = aperture * 16.0f;
+ * hi = (float)(16 R) with R = maxRadius.
+ * Circle of confusion of a depth texel, c = 0 .. 16 R <= 128, in 1/16 pixel:
+ *   d = d24_to_float(depth);  x = (d - A) g  (= focusDistance / viewZ, the thin-lens term, without a reciprocal per texel);
+ *   e = fabsf(1.0f - x);  u = e ap16;  c = (uint32_t)(clampf(u, 0.0f, hi) + 0.5f).
+ * Tables, pure integer:  for every offset o = (ox, oy) with ox^2 + oy^2 <= R^2 (5, 13, 29, 49, 81, 113, 149, 197 offsets at
+ * R = 1 .. 8):  d16(o) = isqrt(256 (ox^2 + oy^2)), the floor integer square root;  inv[c] = 2^20 / max(c, 16)^2 (floor) for
+ * c = 0 .. 128, so inv[0 .. 16] = 4096, inv[17] = 3628, inv[64] = 256, inv[128] = 64.
+ * Per output pixel p, with D_p the low 24 bits of its depth word and c_p its circle of confusion: over every offset o of the disc
+ * whose sample s = p + o lies inside the FRAME [0, W) x [0, H) -- the frame, not the row range of the call; a sample outside it is
+ * skipped:
+ *   c_e = (D_s > D_p) ? min(c_s, c_p) : c_s;   k = clamp((int)c_e + 8 - (int)d16(o), 0, 16);   w = k inv[c_e];
+ *   Sw += w;   S_ch += w in_s[ch]  for R, G, B.
+ * The sums are 32-bit unsigned.  The centre tap has c_e = c_p, d16 = 0 and k = min(c_p + 8, 16) >= 8, so Sw >= min over c of
+ * min(c + 8, 16) inv[c] = 16 inv[128] = 1024 > 0;  w <= 16 * 4096, so the largest channel sum is 197 * 16 * 4096 * 255 =
+ * 3 292 200 960 < 2^32, and adding Sw >> 1 (at most 197 * 32768) does not reach 2^32 either.
+ *   out[ch] = (S_ch + (Sw >> 1)) / Sw  for R, G, B;   alpha is the pixel's own input alpha.
+ * Integer sums make the result independent of the order of the taps, which is what lets the kernel reorder and skip them.
+ * Known answers: aperture 0 gives out == in byte for byte (a tap other than the centre has d16 >= 16 and needs c_e >= 9 to weigh
+ * anything); a frame of one colour stays that colour under any depth and parameters; a depth step with the near half at c = 0 and
+ * the far half at c = 128 gives the near half back byte for byte and changes the far half; with the near half at c = 128 and the far
+ * half at c = 0 the far pixels more than 8 columns from the step come back byte for byte and those within 8 columns change; under
+ * constant depth an input symmetric under the eight symmetries of the square lattice gives a symmetric output.
+ *
+ * Parameters: focusDistance (view-space units, default 15; finite, > 0), aperture (the circle-of-confusion radius in pixels of a
+ * point at infinity, default 6; finite, 0 .. 64), maxRadius = R (pixels, default 8; 1 .. CRYCHIC_DOF_MAX_RADIUS), reserved (must be
+ * 0).  crychic_dof_default_params fills the defaults (pure host code; CRYCHIC_E_INVALID_ARG for NULL). */
+#define CRYCHIC_DOF_MAX_RADIUS 8
+typedef struct crychic_dof_params {
+    float focusDistance;
+    float aperture;
+    uint32_t maxRadius;
+    uint32_t reserved[5];
+} crychic_dof_params;   /* 32 bytes */
+int crychic_dof_default_params(crychic_dof_params* out);
+/* Writes rows [row0, row0 + rows) of out_rgba8_dev and no other byte; reads rows [row0 - R, row0 + rows + R) cut to [0, H) of
+ * in_rgba8_dev and depth_dev (W x H, D24 in the low 24 bits), and Proj of cb (a host pointer, read during the call).  Stitched row
+ * ranges equal the whole-frame call byte for byte, for any row0 and rows; rows == 0 launches nothing.  in and out must not overlap
+ * at all within W * H * 4 bytes: a pixel reads its neighbours.  params == NULL = the defaults.  One launch on `stream`: no
+ * allocation, no synchronisation, no host read-back; capturable into a graph.
+ * CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and before anything is enqueued: a NULL plane or cb, a
+ * plane that is not 4-byte aligned, W or H of 0, a row range outside the frame, a parameter outside its range or a non-zero reserved
+ * word, a non-finite Proj[10] or Proj[11] or Proj[11] == 0, in and out overlapping.  More than 2^28 pixels: CRYCHIC_E_UNSUPPORTED. */
+int crychic_dof(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32_t* depth_dev, const uint8_t* in_rgba8_dev,
+                uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                const crychic_dof_params* params /* NULL = defaults */, void* stream);
+
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
  * of 2 rows (half-res alignment); the last rank takes the remainder. */
