@@ -100,14 +100,19 @@ def same_floats(a, b):
     return bool(np.array_equal(an, bn) and np.array_equal(a.view(np.uint32)[~an], b.view(np.uint32)[~bn]))
 
 
-def sky_probe_case(seed):
+def sky_probe_case(seed, consts=None, cam=None):
     """Inputs for the SSAO sky-shortcut probe (tests/test_hostsim_parity.py::test_sky_shortcut_is_exact and its device twin): a sky
-    field with small patches of geometry within OcclusionFadeEnd of the far distance."""
+    field with small patches of geometry within OcclusionFadeEnd of the far distance.
+    cam: the camera in place of the reference one; consts: a scene.Constants to use as it is (its W x H is the frame's size).  The
+    patches sit at 0.99 .. 0.99999 of the camera's far distance and are encoded with the constants' own A and B."""
     import oracle_lib
     from crychic_renderer_amd import scene
     rng = np.random.default_rng(1000 + seed)
     W, H = int(rng.choice([640, 770, 1024])), int(rng.choice([384, 400, 512]))       # several cells of the coarse geometry map each way
-    c = scene.Constants(W, H, shadow_dim=64)
+    if consts is not None:
+        W, H = consts.W, consts.H
+    c = consts if consts is not None else scene.Constants(W, H, shadow_dim=64, cam=cam)
+    far = float(c.cam.farZ)
     scb = oracle_lib.as_oracle_cb(c.ssao_cb, oracle_lib.OrSsaoConstants)
     A, B = c.ssao_cb.Proj[10], c.ssao_cb.Proj[11]
     depth = np.full((H, W), 0xFFFFFF, dtype=np.uint32)
@@ -123,9 +128,9 @@ def sky_probe_case(seed):
             pw, ph = int(rng.integers(1, 3)), int(rng.integers(1, 3))
             x0 = min(W - pw, 128 * int(rng.integers(1, W // 128)) - 2 - int(rng.integers(0, 2)) * pw)
             y0 = min(H - ph, 32 * int(rng.integers(1, H // 32)) - int(rng.integers(0, 2)) * ph)
-        vz = rng.uniform(99.0, 99.999, size=(ph, pw))                       # inside the occluding band of a pixel at the far distance
+        vz = rng.uniform(far * 0.99, far * 99.999 / 100.0, size=(ph, pw))   # inside the occluding band of a pixel at the far distance
         zndc = A + B / vz
-        depth[y0:y0 + ph, x0:x0 + pw] = np.round(zndc * 16777215.0).astype(np.uint32)
+        depth[y0:y0 + ph, x0:x0 + pw] = np.clip(np.round(zndc * 16777215.0), 0, 0xFFFFFF).astype(np.uint32)
         normal[y0:y0 + ph, x0:x0 + pw, :3] = rng.standard_normal((ph, pw, 3)).astype(np.float16)
     if seed % 4 == 3:
         normal[rng.random((H, W)) < 0.01, 0] = np.inf                        # a non-finite normal keeps its wavefront off the shortcut
@@ -135,37 +140,45 @@ def sky_probe_case(seed):
     return W, H, c, scb, depth, normal, randvec
 
 
-def clear_cell_probe_case(seed):
+def clear_cell_probe_case(seed, consts=None, cam=None):
     """Inputs for the clear-cell rule of the SSAO depth pass (ssao_core.hpp "clear cells"): sky next to geometry that hugs the near
     plane, an occlusion radius that puts taps at and behind the camera (q.z < 1e-3: never culled, landing anywhere -- mostly beyond
-    the plane's edge, which is clear by definition) and a few non-finite normals (pixels that may not cull at all)."""
+    the plane's edge, which is clear by definition) and a few non-finite normals (pixels that may not cull at all).
+    consts / cam: as sky_probe_case takes them; the geometry sits at 1.0 .. 1.8 times the camera's near distance and the occlusion
+    radius is three times that distance."""
     import oracle_lib
-    W, H, c, scb, depth, normal, randvec = sky_probe_case(seed)
+    W, H, c, scb, depth, normal, randvec = sky_probe_case(seed, consts, cam)
     rng = np.random.default_rng(77 + seed)
     A, B = c.ssao_cb.Proj[10], c.ssao_cb.Proj[11]
+    near = float(c.cam.nearZ)
     x0, x1 = W // 5, W // 5 + 90 + 8 * seed
-    vz = rng.uniform(1.0, 1.8, size=(H // 2, x1 - x0))
+    vz = rng.uniform(1.0, 1.8, size=(H // 2, x1 - x0)) * near
     depth[H // 4:H // 4 + H // 2, x0:x1] = np.clip(np.round((A + B / vz) * 16777215.0), 0, 0xFFFFFF).astype(np.uint32)
     normal[H // 4:H // 4 + H // 2, x0:x1, :3] = rng.standard_normal((H // 2, x1 - x0, 3)).astype(np.float16)
     normal[rng.random((H, W)) < 0.002, 1] = np.nan
-    c.ssao_cb.OcclusionRadius = 3.0
+    c.ssao_cb.OcclusionRadius = 3.0 * near
     scb = oracle_lib.as_oracle_cb(c.ssao_cb, oracle_lib.OrSsaoConstants)
     return W, H, c, scb, depth, normal, randvec
 
 
-def rough_wall_case(seed, W, H, sky_blocks):
+def rough_wall_case(seed, W, H, sky_blocks, consts=None, cam=None):
     """Frames for the blur chain's tile hand-off (tests/test_blur_chain_handoff.py): a "rough wall" -- view depth uniform in
     [6.0, 6.6] per texel, normals (0.5 n1, 0.5 n2, -1) with n1, n2 standard normal, random randvec.  About 90 % of the texels
     come out occluded, every texel changes under the blur and NO tile settles, so every tile of the chain takes part in the
     hand-off and a stale apron read changes the result.  sky_blocks: rectangles of sky (clear depth, normal (0, 0, -1)) on a grid
     of 256 x 96 full-res texels (2 x 3 blur tiles), each present with probability 1/2 -- tiles inside them settle and their
-    workgroups return at once, which makes the load uneven.  Returns (c, scb, depth, normal, randvec)."""
+    workgroups return at once, which makes the load uneven.
+    consts / cam: as sky_probe_case takes them (consts must be W x H); a camera whose frustum does not hold [6.0, 6.6] gets the
+    wall scaled to the geometric middle of its near and far distances.  Returns (c, scb, depth, normal, randvec)."""
     import oracle_lib
     from crychic_renderer_amd import scene
     rng = np.random.default_rng(seed)
-    c = scene.Constants(W, H, shadow_dim=64)
+    c = consts if consts is not None else scene.Constants(W, H, shadow_dim=64, cam=cam)
+    assert (c.W, c.H) == (W, H)
     A, B = c.ssao_cb.Proj[10], c.ssao_cb.Proj[11]
-    vz = rng.uniform(6.0, 6.6, size=(H, W))
+    near, far = float(c.cam.nearZ), float(c.cam.farZ)
+    k = 1.0 if near < 6.0 and far > 6.6 else (near * far) ** 0.5 / 6.3
+    vz = rng.uniform(6.0, 6.6, size=(H, W)) * k
     depth = np.clip(np.round((A + B / vz) * 16777215.0), 0, 0xFFFFFE).astype(np.uint32)
     normal = np.zeros((H, W, 4), np.float16); normal[..., 2] = -1.0
     normal[..., :2] = (0.5 * rng.standard_normal((H, W, 2))).astype(np.float16)
@@ -181,13 +194,21 @@ def rough_wall_case(seed, W, H, sky_blocks):
     return c, scb, depth, normal, randvec
 
 
-def cull_probe_case(seed, W=256, H=160):
+def cull_probe_case(seed, W=256, H=160, consts=None, cam=None):
     """Frames for the SSAO tap culling (ssao_core.hpp): the reference scene -- open ground, where most taps are culled -- with what
     the nearest-depth bound must not miss: single near texels (spikes a fraction of a block wide), texels just in front of their
     surroundings (around SurfaceEpsilon in view space), holes to the far plane, depth 0, a few small patches, NaN normals, and one
-    of several SurfaceEpsilon values.  Returns (W, H, constants, depth, normal, randvec)."""
+    of several SurfaceEpsilon values.
+    consts / cam: as sky_probe_case takes them (consts must be W x H): the scene is then ray-cast through that camera, and depth
+    is encoded with its near and far distances.  Returns (W, H, constants, depth, normal, randvec)."""
     import scene_util
-    pl = scene_util.cpu_scene(W, H, 64, 8)
+    if consts is not None or cam is not None:
+        from crychic_renderer_amd import scene
+        consts = consts if consts is not None else scene.Constants(W, H, shadow_dim=64, cam=cam)
+        assert (consts.W, consts.H) == (W, H)
+        pl = scene.make_scene(W, H, shadow_dim=consts.shadow_dim, cube_dim=8, device="cpu", consts=consts)
+    else:
+        pl = scene_util.cpu_scene(W, H, 64, 8)
     p = scene_util.np_planes(pl)
     c = pl["consts"]
     rng = np.random.default_rng(1234 + seed)

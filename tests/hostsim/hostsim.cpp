@@ -210,6 +210,21 @@ void hs_ssao(const crychic_ssao_constants* cb, const void* normal, const uint32_
     hs_ssao_path(cb, normal, depth, randvec, ambient, edge_base, W, H, row0, rows, 1);
 }
 
+// What the launchers' guards decide for these constants (ssao_core.hpp, blur_tiles.hpp; the functions kernels.hip calls once per
+// launch): out = { sparse, sky.enabled, sky.rx, sky.ry, cull.enabled, cull.clear, weights positive }.
+void hs_ssao_guards(const crychic_ssao_constants* cb, uint32_t W, uint32_t H, uint32_t out[7])
+{
+    const SkyReach sky = ssao_sky_reach(*cb, W, H);
+    const CullParams cp = ssao_cull_params(*cb);
+    out[0] = ssao_projtex_is_sparse(*cb) ? 1u : 0u;
+    out[1] = sky.enabled ? 1u : 0u;
+    out[2] = sky.rx;
+    out[3] = sky.ry;
+    out[4] = cp.enabled ? 1u : 0u;
+    out[5] = cp.clear ? 1u : 0u;
+    out[6] = blur_weights_positive(*cb) ? 1u : 0u;
+}
+
 void hs_blur(const crychic_ssao_constants* cb, void* edge_base, const uint16_t* in, uint16_t* out, uint32_t W,
              uint32_t H, int horizontal, uint32_t row0, uint32_t rows)
 {

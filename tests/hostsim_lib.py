@@ -124,6 +124,7 @@ class HostSim:
         L.hs_eval_array.argtypes = [i, C.c_size_t, vp, vp, vp]
         L.hs_ssao.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32]
         L.hs_ssao_path.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, u32, u32, i]
+        L.hs_ssao_guards.argtypes = [vp, u32, u32, vp]
         L.hs_last_sky_waves.restype = u32
         L.hs_last_culled_taps.restype = u32
         L.hs_last_clear_cell_taps.restype = u32
@@ -165,6 +166,13 @@ class HostSim:
         self.lib.hs_ssao_path(C.addressof(cb), n.ctypes.data, d.ctypes.data, r.ctypes.data, out.ctypes.data if emit else None,
                               edge.ctypes.data, W, H, row0, rows, (1 if cull else 2) if pairs else 0)
         return out, edge
+
+    def ssao_guards(self, cb, W, H):
+        """What the launchers' guards decide for cb on a W x H frame, from the product's own functions: a dict of sparse, sky, rx,
+        ry, cull, clear, weights (hs_ssao_guards)."""
+        out = (C.c_uint32 * 7)()
+        self.lib.hs_ssao_guards(C.addressof(cb), W, H, out)
+        return dict(zip(("sparse", "sky", "rx", "ry", "cull", "clear", "weights"), (int(v) for v in out)))
 
     def blur(self, cb, edge, ambient_in, W, H, horizontal, row0=0, rows=None):
         rows = H // 2 - row0 if rows is None else rows

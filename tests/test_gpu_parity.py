@@ -195,6 +195,29 @@ def test_compute_ssao_bit_exact(ctx, built_lib, oracle, W, H, blur_count):
         assert np.array_equal(got[row0:row0 + rows], ref[row0:row0 + rows]), (row0, rows, int((got[row0:row0 + rows] != ref[row0:row0 + rows]).sum()))
 
 
+@pytest.mark.parametrize("W,H", [(322, 190), (130, 34)])
+@pytest.mark.parametrize("blur_count", [9, 10, 12])
+def test_compute_ssao_at_the_chain_plan_boundary(ctx, built_lib, oracle, W, H, blur_count):
+    """blurCount 9 is the longest chain that runs as one launch (its 8 replay iterations fill BlurChainPlan); from 10 on api.cpp
+    issues one replay launch per iteration in the same process (blurCount - 1 > 8).  Both equal the oracle's sweeps, whole map and
+    row strips, both planes poisoned before every call.  crychic_blur_chain_status reports 0 either way: at 9 no workgroup timed
+    out; at 10 and 12 no chain ran, and the call answers for the last chain of this context (or 0 if there was none)."""
+    c = get_case(ctx, built_lib, W, H)
+    lib, check = built_lib.lib, built_lib.check
+    ref = oracle.compute_ssao(c.scb, c.np["normal"], c.np["depth"], c.np["randvec"], blur_count)
+    h2 = H // 2
+    flag = C.c_uint32(7)
+    for row0, rows in ((0, h2), (h2 // 3, h2 // 4 + 1), (h2 - 9, 9)):
+        c.a0.fill_(0x5A5A); c.a1.fill_(0x2525)
+        check(lib.crychic_ssao_compute(ctx.handle, C.byref(c.consts.ssao_cb), ptr(c.dev["normal"]), ptr(c.dev["depth"]),
+                                       ptr(c.dev["randvec"]), ptr(c.a0), ptr(c.a1), ptr(c.edge), W, H, blur_count, row0, rows,
+                                       stream(ctx)))
+        check(lib.crychic_blur_chain_status(ctx.handle, stream(ctx), C.byref(flag)))
+        assert flag.value == 0
+        got = dev_u16(c.a0)
+        assert np.array_equal(got[row0:row0 + rows], ref[row0:row0 + rows]), (row0, rows, int((got[row0:row0 + rows] != ref[row0:row0 + rows]).sum()))
+
+
 def test_blur_chain_single_launch_equals_per_iteration(ctx, built_lib, oracle):
     """Iterations 1 .. blurCount - 1 as ONE launch with per-tile dependencies (kernels.hip blur_replay_chain_kernel) against the oracle's
     sweep-by-sweep chain and against one launch per iteration (CRYCHIC_BLUR_PER_ITERATION=1 in a child process): whole maps and

@@ -52,7 +52,7 @@ def oracle_chain(oracle, scb, normal, depth, start, blur_count):
 
 
 @pytest.mark.parametrize("W,H", [(64, 64), (130, 34), (256, 256), (300, 100)])
-@pytest.mark.parametrize("blur_count", [1, 2, 3, 4, 5, 8])
+@pytest.mark.parametrize("blur_count", [1, 2, 3, 4, 5, 8, 9, 10])
 def test_blur_chain_matches_oracle(built_lib, oracle, hostsim, W, H, blur_count):
     """The two-launch blur chain (blur_tiles.hpp: iteration 0 as one H + V launch, the others fused and replayed, tile by tile
     with recomputed aprons) equals the oracle's 2 * blurCount separate sweeps -- on the SSAO output and on noise (noise exercises
