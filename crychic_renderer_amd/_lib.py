@@ -139,6 +139,24 @@ class DofParams(C.Structure):
         return p
 
 
+MAX_DECALS, DECAL_MAX_TEXTURES = 64, 16       # CRYCHIC_MAX_DECALS, CRYCHIC_DECAL_MAX_TEXTURES
+DECAL_ALBEDO, DECAL_ROUGHNESS, DECAL_METALNESS, DECAL_NORMAL = 1, 2, 4, 8
+DECAL_NO_TEXTURE = 0xFFFFFFFF
+
+
+class Decal(C.Structure):
+    """crychic_decal (160 bytes): an oriented box that blends a texture into the G-buffer planes (extension; crychic_apply_decals).
+    geometry.decal_from_box fills one from a matrix."""
+    _fields_ = [("invWorld", C.c_float * 12), ("boundsMin", C.c_float * 3), ("boundsMax", C.c_float * 3), ("tangentW", C.c_float * 3),
+                ("bitangentW", C.c_float * 3), ("normalW", C.c_float * 3), ("tint", C.c_float * 3), ("opacity", C.c_float),
+                ("roughness", C.c_float), ("metalness", C.c_float), ("fadeScale", C.c_float), ("fadeBias", C.c_float),
+                ("texelsPerUnit", C.c_float), ("texture", C.c_uint32), ("normalTexture", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(Decal) == 160
+
+
 class PassTimes(C.Structure):
     _fields_ = [("ssao_ms", C.c_float), ("blur_ms", C.c_float), ("light_ms", C.c_float), ("total_ms", C.c_float)]
 
@@ -237,6 +255,8 @@ PROTOTYPES = {
     "crychic_fog": (_i, [_vp, _P(PassConstants), _vp, _P(_vp), _u32, _vp, _vp, _u32, _u32, _u32, _u32, _P(FogParams), _vp]),
     "crychic_dof_default_params": (_i, [_P(DofParams)]),
     "crychic_dof": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(DofParams), _vp]),
+    "crychic_decal_from_box": (_i, [_P(_f), _u32, _u32, _f, _f, _P(Decal)]),
+    "crychic_apply_decals": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _u32, _vp, _u32, _P(Texture), _u32, _u32, _u32, _u32, _u32, _vp]),
     "crychic_save_ppm": (_i, [C.c_char_p, _vp, _u32, _u32]),
     "crychic_raster_workspace_bytes": (_sz, [C.c_uint64, _u32, _u32]),
     "crychic_raster_status": (_i, [_vp, _vp, _P(_u32)]),

@@ -3,6 +3,7 @@
 // CRYCHIC::Draw (CRYCHIC.cpp:220-221,238-279), and per-pass HIP-event timing.  No CPU compute path exists
 // here: every compute entry point needs a context bound to a HIP device.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -21,6 +22,7 @@
 #include "post_aa_core.hpp"
 #include "fog_core.hpp"
 #include "dof_core.hpp"
+#include "decal_core.hpp"
 #include "internal.hpp"
 
 namespace {
@@ -926,6 +928,122 @@ int crychic_dof(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32
     cry::DofParams q;
     std::memcpy(&q, &p, sizeof q);
     CRY_HIP(cry::launch_dof(cb->Proj, depth_dev, in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, q, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(sizeof(crychic_decal) == 160 && sizeof(cry::DecalTexture) == sizeof(crychic_texture), "crychic_decal is 160 bytes");
+
+int crychic_decal_from_box(const float world[16], uint32_t texW, uint32_t texH, float cosFadeStart, float cosFadeEnd, crychic_decal* out)
+{
+    if (!world || !out) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(world[k])) return fail(CRYCHIC_E_INVALID_ARG, "decal matrix entry %d is not finite", k);
+    if (!(world[12] == 0.0f && world[13] == 0.0f && world[14] == 0.0f && world[15] == 1.0f))
+        return fail(CRYCHIC_E_INVALID_ARG, "decal matrix is not affine (last column %g %g %g %g, not 0 0 0 1)", (double)world[12], (double)world[13],
+                    (double)world[14], (double)world[15]);
+    if (texW == 0 || texH == 0) return fail(CRYCHIC_E_INVALID_ARG, "decal texture size %ux%u must be non-zero", texW, texH);
+    if (!(cosFadeStart >= -1.0f && cosFadeStart <= 1.0f && cosFadeEnd >= -1.0f && cosFadeEnd <= 1.0f) || cosFadeStart < cosFadeEnd ||
+        (cosFadeStart == cosFadeEnd && cosFadeStart != 1.0f))
+        return fail(CRYCHIC_E_INVALID_ARG, "decal fade cosines (%g, %g): both in [-1, 1] and start > end, or (1, 1) for no fade", (double)cosFadeStart,
+                    (double)cosFadeEnd);
+    // m[r][a]: component r of the cube's axis a; m[r][3]: the centre
+    double m[3][4], len[3];
+    for (int r = 0; r < 3; ++r)
+        for (int a = 0; a < 4; ++a) m[r][a] = (double)world[4 * r + a];
+    for (int a = 0; a < 3; ++a) {
+        len[a] = std::sqrt(m[0][a] * m[0][a] + m[1][a] * m[1][a] + m[2][a] * m[2][a]);
+        if (!(len[a] >= 0x1p-60)) return fail(CRYCHIC_E_INVALID_ARG, "decal matrix is singular (axis %d has length %g)", a, len[a]);
+    }
+    // the inverse of the 3 x 3 part by cofactors; each axis is scaled to unit length first so that the determinant test is about angles
+    double u[3][3];
+    for (int r = 0; r < 3; ++r)
+        for (int a = 0; a < 3; ++a) u[r][a] = m[r][a] / len[a];
+    const double c00 = u[1][1] * u[2][2] - u[1][2] * u[2][1], c01 = u[1][2] * u[2][0] - u[1][0] * u[2][2], c02 = u[1][0] * u[2][1] - u[1][1] * u[2][0];
+    const double det = u[0][0] * c00 + u[0][1] * c01 + u[0][2] * c02;
+    if (!(std::fabs(det) >= 0x1p-40)) return fail(CRYCHIC_E_INVALID_ARG, "decal matrix is singular (its unit axes span a volume of %g)", det);
+    double iu[3][3];        // inverse of u: iu[a][r]
+    iu[0][0] = c00 / det; iu[1][0] = c01 / det; iu[2][0] = c02 / det;
+    iu[0][1] = (u[0][2] * u[2][1] - u[0][1] * u[2][2]) / det; iu[1][1] = (u[0][0] * u[2][2] - u[0][2] * u[2][0]) / det; iu[2][1] = (u[0][1] * u[2][0] - u[0][0] * u[2][1]) / det;
+    iu[0][2] = (u[0][1] * u[1][2] - u[0][2] * u[1][1]) / det; iu[1][2] = (u[0][2] * u[1][0] - u[0][0] * u[1][2]) / det; iu[2][2] = (u[0][0] * u[1][1] - u[0][1] * u[1][0]) / det;
+    *out = crychic_decal{};
+    for (int a = 0; a < 3; ++a) {
+        double t = 0.0;
+        for (int r = 0; r < 3; ++r) {
+            const double e = iu[a][r] / len[a];
+            out->invWorld[4 * a + r] = (float)e;
+            t -= e * m[r][3];
+        }
+        out->invWorld[4 * a + 3] = (float)t;
+    }
+    for (int r = 0; r < 3; ++r) {
+        out->tangentW[r] = (float)u[r][0]; out->bitangentW[r] = (float)u[r][1]; out->normalW[r] = (float)u[r][2];
+        out->tint[r] = 1.0f;
+    }
+    out->opacity = 1.0f;
+    const double tx = (double)texW / len[0], ty = (double)texH / len[1];
+    out->texelsPerUnit = (float)(tx > ty ? tx : ty);
+    if (cosFadeStart == cosFadeEnd) { out->fadeScale = 0.0f; out->fadeBias = 1.0f; }
+    else { out->fadeScale = 1.0f / (cosFadeStart - cosFadeEnd); out->fadeBias = -cosFadeEnd * out->fadeScale; }
+    double big = 0.0, lo[3], hi[3];
+    for (int r = 0; r < 3; ++r) { lo[r] = HUGE_VAL; hi[r] = -HUGE_VAL; }
+    for (int k = 0; k < 8; ++k)
+        for (int r = 0; r < 3; ++r) {
+            const double p = m[r][3] + ((k & 1) ? 0.5 : -0.5) * m[r][0] + ((k & 2) ? 0.5 : -0.5) * m[r][1] + ((k & 4) ? 0.5 : -0.5) * m[r][2];
+            lo[r] = p < lo[r] ? p : lo[r]; hi[r] = p > hi[r] ? p : hi[r];
+            big = std::fabs(p) > big ? std::fabs(p) : big;
+        }
+    for (int r = 0; r < 3; ++r) {
+        const double pad = 0x1p-10 * ((hi[r] - lo[r]) + big);
+        float a = (float)(lo[r] - pad), b = (float)(hi[r] + pad);
+        if ((double)a > lo[r] - pad) a = std::nextafterf(a, -HUGE_VALF);
+        if ((double)b < hi[r] + pad) b = std::nextafterf(b, HUGE_VALF);
+        out->boundsMin[r] = a; out->boundsMax[r] = b;
+    }
+    out->flags = CRYCHIC_DECAL_ALBEDO;
+    out->normalTexture = CRYCHIC_DECAL_NO_TEXTURE;
+    return 0;
+}
+
+int crychic_apply_decals(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32_t* depth_dev, void* g0_dev, void* g1_dev, void* g2_dev,
+                         uint32_t formatFlags, const crychic_decal* decals_dev, uint32_t nDecals, const crychic_texture* textures,
+                         uint32_t nTextures, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, void* stream)
+{
+    // every argument is checked before the context is looked at: a refusal needs no device
+    if (!cb || !depth_dev || !g0_dev || !g1_dev || !g2_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (nDecals > 0 && !decals_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument (decals_dev with nDecals %u)", nDecals);
+    if (nTextures > 0 && !textures) return fail(CRYCHIC_E_INVALID_ARG, "null argument (textures with nTextures %u)", nTextures);
+    if (formatFlags & ~CRYCHIC_GBUFFER_F16_MASK)
+        return fail(CRYCHIC_E_INVALID_ARG, "formatFlags 0x%x: bits outside CRYCHIC_GBUFFER_G0_F16 | G1_F16 | G2_F16", formatFlags);
+    void* const planes[3] = { g0_dev, g1_dev, g2_dev };
+    for (int k = 0; k < 3; ++k) {
+        const uintptr_t need = (formatFlags & (CRYCHIC_GBUFFER_G0_F16 << k)) ? 8u : 16u;
+        if (reinterpret_cast<uintptr_t>(planes[k]) & (need - 1u))
+            return fail(CRYCHIC_E_INVALID_ARG, "G-buffer plane %d is not %u-byte aligned", k, (unsigned)need);
+    }
+    if ((reinterpret_cast<uintptr_t>(depth_dev) | reinterpret_cast<uintptr_t>(decals_dev)) & 3u)
+        return fail(CRYCHIC_E_INVALID_ARG, "the depth plane and the decals are not 4-byte aligned");
+    if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
+    if (int rc = check_extent("frame", W, H, false, 0u)) return rc;                   // a one-dimensional grid, at most 2^27 workgroups
+    if (int rc = check_rows(kFrameRows, row0, rows, H)) return rc;
+    if (nDecals > CRYCHIC_MAX_DECALS) return fail(CRYCHIC_E_INVALID_ARG, "nDecals %u exceeds %d", nDecals, CRYCHIC_MAX_DECALS);
+    if (nTextures > CRYCHIC_DECAL_MAX_TEXTURES) return fail(CRYCHIC_E_INVALID_ARG, "nTextures %u exceeds %d", nTextures, CRYCHIC_DECAL_MAX_TEXTURES);
+    for (uint32_t k = 0; k < nTextures; ++k) {
+        const crychic_texture& t = textures[k];
+        if (!t.rgba8_dev || t.width == 0 || t.height == 0)
+            return fail(CRYCHIC_E_INVALID_ARG, "decal texture %u: a NULL pointer or a zero side (%ux%u)", k, t.width, t.height);
+        if (reinterpret_cast<uintptr_t>(t.rgba8_dev) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "decal texture %u is not 4-byte aligned", k);
+        uint32_t most = 0;
+        for (uint32_t s = t.width > t.height ? t.width : t.height; s; s >>= 1) ++most;      // floor(log2(max(w, h))) + 1
+        if (t.mipLevels > most) return fail(CRYCHIC_E_INVALID_ARG, "decal texture %u: %u levels, a %ux%u texture has at most %u", k, t.mipLevels, t.width, t.height, most);
+        if ((uint64_t)t.width * t.height > (1ull << 28)) return fail(CRYCHIC_E_UNSUPPORTED, "decal texture %u: %ux%u exceeds 2^28 texels", k, t.width, t.height);
+    }
+    for (int k = 8; k < 12; ++k)
+        if (!std::isfinite(cb->View[k])) return fail(CRYCHIC_E_INVALID_ARG, "View[%d] = %g is not finite", k, (double)cb->View[k]);
+    if (!std::isfinite(cb->Proj[5]) || cb->Proj[5] == 0.0f) return fail(CRYCHIC_E_INVALID_ARG, "Proj[5] = %g must be finite and not 0", (double)cb->Proj[5]);
+    if (int rc = bind(ctx)) return rc;
+    if (nDecals == 0 || rows == 0) return 0;
+    CRY_HIP(cry::launch_decals(cb->View, cb->Proj, depth_dev, g0_dev, g1_dev, g2_dev, formatFlags, decals_dev, nDecals, textures, nTextures, W, H, row0,
+                               rows, (hipStream_t)stream));
     return 0;
 }
 

@@ -209,6 +209,15 @@ CRY_HD float half_to_float(uint16_t h)
     return (float)v;
 }
 
+// float -> half, round to nearest even (fp16 render-target write)
+CRY_HD uint16_t float_to_half(float f)
+{
+    _Float16 h = (_Float16)f;
+    uint16_t u;
+    __builtin_memcpy(&u, &h, 2);
+    return u;
+}
+
 // ---- deterministic transcendentals -------------------------------------------------------------------
 // sin/cos: 3-term Cody-Waite reduction by pi/2, degree-7 / degree-8 kernels on [-pi/4, pi/4], every step one mad.
 CRY_HD float det_sincos(float x, int want_cos)

@@ -107,6 +107,14 @@ struct DofParams;
 hipError_t launch_dof(const float* proj, const uint32_t* depth, const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0,
                       uint32_t rows, const DofParams& p, hipStream_t stream);
 
+// decal.hip: rows [row0, row0 + rows) of the W x H G-buffer planes g0, g1, g2 (half4 where formatFlags has the plane's
+// CRYCHIC_GBUFFER_G*_F16 bit) with the nDecals decals of the device array blended in (decal_core.hpp); view and proj are the pass
+// constants' fields and textures the host table, all read before the call returns.  One launch on `stream`, none for nDecals == 0 or
+// rows == 0.  The caller has checked the pointers, their alignment, the sizes, the rows, the counts, the textures and the constants.
+hipError_t launch_decals(const float* view, const float* proj, const uint32_t* depth, void* g0, void* g1, void* g2, uint32_t formatFlags,
+                         const crychic_decal* decals, uint32_t nDecals, const crychic_texture* textures, uint32_t nTextures, uint32_t W, uint32_t H,
+                         uint32_t row0, uint32_t rows, hipStream_t stream);
+
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
 struct Texture;

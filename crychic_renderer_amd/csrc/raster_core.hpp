@@ -212,15 +212,6 @@ CRY_HD uint64_t fragment_key(const SetupTri& t, const EdgeFlags& e, double bias,
 
 constexpr uint64_t kVisClear = (uint64_t)0x00FFFFFFu << 32;   // depth 1.0, no primitive
 
-// float -> half, round to nearest even (fp16 render-target write)
-CRY_HD uint16_t float_to_half(float f)
-{
-    _Float16 h = (_Float16)f;
-    uint16_t u;
-    __builtin_memcpy(&u, &h, 2);
-    return u;
-}
-
 // One texel of a G-buffer plane in the plane's format (crychic_hip.h CRYCHIC_GBUFFER_G*_F16): float4 as computed, or the same four
 // values through float_to_half packed into one 8-byte store (x in the low half of the first dword, the normal map's layout).
 CRY_HD void gbuffer_store(void* plane, uint32_t idx, uint32_t isHalf, f4 v)

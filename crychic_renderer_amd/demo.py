@@ -29,7 +29,9 @@ lighting pass, the deferred path's stand-in for the framework's 4x MSAA switch) 
 buffer, in front of --aa); --fog-density (default 0.02) and --fog-steps (default 16, at most 64) set its parameters.
 --dof: depth of field from the depth plane (Crychic.depthOfField: crychic_dof after the lighting pass and the fog, in front of --aa);
 --dof-focus (the distance in focus, default 15), --dof-aperture (the blur radius in pixels of a point at infinity, default 6, at most
-64) and --dof-radius (the gather radius in pixels, default 8, at most 8) set its parameters.  The PPM is the last stage's output."""
+64) and --dof-radius (the gather radius in pixels, default 8, at most 8) set its parameters.  The PPM is the last stage's output.
+--decals: deferred decals between the G-buffer pass and the lighting pass (Crychic.set_decals / apply_decals: crychic_apply_decals): a
+glossy puddle with a dent normal map on the floor and a painted ring on the face of a box."""
 import argparse
 import ctypes as C
 
@@ -65,6 +67,7 @@ def main():
     ap.add_argument("--dof-aperture", type=float, default=None, metavar="X", help="circle-of-confusion radius in pixels of a point at infinity, "
                                                                                   "0 .. 64 (default 6; needs --dof)")
     ap.add_argument("--dof-radius", type=int, default=None, metavar="N", help="gather radius in pixels, 1 .. 8 (default 8; needs --dof)")
+    ap.add_argument("--decals", action="store_true", help="a puddle on the floor and a mark on a box face, blended into the G-buffer")
     a = ap.parse_args()
     if (a.dof_focus is not None or a.dof_aperture is not None or a.dof_radius is not None) and not a.dof:
         ap.error("--dof-focus, --dof-aperture and --dof-radius need --dof")
@@ -124,6 +127,14 @@ def main():
         sgeo.DrawSceneToShadowMap(cb, app.mShadowMap.mShadowMap[k])
     geo.DrawNormalsAndDepth(app.mMainPassCB, app.mSsao.mNormalMap, app.mDepthStencilBuffer)
     geo.DrawGBuffer(app.mMainPassCB, app.mDeferred.mGBuffer, app.mDepthStencilBuffer)
+    if a.decals:          # once, on the fresh G-buffer: a second application would stack
+        from ._lib import DECAL_ALBEDO, DECAL_METALNESS, DECAL_NORMAL, DECAL_ROUGHNESS
+        puddle = g.decal_from_box(g.decal_box_world((2.5, 0.0, -7.5), (1.5, 0.25, 1.5)), (64, 64), 0.5, 0.0, texture=0, normalTexture=1,
+                                  flags=DECAL_ALBEDO | DECAL_ROUGHNESS | DECAL_NORMAL, roughness=0.03, opacity=0.85)
+        mark = g.decal_from_box(g.decal_box_world((0.0, 0.8, -10.8), (0.6, 0.6, 0.3), down=False), (64, 64), 0.5, 0.0, texture=2,
+                                flags=DECAL_ALBEDO | DECAL_METALNESS, metalness=0.0, tint=(0.9, 0.1, 0.1))
+        app.set_decals([puddle, mark], [g.decal_texture("disc", 64), g.decal_texture("dent", 64), g.decal_texture("ring", 64)])
+        app.apply_decals()
     app.blurCount, app.numDirLights, app.flags = 3, 1, LIGHT_SKY        # the reference's settings (CRYCHIC.cpp:221, Common.hlsl:6-8)
     if a.capture_env:
         pos = [float(v) for v in a.capture_env.split(",")]

@@ -287,3 +287,66 @@ def reference_textures(texture_dir):
     import os
     names = ["bricks2.dds", "bricks2_nmap.dds", "tile.dds", "tile_nmap.dds", "white1x1.dds", "default_nmap.dds"]
     return [load_dds(os.path.join(texture_dir, n)) for n in names]
+
+
+# ---- deferred decals (extension; crychic_apply_decals) --------------------------------------------------------------------------
+
+def decal_from_box(world, tex_size, cos_fade_start=1.0, cos_fade_end=1.0, **fields):
+    """A Decal for the box that is the image of the unit cube [-1/2, 1/2]^3 under `world` (16 floats in the layout of
+    crychic_instance_data.World, or a 4 x 4 array in the same transposed storage), by crychic_decal_from_box.  The decal looks down
+    its local -z and lands on surfaces whose normals point along its +z.  tex_size: (width, height) of its texture's level 0; the
+    angle fade runs from 1 at cos_fade_start down to 0 at cos_fade_end, (1, 1) = none.  `fields` (tint, opacity, roughness,
+    metalness, texture, normalTexture, flags, ...) are set on the result."""
+    from ._lib import Decal
+    w = (C.c_float * 16)(*[float(x) for x in np.asarray(world, np.float32).reshape(16)])
+    d = Decal()
+    check(lib.crychic_decal_from_box(w, int(tex_size[0]), int(tex_size[1]), float(cos_fade_start), float(cos_fade_end), C.byref(d)))
+    for k, v in fields.items():
+        if isinstance(getattr(d, k), (int, float)):
+            setattr(d, k, v)
+        else:
+            getattr(d, k)[:] = [float(x) for x in v]
+    return d
+
+
+def decal_box_world(center, half, down=True, yaw=0.0):
+    """The `world` of decal_from_box for an axis-aligned box of half extents `half` (world x, y, z) about `center`, turned by `yaw`
+    about +y.  down=True: the decal looks down (its +z is world +y: floors); down=False: it looks along world +z (its +z is world
+    -z: faces turned towards -z)."""
+    c, s = np.cos(yaw), np.sin(yaw)
+    if down:
+        R, ext = np.array([[c, s, 0], [0, 0, 1], [-s, c, 0]], np.float64), (half[0], half[2], half[1])
+    else:
+        R, ext = np.array([[-c, 0, -s], [0, 1, 0], [s, 0, -c]], np.float64), half
+    M = np.eye(4)
+    M[:3, :3] = R * (2.0 * np.asarray(ext, np.float64))[None, :]
+    M[:3, 3] = center
+    return M.astype(np.float32).reshape(16)
+
+
+def decal_texture(kind, size=64):
+    """A procedural RGBA8 decal with a 2 x 2-box mip chain (box_mips): (flat uint8 chain, width, height, mipLevels), what
+    Crychic.set_decals takes.  kind: "disc" -- a dark soft disc, alpha 1 in the middle falling to 0 at the rim (a puddle, a scorch
+    mark); "ring" -- a white ring (a painted marking); "dent" -- a normal map of a round dent, alpha as the disc's."""
+    y, x = np.mgrid[0:size, 0:size]
+    u, v = (x + 0.5) / size * 2.0 - 1.0, (y + 0.5) / size * 2.0 - 1.0
+    r = np.sqrt(u * u + v * v)
+    soft = np.clip((1.0 - r) * 4.0, 0.0, 1.0)
+    img = np.zeros((size, size, 4), np.float64)
+    if kind == "disc":
+        img[..., :3] = 0.08
+        img[..., 3] = soft
+    elif kind == "ring":
+        img[..., :3] = 1.0
+        img[..., 3] = np.clip(1.0 - np.abs(r - 0.7) * 8.0, 0.0, 1.0)
+    elif kind == "dent":
+        slope = np.where(r < 1.0, np.sin(np.pi * np.minimum(r, 1.0)), 0.0) * 0.8       # steepest half way out, flat in the middle and at the rim
+        rr = np.maximum(r, 1e-6)
+        n = np.stack([slope * u / rr, -slope * v / rr, np.ones_like(r)], -1)
+        n /= np.linalg.norm(n, axis=-1, keepdims=True)
+        img[..., :3] = n * 0.5 + 0.5
+        img[..., 3] = soft
+    else:
+        raise ValueError("decal_texture kind %r: 'disc', 'ring' or 'dent'" % (kind,))
+    levels = box_mips((img * 255.0 + 0.5).astype(np.uint8))
+    return np.concatenate([lv.reshape(-1) for lv in levels]), size, size, len(levels)

@@ -228,6 +228,8 @@ class Crychic:
         self._fog = None             # fog, extension: None | True | FogParams -- Draw() of a whole frame runs crychic_fog in place on mBackBuffer
         self._depthOfField = None    # depthOfField, extension: None | True | DofParams -- Draw() of a whole frame runs crychic_dof into mBackBufferDoF
         self.mBackBufferDoF = None   # the frame behind the depth-of-field pass, allocated by the first depth_of_field() that needs it
+        self.mDecals, self.mDecalCount = None, 0                             # set_decals, extension: the device array of Decal structs
+        self._decalTextures, self._decalTextureCount, self._decalKeep = None, 0, []     # the host texture table and the chains it points into
 
     def _post_switch(name):          # noqa: N805 -- a class-body helper: the property of one switch
         def get(self):
@@ -433,6 +435,42 @@ class Crychic:
                               _ptr(src), _ptr(out), W, H, int(row0), int(H - row0 if rows is None else rows),
                               None if params is None else C.byref(params), _stream(self.ctx.device)))
         return out
+
+    def set_decals(self, decals, textures=()):
+        """The decals of apply_decals (extension): a sequence of at most MAX_DECALS Decal structs (geometry.decal_from_box), uploaded
+        here, and the textures their indices address: at most DECAL_MAX_TEXTURES entries, each a (tensor, width, height, mipLevels)
+        tuple as geometry.decal_texture returns -- a flat uint8 RGBA8 chain, uploaded here if it is not on the device -- or a Texture
+        whose pointer the caller keeps alive.  An empty sequence clears them."""
+        decals = list(decals)
+        if len(decals) > _lib.MAX_DECALS or len(textures) > _lib.DECAL_MAX_TEXTURES:
+            raise CrychicError(-1, "set_decals takes at most %d decals and %d textures" % (_lib.MAX_DECALS, _lib.DECAL_MAX_TEXTURES))
+        self._decalKeep, table = [], (_lib.Texture * max(len(textures), 1))()
+        for k, t in enumerate(textures):
+            if isinstance(t, _lib.Texture):
+                table[k] = t
+                continue
+            chain, w, h, levels = t
+            chain = torch.as_tensor(chain).contiguous().view(torch.uint8).to(self.ctx.device)
+            self._decalKeep.append(chain)
+            table[k] = _lib.Texture(chain.data_ptr(), int(w), int(h), int(levels))
+        self._decalTextures, self._decalTextureCount = table, len(textures)
+        self.mDecalCount = len(decals)
+        self.mDecals = None
+        if decals:
+            host = (_lib.Decal * len(decals))(*decals)
+            self.mDecals = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(self.ctx.device)
+
+    def apply_decals(self, row0=0, rows=None):
+        """crychic_apply_decals on the context's stream: the decals of set_decals blended into rows [row0, row0 + rows) of
+        mDeferred.mGBuffer, in the planes' formats, with this frame's depth plane and pass constants.  Explicit only: Draw() runs no
+        producer passes here, so it cannot know whether the planes are fresh, and a second application stacks on the first."""
+        n = self.mDecalCount
+        g = self.mDeferred.mGBuffer
+        H, W = self.mClientHeight, self.mClientWidth
+        check(lib.crychic_apply_decals(self.ctx.handle, C.byref(self.mMainPassCB), self.mDepthStencilBuffer.data_ptr(), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
+                                       gbuffer_flags(g), self.mDecals.data_ptr() if n else None, n, self._decalTextures if n else None,
+                                       self._decalTextureCount if n else 0, W, H, int(row0), int(H - row0 if rows is None else rows),
+                                       _stream(self.ctx.device)))
 
     def antialias(self, src=None, out=None, row0=0, rows=None, params=None):
         """crychic_antialias on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferAA, allocated on first

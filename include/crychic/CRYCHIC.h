@@ -219,6 +219,7 @@ public:
             DrawSceneToShadowMap();                                                                 // :208
             if (mFuseCameraPasses) DrawNormalsDepthAndGBuffer();                                    // :214 + :236 on one rasterisation
             else { DrawNormalsAndDepth(); DrawGBuffer(); }
+            if (mDecalCount) ApplyDecals();                                                         // SetDecals: into the fresh G-buffer
         }
         // L: whose cube map, local lights and local-light shadow maps this frame reads -- a capture's probe reads its owner's
         const CRYCHIC& L = mOwner ? *mOwner : *this;
@@ -363,6 +364,33 @@ public:
     }
     bool DepthOfField() const { return mDepthOfField; }
     ID3D12Resource* DepthOfFieldBackBuffer() { return mBackBufferDoF.get(); }
+
+    // ---- deferred decals (extension) ------------------------------------------------------------------------------------------------
+    // Oriented boxes that blend textures into the G-buffer between the producer passes and the lighting pass (include/crychic_hip.h
+    // crychic_apply_decals; crychic_decal_from_box fills a decal from a matrix).  SetDecals uploads the n <= CRYCHIC_MAX_DECALS decals to
+    // a device buffer this object owns and copies the table of nTex <= CRYCHIC_DECAL_MAX_TEXTURES textures (device pointers the caller
+    // keeps alive).  While decals are set and mRunProducerPasses is on, Draw issues the pass behind the camera producer passes, for the
+    // rows it draws: it is valid with SetStrip / JoinNode, each GPU decaling its own strip.  With mRunProducerPasses off Draw leaves the
+    // caller's planes alone (a second application would stack).  The probe of CaptureEnvironment is an object of its own and has no
+    // decals: captures do not show them.  The SSAO pass's view-normal map is not touched.  With none set (the default) Draw issues
+    // exactly the calls it issues without this extension.  Waits for the frames in flight first, which may still read the buffer.
+    void SetDecals(const crychic_decal* decals, uint32_t n, const crychic_texture* textures, uint32_t nTex)
+    {
+        if (n > CRYCHIC_MAX_DECALS || nTex > CRYCHIC_DECAL_MAX_TEXTURES || (n && !decals) || (nTex && !textures))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetDecals (at most 64 decals and 16 textures, non-null when non-empty)", __FILE__,
+                                   __LINE__);
+        mCommandList->Flush();
+        mDecals.reset();
+        mDecalCount = 0;
+        mDecalTextures.assign(textures, textures + nTex);
+        if (n == 0) return;
+        mDecals = std::make_unique<ID3D12Resource>((size_t)n * sizeof(crychic_decal), ID3D12Resource::DEFAULT_HEAP);
+        mDecals->Upload(decals, (size_t)n * sizeof(crychic_decal), mCommandList->Stream());
+        mDecalCount = n;
+        mCommandList->Flush();                  // the caller's array may go once this returns
+    }
+    void ClearDecals() { SetDecals(nullptr, 0, nullptr, 0); }
+    uint32_t DecalCount() const { return mDecalCount; }
 
     // ---- local lights (extension: the reference's point and spot branches, PBR.hlsl:109-147, are dead code) -------------------
     // Uploads both lists to device buffers this object owns (at most 1024 each); Draw lights them after the directional lights,
@@ -990,6 +1018,16 @@ private:
                                                           mClientHeight, mStripRow0, mWholeFrame ? mClientHeight : mStripRows, ws, bytes,
                                                           mCommandList->Stream()));
     }
+    void ApplyDecals()  // the decals of SetDecals into this GPU's rows of the G-buffer the camera pass has just written
+    {
+        const PassConstants& cb = mCurrFrameResource->PassCB->Element(0);
+        CrychicThrowIfFailed(crychic_apply_decals(md3dDevice->Ctx(), reinterpret_cast<const crychic_pass_constants*>(&cb),
+                                                  static_cast<const uint32_t*>(mDepthStencilBuffer->Data()), mDeferred->Resource(0)->Data(),
+                                                  mDeferred->Resource(1)->Data(), mDeferred->Resource(2)->Data(), mDeferred->FormatFlags(),
+                                                  static_cast<const crychic_decal*>(mDecals->Data()), mDecalCount,
+                                                  mDecalTextures.empty() ? nullptr : mDecalTextures.data(), (uint32_t)mDecalTextures.size(), mClientWidth,
+                                                  mClientHeight, mStripRow0, mWholeFrame ? mClientHeight : mStripRows, mCommandList->Stream()));
+    }
     void UpdateCascadeShadowTransform(const GameTimer&)  // CRYCHIC.cpp:634-815
     {
         const float ld[3] = { mBaseLightDirections[0].x, mBaseLightDirections[0].y, mBaseLightDirections[0].z };  // :726
@@ -1061,6 +1099,9 @@ private:
     bool mWholeFrame = true;
     bool mFog = false;                        // SetFog
     crychic_fog_params mFogParams = {};
+    std::unique_ptr<ID3D12Resource> mDecals;  // SetDecals: the device array
+    uint32_t mDecalCount = 0;
+    std::vector<crychic_texture> mDecalTextures;
     bool mDepthOfField = false;               // SetDepthOfField
     crychic_dof_params mDofParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferDoF;  // the frame behind the depth-of-field pass, while mDepthOfField

@@ -985,6 +985,106 @@ int crychic_dof(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32
                 uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
                 const crychic_dof_params* params /* NULL = defaults */, void* stream);
 
+/* ---- deferred decals (extension) ---------------------------------------------------------------------------
+ * One pass over the G-buffer planes, a separate call between the producer passes and the lighting pass: oriented boxes project
+ * RGBA8 textures onto whatever surface lies inside them and blend albedo, roughness, metalness and the normal of the planes in
+ * place.  A build definition: nothing of it is the reference's.  The device, a host build and the checker (tests/decal_ref) agree
+ * bit for bit.  The SSAO pass's own view-normal map is NOT touched: ambient occlusion sees the surface without the decals' normals.
+ *
+ * Float operations are IEEE binary32, each rounded once, in the order written; fma is fused only where written.  Primitives:
+ *   mulcol1 as under crychic_fog;  dot3(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x b.x));  lerpf(a, b, t) = fma(t, b - a, a);
+ *   saturate(x) = 0 for x <= 0 or NaN, 1 for x >= 1, else x;  clampf(x, lo, hi) = fminf(fmaxf(x, lo), hi), so a NaN gives lo;
+ *   clampi the same on integers;
+ *   normalize3(v) = v.c * inv for each c with inv = 1 / sqrtf(L), L = dot3(v, v) clamped to [2^-100, 2^100] (a NaN gives 2^-100),
+ *   square root and quotient correctly rounded: the zero vector stays zero;
+ *   unorm8_to_float(b) = (float)b / 255 (IEEE);  half_to_float exact;  float_to_half round to nearest even;
+ *   det_log2(x): -inf for +-0 and positive subnormals, NaN for negative x and NaN, else with bits(x) - 0x3F3504F3 = ue:
+ *     ef = (float)((int32_t)ue >> 23), m = float of bits (ue & 0x7FFFFF) + 0x3F3504F3, s = (m - 1) * (1 / (m + 1)), s2 = s s,
+ *     p = fma(fma(fma(0.43174004554748535f, s2, 0.5767142176628113f), s2, 0.9617988467216492f), s2, 2.885390043258667f),
+ *     result fma(s, p, ef);
+ *   bilinear_setup(u, v, w, h) for finite u, v: tx = fma(u, (float)w, -0.5f), i0 = (int)floorf(tx), fx = tx - floorf(tx); ty, j0, fy
+ *     likewise with v and h;  bilerp(t00, t10, t01, t11, fx, fy) = lerpf(lerpf(t00, t10, fx), lerpf(t01, t11, fx), fy).
+ *
+ * A decal is an oriented box: the image of the unit cube [-1/2, 1/2]^3 under an affine map.  It looks down its local -z and lands
+ * on surfaces whose normals point towards normalW; the texture's u runs along local +x, v against local +y.  The array is DEVICE
+ * memory the caller uploads (as the local lights are), at most CRYCHIC_MAX_DECALS entries.
+ *
+ * Host side, once per call:  pix = 2.0f / (Proj[5] * (float)H) with H the frame height;  Vz = View + 8 (four floats).
+ * Per pixel of the call's rows:
+ *  0. Covered iff (depth & 0xFFFFFF) < 0xFFFFFF; otherwise nothing further is read and nothing is written.  G0, G1, G2 are loaded in
+ *     their formats (half texels widened exactly).  P = G0.xyz;  n0 = normalize3(G2.xyz);  running values alb = G1.xyz,
+ *     rough = G1.w, metal = G0.w, nrm = n0;  s = mulcol1(P.x, P.y, P.z, Vz) * pix  (the world-space size of a pixel at P's view depth).
+ * Then for d = 0 .. nDecals - 1 in ASCENDING order (a later decal lies over an earlier one):
+ *  1. texture >= nTextures: the decal changes nothing.
+ *  2. Bounds: P.c >= boundsMin[c] && P.c <= boundsMax[c] for c = 0 .. 2 (false for a NaN on either side); otherwise the decal changes
+ *     nothing.  The bounds are part of the definition, not a hint: a caller that sets them narrower than the box cuts the decal.
+ *  3. q[c] = mulcol1(P.x, P.y, P.z, invWorld + 4c), c = 0 .. 2.  Inside iff fabsf(q[c]) <= 0.5f for all c; otherwise nothing.
+ *  4. fade = saturate(fma(dot3(n0, normalW), fadeScale, fadeBias)).  Always n0, never the running normal.
+ *  5. u = q[0] + 0.5f;  v = 0.5f - q[1].
+ *  6. t = sample(textures[texture]), where sample(T) with L = max(mipLevels, 1) levels in the layout of crychic_texture is
+ *       L == 1: fetch(0);  otherwise  lod = clampf(det_log2(s * texelsPerUnit), 0.0f, (float)(L - 1))  (NaN and -inf give 0),
+ *       l0f = floorf(lod), fl = lod - l0f, l0 = (uint32_t)l0f, l1 = min(l0 + 1, L - 1), per channel lerpf(fetch(l0), fetch(l1), fl);
+ *     fetch(k) with level k's own w, h:  b = bilinear_setup(u, v, w, h);  CLAMP addressing x0 = clampi(b.i0, 0, w - 1),
+ *       x1 = clampi(b.i0 + 1, 0, w - 1), rows likewise;  the four texels' channels through unorm8_to_float, then bilerp.
+ *  7. a = (t.w * opacity) * fade.  If !(a > 0.0f) the decal changes nothing here -- a rule, not a shortcut: lerpf(inf, y, 0) is NaN.
+ *  8. ALBEDO: alb.c = lerpf(alb.c, t.c * tint[c], a);  ROUGHNESS: rough = lerpf(rough, roughness, a);
+ *     METALNESS: metal = lerpf(metal, metalness, a).
+ *  9. NORMAL with normalTexture < nTextures:  m = sample(textures[normalTexture]) with the same u, v, s and texelsPerUnit;
+ *     e.c = fma(m.c, 2.0f, -1.0f);  wv.c = fma(e.z, normalW[c], fma(e.y, bitangentW[c], e.x * tangentW[c]));
+ *     nrm.c = lerpf(nrm.c, wv.c, a).  With no valid normal texture the flag does nothing.
+ * Stores: a component of a plane is stored iff at least one decal passed step 7 at this pixel carrying its flag: ALBEDO stores
+ * G1.xyz, ROUGHNESS G1.w, METALNESS G0.w, NORMAL with a valid map G2.xyz.  The stored value is in the plane's format: the float, or
+ * float_to_half of it.  Every other component and every other byte keeps its bits: uncovered pixels, pixels inside no decal, rows
+ * outside the call, G0.xyz, G2.w and the depth plane.
+ * Known answers: a 1 x 1 opaque texel with opacity 1 and no fade puts fma(1, tint - x, x) into the albedo x inside the box; two
+ * overlapping decals give different planes in either order; normalW pointing away from the surface (fade 0) changes nothing. */
+#define CRYCHIC_MAX_DECALS 64
+#define CRYCHIC_DECAL_MAX_TEXTURES 16
+#define CRYCHIC_DECAL_ALBEDO 1u
+#define CRYCHIC_DECAL_ROUGHNESS 2u
+#define CRYCHIC_DECAL_METALNESS 4u
+#define CRYCHIC_DECAL_NORMAL 8u
+#define CRYCHIC_DECAL_NO_TEXTURE 0xFFFFFFFFu
+typedef struct crychic_decal {
+    float invWorld[12];                             /* world -> unit cube: q[c] = mulcol1(P.x, P.y, P.z, invWorld + 4c) */
+    float boundsMin[3], boundsMax[3];               /* a world-space box around the decal (step 2) */
+    float tangentW[3], bitangentW[3], normalW[3];   /* unit world directions of the cube's +x, +y, +z */
+    float tint[3]; float opacity;
+    float roughness, metalness;
+    float fadeScale, fadeBias;                      /* angle fade; (0, 1) = none */
+    float texelsPerUnit;                            /* max(texW / |edge x|, texH / |edge y|) */
+    uint32_t texture, normalTexture, flags;         /* indices into the call's texture table; normalTexture 0xFFFFFFFF = none */
+    uint32_t reserved;                              /* 0 */
+} crychic_decal;   /* 160 bytes */
+/* Fills *out from the unit cube -> world matrix `world` (the layout of crychic_instance_data.World: world.c = mulcol1(x, y, z,
+ * world + 4c), world[12 .. 15] = 0 0 0 1), the decal texture's level-0 size and the cosines between which the angle fade runs
+ * (fade 1 at dot(n0, normalW) >= cosFadeStart, 0 at <= cosFadeEnd).  invWorld: the inverse computed in double, rounded once; the
+ * three unit axes; texelsPerUnit; fadeScale = 1 / (start - end), fadeBias = -end * fadeScale, and start == end, which only the pair
+ * (1, 1) may be, means "no fade" and stores (0, 1); boundsMin / boundsMax: the box of the eight corners computed in double, widened per
+ * side by 2^-10 * (that axis' extent + the largest |corner coordinate|) and rounded outwards.  It leaves tint = 1, opacity = 1,
+ * roughness = metalness = 0, flags = CRYCHIC_DECAL_ALBEDO, texture = 0, normalTexture = none, reserved = 0.  Pure host code.
+ * CRYCHIC_E_INVALID_ARG: a NULL argument, a non-finite or non-affine matrix, a singular one (an axis shorter than 2^-60, or a zero
+ * determinant), a texture side of 0, a cosine outside [-1, 1], start < end, or start == end other than (1, 1). */
+int crychic_decal_from_box(const float world[16], uint32_t texW, uint32_t texH, float cosFadeStart, float cosFadeEnd, crychic_decal* out);
+/* Modifies rows [row0, row0 + rows) of the three planes in place and no other byte; reads the same rows of depth_dev (W x H, D24 in
+ * the low 24 bits), the decals, the textures' texels, and View[8 .. 11] and Proj[5] of cb (a host pointer, read during the call).
+ * formatFlags: the CRYCHIC_GBUFFER_G*_F16 bits, as the producers and the lighting pass take them.  textures: a HOST array of at most
+ * CRYCHIC_DECAL_MAX_TEXTURES entries (device pointers inside), read during the call: it travels in the kernel's arguments, with no copy
+ * and no workspace.  A pixel reads and writes only its own texels, so stitched row ranges equal the whole-frame call byte for byte,
+ * for any row0 and rows, and the pass runs per strip under the multi-GPU path.  A second call blends the decals again over the first
+ * call's result.  One launch on `stream`: no allocation, no synchronisation, no host read-back; capturable into a graph.
+ * nDecals == 0 or rows == 0 launches nothing.
+ * CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and before anything is enqueued: a NULL plane or cb;
+ * decals_dev NULL with nDecals > 0; textures NULL with nTextures > 0; a misaligned plane (16 bytes for a float4 plane, 8 for a half4
+ * one, 4 for depth and the decals); W or H of 0; a row range outside the frame; nDecals > CRYCHIC_MAX_DECALS; nTextures >
+ * CRYCHIC_DECAL_MAX_TEXTURES; a texture with a NULL pointer, a zero side or more levels than floor(log2(max(w, h))) + 1; a bit outside
+ * the three format bits; a non-finite View[8 .. 11] or Proj[5], or Proj[5] == 0.  More than 2^28 pixels, or a texture of more than
+ * 2^28 texels: CRYCHIC_E_UNSUPPORTED. */
+int crychic_apply_decals(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32_t* depth_dev, void* g0_dev, void* g1_dev,
+                         void* g2_dev, uint32_t formatFlags, const crychic_decal* decals_dev, uint32_t nDecals,
+                         const crychic_texture* textures, uint32_t nTextures, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                         void* stream);
+
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
  * of 2 rows (half-res alignment); the last rank takes the remainder. */
