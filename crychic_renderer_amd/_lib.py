@@ -27,6 +27,7 @@ COMM_ID_BYTES = 128
 AA_MAX_SEARCH = 16            # CRYCHIC_AA_MAX_SEARCH: the longest end search of crychic_antialias, in pixels
 FOG_MAX_STEPS = 64            # CRYCHIC_FOG_MAX_STEPS: the most samples crychic_fog takes along a view ray
 DOF_MAX_RADIUS = 8            # CRYCHIC_DOF_MAX_RADIUS: the largest gather radius of crychic_dof, in pixels
+BLOOM_MAX_LEVELS = 8          # CRYCHIC_BLOOM_MAX_LEVELS: the most levels of crychic_bloom's pyramid
 
 
 class Light(C.Structure):
@@ -157,6 +158,22 @@ class Decal(C.Structure):
 assert C.sizeof(Decal) == 160
 
 
+class BloomParams(C.Structure):
+    """crychic_bloom_params: the knobs of crychic_bloom (extension); BloomParams.default() = crychic_bloom_default_params, any field
+    replaced by its keyword."""
+    _fields_ = [("threshold", C.c_uint32), ("knee", C.c_uint32), ("scatter", C.c_uint32), ("intensity", C.c_uint32), ("levels", C.c_uint32),
+                ("reserved", C.c_uint32 * 3)]
+
+    @classmethod
+    def default(cls, threshold=None, knee=None, scatter=None, intensity=None, levels=None):
+        p = cls()
+        check(lib.crychic_bloom_default_params(C.byref(p)))
+        for name, v in (("threshold", threshold), ("knee", knee), ("scatter", scatter), ("intensity", intensity), ("levels", levels)):
+            if v is not None:
+                setattr(p, name, int(v))
+        return p
+
+
 class PassTimes(C.Structure):
     _fields_ = [("ssao_ms", C.c_float), ("blur_ms", C.c_float), ("light_ms", C.c_float), ("total_ms", C.c_float)]
 
@@ -257,6 +274,12 @@ PROTOTYPES = {
     "crychic_dof": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(DofParams), _vp]),
     "crychic_decal_from_box": (_i, [_P(_f), _u32, _u32, _f, _f, _P(Decal)]),
     "crychic_apply_decals": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _u32, _vp, _u32, _P(Texture), _u32, _u32, _u32, _u32, _u32, _vp]),
+    "crychic_bloom_default_params": (_i, [_P(BloomParams)]),
+    "crychic_bloom_workspace_bytes": (_sz, [_u32, _u32, _u32]),
+    "crychic_bloom_level_offset": (_sz, [_u32, _u32, _u32, _u32]),
+    "crychic_bloom_pyramid": (_i, [_vp, _vp, _u32, _u32, _P(BloomParams), _vp, _sz, _vp]),
+    "crychic_bloom_composite": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(BloomParams), _vp, _sz, _vp]),
+    "crychic_bloom": (_i, [_vp, _vp, _vp, _u32, _u32, _P(BloomParams), _vp, _sz, _vp]),
     "crychic_save_ppm": (_i, [C.c_char_p, _vp, _u32, _u32]),
     "crychic_raster_workspace_bytes": (_sz, [C.c_uint64, _u32, _u32]),
     "crychic_raster_status": (_i, [_vp, _vp, _P(_u32)]),

@@ -22,6 +22,7 @@
 #include "post_aa_core.hpp"
 #include "fog_core.hpp"
 #include "dof_core.hpp"
+#include "bloom_core.hpp"
 #include "decal_core.hpp"
 #include "internal.hpp"
 
@@ -1044,6 +1045,91 @@ int crychic_apply_decals(crychic_ctx* ctx, const crychic_pass_constants* cb, con
     if (nDecals == 0 || rows == 0) return 0;
     CRY_HIP(cry::launch_decals(cb->View, cb->Proj, depth_dev, g0_dev, g1_dev, g2_dev, formatFlags, decals_dev, nDecals, textures, nTextures, W, H, row0,
                                rows, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(CRYCHIC_BLOOM_MAX_LEVELS == cry::kBloomMaxLevels && sizeof(crychic_bloom_params) == 32 && sizeof(crychic_bloom_params) == sizeof(cry::BloomParams),
+              "bloom_core.hpp mirrors the ABI");
+
+int crychic_bloom_default_params(crychic_bloom_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    *out = crychic_bloom_params{};
+    out->threshold = 192u; out->knee = 32u; out->scatter = 179u; out->intensity = 128u; out->levels = 6u;
+    return 0;
+}
+
+size_t crychic_bloom_workspace_bytes(uint32_t W, uint32_t H, uint32_t levels) { return cry::bloom_plan(W, H, levels).bytes; }
+size_t crychic_bloom_level_offset(uint32_t W, uint32_t H, uint32_t levels, uint32_t k)
+{
+    const cry::BloomPlan plan = cry::bloom_plan(W, H, levels);
+    return k >= 1u && k <= plan.nEff ? plan.off[k] : 0u;
+}
+
+namespace {
+
+// What the three bloom entries check alike, before the context is looked at: `out` is NULL for the pyramid, which has no row range.
+// Fills `q` with the parameters in force.
+int bloom_check(const uint8_t* in, const uint8_t* out, bool hasOut, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const crychic_bloom_params* params,
+                const void* workspace, size_t workspaceBytes, cry::BloomParams& q)
+{
+    if (!in || (hasOut && !out) || !workspace) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    const uintptr_t s = reinterpret_cast<uintptr_t>(in), d = reinterpret_cast<uintptr_t>(out), w = reinterpret_cast<uintptr_t>(workspace);
+    if ((s | d) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "bloom planes are not 4-byte aligned");
+    if (w & 15u) return fail(CRYCHIC_E_INVALID_ARG, "the bloom workspace is not 16-byte aligned");
+    if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
+    if (int rc = check_extent("frame", W, H, false, 0u)) return rc;                   // one-dimensional grids, at most 2^18 workgroups
+    if (int rc = check_rows(kFrameRows, row0, rows, H)) return rc;
+    crychic_bloom_params p;
+    crychic_bloom_default_params(&p);
+    if (params) p = *params;
+    if (p.threshold > 255u) return fail(CRYCHIC_E_INVALID_ARG, "bloom threshold %u outside 0 .. 255", p.threshold);
+    if (p.knee == 0u || p.knee > 255u) return fail(CRYCHIC_E_INVALID_ARG, "bloom knee %u outside 1 .. 255", p.knee);
+    if (p.scatter > 256u) return fail(CRYCHIC_E_INVALID_ARG, "bloom scatter %u outside 0 .. 256", p.scatter);
+    if (p.intensity > 1024u) return fail(CRYCHIC_E_INVALID_ARG, "bloom intensity %u outside 0 .. 1024", p.intensity);
+    if (p.levels == 0u || p.levels > CRYCHIC_BLOOM_MAX_LEVELS) return fail(CRYCHIC_E_INVALID_ARG, "bloom levels %u outside 1 .. %d", p.levels, CRYCHIC_BLOOM_MAX_LEVELS);
+    if (p.reserved[0] | p.reserved[1] | p.reserved[2]) return fail(CRYCHIC_E_INVALID_ARG, "bloom reserved words must be 0");
+    const size_t need = crychic_bloom_workspace_bytes(W, H, p.levels);
+    if (workspaceBytes < need) return fail(CRYCHIC_E_INVALID_ARG, "the bloom workspace has %zu bytes, %ux%u with %u levels needs %zu", workspaceBytes, W, H, p.levels, need);
+    const size_t bytes = (size_t)W * H * 4u;
+    if (ranges_overlap(w, need, s, bytes) || (hasOut && ranges_overlap(w, need, d, bytes)))
+        return fail(CRYCHIC_E_INVALID_ARG, "the bloom workspace overlaps a plane");
+    if (hasOut && s != d && ranges_overlap(s, bytes, d, bytes))
+        return fail(CRYCHIC_E_INVALID_ARG, "the bloom input and output planes overlap (in place takes the same address)");
+    std::memcpy(&q, &p, sizeof q);
+    return 0;
+}
+
+}  // namespace
+
+int crychic_bloom_pyramid(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint32_t W, uint32_t H, const crychic_bloom_params* params, void* workspace_dev,
+                          size_t workspace_bytes, void* stream)
+{
+    cry::BloomParams q;
+    if (int rc = bloom_check(in_rgba8_dev, nullptr, false, W, H, 0u, 0u, params, workspace_dev, workspace_bytes, q)) return rc;
+    if (int rc = bind(ctx)) return rc;
+    CRY_HIP(cry::launch_bloom_pyramid(in_rgba8_dev, W, H, q, workspace_dev, (hipStream_t)stream));
+    return 0;
+}
+
+int crychic_bloom_composite(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                            const crychic_bloom_params* params, const void* workspace_dev, size_t workspace_bytes, void* stream)
+{
+    cry::BloomParams q;
+    if (int rc = bloom_check(in_rgba8_dev, out_rgba8_dev, true, W, H, row0, rows, params, workspace_dev, workspace_bytes, q)) return rc;
+    if (int rc = bind(ctx)) return rc;
+    CRY_HIP(cry::launch_bloom_composite(in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, q, workspace_dev, (hipStream_t)stream));
+    return 0;
+}
+
+int crychic_bloom(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, const crychic_bloom_params* params,
+                  void* workspace_dev, size_t workspace_bytes, void* stream)
+{
+    cry::BloomParams q;
+    if (int rc = bloom_check(in_rgba8_dev, out_rgba8_dev, true, W, H, 0u, H, params, workspace_dev, workspace_bytes, q)) return rc;
+    if (int rc = bind(ctx)) return rc;
+    CRY_HIP(cry::launch_bloom_pyramid(in_rgba8_dev, W, H, q, workspace_dev, (hipStream_t)stream));
+    CRY_HIP(cry::launch_bloom_composite(in_rgba8_dev, out_rgba8_dev, W, H, 0u, H, q, workspace_dev, (hipStream_t)stream));
     return 0;
 }
 

@@ -115,6 +115,15 @@ hipError_t launch_decals(const float* view, const float* proj, const uint32_t* d
                          const crychic_decal* decals, uint32_t nDecals, const crychic_texture* textures, uint32_t nTextures, uint32_t W, uint32_t H,
                          uint32_t row0, uint32_t rows, hipStream_t stream);
 
+// bloom.hip: launch_bloom_pyramid leaves U_k in level k = 1 .. n_eff of `workspace` from the W x H RGBA8 frame `in` (bloom_core.hpp):
+// n_eff downsample launches and n_eff - 1 unwind launches on `stream`, one behind the other.  launch_bloom_composite writes rows
+// [row0, row0 + rows) of `out` from `in` and level 1 of `workspace`: one launch, none for rows == 0; in == out is in place.  The
+// caller has checked the pointers, their alignment and overlap, the sizes, the rows, the workspace's size and `p`.
+struct BloomParams;
+hipError_t launch_bloom_pyramid(const uint8_t* in, uint32_t W, uint32_t H, const BloomParams& p, void* workspace, hipStream_t stream);
+hipError_t launch_bloom_composite(const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const BloomParams& p,
+                                  const void* workspace, hipStream_t stream);
+
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
 struct Texture;

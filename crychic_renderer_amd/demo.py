@@ -3,6 +3,7 @@
                                    [--probe-box X0,Y0,Z0,X1,Y1,Z1] [--aa]
                                    [--fog [--fog-density X] [--fog-steps N]]
                                    [--dof [--dof-focus X] [--dof-aperture X] [--dof-radius N]]
+                                   [--bloom [--bloom-threshold N] [--bloom-intensity N] [--bloom-levels N]]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
@@ -30,6 +31,9 @@ buffer, in front of --aa); --fog-density (default 0.02) and --fog-steps (default
 --dof: depth of field from the depth plane (Crychic.depthOfField: crychic_dof after the lighting pass and the fog, in front of --aa);
 --dof-focus (the distance in focus, default 15), --dof-aperture (the blur radius in pixels of a point at infinity, default 6, at most
 64) and --dof-radius (the gather radius in pixels, default 8, at most 8) set its parameters.  The PPM is the last stage's output.
+--bloom: what lies over a luma threshold is spread down and up a pyramid and added back (Crychic.bloom: crychic_bloom after the lighting
+pass, the fog and --dof, in front of --aa); --bloom-threshold (8-bit luma, default 192), --bloom-intensity (256 = 1.0, default 128, at
+most 1024) and --bloom-levels (default 6, at most 8) set its parameters.
 --decals: deferred decals between the G-buffer pass and the lighting pass (Crychic.set_decals / apply_decals: crychic_apply_decals): a
 glossy puddle with a dent normal map on the floor and a painted ring on the face of a box."""
 import argparse
@@ -68,7 +72,13 @@ def main():
                                                                                   "0 .. 64 (default 6; needs --dof)")
     ap.add_argument("--dof-radius", type=int, default=None, metavar="N", help="gather radius in pixels, 1 .. 8 (default 8; needs --dof)")
     ap.add_argument("--decals", action="store_true", help="a puddle on the floor and a mark on a box face, blended into the G-buffer")
+    ap.add_argument("--bloom", action="store_true", help="bloom, after the lighting pass, the fog and the depth of field")
+    ap.add_argument("--bloom-threshold", type=int, default=None, metavar="N", help="luma threshold, 0 .. 255 (default 192; needs --bloom)")
+    ap.add_argument("--bloom-intensity", type=int, default=None, metavar="N", help="strength, 256 = 1.0, 0 .. 1024 (default 128; needs --bloom)")
+    ap.add_argument("--bloom-levels", type=int, default=None, metavar="N", help="pyramid levels, 1 .. 8 (default 6; needs --bloom)")
     a = ap.parse_args()
+    if (a.bloom_threshold is not None or a.bloom_intensity is not None or a.bloom_levels is not None) and not a.bloom:
+        ap.error("--bloom-threshold, --bloom-intensity and --bloom-levels need --bloom")
     if (a.dof_focus is not None or a.dof_aperture is not None or a.dof_radius is not None) and not a.dof:
         ap.error("--dof-focus, --dof-aperture and --dof-radius need --dof")
     if (a.fog_density is not None or a.fog_steps is not None) and not a.fog:
@@ -90,7 +100,7 @@ def main():
     W, H = (int(v) for v in a.size.lower().split("x"))
     import torch
     from . import Context, Crychic, LIGHT_SKY, SceneGeometry, check, geometry as g, lib, scene
-    from ._lib import DofParams, FogParams, PassConstants
+    from ._lib import BloomParams, DofParams, FogParams, PassConstants
     ctx = Context(0)
     consts = scene.Constants(W, H, a.shadow_dim)
     tex = g.reference_textures(a.textures) if a.textures else g.procedural_textures(64)
@@ -150,13 +160,15 @@ def main():
         app.fog = FogParams.default(**knobs) if knobs else True
     if a.dof:
         app.depthOfField = DofParams.default(focus=a.dof_focus, aperture=a.dof_aperture, radius=a.dof_radius)
+    if a.bloom:
+        app.bloom = BloomParams.default(threshold=a.bloom_threshold, intensity=a.bloom_intensity, levels=a.bloom_levels)
     if a.aa:
         app.antiAliasing = True
     app.Draw()
     torch.cuda.synchronize()
-    img = np.ascontiguousarray((app.mBackBufferAA if a.aa else (app.mBackBufferDoF if a.dof else app.mBackBuffer)).cpu().numpy())
+    img = np.ascontiguousarray((app.mBackBufferAA if a.aa else (app.mBackBufferBloom if a.bloom else (app.mBackBufferDoF if a.dof else app.mBackBuffer))).cpu().numpy())
     check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, W, H))
-    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, (", fog" if a.fog else "") + (", depth of field" if a.dof else "") + (", anti-aliased" if a.aa else ""), ctx.device_name))
+    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, (", fog" if a.fog else "") + (", depth of field" if a.dof else "") + (", bloom" if a.bloom else "") + (", anti-aliased" if a.aa else ""), ctx.device_name))
 
 
 if __name__ == "__main__":

@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (AAParams, CrychicError, FogParams, DofParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, FogParams, DofParams, BloomParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -228,6 +228,9 @@ class Crychic:
         self._fog = None             # fog, extension: None | True | FogParams -- Draw() of a whole frame runs crychic_fog in place on mBackBuffer
         self._depthOfField = None    # depthOfField, extension: None | True | DofParams -- Draw() of a whole frame runs crychic_dof into mBackBufferDoF
         self.mBackBufferDoF = None   # the frame behind the depth-of-field pass, allocated by the first depth_of_field() that needs it
+        self._bloom = None           # bloom, extension: None | True | BloomParams -- Draw() of a whole frame runs crychic_bloom into mBackBufferBloom
+        self.mBackBufferBloom = None  # the frame behind the bloom pass, allocated by the first apply_bloom() that needs it
+        self.mBloomWorkspace = None  # the pass's pyramid: crychic_bloom_workspace_bytes of the frame at the most levels, with the first apply_bloom()
         self.mDecals, self.mDecalCount = None, 0                             # set_decals, extension: the device array of Decal structs
         self._decalTextures, self._decalTextureCount, self._decalKeep = None, 0, []     # the host texture table and the chains it points into
 
@@ -237,12 +240,13 @@ class Crychic:
 
         def put(self, value):
             setattr(self, name, value)
-            self._post = bool(self._fog or self._antiAliasing or self._depthOfField)
+            self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom)
         return property(get, put)
 
     antiAliasing = _post_switch("_antiAliasing")
     fog = _post_switch("_fog")
     depthOfField = _post_switch("_depthOfField")
+    bloom = _post_switch("_bloom")
     del _post_switch
 
     def set_gbuffer_formats(self, formats):
@@ -308,8 +312,13 @@ class Crychic:
         fog = True or a FogParams (extension): a whole frame, then crychic_fog in place on mBackBuffer (in front of the anti-aliasing
         if that is set too).  A strip or a shared draw then raises CrychicError.
         depthOfField = True or a DofParams (extension): a whole frame (fogged if fog is set), then crychic_dof from mBackBuffer into
-        mBackBufferDoF; the anti-aliasing, if set too, then reads mBackBufferDoF.  A strip or a shared draw then raises CrychicError."""
+        mBackBufferDoF; the anti-aliasing, if set too, then reads mBackBufferDoF.  A strip or a shared draw then raises CrychicError.
+        bloom = True or a BloomParams (extension): a whole frame (fogged, and through the depth of field, as set), then crychic_bloom
+        from that frame into mBackBufferBloom; the anti-aliasing, if set too, then reads mBackBufferBloom.  A strip or a shared draw
+        then raises CrychicError."""
         if self._post:
+            if self._bloom:
+                return self._draw_with_bloom(row0, rows, shared)
             if self._depthOfField:
                 return self._draw_with_depth_of_field(row0, rows, shared)
             if self._fog:
@@ -399,6 +408,41 @@ class Crychic:
         self.depth_of_field(params=dof if isinstance(dof, DofParams) else None)
         if aa:
             self.antialias(src=self.mBackBufferDoF, params=aa if isinstance(aa, AAParams) else None)
+
+    def _draw_with_bloom(self, row0, rows, shared):
+        """Draw() with bloom set: the frame as Draw() issues it without (fog and depth of field as they are set), the bloom pass from
+        that frame -- mBackBufferDoF behind the depth of field, else mBackBuffer -- into mBackBufferBloom, then the anti-aliasing of
+        mBackBufferBloom if that is set."""
+        self._whole_frame_only("bloom", row0, rows, shared)
+        bloom, aa, self.bloom, self.antiAliasing = self.bloom, self.antiAliasing, None, None
+        try:
+            self.Draw()
+        finally:
+            self.bloom, self.antiAliasing = bloom, aa
+        self.apply_bloom(src=self.mBackBufferDoF if self._depthOfField else self.mBackBuffer, params=bloom if isinstance(bloom, BloomParams) else None)
+        if aa:
+            self.antialias(src=self.mBackBufferBloom, params=aa if isinstance(aa, AAParams) else None)
+
+    def apply_bloom(self, src=None, out=None, params=None):
+        """crychic_bloom on the context's stream: the whole frame `out` (default: mBackBufferBloom, allocated on first use) from `src`
+        (default: mBackBuffer), both (H, W, 4) uint8 tensors of the frame's size; `out` may be `src` itself (in place) and must not
+        overlap it otherwise.  params: a BloomParams, None = the defaults.  The pyramid goes through mBloomWorkspace, allocated on
+        first use for the frame's size at BLOOM_MAX_LEVELS levels; afterwards its level k holds U_k.  Returns `out`."""
+        src = self.mBackBuffer if src is None else src
+        if out is None:
+            if self.mBackBufferBloom is None or self.mBackBufferBloom.shape != src.shape or self.mBackBufferBloom.device != src.device:
+                self.mBackBufferBloom = torch.zeros_like(src)
+            out = self.mBackBufferBloom
+        H, W = int(src.shape[0]), int(src.shape[1])
+        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
+                or not src.is_contiguous() or not out.is_contiguous() or (H, W) != (self.mClientHeight, self.mClientWidth):
+            raise CrychicError(-1, "apply_bloom takes contiguous (H, W, 4) uint8 tensors of the frame's size")
+        need = int(lib.crychic_bloom_workspace_bytes(W, H, _lib.BLOOM_MAX_LEVELS))
+        if self.mBloomWorkspace is None or self.mBloomWorkspace.numel() != need or self.mBloomWorkspace.device != src.device:
+            self.mBloomWorkspace = torch.zeros((need,), dtype=torch.uint8, device=src.device)
+        check(lib.crychic_bloom(self.ctx.handle, _ptr(src), _ptr(out), W, H, None if params is None else C.byref(params),
+                                _ptr(self.mBloomWorkspace), need, _stream(self.ctx.device)))
+        return out
 
     def depth_of_field(self, src=None, out=None, row0=0, rows=None, params=None):
         """crychic_dof on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferDoF, allocated on first use)

@@ -166,6 +166,7 @@ public:
         mBackBuffer = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
         if (mAntiAliasing) mBackBufferAA = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
         if (mDepthOfField) mBackBufferDoF = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
+        if (mBloom) AllocateBloom();
         mCamera.SetLens(0.25f * 3.1415926535f, AspectRatio(), 1.0f, 100.0f);                       // :114
         if (mSsao) { mSsao->OnResize(mClientWidth, mClientHeight); mSsao->RebuildDescriptors(mDepthStencilBuffer.get()); }
         if (mDeferred) { mDeferred->OnResize(mClientWidth, mClientHeight); mDeferred->BuildDescriptors(); }
@@ -215,6 +216,9 @@ public:
         if (mDepthOfField && (!mWholeFrame || mComm))
             throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (depth of field takes the whole frame on one GPU: no SetStrip / JoinNode)",
                                    __FILE__, __LINE__);
+        if (mBloom && (!mWholeFrame || mComm))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (bloom takes the whole frame on one GPU: no SetStrip / JoinNode)", __FILE__,
+                                   __LINE__);
         if (mRunProducerPasses) {
             DrawSceneToShadowMap();                                                                 // :208
             if (mFuseCameraPasses) DrawNormalsDepthAndGBuffer();                                    // :214 + :236 on one rasterisation
@@ -289,9 +293,14 @@ public:
         if (mDepthOfField)
             CrychicThrowIfFailed(crychic_dof(md3dDevice->Ctx(), passCB, f.depth_dev, f.out_rgba8_dev, static_cast<uint8_t*>(mBackBufferDoF->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
                                              &mDofParams, mCommandList->Stream()));
+        // SetBloom: the frame as it stands (fogged, through the lens blur) with its highlights spread, into its own back buffer
+        if (mBloom)
+            CrychicThrowIfFailed(crychic_bloom(md3dDevice->Ctx(), static_cast<const uint8_t*>((mDepthOfField ? mBackBufferDoF : mBackBuffer)->Data()),
+                                               static_cast<uint8_t*>(mBackBufferBloom->Data()), mClientWidth, mClientHeight, &mBloomParams,
+                                               mBloomWorkspace->Data(), mBloomWorkspace->Bytes(), mCommandList->Stream()));
         // SetAntiAliasing: the finished frame through the post-process pass into the second back buffer, behind the lighting pass
         if (mAntiAliasing)
-            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), static_cast<const uint8_t*>((mDepthOfField ? mBackBufferDoF : mBackBuffer)->Data()),
+            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), static_cast<const uint8_t*>((mBloom ? mBackBufferBloom : (mDepthOfField ? mBackBufferDoF : mBackBuffer))->Data()),
                                                    static_cast<uint8_t*>(mBackBufferAA->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
                                                    &mAAParams, mCommandList->Stream()));
         // :300-305: advance the fence and signal it behind this frame's commands
@@ -364,6 +373,32 @@ public:
     }
     bool DepthOfField() const { return mDepthOfField; }
     ID3D12Resource* DepthOfFieldBackBuffer() { return mBackBufferDoF.get(); }
+
+    // ---- bloom (extension) ------------------------------------------------------------------------------------------------------------
+    // Highlights over a luma threshold spread through a pyramid and added back (include/crychic_hip.h crychic_bloom).  On: Draw issues
+    // the pass after the lighting pass of a whole frame (and after the fog and the depth of field, if they are on), from the frame as
+    // it then stands into a buffer of its own, through a workspace this object owns; OnResize re-creates both.  The anti-aliasing, if
+    // on too, then reads that buffer, and Present writes the last stage's output.  CurrentBackBuffer stays the frame without it.
+    // p == nullptr: the default parameters.  With it on, SetStrip / JoinNode make Draw throw (the pass is not sharded).  Off (the
+    // default): nothing changes.
+    void SetBloom(bool on, const crychic_bloom_params* p = nullptr)
+    {
+        crychic_bloom_params q;
+        CrychicThrowIfFailed(crychic_bloom_default_params(&q));
+        if (p) q = *p;
+        if (q.threshold > 255u || q.knee == 0u || q.knee > 255u || q.scatter > 256u || q.intensity > 1024u || q.levels == 0u ||
+            q.levels > CRYCHIC_BLOOM_MAX_LEVELS || (q.reserved[0] | q.reserved[1] | q.reserved[2]))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG,
+                                   "CRYCHIC::SetBloom (threshold 0 .. 255, knee 1 .. 255, scatter 0 .. 256, intensity 0 .. 1024, levels 1 .. 8, reserved 0)",
+                                   __FILE__, __LINE__);
+        mCommandList->Flush();                                  // a frame in flight may still write the buffers released below
+        mBloom = on;
+        mBloomParams = q;
+        if (on) AllocateBloom();
+        else { mBackBufferBloom.reset(); mBloomWorkspace.reset(); }
+    }
+    bool Bloom() const { return mBloom; }
+    ID3D12Resource* BloomBackBuffer() { return mBackBufferBloom.get(); }
 
     // ---- deferred decals (extension) ------------------------------------------------------------------------------------------------
     // Oriented boxes that blend textures into the G-buffer between the producer passes and the lighting pass (include/crychic_hip.h
@@ -619,7 +654,7 @@ public:
     void Present(const std::string& path)
     {
         std::vector<uint8_t> host((size_t)mClientWidth * mClientHeight * 4);
-        (mAntiAliasing ? mBackBufferAA : (mDepthOfField ? mBackBufferDoF : mBackBuffer))->Download(host.data(), host.size(), mCommandList->Stream());
+        (mAntiAliasing ? mBackBufferAA : (mBloom ? mBackBufferBloom : (mDepthOfField ? mBackBufferDoF : mBackBuffer)))->Download(host.data(), host.size(), mCommandList->Stream());
         mCommandList->Flush();
         CrychicThrowIfFailed(crychic_save_ppm(path.c_str(), host.data(), mClientWidth, mClientHeight));
     }
@@ -1105,6 +1140,16 @@ private:
     bool mDepthOfField = false;               // SetDepthOfField
     crychic_dof_params mDofParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferDoF;  // the frame behind the depth-of-field pass, while mDepthOfField
+    bool mBloom = false;                      // SetBloom
+    crychic_bloom_params mBloomParams = {};
+    std::unique_ptr<ID3D12Resource> mBackBufferBloom;  // the frame behind the bloom pass, while mBloom
+    std::unique_ptr<ID3D12Resource> mBloomWorkspace;   // its pyramid: the frame's size at the most levels, so any parameters fit
+    void AllocateBloom()
+    {
+        mBackBufferBloom = std::make_unique<ID3D12Resource>((size_t)mClientWidth * mClientHeight * 4, ID3D12Resource::DEFAULT_HEAP);
+        mBloomWorkspace = std::make_unique<ID3D12Resource>(crychic_bloom_workspace_bytes(mClientWidth, mClientHeight, CRYCHIC_BLOOM_MAX_LEVELS),
+                                                           ID3D12Resource::DEFAULT_HEAP);
+    }
     bool mAntiAliasing = false;               // SetAntiAliasing
     crychic_aa_params mAAParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferAA;   // the anti-aliased frame, while mAntiAliasing

@@ -1085,6 +1085,79 @@ int crychic_apply_decals(crychic_ctx* ctx, const crychic_pass_constants* cb, con
                          const crychic_texture* textures, uint32_t nTextures, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
                          void* stream);
 
+/* ---- bloom: threshold, binomial pyramid and additive composite (extension) --------------------------------
+ * A pass over the finished RGBA8 frame, a separate call after the lighting pass, the fog and the depth of field and before the
+ * anti-aliasing: what lies over a luma threshold is filtered down a chain of half-size levels, the chain is folded back up with a
+ * scatter weight, and the result is added to the frame.  The first pass here that is a multi-resolution chain over a workspace of
+ * the caller's.  A build definition: nothing of it is the reference's.  The device, a host build and the checker (tests/bloom_ref)
+ * agree bit for bit.
+ *
+ * All arithmetic is unsigned 32-bit, divisions are integer divisions, and no intermediate reaches 2^32 (the bounds stand beside
+ * each step).  Parameters: T = threshold (8-bit luma units, default 192; 0 .. 255), K = knee (default 32; 1 .. 255), r = scatter
+ * (default 179; 0 .. 256), I = intensity (256 = 1.0, default 128; 0 .. 1024), n = levels (default 6;
+ * 1 .. CRYCHIC_BLOOM_MAX_LEVELS), reserved (must be 0).  crychic_bloom_default_params fills the defaults (pure host code;
+ * CRYCHIC_E_INVALID_ARG for NULL).
+ *
+ * Level sizes: W_0 = W, H_0 = H;  W_k = (W_(k-1) + 1) >> 1, H_k = (H_(k-1) + 1) >> 1 for k >= 1.  The effective level count is
+ * n_eff = min(n, max(1, ceil(log2(max(W, H))))): the chain stops at the first 1 x 1 level, and a 1 x 1 frame has one level.  A
+ * pyramid texel is four uint16_t: R, G, B and 0 -- 8 bytes.
+ * Bright value of a frame texel (R, G, B, A):  L = 77 R + 150 G + 29 B (crychic_antialias's luma, at most 65280);  w = 0 if
+ * L <= 256 T, else w = min(256, (L - 256 T) / K);  b_ch = in_ch w for R, G and B, 0 .. 255 * 256 = 65280.
+ * Downsample: D_1 from b (level 0), D_(k+1) from D_k.  The filter is the 4 x 4 binomial (1, 3, 3, 1) x (1, 3, 3, 1): destination
+ * (x, y) reads source columns 2x - 1 .. 2x + 2 and rows 2y - 1 .. 2y + 2, each coordinate clamped to the source level's edge,
+ * sum = the 16 products (at most 64 * 65280 = 4 177 920), v = (sum + 32) >> 6, again at most 65280.
+ * 2x upsample up(S)(x, y) of a level S of W_S x H_S texels:  x' = x >> 1;  xn = x' + 1 if x is odd, else x' - 1, clamped to
+ * [0, W_S - 1] (x' - 1 in signed terms: it clamps to 0);  y', yn likewise from y and H_S;
+ *   up = (9 S(x', y') + 3 S(xn, y') + 3 S(x', yn) + S(xn, yn) + 8) >> 4   (at most 16 * 65280 + 8, and up <= 65280).
+ * Unwind:  U_(n_eff) = D_(n_eff);  for k = n_eff - 1 .. 1:  U_k = (D_k (256 - r) + up(U_(k+1)) r + 128) >> 8  (at most
+ * 256 * 65280 + 128 before the shift and 65280 after it).
+ * Composite, for R, G and B:  out_ch = min(255, in_ch + ((up(U_1)_ch I + 32768) >> 16))  (65280 * 1024 + 32768 < 2^27); alpha is
+ * the pixel's own.
+ * Known answers: (1) intensity 0 gives out == in; (2) a frame with every L <= 256 T gives out == in and every level zero; (3) a
+ * frame of one colour c over the threshold has c w in every texel of every level and out_ch = min(255, c_ch + ((c_ch w I + 32768)
+ * >> 16)); (4) out_ch >= in_ch always; (5) scatter 0 makes U_1 = D_1, so levels >= 2 have no influence on the frame; (6) a square
+ * power-of-two frame whose input is symmetric under the eight symmetries of the square gives a symmetric output; (7) transposing any
+ * input transposes the output.
+ *
+ * Workspace: levels 1 .. n_eff back to back, each starting on a 16-byte boundary (a level of an odd number of texels is followed by
+ * 8 bytes that are never written); level k is W_k x H_k texels, row-major.  crychic_bloom_workspace_bytes is the end of level n_eff,
+ * crychic_bloom_level_offset the start of level k (0 for k = 0 or k > n_eff, as for W or H of 0 or levels outside
+ * 1 .. CRYCHIC_BLOOM_MAX_LEVELS); both are pure host code. */
+#define CRYCHIC_BLOOM_MAX_LEVELS 8
+typedef struct crychic_bloom_params {
+    uint32_t threshold;
+    uint32_t knee;
+    uint32_t scatter;
+    uint32_t intensity;
+    uint32_t levels;
+    uint32_t reserved[3];
+} crychic_bloom_params;   /* 32 bytes */
+int crychic_bloom_default_params(crychic_bloom_params* out);
+size_t crychic_bloom_workspace_bytes(uint32_t W, uint32_t H, uint32_t levels);
+size_t crychic_bloom_level_offset(uint32_t W, uint32_t H, uint32_t levels, uint32_t k);
+/* crychic_bloom_pyramid: after it level k of workspace_dev holds U_k for k = 1 .. n_eff (the unwind runs in place over D_k); no
+ * other byte of the workspace is written and in_rgba8_dev is only read.  2 n_eff - 1 launches on `stream`, one behind the other.
+ * crychic_bloom_composite: rows [row0, row0 + rows) of out_rgba8_dev from the same rows of in_rgba8_dev and level 1 of the
+ * workspace, and no other byte; every pixel is independent, so stitched row ranges equal the whole-frame call byte for byte;
+ * rows == 0 launches nothing.  in == out exactly is allowed (in place); any other overlap is refused.  One launch.
+ * crychic_bloom: the two calls above over the whole frame.
+ * All three: params == NULL = the defaults; no allocation, no synchronisation, no host read-back; capturable into a graph as one
+ * linear sequence of launches on `stream`.
+ * CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and before anything is enqueued: a NULL plane or
+ * workspace; a plane that is not 4-byte aligned or a workspace that is not 16-byte aligned; W or H of 0; a row range outside the
+ * frame; a parameter outside its range or a non-zero reserved word; workspace_bytes below crychic_bloom_workspace_bytes(W, H,
+ * levels); a workspace (its first crychic_bloom_workspace_bytes bytes) overlapping a plane; in and out overlapping without being
+ * equal.  More than 2^28 pixels: CRYCHIC_E_UNSUPPORTED. */
+int crychic_bloom_pyramid(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint32_t W, uint32_t H,
+                          const crychic_bloom_params* params /* NULL = defaults */, void* workspace_dev, size_t workspace_bytes,
+                          void* stream);
+int crychic_bloom_composite(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H,
+                            uint32_t row0, uint32_t rows, const crychic_bloom_params* params /* NULL = defaults */,
+                            const void* workspace_dev, size_t workspace_bytes, void* stream);
+int crychic_bloom(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H,
+                  const crychic_bloom_params* params /* NULL = defaults */, void* workspace_dev, size_t workspace_bytes,
+                  void* stream);
+
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
  * of 2 rows (half-res alignment); the last rank takes the remainder. */
