@@ -174,6 +174,25 @@ class BloomParams(C.Structure):
         return p
 
 
+TAA_RESET, TAA_NO_CLAMP = 1, 2               # CRYCHIC_TAA_RESET, CRYCHIC_TAA_NO_CLAMP
+
+
+class TaaParams(C.Structure):
+    """crychic_taa_params: the knobs of crychic_taa (extension); TaaParams.default() = crychic_taa_default_params, any field replaced by
+    its keyword."""
+    _fields_ = [("blend", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+    @classmethod
+    def default(cls, blend=None, flags=None):
+        p = cls()
+        check(lib.crychic_taa_default_params(C.byref(p)))
+        if blend is not None:
+            p.blend = int(blend)
+        if flags is not None:
+            p.flags = int(flags)
+        return p
+
+
 class PassTimes(C.Structure):
     _fields_ = [("ssao_ms", C.c_float), ("blur_ms", C.c_float), ("light_ms", C.c_float), ("total_ms", C.c_float)]
 
@@ -280,7 +299,13 @@ PROTOTYPES = {
     "crychic_bloom_pyramid": (_i, [_vp, _vp, _u32, _u32, _P(BloomParams), _vp, _sz, _vp]),
     "crychic_bloom_composite": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(BloomParams), _vp, _sz, _vp]),
     "crychic_bloom": (_i, [_vp, _vp, _vp, _u32, _u32, _P(BloomParams), _vp, _sz, _vp]),
-    "crychic_save_ppm": (_i, [C.c_char_p, _vp, _u32, _u32]),
+    "crychic_taa_jitter": (_i, [_u32, _P(_f), _P(_f)]),
+    "crychic_update_main_pass_cb_jittered": (_i, [_P(Camera), _u32, _u32, _vp, _vp, _f, _f, _P(PassConstants)]),
+    "crychic_update_ssao_cb_jittered": (_i, [_P(Camera), _u32, _u32, _vp, _f, _f, _P(SsaoConstants)]),
+    "crychic_taa_default_params": (_i, [_P(TaaParams)]),
+    "crychic_taa_history_bytes": (_sz, [_u32, _u32]),
+    "crychic_taa": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(TaaParams), _vp]),
+    "crychic_save_ppm":(_i, [C.c_char_p, _vp, _u32, _u32]),
     "crychic_raster_workspace_bytes": (_sz, [C.c_uint64, _u32, _u32]),
     "crychic_raster_status": (_i, [_vp, _vp, _P(_u32)]),
     "crychic_blur_chain_status": (_i, [_vp, _vp, _P(_u32)]),

@@ -23,6 +23,7 @@
 #include "fog_core.hpp"
 #include "dof_core.hpp"
 #include "bloom_core.hpp"
+#include "taa_core.hpp"
 #include "decal_core.hpp"
 #include "internal.hpp"
 
@@ -1130,6 +1131,60 @@ int crychic_bloom(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rg
     if (int rc = bind(ctx)) return rc;
     CRY_HIP(cry::launch_bloom_pyramid(in_rgba8_dev, W, H, q, workspace_dev, (hipStream_t)stream));
     CRY_HIP(cry::launch_bloom_composite(in_rgba8_dev, out_rgba8_dev, W, H, 0u, H, q, workspace_dev, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(CRYCHIC_TAA_RESET == cry::kTaaReset && CRYCHIC_TAA_NO_CLAMP == cry::kTaaNoClamp && sizeof(crychic_taa_params) == 32 &&
+              sizeof(crychic_taa_params) == sizeof(cry::TaaParams), "taa_core.hpp mirrors the ABI");
+
+int crychic_taa_default_params(crychic_taa_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    *out = crychic_taa_params{};
+    out->blend = 26u;
+    return 0;
+}
+
+size_t crychic_taa_history_bytes(uint32_t W, uint32_t H) { return (size_t)W * H * 8u; }
+
+int crychic_taa(crychic_ctx* ctx, const crychic_pass_constants* cb, const float curViewProj[16], const float prevViewProj[16], const uint32_t* depth_dev,
+                const uint8_t* in_rgba8_dev, const uint16_t* history_in_dev, uint16_t* history_out_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H,
+                uint32_t row0, uint32_t rows, const crychic_taa_params* params, void* stream)
+{
+    // every argument is checked before the context is looked at: a refusal needs no device
+    crychic_taa_params p;
+    crychic_taa_default_params(&p);
+    if (params) p = *params;
+    if (p.blend == 0u || p.blend > 256u) return fail(CRYCHIC_E_INVALID_ARG, "temporal anti-aliasing blend %u outside 1 .. 256", p.blend);
+    if (p.flags & ~(CRYCHIC_TAA_RESET | CRYCHIC_TAA_NO_CLAMP)) return fail(CRYCHIC_E_INVALID_ARG, "temporal anti-aliasing flags 0x%x: unknown bits", p.flags);
+    for (uint32_t r : p.reserved)
+        if (r) return fail(CRYCHIC_E_INVALID_ARG, "temporal anti-aliasing reserved words must be 0");
+    const bool reset = (p.flags & CRYCHIC_TAA_RESET) != 0u;
+    if (!cb || !curViewProj || !prevViewProj || !depth_dev || !in_rgba8_dev || !history_out_dev || !out_rgba8_dev || (!history_in_dev && !reset))
+        return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    const uintptr_t z = reinterpret_cast<uintptr_t>(depth_dev), s = reinterpret_cast<uintptr_t>(in_rgba8_dev), d = reinterpret_cast<uintptr_t>(out_rgba8_dev);
+    const uintptr_t hi = reinterpret_cast<uintptr_t>(history_in_dev), ho = reinterpret_cast<uintptr_t>(history_out_dev);
+    if ((z | s | d) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "temporal anti-aliasing frame planes are not 4-byte aligned");
+    if ((hi | ho) & 7u) return fail(CRYCHIC_E_INVALID_ARG, "temporal anti-aliasing history planes are not 8-byte aligned");
+    if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
+    if (int rc = check_extent("frame", W, H, false, 0u)) return rc;                   // a one-dimensional grid, at most 2^27 workgroups
+    if (W > cry::kTaaMaxSide || H > cry::kTaaMaxSide) return fail(CRYCHIC_E_UNSUPPORTED, "frame %ux%u: temporal anti-aliasing takes at most 2^22 texels a side", W, H);
+    if (int rc = check_rows(kFrameRows, row0, rows, H)) return rc;
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(cb->InvViewProj[k]) || !std::isfinite(curViewProj[k]) || !std::isfinite(prevViewProj[k]))
+            return fail(CRYCHIC_E_INVALID_ARG, "temporal anti-aliasing: entry %d of InvViewProj, curViewProj or prevViewProj is not finite", k);
+    const size_t bytes = (size_t)W * H * 4u, hbytes = crychic_taa_history_bytes(W, H);
+    if (ranges_overlap(s, bytes, d, bytes))
+        return fail(CRYCHIC_E_INVALID_ARG, "the temporal anti-aliasing input and output planes overlap (the pass reads neighbours: it cannot run in place)");
+    if (history_in_dev && ranges_overlap(hi, hbytes, ho, hbytes)) return fail(CRYCHIC_E_INVALID_ARG, "the temporal anti-aliasing history planes overlap");
+    for (const uintptr_t h : { hi, ho })
+        if (h && (ranges_overlap(h, hbytes, s, bytes) || ranges_overlap(h, hbytes, d, bytes) || ranges_overlap(h, hbytes, z, bytes)))
+            return fail(CRYCHIC_E_INVALID_ARG, "a temporal anti-aliasing history plane overlaps a frame plane");
+    if (int rc = bind(ctx)) return rc;
+    cry::TaaParams q;
+    std::memcpy(&q, &p, sizeof q);
+    CRY_HIP(cry::launch_taa(cb->InvViewProj, curViewProj, prevViewProj, depth_dev, in_rgba8_dev, reset ? nullptr : history_in_dev, history_out_dev,
+                            out_rgba8_dev, W, H, row0, rows, q, (hipStream_t)stream));
     return 0;
 }
 

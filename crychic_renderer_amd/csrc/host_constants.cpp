@@ -152,6 +152,17 @@ void transform_point(V3 v, const Mat4& m, float out[4])
     for (int j = 0; j < 4; ++j) out[j] = v.x * m.m[0][j] + v.y * m.m[1][j] + v.z * m.m[2][j] + m.m[3][j];
 }
 
+// The camera's projection with a world point moved by (jx, jy) pixels on a W x H target, y growing downwards (temporal
+// anti-aliasing; crychic_hip.h): x_ndc grows by 2 jx / W and y_ndc by -2 jy / H, each times the clip w = view z.  A zero offset
+// adds 0.0f to elements that are 0.0f.
+Mat4 jittered_projection(const crychic_camera& c, uint32_t W, uint32_t H, float jx, float jy)
+{
+    Mat4 p = perspective_fov_lh(c.fovY, c.aspect, c.nearZ, c.farZ);
+    p.m[2][0] += 2.0f * jx / (float)W;
+    p.m[2][1] += (-2.0f * jy) / (float)H;
+    return p;
+}
+
 float randf(uint32_t* s) { return (float)crychic_msvc_rand(s) / 32767.0f; }  // MathHelper::RandF, RAND_MAX 0x7FFF
 
 }  // namespace
@@ -389,12 +400,12 @@ int crychic_cube_prefilter_samples(uint32_t dim, uint32_t levels, uint32_t level
     return 0;
 }
 
-int crychic_update_main_pass_cb(const crychic_camera* cam, uint32_t W, uint32_t H, const float shadowTransform[4][16],
-                                const float lightDirs[3][3], crychic_pass_constants* out)
+int crychic_update_main_pass_cb_jittered(const crychic_camera* cam, uint32_t W, uint32_t H, const float shadowTransform[4][16],
+                                         const float lightDirs[3][3], float jx, float jy, crychic_pass_constants* out)
 {
-    if (!cam || !shadowTransform || !lightDirs || !out || W == 0 || H == 0) return CRYCHIC_E_INVALID_ARG;
+    if (!cam || !shadowTransform || !lightDirs || !out || W == 0 || H == 0 || !std::isfinite(jx) || !std::isfinite(jy)) return CRYCHIC_E_INVALID_ARG;
     const Mat4 view = camera_view(*cam);
-    const Mat4 proj = perspective_fov_lh(cam->fovY, cam->aspect, cam->nearZ, cam->farZ);
+    const Mat4 proj = jittered_projection(*cam, W, H, jx, jy);
     const Mat4 viewProj = view * proj;
     Mat4 invView, invProj, invViewProj;
     if (!inverse(view, invView) || !inverse(proj, invProj) || !inverse(viewProj, invViewProj)) return CRYCHIC_E_INVALID_ARG;
@@ -433,11 +444,17 @@ int crychic_update_main_pass_cb(const crychic_camera* cam, uint32_t W, uint32_t 
     return 0;
 }
 
-int crychic_update_ssao_cb(const crychic_camera* cam, uint32_t W, uint32_t H, const float offsets[14][4],
-                           crychic_ssao_constants* out)
+int crychic_update_main_pass_cb(const crychic_camera* cam, uint32_t W, uint32_t H, const float shadowTransform[4][16],
+                                const float lightDirs[3][3], crychic_pass_constants* out)
 {
-    if (!cam || !offsets || !out || W < 2 || H < 2) return CRYCHIC_E_INVALID_ARG;
-    const Mat4 proj = perspective_fov_lh(cam->fovY, cam->aspect, cam->nearZ, cam->farZ);
+    return crychic_update_main_pass_cb_jittered(cam, W, H, shadowTransform, lightDirs, 0.0f, 0.0f, out);
+}
+
+int crychic_update_ssao_cb_jittered(const crychic_camera* cam, uint32_t W, uint32_t H, const float offsets[14][4], float jx, float jy,
+                                    crychic_ssao_constants* out)
+{
+    if (!cam || !offsets || !out || W < 2 || H < 2 || !std::isfinite(jx) || !std::isfinite(jy)) return CRYCHIC_E_INVALID_ARG;
+    const Mat4 proj = jittered_projection(*cam, W, H, jx, jy);
     Mat4 invProj;
     if (!inverse(proj, invProj)) return CRYCHIC_E_INVALID_ARG;
     std::memset(out, 0, sizeof *out);
@@ -454,6 +471,25 @@ int crychic_update_ssao_cb(const crychic_camera* cam, uint32_t W, uint32_t H, co
     out->OcclusionFadeStart = 0.2f;
     out->OcclusionFadeEnd = 1.0f;
     out->SurfaceEpsilon = 0.05f;
+    return 0;
+}
+
+int crychic_update_ssao_cb(const crychic_camera* cam, uint32_t W, uint32_t H, const float offsets[14][4],
+                           crychic_ssao_constants* out)
+{
+    return crychic_update_ssao_cb_jittered(cam, W, H, offsets, 0.0f, 0.0f, out);
+}
+
+// Sample 1 + index % 16 of the Halton (2, 3) sequence minus 0.5 (crychic_hip.h states the rounding).
+int crychic_taa_jitter(uint32_t index, float* jx, float* jy)
+{
+    if (!jx || !jy) return cry::fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    const uint32_t i = 1u + index % 16u;
+    uint32_t n2 = 0u, d2 = 1u, n3 = 0u, d3 = 1u;
+    for (uint32_t k = i; k; k >>= 1) { n2 = 2u * n2 + (k & 1u); d2 *= 2u; }
+    for (uint32_t k = i; k; k /= 3u) { n3 = 3u * n3 + k % 3u; d3 *= 3u; }
+    *jx = (float)n2 / (float)d2 - 0.5f;       // a multiple of 1/32 at the finest: exact
+    *jy = (float)n3 / (float)d3 - 0.5f;
     return 0;
 }
 

@@ -124,6 +124,15 @@ hipError_t launch_bloom_pyramid(const uint8_t* in, uint32_t W, uint32_t H, const
 hipError_t launch_bloom_composite(const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const BloomParams& p,
                                   const void* workspace, hipStream_t stream);
 
+// taa.hip: rows [row0, row0 + rows) of the W x H RGBA8 frame `out` and of the history plane `historyOut` from `in`, the D24 plane
+// `depth` and the history plane `historyIn` (NULL only with the reset flag) (taa_core.hpp); the three matrices are read before the
+// call returns.  One launch on `stream`, none for rows == 0.  The caller has checked the pointers, their alignment and overlap, the
+// sizes, the rows, the matrices and `p`.
+struct TaaParams;
+hipError_t launch_taa(const float* invViewProj, const float* curViewProj, const float* prevViewProj, const uint32_t* depth, const uint8_t* in,
+                      const uint16_t* historyIn, uint16_t* historyOut, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                      const TaaParams& p, hipStream_t stream);
+
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
 struct Texture;

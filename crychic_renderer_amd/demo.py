@@ -4,6 +4,7 @@
                                    [--fog [--fog-density X] [--fog-steps N]]
                                    [--dof [--dof-focus X] [--dof-aperture X] [--dof-radius N]]
                                    [--bloom [--bloom-threshold N] [--bloom-intensity N] [--bloom-levels N]]
+                                   [--taa [--taa-frames N]]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
@@ -34,6 +35,9 @@ buffer, in front of --aa); --fog-density (default 0.02) and --fog-steps (default
 --bloom: what lies over a luma threshold is spread down and up a pyramid and added back (Crychic.bloom: crychic_bloom after the lighting
 pass, the fog and --dof, in front of --aa); --bloom-threshold (8-bit luma, default 192), --bloom-intensity (256 = 1.0, default 128, at
 most 1024) and --bloom-levels (default 6, at most 8) set its parameters.
+--taa: temporal anti-aliasing (Crychic.temporalAA: crychic_taa after the lighting pass and the fog, in front of --dof, --bloom and
+--aa): --taa-frames frames (default 16) of the still scene are rendered, each with the projection shifted by its sub-pixel jitter
+(crychic_taa_jitter), and blended into the history; the resolved frame of the last one is what the later stages read.
 --decals: deferred decals between the G-buffer pass and the lighting pass (Crychic.set_decals / apply_decals: crychic_apply_decals): a
 glossy puddle with a dent normal map on the floor and a painted ring on the face of a box."""
 import argparse
@@ -76,7 +80,11 @@ def main():
     ap.add_argument("--bloom-threshold", type=int, default=None, metavar="N", help="luma threshold, 0 .. 255 (default 192; needs --bloom)")
     ap.add_argument("--bloom-intensity", type=int, default=None, metavar="N", help="strength, 256 = 1.0, 0 .. 1024 (default 128; needs --bloom)")
     ap.add_argument("--bloom-levels", type=int, default=None, metavar="N", help="pyramid levels, 1 .. 8 (default 6; needs --bloom)")
+    ap.add_argument("--taa", action="store_true", help="temporal anti-aliasing: jittered frames of the still scene blended into a history")
+    ap.add_argument("--taa-frames", type=int, default=None, metavar="N", help="jittered frames to render (default 16; needs --taa)")
     a = ap.parse_args()
+    if a.taa_frames is not None and not (a.taa and a.taa_frames >= 1):
+        ap.error("--taa-frames takes a positive count and needs --taa")
     if (a.bloom_threshold is not None or a.bloom_intensity is not None or a.bloom_levels is not None) and not a.bloom:
         ap.error("--bloom-threshold, --bloom-intensity and --bloom-levels need --bloom")
     if (a.dof_focus is not None or a.dof_aperture is not None or a.dof_radius is not None) and not a.dof:
@@ -135,9 +143,14 @@ def main():
         cb = PassConstants()
         cb.ViewProj[:] = list((consts.light_view[k].astype(np.float32) @ consts.light_proj[k].astype(np.float32)).T.reshape(-1))
         sgeo.DrawSceneToShadowMap(cb, app.mShadowMap.mShadowMap[k])
+    def camera_passes():
+        geo.DrawNormalsAndDepth(app.mMainPassCB, app.mSsao.mNormalMap, app.mDepthStencilBuffer)
+        geo.DrawGBuffer(app.mMainPassCB, app.mDeferred.mGBuffer, app.mDepthStencilBuffer)
+        if a.decals:
+            app.apply_decals()
     geo.DrawNormalsAndDepth(app.mMainPassCB, app.mSsao.mNormalMap, app.mDepthStencilBuffer)
     geo.DrawGBuffer(app.mMainPassCB, app.mDeferred.mGBuffer, app.mDepthStencilBuffer)
-    if a.decals:          # once, on the fresh G-buffer: a second application would stack
+    if a.decals:          # once on each fresh G-buffer: a second application would stack
         from ._lib import DECAL_ALBEDO, DECAL_METALNESS, DECAL_NORMAL, DECAL_ROUGHNESS
         puddle = g.decal_from_box(g.decal_box_world((2.5, 0.0, -7.5), (1.5, 0.25, 1.5)), (64, 64), 0.5, 0.0, texture=0, normalTexture=1,
                                   flags=DECAL_ALBEDO | DECAL_ROUGHNESS | DECAL_NORMAL, roughness=0.03, opacity=0.85)
@@ -164,11 +177,24 @@ def main():
         app.bloom = BloomParams.default(threshold=a.bloom_threshold, intensity=a.bloom_intensity, levels=a.bloom_levels)
     if a.aa:
         app.antiAliasing = True
-    app.Draw()
+    if a.taa:
+        # the still scene under the jitter sequence: the camera planes are rasterised again with each frame's shifted projection, the
+        # pass gets the unjittered ViewProj of the same camera for this frame and the previous one
+        app.temporalAA = True
+        jx, jy = C.c_float(), C.c_float()
+        for k in range(a.taa_frames or 16):
+            check(lib.crychic_taa_jitter(k, C.byref(jx), C.byref(jy)))
+            jittered = scene.Constants(W, H, a.shadow_dim, jitter=(jx.value, jy.value))
+            app.mMainPassCB, app.mSsaoCB = jittered.pass_cb, jittered.ssao_cb
+            camera_passes()
+            app.set_frame_view_proj(consts.pass_cb.ViewProj)
+            app.Draw()
+    else:
+        app.Draw()
     torch.cuda.synchronize()
-    img = np.ascontiguousarray((app.mBackBufferAA if a.aa else (app.mBackBufferBloom if a.bloom else (app.mBackBufferDoF if a.dof else app.mBackBuffer))).cpu().numpy())
+    img = np.ascontiguousarray((app.mBackBufferAA if a.aa else (app.mBackBufferBloom if a.bloom else (app.mBackBufferDoF if a.dof else (app.mBackBufferTAA if a.taa else app.mBackBuffer)))).cpu().numpy())
     check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, W, H))
-    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, (", fog" if a.fog else "") + (", depth of field" if a.dof else "") + (", bloom" if a.bloom else "") + (", anti-aliased" if a.aa else ""), ctx.device_name))
+    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, (", fog" if a.fog else "") + (", temporal anti-aliasing" if a.taa else "") + (", depth of field" if a.dof else "") + (", bloom" if a.bloom else "") + (", anti-aliased" if a.aa else ""), ctx.device_name))
 
 
 if __name__ == "__main__":

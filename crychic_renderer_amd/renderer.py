@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (AAParams, CrychicError, FogParams, DofParams, BloomParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, FogParams, DofParams, BloomParams, TaaParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -231,6 +231,11 @@ class Crychic:
         self._bloom = None           # bloom, extension: None | True | BloomParams -- Draw() of a whole frame runs crychic_bloom into mBackBufferBloom
         self.mBackBufferBloom = None  # the frame behind the bloom pass, allocated by the first apply_bloom() that needs it
         self.mBloomWorkspace = None  # the pass's pyramid: crychic_bloom_workspace_bytes of the frame at the most levels, with the first apply_bloom()
+        self._temporalAA = None      # temporalAA, extension: None | True | TaaParams -- Draw() of a whole frame runs crychic_taa into mBackBufferTAA
+        self.mBackBufferTAA = None   # the resolved frame, allocated by the first temporal_aa() that needs it
+        self.mTaaHistory = None      # [history read by the next call, history it writes]: (H, W, 4) int16 planes of 8.8 fixed point, swapped after each call
+        self._taaReset = True        # the next Draw() with temporalAA set is a RESET frame: the first, or the first after the switch was turned on
+        self._taaViewProj = [None, None]     # set_frame_view_proj: the unjittered ViewProj of this frame and of the previous one
         self.mDecals, self.mDecalCount = None, 0                             # set_decals, extension: the device array of Decal structs
         self._decalTextures, self._decalTextureCount, self._decalKeep = None, 0, []     # the host texture table and the chains it points into
 
@@ -239,14 +244,17 @@ class Crychic:
             return getattr(self, name)
 
         def put(self, value):
+            if name == "_temporalAA" and value and not self._temporalAA:
+                self._taaReset = True            # turned on: whatever the history planes hold is stale
             setattr(self, name, value)
-            self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom)
+            self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA)
         return property(get, put)
 
     antiAliasing = _post_switch("_antiAliasing")
     fog = _post_switch("_fog")
     depthOfField = _post_switch("_depthOfField")
     bloom = _post_switch("_bloom")
+    temporalAA = _post_switch("_temporalAA")
     del _post_switch
 
     def set_gbuffer_formats(self, formats):
@@ -315,12 +323,19 @@ class Crychic:
         mBackBufferDoF; the anti-aliasing, if set too, then reads mBackBufferDoF.  A strip or a shared draw then raises CrychicError.
         bloom = True or a BloomParams (extension): a whole frame (fogged, and through the depth of field, as set), then crychic_bloom
         from that frame into mBackBufferBloom; the anti-aliasing, if set too, then reads mBackBufferBloom.  A strip or a shared draw
-        then raises CrychicError."""
+        then raises CrychicError.
+        temporalAA = True or a TaaParams (extension): a whole frame (fogged if fog is set), then crychic_taa from mBackBuffer into
+        mBackBufferTAA with the matrices of set_frame_view_proj; the depth of field, the bloom and the anti-aliasing, as set, then
+        read mBackBufferTAA.  The order is lighting, fog, temporal anti-aliasing, depth of field, bloom, anti-aliasing: the temporal
+        pass needs the frame still aligned with its depth plane.  The first such frame, and the first after the switch was turned on
+        or the frame's size changed, is a RESET frame.  A strip or a shared draw then raises CrychicError."""
         if self._post:
             if self._bloom:
                 return self._draw_with_bloom(row0, rows, shared)
             if self._depthOfField:
                 return self._draw_with_depth_of_field(row0, rows, shared)
+            if self._temporalAA:
+                return self._draw_with_temporal_aa(row0, rows, shared)
             if self._fog:
                 return self._draw_fogged(row0, rows, shared)
             return self._draw_antialiased(row0, rows, shared)
@@ -405,7 +420,7 @@ class Crychic:
             self.Draw()
         finally:
             self.depthOfField, self.antiAliasing = dof, aa
-        self.depth_of_field(params=dof if isinstance(dof, DofParams) else None)
+        self.depth_of_field(src=self.mBackBufferTAA if self._temporalAA else self.mBackBuffer, params=dof if isinstance(dof, DofParams) else None)
         if aa:
             self.antialias(src=self.mBackBufferDoF, params=aa if isinstance(aa, AAParams) else None)
 
@@ -419,9 +434,66 @@ class Crychic:
             self.Draw()
         finally:
             self.bloom, self.antiAliasing = bloom, aa
-        self.apply_bloom(src=self.mBackBufferDoF if self._depthOfField else self.mBackBuffer, params=bloom if isinstance(bloom, BloomParams) else None)
+        self.apply_bloom(src=self.mBackBufferDoF if self._depthOfField else (self.mBackBufferTAA if self._temporalAA else self.mBackBuffer), params=bloom if isinstance(bloom, BloomParams) else None)
         if aa:
             self.antialias(src=self.mBackBufferBloom, params=aa if isinstance(aa, AAParams) else None)
+
+    def _draw_with_temporal_aa(self, row0, rows, shared):
+        """Draw() with temporalAA set: the frame as Draw() issues it without (fogged in place if fog is set), the temporal pass from
+        mBackBuffer into mBackBufferTAA, then the anti-aliasing of mBackBufferTAA if that is set."""
+        self._whole_frame_only("temporalAA", row0, rows, shared)
+        taa, aa, self.temporalAA, self.antiAliasing = self.temporalAA, self.antiAliasing, None, None
+        reset = self._taaReset                 # the setter below sets it again: the switch goes from off to on
+        try:
+            self.Draw()
+        finally:
+            self.temporalAA, self.antiAliasing = taa, aa
+            self._taaReset = reset
+        cur, prev = self._taaViewProj
+        if cur is None:                         # set_frame_view_proj was never called: a still camera whose constants are not jittered
+            cur = prev = tuple(self.mMainPassCB.ViewProj)
+        self.temporal_aa(cur, cur if prev is None else prev, reset=self._taaReset, params=taa if isinstance(taa, TaaParams) else None)
+        self._taaReset = False
+        if aa:
+            self.antialias(src=self.mBackBufferTAA, params=aa if isinstance(aa, AAParams) else None)
+
+    def set_frame_view_proj(self, view_proj):
+        """The UNJITTERED view-projection of the frame about to be drawn (16 floats, stored transposed like the pass constants'
+        ViewProj): what was current becomes the previous frame's.  Draw() with temporalAA set hands both to crychic_taa."""
+        m = tuple(float(v) for v in view_proj)
+        if len(m) != 16:
+            raise CrychicError(-1, "set_frame_view_proj takes 16 floats")
+        self._taaViewProj = [m, self._taaViewProj[0]]
+
+    def temporal_aa(self, cur_view_proj, prev_view_proj, src=None, out=None, reset=False, row0=0, rows=None, params=None):
+        """crychic_taa on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferTAA, allocated on first use) from
+        `src` (default: mBackBuffer), both (H, W, 4) uint8 tensors of the frame's size, with this frame's depth plane and (jittered)
+        pass constants and the two UNJITTERED view-projections (16 floats each, stored transposed).  The two history planes
+        mTaaHistory are this object's: allocated on first use (which makes the call a RESET call, as does reset=True or a RESET flag
+        in params), read from [0], written to [1] and swapped after the call, so that mTaaHistory[0] is the history just written.
+        params: a TaaParams, None = the defaults.  `src` and `out` must not overlap.  Returns `out`."""
+        src = self.mBackBuffer if src is None else src
+        if out is None:
+            if self.mBackBufferTAA is None or self.mBackBufferTAA.shape != src.shape or self.mBackBufferTAA.device != src.device:
+                self.mBackBufferTAA = torch.zeros_like(src)
+            out = self.mBackBufferTAA
+        H, W = int(src.shape[0]), int(src.shape[1])
+        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
+                or not src.is_contiguous() or not out.is_contiguous() or (H, W) != (self.mClientHeight, self.mClientWidth):
+            raise CrychicError(-1, "temporal_aa takes contiguous (H, W, 4) uint8 tensors of the frame's size")
+        if self.mTaaHistory is None or self.mTaaHistory[0].shape != src.shape or self.mTaaHistory[0].device != src.device:
+            self.mTaaHistory = [torch.zeros((H, W, 4), dtype=torch.int16, device=src.device) for _ in range(2)]
+            reset = True
+        p = TaaParams.default() if params is None else TaaParams.from_buffer_copy(params)
+        if reset:
+            p.flags |= _lib.TAA_RESET
+        cur, prev = (C.c_float * 16)(*cur_view_proj), (C.c_float * 16)(*prev_view_proj)
+        hin, hout = self.mTaaHistory
+        check(lib.crychic_taa(self.ctx.handle, C.byref(self.mMainPassCB), cur, prev, self.mDepthStencilBuffer.data_ptr(), _ptr(src),
+                              None if p.flags & _lib.TAA_RESET else _ptr(hin), _ptr(hout), _ptr(out), W, H, int(row0),
+                              int(H - row0 if rows is None else rows), C.byref(p), _stream(self.ctx.device)))
+        self.mTaaHistory = [hout, hin]
+        return out
 
     def apply_bloom(self, src=None, out=None, params=None):
         """crychic_bloom on the context's stream: the whole frame `out` (default: mBackBufferBloom, allocated on first use) from `src`

@@ -51,8 +51,12 @@ class Constants:
     """SsaoConstants + PassConstants + the light matrices of one frame (UpdateSsaoCB / UpdateMainPassCB /
     UpdateCascadeShadowTransform, CRYCHIC.cpp:634-937), built by the library's host code."""
 
-    def __init__(self, W, H, shadow_dim=4096, cam=None):
+    def __init__(self, W, H, shadow_dim=4096, cam=None, jitter=(0.0, 0.0)):
+        """jitter = (jx, jy): the frame's sub-pixel offset in pixels (temporal anti-aliasing, crychic_taa_jitter): the constants come
+        from the _jittered builders and the synthetic ray-caster shifts its rays to match.  (0, 0) is the unjittered frame, byte for
+        byte."""
         self.W, self.H, self.shadow_dim = W, H, shadow_dim
+        self.jitter = (float(jitter[0]), float(jitter[1]))
         self.cam = cam or default_camera(W, H)
         # The Ssao object is the first user of rand() in the process (CRYCHIC.cpp:51, Ssao.cpp:18-19).
         self.rand_state = C.c_uint32(1)
@@ -69,11 +73,11 @@ class Constants:
             self.shadow_transform.ctypes.data))
         self.pass_cb = PassConstants()
         dirs = np.asarray(BASE_LIGHT_DIRS, dtype=np.float32)
-        _lib.check(lib.crychic_update_main_pass_cb(C.byref(self.cam), W, H, self.shadow_transform.ctypes.data,
-                                                   dirs.ctypes.data, C.byref(self.pass_cb)))
+        _lib.check(lib.crychic_update_main_pass_cb_jittered(C.byref(self.cam), W, H, self.shadow_transform.ctypes.data,
+                                                            dirs.ctypes.data, self.jitter[0], self.jitter[1], C.byref(self.pass_cb)))
         self.ssao_cb = SsaoConstants()
-        _lib.check(lib.crychic_update_ssao_cb(C.byref(self.cam), W, H, C.cast(self.offsets, C.c_void_p),
-                                              C.byref(self.ssao_cb)))
+        _lib.check(lib.crychic_update_ssao_cb_jittered(C.byref(self.cam), W, H, C.cast(self.offsets, C.c_void_p),
+                                                       self.jitter[0], self.jitter[1], C.byref(self.ssao_cb)))
 
 
 def _box_centres(device, dtype):
@@ -146,8 +150,11 @@ def _camera_planes(consts, device):
     eye = torch.tensor(list(cam.pos), device=device, dtype=dt)
     R, U, L = _camera_basis(cam, device, dt)
     th = math.tan(0.5 * cam.fovY)
-    xs = (torch.arange(W, device=device, dtype=dt) + 0.5) / W * 2.0 - 1.0
-    ys = 1.0 - (torch.arange(H, device=device, dtype=dt) + 0.5) / H * 2.0
+    # the ray of pixel (px, py) goes through the screen position (px + 0.5 - jx, py + 0.5 - jy): what the jittered projection shows
+    # at a pixel's centre is what the unjittered one shows (jx, jy) before it
+    jx, jy = getattr(consts, "jitter", (0.0, 0.0))
+    xs = (torch.arange(W, device=device, dtype=dt) + 0.5 - jx) / W * 2.0 - 1.0
+    ys = 1.0 - (torch.arange(H, device=device, dtype=dt) + 0.5 - jy) / H * 2.0
     vx = (xs * cam.aspect * th)[None, :].expand(H, W).reshape(-1)
     vy = (ys * th)[:, None].expand(H, W).reshape(-1)
     D = vx[:, None] * R[None] + vy[:, None] * U[None] + L[None]

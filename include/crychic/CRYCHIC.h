@@ -167,6 +167,7 @@ public:
         if (mAntiAliasing) mBackBufferAA = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
         if (mDepthOfField) mBackBufferDoF = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
         if (mBloom) AllocateBloom();
+        if (mTemporalAA) AllocateTemporalAA();                                                      // new history planes: the next frame is a reset frame
         mCamera.SetLens(0.25f * 3.1415926535f, AspectRatio(), 1.0f, 100.0f);                       // :114
         if (mSsao) { mSsao->OnResize(mClientWidth, mClientHeight); mSsao->RebuildDescriptors(mDepthStencilBuffer.get()); }
         if (mDeferred) { mDeferred->OnResize(mClientWidth, mClientHeight); mDeferred->BuildDescriptors(); }
@@ -200,6 +201,7 @@ public:
         UpdateCascadeShadowTransform(gt);
         UpdateSpotShadowTransforms();
         UpdatePointShadowTransforms();
+        if (mTemporalAA) CrychicThrowIfFailed(crychic_taa_jitter(mTaaFrameIndex++, &mTaaJitter[0], &mTaaJitter[1]));   // this frame's sub-pixel offset
         UpdateMainPassCB(gt);
         UpdateShadowPassCB(gt);
         UpdateSsaoCB(gt);
@@ -219,6 +221,9 @@ public:
         if (mBloom && (!mWholeFrame || mComm))
             throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (bloom takes the whole frame on one GPU: no SetStrip / JoinNode)", __FILE__,
                                    __LINE__);
+        if (mTemporalAA && (!mWholeFrame || mComm))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (temporal anti-aliasing takes the whole frame on one GPU: no SetStrip / JoinNode)",
+                                   __FILE__, __LINE__);
         if (mRunProducerPasses) {
             DrawSceneToShadowMap();                                                                 // :208
             if (mFuseCameraPasses) DrawNormalsDepthAndGBuffer();                                    // :214 + :236 on one rasterisation
@@ -289,18 +294,34 @@ public:
         if (mFog)
             CrychicThrowIfFailed(crychic_fog(md3dDevice->Ctx(), passCB, f.depth_dev, f.shadow_dev, f.shadowDim, f.out_rgba8_dev, f.out_rgba8_dev,
                                              mClientWidth, mClientHeight, 0, mClientHeight, &mFogParams, mCommandList->Stream()));
+        // SetTemporalAA: the finished (and fogged) frame blended into the reprojected history, into its own back buffer, while the
+        // frame is still aligned with its depth plane; the later passes read that buffer
+        const uint8_t* lit = f.out_rgba8_dev;
+        if (mTemporalAA) {
+            crychic_taa_params tp = mTaaParams;
+            if (mTaaReset) tp.flags |= CRYCHIC_TAA_RESET;
+            ID3D12Resource* hin = mTaaHistory[mTaaHistoryIndex].get();
+            ID3D12Resource* hout = mTaaHistory[mTaaHistoryIndex ^ 1].get();
+            CrychicThrowIfFailed(crychic_taa(md3dDevice->Ctx(), passCB, mTaaViewProj[0], mTaaViewProj[1], f.depth_dev, f.out_rgba8_dev,
+                                             mTaaReset ? nullptr : static_cast<const uint16_t*>(hin->Data()), static_cast<uint16_t*>(hout->Data()),
+                                             static_cast<uint8_t*>(mBackBufferTAA->Data()), mClientWidth, mClientHeight, 0, mClientHeight, &tp,
+                                             mCommandList->Stream()));
+            mTaaHistoryIndex ^= 1;
+            mTaaReset = false;
+            lit = static_cast<const uint8_t*>(mBackBufferTAA->Data());
+        }
         // SetDepthOfField: the finished (and fogged) frame through the lens blur into its own back buffer, in front of the anti-aliasing
         if (mDepthOfField)
-            CrychicThrowIfFailed(crychic_dof(md3dDevice->Ctx(), passCB, f.depth_dev, f.out_rgba8_dev, static_cast<uint8_t*>(mBackBufferDoF->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
+            CrychicThrowIfFailed(crychic_dof(md3dDevice->Ctx(), passCB, f.depth_dev, lit, static_cast<uint8_t*>(mBackBufferDoF->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
                                              &mDofParams, mCommandList->Stream()));
         // SetBloom: the frame as it stands (fogged, through the lens blur) with its highlights spread, into its own back buffer
         if (mBloom)
-            CrychicThrowIfFailed(crychic_bloom(md3dDevice->Ctx(), static_cast<const uint8_t*>((mDepthOfField ? mBackBufferDoF : mBackBuffer)->Data()),
+            CrychicThrowIfFailed(crychic_bloom(md3dDevice->Ctx(), mDepthOfField ? static_cast<const uint8_t*>(mBackBufferDoF->Data()) : (mTemporalAA ? lit : static_cast<const uint8_t*>(mBackBuffer->Data())),
                                                static_cast<uint8_t*>(mBackBufferBloom->Data()), mClientWidth, mClientHeight, &mBloomParams,
                                                mBloomWorkspace->Data(), mBloomWorkspace->Bytes(), mCommandList->Stream()));
         // SetAntiAliasing: the finished frame through the post-process pass into the second back buffer, behind the lighting pass
         if (mAntiAliasing)
-            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), static_cast<const uint8_t*>((mBloom ? mBackBufferBloom : (mDepthOfField ? mBackBufferDoF : mBackBuffer))->Data()),
+            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), static_cast<const uint8_t*>((mBloom ? mBackBufferBloom : (mDepthOfField ? mBackBufferDoF : (mTemporalAA ? mBackBufferTAA : mBackBuffer)))->Data()),
                                                    static_cast<uint8_t*>(mBackBufferAA->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
                                                    &mAAParams, mCommandList->Stream()));
         // :300-305: advance the fence and signal it behind this frame's commands
@@ -399,6 +420,27 @@ public:
     }
     bool Bloom() const { return mBloom; }
     ID3D12Resource* BloomBackBuffer() { return mBackBufferBloom.get(); }
+
+    // ---- temporal anti-aliasing (extension) -----------------------------------------------------------------------------------------
+    // Jittered frames blended into a reprojected history (include/crychic_hip.h crychic_taa).  On: Update shifts the projection of the
+    // main pass and SSAO constants by the frame's sub-pixel offset (crychic_taa_jitter of a running frame index) and keeps the
+    // unjittered ViewProj of this frame and of the previous one; Draw issues the pass after the lighting pass of a whole frame and
+    // the fog, from the back buffer into a buffer of its own that the depth of field, the bloom and the anti-aliasing then read and
+    // Present writes, through two history planes this object owns and swaps.  The first frame after it was turned on, and after
+    // OnResize, is a reset frame.  CurrentBackBuffer stays the jittered frame without the pass.  With it on, SetStrip / JoinNode
+    // make Draw throw (the pass is not sharded).  Off (the default): nothing changes.
+    void SetTemporalAA(bool on)
+    {
+        crychic_taa_params q;
+        CrychicThrowIfFailed(crychic_taa_default_params(&q));
+        SetTemporalAA(on, q);
+    }
+    void SetTemporalAA(const crychic_taa_params& p) { SetTemporalAA(true, p); }
+    bool TemporalAA() const { return mTemporalAA; }
+    ID3D12Resource* TemporalAABackBuffer() { return mBackBufferTAA.get(); }
+    ID3D12Resource* TemporalAAHistory() { return mTaaHistory[mTaaHistoryIndex].get(); }     // the history the last Draw wrote
+    const float* TemporalAAViewProj(int previous) const { return mTaaViewProj[previous ? 1 : 0]; }   // unjittered, of the last Update
+    const float* TemporalAAJitter() const { return mTaaJitter; }                            // the last Update's offset in pixels
 
     // ---- deferred decals (extension) ------------------------------------------------------------------------------------------------
     // Oriented boxes that blend textures into the G-buffer between the producer passes and the lighting pass (include/crychic_hip.h
@@ -654,7 +696,7 @@ public:
     void Present(const std::string& path)
     {
         std::vector<uint8_t> host((size_t)mClientWidth * mClientHeight * 4);
-        (mAntiAliasing ? mBackBufferAA : (mBloom ? mBackBufferBloom : (mDepthOfField ? mBackBufferDoF : mBackBuffer)))->Download(host.data(), host.size(), mCommandList->Stream());
+        (mAntiAliasing ? mBackBufferAA : (mBloom ? mBackBufferBloom : (mDepthOfField ? mBackBufferDoF : (mTemporalAA ? mBackBufferTAA : mBackBuffer))))->Download(host.data(), host.size(), mCommandList->Stream());
         mCommandList->Flush();
         CrychicThrowIfFailed(crychic_save_ppm(path.c_str(), host.data(), mClientWidth, mClientHeight));
     }
@@ -1094,6 +1136,14 @@ private:
         for (int i = 0; i < 3; ++i) { dirs[i][0] = mRotatedLightDirections[i].x; dirs[i][1] = mRotatedLightDirections[i].y; dirs[i][2] = mRotatedLightDirections[i].z; }
         CrychicThrowIfFailed(crychic_update_main_pass_cb(&mCamera.Raw(), mClientWidth, mClientHeight, st, dirs,
                                                          reinterpret_cast<crychic_pass_constants*>(&mMainPassCB)));
+        if (mTemporalAA) {
+            // the unjittered ViewProj built above becomes this frame's, what was this frame's the previous one's (its own on a reset
+            // frame); then the constants again with the projection shifted by the frame's jitter
+            std::memcpy(mTaaViewProj[1], mTaaReset ? reinterpret_cast<const float*>(&mMainPassCB.ViewProj) : mTaaViewProj[0], 64);
+            std::memcpy(mTaaViewProj[0], &mMainPassCB.ViewProj, 64);
+            CrychicThrowIfFailed(crychic_update_main_pass_cb_jittered(&mCamera.Raw(), mClientWidth, mClientHeight, st, dirs, mTaaJitter[0], mTaaJitter[1],
+                                                                      reinterpret_cast<crychic_pass_constants*>(&mMainPassCB)));
+        }
         const CRYCHIC& L = mOwner ? *mOwner : *this;                                                // a capture's probe: its owner's spot shadows
         for (uint32_t k = 0; k < L.mSpotShadowCount; ++k)                                           // slots 4..11, transposed like :826-830
             for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) mMainPassCB.ShadowTransforms[4 + k].m[c][r] = L.mShadowTransforms[4 + k].m[r][c];
@@ -1108,7 +1158,11 @@ private:
         mSsao->GetOffsetVectors(off);                                                               // :920
         float o[14][4];
         for (int i = 0; i < 14; ++i) { o[i][0] = off[i].x; o[i][1] = off[i].y; o[i][2] = off[i].z; o[i][3] = off[i].w; }
-        CrychicThrowIfFailed(crychic_update_ssao_cb(&mCamera.Raw(), mClientWidth, mClientHeight, o, reinterpret_cast<crychic_ssao_constants*>(&ssaoCB)));
+        if (mTemporalAA)
+            CrychicThrowIfFailed(crychic_update_ssao_cb_jittered(&mCamera.Raw(), mClientWidth, mClientHeight, o, mTaaJitter[0], mTaaJitter[1],
+                                                                 reinterpret_cast<crychic_ssao_constants*>(&ssaoCB)));
+        else
+            CrychicThrowIfFailed(crychic_update_ssao_cb(&mCamera.Raw(), mClientWidth, mClientHeight, o, reinterpret_cast<crychic_ssao_constants*>(&ssaoCB)));
         mCurrFrameResource->SsaoCB->CopyData(0, ssaoCB);                                            // :935-936
     }
 
@@ -1149,6 +1203,35 @@ private:
         mBackBufferBloom = std::make_unique<ID3D12Resource>((size_t)mClientWidth * mClientHeight * 4, ID3D12Resource::DEFAULT_HEAP);
         mBloomWorkspace = std::make_unique<ID3D12Resource>(crychic_bloom_workspace_bytes(mClientWidth, mClientHeight, CRYCHIC_BLOOM_MAX_LEVELS),
                                                            ID3D12Resource::DEFAULT_HEAP);
+    }
+    bool mTemporalAA = false;                 // SetTemporalAA
+    crychic_taa_params mTaaParams = {};
+    std::unique_ptr<ID3D12Resource> mBackBufferTAA;    // the resolved frame, while mTemporalAA
+    std::unique_ptr<ID3D12Resource> mTaaHistory[2];    // the history planes: [mTaaHistoryIndex] is read by the next Draw, the other written
+    int mTaaHistoryIndex = 0;
+    bool mTaaReset = true;                    // the next frame does not read the history
+    uint32_t mTaaFrameIndex = 0;              // the jitter sequence's running index
+    float mTaaJitter[2] = { 0.0f, 0.0f };     // this frame's offset in pixels
+    float mTaaViewProj[2][16] = {};           // the unjittered ViewProj of this frame and of the previous one (stored transposed)
+    void AllocateTemporalAA()
+    {
+        const size_t n = (size_t)mClientWidth * mClientHeight;
+        mBackBufferTAA = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
+        for (auto& h : mTaaHistory) h = std::make_unique<ID3D12Resource>(crychic_taa_history_bytes(mClientWidth, mClientHeight), ID3D12Resource::DEFAULT_HEAP);
+        mTaaHistoryIndex = 0;
+        mTaaReset = true;
+    }
+    void SetTemporalAA(bool on, const crychic_taa_params& q)
+    {
+        if (q.blend == 0u || q.blend > 256u || (q.flags & ~(CRYCHIC_TAA_RESET | CRYCHIC_TAA_NO_CLAMP)) ||
+            (q.reserved[0] | q.reserved[1] | q.reserved[2] | q.reserved[3] | q.reserved[4] | q.reserved[5]))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetTemporalAA (blend 1 .. 256, flags RESET | NO_CLAMP, reserved 0)", __FILE__, __LINE__);
+        mCommandList->Flush();                                  // a frame in flight may still write the buffers released below
+        const bool was = mTemporalAA;
+        mTemporalAA = on;
+        mTaaParams = q;
+        if (on && !was) { AllocateTemporalAA(); mTaaFrameIndex = 0; }
+        if (!on) { mBackBufferTAA.reset(); mTaaHistory[0].reset(); mTaaHistory[1].reset(); }
     }
     bool mAntiAliasing = false;               // SetAntiAliasing
     crychic_aa_params mAAParams = {};

@@ -1158,6 +1158,86 @@ int crychic_bloom(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rg
                   const crychic_bloom_params* params /* NULL = defaults */, void* workspace_dev, size_t workspace_bytes,
                   void* stream);
 
+/* ---- temporal anti-aliasing: jittered frames blended into a reprojected history (extension) ---------------
+ * The camera is shifted by a sub-pixel offset each frame (crychic_taa_jitter, the _jittered constant builders); crychic_taa blends
+ * the finished RGBA8 frame into a history plane that it fetches through the depth plane and the previous frame's view-projection.
+ * A separate call after the lighting pass and the fog and before the depth of field, the bloom and the post-process anti-aliasing:
+ * the frame must still be aligned with its depth plane.  The first pass with state from one frame to the next: the caller owns two
+ * history planes and swaps them.  A build definition: nothing of it is the reference's.  The device, a host build and the checker
+ * (tests/taa_ref) agree bit for bit on both outputs.
+ *
+ * crychic_taa_jitter: sample 1 + index % 16 of the Halton (2, 3) sequence minus 0.5, in pixels, in [-0.5, 0.5).  With i = 1 + index % 16:
+ * *jx = r2(i) - 0.5f, r2 the base-2 radical inverse, a multiple of 1/32: exact.  *jy = (float)n / (float)d - 0.5f with n / d the base-3
+ * radical inverse of i over the denominator d = 3^k of its k digits (3, 9 or 27): one IEEE binary32 division of two exactly
+ * representable integers, then one binary32 subtraction.  Pure host code; CRYCHIC_E_INVALID_ARG for a NULL pointer.
+ * crychic_update_main_pass_cb_jittered / crychic_update_ssao_cb_jittered: the unjittered builders with the projection shifted so that
+ * a world point which the unjittered frame shows at pixel position (x, y) is shown at (x + jx, y + jy), y growing downwards: element
+ * (2, 0) of the row-vector projection becomes 0.0f + 2.0f * jx / (float)W and element (2, 1) becomes 0.0f + (-2.0f * jy) / (float)H; Proj,
+ * InvProj, ViewProj, InvViewProj and ViewProjTex (ProjTex for the SSAO constants) are built from the shifted matrix by the builder's
+ * own code.  jx == jy == 0 gives structures byte-identical to the unjittered builders'.  A non-finite offset: CRYCHIC_E_INVALID_ARG.
+ *
+ * The pass.  Float operations are IEEE binary32, each rounded once, in the order written; the named primitives are those of
+ * crychic_fog above (d24_to_float, mulcol, mulcol1, rcp).  curViewProj and prevViewProj are the UNJITTERED view-projections of this
+ * frame and the previous one, stored transposed like cb's matrices; cb is the frame's own (jittered) constants, of which InvViewProj
+ * is read.  A history plane is W x H texels of four uint16_t (R, G, B, A), 8.8 fixed point: crychic_taa_history_bytes = W H 8.
+ * Host-side constants, once per call:  sx = 2.0f / (float)W;  sy = 2.0f / (float)H;  hw = 0.5f * (float)W;  hh = 0.5f * (float)H;
+ * xmax = (float)((W - 1) 256);  ymax = (float)((H - 1) 256)  (exact: W and H are at most 2^22).
+ * Per pixel (px, py), with c[k], k = R, G, B, A, the four bytes of the current texel in[py W + px]:
+ *   1  lo[k] = 256 min, hi[k] = 256 max of channel k = R, G, B over the 3 x 3 texels of `in` at (clamp(px + i, 0, W - 1),
+ *      clamp(py + j, 0, H - 1)), i, j = -1 .. 1: clamped to the frame, not to the row range.
+ *   2  d = d24_to_float(depth[py W + px]);  nx = fma((float)px + 0.5f, sx, -1.0f);  ny = fma((float)py + 0.5f, -sy, 1.0f);
+ *      h[c] = mulcol(nx, ny, d, 1.0f, cb->InvViewProj + 4c), c = 0 .. 3;  rw = rcp(h[3]);  P = (h[0] rw, h[1] rw, h[2] rw).  A sky texel
+ *      is no special case.
+ *   3  a[c] = mulcol1(P, curViewProj + 4c), b[c] = mulcol1(P, prevViewProj + 4c), c = 0, 1, 3;  ra = rcp(a[3]);  rb = rcp(b[3]);
+ *      vx = (a[0] ra - b[0] rb) hw;  vy = (b[1] rb - a[1] ra) hh  (two products, one difference, one product: four roundings each).
+ *      Bitwise-equal matrices give a velocity of exactly +0 or NaN.
+ *   4  fxp = ((float)px - vx) 256.0f;  fyp = ((float)py - vy) 256.0f.  The pixel HAS HISTORY iff CRYCHIC_TAA_RESET is clear and
+ *      b[3] > 0 and fxp >= 0 and fxp <= xmax and fyp >= 0 and fyp <= ymax (every comparison false for NaN).  Then X = (int)floorf(fxp),
+ *      xi = X >> 8, fx = X & 255, x1 = min(xi + 1, W - 1), and Y, yi, fy, y1 likewise; with t00 = history_in[yi W + xi], t10 at
+ *      (x1, yi), t01 at (xi, y1), t11 at (x1, y1), per channel k = R, G, B in 32-bit unsigned arithmetic:
+ *      top = t00 (256 - fx) + t10 fx;  bot = t01 (256 - fx) + t11 fx;  hv = (top (256 - fy) + bot fy + 32768) >> 16  (at most
+ *      65535 2^16 + 2^15: it fits for any uint16_t content).
+ *   5  hc[k] = min(max(hv[k], lo[k]), hi[k]); with CRYCHIC_TAA_NO_CLAMP hc[k] = hv[k].
+ *   6  with history n[k] = (hc[k] (256 - blend) + c[k] 256 blend + 128) >> 8 (at most 65535); without, n[k] = 256 c[k].
+ *   7  history_out[py W + px] = (n[R], n[G], n[B], 256 c[A]);  out[py W + px] = (min((n[k] + 128) >> 8, 255) for R, G, B;  c[A]).
+ * Known answers: RESET gives out == in and history_out == 256 in.  blend == 256 gives out == in whatever the history.  Identical
+ * matrices and history_in == 256 in give out == in and history_out == history_in.  A constant frame C over a constant history Hc
+ * with identical matrices and NO_CLAMP: n = (Hc (256 - blend) + 256 C blend + 128) >> 8 in every texel; without NO_CLAMP hc = 256 C
+ * and out == C.
+ *
+ * Parameters (32 bytes): blend, the weight of the current frame in 1/256 (default 26; 1 .. 256); flags (CRYCHIC_TAA_RESET: the history
+ * is not read and history_in_dev may be NULL; CRYCHIC_TAA_NO_CLAMP: step 5 is skipped); reserved (must be 0).
+ * crychic_taa_default_params fills the defaults (pure host code; CRYCHIC_E_INVALID_ARG for NULL).
+ *
+ * crychic_taa writes rows [row0, row0 + rows) of out_rgba8_dev and history_out_dev and no other byte; it reads the texels of
+ * in_rgba8_dev within one row of that range, the range's rows of depth_dev and any texel of history_in_dev.  Stitched row ranges
+ * therefore equal the whole-frame call byte for byte in both outputs, for any split; rows == 0 launches nothing.  params == NULL = the
+ * defaults.  One launch on `stream`: no allocation, no synchronisation, no host read-back; capturable into a graph.
+ * CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and before anything is enqueued: a NULL plane (history_in_dev
+ * only without RESET), cb or matrix; an RGBA8 or depth plane that is not 4-byte aligned or a history plane that is not 8-byte
+ * aligned; W or H of 0; a row range outside the frame; a non-finite entry in cb->InvViewProj, curViewProj or prevViewProj; blend
+ * outside 1 .. 256, an unknown flag bit or a non-zero reserved word; out overlapping in (the pass reads neighbours); history_out
+ * overlapping history_in; a history plane overlapping in, out or depth.  More than 2^28 pixels, or W or H above 2^22 (the history
+ * position in 1/256 texel is a 32-bit integer): CRYCHIC_E_UNSUPPORTED. */
+#define CRYCHIC_TAA_RESET 1u
+#define CRYCHIC_TAA_NO_CLAMP 2u
+typedef struct crychic_taa_params {
+    uint32_t blend;
+    uint32_t flags;
+    uint32_t reserved[6];
+} crychic_taa_params;   /* 32 bytes */
+int crychic_taa_jitter(uint32_t index, float* jx, float* jy);
+int crychic_update_main_pass_cb_jittered(const crychic_camera* cam, uint32_t W, uint32_t H, const float shadowTransform[4][16],
+                                         const float lightDirs[3][3], float jx, float jy, crychic_pass_constants* out);
+int crychic_update_ssao_cb_jittered(const crychic_camera* cam, uint32_t W, uint32_t H, const float offsets[14][4], float jx, float jy,
+                                    crychic_ssao_constants* out);
+int crychic_taa_default_params(crychic_taa_params* out);
+size_t crychic_taa_history_bytes(uint32_t W, uint32_t H);
+int crychic_taa(crychic_ctx* ctx, const crychic_pass_constants* cb, const float curViewProj[16], const float prevViewProj[16],
+                const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, const uint16_t* history_in_dev, uint16_t* history_out_dev,
+                uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                const crychic_taa_params* params /* NULL = defaults */, void* stream);
+
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
  * of 2 rows (half-res alignment); the last rank takes the remainder. */
