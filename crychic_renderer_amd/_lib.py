@@ -193,6 +193,21 @@ class TaaParams(C.Structure):
         return p
 
 
+class MotionBlurParams(C.Structure):
+    """crychic_motion_blur_params: the knobs of crychic_motion_blur (extension); MotionBlurParams.default() =
+    crychic_motion_blur_default_params, any field replaced by its keyword."""
+    _fields_ = [("shutter", C.c_uint32), ("samples", C.c_uint32), ("maxRadius", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+    @classmethod
+    def default(cls, shutter=None, samples=None, maxRadius=None, flags=None):
+        p = cls()
+        check(lib.crychic_motion_blur_default_params(C.byref(p)))
+        for name, v in (("shutter", shutter), ("samples", samples), ("maxRadius", maxRadius), ("flags", flags)):
+            if v is not None:
+                setattr(p, name, int(v))
+        return p
+
+
 class PassTimes(C.Structure):
     _fields_ = [("ssao_ms", C.c_float), ("blur_ms", C.c_float), ("light_ms", C.c_float), ("total_ms", C.c_float)]
 
@@ -304,6 +319,12 @@ PROTOTYPES = {
     "crychic_update_ssao_cb_jittered": (_i, [_P(Camera), _u32, _u32, _vp, _f, _f, _P(SsaoConstants)]),
     "crychic_taa_default_params": (_i, [_P(TaaParams)]),
     "crychic_taa_history_bytes": (_sz, [_u32, _u32]),
+    "crychic_motion_blur_default_params": (_i, [_P(MotionBlurParams)]),
+    "crychic_motion_blur_workspace_bytes": (_sz, [_u32, _u32]),
+    "crychic_motion_blur_tile_offset": (_sz, [_u32, _u32]),
+    "crychic_motion_blur_velocity": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _u32, _u32, _P(MotionBlurParams), _vp, _sz, _vp]),
+    "crychic_motion_blur_gather": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(MotionBlurParams), _vp, _sz, _vp]),
+    "crychic_motion_blur": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _u32, _u32, _P(MotionBlurParams), _vp, _sz, _vp]),
     "crychic_taa": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(TaaParams), _vp]),
     "crychic_save_ppm":(_i, [C.c_char_p, _vp, _u32, _u32]),
     "crychic_raster_workspace_bytes": (_sz, [C.c_uint64, _u32, _u32]),

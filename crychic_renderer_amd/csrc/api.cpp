@@ -24,6 +24,7 @@
 #include "dof_core.hpp"
 #include "bloom_core.hpp"
 #include "taa_core.hpp"
+#include "motion_blur_core.hpp"
 #include "decal_core.hpp"
 #include "internal.hpp"
 
@@ -1185,6 +1186,96 @@ int crychic_taa(crychic_ctx* ctx, const crychic_pass_constants* cb, const float 
     std::memcpy(&q, &p, sizeof q);
     CRY_HIP(cry::launch_taa(cb->InvViewProj, curViewProj, prevViewProj, depth_dev, in_rgba8_dev, reset ? nullptr : history_in_dev, history_out_dev,
                             out_rgba8_dev, W, H, row0, rows, q, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(sizeof(crychic_motion_blur_params) == 32 && sizeof(crychic_motion_blur_params) == sizeof(cry::MotionBlurParams), "motion_blur_core.hpp mirrors the ABI");
+
+int crychic_motion_blur_default_params(crychic_motion_blur_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    *out = crychic_motion_blur_params{};
+    out->shutter = 128u; out->samples = 8u; out->maxRadius = 16u;
+    return 0;
+}
+
+size_t crychic_motion_blur_workspace_bytes(uint32_t W, uint32_t H) { return cry::mb_workspace_bytes(W, H); }
+size_t crychic_motion_blur_tile_offset(uint32_t W, uint32_t H) { return cry::mb_tile_offset(W, H); }
+
+namespace {
+
+// What the three motion blur entries check alike, before the context is looked at.  The velocity entry has no frame planes (`frame`
+// false: in and out are not looked at), the gather entry no depth plane and no matrices (`reproject` false).  Fills `q` with the
+// parameters in force.
+int motion_blur_check(bool reproject, bool frame, const crychic_pass_constants* cb, const float* cur, const float* prev, const uint32_t* depth,
+                      const uint8_t* in, const uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const crychic_motion_blur_params* params,
+                      const void* workspace, size_t workspaceBytes, cry::MotionBlurParams& q)
+{
+    crychic_motion_blur_params p;
+    crychic_motion_blur_default_params(&p);
+    if (params) p = *params;
+    if (p.shutter > 256u) return fail(CRYCHIC_E_INVALID_ARG, "motion blur shutter %u outside 0 .. 256", p.shutter);
+    if (p.samples < 2u || p.samples > 32u || (p.samples & (p.samples - 1u))) return fail(CRYCHIC_E_INVALID_ARG, "motion blur samples %u: not 2, 4, 8, 16 or 32", p.samples);
+    if (p.maxRadius == 0u || p.maxRadius > 32u) return fail(CRYCHIC_E_INVALID_ARG, "motion blur maxRadius %u outside 1 .. 32", p.maxRadius);
+    if (p.flags) return fail(CRYCHIC_E_INVALID_ARG, "motion blur flags 0x%x: must be 0", p.flags);
+    for (uint32_t r : p.reserved)
+        if (r) return fail(CRYCHIC_E_INVALID_ARG, "motion blur reserved words must be 0");
+    if (!workspace || (reproject && (!cb || !cur || !prev || !depth)) || (frame && (!in || !out))) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    const uintptr_t z = reproject ? reinterpret_cast<uintptr_t>(depth) : 0u, s = frame ? reinterpret_cast<uintptr_t>(in) : 0u;
+    const uintptr_t d = frame ? reinterpret_cast<uintptr_t>(out) : 0u, w = reinterpret_cast<uintptr_t>(workspace);
+    if ((z | s | d) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "motion blur planes are not 4-byte aligned");
+    if (w & 7u) return fail(CRYCHIC_E_INVALID_ARG, "the motion blur workspace is not 8-byte aligned");
+    if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
+    if (int rc = check_extent("frame", W, H, false, 0u)) return rc;                   // one-dimensional grids, at most 2^20 workgroups
+    if (W > cry::kMbMaxSide || H > cry::kMbMaxSide) return fail(CRYCHIC_E_UNSUPPORTED, "frame %ux%u: motion blur takes at most 2^22 texels a side", W, H);
+    if (int rc = check_rows(kFrameRows, row0, rows, H)) return rc;
+    const size_t need = crychic_motion_blur_workspace_bytes(W, H), bytes = (size_t)W * H * 4u;
+    if (workspaceBytes < need) return fail(CRYCHIC_E_INVALID_ARG, "the motion blur workspace has %zu bytes, %ux%u needs %zu", workspaceBytes, W, H, need);
+    if (frame && ranges_overlap(s, bytes, d, bytes))
+        return fail(CRYCHIC_E_INVALID_ARG, "the motion blur input and output planes overlap (the pass gathers: it cannot run in place)");
+    if ((reproject && ranges_overlap(w, need, z, bytes)) || (frame && (ranges_overlap(w, need, s, bytes) || ranges_overlap(w, need, d, bytes))))
+        return fail(CRYCHIC_E_INVALID_ARG, "the motion blur workspace overlaps a plane");
+    std::memcpy(&q, &p, sizeof q);
+    return 0;
+}
+
+}  // namespace
+
+int crychic_motion_blur_velocity(crychic_ctx* ctx, const crychic_pass_constants* cb, const float curViewProj[16], const float prevViewProj[16],
+                                 const uint32_t* depth_dev, uint32_t W, uint32_t H, const crychic_motion_blur_params* params, void* workspace_dev,
+                                 size_t workspace_bytes, void* stream)
+{
+    cry::MotionBlurParams q;
+    if (int rc = motion_blur_check(true, false, cb, curViewProj, prevViewProj, depth_dev, nullptr, nullptr, W, H, 0u, H, params, workspace_dev, workspace_bytes, q))
+        return rc;
+    if (int rc = bind(ctx)) return rc;
+    CRY_HIP(cry::launch_motion_blur_velocity(cb->InvViewProj, curViewProj, prevViewProj, depth_dev, W, H, q, workspace_dev, (hipStream_t)stream));
+    return 0;
+}
+
+int crychic_motion_blur_gather(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                               const crychic_motion_blur_params* params, const void* workspace_dev, size_t workspace_bytes, void* stream)
+{
+    cry::MotionBlurParams q;
+    if (int rc = motion_blur_check(false, true, nullptr, nullptr, nullptr, nullptr, in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, params, workspace_dev,
+                                   workspace_bytes, q))
+        return rc;
+    if (int rc = bind(ctx)) return rc;
+    CRY_HIP(cry::launch_motion_blur_gather(in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, q, workspace_dev, (hipStream_t)stream));
+    return 0;
+}
+
+int crychic_motion_blur(crychic_ctx* ctx, const crychic_pass_constants* cb, const float curViewProj[16], const float prevViewProj[16], const uint32_t* depth_dev,
+                        const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, const crychic_motion_blur_params* params,
+                        void* workspace_dev, size_t workspace_bytes, void* stream)
+{
+    cry::MotionBlurParams q;
+    if (int rc = motion_blur_check(true, true, cb, curViewProj, prevViewProj, depth_dev, in_rgba8_dev, out_rgba8_dev, W, H, 0u, H, params, workspace_dev,
+                                   workspace_bytes, q))
+        return rc;
+    if (int rc = bind(ctx)) return rc;
+    CRY_HIP(cry::launch_motion_blur_velocity(cb->InvViewProj, curViewProj, prevViewProj, depth_dev, W, H, q, workspace_dev, (hipStream_t)stream));
+    CRY_HIP(cry::launch_motion_blur_gather(in_rgba8_dev, out_rgba8_dev, W, H, 0u, H, q, workspace_dev, (hipStream_t)stream));
     return 0;
 }
 

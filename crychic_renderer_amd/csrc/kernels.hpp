@@ -133,6 +133,16 @@ hipError_t launch_taa(const float* invViewProj, const float* curViewProj, const 
                       const uint16_t* historyIn, uint16_t* historyOut, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
                       const TaaParams& p, hipStream_t stream);
 
+// motion_blur.hip: launch_motion_blur_velocity fills the velocity plane and the tile plane of `workspace` for the whole W x H frame
+// from the D24 plane `depth` (motion_blur_core.hpp); the three matrices are read before the call returns.  launch_motion_blur_gather
+// writes rows [row0, row0 + rows) of `out` from `in` and the workspace: none for rows == 0.  One launch each on `stream`.  The caller
+// has checked the pointers, their alignment and overlap, the sizes, the rows, the workspace's size and `p`.
+struct MotionBlurParams;
+hipError_t launch_motion_blur_velocity(const float* invViewProj, const float* curViewProj, const float* prevViewProj, const uint32_t* depth, uint32_t W,
+                                       uint32_t H, const MotionBlurParams& p, void* workspace, hipStream_t stream);
+hipError_t launch_motion_blur_gather(const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const MotionBlurParams& p,
+                                     const void* workspace, hipStream_t stream);
+
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
 struct Texture;

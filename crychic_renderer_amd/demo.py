@@ -5,6 +5,7 @@
                                    [--dof [--dof-focus X] [--dof-aperture X] [--dof-radius N]]
                                    [--bloom [--bloom-threshold N] [--bloom-intensity N] [--bloom-levels N]]
                                    [--taa [--taa-frames N]]
+                                   [--motion-blur [--motion-blur-shutter N] [--motion-blur-samples N] [--motion-blur-pan DX]]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
@@ -38,6 +39,10 @@ most 1024) and --bloom-levels (default 6, at most 8) set its parameters.
 --taa: temporal anti-aliasing (Crychic.temporalAA: crychic_taa after the lighting pass and the fog, in front of --dof, --bloom and
 --aa): --taa-frames frames (default 16) of the still scene are rendered, each with the projection shifted by its sub-pixel jitter
 (crychic_taa_jitter), and blended into the history; the resolved frame of the last one is what the later stages read.
+--motion-blur: camera-motion blur (Crychic.motionBlur: crychic_motion_blur behind --dof, in front of --bloom and --aa): the frame is
+drawn as if the camera had stood --motion-blur-pan world units (default 0.5) further along +x one frame earlier, and blurred along the
+velocity that gives each pixel through its depth; --motion-blur-shutter (exposure in 1/256 of the frame interval, default 128, at
+most 256) and --motion-blur-samples (2, 4, 8, 16 or 32, default 8) set its parameters.  With --taa the last frame is the one that moved.
 --decals: deferred decals between the G-buffer pass and the lighting pass (Crychic.set_decals / apply_decals: crychic_apply_decals): a
 glossy puddle with a dent normal map on the floor and a painted ring on the face of a box."""
 import argparse
@@ -82,7 +87,14 @@ def main():
     ap.add_argument("--bloom-levels", type=int, default=None, metavar="N", help="pyramid levels, 1 .. 8 (default 6; needs --bloom)")
     ap.add_argument("--taa", action="store_true", help="temporal anti-aliasing: jittered frames of the still scene blended into a history")
     ap.add_argument("--taa-frames", type=int, default=None, metavar="N", help="jittered frames to render (default 16; needs --taa)")
+    ap.add_argument("--motion-blur", action="store_true", help="camera-motion blur, behind the depth of field and in front of the bloom")
+    ap.add_argument("--motion-blur-shutter", type=int, default=None, metavar="N", help="exposure in 1/256 of the frame interval, 0 .. 256 (default 128; needs --motion-blur)")
+    ap.add_argument("--motion-blur-samples", type=int, default=None, metavar="N", help="samples along the velocity: 2, 4, 8, 16 or 32 (default 8; needs --motion-blur)")
+    ap.add_argument("--motion-blur-pan", type=float, default=None, metavar="DX", help="the previous camera's displacement along +x in world units (default 0.5; "
+                                                                                      "needs --motion-blur)")
     a = ap.parse_args()
+    if (a.motion_blur_shutter is not None or a.motion_blur_samples is not None or a.motion_blur_pan is not None) and not a.motion_blur:
+        ap.error("--motion-blur-shutter, --motion-blur-samples and --motion-blur-pan need --motion-blur")
     if a.taa_frames is not None and not (a.taa and a.taa_frames >= 1):
         ap.error("--taa-frames takes a positive count and needs --taa")
     if (a.bloom_threshold is not None or a.bloom_intensity is not None or a.bloom_levels is not None) and not a.bloom:
@@ -108,7 +120,7 @@ def main():
     W, H = (int(v) for v in a.size.lower().split("x"))
     import torch
     from . import Context, Crychic, LIGHT_SKY, SceneGeometry, check, geometry as g, lib, scene
-    from ._lib import BloomParams, DofParams, FogParams, PassConstants
+    from ._lib import BloomParams, DofParams, FogParams, MotionBlurParams, PassConstants
     ctx = Context(0)
     consts = scene.Constants(W, H, a.shadow_dim)
     tex = g.reference_textures(a.textures) if a.textures else g.procedural_textures(64)
@@ -177,24 +189,36 @@ def main():
         app.bloom = BloomParams.default(threshold=a.bloom_threshold, intensity=a.bloom_intensity, levels=a.bloom_levels)
     if a.aa:
         app.antiAliasing = True
+    prev_view_proj = None
+    if a.motion_blur:
+        app.motionBlur = MotionBlurParams.default(shutter=a.motion_blur_shutter, samples=a.motion_blur_samples)
+        before = scene.default_camera(W, H)
+        before.pos[0] += 0.5 if a.motion_blur_pan is None else a.motion_blur_pan
+        prev_view_proj = scene.Constants(W, H, a.shadow_dim, cam=before).pass_cb.ViewProj
     if a.taa:
         # the still scene under the jitter sequence: the camera planes are rasterised again with each frame's shifted projection, the
         # pass gets the unjittered ViewProj of the same camera for this frame and the previous one
         app.temporalAA = True
         jx, jy = C.c_float(), C.c_float()
-        for k in range(a.taa_frames or 16):
+        frames = a.taa_frames or 16
+        for k in range(frames):
             check(lib.crychic_taa_jitter(k, C.byref(jx), C.byref(jy)))
             jittered = scene.Constants(W, H, a.shadow_dim, jitter=(jx.value, jy.value))
             app.mMainPassCB, app.mSsaoCB = jittered.pass_cb, jittered.ssao_cb
             camera_passes()
+            if prev_view_proj is not None and k == frames - 1:
+                app.set_frame_view_proj(prev_view_proj)
             app.set_frame_view_proj(consts.pass_cb.ViewProj)
             app.Draw()
     else:
+        if prev_view_proj is not None:
+            app.set_frame_view_proj(prev_view_proj)
+            app.set_frame_view_proj(consts.pass_cb.ViewProj)
         app.Draw()
     torch.cuda.synchronize()
-    img = np.ascontiguousarray((app.mBackBufferAA if a.aa else (app.mBackBufferBloom if a.bloom else (app.mBackBufferDoF if a.dof else (app.mBackBufferTAA if a.taa else app.mBackBuffer)))).cpu().numpy())
+    img = np.ascontiguousarray((app.mBackBufferAA if a.aa else (app.mBackBufferBloom if a.bloom else (app.mBackBufferMB if a.motion_blur else (app.mBackBufferDoF if a.dof else (app.mBackBufferTAA if a.taa else app.mBackBuffer))))).cpu().numpy())
     check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, W, H))
-    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, (", fog" if a.fog else "") + (", temporal anti-aliasing" if a.taa else "") + (", depth of field" if a.dof else "") + (", bloom" if a.bloom else "") + (", anti-aliased" if a.aa else ""), ctx.device_name))
+    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, (", fog" if a.fog else "") + (", temporal anti-aliasing" if a.taa else "") + (", depth of field" if a.dof else "") + (", motion blur" if a.motion_blur else "") + (", bloom" if a.bloom else "") + (", anti-aliased" if a.aa else ""), ctx.device_name))
 
 
 if __name__ == "__main__":

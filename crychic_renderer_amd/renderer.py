@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (AAParams, CrychicError, FogParams, DofParams, BloomParams, TaaParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, FogParams, DofParams, BloomParams, TaaParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -236,6 +236,9 @@ class Crychic:
         self.mTaaHistory = None      # [history read by the next call, history it writes]: (H, W, 4) int16 planes of 8.8 fixed point, swapped after each call
         self._taaReset = True        # the next Draw() with temporalAA set is a RESET frame: the first, or the first after the switch was turned on
         self._taaViewProj = [None, None]     # set_frame_view_proj: the unjittered ViewProj of this frame and of the previous one
+        self._motionBlur = None      # motionBlur, extension: None | True | MotionBlurParams -- Draw() of a whole frame runs crychic_motion_blur into mBackBufferMB
+        self.mBackBufferMB = None    # the frame behind the motion blur, allocated by the first motion_blur() that needs it
+        self.mMotionBlurWorkspace = None     # the velocity and tile planes: crychic_motion_blur_workspace_bytes of the frame, with the first motion_blur()
         self.mDecals, self.mDecalCount = None, 0                             # set_decals, extension: the device array of Decal structs
         self._decalTextures, self._decalTextureCount, self._decalKeep = None, 0, []     # the host texture table and the chains it points into
 
@@ -247,7 +250,7 @@ class Crychic:
             if name == "_temporalAA" and value and not self._temporalAA:
                 self._taaReset = True            # turned on: whatever the history planes hold is stale
             setattr(self, name, value)
-            self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA)
+            self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA or self._motionBlur)
         return property(get, put)
 
     antiAliasing = _post_switch("_antiAliasing")
@@ -255,6 +258,7 @@ class Crychic:
     depthOfField = _post_switch("_depthOfField")
     bloom = _post_switch("_bloom")
     temporalAA = _post_switch("_temporalAA")
+    motionBlur = _post_switch("_motionBlur")
     del _post_switch
 
     def set_gbuffer_formats(self, formats):
@@ -328,10 +332,16 @@ class Crychic:
         mBackBufferTAA with the matrices of set_frame_view_proj; the depth of field, the bloom and the anti-aliasing, as set, then
         read mBackBufferTAA.  The order is lighting, fog, temporal anti-aliasing, depth of field, bloom, anti-aliasing: the temporal
         pass needs the frame still aligned with its depth plane.  The first such frame, and the first after the switch was turned on
-        or the frame's size changed, is a RESET frame.  A strip or a shared draw then raises CrychicError."""
+        or the frame's size changed, is a RESET frame.  A strip or a shared draw then raises CrychicError.
+        motionBlur = True or a MotionBlurParams (extension): a whole frame (fog, temporal anti-aliasing and depth of field as set),
+        then crychic_motion_blur from that frame into mBackBufferMB with the matrices of set_frame_view_proj (never called: a still
+        camera); the bloom and the anti-aliasing, as set, then read mBackBufferMB.  A strip or a shared draw then raises
+        CrychicError."""
         if self._post:
             if self._bloom:
                 return self._draw_with_bloom(row0, rows, shared)
+            if self._motionBlur:
+                return self._draw_with_motion_blur(row0, rows, shared)
             if self._depthOfField:
                 return self._draw_with_depth_of_field(row0, rows, shared)
             if self._temporalAA:
@@ -434,9 +444,60 @@ class Crychic:
             self.Draw()
         finally:
             self.bloom, self.antiAliasing = bloom, aa
-        self.apply_bloom(src=self.mBackBufferDoF if self._depthOfField else (self.mBackBufferTAA if self._temporalAA else self.mBackBuffer), params=bloom if isinstance(bloom, BloomParams) else None)
+        self.apply_bloom(src=self.mBackBufferMB if self._motionBlur else self._frame_behind_dof(), params=bloom if isinstance(bloom, BloomParams) else None)
         if aa:
             self.antialias(src=self.mBackBufferBloom, params=aa if isinstance(aa, AAParams) else None)
+
+    def _frame_behind_dof(self):
+        """The frame the passes behind the depth of field read: mBackBufferDoF, else mBackBufferTAA, else mBackBuffer."""
+        return self.mBackBufferDoF if self._depthOfField else (self.mBackBufferTAA if self._temporalAA else self.mBackBuffer)
+
+    def _draw_with_motion_blur(self, row0, rows, shared):
+        """Draw() with motionBlur set: the frame as Draw() issues it without (fog, temporal anti-aliasing and depth of field as they
+        are set), the motion blur from that frame into mBackBufferMB, then the anti-aliasing of mBackBufferMB if that is set."""
+        self._whole_frame_only("motionBlur", row0, rows, shared)
+        mb, aa, self.motionBlur, self.antiAliasing = self.motionBlur, self.antiAliasing, None, None
+        try:
+            self.Draw()
+        finally:
+            self.motionBlur, self.antiAliasing = mb, aa
+        cur, prev = self._taaViewProj
+        if cur is None:                         # set_frame_view_proj was never called: the camera counts as still
+            cur = prev = tuple(self.mMainPassCB.ViewProj)
+        self.motion_blur(cur, cur if prev is None else prev, src=self._frame_behind_dof(), params=mb if isinstance(mb, MotionBlurParams) else None)
+        if aa:
+            self.antialias(src=self.mBackBufferMB, params=aa if isinstance(aa, AAParams) else None)
+
+    def motion_blur(self, cur_view_proj, prev_view_proj, src=None, out=None, row0=0, rows=None, params=None):
+        """crychic_motion_blur on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferMB, allocated on first
+        use) from `src` (default: mBackBuffer), both (H, W, 4) uint8 tensors of the frame's size, with this frame's depth plane and
+        pass constants and the two UNJITTERED view-projections (16 floats each, stored transposed).  The velocity and tile planes go
+        through mMotionBlurWorkspace, allocated on first use: the velocity launch always covers the whole frame, the gather the row
+        range.  params: a MotionBlurParams, None = the defaults.  `src` and `out` must not overlap.  Returns `out`."""
+        src = self.mBackBuffer if src is None else src
+        if out is None:
+            if self.mBackBufferMB is None or self.mBackBufferMB.shape != src.shape or self.mBackBufferMB.device != src.device:
+                self.mBackBufferMB = torch.zeros_like(src)
+            out = self.mBackBufferMB
+        H, W = int(src.shape[0]), int(src.shape[1])
+        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
+                or not src.is_contiguous() or not out.is_contiguous() or (H, W) != (self.mClientHeight, self.mClientWidth):
+            raise CrychicError(-1, "motion_blur takes contiguous (H, W, 4) uint8 tensors of the frame's size")
+        need = int(lib.crychic_motion_blur_workspace_bytes(W, H))
+        if self.mMotionBlurWorkspace is None or self.mMotionBlurWorkspace.numel() != need or self.mMotionBlurWorkspace.device != src.device:
+            self.mMotionBlurWorkspace = torch.zeros((need,), dtype=torch.uint8, device=src.device)
+        p = C.byref(params) if params is not None else None
+        cur, prev = (C.c_float * 16)(*cur_view_proj), (C.c_float * 16)(*prev_view_proj)
+        ws, stream = _ptr(self.mMotionBlurWorkspace), _stream(self.ctx.device)
+        if row0 == 0 and (rows is None or rows == H):
+            check(lib.crychic_motion_blur(self.ctx.handle, C.byref(self.mMainPassCB), cur, prev, self.mDepthStencilBuffer.data_ptr(), _ptr(src), _ptr(out),
+                                          W, H, p, ws, need, stream))
+        else:
+            check(lib.crychic_motion_blur_velocity(self.ctx.handle, C.byref(self.mMainPassCB), cur, prev, self.mDepthStencilBuffer.data_ptr(), W, H, p, ws,
+                                                   need, stream))
+            check(lib.crychic_motion_blur_gather(self.ctx.handle, _ptr(src), _ptr(out), W, H, int(row0), int(H - row0 if rows is None else rows), p, ws,
+                                                 need, stream))
+        return out
 
     def _draw_with_temporal_aa(self, row0, rows, shared):
         """Draw() with temporalAA set: the frame as Draw() issues it without (fogged in place if fog is set), the temporal pass from

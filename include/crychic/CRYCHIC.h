@@ -168,6 +168,7 @@ public:
         if (mDepthOfField) mBackBufferDoF = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
         if (mBloom) AllocateBloom();
         if (mTemporalAA) AllocateTemporalAA();                                                      // new history planes: the next frame is a reset frame
+        if (mMotionBlur) AllocateMotionBlur();                                                      // the next frame counts as the first: no previous camera
         mCamera.SetLens(0.25f * 3.1415926535f, AspectRatio(), 1.0f, 100.0f);                       // :114
         if (mSsao) { mSsao->OnResize(mClientWidth, mClientHeight); mSsao->RebuildDescriptors(mDepthStencilBuffer.get()); }
         if (mDeferred) { mDeferred->OnResize(mClientWidth, mClientHeight); mDeferred->BuildDescriptors(); }
@@ -224,6 +225,9 @@ public:
         if (mTemporalAA && (!mWholeFrame || mComm))
             throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (temporal anti-aliasing takes the whole frame on one GPU: no SetStrip / JoinNode)",
                                    __FILE__, __LINE__);
+        if (mMotionBlur && (!mWholeFrame || mComm))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (motion blur takes the whole frame on one GPU: no SetStrip / JoinNode)", __FILE__,
+                                   __LINE__);
         if (mRunProducerPasses) {
             DrawSceneToShadowMap();                                                                 // :208
             if (mFuseCameraPasses) DrawNormalsDepthAndGBuffer();                                    // :214 + :236 on one rasterisation
@@ -314,14 +318,21 @@ public:
         if (mDepthOfField)
             CrychicThrowIfFailed(crychic_dof(md3dDevice->Ctx(), passCB, f.depth_dev, lit, static_cast<uint8_t*>(mBackBufferDoF->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
                                              &mDofParams, mCommandList->Stream()));
-        // SetBloom: the frame as it stands (fogged, through the lens blur) with its highlights spread, into its own back buffer
+        // SetMotionBlur: the frame as it stands blurred along the camera's motion since the previous Update, into its own back buffer
+        if (mMotionBlur) {
+            CrychicThrowIfFailed(crychic_motion_blur(md3dDevice->Ctx(), passCB, mMbViewProj[0], mMbViewProj[1], f.depth_dev,
+                                                     mDepthOfField ? static_cast<const uint8_t*>(mBackBufferDoF->Data()) : lit,
+                                                     static_cast<uint8_t*>(mBackBufferMB->Data()), mClientWidth, mClientHeight, &mMbParams,
+                                                     mMbWorkspace->Data(), mMbWorkspace->Bytes(), mCommandList->Stream()));
+        }
+        // SetBloom: the frame as it stands (fogged, through the lens blur and the motion blur) with its highlights spread, into its own back buffer
         if (mBloom)
-            CrychicThrowIfFailed(crychic_bloom(md3dDevice->Ctx(), mDepthOfField ? static_cast<const uint8_t*>(mBackBufferDoF->Data()) : (mTemporalAA ? lit : static_cast<const uint8_t*>(mBackBuffer->Data())),
+            CrychicThrowIfFailed(crychic_bloom(md3dDevice->Ctx(), mMotionBlur ? static_cast<const uint8_t*>(mBackBufferMB->Data()) : (mDepthOfField ? static_cast<const uint8_t*>(mBackBufferDoF->Data()) : (mTemporalAA ? lit : static_cast<const uint8_t*>(mBackBuffer->Data()))),
                                                static_cast<uint8_t*>(mBackBufferBloom->Data()), mClientWidth, mClientHeight, &mBloomParams,
                                                mBloomWorkspace->Data(), mBloomWorkspace->Bytes(), mCommandList->Stream()));
         // SetAntiAliasing: the finished frame through the post-process pass into the second back buffer, behind the lighting pass
         if (mAntiAliasing)
-            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), static_cast<const uint8_t*>((mBloom ? mBackBufferBloom : (mDepthOfField ? mBackBufferDoF : (mTemporalAA ? mBackBufferTAA : mBackBuffer)))->Data()),
+            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), static_cast<const uint8_t*>((mBloom ? mBackBufferBloom : (mMotionBlur ? mBackBufferMB : (mDepthOfField ? mBackBufferDoF : (mTemporalAA ? mBackBufferTAA : mBackBuffer))))->Data()),
                                                    static_cast<uint8_t*>(mBackBufferAA->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
                                                    &mAAParams, mCommandList->Stream()));
         // :300-305: advance the fence and signal it behind this frame's commands
@@ -441,6 +452,34 @@ public:
     ID3D12Resource* TemporalAAHistory() { return mTaaHistory[mTaaHistoryIndex].get(); }     // the history the last Draw wrote
     const float* TemporalAAViewProj(int previous) const { return mTaaViewProj[previous ? 1 : 0]; }   // unjittered, of the last Update
     const float* TemporalAAJitter() const { return mTaaJitter; }                            // the last Update's offset in pixels
+
+    // ---- motion blur (extension) ------------------------------------------------------------------------------------------------------
+    // Camera motion turned into blur (include/crychic_hip.h crychic_motion_blur).  On: Update keeps the unjittered ViewProj of this
+    // frame and of the previous one (the first frame after it was turned on, and after OnResize, has no previous one: a still
+    // camera); Draw issues the pass behind the depth of field and in front of the bloom and the anti-aliasing, from the frame as it
+    // then stands into a buffer of its own, through a workspace this object owns; the bloom and the anti-aliasing then read that
+    // buffer and Present writes the last stage's output.  CurrentBackBuffer stays the frame without it.  p == nullptr: the default
+    // parameters.  With it on, SetStrip / JoinNode make Draw throw (the pass is not sharded).  Off (the default): nothing changes.
+    void SetMotionBlur(bool on, const crychic_motion_blur_params* p = nullptr)
+    {
+        crychic_motion_blur_params q;
+        CrychicThrowIfFailed(crychic_motion_blur_default_params(&q));
+        if (p) q = *p;
+        if (q.shutter > 256u || q.samples < 2u || q.samples > 32u || (q.samples & (q.samples - 1u)) || q.maxRadius == 0u || q.maxRadius > 32u || q.flags ||
+            (q.reserved[0] | q.reserved[1] | q.reserved[2] | q.reserved[3]))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetMotionBlur (shutter 0 .. 256, samples 2, 4, 8, 16 or 32, maxRadius 1 .. 32, flags 0, reserved 0)",
+                                   __FILE__, __LINE__);
+        mCommandList->Flush();                                  // a frame in flight may still write the buffers released below
+        const bool was = mMotionBlur;
+        mMotionBlur = on;
+        mMbParams = q;
+        if (on && !was) AllocateMotionBlur();
+        if (!on) { mBackBufferMB.reset(); mMbWorkspace.reset(); }
+    }
+    bool MotionBlur() const { return mMotionBlur; }
+    ID3D12Resource* MotionBlurBackBuffer() { return mBackBufferMB.get(); }
+    ID3D12Resource* MotionBlurWorkspace() { return mMbWorkspace.get(); }
+    const float* MotionBlurViewProj(int previous) const { return mMbViewProj[previous ? 1 : 0]; }   // unjittered, of the last Update
 
     // ---- deferred decals (extension) ------------------------------------------------------------------------------------------------
     // Oriented boxes that blend textures into the G-buffer between the producer passes and the lighting pass (include/crychic_hip.h
@@ -696,7 +735,7 @@ public:
     void Present(const std::string& path)
     {
         std::vector<uint8_t> host((size_t)mClientWidth * mClientHeight * 4);
-        (mAntiAliasing ? mBackBufferAA : (mBloom ? mBackBufferBloom : (mDepthOfField ? mBackBufferDoF : (mTemporalAA ? mBackBufferTAA : mBackBuffer))))->Download(host.data(), host.size(), mCommandList->Stream());
+        (mAntiAliasing ? mBackBufferAA : (mBloom ? mBackBufferBloom : (mMotionBlur ? mBackBufferMB : (mDepthOfField ? mBackBufferDoF : (mTemporalAA ? mBackBufferTAA : mBackBuffer)))))->Download(host.data(), host.size(), mCommandList->Stream());
         mCommandList->Flush();
         CrychicThrowIfFailed(crychic_save_ppm(path.c_str(), host.data(), mClientWidth, mClientHeight));
     }
@@ -1136,6 +1175,12 @@ private:
         for (int i = 0; i < 3; ++i) { dirs[i][0] = mRotatedLightDirections[i].x; dirs[i][1] = mRotatedLightDirections[i].y; dirs[i][2] = mRotatedLightDirections[i].z; }
         CrychicThrowIfFailed(crychic_update_main_pass_cb(&mCamera.Raw(), mClientWidth, mClientHeight, st, dirs,
                                                          reinterpret_cast<crychic_pass_constants*>(&mMainPassCB)));
+        if (mMotionBlur) {
+            // the unjittered ViewProj built above becomes this frame's, what was this frame's the previous one's (its own on a first frame)
+            std::memcpy(mMbViewProj[1], mMbFirst ? reinterpret_cast<const float*>(&mMainPassCB.ViewProj) : mMbViewProj[0], 64);
+            std::memcpy(mMbViewProj[0], &mMainPassCB.ViewProj, 64);
+            mMbFirst = false;
+        }
         if (mTemporalAA) {
             // the unjittered ViewProj built above becomes this frame's, what was this frame's the previous one's (its own on a reset
             // frame); then the constants again with the projection shifted by the frame's jitter
@@ -1232,6 +1277,18 @@ private:
         mTaaParams = q;
         if (on && !was) { AllocateTemporalAA(); mTaaFrameIndex = 0; }
         if (!on) { mBackBufferTAA.reset(); mTaaHistory[0].reset(); mTaaHistory[1].reset(); }
+    }
+    bool mMotionBlur = false;                 // SetMotionBlur
+    crychic_motion_blur_params mMbParams = {};
+    std::unique_ptr<ID3D12Resource> mBackBufferMB;     // the frame behind the motion blur, while mMotionBlur
+    std::unique_ptr<ID3D12Resource> mMbWorkspace;      // its velocity and tile planes
+    bool mMbFirst = true;                     // the next Update has no previous camera
+    float mMbViewProj[2][16] = {};            // the unjittered ViewProj of this frame and of the previous one (stored transposed)
+    void AllocateMotionBlur()
+    {
+        mBackBufferMB = std::make_unique<ID3D12Resource>((size_t)mClientWidth * mClientHeight * 4, ID3D12Resource::DEFAULT_HEAP);
+        mMbWorkspace = std::make_unique<ID3D12Resource>(crychic_motion_blur_workspace_bytes(mClientWidth, mClientHeight), ID3D12Resource::DEFAULT_HEAP);
+        mMbFirst = true;
     }
     bool mAntiAliasing = false;               // SetAntiAliasing
     crychic_aa_params mAAParams = {};

@@ -1238,6 +1238,85 @@ int crychic_taa(crychic_ctx* ctx, const crychic_pass_constants* cb, const float 
                 uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
                 const crychic_taa_params* params /* NULL = defaults */, void* stream);
 
+/* ---- motion blur: depth-reprojected velocity, tile maximum, gather (extension) ---------------------------
+ * Camera motion turned into blur of the finished RGBA8 frame.  A separate call behind the depth of field and in front of the bloom and
+ * the post-process anti-aliasing; it writes a buffer of its own.  Each pixel's velocity is the reprojection of crychic_taa (steps 2
+ * and 3 above) through the depth plane; each 16 x 16 tile keeps its largest velocity; each pixel gathers N samples along the largest
+ * velocity of the 3 x 3 tiles around it, weighted by depth and by each side's own reach.  Camera motion only: a render item carries
+ * no previous world matrix; the velocity plane is where object motion would be added.  A build definition: nothing of it is the
+ * reference's.  The device, a host build and the checker (tests/motion_blur_ref) agree bit for bit on the workspace and the frame.
+ *
+ * Parameters (32 bytes): shutter, the exposure in 1/256 of the frame interval (default 128; 0 .. 256); samples = N (default 8; 2, 4, 8,
+ * 16 or 32); maxRadius = R in pixels (default 16; 1 .. 32); flags (must be 0); reserved (must be 0).
+ * crychic_motion_blur_default_params fills the defaults (pure host code; CRYCHIC_E_INVALID_ARG for NULL).
+ *
+ * Workspace: the velocity plane, W x H texels of two uint32_t, row-major, at offset 0; behind it, at
+ * crychic_motion_blur_tile_offset(W, H) = W H 8, the tile plane, ceil(W / 16) x ceil(H / 16) uint32_t, row-major.
+ * crychic_motion_blur_workspace_bytes(W, H) is the end of the tile plane.  Both are pure host code.
+ *
+ * Float operations are IEEE binary32, each rounded once, in the order written; the named primitives are those of crychic_fog and
+ * crychic_taa (d24_to_float, mulcol, mulcol1, rcp).  curViewProj and prevViewProj are the UNJITTERED view-projections of this frame
+ * and the previous one, stored transposed; of cb, InvViewProj is read.  The matrices may hold anything, NaN and infinity included.
+ * Host-side constants:  sx, sy, hw, hh as in crychic_taa;  sh = (float)shutter * 0.00390625f (exact);  Rf = (float)R.
+ * Step A, per pixel (px, py) of the whole frame:
+ *   1  vx, vy as steps 2 and 3 of crychic_taa give them, a[3] and b[3] included.  The velocity is VALID iff a[3] > 0 and b[3] > 0
+ *      and |vx| < infinity and |vy| < infinity (every comparison false for NaN); an invalid velocity is (+0, +0).
+ *   2  s_x = vx sh;  s_y = vy sh  (one product each).
+ *   3  m = max(|s_x|, |s_y|);  if m > Rf:  k = Rf rcp(m) (one product);  s_x = s_x k;  s_y = s_y k.
+ *   4  q = clamp((int)floorf(fma(s, 16.0f, 0.5f)), -16 R, 16 R) for s = s_x, s_y: 1/16 pixel.
+ *   5  velocity[py W + px] = { (uint16_t)qx | (uint32_t)(uint16_t)qy << 16,  depth[py W + px] & 0xFFFFFF }.
+ * len(word) = max(|qx|, |qy|) of the two int16_t in a velocity word: the Chebyshev norm, in 1/16 pixel, at most 512.
+ * key(word) = (uint64_t)len(word) << 32 | word.  Equal keys are equal words, so "the word of the largest key" is well defined.
+ * Step A', per tile: tile (tx, ty) covers pixels [16 tx, 16 tx + 16) x [16 ty, 16 ty + 16) cut to the frame;
+ *   tiles[ty ceil(W / 16) + tx] = the word of the largest key among the tile's velocity words.
+ * Step B, per pixel (px, py) of the row range, in tile (tx, ty) = (px >> 4, py >> 4):
+ *   1  vN = (nx, ny) = the word of the largest key among tiles (tx + i, ty + j), i, j = -1 .. 1, inside the tile grid.
+ *   2  if len(vN) < 8:  out = in, all four bytes.
+ *   3  else  b = B[py & 3][px & 3] of crychic_fog's Bayer matrix, 0 .. 15;  (wordX, dX) = velocity[py W + px];  lenX = len(wordX).
+ *   4  for i = 0 .. N - 1:  m = 16 i + b - 8 N;  ox = floor((nx m + 8 N) / (16 N)), oy = floor((ny m + 8 N) / (16 N)) (floor of the
+ *      exact quotient: an arithmetic shift);  dist = max(|ox|, |oy|);  the sample pixel is (clamp(px + ((ox + 8) >> 4), 0, W - 1),
+ *      clamp(py + ((oy + 8) >> 4), 0, H - 1)), >> arithmetic;  (wordY, dY) is its velocity texel, lenY = len(wordY), c_i its texel
+ *      of `in`;  w_i = [dY <= dX and 2 dist <= lenY] + [dY >= dX and 2 dist <= lenX]  (0, 1 or 2).
+ *   5  Wt = 1 + sum w_i (at most 65);  per channel R, G, B:  S = c_X + sum w_i c_i,  out = floor((2 S + Wt) / (2 Wt)) (at most
+ *      255);  alpha is the pixel's own.
+ * Known answers: a still camera (bitwise-equal matrices), shutter 0 and a first frame (prev = cur) give out == in and a tile plane
+ * of zeros; a pixel with velocity 0 all of whose samples lie strictly behind it keeps its bytes (a static foreground over a moving
+ * background); velocities of equal length in one tile resolve to the numerically larger word.
+ *
+ * crychic_motion_blur_velocity: steps A and A' over the whole frame: it writes the first crychic_motion_blur_workspace_bytes(W, H)
+ * bytes of the workspace and no other byte.  One launch.
+ * crychic_motion_blur_gather: step B for rows [row0, row0 + rows) of out_rgba8_dev and no other byte, from in_rgba8_dev and the
+ * workspace (any texel of either); stitched row ranges equal the whole-frame call byte for byte; rows == 0 launches nothing.  One
+ * launch.
+ * crychic_motion_blur: the two calls above over the whole frame, two launches on `stream`, one behind the other.
+ * All three: params == NULL = the defaults; no allocation, no synchronisation, no host read-back; capturable into a graph.
+ * CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and before anything is enqueued: a NULL plane, workspace,
+ * cb or matrix; a plane that is not 4-byte aligned or a workspace that is not 8-byte aligned; W or H of 0; a row range outside the
+ * frame; a parameter outside its range, samples that is no power of two, non-zero flags or a non-zero reserved word; workspace_bytes
+ * below crychic_motion_blur_workspace_bytes(W, H); out overlapping in (the pass gathers: it cannot run in place); the workspace (its
+ * first crychic_motion_blur_workspace_bytes bytes) overlapping a plane.  More than 2^28 pixels, or W or H above 2^22:
+ * CRYCHIC_E_UNSUPPORTED. */
+typedef struct crychic_motion_blur_params {
+    uint32_t shutter;
+    uint32_t samples;
+    uint32_t maxRadius;
+    uint32_t flags;
+    uint32_t reserved[4];
+} crychic_motion_blur_params;   /* 32 bytes */
+int crychic_motion_blur_default_params(crychic_motion_blur_params* out);
+size_t crychic_motion_blur_workspace_bytes(uint32_t W, uint32_t H);
+size_t crychic_motion_blur_tile_offset(uint32_t W, uint32_t H);
+int crychic_motion_blur_velocity(crychic_ctx* ctx, const crychic_pass_constants* cb, const float curViewProj[16], const float prevViewProj[16],
+                                 const uint32_t* depth_dev, uint32_t W, uint32_t H, const crychic_motion_blur_params* params /* NULL = defaults */,
+                                 void* workspace_dev, size_t workspace_bytes, void* stream);
+int crychic_motion_blur_gather(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0,
+                               uint32_t rows, const crychic_motion_blur_params* params /* NULL = defaults */, const void* workspace_dev,
+                               size_t workspace_bytes, void* stream);
+int crychic_motion_blur(crychic_ctx* ctx, const crychic_pass_constants* cb, const float curViewProj[16], const float prevViewProj[16],
+                        const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H,
+                        const crychic_motion_blur_params* params /* NULL = defaults */, void* workspace_dev, size_t workspace_bytes,
+                        void* stream);
+
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
  * of 2 rows (half-res alignment); the last rank takes the remainder. */

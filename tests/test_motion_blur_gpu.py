@@ -1,0 +1,308 @@
+"""crychic_motion_blur on the device: the two kernels against the checker (tests/motion_blur_ref) byte for byte on the workspace and
+the frame over the corpus of the CPU tier, behind guard bytes and on misaligned planes; the known answers; row ranges; refusals; a
+five-frame sequence with a moving camera; the pass behind Crychic.Draw -- alone, with the fog, the temporal anti-aliasing and the depth
+of field in front and the bloom and the anti-aliasing behind, switched off, on a strip -- and replayed from a graph."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import motion_blur_lib as mbl
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev(built_lib):
+    import torch
+    from crychic_renderer_amd import Context
+    ctx = Context(0)
+    yield built_lib, ctx, torch
+    ctx.close()
+
+
+def test_device_equals_checker(dev):
+    for i, case in enumerate(mbl.corpus()):
+        ref_ws, ref_out, _ = mbl.expected(case)
+        ws, out = mbl.run_device(dev, case, misalign=(0, 4, 12, 8)[i % 4], entry=("both", "split")[(i // 4) % 2])
+        assert np.array_equal(ws, ref_ws), "%s: %d bytes of the workspace differ" % (case.name, int((ws != ref_ws).sum()))
+        assert np.array_equal(out, ref_out), "%s: %d bytes of out differ" % (case.name, int((out != ref_out).sum()))
+
+
+def test_known_answers(dev):
+    from test_motion_blur_host import answers
+    answers(lambda c: mbl.run_device(dev, c))
+    answers(lambda c: mbl.run_device(dev, c, misalign=12, entry="split"))
+
+
+@pytest.mark.parametrize("split", [(0, 1, 2, 33, 34, 69, 190), (0, 16, 190), (0, 7, 12, 95, 189, 190)])
+def test_row_ranges_stitch_to_the_whole_frame(dev, split):
+    from test_motion_blur_host import tall_case
+    case = tall_case("yaw")
+    whole_ws, whole_out, _ = mbl.expected(case)
+    stitched = np.full_like(whole_out, mbl.GUARD)
+    for k, (row0, end) in enumerate(zip(split[:-1], split[1:])):
+        # the first range through the velocity entry, the others over the checker's workspace
+        ws, out = mbl.run_device(dev, case, row0=row0, rows=end - row0, misalign=4 if row0 else 0, entry="gather" if k else "split",
+                                 ws_host=whole_ws if k else None)
+        assert np.array_equal(ws, whole_ws), "the gather entry wrote the workspace" if k else "the velocity entry covers the whole frame"
+        assert (out[:row0] == mbl.GUARD).all() and (out[end:] == mbl.GUARD).all(), "rows outside the range were written"
+        stitched[row0:end] = out[row0:end]
+    assert np.array_equal(stitched, whole_out)
+    assert (mbl.run_device(dev, case, row0=190, rows=0, entry="gather", ws_host=whole_ws)[1] == mbl.GUARD).all()
+
+
+def test_refusals_with_a_context(dev):
+    lib, ctx, torch = dev
+    W, H = 64, 32
+    need = mbl.workspace_bytes(W, H)
+    a = torch.zeros((H, W, 4), dtype=torch.uint8, device=ctx.device)
+    b = torch.full((H, W, 4), mbl.GUARD, dtype=torch.uint8, device=ctx.device)
+    w = torch.full((need,), mbl.GUARD, dtype=torch.uint8, device=ctx.device)
+    d = torch.zeros((H, W), dtype=torch.int32, device=ctx.device)
+    pa, pb, pw, pd = (C.c_void_p(t.data_ptr()) for t in (a, b, w, d))
+    cb = lib.PassConstants()
+    cb.InvViewProj[:] = list(mbl.IDENTITY)
+    eye = (C.c_float * 16)(*mbl.IDENTITY)
+    f, v, g = lib.lib.crychic_motion_blur, lib.lib.crychic_motion_blur_velocity, lib.lib.crychic_motion_blur_gather
+    err = lib.lib.crychic_last_error
+    assert f(ctx.handle, C.byref(cb), eye, eye, pd, pa, C.c_void_p(a.data_ptr() + 4), W, H, None, pw, need, None) == -1 and "cannot run in place" in err().decode()
+    assert f(ctx.handle, C.byref(cb), eye, eye, pd, pa, pb, W, H, None, pw, need - 1, None) == -1 and "workspace has" in err().decode()
+    assert f(ctx.handle, C.byref(cb), eye, eye, pd, pa, pb, W, H, None, pb, need, None) == -1 and "workspace overlaps" in err().decode()
+    assert v(ctx.handle, C.byref(cb), eye, eye, None, W, H, None, pw, need, None) == -1 and "null argument" in err().decode()
+    assert g(ctx.handle, pa, pb, W, H, 1, H, None, pw, need, None) == -1 and "outside" in err().decode()
+    bad = lib.MotionBlurParams.default(samples=3)
+    assert f(ctx.handle, C.byref(cb), eye, eye, pd, pa, pb, W, H, C.byref(bad), pw, need, None) == -1 and "samples" in err().decode()
+    torch.cuda.synchronize()
+    assert bool((b == mbl.GUARD).all()) and bool((w == mbl.GUARD).all()), "a refused call wrote"
+
+
+def test_five_frames_with_a_moving_camera(dev):
+    """The 70 x 38 synthetic scene under a camera that strafes, turns and dollies: every frame's workspace and output equal the
+    checker's, the previous matrix being the frame before's."""
+    lib, ctx, torch = dev
+    from crychic_renderer_amd import scene
+    W, H = 70, 38
+    rng = np.random.default_rng(39)
+    cams = [mbl.moved_camera(W, H), mbl.moved_camera(W, H, dx=0.2), mbl.moved_camera(W, H, dx=0.5, yaw=0.05), mbl.moved_camera(W, H, dx=0.5, dz=0.8, yaw=0.12),
+            mbl.moved_camera(W, H, dx=0.5, dz=0.8, yaw=0.12)]
+    prev, moving = None, 0
+    for k, cam in enumerate(cams):
+        consts = scene.Constants(W, H, 64, cam=cam)
+        depth = scene._camera_planes(consts, "cpu")["depth"].numpy().view(np.uint32)
+        img = rng.integers(0, 256, (H, W, 4), dtype=np.uint8)
+        img[..., :3] = (img[..., :3] >> 3) + (depth[..., None] >> 17).astype(np.uint8)      # the scene's shapes with a little noise
+        cur = mbl.camera_matrices(W, H, cam=cam)[0]
+        case = mbl.Case("frame%d" % k, np.array(consts.pass_cb.InvViewProj[:], np.float32), cur, cur if prev is None else prev, depth, img, 256,
+                        mbl.SAMPLES[k], 16)
+        ref_ws, ref_out, branch = mbl.expected(case)
+        ws, out = mbl.run_device(dev, case, misalign=4 * (k % 2))
+        assert np.array_equal(ws, ref_ws) and np.array_equal(out, ref_out), k
+        still = bool((branch & mbl.B_STILL).all())
+        assert still == (k in (0, 4)), "the first frame and a camera that has stopped copy the frame"
+        assert still == np.array_equal(out, img)
+        moving += not still
+        prev = cur
+    assert moving == 3
+
+
+def test_one_captured_call_replays_to_the_same_bytes(dev):
+    lib, ctx, torch = dev
+    case = {c.name: c for c in mbl.corpus()}["70x38_shear1"]
+    ref_ws, ref_out, _ = mbl.expected(case)
+    H, W = case.H, case.W
+    need = mbl.workspace_bytes(W, H)
+    src = torch.from_numpy(case.img.copy()).to(ctx.device)
+    depth = torch.from_numpy(case.depth.view(np.int32).copy()).to(ctx.device)
+    out, ws = torch.zeros_like(src), torch.zeros((need,), dtype=torch.uint8, device=ctx.device)
+    pcb, p = case.pass_constants(lib), case.params(lib)
+    cur, prev = (C.c_float * 16)(*case.cur), (C.c_float * 16)(*case.prev)
+
+    def call():
+        s = torch.cuda.current_stream(ctx.device)
+        lib.check(lib.lib.crychic_motion_blur(ctx.handle, C.byref(pcb), cur, prev, C.c_void_p(depth.data_ptr()), C.c_void_p(src.data_ptr()),
+                                              C.c_void_p(out.data_ptr()), W, H, C.byref(p), C.c_void_p(ws.data_ptr()), need, C.c_void_p(s.cuda_stream)))
+    call()                              # before the capture: the code object loaded
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        call()
+    for _ in range(2):
+        out.zero_()
+        ws.zero_()
+        torch.cuda.synchronize()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert np.array_equal(out.cpu().numpy(), ref_out) and np.array_equal(ws.cpu().numpy(), ref_ws)
+
+
+# ---- behind Crychic.Draw ----------------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def app_frame(dev):
+    """A Crychic over the 128 x 96 synthetic scene and the frame Draw() gives without the pass."""
+    lib, ctx, torch = dev
+    from crychic_renderer_amd import Crychic, LIGHT_SKY, scene
+    W, H, SD = 128, 96, 256
+    planes = scene.make_scene(W, H, shadow_dim=SD, cube_dim=32, device="cuda:0")
+    app = Crychic(ctx, W, H, planes["randvec"], planes["cube"], shadow_dim=SD)
+    app.load_scene(planes)
+    app.blurCount, app.numDirLights, app.flags = 3, 3, LIGHT_SKY
+    assert app.motionBlur is None
+    app.Draw()
+    torch.cuda.synchronize()
+    return app, app.mBackBuffer.cpu().numpy().copy(), planes
+
+
+def check_blur(app, planes, img, cur, prev, **params):
+    """The checker's (workspace, out) of the pass over `img` with the app's constants and depth plane."""
+    case = mbl.Case("draw", np.array(app.mMainPassCB.InvViewProj[:], np.float32), cur, prev, planes["depth"].cpu().numpy().view(np.uint32), img, **params)
+    ws, _ = mbl.checker_velocity(case)
+    return ws, mbl.checker_gather(case, ws)
+
+
+def test_draw_with_motion_blur(dev, app_frame):
+    """Draw() with motionBlur alone equals the pass issued by hand: a still camera while set_frame_view_proj was never called, then
+    the matrices it was given; a MotionBlurParams reaches the pass; motion_blur() takes a row range."""
+    lib, ctx, torch = dev
+    app, plain, planes = app_frame
+    cur = np.array(app.mMainPassCB.ViewProj[:], np.float32)
+    moved = mbl.camera_matrices(128, 96, cam=mbl.moved_camera(128, 96, dx=0.4, yaw=0.03))[0]
+    app.motionBlur = True
+    try:
+        app.Draw()
+        torch.cuda.synchronize()
+        assert np.array_equal(app.mBackBuffer.cpu().numpy(), plain) and np.array_equal(app.mBackBufferMB.cpu().numpy(), plain), "a still camera copies"
+        app.set_frame_view_proj(moved)                          # the "previous" frame's
+        app.set_frame_view_proj(cur)
+        app.Draw()
+        torch.cuda.synchronize()
+        ws, out = check_blur(app, planes, plain, cur, moved)
+        assert not np.array_equal(out, plain)
+        assert np.array_equal(app.mBackBuffer.cpu().numpy(), plain), "mBackBuffer stays the frame without the pass"
+        assert np.array_equal(app.mBackBufferMB.cpu().numpy(), out) and np.array_equal(app.mMotionBlurWorkspace.cpu().numpy(), ws)
+        app.motionBlur = lib.MotionBlurParams.default(shutter=256, samples=16, maxRadius=32)
+        app.Draw()
+        torch.cuda.synchronize()
+        ws, out2 = check_blur(app, planes, plain, cur, moved, shutter=256, samples=16, radius=32)
+        assert not np.array_equal(out2, out) and np.array_equal(app.mBackBufferMB.cpu().numpy(), out2)
+        dst = torch.full_like(app.mBackBuffer, mbl.GUARD)
+        assert app.motion_blur(cur, moved, out=dst, row0=20, rows=37, params=app.motionBlur) is dst
+        torch.cuda.synchronize()
+        got = dst.cpu().numpy()
+        assert np.array_equal(got[20:57], out2[20:57]) and (got[:20] == mbl.GUARD).all() and (got[57:] == mbl.GUARD).all()
+        app.set_frame_view_proj(cur)                            # the camera has stopped
+        app.Draw()
+        torch.cuda.synchronize()
+        assert np.array_equal(app.mBackBufferMB.cpu().numpy(), plain)
+    finally:
+        app.motionBlur = None
+        app._taaViewProj = [None, None]
+
+
+def test_the_passes_in_front_and_behind(dev, app_frame):
+    """lighting -> fog -> temporal anti-aliasing -> depth of field -> motion blur -> bloom -> anti-aliasing: every buffer equals its
+    checker over the one before; without the depth of field the pass reads mBackBufferTAA, without that mBackBuffer."""
+    lib, ctx, torch = dev
+    import bloom_lib
+    import dof_lib
+    import fog_lib
+    import post_aa_lib as aa
+    import taa_lib as ta
+    app, plain, planes = app_frame
+    depth = planes["depth"].cpu().numpy().view(np.uint32)
+    fogged, _ = fog_lib.checker(fog_lib.Frame.from_pass_cb(app.mMainPassCB, depth, planes["shadow"].cpu().numpy().view(np.uint32)), plain)
+    cur = np.array(app.mMainPassCB.ViewProj[:], np.float32)
+    moved = mbl.camera_matrices(128, 96, cam=mbl.moved_camera(128, 96, dx=-0.3, yaw=0.02))[0]
+    ivp = np.array(app.mMainPassCB.InvViewProj[:], np.float32)
+    app.fog, app.temporalAA, app.depthOfField, app.motionBlur, app.bloom, app.antiAliasing = True, True, True, True, True, True
+    try:
+        app.set_frame_view_proj(moved)
+        app.set_frame_view_proj(cur)
+        app.Draw()                                              # the temporal pass's RESET frame: it hands the fogged frame on
+        torch.cuda.synchronize()
+        assert np.array_equal(app.mBackBuffer.cpu().numpy(), fogged) and np.array_equal(app.mBackBufferTAA.cpu().numpy(), fogged)
+        focused, _ = dof_lib.checker(dof_lib.Frame.from_pass_cb(app.mMainPassCB, depth), fogged)
+        assert np.array_equal(app.mBackBufferDoF.cpu().numpy(), focused)
+        _, blurred = check_blur(app, planes, focused, cur, moved)
+        assert not np.array_equal(blurred, focused)
+        assert np.array_equal(app.mBackBufferMB.cpu().numpy(), blurred), "the motion blur did not read mBackBufferDoF"
+        bloomed = bloom_lib.checker(blurred)[0]
+        assert np.array_equal(app.mBackBufferBloom.cpu().numpy(), bloomed), "the bloom did not read mBackBufferMB"
+        assert np.array_equal(app.mBackBufferAA.cpu().numpy(), aa.checker(bloomed)[0])
+        # without the depth of field and the bloom: the pass reads mBackBufferTAA and the anti-aliasing reads mBackBufferMB
+        app.depthOfField, app.bloom = None, None
+        h0 = app.mTaaHistory[0].cpu().numpy().view(np.uint16).copy()
+        app.Draw()
+        torch.cuda.synchronize()
+        resolved, _, _ = ta.checker(ta.Case("draw", ivp, cur, moved, depth, fogged, h0))
+        assert np.array_equal(app.mBackBufferTAA.cpu().numpy(), resolved)
+        _, blurred = check_blur(app, planes, resolved, cur, moved)
+        assert np.array_equal(app.mBackBufferMB.cpu().numpy(), blurred), "the motion blur did not read mBackBufferTAA"
+        assert np.array_equal(app.mBackBufferAA.cpu().numpy(), aa.checker(blurred)[0])
+        # the fog alone in front: the pass reads mBackBuffer
+        app.temporalAA, app.antiAliasing = None, None
+        app.Draw()
+        torch.cuda.synchronize()
+        assert np.array_equal(app.mBackBufferMB.cpu().numpy(), check_blur(app, planes, fogged, cur, moved)[1])
+        assert app.fog is True and app.motionBlur is True
+    finally:
+        app.fog, app.temporalAA, app.depthOfField, app.motionBlur, app.bloom, app.antiAliasing = None, None, None, None, None, None
+        app._taaViewProj = [None, None]
+
+
+class Recorder:
+    """The library with every crychic_* call of its user recorded by name."""
+
+    def __init__(self, lib):
+        self._lib, self.calls = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("crychic_"):
+            return fn
+
+        def wrapped(*a):
+            self.calls.append(name)
+            return fn(*a)
+        return wrapped
+
+
+def test_switch_off_is_the_frame_and_the_calls_of_before(dev, app_frame, monkeypatch):
+    lib, ctx, torch = dev
+    from crychic_renderer_amd import renderer
+    app, plain, planes = app_frame
+    rec = Recorder(renderer.lib)
+    monkeypatch.setattr(renderer, "lib", rec)
+    assert app.motionBlur is None and not app._post
+    app.Draw()
+    torch.cuda.synchronize()
+    assert rec.calls == ["crychic_draw_hot_path_point_shadows"], rec.calls
+    assert np.array_equal(app.mBackBuffer.cpu().numpy(), plain)
+    del rec.calls[:]
+    app.motionBlur = True
+    try:
+        app.Draw()
+        torch.cuda.synchronize()
+        assert rec.calls == ["crychic_draw_hot_path_point_shadows", "crychic_motion_blur_workspace_bytes", "crychic_motion_blur"], rec.calls
+    finally:
+        app.motionBlur = None
+    del rec.calls[:]
+    app.Draw()
+    torch.cuda.synchronize()
+    assert rec.calls == ["crychic_draw_hot_path_point_shadows"] and np.array_equal(app.mBackBuffer.cpu().numpy(), plain)
+
+
+def test_strip_or_shared_draw_raises(dev, app_frame):
+    lib, ctx, torch = dev
+    app, plain, planes = app_frame
+    app.motionBlur = True
+    try:
+        for kw in (dict(row0=0, rows=48), dict(row0=48), dict(shared=(None, None, 1))):
+            with pytest.raises(lib.CrychicError):
+                app.Draw(**kw)
+        app.Draw(row0=0, rows=96)           # the whole frame, spelled out
+    finally:
+        app.motionBlur = None
+    app.Draw(row0=0, rows=48)               # without it a strip is a strip
+    torch.cuda.synchronize()

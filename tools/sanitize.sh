@@ -11,6 +11,15 @@ RT=$(/opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so)
 export CRYCHIC_SANITIZE=1
 export ASAN_OPTIONS=detect_leaks=0:abort_on_error=1:halt_on_error=1
 export UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1
+# The motion blur's kernel bodies (csrc/motion_blur_core.hpp) against their checker: a stand-alone program linked with the sanitizers'
+# runtimes, so it needs no preload (tests/motion_blur_host/motion_blur_san_main.cpp).
+CLANG=/opt/rocm/lib/llvm/bin/clang
+SAN_DIR=$(mktemp -d)
+trap 'rm -rf "$SAN_DIR"' EXIT
+"$CLANG" -O1 -g -std=c99 -ffp-contract=off -fsanitize=address,undefined -fno-sanitize-recover=all -c tests/motion_blur_ref/motion_blur_ref.c -o "$SAN_DIR/motion_blur_ref.o"
+"$CLANG"++ -O1 -g -std=c++17 -ffp-contract=off -mfma -fsanitize=address,undefined,float-cast-overflow -fno-sanitize-recover=all -I crychic_renderer_amd/csrc \
+    tests/motion_blur_host/motion_blur_san_main.cpp tests/motion_blur_host/motion_blur_host.cpp "$SAN_DIR/motion_blur_ref.o" -lm -o "$SAN_DIR/motion_blur_san"
+"$SAN_DIR/motion_blur_san"
 LD_PRELOAD="$RT" python -m pytest -q -x -m "not gpu" -p no:cacheprovider \
     tests/test_oracle_kat.py tests/test_devmath_host.py tests/test_hostsim_parity.py tests/test_fuzz.py tests/test_golden.py \
     tests/test_numpy_restatements.py tests/test_raster_cpu.py tests/test_constants.py tests/test_culling.py tests/test_textures.py \
