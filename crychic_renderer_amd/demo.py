@@ -216,9 +216,11 @@ def main():
             app.set_frame_view_proj(consts.pass_cb.ViewProj)
         app.Draw()
     torch.cuda.synchronize()
-    img = np.ascontiguousarray((app.mBackBufferAA if a.aa else (app.mBackBufferBloom if a.bloom else (app.mBackBufferMB if a.motion_blur else (app.mBackBufferDoF if a.dof else (app.mBackBufferTAA if a.taa else app.mBackBuffer))))).cpu().numpy())
+    img = np.ascontiguousarray(app.final_frame().cpu().numpy())
     check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, W, H))
-    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, (", fog" if a.fog else "") + (", temporal anti-aliasing" if a.taa else "") + (", depth of field" if a.dof else "") + (", motion blur" if a.motion_blur else "") + (", bloom" if a.bloom else "") + (", anti-aliased" if a.aa else ""), ctx.device_name))
+    chain = (("fog", "fog"), ("temporalAA", "temporal anti-aliasing"), ("depthOfField", "depth of field"), ("motionBlur", "motion blur"),
+             ("bloom", "bloom"), ("antiAliasing", "anti-aliased"))                   # Draw()'s order
+    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, "".join(", " + text for switch, text in chain if getattr(app, switch)), ctx.device_name))
 
 
 if __name__ == "__main__":

@@ -319,36 +319,19 @@ class Crychic:
     def Draw(self, row0=0, rows=None, shared=None):  # CRYCHIC.cpp:172-306 (hot part)
         """shared = (communicator handle, bounds array or None, parts): the _shared entry -- the strip AND its exchange,
         the lighting pass in `parts` row ranges that travel while the next is lit (sharding.StripExchange.draw).
-        antiAliasing = True or an AAParams (extension): a whole frame, then crychic_antialias over it into mBackBufferAA; mBackBuffer is
-        the frame without it.  A strip or a shared draw then raises CrychicError.
-        fog = True or a FogParams (extension): a whole frame, then crychic_fog in place on mBackBuffer (in front of the anti-aliasing
-        if that is set too).  A strip or a shared draw then raises CrychicError.
-        depthOfField = True or a DofParams (extension): a whole frame (fogged if fog is set), then crychic_dof from mBackBuffer into
-        mBackBufferDoF; the anti-aliasing, if set too, then reads mBackBufferDoF.  A strip or a shared draw then raises CrychicError.
-        bloom = True or a BloomParams (extension): a whole frame (fogged, and through the depth of field, as set), then crychic_bloom
-        from that frame into mBackBufferBloom; the anti-aliasing, if set too, then reads mBackBufferBloom.  A strip or a shared draw
-        then raises CrychicError.
-        temporalAA = True or a TaaParams (extension): a whole frame (fogged if fog is set), then crychic_taa from mBackBuffer into
-        mBackBufferTAA with the matrices of set_frame_view_proj; the depth of field, the bloom and the anti-aliasing, as set, then
-        read mBackBufferTAA.  The order is lighting, fog, temporal anti-aliasing, depth of field, bloom, anti-aliasing: the temporal
-        pass needs the frame still aligned with its depth plane.  The first such frame, and the first after the switch was turned on
-        or the frame's size changed, is a RESET frame.  A strip or a shared draw then raises CrychicError.
-        motionBlur = True or a MotionBlurParams (extension): a whole frame (fog, temporal anti-aliasing and depth of field as set),
-        then crychic_motion_blur from that frame into mBackBufferMB with the matrices of set_frame_view_proj (never called: a still
-        camera); the bloom and the anti-aliasing, as set, then read mBackBufferMB.  A strip or a shared draw then raises
-        CrychicError."""
+        With a switch of the passes behind the lighting pass set (extensions; True, or the pass's parameter struct): a whole frame,
+        then the set passes in the order
+            lighting -> fog (in place) -> temporalAA -> depthOfField -> motionBlur -> bloom -> antiAliasing,
+        each but the fog from the buffer of the nearest set stage in front of it that writes one of its own (mBackBuffer if there is
+        none) into its own mBackBuffer*; final_frame() is the last one.  The temporal pass and the motion blur take the matrices of
+        set_frame_view_proj (never called: a still camera); the first frame after temporalAA was turned on is a RESET frame.  A strip
+        or a shared draw then raises CrychicError: these passes are not sharded."""
         if self._post:
-            if self._bloom:
-                return self._draw_with_bloom(row0, rows, shared)
-            if self._motionBlur:
-                return self._draw_with_motion_blur(row0, rows, shared)
-            if self._depthOfField:
-                return self._draw_with_depth_of_field(row0, rows, shared)
-            if self._temporalAA:
-                return self._draw_with_temporal_aa(row0, rows, shared)
-            if self._fog:
-                return self._draw_fogged(row0, rows, shared)
-            return self._draw_antialiased(row0, rows, shared)
+            return self._draw_post_chain(row0, rows, shared)
+        return self._draw_lighting(row0, rows, shared)
+
+    def _draw_lighting(self, row0, rows, shared):
+        """The lighting frame: all of Draw() while no switch is set."""
         # The descriptor only changes when a plane is re-allocated or a knob is turned: keep it across frames so the
         # per-frame host cost is one FFI call (matters once a strip takes tens of microseconds on 8 GPUs).  The key holds
         # every device pointer and size frame_desc() reads, so replacing any plane object invalidates the cached descriptor.
@@ -392,81 +375,60 @@ class Crychic:
             check(lib.crychic_draw_hot_path_point_shadows(self.ctx.handle, C.byref(self.mSsaoCB), C.byref(pcb), f, spots, n, desc,
                                                           pdesc, _stream(self.ctx.device)))
 
-    def _whole_frame_only(self, what, row0, rows, shared):
-        """The guard of the passes that are not sharded and do not run behind the exchange."""
+    def _draw_post_chain(self, row0, rows, shared):
+        """Draw() with a switch set: the lighting frame, then one walk along the chain with the frame each stage reads."""
         if shared is not None or row0 != 0 or (rows is not None and rows != self.mClientHeight):
+            what = next(s for s in ("bloom", "motionBlur", "depthOfField", "temporalAA", "fog", "antiAliasing") if getattr(self, s))
             raise CrychicError(-1, "%s is set: Draw() takes the whole frame on one GPU (the pass is not sharded and does not run behind the "
                                "exchange)" % what)
+        self._draw_lighting(0, None, None)
 
-    def _draw_antialiased(self, row0, rows, shared):
-        """Draw() with antiAliasing set: the frame as Draw() issues it without, then the pass over it into mBackBufferAA."""
-        self._whole_frame_only("antiAliasing", row0, rows, shared)
-        aa, self.antiAliasing = self.antiAliasing, None
-        try:
-            self.Draw()
-        finally:
-            self.antiAliasing = aa
-        self.antialias(params=aa if isinstance(aa, AAParams) else None)
-
-    def _draw_fogged(self, row0, rows, shared):
-        """Draw() with fog set: the frame as Draw() issues it without, the fog pass in place on mBackBuffer, then the anti-aliasing if
-        that is set."""
-        self._whole_frame_only("fog", row0, rows, shared)
-        fog, aa, self.fog, self.antiAliasing = self.fog, self.antiAliasing, None, None
-        try:
-            self.Draw()
-        finally:
-            self.fog, self.antiAliasing = fog, aa
-        self.apply_fog(params=fog if isinstance(fog, FogParams) else None)
-        if aa:
-            self.antialias(params=aa if isinstance(aa, AAParams) else None)
-
-    def _draw_with_depth_of_field(self, row0, rows, shared):
-        """Draw() with depthOfField set: the frame as Draw() issues it without (fogged in place if fog is set), the depth-of-field
-        pass from mBackBuffer into mBackBufferDoF, then the anti-aliasing of mBackBufferDoF if that is set."""
-        self._whole_frame_only("depthOfField", row0, rows, shared)
-        dof, aa, self.depthOfField, self.antiAliasing = self.depthOfField, self.antiAliasing, None, None
-        try:
-            self.Draw()
-        finally:
-            self.depthOfField, self.antiAliasing = dof, aa
-        self.depth_of_field(src=self.mBackBufferTAA if self._temporalAA else self.mBackBuffer, params=dof if isinstance(dof, DofParams) else None)
-        if aa:
-            self.antialias(src=self.mBackBufferDoF, params=aa if isinstance(aa, AAParams) else None)
-
-    def _draw_with_bloom(self, row0, rows, shared):
-        """Draw() with bloom set: the frame as Draw() issues it without (fog and depth of field as they are set), the bloom pass from
-        that frame -- mBackBufferDoF behind the depth of field, else mBackBuffer -- into mBackBufferBloom, then the anti-aliasing of
-        mBackBufferBloom if that is set."""
-        self._whole_frame_only("bloom", row0, rows, shared)
-        bloom, aa, self.bloom, self.antiAliasing = self.bloom, self.antiAliasing, None, None
-        try:
-            self.Draw()
-        finally:
-            self.bloom, self.antiAliasing = bloom, aa
-        self.apply_bloom(src=self.mBackBufferMB if self._motionBlur else self._frame_behind_dof(), params=bloom if isinstance(bloom, BloomParams) else None)
-        if aa:
-            self.antialias(src=self.mBackBufferBloom, params=aa if isinstance(aa, AAParams) else None)
-
-    def _frame_behind_dof(self):
-        """The frame the passes behind the depth of field read: mBackBufferDoF, else mBackBufferTAA, else mBackBuffer."""
-        return self.mBackBufferDoF if self._depthOfField else (self.mBackBufferTAA if self._temporalAA else self.mBackBuffer)
-
-    def _draw_with_motion_blur(self, row0, rows, shared):
-        """Draw() with motionBlur set: the frame as Draw() issues it without (fog, temporal anti-aliasing and depth of field as they
-        are set), the motion blur from that frame into mBackBufferMB, then the anti-aliasing of mBackBufferMB if that is set."""
-        self._whole_frame_only("motionBlur", row0, rows, shared)
-        mb, aa, self.motionBlur, self.antiAliasing = self.motionBlur, self.antiAliasing, None, None
-        try:
-            self.Draw()
-        finally:
-            self.motionBlur, self.antiAliasing = mb, aa
-        cur, prev = self._taaViewProj
-        if cur is None:                         # set_frame_view_proj was never called: the camera counts as still
+        def params(switch, kind):               # a switch holds True or the pass's parameters
+            return switch if isinstance(switch, kind) else None
+        frame = self.mBackBuffer
+        if self._fog:
+            self.apply_fog(params=params(self._fog, FogParams))
+        cur, prev = self._taaViewProj           # of the temporal pass and the motion blur
+        if cur is None:                         # set_frame_view_proj was never called: a still camera whose constants are not jittered
             cur = prev = tuple(self.mMainPassCB.ViewProj)
-        self.motion_blur(cur, cur if prev is None else prev, src=self._frame_behind_dof(), params=mb if isinstance(mb, MotionBlurParams) else None)
-        if aa:
-            self.antialias(src=self.mBackBufferMB, params=aa if isinstance(aa, AAParams) else None)
+        elif prev is None:                      # no previous frame
+            prev = cur
+        if self._temporalAA:
+            frame = self.temporal_aa(cur, prev, src=frame, reset=self._taaReset, params=params(self._temporalAA, TaaParams))
+            self._taaReset = False
+        if self._depthOfField:
+            frame = self.depth_of_field(src=frame, params=params(self._depthOfField, DofParams))
+        if self._motionBlur:
+            frame = self.motion_blur(cur, prev, src=frame, params=params(self._motionBlur, MotionBlurParams))
+        if self._bloom:
+            frame = self.apply_bloom(src=frame, params=params(self._bloom, BloomParams))
+        if self._antiAliasing:
+            self.antialias(src=frame, params=params(self._antiAliasing, AAParams))
+
+    def final_frame(self):
+        """The tensor a Draw() with the switches as they are leaves the finished frame in: the last set stage's buffer."""
+        for switch, name in ((self._antiAliasing, "mBackBufferAA"), (self._bloom, "mBackBufferBloom"), (self._motionBlur, "mBackBufferMB"),
+                             (self._depthOfField, "mBackBufferDoF"), (self._temporalAA, "mBackBufferTAA")):
+            if switch:
+                return getattr(self, name)
+        return self.mBackBuffer
+
+    def _pass_frames(self, who, buffer, src, out, any_shape=False):
+        """(src, out, H, W) of the pass method `who`: src defaults to mBackBuffer, out to the attribute `buffer` -- allocated, or
+        re-allocated to src's shape and device, on first use -- or with buffer None to src (in place); both checked."""
+        src = self.mBackBuffer if src is None else src
+        if out is None and buffer is None:
+            out = src
+        elif out is None:
+            out = getattr(self, buffer)
+            if out is None or out.shape != src.shape or out.device != src.device:
+                out = torch.zeros_like(src)
+                setattr(self, buffer, out)
+        H, W = int(src.shape[0]), int(src.shape[1])
+        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
+                or not src.is_contiguous() or not out.is_contiguous() or not (any_shape or (H, W) == (self.mClientHeight, self.mClientWidth)):
+            raise CrychicError(-1, "%s takes contiguous (H, W, 4) uint8 tensors of %s" % (who, "one shape" if any_shape else "the frame's size"))
+        return src, out, H, W
 
     def motion_blur(self, cur_view_proj, prev_view_proj, src=None, out=None, row0=0, rows=None, params=None):
         """crychic_motion_blur on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferMB, allocated on first
@@ -474,15 +436,7 @@ class Crychic:
         pass constants and the two UNJITTERED view-projections (16 floats each, stored transposed).  The velocity and tile planes go
         through mMotionBlurWorkspace, allocated on first use: the velocity launch always covers the whole frame, the gather the row
         range.  params: a MotionBlurParams, None = the defaults.  `src` and `out` must not overlap.  Returns `out`."""
-        src = self.mBackBuffer if src is None else src
-        if out is None:
-            if self.mBackBufferMB is None or self.mBackBufferMB.shape != src.shape or self.mBackBufferMB.device != src.device:
-                self.mBackBufferMB = torch.zeros_like(src)
-            out = self.mBackBufferMB
-        H, W = int(src.shape[0]), int(src.shape[1])
-        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
-                or not src.is_contiguous() or not out.is_contiguous() or (H, W) != (self.mClientHeight, self.mClientWidth):
-            raise CrychicError(-1, "motion_blur takes contiguous (H, W, 4) uint8 tensors of the frame's size")
+        src, out, H, W = self._pass_frames("motion_blur", "mBackBufferMB", src, out)
         need = int(lib.crychic_motion_blur_workspace_bytes(W, H))
         if self.mMotionBlurWorkspace is None or self.mMotionBlurWorkspace.numel() != need or self.mMotionBlurWorkspace.device != src.device:
             self.mMotionBlurWorkspace = torch.zeros((need,), dtype=torch.uint8, device=src.device)
@@ -499,25 +453,6 @@ class Crychic:
                                                  need, stream))
         return out
 
-    def _draw_with_temporal_aa(self, row0, rows, shared):
-        """Draw() with temporalAA set: the frame as Draw() issues it without (fogged in place if fog is set), the temporal pass from
-        mBackBuffer into mBackBufferTAA, then the anti-aliasing of mBackBufferTAA if that is set."""
-        self._whole_frame_only("temporalAA", row0, rows, shared)
-        taa, aa, self.temporalAA, self.antiAliasing = self.temporalAA, self.antiAliasing, None, None
-        reset = self._taaReset                 # the setter below sets it again: the switch goes from off to on
-        try:
-            self.Draw()
-        finally:
-            self.temporalAA, self.antiAliasing = taa, aa
-            self._taaReset = reset
-        cur, prev = self._taaViewProj
-        if cur is None:                         # set_frame_view_proj was never called: a still camera whose constants are not jittered
-            cur = prev = tuple(self.mMainPassCB.ViewProj)
-        self.temporal_aa(cur, cur if prev is None else prev, reset=self._taaReset, params=taa if isinstance(taa, TaaParams) else None)
-        self._taaReset = False
-        if aa:
-            self.antialias(src=self.mBackBufferTAA, params=aa if isinstance(aa, AAParams) else None)
-
     def set_frame_view_proj(self, view_proj):
         """The UNJITTERED view-projection of the frame about to be drawn (16 floats, stored transposed like the pass constants'
         ViewProj): what was current becomes the previous frame's.  Draw() with temporalAA set hands both to crychic_taa."""
@@ -533,15 +468,7 @@ class Crychic:
         mTaaHistory are this object's: allocated on first use (which makes the call a RESET call, as does reset=True or a RESET flag
         in params), read from [0], written to [1] and swapped after the call, so that mTaaHistory[0] is the history just written.
         params: a TaaParams, None = the defaults.  `src` and `out` must not overlap.  Returns `out`."""
-        src = self.mBackBuffer if src is None else src
-        if out is None:
-            if self.mBackBufferTAA is None or self.mBackBufferTAA.shape != src.shape or self.mBackBufferTAA.device != src.device:
-                self.mBackBufferTAA = torch.zeros_like(src)
-            out = self.mBackBufferTAA
-        H, W = int(src.shape[0]), int(src.shape[1])
-        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
-                or not src.is_contiguous() or not out.is_contiguous() or (H, W) != (self.mClientHeight, self.mClientWidth):
-            raise CrychicError(-1, "temporal_aa takes contiguous (H, W, 4) uint8 tensors of the frame's size")
+        src, out, H, W = self._pass_frames("temporal_aa", "mBackBufferTAA", src, out)
         if self.mTaaHistory is None or self.mTaaHistory[0].shape != src.shape or self.mTaaHistory[0].device != src.device:
             self.mTaaHistory = [torch.zeros((H, W, 4), dtype=torch.int16, device=src.device) for _ in range(2)]
             reset = True
@@ -561,15 +488,7 @@ class Crychic:
         (default: mBackBuffer), both (H, W, 4) uint8 tensors of the frame's size; `out` may be `src` itself (in place) and must not
         overlap it otherwise.  params: a BloomParams, None = the defaults.  The pyramid goes through mBloomWorkspace, allocated on
         first use for the frame's size at BLOOM_MAX_LEVELS levels; afterwards its level k holds U_k.  Returns `out`."""
-        src = self.mBackBuffer if src is None else src
-        if out is None:
-            if self.mBackBufferBloom is None or self.mBackBufferBloom.shape != src.shape or self.mBackBufferBloom.device != src.device:
-                self.mBackBufferBloom = torch.zeros_like(src)
-            out = self.mBackBufferBloom
-        H, W = int(src.shape[0]), int(src.shape[1])
-        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
-                or not src.is_contiguous() or not out.is_contiguous() or (H, W) != (self.mClientHeight, self.mClientWidth):
-            raise CrychicError(-1, "apply_bloom takes contiguous (H, W, 4) uint8 tensors of the frame's size")
+        src, out, H, W = self._pass_frames("apply_bloom", "mBackBufferBloom", src, out)
         need = int(lib.crychic_bloom_workspace_bytes(W, H, _lib.BLOOM_MAX_LEVELS))
         if self.mBloomWorkspace is None or self.mBloomWorkspace.numel() != need or self.mBloomWorkspace.device != src.device:
             self.mBloomWorkspace = torch.zeros((need,), dtype=torch.uint8, device=src.device)
@@ -582,15 +501,7 @@ class Crychic:
         from `src` (default: mBackBuffer), both (H, W, 4) uint8 tensors of the frame's size, with this frame's depth plane and pass
         constants; params: a DofParams, None = the defaults.  The pass reads rows [row0 - R, row0 + rows + R) of `src` and of the
         depth plane and writes no other byte of `out`; `src` and `out` must not overlap.  Returns `out`."""
-        src = self.mBackBuffer if src is None else src
-        if out is None:
-            if self.mBackBufferDoF is None or self.mBackBufferDoF.shape != src.shape or self.mBackBufferDoF.device != src.device:
-                self.mBackBufferDoF = torch.zeros_like(src)
-            out = self.mBackBufferDoF
-        H, W = int(src.shape[0]), int(src.shape[1])
-        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
-                or not src.is_contiguous() or not out.is_contiguous() or (H, W) != (self.mClientHeight, self.mClientWidth):
-            raise CrychicError(-1, "depth_of_field takes contiguous (H, W, 4) uint8 tensors of the frame's size")
+        src, out, H, W = self._pass_frames("depth_of_field", "mBackBufferDoF", src, out)
         check(lib.crychic_dof(self.ctx.handle, C.byref(self.mMainPassCB), self.mDepthStencilBuffer.data_ptr(), _ptr(src), _ptr(out), W, H,
                               int(row0), int(H - row0 if rows is None else rows), None if params is None else C.byref(params),
                               _stream(self.ctx.device)))
@@ -601,12 +512,7 @@ class Crychic:
         mBackBuffer, in place; `out` alone given: from mBackBuffer into it; `src` alone given: in place on it), with this frame's depth
         plane, pass constants and cascade maps; params: a FogParams, None = the defaults.  Writes no other byte of `out`.  Returns
         `out`."""
-        src = self.mBackBuffer if src is None else src
-        out = src if out is None else out
-        H, W = int(src.shape[0]), int(src.shape[1])
-        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
-                or not src.is_contiguous() or not out.is_contiguous() or (H, W) != (self.mClientHeight, self.mClientWidth):
-            raise CrychicError(-1, "apply_fog takes contiguous (H, W, 4) uint8 tensors of the frame's size")
+        src, out, H, W = self._pass_frames("apply_fog", None, src, out)
         maps = (C.c_void_p * 4)(*[self.mShadowMap.mShadowMap[i].data_ptr() for i in range(4)])
         check(lib.crychic_fog(self.ctx.handle, C.byref(self.mMainPassCB), self.mDepthStencilBuffer.data_ptr(), maps, self.mShadowMap.Width(),
                               _ptr(src), _ptr(out), W, H, int(row0), int(H - row0 if rows is None else rows),
@@ -653,15 +559,7 @@ class Crychic:
         """crychic_antialias on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferAA, allocated on first
         use) from `src` (default: mBackBuffer), both (H, W, 4) uint8 tensors; params: an AAParams, None = the defaults.  The pass reads
         rows [row0 - 16, row0 + rows + 16) of `src` and writes no other byte of `out`.  Returns `out`."""
-        src = self.mBackBuffer if src is None else src
-        if out is None:
-            if self.mBackBufferAA is None or self.mBackBufferAA.shape != src.shape or self.mBackBufferAA.device != src.device:
-                self.mBackBufferAA = torch.zeros_like(src)
-            out = self.mBackBufferAA
-        H, W = int(src.shape[0]), int(src.shape[1])
-        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] != 4 or out.shape != src.shape \
-                or not src.is_contiguous() or not out.is_contiguous():
-            raise CrychicError(-1, "antialias takes contiguous (H, W, 4) uint8 tensors of one shape")
+        src, out, H, W = self._pass_frames("antialias", "mBackBufferAA", src, out, any_shape=True)
         check(lib.crychic_antialias(self.ctx.handle, _ptr(src), _ptr(out), W, H, int(row0), int(H - row0 if rows is None else rows),
                                     None if params is None else C.byref(params), _stream(self.ctx.device)))
         return out

@@ -161,11 +161,11 @@ public:
     void OnResize()  // CRYCHIC.cpp:110-128 (+ D3DApp::OnResize's back/depth buffer re-creation)
     {
         const size_t n = (size_t)mClientWidth * mClientHeight;
-        mDepthStencilBuffer = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
+        mDepthStencilBuffer = FramePlane();
         CrychicHipThrowIfFailed(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(mDepthStencilBuffer->Data()), 0x00FFFFFF, n));
-        mBackBuffer = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
-        if (mAntiAliasing) mBackBufferAA = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
-        if (mDepthOfField) mBackBufferDoF = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
+        mBackBuffer = FramePlane();
+        if (mAntiAliasing) mBackBufferAA = FramePlane();
+        if (mDepthOfField) mBackBufferDoF = FramePlane();
         if (mBloom) AllocateBloom();
         if (mTemporalAA) AllocateTemporalAA();                                                      // new history planes: the next frame is a reset frame
         if (mMotionBlur) AllocateMotionBlur();                                                      // the next frame counts as the first: no previous camera
@@ -210,24 +210,12 @@ public:
 
     void Draw(const GameTimer&)  // CRYCHIC.cpp:172-306, deferred branch
     {
-        if (mAntiAliasing && (!mWholeFrame || mComm))
-            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (anti-aliasing takes the whole frame on one GPU: no SetStrip / JoinNode)",
+        if ((!mWholeFrame || mComm) && (mAntiAliasing || mFog || mDepthOfField || mBloom || mTemporalAA || mMotionBlur)) {
+            const char* pass = mAntiAliasing ? "anti-aliasing" : mFog ? "fog" : mDepthOfField ? "depth of field" : mBloom ? "bloom"
+                             : mTemporalAA ? "temporal anti-aliasing" : "motion blur";
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, std::string("CRYCHIC::Draw (") + pass + " takes the whole frame on one GPU: no SetStrip / JoinNode)",
                                    __FILE__, __LINE__);
-        if (mFog && (!mWholeFrame || mComm))
-            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (fog takes the whole frame on one GPU: no SetStrip / JoinNode)", __FILE__,
-                                   __LINE__);
-        if (mDepthOfField && (!mWholeFrame || mComm))
-            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (depth of field takes the whole frame on one GPU: no SetStrip / JoinNode)",
-                                   __FILE__, __LINE__);
-        if (mBloom && (!mWholeFrame || mComm))
-            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (bloom takes the whole frame on one GPU: no SetStrip / JoinNode)", __FILE__,
-                                   __LINE__);
-        if (mTemporalAA && (!mWholeFrame || mComm))
-            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (temporal anti-aliasing takes the whole frame on one GPU: no SetStrip / JoinNode)",
-                                   __FILE__, __LINE__);
-        if (mMotionBlur && (!mWholeFrame || mComm))
-            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (motion blur takes the whole frame on one GPU: no SetStrip / JoinNode)", __FILE__,
-                                   __LINE__);
+        }
         if (mRunProducerPasses) {
             DrawSceneToShadowMap();                                                                 // :208
             if (mFuseCameraPasses) DrawNormalsDepthAndGBuffer();                                    // :214 + :236 on one rasterisation
@@ -294,58 +282,62 @@ public:
         else
             CrychicThrowIfFailed(crychic_draw_hot_path_point_shadows(md3dDevice->Ctx(), ssaoCB, passCB, &f, spots, L.mNumSpotLights, &sh, &psh,
                                                                      mCommandList->Stream()));
-        // SetFog: the finished frame through the fog pass, in place, behind the lighting pass and in front of the anti-aliasing
+        // The passes behind the lighting pass, in the chain's order (the comment above SetAntiAliasing).  `frame` is what the next
+        // stage reads: the fog works in place on it, every other stage writes a buffer of its own and hands that on.
+        const uint8_t* frame = f.out_rgba8_dev;
+        auto bytes = [](const std::unique_ptr<ID3D12Resource>& r) { return static_cast<uint8_t*>(r->Data()); };
         if (mFog)
             CrychicThrowIfFailed(crychic_fog(md3dDevice->Ctx(), passCB, f.depth_dev, f.shadow_dev, f.shadowDim, f.out_rgba8_dev, f.out_rgba8_dev,
                                              mClientWidth, mClientHeight, 0, mClientHeight, &mFogParams, mCommandList->Stream()));
-        // SetTemporalAA: the finished (and fogged) frame blended into the reprojected history, into its own back buffer, while the
-        // frame is still aligned with its depth plane; the later passes read that buffer
-        const uint8_t* lit = f.out_rgba8_dev;
-        if (mTemporalAA) {
+        if (mTemporalAA) {                      // blended into the reprojected history while the frame is still aligned with its depth plane
             crychic_taa_params tp = mTaaParams;
             if (mTaaReset) tp.flags |= CRYCHIC_TAA_RESET;
             ID3D12Resource* hin = mTaaHistory[mTaaHistoryIndex].get();
             ID3D12Resource* hout = mTaaHistory[mTaaHistoryIndex ^ 1].get();
-            CrychicThrowIfFailed(crychic_taa(md3dDevice->Ctx(), passCB, mTaaViewProj[0], mTaaViewProj[1], f.depth_dev, f.out_rgba8_dev,
+            CrychicThrowIfFailed(crychic_taa(md3dDevice->Ctx(), passCB, mTaaViewProj[0], mTaaViewProj[1], f.depth_dev, frame,
                                              mTaaReset ? nullptr : static_cast<const uint16_t*>(hin->Data()), static_cast<uint16_t*>(hout->Data()),
-                                             static_cast<uint8_t*>(mBackBufferTAA->Data()), mClientWidth, mClientHeight, 0, mClientHeight, &tp,
-                                             mCommandList->Stream()));
+                                             bytes(mBackBufferTAA), mClientWidth, mClientHeight, 0, mClientHeight, &tp, mCommandList->Stream()));
             mTaaHistoryIndex ^= 1;
             mTaaReset = false;
-            lit = static_cast<const uint8_t*>(mBackBufferTAA->Data());
+            frame = bytes(mBackBufferTAA);
         }
-        // SetDepthOfField: the finished (and fogged) frame through the lens blur into its own back buffer, in front of the anti-aliasing
-        if (mDepthOfField)
-            CrychicThrowIfFailed(crychic_dof(md3dDevice->Ctx(), passCB, f.depth_dev, lit, static_cast<uint8_t*>(mBackBufferDoF->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
-                                             &mDofParams, mCommandList->Stream()));
-        // SetMotionBlur: the frame as it stands blurred along the camera's motion since the previous Update, into its own back buffer
-        if (mMotionBlur) {
-            CrychicThrowIfFailed(crychic_motion_blur(md3dDevice->Ctx(), passCB, mMbViewProj[0], mMbViewProj[1], f.depth_dev,
-                                                     mDepthOfField ? static_cast<const uint8_t*>(mBackBufferDoF->Data()) : lit,
-                                                     static_cast<uint8_t*>(mBackBufferMB->Data()), mClientWidth, mClientHeight, &mMbParams,
-                                                     mMbWorkspace->Data(), mMbWorkspace->Bytes(), mCommandList->Stream()));
+        if (mDepthOfField) {
+            CrychicThrowIfFailed(crychic_dof(md3dDevice->Ctx(), passCB, f.depth_dev, frame, bytes(mBackBufferDoF), mClientWidth, mClientHeight, 0,
+                                             mClientHeight, &mDofParams, mCommandList->Stream()));
+            frame = bytes(mBackBufferDoF);
         }
-        // SetBloom: the frame as it stands (fogged, through the lens blur and the motion blur) with its highlights spread, into its own back buffer
-        if (mBloom)
-            CrychicThrowIfFailed(crychic_bloom(md3dDevice->Ctx(), mMotionBlur ? static_cast<const uint8_t*>(mBackBufferMB->Data()) : (mDepthOfField ? static_cast<const uint8_t*>(mBackBufferDoF->Data()) : (mTemporalAA ? lit : static_cast<const uint8_t*>(mBackBuffer->Data()))),
-                                               static_cast<uint8_t*>(mBackBufferBloom->Data()), mClientWidth, mClientHeight, &mBloomParams,
+        if (mMotionBlur) {                      // along the camera's motion since the previous Update
+            CrychicThrowIfFailed(crychic_motion_blur(md3dDevice->Ctx(), passCB, mMbViewProj[0], mMbViewProj[1], f.depth_dev, frame, bytes(mBackBufferMB),
+                                                     mClientWidth, mClientHeight, &mMbParams, mMbWorkspace->Data(), mMbWorkspace->Bytes(),
+                                                     mCommandList->Stream()));
+            frame = bytes(mBackBufferMB);
+        }
+        if (mBloom) {
+            CrychicThrowIfFailed(crychic_bloom(md3dDevice->Ctx(), frame, bytes(mBackBufferBloom), mClientWidth, mClientHeight, &mBloomParams,
                                                mBloomWorkspace->Data(), mBloomWorkspace->Bytes(), mCommandList->Stream()));
-        // SetAntiAliasing: the finished frame through the post-process pass into the second back buffer, behind the lighting pass
+            frame = bytes(mBackBufferBloom);
+        }
         if (mAntiAliasing)
-            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), static_cast<const uint8_t*>((mBloom ? mBackBufferBloom : (mMotionBlur ? mBackBufferMB : (mDepthOfField ? mBackBufferDoF : (mTemporalAA ? mBackBufferTAA : mBackBuffer))))->Data()),
-                                                   static_cast<uint8_t*>(mBackBufferAA->Data()), mClientWidth, mClientHeight, 0, mClientHeight,
+            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), frame, bytes(mBackBufferAA), mClientWidth, mClientHeight, 0, mClientHeight,
                                                    &mAAParams, mCommandList->Stream()));
         // :300-305: advance the fence and signal it behind this frame's commands
         mCurrFrameResource->Fence = ++mCurrentFence;
         CrychicHipThrowIfFailed(hipEventRecord(mCurrFrameResource->FenceEvent, mCommandList->Stream()));
     }
 
-    // ---- anti-aliasing (extension) ----------------------------------------------------------------------------------------------
+    // ---- the passes behind the lighting pass (extensions) -----------------------------------------------------------------------------
+    // Six switches, all off by default (then nothing changes).  With any of them on, Draw takes a whole frame on one GPU -- SetStrip /
+    // JoinNode make it throw, the passes are not sharded -- and issues those that are on behind the lighting pass in the order
+    //     lighting -> fog (in place) -> temporal anti-aliasing -> depth of field -> motion blur -> bloom -> anti-aliasing.
+    // The fog works in place on the back buffer.  Every other stage reads the buffer of the nearest stage in front of it that is on
+    // and writes one (the back buffer if there is none) and writes a buffer of its own, which exists while the stage is on and which
+    // OnResize re-creates; Present writes the last one.  CurrentBackBuffer stays the (fogged) frame without them.  A setter's p == nullptr:
+    // the pass's default parameters; parameters outside their ranges are refused and leave the switch as it was.
+
+    // ---- anti-aliasing ------------------------------------------------------------------------------------------------------------
     // The deferred path's stand-in for the framework's Set4xMsaaState (Common/d3dApp.cpp:60-70, F2 at :367): MSAA does not compose
     // with a G-buffer, so edges are smoothed by a post-process pass over the finished frame (include/crychic_hip.h
-    // crychic_antialias).  On: Draw issues the pass after the lighting pass of a whole frame, into a second back buffer that OnResize
-    // re-creates, and Present writes that buffer; CurrentBackBuffer stays the frame without it.  p == nullptr: the default
-    // parameters.  With it on, SetStrip / JoinNode make Draw throw (the pass is not sharded).  Off (the default): nothing changes.
+    // crychic_antialias).
     void SetAntiAliasing(bool on, const crychic_aa_params* p = nullptr)
     {
         crychic_aa_params q;
@@ -357,16 +349,14 @@ public:
         mCommandList->Flush();                                  // a frame in flight may still write the buffer released below
         mAntiAliasing = on;
         mAAParams = q;
-        if (on) mBackBufferAA = std::make_unique<ID3D12Resource>((size_t)mClientWidth * mClientHeight * 4, ID3D12Resource::DEFAULT_HEAP);
+        if (on) mBackBufferAA = FramePlane();
         else mBackBufferAA.reset();
     }
     bool AntiAliasing() const { return mAntiAliasing; }
     ID3D12Resource* AntiAliasedBackBuffer() { return mBackBufferAA.get(); }
 
-    // ---- fog (extension) ----------------------------------------------------------------------------------------------------------
-    // Volumetric fog with sun shafts through the cascade maps (include/crychic_hip.h crychic_fog).  On: Draw issues the pass after the
-    // lighting pass of a whole frame, in place on the back buffer, in front of the anti-aliasing if that is on too.  p == nullptr: the
-    // default parameters.  With it on, SetStrip / JoinNode make Draw throw (the pass is not sharded).  Off (the default): nothing changes.
+    // ---- fog ------------------------------------------------------------------------------------------------------------------------
+    // Volumetric fog with sun shafts through the cascade maps (include/crychic_hip.h crychic_fog), in place on the back buffer.
     void SetFog(bool on, const crychic_fog_params* p = nullptr)
     {
         crychic_fog_params q;
@@ -381,12 +371,8 @@ public:
     }
     bool Fog() const { return mFog; }
 
-    // ---- depth of field (extension) -------------------------------------------------------------------------------------------------
-    // A thin-lens blur from the depth plane (include/crychic_hip.h crychic_dof).  On: Draw issues the pass after the lighting pass of a
-    // whole frame (and after the fog, if that is on), from the back buffer into a buffer of its own that OnResize re-creates; the
-    // anti-aliasing, if on too, then reads that buffer, and Present writes the last stage's output.  CurrentBackBuffer stays the frame
-    // without it.  p == nullptr: the default parameters.  With it on, SetStrip / JoinNode make Draw throw (the pass is not sharded).
-    // Off (the default): nothing changes.
+    // ---- depth of field ----------------------------------------------------------------------------------------------------------------
+    // A thin-lens blur from the depth plane (include/crychic_hip.h crychic_dof).
     void SetDepthOfField(bool on, const crychic_dof_params* p = nullptr)
     {
         crychic_dof_params q;
@@ -400,19 +386,15 @@ public:
         mCommandList->Flush();                                  // a frame in flight may still write the buffer released below
         mDepthOfField = on;
         mDofParams = q;
-        if (on) mBackBufferDoF = std::make_unique<ID3D12Resource>((size_t)mClientWidth * mClientHeight * 4, ID3D12Resource::DEFAULT_HEAP);
+        if (on) mBackBufferDoF = FramePlane();
         else mBackBufferDoF.reset();
     }
     bool DepthOfField() const { return mDepthOfField; }
     ID3D12Resource* DepthOfFieldBackBuffer() { return mBackBufferDoF.get(); }
 
-    // ---- bloom (extension) ------------------------------------------------------------------------------------------------------------
-    // Highlights over a luma threshold spread through a pyramid and added back (include/crychic_hip.h crychic_bloom).  On: Draw issues
-    // the pass after the lighting pass of a whole frame (and after the fog and the depth of field, if they are on), from the frame as
-    // it then stands into a buffer of its own, through a workspace this object owns; OnResize re-creates both.  The anti-aliasing, if
-    // on too, then reads that buffer, and Present writes the last stage's output.  CurrentBackBuffer stays the frame without it.
-    // p == nullptr: the default parameters.  With it on, SetStrip / JoinNode make Draw throw (the pass is not sharded).  Off (the
-    // default): nothing changes.
+    // ---- bloom ----------------------------------------------------------------------------------------------------------------------
+    // Highlights over a luma threshold spread through a pyramid and added back (include/crychic_hip.h crychic_bloom), through a
+    // workspace this object owns while the pass is on; OnResize re-creates it with the buffer.
     void SetBloom(bool on, const crychic_bloom_params* p = nullptr)
     {
         crychic_bloom_params q;
@@ -432,14 +414,12 @@ public:
     bool Bloom() const { return mBloom; }
     ID3D12Resource* BloomBackBuffer() { return mBackBufferBloom.get(); }
 
-    // ---- temporal anti-aliasing (extension) -----------------------------------------------------------------------------------------
+    // ---- temporal anti-aliasing ---------------------------------------------------------------------------------------------------------
     // Jittered frames blended into a reprojected history (include/crychic_hip.h crychic_taa).  On: Update shifts the projection of the
     // main pass and SSAO constants by the frame's sub-pixel offset (crychic_taa_jitter of a running frame index) and keeps the
-    // unjittered ViewProj of this frame and of the previous one; Draw issues the pass after the lighting pass of a whole frame and
-    // the fog, from the back buffer into a buffer of its own that the depth of field, the bloom and the anti-aliasing then read and
-    // Present writes, through two history planes this object owns and swaps.  The first frame after it was turned on, and after
-    // OnResize, is a reset frame.  CurrentBackBuffer stays the jittered frame without the pass.  With it on, SetStrip / JoinNode
-    // make Draw throw (the pass is not sharded).  Off (the default): nothing changes.
+    // unjittered ViewProj of this frame and of the previous one; Draw issues the pass through two history planes this object owns
+    // and swaps.  The first frame after it was turned on, and after OnResize, is a reset frame.  CurrentBackBuffer is then the
+    // jittered frame.
     void SetTemporalAA(bool on)
     {
         crychic_taa_params q;
@@ -453,13 +433,10 @@ public:
     const float* TemporalAAViewProj(int previous) const { return mTaaViewProj[previous ? 1 : 0]; }   // unjittered, of the last Update
     const float* TemporalAAJitter() const { return mTaaJitter; }                            // the last Update's offset in pixels
 
-    // ---- motion blur (extension) ------------------------------------------------------------------------------------------------------
+    // ---- motion blur ------------------------------------------------------------------------------------------------------------------
     // Camera motion turned into blur (include/crychic_hip.h crychic_motion_blur).  On: Update keeps the unjittered ViewProj of this
     // frame and of the previous one (the first frame after it was turned on, and after OnResize, has no previous one: a still
-    // camera); Draw issues the pass behind the depth of field and in front of the bloom and the anti-aliasing, from the frame as it
-    // then stands into a buffer of its own, through a workspace this object owns; the bloom and the anti-aliasing then read that
-    // buffer and Present writes the last stage's output.  CurrentBackBuffer stays the frame without it.  p == nullptr: the default
-    // parameters.  With it on, SetStrip / JoinNode make Draw throw (the pass is not sharded).  Off (the default): nothing changes.
+    // camera); Draw issues the pass through a workspace this object owns while the pass is on.
     void SetMotionBlur(bool on, const crychic_motion_blur_params* p = nullptr)
     {
         crychic_motion_blur_params q;
@@ -730,12 +707,12 @@ public:
         SetWholeFrame();
     }
 
-    // mSwapChain->Present (CRYCHIC.cpp:294-297) for a headless build: read the back buffer back and write it as PPM (with
-    // SetAntiAliasing on: the anti-aliased one).
+    // mSwapChain->Present (CRYCHIC.cpp:294-297) for a headless build: read the finished frame back -- the buffer of the last stage
+    // that is on, the back buffer if none is -- and write it as PPM.
     void Present(const std::string& path)
     {
         std::vector<uint8_t> host((size_t)mClientWidth * mClientHeight * 4);
-        (mAntiAliasing ? mBackBufferAA : (mBloom ? mBackBufferBloom : (mMotionBlur ? mBackBufferMB : (mDepthOfField ? mBackBufferDoF : (mTemporalAA ? mBackBufferTAA : mBackBuffer)))))->Download(host.data(), host.size(), mCommandList->Stream());
+        FinalFrame()->Download(host.data(), host.size(), mCommandList->Stream());
         mCommandList->Flush();
         CrychicThrowIfFailed(crychic_save_ppm(path.c_str(), host.data(), mClientWidth, mClientHeight));
     }
@@ -1245,7 +1222,7 @@ private:
     std::unique_ptr<ID3D12Resource> mBloomWorkspace;   // its pyramid: the frame's size at the most levels, so any parameters fit
     void AllocateBloom()
     {
-        mBackBufferBloom = std::make_unique<ID3D12Resource>((size_t)mClientWidth * mClientHeight * 4, ID3D12Resource::DEFAULT_HEAP);
+        mBackBufferBloom = FramePlane();
         mBloomWorkspace = std::make_unique<ID3D12Resource>(crychic_bloom_workspace_bytes(mClientWidth, mClientHeight, CRYCHIC_BLOOM_MAX_LEVELS),
                                                            ID3D12Resource::DEFAULT_HEAP);
     }
@@ -1260,8 +1237,7 @@ private:
     float mTaaViewProj[2][16] = {};           // the unjittered ViewProj of this frame and of the previous one (stored transposed)
     void AllocateTemporalAA()
     {
-        const size_t n = (size_t)mClientWidth * mClientHeight;
-        mBackBufferTAA = std::make_unique<ID3D12Resource>(n * 4, ID3D12Resource::DEFAULT_HEAP);
+        mBackBufferTAA = FramePlane();
         for (auto& h : mTaaHistory) h = std::make_unique<ID3D12Resource>(crychic_taa_history_bytes(mClientWidth, mClientHeight), ID3D12Resource::DEFAULT_HEAP);
         mTaaHistoryIndex = 0;
         mTaaReset = true;
@@ -1286,13 +1262,22 @@ private:
     float mMbViewProj[2][16] = {};            // the unjittered ViewProj of this frame and of the previous one (stored transposed)
     void AllocateMotionBlur()
     {
-        mBackBufferMB = std::make_unique<ID3D12Resource>((size_t)mClientWidth * mClientHeight * 4, ID3D12Resource::DEFAULT_HEAP);
+        mBackBufferMB = FramePlane();
         mMbWorkspace = std::make_unique<ID3D12Resource>(crychic_motion_blur_workspace_bytes(mClientWidth, mClientHeight), ID3D12Resource::DEFAULT_HEAP);
         mMbFirst = true;
     }
     bool mAntiAliasing = false;               // SetAntiAliasing
     crychic_aa_params mAAParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferAA;   // the anti-aliased frame, while mAntiAliasing
+    std::unique_ptr<ID3D12Resource> FramePlane() const      // a plane of the frame's size at four bytes a pixel: RGBA8, or the depth plane
+    {
+        return std::make_unique<ID3D12Resource>((size_t)mClientWidth * mClientHeight * 4, ID3D12Resource::DEFAULT_HEAP);
+    }
+    ID3D12Resource* FinalFrame() const           // where Draw leaves the finished frame: the buffer of the last stage that is on
+    {
+        return (mAntiAliasing ? mBackBufferAA : mBloom ? mBackBufferBloom : mMotionBlur ? mBackBufferMB : mDepthOfField ? mBackBufferDoF
+                : mTemporalAA ? mBackBufferTAA : mBackBuffer).get();
+    }
     std::unique_ptr<ID3D12Resource> mDepthStencilBuffer, mBackBuffer, mCubeMap;
     std::unique_ptr<ID3D12Resource> mPointLights, mSpotLights;   // SetLocalLights
     uint32_t mNumPointLights = 0, mNumSpotLights = 0;

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import motion_blur_lib as mbl
+from recorder_lib import Recorder
 
 pytestmark = pytest.mark.gpu
 
@@ -249,23 +250,6 @@ def test_the_passes_in_front_and_behind(dev, app_frame):
     finally:
         app.fog, app.temporalAA, app.depthOfField, app.motionBlur, app.bloom, app.antiAliasing = None, None, None, None, None, None
         app._taaViewProj = [None, None]
-
-
-class Recorder:
-    """The library with every crychic_* call of its user recorded by name."""
-
-    def __init__(self, lib):
-        self._lib, self.calls = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith("crychic_"):
-            return fn
-
-        def wrapped(*a):
-            self.calls.append(name)
-            return fn(*a)
-        return wrapped
 
 
 def test_switch_off_is_the_frame_and_the_calls_of_before(dev, app_frame, monkeypatch):

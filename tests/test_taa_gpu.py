@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import taa_lib as ta
+from recorder_lib import Recorder
 
 pytestmark = pytest.mark.gpu
 
@@ -241,23 +242,6 @@ def test_fog_in_front_and_the_other_passes_behind(dev, app_frame):
         assert app.fog is True and app.temporalAA is True and app.antiAliasing is True
     finally:
         app.fog, app.temporalAA, app.depthOfField, app.bloom, app.antiAliasing = None, None, None, None, None
-
-
-class Recorder:
-    """The library with every crychic_* call of its user recorded by name."""
-
-    def __init__(self, lib):
-        self._lib, self.calls = lib, []
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-        if not name.startswith("crychic_"):
-            return fn
-
-        def wrapped(*a):
-            self.calls.append(name)
-            return fn(*a)
-        return wrapped
 
 
 def test_switch_off_is_the_frame_and_the_calls_of_before(dev, app_frame, monkeypatch):
