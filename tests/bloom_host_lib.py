@@ -2,11 +2,11 @@
 host with the workgroups, the LDS arrays, the barriers and the votes emulated."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from hostsim_lib import CLANG, CSRC, ROOT
+from hostsim_lib import ROOT
+from post_pass_lib import build_host_shim
 import bloom_lib
 
 DIR = os.path.join(ROOT, "tests", "bloom_host")
@@ -15,11 +15,7 @@ STATS = ("groups", "zero_tiles", "silent_waves", "vec_composites")
 
 
 def build():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("bloom_core.hpp", "devmath.hpp", "gamma_pow.inc")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.run([CLANG, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-I", CSRC, SRC, "-o", LIB],
-                       check=True)
-    return LIB
+    return build_host_shim(SRC, LIB, ("bloom_core.hpp", "devmath.hpp", "gamma_pow.inc"))
 
 
 _LIB = None

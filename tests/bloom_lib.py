@@ -3,11 +3,10 @@ include/crychic_hip.h with none of the kernels' code; a Python restatement of th
 parameter sets the host and the device tests share."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from dof_lib import GUARD, guarded, guards_intact      # noqa: F401 -- the guarded planes of the post passes' tests
+from post_pass_lib import GUARD, build_checker, guarded, guards_intact      # noqa: F401 -- what the post passes' tests share
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIR = os.path.join(ROOT, "tests", "bloom_ref")
@@ -34,9 +33,7 @@ SIZES = ((1, 1), (2, 3), (7, 5), (33, 17), (64, 64), (65, 63), (129, 97), (322, 
 
 
 def build():
-    if not os.path.exists(LIB) or os.path.getmtime(SRC) > os.path.getmtime(LIB):
-        subprocess.run(["gcc", "-O2", "-std=c99", "-fPIC", "-Wall", "-shared", "-o", LIB, SRC], check=True)
-    return LIB
+    return build_checker(SRC, LIB, fp=False)
 
 
 # ---- the layout, restated ---------------------------------------------------------------------------------------------------------

@@ -4,67 +4,29 @@
 // planes), then cleared (plain_again.bin), then with the decals as a strip of the frame (g1_strip.bin: the strip's rows decaled, the
 // others as the plain frame left them); too many decals must be refused (tests/test_decal_veneer.py).
 // Usage: decal_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <numDirLights> <texW> <texH> <texLevels> <strip row0> <strip rows>
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "crychic/CRYCHIC.h"
-
-static std::vector<char> slurp(const std::string& p)
-{
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", p.c_str()); std::exit(2); }
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void dump(const std::string& p, const void* d, size_t n)
-{
-    std::ofstream f(p, std::ios::binary);
-    f.write(static_cast<const char*>(d), (std::streamsize)n);
-}
+#include "driver_util.hpp"
 
 int main(int argc, char** argv)
 {
-    if (argc < 13) { std::fprintf(stderr, "usage\n"); return 2; }
-    const std::string dir = argv[1];
-    const UINT W = std::atoi(argv[2]), H = std::atoi(argv[3]), SD = std::atoi(argv[4]), CD = std::atoi(argv[5]);
-    const UINT texW = std::atoi(argv[8]), texH = std::atoi(argv[9]), texLevels = std::atoi(argv[10]), stripRow0 = std::atoi(argv[11]), stripRows = std::atoi(argv[12]);
-    try {
-        CRYCHIC app(0, W, H);
-        app.mShadowMapSize = SD;
-        app.mBlurCount = std::atoi(argv[6]);
-        app.mNumDirLights = std::atoi(argv[7]);
-        app.mSkyEnabled = true;
-        app.mRunProducerPasses = true;
-        if (!app.Initialize()) return 3;
-        hipStream_t s = app.CommandList()->Stream();
+    return run_post_driver(argc, argv, [argv](PostDriver& d) {
+        CRYCHIC& app = d.app;
+        const std::string& dir = d.dir;
+        const UINT W = d.W, H = d.H;
+        const UINT texW = std::atoi(argv[8]), texH = std::atoi(argv[9]), texLevels = std::atoi(argv[10]), stripRow0 = std::atoi(argv[11]), stripRows = std::atoi(argv[12]);
         if (app.DecalCount() != 0) { std::fprintf(stderr, "decals are set by default\n"); return 4; }
-        auto cubeBytes = slurp(dir + "/cube.bin");
-        auto cube = std::make_unique<ID3D12Resource>((size_t)6 * CD * CD * 4, ID3D12Resource::DEFAULT_HEAP);
-        if (cubeBytes.size() != cube->Bytes()) { std::fprintf(stderr, "cube.bin size\n"); return 2; }
-        cube->Upload(cubeBytes.data(), cubeBytes.size(), s);
         auto texBytes = slurp(dir + "/tex.bin");
         auto tex = std::make_unique<ID3D12Resource>(texBytes.size(), ID3D12Resource::DEFAULT_HEAP);
-        tex->Upload(texBytes.data(), texBytes.size(), s);
-        CrychicHipThrowIfFailed(hipStreamSynchronize(s));
-        app.SetCubeMap(std::move(cube), CD);
+        tex->Upload(texBytes.data(), texBytes.size(), d.s);
+        CrychicHipThrowIfFailed(hipStreamSynchronize(d.s));
         auto decalBytes = slurp(dir + "/decals.bin");
         const uint32_t n = (uint32_t)(decalBytes.size() / sizeof(crychic_decal));
         const crychic_decal* decals = reinterpret_cast<const crychic_decal*>(decalBytes.data());
         const crychic_texture table[1] = { { static_cast<const uint8_t*>(tex->Data()), texW, texH, texLevels } };
 
-        GameTimer gt;
-        auto frame = [&] { gt.Tick(1.0f / 60.0f); app.Update(gt); app.Draw(gt); app.CommandList()->Flush(); };
-        auto grab = [&](ID3D12Resource* r, const std::string& name) {
-            std::vector<char> h(r->Bytes());
-            r->Download(h.data(), h.size(), s);
-            app.CommandList()->Flush();
-            dump(dir + "/" + name, h.data(), h.size());
-        };
-        frame();
-        grab(app.CurrentBackBuffer(), "plain.bin");
-        grab(app.DepthStencilBuffer(), "depth.bin");
-        for (int i = 0; i < 3; ++i) grab(app.mDeferred->Resource(i), "g" + std::to_string(i) + ".bin");
+        d.frame();
+        d.grab(app.CurrentBackBuffer(), "plain.bin");
+        d.grab(app.DepthStencilBuffer(), "depth.bin");
+        for (int i = 0; i < 3; ++i) d.grab(app.mDeferred->Resource(i), "g" + std::to_string(i) + ".bin");
         dump(dir + "/pass_cb.bin", &app.mMainPassCB, sizeof app.mMainPassCB);
 
         // more decals than the pass takes are refused and leave none set
@@ -75,25 +37,22 @@ int main(int argc, char** argv)
 
         app.SetDecals(decals, n, table, 1);
         if (app.DecalCount() != n) { std::fprintf(stderr, "SetDecals\n"); return 6; }
-        frame();
-        grab(app.CurrentBackBuffer(), "decal.bin");
-        for (int i = 0; i < 3; ++i) grab(app.mDeferred->Resource(i), "g" + std::to_string(i) + "_decal.bin");
+        d.frame();
+        d.grab(app.CurrentBackBuffer(), "decal.bin");
+        for (int i = 0; i < 3; ++i) d.grab(app.mDeferred->Resource(i), "g" + std::to_string(i) + "_decal.bin");
 
         app.ClearDecals();
         if (app.DecalCount() != 0) { std::fprintf(stderr, "ClearDecals\n"); return 7; }
-        frame();
-        grab(app.CurrentBackBuffer(), "plain_again.bin");
+        d.frame();
+        d.grab(app.CurrentBackBuffer(), "plain_again.bin");
 
         // a strip: the producers and the decals touch its rows alone
         app.SetDecals(decals, n, table, 1);
         app.SetStrip(stripRow0, stripRows);
-        frame();
-        grab(app.mDeferred->Resource(1), "g1_strip.bin");
+        d.frame();
+        d.grab(app.mDeferred->Resource(1), "g1_strip.bin");
         app.SetWholeFrame();
         std::printf("decal driver ok %ux%u %u decals\n", W, H, n);
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "exception: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    }, 13);
 }

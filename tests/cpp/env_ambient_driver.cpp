@@ -6,24 +6,7 @@
 // and its tail), then a frame with it bound: out.bin, pass_cb.bin, ssao_cb.bin.
 // Usage: env_ambient_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <dim> <captureShadowDim> <x> <y> <z> <gloss>
 // <dir> holds cube.bin, the one-level source cube map of <cubeDim>.
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "crychic/CRYCHIC.h"
-
-static std::vector<char> slurp(const std::string& p)
-{
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", p.c_str()); std::exit(2); }
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void dump(const std::string& p, const void* d, size_t n)
-{
-    std::ofstream f(p, std::ios::binary);
-    f.write(static_cast<const char*>(d), (std::streamsize)n);
-}
+#include "driver_util.hpp"
 
 int main(int argc, char** argv)
 {

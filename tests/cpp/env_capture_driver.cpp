@@ -6,25 +6,9 @@
 // Usage: env_capture_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <dim> <levels> <captureShadowDim> <x> <y> <z> [lights]
 // <dir> holds cube.bin, the one-level source cube map of <cubeDim>; with `lights` also points.bin and spots.bin (arrays of Light):
 // SetLocalLights with both and SetSpotShadows(1, 128, pi / 2, 0.5), so that the probe reads this object's lights and shadow map.
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "crychic/CRYCHIC.h"
+#include "driver_util.hpp"
 
-static std::vector<char> slurp(const std::string& p)
-{
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", p.c_str()); std::exit(2); }
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void dump(const std::string& p, const void* d, size_t n)
-{
-    std::ofstream f(p, std::ios::binary);
-    f.write(static_cast<const char*>(d), (std::streamsize)n);
-}
 static std::vector<Light> lights(const std::string& path)
 {
     auto b = slurp(path);

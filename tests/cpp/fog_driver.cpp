@@ -4,59 +4,19 @@
 // fog_aa.bin = the second back buffer), then off again (plain_again.bin); a parameter outside its range must be refused, and a strip
 // with the switch on must make Draw throw (tests/test_fog_veneer.py).
 // Usage: fog_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <numDirLights>
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "crychic/CRYCHIC.h"
-
-static std::vector<char> slurp(const std::string& p)
-{
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", p.c_str()); std::exit(2); }
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void dump(const std::string& p, const void* d, size_t n)
-{
-    std::ofstream f(p, std::ios::binary);
-    f.write(static_cast<const char*>(d), (std::streamsize)n);
-}
+#include "driver_util.hpp"
 
 int main(int argc, char** argv)
 {
-    if (argc < 8) { std::fprintf(stderr, "usage\n"); return 2; }
-    const std::string dir = argv[1];
-    const UINT W = std::atoi(argv[2]), H = std::atoi(argv[3]), SD = std::atoi(argv[4]), CD = std::atoi(argv[5]);
-    try {
-        CRYCHIC app(0, W, H);
-        app.mShadowMapSize = SD;
-        app.mBlurCount = std::atoi(argv[6]);
-        app.mNumDirLights = std::atoi(argv[7]);
-        app.mSkyEnabled = true;
-        app.mRunProducerPasses = true;
-        if (!app.Initialize()) return 3;
-        hipStream_t s = app.CommandList()->Stream();
+    return run_post_driver(argc, argv, [](PostDriver& d) {
+        CRYCHIC& app = d.app;
+        const std::string& dir = d.dir;
+        const UINT W = d.W, H = d.H;
         if (app.Fog()) { std::fprintf(stderr, "fog is on by default\n"); return 4; }
-        auto cubeBytes = slurp(dir + "/cube.bin");
-        auto cube = std::make_unique<ID3D12Resource>((size_t)6 * CD * CD * 4, ID3D12Resource::DEFAULT_HEAP);
-        if (cubeBytes.size() != cube->Bytes()) { std::fprintf(stderr, "cube.bin size\n"); return 2; }
-        cube->Upload(cubeBytes.data(), cubeBytes.size(), s);
-        CrychicHipThrowIfFailed(hipStreamSynchronize(s));
-        app.SetCubeMap(std::move(cube), CD);
-
-        GameTimer gt;
-        auto frame = [&] { gt.Tick(1.0f / 60.0f); app.Update(gt); app.Draw(gt); app.CommandList()->Flush(); };
-        auto grab = [&](ID3D12Resource* r, const std::string& name) {
-            std::vector<char> h(r->Bytes());
-            r->Download(h.data(), h.size(), s);
-            app.CommandList()->Flush();
-            dump(dir + "/" + name, h.data(), h.size());
-        };
-        frame();
-        grab(app.CurrentBackBuffer(), "plain.bin");
-        grab(app.DepthStencilBuffer(), "depth.bin");
-        for (int i = 0; i < 4; ++i) grab(app.mShadowMap->Resource(i), "shadow" + std::to_string(i) + ".bin");
+        d.frame();
+        d.grab(app.CurrentBackBuffer(), "plain.bin");
+        d.grab(app.DepthStencilBuffer(), "depth.bin");
+        for (int i = 0; i < 4; ++i) d.grab(app.mShadowMap->Resource(i), "shadow" + std::to_string(i) + ".bin");
         dump(dir + "/pass_cb.bin", &app.mMainPassCB, sizeof app.mMainPassCB);
 
         // a parameter outside its range is refused and leaves the switch as it was
@@ -69,14 +29,14 @@ int main(int argc, char** argv)
 
         app.SetFog(true);
         if (!app.Fog()) { std::fprintf(stderr, "SetFog(true)\n"); return 6; }
-        frame();
-        grab(app.CurrentBackBuffer(), "fog.bin");
+        d.frame();
+        d.grab(app.CurrentBackBuffer(), "fog.bin");
 
         // a strip with the switch on: Draw throws, and the whole frame works again afterwards
         app.SetStrip(0, H / 2);
-        gt.Tick(1.0f / 60.0f);
-        app.Update(gt);
-        try { app.Draw(gt); } catch (const CrychicException& e) { refused += e.Status == CRYCHIC_E_INVALID_ARG; }
+        d.gt.Tick(1.0f / 60.0f);
+        app.Update(d.gt);
+        try { app.Draw(d.gt); } catch (const CrychicException& e) { refused += e.Status == CRYCHIC_E_INVALID_ARG; }
         if (refused != 2) { std::fprintf(stderr, "a strip with fog on did not throw\n"); return 7; }
         app.SetWholeFrame();
 
@@ -85,26 +45,23 @@ int main(int argc, char** argv)
         crychic_fog_default_params(&p);
         p.density = 0.08f; p.steps = 7; p.sun[0] = 250; p.sun[1] = 200; p.sun[2] = 90;
         app.SetFog(true, &p);
-        frame();
-        grab(app.CurrentBackBuffer(), "fog_params.bin");
+        d.frame();
+        d.grab(app.CurrentBackBuffer(), "fog_params.bin");
 
         // with the anti-aliasing: lighting, fog in place, then the anti-aliasing of the fogged frame into the second back buffer
         app.SetFog(true);
         app.SetAntiAliasing(true);
-        frame();
-        grab(app.CurrentBackBuffer(), "fog_frame.bin");
-        grab(app.AntiAliasedBackBuffer(), "fog_aa.bin");
+        d.frame();
+        d.grab(app.CurrentBackBuffer(), "fog_frame.bin");
+        d.grab(app.AntiAliasedBackBuffer(), "fog_aa.bin");
         app.SetAntiAliasing(false);
 
         // off again
         app.SetFog(false);
         if (app.Fog()) { std::fprintf(stderr, "SetFog(false)\n"); return 9; }
-        frame();
-        grab(app.CurrentBackBuffer(), "plain_again.bin");
+        d.frame();
+        d.grab(app.CurrentBackBuffer(), "plain_again.bin");
         std::printf("fog driver ok %ux%u\n", W, H);
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "exception: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

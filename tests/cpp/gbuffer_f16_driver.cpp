@@ -3,24 +3,7 @@
 // CRYCHIC::SetGBufferFormat followed by Update / Draw on the application's built-in scene (producer passes included), and the
 // refusal of any other format.  The planes and the back buffer go back as raw files (tests/test_gbuffer_f16_gpu.py).
 // Usage: gbuffer_f16_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <numDirLights> <f32|mixed|f16>
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "crychic/CRYCHIC.h"
-
-static std::vector<char> slurp(const std::string& p)
-{
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", p.c_str()); std::exit(2); }
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void dump(const std::string& p, const void* d, size_t n)
-{
-    std::ofstream f(p, std::ios::binary);
-    f.write(static_cast<const char*>(d), (std::streamsize)n);
-}
+#include "driver_util.hpp"
 
 int main(int argc, char** argv)
 {

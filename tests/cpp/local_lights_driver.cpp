@@ -8,25 +8,9 @@
 // Usage: local_lights_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <numDirLights> <count> <dim>
 // <dir> holds the planes veneer_driver reads, points.bin and spots.bin (arrays of Light), randvec.bin (run 2's random-vector map),
 // spotmap<k>.bin (the first <count> maps, dim x dim D24) and scene_spots.bin (the spot light of run 3).
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "crychic/CRYCHIC.h"
+#include "driver_util.hpp"
 
-static std::vector<char> slurp(const std::string& p)
-{
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", p.c_str()); std::exit(2); }
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void dump(const std::string& p, const void* d, size_t n)
-{
-    std::ofstream f(p, std::ios::binary);
-    f.write(static_cast<const char*>(d), (std::streamsize)n);
-}
 static void put(ID3D12Resource* r, const std::string& path, hipStream_t s)
 {
     auto b = slurp(path);

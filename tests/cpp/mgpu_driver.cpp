@@ -9,20 +9,9 @@
 // Every rank writes <dir>/frame_<rank>.bin (the gathered frame); rank 0 also renders the whole frame alone into
 // <dir>/frame_single.bin.  The pytest side compares them byte for byte.  `ragged` uses strips of different heights.
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <string>
 #include <thread>
-#include <vector>
-#include "crychic/CRYCHIC.h"
-
-static void dump(const std::string& p, const void* d, size_t n)
-{
-    std::ofstream f(p, std::ios::binary);
-    f.write(static_cast<const char*>(d), (std::streamsize)n);
-}
+#include "driver_util.hpp"
 
 static std::unique_ptr<CRYCHIC> make_app(int device, UINT W, UINT H)
 {

@@ -6,61 +6,21 @@
 // of the bloom and the anti-aliasing (chain_*.bin), and off again (plain_again.bin).  Parameters outside their ranges must be refused,
 // and a strip with the switch on must make Draw throw (tests/test_motion_blur_veneer.py).
 // Usage: motion_blur_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <numDirLights>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "crychic/CRYCHIC.h"
-
-static std::vector<char> slurp(const std::string& p)
-{
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", p.c_str()); std::exit(2); }
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void dump(const std::string& p, const void* d, size_t n)
-{
-    std::ofstream f(p, std::ios::binary);
-    f.write(static_cast<const char*>(d), (std::streamsize)n);
-}
+#include "driver_util.hpp"
 
 int main(int argc, char** argv)
 {
-    if (argc < 8) { std::fprintf(stderr, "usage\n"); return 2; }
-    const std::string dir = argv[1];
-    const UINT W = std::atoi(argv[2]), H = std::atoi(argv[3]), SD = std::atoi(argv[4]), CD = std::atoi(argv[5]);
-    try {
-        CRYCHIC app(0, W, H);
-        app.mShadowMapSize = SD;
-        app.mBlurCount = std::atoi(argv[6]);
-        app.mNumDirLights = std::atoi(argv[7]);
-        app.mSkyEnabled = true;
-        app.mRunProducerPasses = true;
-        if (!app.Initialize()) return 3;
-        hipStream_t s = app.CommandList()->Stream();
+    return run_post_driver(argc, argv, [](PostDriver& d) {
+        CRYCHIC& app = d.app;
+        const std::string& dir = d.dir;
+        const UINT W = d.W, H = d.H;
         if (app.MotionBlur() || app.MotionBlurBackBuffer() || app.MotionBlurWorkspace()) { std::fprintf(stderr, "motion blur is on by default\n"); return 4; }
-        auto cubeBytes = slurp(dir + "/cube.bin");
-        auto cube = std::make_unique<ID3D12Resource>((size_t)6 * CD * CD * 4, ID3D12Resource::DEFAULT_HEAP);
-        if (cubeBytes.size() != cube->Bytes()) { std::fprintf(stderr, "cube.bin size\n"); return 2; }
-        cube->Upload(cubeBytes.data(), cubeBytes.size(), s);
-        CrychicHipThrowIfFailed(hipStreamSynchronize(s));
-        app.SetCubeMap(std::move(cube), CD);
-
-        GameTimer gt;
-        auto frame = [&] { gt.Tick(1.0f / 60.0f); app.Update(gt); app.Draw(gt); app.CommandList()->Flush(); };
-        auto grab = [&](ID3D12Resource* r, const std::string& name) {
-            std::vector<char> h(r->Bytes());
-            r->Download(h.data(), h.size(), s);
-            app.CommandList()->Flush();
-            dump(dir + "/" + name, h.data(), h.size());
-        };
         auto record = [&](const std::string& tag) {
-            grab(app.CurrentBackBuffer(), "in_" + tag + ".bin");
-            grab(app.DepthStencilBuffer(), "depth_" + tag + ".bin");
-            grab(app.MotionBlurBackBuffer(), "mb_" + tag + ".bin");
-            grab(app.MotionBlurWorkspace(), "ws_" + tag + ".bin");
+            d.grab(app.CurrentBackBuffer(), "in_" + tag + ".bin");
+            d.grab(app.DepthStencilBuffer(), "depth_" + tag + ".bin");
+            d.grab(app.MotionBlurBackBuffer(), "mb_" + tag + ".bin");
+            d.grab(app.MotionBlurWorkspace(), "ws_" + tag + ".bin");
             float m[48];
             std::memcpy(m, &app.mMainPassCB.InvViewProj, 64);
             std::memcpy(m + 16, app.MotionBlurViewProj(0), 64);
@@ -68,8 +28,8 @@ int main(int argc, char** argv)
             dump(dir + "/mats_" + tag + ".bin", m, sizeof m);
         };
         const DirectX::XMFLOAT3 home = app.mCamera.GetPosition3f();
-        frame();
-        grab(app.CurrentBackBuffer(), "plain.bin");
+        d.frame();
+        d.grab(app.CurrentBackBuffer(), "plain.bin");
 
         // parameters outside their ranges are refused and leave the switch as it was
         int refused = 0;
@@ -96,22 +56,22 @@ int main(int argc, char** argv)
         if (!app.MotionBlur() || !app.MotionBlurBackBuffer() || !app.MotionBlurWorkspace()) { std::fprintf(stderr, "SetMotionBlur(params)\n"); return 6; }
         for (int k = 0; k < 5; ++k) {
             if (k >= 2) app.mCamera.Strafe(0.15f * (float)k);
-            frame();
+            d.frame();
             record(std::to_string(k));
         }
 
         // a strip with the switch on: Draw throws, and the whole frame works again afterwards
         app.SetStrip(0, H / 2);
-        gt.Tick(1.0f / 60.0f);
-        app.Update(gt);
-        try { app.Draw(gt); } catch (const CrychicException& e) { refused += e.Status == CRYCHIC_E_INVALID_ARG; }
+        d.gt.Tick(1.0f / 60.0f);
+        app.Update(d.gt);
+        try { app.Draw(d.gt); } catch (const CrychicException& e) { refused += e.Status == CRYCHIC_E_INVALID_ARG; }
         if (refused != 7) { std::fprintf(stderr, "a strip with motion blur on did not throw\n"); return 7; }
         app.SetWholeFrame();
 
         // a resize (to the same size): the next frame has no previous camera, although the camera moves
         app.Resize(W, H);
         app.mCamera.Strafe(0.3f);
-        frame();
+        d.frame();
         record("resized");
 
         // behind the depth of field, in front of the bloom and the anti-aliasing, with the defaults
@@ -120,11 +80,11 @@ int main(int argc, char** argv)
         app.SetBloom(true);
         app.SetAntiAliasing(true);
         app.mCamera.Strafe(0.4f);
-        frame();
+        d.frame();
         record("chain");
-        grab(app.DepthOfFieldBackBuffer(), "chain_dof.bin");
-        grab(app.BloomBackBuffer(), "chain_bloom.bin");
-        grab(app.AntiAliasedBackBuffer(), "chain_aa.bin");
+        d.grab(app.DepthOfFieldBackBuffer(), "chain_dof.bin");
+        d.grab(app.BloomBackBuffer(), "chain_bloom.bin");
+        d.grab(app.AntiAliasedBackBuffer(), "chain_aa.bin");
         app.SetAntiAliasing(false);
         app.SetBloom(false);
         app.SetDepthOfField(false);
@@ -133,12 +93,9 @@ int main(int argc, char** argv)
         app.SetMotionBlur(false);
         if (app.MotionBlur() || app.MotionBlurBackBuffer() || app.MotionBlurWorkspace()) { std::fprintf(stderr, "SetMotionBlur(false)\n"); return 9; }
         app.mCamera.SetPosition(home.x, home.y, home.z);
-        frame();
-        grab(app.CurrentBackBuffer(), "plain_again.bin");
+        d.frame();
+        d.grab(app.CurrentBackBuffer(), "plain_again.bin");
         std::printf("motion blur driver ok %ux%u\n", W, H);
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "exception: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        return 0;
+    });
 }

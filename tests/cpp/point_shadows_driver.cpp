@@ -7,25 +7,9 @@
 // Usage: point_shadows_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <numDirLights> <count> <dim>
 // <dir> holds the planes veneer_driver reads, points.bin (an array of Light), pointmap<k>.bin (six dim x dim D24 faces of the first
 // <count> point lights) and scene_points.bin (the point light of run 2).
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "crychic/CRYCHIC.h"
+#include "driver_util.hpp"
 
-static std::vector<char> slurp(const std::string& p)
-{
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", p.c_str()); std::exit(2); }
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void dump(const std::string& p, const void* d, size_t n)
-{
-    std::ofstream f(p, std::ios::binary);
-    f.write(static_cast<const char*>(d), (std::streamsize)n);
-}
 static void put(ID3D12Resource* r, const std::string& path, hipStream_t s)
 {
     auto b = slurp(path);

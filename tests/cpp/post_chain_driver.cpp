@@ -7,57 +7,16 @@
 // floats), every set stage's buffer (taa_, hist_, dof_, mb_, bloom_, aa_) and present_m_k.ppm (what Present writes).  At the end all
 // switches are off again (plain_again.bin).  tests/test_post_chain_veneer.py applies each pass to the buffer in front of it.
 // Usage: post_chain_driver <dir> <W> <H> <shadowDim> <cubeDim> <blurCount> <numDirLights>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "crychic/CRYCHIC.h"
-
-static std::vector<char> slurp(const std::string& p)
-{
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", p.c_str()); std::exit(2); }
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void dump(const std::string& p, const void* d, size_t n)
-{
-    std::ofstream f(p, std::ios::binary);
-    f.write(static_cast<const char*>(d), (std::streamsize)n);
-}
+#include "driver_util.hpp"
 
 enum { FOG = 1, TAA = 2, DOF = 4, MB = 8, BLOOM = 16, AA = 32, ALL = 63 };
 
 int main(int argc, char** argv)
 {
-    if (argc < 8) { std::fprintf(stderr, "usage\n"); return 2; }
-    const std::string dir = argv[1];
-    const UINT W = std::atoi(argv[2]), H = std::atoi(argv[3]), SD = std::atoi(argv[4]), CD = std::atoi(argv[5]);
-    try {
-        CRYCHIC app(0, W, H);
-        app.mShadowMapSize = SD;
-        app.mBlurCount = std::atoi(argv[6]);
-        app.mNumDirLights = std::atoi(argv[7]);
-        app.mSkyEnabled = true;
-        app.mRunProducerPasses = true;
-        if (!app.Initialize()) return 3;
-        hipStream_t s = app.CommandList()->Stream();
-        auto cubeBytes = slurp(dir + "/cube.bin");
-        auto cube = std::make_unique<ID3D12Resource>((size_t)6 * CD * CD * 4, ID3D12Resource::DEFAULT_HEAP);
-        if (cubeBytes.size() != cube->Bytes()) { std::fprintf(stderr, "cube.bin size\n"); return 2; }
-        cube->Upload(cubeBytes.data(), cubeBytes.size(), s);
-        CrychicHipThrowIfFailed(hipStreamSynchronize(s));
-        app.SetCubeMap(std::move(cube), CD);
-
-        GameTimer gt;
-        auto frame = [&] { gt.Tick(1.0f / 60.0f); app.Update(gt); app.Draw(gt); app.CommandList()->Flush(); };
-        auto grab = [&](ID3D12Resource* r, const std::string& name) {
-            std::vector<char> h(r->Bytes());
-            r->Download(h.data(), h.size(), s);
-            app.CommandList()->Flush();
-            dump(dir + "/" + name, h.data(), h.size());
-        };
+    return run_post_driver(argc, argv, [](PostDriver& d) {
+        CRYCHIC& app = d.app;
+        const std::string& dir = d.dir;
         crychic_bloom_params glow;                              // a threshold the scene's highlights pass (the test states the same numbers)
         crychic_bloom_default_params(&glow);
         glow.threshold = 160; glow.knee = 32; glow.scatter = 179; glow.intensity = 64; glow.levels = 6;
@@ -80,10 +39,10 @@ int main(int argc, char** argv)
             app.mCamera.SetPosition(home.x, home.y, home.z);
             for (int k = 0; k < 2; ++k) {
                 if (k) app.mCamera.Strafe(0.3f);
-                frame();
+                d.frame();
                 const std::string tag = "_" + std::to_string(mask) + "_" + std::to_string(k);
-                grab(app.CurrentBackBuffer(), "back" + tag + ".bin");
-                grab(app.DepthStencilBuffer(), "depth" + tag + ".bin");
+                d.grab(app.CurrentBackBuffer(), "back" + tag + ".bin");
+                d.grab(app.DepthStencilBuffer(), "depth" + tag + ".bin");
                 dump(dir + "/cb" + tag + ".bin", &app.mMainPassCB, sizeof app.mMainPassCB);
                 float m[64];
                 std::memcpy(m, app.TemporalAAViewProj(0), 64);
@@ -91,23 +50,20 @@ int main(int argc, char** argv)
                 std::memcpy(m + 32, app.MotionBlurViewProj(0), 64);
                 std::memcpy(m + 48, app.MotionBlurViewProj(1), 64);
                 dump(dir + "/mats" + tag + ".bin", m, sizeof m);
-                if (mask & TAA) { grab(app.TemporalAABackBuffer(), "taa" + tag + ".bin"); grab(app.TemporalAAHistory(), "hist" + tag + ".bin"); }
-                if (mask & DOF) grab(app.DepthOfFieldBackBuffer(), "dof" + tag + ".bin");
-                if (mask & MB) grab(app.MotionBlurBackBuffer(), "mb" + tag + ".bin");
-                if (mask & BLOOM) grab(app.BloomBackBuffer(), "bloom" + tag + ".bin");
-                if (mask & AA) grab(app.AntiAliasedBackBuffer(), "aa" + tag + ".bin");
+                if (mask & TAA) { d.grab(app.TemporalAABackBuffer(), "taa" + tag + ".bin"); d.grab(app.TemporalAAHistory(), "hist" + tag + ".bin"); }
+                if (mask & DOF) d.grab(app.DepthOfFieldBackBuffer(), "dof" + tag + ".bin");
+                if (mask & MB) d.grab(app.MotionBlurBackBuffer(), "mb" + tag + ".bin");
+                if (mask & BLOOM) d.grab(app.BloomBackBuffer(), "bloom" + tag + ".bin");
+                if (mask & AA) d.grab(app.AntiAliasedBackBuffer(), "aa" + tag + ".bin");
                 app.Present(dir + "/present" + tag + ".ppm");
             }
             ++drawn;
         }
         set(0);
         app.mCamera.SetPosition(home.x, home.y, home.z);
-        frame();
-        grab(app.CurrentBackBuffer(), "plain_again.bin");
-        std::printf("post chain driver ok %ux%u, %d subsets\n", W, H, drawn);
-    } catch (const std::exception& e) {
-        std::fprintf(stderr, "exception: %s\n", e.what());
-        return 1;
-    }
-    return 0;
+        d.frame();
+        d.grab(app.CurrentBackBuffer(), "plain_again.bin");
+        std::printf("post chain driver ok %ux%u, %d subsets\n", d.W, d.H, drawn);
+        return 0;
+    });
 }

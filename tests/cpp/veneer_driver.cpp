@@ -6,24 +6,8 @@
 // grid) instead of loading depth / normal / G-buffer / shadow planes from <dir>.  `transforms` is `scene` with the grid of the
 // camera layer under a World with a rotation and a non-symmetric TexTransform, and its material under a non-symmetric
 // MatTransform (tests/test_cpp_veneer.py holds the same numbers): what UpdateInstanceData and UpdateMaterialBuffer transpose.
-#include <cstdio>
-#include <cstdlib>
-#include <fstream>
-#include <string>
-#include <vector>
-#include "crychic/CRYCHIC.h"
+#include "driver_util.hpp"
 
-static std::vector<char> slurp(const std::string& p)
-{
-    std::ifstream f(p, std::ios::binary);
-    if (!f) { std::fprintf(stderr, "cannot open %s\n", p.c_str()); std::exit(2); }
-    return std::vector<char>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-}
-static void dump(const std::string& p, const void* d, size_t n)
-{
-    std::ofstream f(p, std::ios::binary);
-    f.write(static_cast<const char*>(d), (std::streamsize)n);
-}
 static void put(ID3D12Resource* r, const std::string& path, hipStream_t s)
 {
     auto b = slurp(path);

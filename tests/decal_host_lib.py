@@ -2,11 +2,11 @@
 with the workgroup walk, the wavefront's box reduction, lane k's test of decal k, the vote and the mask walk emulated."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from hostsim_lib import CLANG, CSRC, ROOT
+from hostsim_lib import ROOT
+from post_pass_lib import build_host_shim
 import decal_lib
 
 DIR = os.path.join(ROOT, "tests", "decal_host")
@@ -14,11 +14,7 @@ SRC, LIB = os.path.join(DIR, "decal_host.cpp"), os.path.join(DIR, "libdecalhost.
 
 
 def build():
-    deps = [SRC, os.path.join(ROOT, "include", "crychic_hip.h")] + [os.path.join(CSRC, f) for f in ("decal_core.hpp", "light_core.hpp", "devmath.hpp", "gamma_pow.inc")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.run([CLANG, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-I", os.path.join(ROOT, "include"),
-                        "-I", CSRC, SRC, "-o", LIB], check=True)
-    return LIB
+    return build_host_shim(SRC, LIB, ("decal_core.hpp", "light_core.hpp", "devmath.hpp", "gamma_pow.inc"), api_header=True)
 
 
 _LIB = None

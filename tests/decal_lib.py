@@ -3,9 +3,10 @@ definition in include/crychic_hip.h with none of the kernel's code; and the corp
 device tests share."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from post_pass_lib import GUARD, build_checker, guarded, guards_intact      # noqa: F401 -- what the post passes' tests share
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIR = os.path.join(ROOT, "tests", "decal_ref")
@@ -19,7 +20,6 @@ ALBEDO, ROUGHNESS, METALNESS, NORMAL = 1, 2, 4, 8
 NO_TEXTURE = 0xFFFFFFFF
 MIXES = {"f32": 0, "mixed": 0x6000, "f16": 0x7000}        # CRYCHIC_GBUFFER_G*_F16 bits: G1 and G2 half, all three half
 SIZES = ((1, 1), (3, 5), (63, 4), (64, 4), (65, 7), (130, 9))
-GUARD = 0xA5
 
 DECAL = np.dtype([("invWorld", "f4", 12), ("boundsMin", "f4", 3), ("boundsMax", "f4", 3), ("tangentW", "f4", 3), ("bitangentW", "f4", 3),
                   ("normalW", "f4", 3), ("tint", "f4", 3), ("opacity", "f4"), ("roughness", "f4"), ("metalness", "f4"), ("fadeScale", "f4"),
@@ -32,9 +32,7 @@ class RefTexture(C.Structure):
 
 
 def build():
-    if not os.path.exists(LIB) or os.path.getmtime(SRC) > os.path.getmtime(LIB):
-        subprocess.run(["gcc", "-O2", "-std=c99", "-fPIC", "-Wall", "-ffp-contract=off", "-shared", "-o", LIB, SRC, "-lm"], check=True)
-    return LIB
+    return build_checker(SRC, LIB)
 
 
 _REF = None
@@ -180,20 +178,6 @@ def checker(frame, mix, decals, textures, row0=0, rows=None, planes=None, passed
                      n.ctypes.data, None if p2 is None else p2.ctypes.data)
     counts = dict(zip(COUNTERS, (int(v) for v in n)))
     return (planes, counts, p2) if passed else (planes, counts)
-
-
-def guarded(shape, dtype=np.uint8, guard=64, misalign=0, fill=GUARD):
-    """(raw, view): `view` is an array of `shape` and `dtype` inside the uint8 array `raw` of `fill`, at least `guard` bytes of it on
-    either side; the view starts `misalign` bytes past a 64-byte boundary."""
-    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-    raw = np.full(n + 2 * guard + 128, fill, np.uint8)
-    off = guard + (-(raw.ctypes.data + guard)) % 64 + misalign
-    return raw, raw[off:off + n].view(dtype).reshape(shape)
-
-
-def guards_intact(raw, view, fill=GUARD):
-    off = view.ctypes.data - raw.ctypes.data
-    return bool((raw[:off] == fill).all() and (raw[off + view.nbytes:] == fill).all())
 
 
 # ---- the corpus ------------------------------------------------------------------------------------------------------------------

@@ -3,9 +3,10 @@ include/crychic_hip.h with none of the kernel's code; and the corpus of frames, 
 tests share."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from post_pass_lib import GUARD, build_checker, guarded, guards_intact      # noqa: F401 -- what the post passes' tests share
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIR = os.path.join(ROOT, "tests", "dof_ref")
@@ -37,13 +38,10 @@ PARAM_SETS = {
 # and one frame of several workgroups each way
 SIZES = ((1, 1), (3, 5), (63, 4), (64, 4), (65, 7), (130, 9), (322, 190))
 DEPTH_KINDS = ("zeros", "ones", "random", "step_near_left", "step_near_right")
-GUARD = 0xA5
 
 
 def build():
-    if not os.path.exists(LIB) or os.path.getmtime(SRC) > os.path.getmtime(LIB):
-        subprocess.run(["gcc", "-O2", "-std=c99", "-fPIC", "-Wall", "-ffp-contract=off", "-shared", "-o", LIB, SRC, "-lm"], check=True)
-    return LIB
+    return build_checker(SRC, LIB)
 
 
 def f32(x):
@@ -141,20 +139,6 @@ def tables():
     r = _ref()
     d16 = {(ox, oy): int(r.dof_ref_d16(ox, oy)) for oy in range(-8, 9) for ox in range(-8, 9) if ox * ox + oy * oy <= 64}
     return [int(r.dof_ref_disc(R)) for R in range(1, 9)], [int(r.dof_ref_inv(c)) for c in range(129)], d16
-
-
-def guarded(shape, dtype=np.uint8, guard=64, misalign=0, fill=GUARD):
-    """(raw, view): `view` is an array of `shape` and `dtype` inside the uint8 array `raw` of `fill`, `guard` bytes of it on either
-    side; the view starts `misalign` bytes (a multiple of 4) past a 16-byte boundary."""
-    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-    raw = np.full(n + 2 * guard + 32, fill, np.uint8)
-    off = guard + (-(raw.ctypes.data + guard)) % 16 + misalign
-    return raw, raw[off:off + n].view(dtype).reshape(shape)
-
-
-def guards_intact(raw, view, fill=GUARD):
-    off = view.ctypes.data - raw.ctypes.data
-    return bool((raw[:off] == fill).all() and (raw[off + view.nbytes:] == fill).all())
 
 
 # ---- the corpus ------------------------------------------------------------------------------------------------------------------

@@ -2,11 +2,11 @@
 the workgroup and lane walk emulated."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from hostsim_lib import CLANG, CSRC, ROOT
+from hostsim_lib import ROOT
+from post_pass_lib import build_host_shim
 import fog_lib
 
 DIR = os.path.join(ROOT, "tests", "fog_host")
@@ -14,11 +14,7 @@ SRC, LIB = os.path.join(DIR, "fog_host.cpp"), os.path.join(DIR, "libfoghost.so")
 
 
 def build():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("fog_core.hpp", "devmath.hpp", "gamma_pow.inc")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.run([CLANG, "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-mfma", "-I", CSRC, SRC, "-o", LIB],
-                       check=True)
-    return LIB
+    return build_host_shim(SRC, LIB, ("fog_core.hpp", "devmath.hpp", "gamma_pow.inc"))
 
 
 _LIB = None

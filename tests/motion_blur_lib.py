@@ -3,12 +3,12 @@ definition in include/crychic_hip.h with none of the kernels' code; and the corp
 device tests share."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+from post_pass_lib import GUARD, DevicePlanes, build_checker, guarded, guards_intact      # noqa: F401 -- what the post passes' tests share
 import taa_lib
-from taa_lib import GUARD, IDENTITY, camera_matrices, device_guards_intact, guarded, guarded_plane, guards_intact, moved_camera  # noqa: F401
+from taa_lib import IDENTITY, camera_matrices, moved_camera
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIR = os.path.join(ROOT, "tests", "motion_blur_ref")
@@ -27,9 +27,7 @@ SHUTTERS = (0, 1, 128, 256)
 
 
 def build():
-    if not os.path.exists(LIB) or os.path.getmtime(SRC) > os.path.getmtime(LIB):
-        subprocess.run(["gcc", "-O2", "-std=c99", "-fPIC", "-Wall", "-ffp-contract=off", "-shared", "-o", LIB, SRC, "-lm"], check=True)
-    return LIB
+    return build_checker(SRC, LIB)
 
 
 def tiles(n):
@@ -219,10 +217,11 @@ def run_device(dev, case, row0=0, rows=None, misalign=0, entry="both", ws_host=N
     H, W = case.H, case.W
     rows = H - row0 if rows is None else rows
     need = workspace_bytes(W, H)
-    sraw, src = guarded_plane(torch, ctx, case.img, misalign)
-    draw, depth = guarded_plane(torch, ctx, case.depth, misalign)
-    oraw, out = guarded_plane(torch, ctx, np.full(case.img.shape, GUARD, np.uint8), misalign)
-    wraw, ws = guarded_plane(torch, ctx, np.full(need, GUARD, np.uint8) if ws_host is None else ws_host, misalign & 8)
+    planes = DevicePlanes(dev)
+    src = planes.upload("input", case.img, misalign)
+    depth = planes.upload("depth", case.depth, misalign)
+    out = planes.blank("out", case.img.shape, np.uint8, misalign)
+    ws = planes.upload("workspace", np.full(need, GUARD, np.uint8) if ws_host is None else ws_host, misalign & 8, writable=True)
     pcb = case.pass_constants(lib)
     p = case.params(lib)
     cur, prev = (C.c_float * 16)(*case.cur), (C.c_float * 16)(*case.prev)
@@ -237,8 +236,5 @@ def run_device(dev, case, row0=0, rows=None, misalign=0, entry="both", ws_host=N
             lib.check(lib.lib.crychic_motion_blur_velocity(ctx.handle, C.byref(pcb), cur, prev, ptr(depth), W, H, C.byref(p), ptr(ws), need, st))
         lib.check(lib.lib.crychic_motion_blur_gather(ctx.handle, ptr(src), ptr(out), W, H, row0, rows, C.byref(p), ptr(ws), need, st))
     s.synchronize()
-    for raw, view in ((sraw, src), (draw, depth), (oraw, out), (wraw, ws)):
-        assert device_guards_intact(raw, view), "guard bytes changed"
-    assert np.array_equal(depth.cpu().numpy().view(np.uint32).reshape(H, W), case.depth), "the depth plane changed"
-    assert np.array_equal(src.cpu().numpy().reshape(case.img.shape), case.img), "the input plane changed"
+    planes.verify()
     return ws.cpu().numpy(), out.cpu().numpy().reshape(H, W, 4)

@@ -3,9 +3,10 @@ in include/crychic_hip.h with none of the kernel's code; and the corpus of image
 share."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
+
+from post_pass_lib import GUARD, build_checker, guarded, guards_intact      # noqa: F401 -- what the post passes' tests share
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIR = os.path.join(ROOT, "tests", "post_aa_ref")
@@ -27,13 +28,10 @@ PARAM_SETS = {
 }
 # tile edges +- 1 of the kernel's 64 x 32 tile, degenerate frames, and one frame of several tiles each way
 SIZES = ((1, 1), (1, 7), (7, 1), (2, 2), (63, 31), (64, 32), (65, 33), (130, 70), (322, 190))
-GUARD = 0xA5
 
 
 def build():
-    if not os.path.exists(LIB) or os.path.getmtime(SRC) > os.path.getmtime(LIB):
-        subprocess.run(["gcc", "-O2", "-std=c99", "-fPIC", "-Wall", "-shared", "-o", LIB, SRC], check=True)
-    return LIB
+    return build_checker(SRC, LIB, fp=False)
 
 
 def params_array(params=None):
@@ -64,20 +62,6 @@ def checker(img, params=None, row0=0, rows=None, out=None):
     p = params_array(params)
     _ref().aa_ref(img.ctypes.data, out.ctypes.data, W, H, row0, rows, p.ctypes.data, n.ctypes.data)
     return out, dict(zip(COUNTERS, (int(v) for v in n)))
-
-
-def guarded(shape, guard=64, misalign=0, fill=GUARD):
-    """(raw, view): `view` is a (H, W, 4) uint8 array of `fill` inside `raw`, `guard` bytes of `fill` on either side; the view starts
-    `misalign` bytes (a multiple of 4) past a 16-byte boundary."""
-    n = int(np.prod(shape))
-    raw = np.full(n + 2 * guard + 32, fill, np.uint8)
-    off = guard + (-(raw.ctypes.data + guard)) % 16 + misalign
-    return raw, raw[off:off + n].reshape(shape)
-
-
-def guards_intact(raw, view, fill=GUARD):
-    off = view.ctypes.data - raw.ctypes.data
-    return bool((raw[:off] == fill).all() and (raw[off + view.size:] == fill).all())
 
 
 # ---- the corpus ------------------------------------------------------------------------------------------------------------------

@@ -4,9 +4,10 @@ share."""
 import ctypes as C
 import math
 import os
-import subprocess
 
 import numpy as np
+
+from post_pass_lib import GUARD, DevicePlanes, build_checker, guarded, guards_intact      # noqa: F401 -- what the post passes' tests share
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIR = os.path.join(ROOT, "tests", "taa_ref")
@@ -19,13 +20,10 @@ TILE_W, TILE_H, WAVE = 32, 8, 8                         # the kernel's workgroup
 # 1 x 1, 3 x 2, one below / at / one above the workgroup each way (and the two crossings), the five-frame scene's size, an odd frame
 SIZES = ((1, 1), (3, 2), (31, 7), (32, 8), (33, 9), (33, 7), (31, 9), (70, 38), (131, 67))
 MOTIONS = ("identical", "subpixel_pan", "large_pan", "dolly", "outside", "behind")
-GUARD = 0xA5
 
 
 def build():
-    if not os.path.exists(LIB) or os.path.getmtime(SRC) > os.path.getmtime(LIB):
-        subprocess.run(["gcc", "-O2", "-std=c99", "-fPIC", "-Wall", "-ffp-contract=off", "-shared", "-o", LIB, SRC, "-lm"], check=True)
-    return LIB
+    return build_checker(SRC, LIB)
 
 
 class Case:
@@ -77,20 +75,6 @@ def checker(case, row0=0, rows=None, out=None, hist_out=None):
                    None if case.hist is None else case.hist.ctypes.data, hist_out.ctypes.data, out.ctypes.data, W, H, row0, rows, case.blend,
                    case.flags, branch.ctypes.data)
     return out, hist_out, branch
-
-
-def guarded(shape, dtype=np.uint8, guard=64, misalign=0, fill=GUARD):
-    """(raw, view): `view` is an array of `shape` and `dtype` inside the uint8 array `raw` of `fill`, `guard` bytes of it on either
-    side; the view starts `misalign` bytes past a 16-byte boundary."""
-    n = int(np.prod(shape)) * np.dtype(dtype).itemsize
-    raw = np.full(n + 2 * guard + 32, fill, np.uint8)
-    off = guard + (-(raw.ctypes.data + guard)) % 16 + misalign
-    return raw, raw[off:off + n].view(dtype).reshape(shape)
-
-
-def guards_intact(raw, view, fill=GUARD):
-    off = view.ctypes.data - raw.ctypes.data
-    return bool((raw[:off] == fill).all() and (raw[off + view.nbytes:] == fill).all())
 
 
 # ---- matrices ----------------------------------------------------------------------------------------------------------------------
@@ -302,37 +286,18 @@ def box_filter(big, f):
 
 # ---- the device (GPU tier) ------------------------------------------------------------------------------------------------------------
 
-GUARD_BYTES = 256
-
-
-def guarded_plane(torch, ctx, host, misalign=0):
-    """(raw, view): a device copy of the numpy array `host` inside a uint8 buffer of 0xA5, GUARD_BYTES of them on either side; the view
-    starts `misalign` bytes past a 256-byte boundary of the allocation."""
-    n = host.nbytes
-    raw = torch.full((n + 2 * GUARD_BYTES + 16,), GUARD, dtype=torch.uint8, device=ctx.device)
-    assert raw.data_ptr() % 16 == 0
-    off = GUARD_BYTES + misalign
-    view = raw[off:off + n]
-    view.copy_(torch.from_numpy(np.array(host).view(np.uint8).reshape(-1)).to(ctx.device))
-    return raw, view
-
-
-def device_guards_intact(raw, view):
-    off = view.data_ptr() - raw.data_ptr()
-    return bool((raw[:off] == GUARD).all()) and bool((raw[off + view.numel():] == GUARD).all())
-
-
 def run_device(dev, case, row0=0, rows=None, misalign=0):
     """crychic_taa on guarded device copies of the case's planes, the frame planes `misalign` bytes and the history planes
     `misalign & 8` bytes past a 256-byte boundary: (out, history_out) as numpy, the guards and the inputs checked.  dev = (the
     product's _lib module, a Context, torch)."""
     lib, ctx, torch = dev
     H, W = case.H, case.W
-    sraw, src = guarded_plane(torch, ctx, case.img, misalign)
-    draw, depth = guarded_plane(torch, ctx, case.depth, misalign)
-    oraw, out = guarded_plane(torch, ctx, np.full(case.img.shape, GUARD, np.uint8), misalign)
-    horaw, hout = guarded_plane(torch, ctx, np.full((H, W, 4), GUARD * 257, np.uint16), misalign & 8)
-    hiraw, hin = (None, None) if case.hist is None else guarded_plane(torch, ctx, case.hist, misalign & 8)
+    planes = DevicePlanes(dev)
+    src = planes.upload("input", case.img, misalign)
+    depth = planes.upload("depth", case.depth, misalign)
+    out = planes.blank("out", case.img.shape, np.uint8, misalign)
+    hout = planes.blank("history out", (H, W, 4), np.uint16, misalign & 8)
+    hin = None if case.hist is None else planes.upload("history in", case.hist, misalign & 8)
     pcb = case.pass_constants(lib)
     p = lib.TaaParams.default(blend=case.blend, flags=case.flags)
     cur, prev = (C.c_float * 16)(*case.cur), (C.c_float * 16)(*case.prev)
@@ -341,9 +306,5 @@ def run_device(dev, case, row0=0, rows=None, misalign=0):
                                   None if hin is None else C.c_void_p(hin.data_ptr()), C.c_void_p(hout.data_ptr()), C.c_void_p(out.data_ptr()), W, H,
                                   row0, H - row0 if rows is None else rows, C.byref(p), C.c_void_p(s.cuda_stream)))
     s.synchronize()
-    for raw, view in ((sraw, src), (draw, depth), (oraw, out), (horaw, hout)) + (() if hin is None else ((hiraw, hin),)):
-        assert device_guards_intact(raw, view), "guard bytes changed"
-    assert np.array_equal(depth.cpu().numpy().view(np.uint32).reshape(H, W), case.depth), "the depth plane changed"
-    assert np.array_equal(src.cpu().numpy().reshape(case.img.shape), case.img), "the input plane changed"
-    assert hin is None or np.array_equal(hin.cpu().numpy().view(np.uint16).reshape(H, W, 4), case.hist), "the history read changed"
+    planes.verify()
     return out.cpu().numpy().reshape(H, W, 4), hout.cpu().numpy().view(np.uint16).reshape(H, W, 4)

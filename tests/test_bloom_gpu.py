@@ -8,35 +8,9 @@ import numpy as np
 import pytest
 
 import bloom_lib as bl
+from post_pass_lib import DevicePlanes, dev      # noqa: F401 -- dev: the module's fixture
 
 pytestmark = pytest.mark.gpu
-GUARD_BYTES = 256
-
-
-@pytest.fixture(scope="module")
-def dev(built_lib):
-    import torch
-    from crychic_renderer_amd import Context
-    ctx = Context(0)
-    yield built_lib, ctx, torch
-    ctx.close()
-
-
-def guarded_plane(torch, ctx, host, misalign=0):
-    """(raw, view): a device copy of the uint8 numpy array `host` inside a uint8 buffer of 0xA5, GUARD_BYTES of them on either side; the
-    view starts `misalign` bytes past a 256-byte boundary of the allocation."""
-    n = host.nbytes
-    raw = torch.full((n + 2 * GUARD_BYTES + 16,), bl.GUARD, dtype=torch.uint8, device=ctx.device)
-    assert raw.data_ptr() % 16 == 0
-    off = GUARD_BYTES + misalign
-    view = raw[off:off + n]
-    view.copy_(torch.from_numpy(np.array(host).reshape(-1)).to(ctx.device))
-    return raw, view
-
-
-def guards_intact(raw, view):
-    off = view.data_ptr() - raw.data_ptr()
-    return bool((raw[:off] == bl.GUARD).all()) and bool((raw[off + view.numel():] == bl.GUARD).all())
 
 
 def bloom_params(lib, params):
@@ -51,9 +25,10 @@ def run_device(dev, img, params=None, misalign=0, in_place=False, split=None, ws
     H, W = img.shape[:2]
     p = dict(bl.DEFAULTS, **(params or {}))
     _, need = bl.level_offsets(W, H, p["levels"])
-    sraw, src = guarded_plane(torch, ctx, img, misalign)
-    oraw, out = (sraw, src) if in_place else guarded_plane(torch, ctx, np.full(img.shape, bl.GUARD, np.uint8), misalign)
-    wraw, ws = guarded_plane(torch, ctx, np.full((need,), bl.GUARD, np.uint8), 16 * ws_misalign)
+    planes = DevicePlanes(dev)
+    src = planes.upload("input", img, misalign, writable=in_place)
+    out = src if in_place else planes.blank("out", img.shape, np.uint8, misalign)
+    ws = planes.blank("workspace", need, np.uint8, 16 * ws_misalign)
     q = bloom_params(lib, params)
     qp = None if q is None else C.byref(q)
     s = torch.cuda.current_stream(ctx.device)
@@ -66,11 +41,9 @@ def run_device(dev, img, params=None, misalign=0, in_place=False, split=None, ws
         for row0, end in zip(split[:-1], split[1:]):
             lib.check(lib.lib.crychic_bloom_composite(ctx.handle, ps, po, W, H, row0, end - row0, qp, pw, need, stream))
     s.synchronize()
-    assert guards_intact(sraw, src) and guards_intact(oraw, out) and guards_intact(wraw, ws), "guard bytes changed"
+    planes.verify()
     wsh = ws.cpu().numpy()
     assert (wsh[~bl.written_mask(W, H, p["levels"], need)] == bl.GUARD).all(), "a workspace byte between two levels was written"
-    if not in_place:
-        assert np.array_equal(src.cpu().numpy().reshape(img.shape), img), "the input plane changed"
     return out.cpu().numpy().reshape(img.shape), bl.split_workspace(wsh, W, H, p["levels"])
 
 

@@ -2,14 +2,12 @@
 (tests/bloom_ref) over the plain frame the application rendered, and the back buffer stays the plain frame; behind the depth of field
 it is the checker over that pass's buffer, and the anti-aliased buffer is the anti-aliasing checker's frame over it; with it off the
 frame is the plain one again; bad parameters are refused and a strip with it on throws."""
-import subprocess
-
 import numpy as np
 import pytest
 
 import bloom_lib as bl
 import post_aa_lib as aa
-from test_cpp_veneer import build_driver
+from test_cpp_veneer import build_driver, run_driver
 
 LOW = dict(threshold=160, intensity=64)         # the caller's parameters the driver sets besides the defaults
 
@@ -21,18 +19,8 @@ def test_bloom_driver_compiles(built_lib):
 
 @pytest.mark.gpu
 def test_veneer_bloom(built_lib, tmp_path):
-    import torch
-    from crychic_renderer_amd import scene
-    exe = build_driver("bloom_driver")
     W, H, SD, CD, BC, NL = 128, 96, 256, 32, 2, 1
-    d = str(tmp_path)
-    scene.make_cubemap(CD, torch.device("cpu")).numpy().tofile(d + "/cube.bin")
-    r = subprocess.run([exe, d, str(W), str(H), str(SD), str(CD), str(BC), str(NL)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "bloom driver ok" in r.stdout
-
-    def frame(name):
-        return np.fromfile(d + "/" + name, np.uint8).reshape(H, W, 4)
+    d, frame = run_driver("bloom_driver", tmp_path, W, H, SD, CD, BC, NL, "bloom driver ok")
     plain = frame("plain.bin")
     want, _, n = bl.checker(plain, LOW)
     assert n["w_interior"] + n["w_full"] > 0 and not np.array_equal(want, plain), "nothing of the scene lies over the threshold"

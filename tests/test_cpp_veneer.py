@@ -16,14 +16,30 @@ EXE = os.path.join(ROOT, "tests", "cpp", "veneer_driver")
 
 def build_driver(name="veneer_driver"):
     """tests/cpp/<name>.cpp -> tests/cpp/<name>, linked against the in-tree libcrychic_hip.so (rebuilt when a header changed)."""
-    src, exe = os.path.join(ROOT, "tests", "cpp", name + ".cpp"), os.path.join(ROOT, "tests", "cpp", name)
+    cpp = os.path.join(ROOT, "tests", "cpp")
+    src, exe = os.path.join(cpp, name + ".cpp"), os.path.join(cpp, name)
     hdrs = [os.path.join(ROOT, "include", "crychic", f) for f in os.listdir(os.path.join(ROOT, "include", "crychic"))]
-    deps = [src, os.path.join(ROOT, "include", "crychic_hip.h")] + hdrs
+    deps = [src, os.path.join(ROOT, "include", "crychic_hip.h")] + hdrs + [os.path.join(cpp, f) for f in os.listdir(cpp) if f.endswith(".hpp")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         subprocess.run(["/opt/rocm/bin/hipcc", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "include"), src,
                         "-L", os.path.join(ROOT, "crychic_renderer_amd"), "-lcrychic_hip",
                         "-Wl,-rpath," + os.path.join(ROOT, "crychic_renderer_amd"), "-o", exe], check=True)
     return exe
+
+
+def run_driver(name, tmp_path, W, H, SD, CD, BC, NL, ok, extra=()):
+    """Runs tests/cpp/<name> -- a driver of a post-process pass -- in tmp_path over the W x H built-in scene with the synthetic cube
+    map of side CD (`extra`: the arguments behind the seven every such driver takes) and checks its exit code and its `ok` line.
+    Returns (the directory, frame), where frame(file name) is an (H, W, 4) uint8 file the driver left there."""
+    import torch
+    from crychic_renderer_amd import scene
+    exe = build_driver(name)
+    d = str(tmp_path)
+    scene.make_cubemap(CD, torch.device("cpu")).numpy().tofile(d + "/cube.bin")
+    r = subprocess.run([exe, d] + [str(v) for v in (W, H, SD, CD, BC, NL) + tuple(extra)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert ok in r.stdout
+    return d, lambda name: np.fromfile(d + "/" + name, np.uint8).reshape(H, W, 4)
 
 
 def test_veneer_compiles(built_lib):

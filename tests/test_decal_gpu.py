@@ -7,34 +7,9 @@ import numpy as np
 import pytest
 
 import decal_lib as dl
+from post_pass_lib import DevicePlanes, dev      # noqa: F401 -- dev: the module's fixture
 
 pytestmark = pytest.mark.gpu
-GUARD_BYTES = 256
-
-
-@pytest.fixture(scope="module")
-def dev(built_lib):
-    import torch
-    from crychic_renderer_amd import Context
-    ctx = Context(0)
-    yield built_lib, ctx, torch
-    ctx.close()
-
-
-def guarded_plane(torch, ctx, host, misalign=0):
-    """(raw, view): a device copy of the numpy array `host` inside a uint8 buffer of 0xA5, at least GUARD_BYTES of them on either
-    side; the view starts `misalign` bytes past a 64-byte boundary."""
-    n = host.nbytes
-    raw = torch.full((n + 2 * GUARD_BYTES + 64,), dl.GUARD, dtype=torch.uint8, device=ctx.device)
-    off = GUARD_BYTES + (-(raw.data_ptr() + GUARD_BYTES)) % 64 + misalign
-    view = raw[off:off + n]
-    view.copy_(torch.from_numpy(np.array(host).view(np.uint8).reshape(-1)).to(ctx.device))
-    return raw, view
-
-
-def guards_intact(raw, view):
-    off = view.data_ptr() - raw.data_ptr()
-    return bool((raw[:off] == dl.GUARD).all()) and bool((raw[off + view.numel():] == dl.GUARD).all())
 
 
 def run_device(dev, frame, mix, decals, textures, ranges=None, misalign=0, planes=None):
@@ -44,29 +19,25 @@ def run_device(dev, frame, mix, decals, textures, ranges=None, misalign=0, plane
     lib, ctx, torch = dev
     H, W = frame.H, frame.W
     host = frame.planes(mix) if planes is None else planes
-    g = [guarded_plane(torch, ctx, p, misalign) for p in host]
-    draw, depth = guarded_plane(torch, ctx, frame.depth, misalign)
+    planes = DevicePlanes(dev)
+    g = [planes.upload("G%d" % k, p, misalign, writable=True) for k, p in enumerate(host)]
+    depth = planes.upload("depth", frame.depth, misalign)
     decals = np.ascontiguousarray(decals)
-    dec = guarded_plane(torch, ctx, decals.view(np.uint8), 0) if len(decals) else (None, None)
-    tex = [guarded_plane(torch, ctx, t[0], 0) for t in textures]
+    dec = planes.upload("decals", decals, 0) if len(decals) else None
+    tex = [planes.upload("texture %d" % k, t[0], 0) for k, t in enumerate(textures)]
     table = (lib.Texture * max(len(textures), 1))()
     for k, t in enumerate(textures):
-        table[k] = lib.Texture(tex[k][1].data_ptr(), t[1], t[2], t[3])
+        table[k] = lib.Texture(tex[k].data_ptr(), t[1], t[2], t[3])
     pcb = frame.pass_constants()
     s = torch.cuda.current_stream(ctx.device)
     for row0, rows in (ranges or [(0, H)]):
-        lib.check(lib.lib.crychic_apply_decals(ctx.handle, C.byref(pcb), C.c_void_p(depth.data_ptr()), C.c_void_p(g[0][1].data_ptr()),
-                                               C.c_void_p(g[1][1].data_ptr()), C.c_void_p(g[2][1].data_ptr()), dl.MIXES[mix],
-                                               C.c_void_p(dec[1].data_ptr()) if len(decals) else None, len(decals), table, len(textures), W, H, row0,
+        lib.check(lib.lib.crychic_apply_decals(ctx.handle, C.byref(pcb), C.c_void_p(depth.data_ptr()), C.c_void_p(g[0].data_ptr()),
+                                               C.c_void_p(g[1].data_ptr()), C.c_void_p(g[2].data_ptr()), dl.MIXES[mix],
+                                               None if dec is None else C.c_void_p(dec.data_ptr()), len(decals), table, len(textures), W, H, row0,
                                                rows, C.c_void_p(s.cuda_stream)))
     s.synchronize()
-    assert all(guards_intact(r, v) for r, v in g) and guards_intact(draw, depth), "guard bytes changed"
-    assert np.array_equal(depth.cpu().numpy().view(np.uint32).reshape(H, W), frame.depth), "the depth plane changed"
-    if len(decals):
-        assert guards_intact(*dec) and np.array_equal(dec[1].cpu().numpy(), decals.view(np.uint8).reshape(-1)), "the decals changed"
-    for (r, v), t in zip(tex, textures):
-        assert guards_intact(r, v) and np.array_equal(v.cpu().numpy(), t[0]), "a texture changed"
-    return [v.cpu().numpy().reshape(p.shape) for (r, v), p in zip(g, host)]
+    planes.verify()
+    return [v.cpu().numpy().reshape(p.shape) for v, p in zip(g, host)]
 
 
 def assert_planes_equal(got, want, name):

@@ -2,13 +2,11 @@
 Draw's producer passes equal the checker (tests/decal_ref) over the planes, the depth plane and the pass constants the application
 rendered without them, and the lit frame shows them; cleared, the frame is the plain one again; as a strip, the strip's rows are
 decaled and the others are not; too many decals are refused."""
-import subprocess
-
 import numpy as np
 import pytest
 
 import decal_lib as dl
-from test_cpp_veneer import build_driver
+from test_cpp_veneer import build_driver, run_driver
 
 
 def test_decal_driver_compiles(built_lib):
@@ -18,13 +16,9 @@ def test_decal_driver_compiles(built_lib):
 
 @pytest.mark.gpu
 def test_veneer_decals(built_lib, tmp_path):
-    import torch
-    from crychic_renderer_amd import scene
-    exe = build_driver("decal_driver")
     W, H, SD, CD, BC, NL = 128, 96, 256, 32, 2, 1
     R0, RN = 32, 24
     d = str(tmp_path)
-    scene.make_cubemap(CD, torch.device("cpu")).numpy().tofile(d + "/cube.bin")
     rng = np.random.default_rng(7)
     tex = dl.random_texture(rng, 8, 4, 3)
     tex[0].tofile(d + "/tex.bin")
@@ -34,13 +28,7 @@ def test_veneer_decals(built_lib, tmp_path):
                           metalness=0.7, tint=(0.9, 0.4, 0.1)),
         dl.decal_from_box(dl.floor_world((1.0, 0.0, -4.0), (3.0, 1.0, 3.0), yaw=0.4), (8, 4), texture=0, flags=1, opacity=0.5)])
     recs.tofile(d + "/decals.bin")
-    r = subprocess.run([exe, d, str(W), str(H), str(SD), str(CD), str(BC), str(NL), "8", "4", "3", str(R0), str(RN)], capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "decal driver ok" in r.stdout
-
-    def frame(name):
-        return np.fromfile(d + "/" + name, np.uint8).reshape(H, W, 4)
+    d, frame = run_driver("decal_driver", tmp_path, W, H, SD, CD, BC, NL, "decal driver ok", extra=(8, 4, 3, R0, RN))
 
     def plane(name):
         return np.fromfile(d + "/" + name, np.float32).reshape(H, W, 4)

@@ -7,35 +7,9 @@ import numpy as np
 import pytest
 
 import dof_lib as dl
+from post_pass_lib import DevicePlanes, dev      # noqa: F401 -- dev: the module's fixture
 
 pytestmark = pytest.mark.gpu
-GUARD_BYTES = 256
-
-
-@pytest.fixture(scope="module")
-def dev(built_lib):
-    import torch
-    from crychic_renderer_amd import Context
-    ctx = Context(0)
-    yield built_lib, ctx, torch
-    ctx.close()
-
-
-def guarded_plane(torch, ctx, host, misalign=0):
-    """(raw, view): a device copy of the numpy array `host` (uint8 or uint32) inside a uint8 buffer of 0xA5, GUARD_BYTES of them on
-    either side; the view starts `misalign` bytes past a 256-byte boundary of the allocation."""
-    n = host.nbytes
-    raw = torch.full((n + 2 * GUARD_BYTES + 16,), dl.GUARD, dtype=torch.uint8, device=ctx.device)
-    assert raw.data_ptr() % 16 == 0
-    off = GUARD_BYTES + misalign
-    view = raw[off:off + n]
-    view.copy_(torch.from_numpy(np.array(host).view(np.uint8).reshape(-1)).to(ctx.device))
-    return raw, view
-
-
-def guards_intact(raw, view):
-    off = view.data_ptr() - raw.data_ptr()
-    return bool((raw[:off] == dl.GUARD).all()) and bool((raw[off + view.numel():] == dl.GUARD).all())
 
 
 def run_device(dev, frame, img, params=None, row0=0, rows=None, misalign=0):
@@ -43,9 +17,10 @@ def run_device(dev, frame, img, params=None, row0=0, rows=None, misalign=0):
     checked."""
     lib, ctx, torch = dev
     H, W = img.shape[:2]
-    sraw, src = guarded_plane(torch, ctx, img, misalign)
-    draw, depth = guarded_plane(torch, ctx, frame.depth, misalign)
-    oraw, out = guarded_plane(torch, ctx, np.full(img.shape, dl.GUARD, np.uint8), misalign)
+    planes = DevicePlanes(dev)
+    src = planes.upload("input", img, misalign)
+    depth = planes.upload("depth", frame.depth, misalign)
+    out = planes.blank("out", img.shape, np.uint8, misalign)
     pcb = frame.pass_constants(lib)
     p = None
     if params is not None:
@@ -55,9 +30,7 @@ def run_device(dev, frame, img, params=None, row0=0, rows=None, misalign=0):
     lib.check(lib.lib.crychic_dof(ctx.handle, C.byref(pcb), C.c_void_p(depth.data_ptr()), C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()), W, H,
                                   row0, H - row0 if rows is None else rows, None if p is None else C.byref(p), C.c_void_p(s.cuda_stream)))
     s.synchronize()
-    assert guards_intact(sraw, src) and guards_intact(oraw, out) and guards_intact(draw, depth), "guard bytes changed"
-    assert np.array_equal(depth.cpu().numpy().view(np.uint32).reshape(H, W), frame.depth), "the depth plane changed"
-    assert np.array_equal(src.cpu().numpy().reshape(img.shape), img), "the input plane changed"
+    planes.verify()
     return out.cpu().numpy().reshape(img.shape)
 
 

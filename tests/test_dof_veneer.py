@@ -2,14 +2,12 @@
 (tests/dof_ref) over the plain frame, the depth plane and the pass constants the application rendered, and the back buffer stays the
 plain frame; with the anti-aliasing on as well, the anti-aliased buffer is the anti-aliasing checker's frame over the blurred one;
 with it off the frame is the plain one again; a bad parameter is refused and a strip with it on throws."""
-import subprocess
-
 import numpy as np
 import pytest
 
 import dof_lib as dl
 import post_aa_lib as aa
-from test_cpp_veneer import build_driver
+from test_cpp_veneer import build_driver, run_driver
 
 
 def test_dof_driver_compiles(built_lib):
@@ -19,18 +17,8 @@ def test_dof_driver_compiles(built_lib):
 
 @pytest.mark.gpu
 def test_veneer_depth_of_field(built_lib, tmp_path):
-    import torch
-    from crychic_renderer_amd import scene
-    exe = build_driver("dof_driver")
     W, H, SD, CD, BC, NL = 128, 96, 256, 32, 2, 1
-    d = str(tmp_path)
-    scene.make_cubemap(CD, torch.device("cpu")).numpy().tofile(d + "/cube.bin")
-    r = subprocess.run([exe, d, str(W), str(H), str(SD), str(CD), str(BC), str(NL)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "dof driver ok" in r.stdout
-
-    def frame(name):
-        return np.fromfile(d + "/" + name, np.uint8).reshape(H, W, 4)
+    d, frame = run_driver("dof_driver", tmp_path, W, H, SD, CD, BC, NL, "dof driver ok")
     plain = frame("plain.bin")
     depth = np.fromfile(d + "/depth.bin", np.uint32).reshape(H, W)
     f = dl.Frame.from_pass_cb(np.fromfile(d + "/pass_cb.bin", np.uint8).tobytes(), depth)

@@ -7,36 +7,9 @@ import numpy as np
 import pytest
 
 import fog_lib as fg
+from post_pass_lib import DevicePlanes, dev      # noqa: F401 -- dev: the module's fixture
 
 pytestmark = pytest.mark.gpu
-GUARD_BYTES = 256
-
-
-@pytest.fixture(scope="module")
-def dev(built_lib):
-    import torch
-    from crychic_renderer_amd import Context
-    ctx = Context(0)
-    yield built_lib, ctx, torch
-    ctx.close()
-
-
-def guarded_plane(torch, ctx, host, misalign=0):
-    """(raw, view): a device copy of the numpy array `host` (uint8 or uint32) inside a uint8 buffer of 0xA5, GUARD_BYTES of them on
-    either side; the view starts `misalign` bytes past a 256-byte boundary of the allocation."""
-    n = host.nbytes
-    raw = torch.full((n + 2 * GUARD_BYTES + 16,), fg.GUARD, dtype=torch.uint8, device=ctx.device)
-    assert raw.data_ptr() % 16 == 0
-    off = GUARD_BYTES + misalign
-    view = raw[off:off + n]
-    view.copy_(torch.from_numpy(np.array(host).view(np.uint8).reshape(-1)).to(ctx.device))
-    return raw, view
-
-
-def guards_intact(raw, view):
-    off = view.data_ptr() - raw.data_ptr()
-    return bool((raw[:off] == fg.GUARD).all()) and bool((raw[off + view.numel():] == fg.GUARD).all())
-
 
 _MAPS = {}
 
@@ -56,9 +29,10 @@ def run_device(dev, frame, img, params=None, row0=0, rows=None, in_place=False, 
     checked."""
     lib, ctx, torch = dev
     H, W = img.shape[:2]
-    sraw, src = guarded_plane(torch, ctx, img, misalign)
-    draw, depth = guarded_plane(torch, ctx, frame.depth, misalign)
-    oraw, out = (sraw, src) if in_place else guarded_plane(torch, ctx, np.full(img.shape, fg.GUARD, np.uint8), misalign)
+    planes = DevicePlanes(dev)
+    src = planes.upload("input", img, misalign, writable=in_place)
+    depth = planes.upload("depth", frame.depth, misalign)
+    out = src if in_place else planes.blank("out", img.shape, np.uint8, misalign)
     maps, mp = device_maps(dev, frame)
     pcb = frame.pass_constants(lib)
     p = None
@@ -70,9 +44,7 @@ def run_device(dev, frame, img, params=None, row0=0, rows=None, in_place=False, 
                                   C.c_void_p(out.data_ptr()), W, H, row0, H - row0 if rows is None else rows, None if p is None else C.byref(p),
                                   C.c_void_p(s.cuda_stream)))
     s.synchronize()
-    assert guards_intact(sraw, src) and guards_intact(oraw, out) and guards_intact(draw, depth), "guard bytes changed"
-    assert np.array_equal(depth.cpu().numpy().view(np.uint32).reshape(H, W), frame.depth), "the depth plane changed"
-    assert in_place or np.array_equal(src.cpu().numpy().reshape(img.shape), img), "the input plane changed"
+    planes.verify()
     assert np.array_equal(maps.cpu().numpy().view(np.uint32), frame.maps), "a map changed"
     return out.cpu().numpy().reshape(img.shape)
 

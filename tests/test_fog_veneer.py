@@ -2,14 +2,12 @@
 (tests/fog_ref) over the plain frame and the depth plane, pass constants and cascade maps the application rendered; with the
 anti-aliasing on as well, the second back buffer is the anti-aliasing checker's frame over the fogged one; with it off the frame is
 the plain one again; a bad parameter is refused and a strip with it on throws."""
-import subprocess
-
 import numpy as np
 import pytest
 
 import fog_lib as fg
 import post_aa_lib as aa
-from test_cpp_veneer import build_driver
+from test_cpp_veneer import build_driver, run_driver
 
 
 def test_fog_driver_compiles(built_lib):
@@ -19,18 +17,8 @@ def test_fog_driver_compiles(built_lib):
 
 @pytest.mark.gpu
 def test_veneer_fog(built_lib, tmp_path):
-    import torch
-    from crychic_renderer_amd import scene
-    exe = build_driver("fog_driver")
     W, H, SD, CD, BC, NL = 128, 96, 256, 32, 2, 1
-    d = str(tmp_path)
-    scene.make_cubemap(CD, torch.device("cpu")).numpy().tofile(d + "/cube.bin")
-    r = subprocess.run([exe, d, str(W), str(H), str(SD), str(CD), str(BC), str(NL)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "fog driver ok" in r.stdout
-
-    def frame(name):
-        return np.fromfile(d + "/" + name, np.uint8).reshape(H, W, 4)
+    d, frame = run_driver("fog_driver", tmp_path, W, H, SD, CD, BC, NL, "fog driver ok")
     plain = frame("plain.bin")
     depth = np.fromfile(d + "/depth.bin", np.uint32).reshape(H, W)
     maps = np.stack([np.fromfile(d + "/shadow%d.bin" % j, np.uint32).reshape(SD, SD) for j in range(4)])

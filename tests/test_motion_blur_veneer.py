@@ -3,13 +3,11 @@ after a resize, has no previous camera and copies the frame; every frame's buffe
 (tests/motion_blur_ref) and the library called from Python over what the application rendered and the matrices it kept; the pass reads
 the depth of field's buffer and the bloom and the anti-aliasing read the pass's; with it off the frame is the plain one again; bad
 parameters are refused and a strip with it on throws."""
-import subprocess
-
 import numpy as np
 import pytest
 
 import motion_blur_lib as mbl
-from test_cpp_veneer import build_driver
+from test_cpp_veneer import build_driver, run_driver
 
 SHUTTER, SAMPLES, RADIUS = 256, 16, 24          # the caller's parameters the driver sets for its five frames
 
@@ -24,17 +22,9 @@ def test_veneer_motion_blur(built_lib, tmp_path):
     import torch
     import bloom_lib
     import post_aa_lib as aa
-    from crychic_renderer_amd import Context, scene
-    exe = build_driver("motion_blur_driver")
+    from crychic_renderer_amd import Context
     W, H, SD, CD, BC, NL = 128, 96, 256, 32, 2, 1
-    d = str(tmp_path)
-    scene.make_cubemap(CD, torch.device("cpu")).numpy().tofile(d + "/cube.bin")
-    r = subprocess.run([exe, d, str(W), str(H), str(SD), str(CD), str(BC), str(NL)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "motion blur driver ok" in r.stdout
-
-    def frame(name):
-        return np.fromfile(d + "/" + name, np.uint8).reshape(H, W, 4)
+    d, frame = run_driver("motion_blur_driver", tmp_path, W, H, SD, CD, BC, NL, "motion blur driver ok")
 
     def record(tag):
         m = np.fromfile(d + "/mats_%s.bin" % tag, np.float32)

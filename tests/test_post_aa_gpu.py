@@ -6,50 +6,25 @@ import numpy as np
 import pytest
 
 import post_aa_lib as aa
+from post_pass_lib import DevicePlanes, dev      # noqa: F401 -- dev: the module's fixture
 
 pytestmark = pytest.mark.gpu
-GUARD_BYTES = 256
-
-
-@pytest.fixture(scope="module")
-def dev(built_lib):
-    import torch
-    from crychic_renderer_amd import Context
-    ctx = Context(0)
-    yield built_lib, ctx, torch
-    ctx.close()
-
-
-def guarded_plane(torch, ctx, shape, misalign=0):
-    """(raw, view): a (H, W, 4) uint8 device view inside a buffer of 0xA5, GUARD_BYTES of them on either side; the view starts
-    `misalign` bytes past a 256-byte boundary of the allocation."""
-    n = int(np.prod(shape))
-    raw = torch.full((n + 2 * GUARD_BYTES + 16,), aa.GUARD, dtype=torch.uint8, device=ctx.device)
-    assert raw.data_ptr() % 16 == 0
-    off = GUARD_BYTES + misalign
-    return raw, raw[off:off + n].view(*shape)
-
-
-def guards_intact(raw, view):
-    off = view.data_ptr() - raw.data_ptr()
-    return bool((raw[:off] == aa.GUARD).all()) and bool((raw[off + view.numel():] == aa.GUARD).all())
 
 
 def run_device(dev, img, params=None, row0=0, rows=None, misalign=0):
     """crychic_antialias on guarded device copies of `img`; returns the output plane as numpy, the guards and the input checked."""
     lib, ctx, torch = dev
-    sraw, src = guarded_plane(torch, ctx, img.shape, misalign)
-    oraw, out = guarded_plane(torch, ctx, img.shape, misalign)
-    src.copy_(torch.from_numpy(np.array(img)).to(ctx.device))         # a writable copy: the corpus is read-only
+    planes = DevicePlanes(dev)
+    src = planes.upload("input", img, misalign)
+    out = planes.blank("out", img.shape, np.uint8, misalign)
     H, W = img.shape[:2]
     p = None if params is None else lib.AAParams(*(int(v) for v in aa.params_array(params)))
     s = torch.cuda.current_stream(ctx.device)
     lib.check(lib.lib.crychic_antialias(ctx.handle, C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()), W, H, row0, H - row0 if rows is None else rows,
                                         None if p is None else C.byref(p), C.c_void_p(s.cuda_stream)))
     s.synchronize()
-    assert guards_intact(sraw, src) and guards_intact(oraw, out), "guard bytes changed"
-    assert np.array_equal(src.cpu().numpy(), img), "the input plane changed"
-    return out.cpu().numpy()
+    planes.verify()
+    return out.cpu().numpy().reshape(img.shape)
 
 
 @pytest.mark.parametrize("pname", list(aa.PARAM_SETS))

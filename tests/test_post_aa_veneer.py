@@ -2,13 +2,12 @@
 frame, which equals the checker (tests/post_aa_ref) on the plain frame; with it off the frame is the oracle's, as before; a strip with
 it on throws."""
 import ctypes as C
-import subprocess
 
 import numpy as np
 import pytest
 
 import post_aa_lib as aa
-from test_cpp_veneer import build_driver
+from test_cpp_veneer import build_driver, run_driver
 
 
 def test_post_aa_driver_compiles(built_lib):
@@ -29,17 +28,9 @@ def test_veneer_anti_aliasing(built_lib, oracle, tmp_path):
     import raster_util
     import torch
     from crychic_renderer_amd import geometry as g, scene
-    exe = build_driver("post_aa_driver")
     W, H, SD, CD, BC, NL = 128, 96, 256, 32, 2, 1
-    d = str(tmp_path)
+    d, frame = run_driver("post_aa_driver", tmp_path, W, H, SD, CD, BC, NL, "post aa driver ok")
     cube = scene.make_cubemap(CD, torch.device("cpu")).numpy()
-    cube.tofile(d + "/cube.bin")
-    r = subprocess.run([exe, d, str(W), str(H), str(SD), str(CD), str(BC), str(NL)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "post aa driver ok" in r.stdout
-
-    def frame(name):
-        return np.fromfile(d + "/" + name, np.uint8).reshape(H, W, 4)
     plain = frame("plain.bin")
     # with the switch off the frame is today's: the all-CPU oracle frame of the built-in scene
     consts = raster_util.frame_constants(W, H, SD)

@@ -6,8 +6,6 @@ For each switch subset the driver draws -- none, each alone, every pair of buffe
 nearest stage in front of it), all five, each with and without the fog -- and both of its frames, every set stage's buffer equals
 that pass's checker over the buffer of the nearest set stage in front of it (the back buffer if there is none), Present wrote the last
 set stage's buffer, and with all switches off again the frame is the first plain one."""
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -16,7 +14,7 @@ import dof_lib
 import motion_blur_lib as mbl
 import post_aa_lib as aa
 import taa_lib as ta
-from test_cpp_veneer import build_driver
+from test_cpp_veneer import build_driver, run_driver
 
 FOG, TAA, DOF, MB, BLOOM, AA = 1, 2, 4, 8, 16, 32      # the driver's mask bits, in the chain's order
 STAGES = ((TAA, "taa"), (DOF, "dof"), (MB, "mb"), (BLOOM, "bloom"), (AA, "aa"))
@@ -44,15 +42,8 @@ def test_post_chain_driver_compiles(built_lib):
 
 @pytest.mark.gpu
 def test_veneer_post_chain(built_lib, tmp_path):
-    import torch
-    from crychic_renderer_amd import scene
-    exe = build_driver("post_chain_driver")
     W, H, SD, CD, BC, NL = 128, 96, 256, 32, 2, 1
-    d = str(tmp_path)
-    scene.make_cubemap(CD, torch.device("cpu")).numpy().tofile(d + "/cube.bin")
-    r = subprocess.run([exe, d, str(W), str(H), str(SD), str(CD), str(BC), str(NL)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "post chain driver ok" in r.stdout and "%d subsets" % len(MASKS) in r.stdout
+    d, _ = run_driver("post_chain_driver", tmp_path, W, H, SD, CD, BC, NL, "post chain driver ok %dx%d, %d subsets" % (W, H, len(MASKS)))
 
     def frame(name, m, k):
         return np.fromfile("%s/%s_%d_%d.bin" % (d, name, m, k), np.uint8).reshape(H, W, 4)

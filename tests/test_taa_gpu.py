@@ -8,18 +8,10 @@ import numpy as np
 import pytest
 
 import taa_lib as ta
+from post_pass_lib import dev      # noqa: F401 -- the module's fixture
 from recorder_lib import Recorder
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def dev(built_lib):
-    import torch
-    from crychic_renderer_amd import Context
-    ctx = Context(0)
-    yield built_lib, ctx, torch
-    ctx.close()
 
 
 def test_device_equals_checker(dev):

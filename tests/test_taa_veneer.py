@@ -3,13 +3,11 @@ resize, is a reset frame; every later frame's buffer and history equal the check
 over what the application rendered and the matrices it kept; the jitter follows crychic_taa_jitter and moves the frame; the depth of
 field and the anti-aliasing read the pass's buffer; with it off the frame is the plain one again; bad parameters are refused and a
 strip with it on throws."""
-import subprocess
-
 import numpy as np
 import pytest
 
 import taa_lib as ta
-from test_cpp_veneer import build_driver
+from test_cpp_veneer import build_driver, run_driver
 
 BLEND = 64          # the caller's blend the driver sets for its five frames
 
@@ -23,17 +21,9 @@ def test_taa_driver_compiles(built_lib):
 def test_veneer_taa(built_lib, tmp_path):
     import torch
     import post_aa_lib as aa
-    from crychic_renderer_amd import Context, scene
-    exe = build_driver("taa_driver")
+    from crychic_renderer_amd import Context
     W, H, SD, CD, BC, NL = 128, 96, 256, 32, 2, 1
-    d = str(tmp_path)
-    scene.make_cubemap(CD, torch.device("cpu")).numpy().tofile(d + "/cube.bin")
-    r = subprocess.run([exe, d, str(W), str(H), str(SD), str(CD), str(BC), str(NL)], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "taa driver ok" in r.stdout
-
-    def frame(name):
-        return np.fromfile(d + "/" + name, np.uint8).reshape(H, W, 4)
+    d, frame = run_driver("taa_driver", tmp_path, W, H, SD, CD, BC, NL, "taa driver ok")
 
     def record(tag):
         m = np.fromfile(d + "/mats_%s.bin" % tag, np.float32)
