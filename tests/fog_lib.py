@@ -175,13 +175,34 @@ def straight_down_frame(W, H, dim, column):
     return f
 
 
+TIE_QI = 62960      # with N = 16: T_13 = 38912 and T_13 qi = 37382 * 65536 + 32768, so T_14 .. T_16 depend on the rounding constant
+
+
+def tie_frame(W, H, dim):
+    """The reference camera over a sphere around the eye: every pixel at the distance L at which the default parameters give
+    qi == TIE_QI (the middle of that qi's range of L, about 32.08 units, where the range is 0.0135 units wide and a D24 step moves L by
+    less than 0.0001), under maps with nothing in the way.  The depth words are found by bisection on a float64 reconstruction."""
+    from post_restate import world_point64
+    pcb = camera_constants(W, H, dim)
+    frame = Frame.from_pass_cb(pcb, np.zeros((H, W), np.uint32), make_maps("ones", dim, None))
+    per_unit = float(np.float32(DEFAULTS["density"]) * np.float32(1.44269504) / np.float32(DEFAULTS["steps"]))
+    want = -np.log2(TIE_QI / 65536.0) / per_unit
+    lo, hi = np.zeros((H, W), np.int64), np.full((H, W), 0xFFFFFF, np.int64)
+    for _ in range(24):         # L grows with the depth word
+        mid = (lo + hi) >> 1
+        r = world_point64(frame.ivp, mid, W, H) - frame.eye.astype(np.float64)
+        nearer = np.sqrt((r * r).sum(axis=-1)) < want
+        lo, hi = np.where(nearer, mid, lo), np.where(nearer, hi, mid)
+    return Frame(frame.ivp, frame.eye, frame.st, hi.astype(np.uint32), frame.maps)
+
+
 _CORPUS = {}
 
 
 def corpus():
     """[(name, Frame, image, parameter-set name, (depth kind, map kind))]: built once and read-only.  The rendered frames under every
     parameter set; every size of SIZES under combinations that between them take every map side, depth kind, map kind and parameter
-    set; an eye far outside the cascades; non-finite entries in InvViewProj."""
+    set; an eye far outside the cascades; non-finite entries in InvViewProj; the rounding tie of T."""
     if "cases" in _CORPUS:
         return _CORPUS["cases"]
     rng = np.random.default_rng(20)
@@ -212,6 +233,10 @@ def corpus():
         for k, val in edits.items():
             ivp[k] = val
         cases.append(("ivp_" + tag, Frame(ivp, base.eye, base.st, base.depth, base.maps), img, "default", ("random", "random")))
+    # the rounding of T (tests/test_post_restate_host.py, mutation t_round_32767): a constant of 32767 for 32768 shows only where
+    # T_i qi is 32768 mod 65536, once in 65536 products, which no other case meets in a byte
+    cases.append(("64x64_t_rounding_tie_default", tie_frame(64, 64, 17), rng.integers(0, 256, (64, 64, 4), dtype=np.uint8), "default",
+                  ("rendered", "ones")))
     for _, frame, im, _, _ in cases:
         for arr in (frame.ivp, frame.eye, frame.st, frame.depth, frame.maps, im):
             arr.setflags(write=False)
