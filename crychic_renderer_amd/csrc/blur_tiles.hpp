@@ -8,6 +8,10 @@
 //   blur_replay_tile  a later iteration of one tile, both sweeps, replaying the recorded decisions: ambient values and masks of
 //                     the tile + apron are staged in one burst of loads, the sweeps touch only LDS, and rows whose whole window
 //                     is 1.0 skip their taps.
+//   blur_replay_fetch_masks / blur_replay_rows / blur_replay_cols
+//                     the same iteration split into fetch and resolve: a lane's six decision words go to registers ahead of
+//                     everything else, the sweeps take them from there (the single-launch chain issues the fetch before it
+//                     waits for the neighbouring tiles; blur_replay_tile_split runs the halves back to back).
 //
 // Tiles whose whole neighbourhood came out of the SSAO pass as 65535 ("unoccluded tiles", ssao_core.hpp) are settled by the first
 // launch (it writes 65535 and a per-tile flag) and cost the later launches one scalar load.
@@ -89,6 +93,7 @@ struct BlockSeq {
     CRY_HD bool wave_all(bool p) const { return p; }
     CRY_HD bool wave_leader() const { return true; }
     CRY_HD void wave_sync() const {}         // device: orders a wavefront's LDS writes before its other lanes' reads of them
+    CRY_HD void loads_issued() const {}      // device: keeps the instruction scheduler from moving a batch's first use into the batch
     // accesses to the ambient planes of a replay iteration (kernels.hip: device-coherent in the single-launch chain)
     CRY_HD uint32_t amb_load(const uint16_t* p) const { return *p; }
     CRY_HD void amb_store(uint16_t* p, uint32_t v) const { *p = (uint16_t)v; }
@@ -331,6 +336,157 @@ CRY_HD void blur_replay_tile(const Block& blk, const BlurTileArgs& a, uint32_t s
             }
         });
     }
+}
+
+// ---- the same iteration split into fetch and resolve: the decision words in registers --------------------------------------------
+// blur_replay_tile stages the decision words of all 74 x 26 positions, but the horizontal sweep of staged row ly only ever reads
+// word (ly, l + 5) in lane l and the vertical sweep of tile row ty word (ty + 5, l + 5) >> 16: a lane's own column.  With NW
+// wavefronts per tile (wavefront wv takes staged rows wv, wv + NW, .. and tile rows wv, wv + NW, ..) that is kH + kV words per
+// lane -- 4 + 2 with the kernels' 8 wavefronts -- and none of the ten apron columns.
+//   blur_replay_fetch_masks   only issues those loads (plain loads: the words are the pair launch's, nothing writes them inside a
+//                             replay launch, so the chain kernel issues them AHEAD of its wait for the neighbouring tiles);
+//   blur_replay_rows          stages the ambient values of the wavefront's rows and runs their horizontal sweep (s_in, s_mid);
+//   blur_replay_cols          after a barrier of the workgroup: the vertical sweep of the wavefront's tile rows.
+// The clamps, the operands and their order are blur_replay_tile's: same bits.  blk.wave() is the wavefront's index WITHIN the
+// tile, 0 .. NW - 1 (a workgroup may hold more than one tile: kernels.hip blur_replay_chain_kernel); the barrier between the
+// two halves is the caller's, so that wavefronts of a tile that has nothing to do can meet it too.
+// s_in: kBlurPairSW * kBlurPairSH words; s_mid: kBlurTileW * kBlurPairSH; s_rows: kBlurMaxWaves words (all per tile).
+template <class Block, int NW>
+struct BlurReplayMasks {
+    static_assert(NW >= 1 && NW <= kBlurMaxWaves, "s_rows holds one word per wavefront of a tile");
+    static constexpr int kH = (kBlurPairSH + NW - 1) / NW, kV = (kBlurTileH + NW - 1) / NW;
+    uint32_t h[kH][Block::kLanes], v[kV][Block::kLanes];         // per lane (kLanes = 1 on the device)
+};
+
+template <int NW, class Block>
+CRY_HD void blur_replay_fetch_masks(const Block& blk, const BlurTileArgs& a, BlurReplayMasks<Block, NW>& mk)
+{
+    constexpr int SH = kBlurPairSH, R = kBlurRadius;
+    using M = BlurReplayMasks<Block, NW>;
+    const int wv = blk.wave();
+    blk.lanes([&](int l) {
+        const int s = l % Block::kLanes;
+        const uint32_t cx = (uint32_t)clampi(a.x0 + l, 0, a.w2 - 1);
+#pragma unroll
+        for (int m = 0; m < M::kH; ++m) {
+            const int ly = wv + m * NW < SH ? wv + m * NW : SH - 1;
+            mk.h[m][s] = a.e.masks[(uint32_t)clampi(a.y0 - R + ly, 0, a.h2 - 1) * (uint32_t)a.w2 + cx];
+        }
+#pragma unroll
+        for (int m = 0; m < M::kV; ++m) {
+            const int ty = wv + m * NW < kBlurTileH ? wv + m * NW : kBlurTileH - 1;
+            mk.v[m][s] = a.e.masks[(uint32_t)clampi(a.y0 + ty, 0, a.h2 - 1) * (uint32_t)a.w2 + cx];
+        }
+    });
+}
+
+template <int NW, class Block>
+CRY_HD void blur_replay_rows(const Block& blk, const BlurTileArgs& a, bool onesShortcut, const BlurReplayMasks<Block, NW>& mk, float* s_in,
+                             float* s_mid, uint32_t* s_rows)
+{
+    constexpr int SW = kBlurPairSW, SH = kBlurPairSH, R = kBlurRadius, MAXR = BlurReplayMasks<Block, NW>::kH;
+    const int wv = blk.wave();
+    // stage the wavefront's rows: lanes 0 .. 63 take columns 0 .. 63, lanes 0 .. 9 also columns 64 .. 73
+    bool ones[MAXR];
+    uint32_t raw[MAXR][2][Block::kLanes];
+    blk.lanes([&](int l) {
+        const int s = l % Block::kLanes;
+#pragma unroll
+        for (int m = 0; m < MAXR; ++m) {
+            const int ly = wv + m * NW < SH ? wv + m * NW : SH - 1;
+            const int cy = clampi(a.y0 - R + ly, 0, a.h2 - 1);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int lx = h ? 64 + (l < 10 ? l : 9) : l;
+                const uint32_t p = (uint32_t)cy * (uint32_t)a.w2 + (uint32_t)clampi(a.x0 - R + lx, 0, a.w2 - 1);   // ambient: point / CLAMP
+                raw[m][h][s] = blk.amb_load(a.in + p);
+            }
+        }
+    });
+    blk.loads_issued();                     // every load of the rows in flight before the first is waited for
+#pragma unroll
+    for (int m = 0; m < MAXR; ++m) ones[m] = true;
+    blk.lanes([&](int l) {
+        const int s = l % Block::kLanes;
+#pragma unroll
+        for (int m = 0; m < MAXR; ++m) {
+            const int ly = wv + m * NW;
+            if (ly < SH) {
+                s_in[ly * SW + l] = unorm16_to_float(raw[m][0][s]);
+                bool o = raw[m][0][s] == 0xFFFFu;
+                if (l < 10) {
+                    s_in[ly * SW + 64 + l] = unorm16_to_float(raw[m][1][s]);
+                    o = o && raw[m][1][s] == 0xFFFFu;
+                }
+                ones[m] = ones[m] && o;
+            }
+        }
+    });
+    // horizontal sweep (gHorizontalBlur = 1, Ssao.cpp:240) of the same rows: the wavefront reads what it wrote itself
+    blk.wave_sync();
+    uint32_t onesRows = 0u;                 // bit ly: the horizontal result of staged row ly is all ones (this wavefront's rows)
+#pragma unroll
+    for (int m = 0; m < MAXR; ++m) {
+        const int ly = wv + m * NW;
+        if (ly >= SH) continue;
+        const bool skip = onesShortcut && blk.wave_all(ones[m]);
+        bool outOnes = true;
+        blk.lanes([&](int l) {
+            if (a.x0 + l < a.w2) {
+                float v = 1.0f;
+                if (!skip) {
+                    const uint32_t mh = mk.h[m][l % Block::kLanes] & 0xFFFFu;
+                    const float* row = s_in + ly * SW + l;
+                    v = unorm16_to_float(blur_pixel_replay(a.w, mh, [&](int i) { return row[i]; }));
+                }
+                s_mid[ly * kBlurTileW + l] = v;
+                outOnes = outOnes && v == 1.0f;
+            }
+        });
+        if (skip || (onesShortcut && blk.wave_all(outOnes))) onesRows |= 1u << ly;
+    }
+    if (blk.wave_leader()) s_rows[wv] = onesRows;
+}
+
+template <int NW, class Block>
+CRY_HD void blur_replay_cols(const Block& blk, const BlurTileArgs& a, const BlurReplayMasks<Block, NW>& mk, const float* s_mid,
+                             const uint32_t* s_rows)
+{
+    const int wv = blk.wave();
+    uint32_t hOnes = 0u;
+    for (int w = 0; w < NW; ++w) hOnes |= s_rows[w];
+    // vertical sweep (gHorizontalBlur = 0, Ssao.cpp:241) of the tile
+#pragma unroll
+    for (int m = 0; m < BlurReplayMasks<Block, NW>::kV; ++m) {
+        const int ty = wv + m * NW, y = a.y0 + ty;
+        if (ty >= kBlurTileH || y < a.row0 || y >= a.row1) continue;
+        const bool skip = ((hOnes >> ty) & 0x7FFu) == 0x7FFu;          // staged rows ty .. ty + 10 = taps y - 5 .. y + 5
+        blk.lanes([&](int l) {
+            const int x = a.x0 + l;
+            if (x < a.w2) {
+                uint32_t v = 0xFFFFu;
+                if (!skip) {
+                    const uint32_t mv = mk.v[m][l % Block::kLanes] >> 16;
+                    const float* col = s_mid + ty * kBlurTileW + l;
+                    v = blur_pixel_replay(a.w, mv, [&](int i) { return col[i * kBlurTileW]; });
+                }
+                blk.amb_store(a.out + ((uint32_t)y * (uint32_t)a.w2 + (uint32_t)x), v);
+            }
+        });
+    }
+}
+
+// blur_replay_tile through the two halves, back to back (the host build; a kernel that has no wait to hide the fetch behind).
+template <int NW, class Block>
+CRY_HD void blur_replay_tile_split(const Block& blk, const BlurTileArgs& a, uint32_t stamp, bool onesShortcut, float* s_in, float* s_mid,
+                                   uint32_t* s_rows)
+{
+    if (stamp != 0u && a.e.tiles[a.tileIndex] == stamp) return;
+    BlurReplayMasks<Block, NW> mk;
+    blur_replay_fetch_masks<NW>(blk, a, mk);
+    blur_replay_rows<NW>(blk, a, onesShortcut, mk, s_in, s_mid, s_rows);
+    blk.sync();
+    blur_replay_cols<NW>(blk, a, mk, s_mid, s_rows);
 }
 
 }  // namespace cry

@@ -302,6 +302,7 @@ struct BlockDevT {
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
+    __device__ void loads_issued() const { __builtin_amdgcn_sched_barrier(0); }
     __device__ uint32_t amb_load(const uint16_t* p) const
     {
         if (COHERENT) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -372,40 +373,94 @@ __global__ __launch_bounds__(512) void blur_replay_kernel(crychic_ssao_constants
     blur_replay_tile(BlockDev{}, a, stamp, onesShortcut != 0, s_in, s_mask, s_mid, s_rows);
 }
 
-// Iterations 1 .. blurCount - 1 of the chain in ONE launch: workgroup (x, y, z) replays iteration z + 1 of tile (x, y).  What the
-// per-iteration launches get from the kernel boundary -- iteration j reads what iteration j - 1 wrote, and may overwrite the plane
+// Iterations 1 .. blurCount - 1 of the chain in ONE launch: workgroup (x, y, z) replays iteration z + 1 of tiles (2 x, y) and
+// (2 x + 1, y).  What the per-iteration launches get from the kernel boundary -- iteration j reads what iteration j - 1 wrote,
+// and may overwrite the plane
 // iteration j - 1 read -- is a per-tile dependency here: a tile's iteration j needs its own and its eight neighbours' iteration
 // j - 1 COMPLETE (their outputs are its apron; their inputs are the plane it writes).  Every tile publishes its count of completed
 // iterations, tagged with the frame stamp (a stale or uninitialised word never matches), after every wavefront of it has drained
-// its write-through stores; a workgroup polls its up to nine predecessors (relaxed) and executes one agent-scope acquire before it
+// its write-through stores; a workgroup polls its tiles' predecessors (relaxed) and executes one agent-scope acquire before it
 // stages (the hand-off's contract: DESIGN.md "Blur: one launch for the replayed iterations").  Forward progress: workgroups are dispatched in
 // increasing (z, y, x) order and a workgroup only ever waits for workgroups of the layer below, which were dispatched before it
 // and wait for nothing above them.  The poll is bounded all the same: a workgroup that gives up sets EdgePlane::progress's error
 // word and goes on (wrong pixels, never a hang).  Tiles the pair launch settled neither work nor publish nor are waited for.
-// Same tile body as blur_replay_kernel (blur_tiles.hpp blur_replay_tile): same bits.  What it buys is the launch boundaries: two
-// of the chain's four drain-and-refill gaps, and a tile's iteration j + 1 can start while other tiles are still in iteration j.
+// Same bits as blur_replay_kernel: the tile body is blur_replay_tile's, split (blur_tiles.hpp blur_replay_fetch_masks / _rows /
+// _cols).  What the launch buys is the launch boundaries: two of the chain's four drain-and-refill gaps, and a tile's iteration
+// j + 1 can start while other tiles are still in iteration j.
+// What the wait costs is the acquire, and it is paid per WORKGROUP that executes one on a CU.  So (CRY_BLUR_CHAIN_TILES = 2) a
+// workgroup of 1024 threads replays TWO horizontally adjacent tiles -- wavefronts 0 .. 7 tile (2 bx, y), wavefronts 8 .. 15 tile
+// (2 bx + 1, y), each half over LDS arrays of its own -- behind ONE poll set (the up to 12 counters of the 4 x 3 neighbourhood:
+// the columns within one of a tile of the pair that works, settled and out-of-grid tiles skipped), ONE acquire and one barrier;
+// after the common drain and barrier each tile's first lane publishes its counter.  A half whose tile is settled, lies outside
+// the grid (odd tile count) or outside the iteration's rows skips the body and meets every barrier all the same (the barriers
+// are in this kernel's uniform control flow, none inside the halves of the body); a workgroup both of whose tiles are settled
+// returns at once.  And every lane fetches its six recorded decision words (written by the pair launch, by no workgroup of this
+// one) BEFORE the poll: they travel while wavefront 0 waits for the neighbours and for the invalidate.
+// Forward progress, restated for pairs: the grid is (ceil(tiles_x / 2), y, z), dispatched in increasing (z, y, x) order as
+// before; a workgroup of layer z waits only for counters of tiles of layer z - 1, each published by a workgroup of layer z - 1,
+// all of which were dispatched before it and wait for nothing of layer z or above.
+#ifndef CRY_BLUR_CHAIN_TILES
+#define CRY_BLUR_CHAIN_TILES 2        // tiles per workgroup of blur_replay_chain_kernel (1: the probe build's one tile per workgroup)
+#endif
+#ifndef CRY_BLUR_CHAIN_SLEEP
+#define CRY_BLUR_CHAIN_SLEEP 16       // s_sleep between two polls of a counter (units of 64 clocks)
+#endif
 struct BlurChainPlan {
     uint16_t* plane[2];
     uint32_t row0[8], row1[8];      // half-res rows of its output iteration z + 1 owes
     uint32_t in[8];                 // plane index it reads (writes the other)
     uint32_t tileRow0;              // first tile row of the grid (absolute 64 x 16 grid)
 };
-__global__ __launch_bounds__(512) void blur_replay_chain_kernel(crychic_ssao_constants cb, EdgePlane edge, BlurChainPlan plan, uint32_t W, uint32_t H,
-                                                                uint32_t stamp, uint32_t exitStamp, int onesShortcut)
+// The eight wavefronts of ONE tile inside a workgroup of TILES tiles, as the split tile body sees them.
+struct BlockChainTile : BlockDevT<true> {
+    __device__ int wave() const { return (int)((threadIdx.x >> 6) & (uint32_t)(kBlurMaxWaves - 1)); }
+    __device__ int waves() const { return kBlurMaxWaves; }
+};
+template <int TILES>
+__global__ __launch_bounds__(512 * TILES) void blur_replay_chain_kernel(crychic_ssao_constants cb, EdgePlane edge, BlurChainPlan plan, uint32_t W,
+                                                                        uint32_t H, uint32_t stamp, uint32_t exitStamp, int onesShortcut)
 {
-    __shared__ float s_in[kBlurPairSW * kBlurPairSH];
-    __shared__ uint32_t s_mask[kBlurPairSW * kBlurPairSH];
-    __shared__ float s_mid[kBlurTileW * kBlurPairSH];
-    __shared__ uint32_t s_rows[kBlurMaxWaves];
-    const uint32_t it = blockIdx.z, tx = blockIdx.x, ty = plan.tileRow0 + blockIdx.y, ntx = blur_tiles_x(W);
-    const uint32_t tile = ty * ntx + tx;
-    if (exitStamp != 0u && edge.tiles[tile] == exitStamp) return;                     // settled: 65535 in both planes, for good
+    static_assert(TILES == 1 || TILES == 2, "one tile or a pair per workgroup");
+    constexpr int NW = kBlurMaxWaves, NC = TILES + 2;          // wavefronts per tile; tile columns of the neighbourhood
+    __shared__ float s_in[TILES][kBlurPairSW * kBlurPairSH];
+    __shared__ float s_mid[TILES][kBlurTileW * kBlurPairSH];
+    __shared__ uint32_t s_rows[TILES][kBlurMaxWaves];
+    const uint32_t half = TILES == 2 ? threadIdx.x >> 9 : 0u;
+    const uint32_t it = blockIdx.z, tx0 = blockIdx.x * (uint32_t)TILES, ty = plan.tileRow0 + blockIdx.y, ntx = blur_tiles_x(W);
+    // live: in the grid and not settled (settled: 65535 in both planes, for good)
+    bool live[2] = { false, false };
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) live[t] = tx0 + (uint32_t)t < ntx && !(exitStamp != 0u && edge.tiles[ty * ntx + tx0 + (uint32_t)t] == exitStamp);
+    if (!live[0] && !live[1]) return;
+    const uint32_t tx = tx0 + half, tile = ty * ntx + tx;
+    const bool liveHere = half ? live[1] : live[0];
+    const uint32_t row0 = plan.row0[it], row1 = plan.row1[it];
+    const bool mine = ty * (uint32_t)kBlurTileH < row1 && (ty + 1u) * (uint32_t)kBlurTileH > row0;
+    const bool work = liveHere && mine;
+    BlurTileArgs a;
+    a.w = &cb.BlurWeights[0][0];
+    a.e = edge;
+    a.in = plan.plane[plan.in[it]];
+    a.out = plan.plane[plan.in[it] ^ 1u];
+    a.w2 = (int)(W / 2);
+    a.h2 = (int)(H / 2);
+    a.x0 = (int)tx * kBlurTileW;
+    a.y0 = (int)ty * kBlurTileH;
+    a.row0 = (int)row0;
+    a.row1 = (int)row1;
+    a.borderZ = ndc_to_view(cb, 1.0f);
+    a.tileIndex = tile;
+    const BlockChainTile blk{};
+    BlurReplayMasks<BlockChainTile, NW> mk;
+    if (work) blur_replay_fetch_masks<NW>(blk, a, mk);            // issued here, used behind the barrier
     const unsigned long long tag = (unsigned long long)stamp << 8;
     if (it > 0u) {
-        // wait for the 3 x 3 neighbourhood's iteration `it` (count >= it), lanes 0..8 of the first wavefront one tile each
-        if (threadIdx.x < 9u) {
-            const int nx = (int)tx + (int)(threadIdx.x % 3u) - 1, ny = (int)ty + (int)(threadIdx.x / 3u) - 1;
-            const bool inGrid = nx >= 0 && nx < (int)ntx && ny >= (int)plan.tileRow0 && ny < (int)(plan.tileRow0 + gridDim.y);
+        // wait for the neighbourhood's iteration `it` (count >= it), lanes 0 .. 3 NC - 1 of the first wavefront one tile each
+        if (threadIdx.x < (uint32_t)(3 * NC)) {
+            const int off = (int)(threadIdx.x % (uint32_t)NC) - 1;               // tile column relative to the pair's left tile
+            const int nx = (int)tx0 + off, ny = (int)ty + (int)(threadIdx.x / (uint32_t)NC) - 1;
+            const bool wanted = (live[0] && off <= 1) || (live[1] && off >= 0);      // within one column of a tile that is not settled
+            const bool inGrid = wanted && nx >= 0 && nx < (int)ntx && ny >= (int)plan.tileRow0 && ny < (int)(plan.tileRow0 + gridDim.y);
             if (inGrid) {
                 const uint32_t n = (uint32_t)ny * ntx + (uint32_t)nx;
                 if (!(exitStamp != 0u && edge.tiles[n] == exitStamp)) {
@@ -416,7 +471,7 @@ __global__ __launch_bounds__(512) void blur_replay_chain_kernel(crychic_ssao_con
                         // hand-off follows the wait, below
                         const unsigned long long v = __hip_atomic_load(edge.progress + n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         ok = (v >> 8) == (tag >> 8) && (v & 255ull) >= (unsigned long long)it;
-                        if (!ok) __builtin_amdgcn_s_sleep(16);
+                        if (!ok) __builtin_amdgcn_s_sleep(CRY_BLUR_CHAIN_SLEEP);
                     }
                     if (!ok) edge.progress[(size_t)ntx * blur_tiles_y(H)] = tag | 255ull;      // the error word (one past the tiles)
                 }
@@ -432,24 +487,9 @@ __global__ __launch_bounds__(512) void blur_replay_chain_kernel(crychic_ssao_con
         }
         __syncthreads();
     }
-    const uint32_t row0 = plan.row0[it], row1 = plan.row1[it];
-    const bool mine = ty * (uint32_t)kBlurTileH < row1 && (ty + 1u) * (uint32_t)kBlurTileH > row0;
-    if (mine) {
-        BlurTileArgs a;
-        a.w = &cb.BlurWeights[0][0];
-        a.e = edge;
-        a.in = plan.plane[plan.in[it]];
-        a.out = plan.plane[plan.in[it] ^ 1u];
-        a.w2 = (int)(W / 2);
-        a.h2 = (int)(H / 2);
-        a.x0 = (int)tx * kBlurTileW;
-        a.y0 = (int)ty * kBlurTileH;
-        a.row0 = (int)row0;
-        a.row1 = (int)row1;
-        a.borderZ = ndc_to_view(cb, 1.0f);
-        a.tileIndex = tile;
-        blur_replay_tile(BlockDevT<true>{}, a, 0u, onesShortcut != 0, s_in, s_mask, s_mid, s_rows);
-    }
+    if (work) blur_replay_rows<NW>(blk, a, onesShortcut != 0, mk, s_in[half], s_mid[half], s_rows[half]);
+    __syncthreads();
+    if (work) blur_replay_cols<NW>(blk, a, mk, s_mid[half], s_rows[half]);
     // Producer side.  The tile's outputs were device-coherent (write-through, sc1) stores: once EVERY wavefront has seen its own
     // stores acknowledged (s_waitcnt vmcnt(0), written as inline assembly: a workgroup-scope release fence emits no vmcnt wait
     // here, and s_barrier waits for no counter) and has then reached the barrier, the texels are visible to every XCD and one
@@ -458,7 +498,8 @@ __global__ __launch_bounds__(512) void blur_replay_chain_kernel(crychic_ssao_con
     // tools/handoff_isa.py checks this order in the emitted assembly on every path (tests/test_chain_handoff_isa.py).
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_store(edge.progress + tile, tag | (unsigned long long)(it + 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((threadIdx.x & 511u) == 0 && liveHere)
+        __hip_atomic_store(edge.progress + tile, tag | (unsigned long long)(it + 1u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 template <bool ZERO_RADIUS, bool FIX, bool MIPS = false>
@@ -679,7 +720,9 @@ hipError_t launch_blur_replay_chain(const crychic_ssao_constants& cb, const void
     const dim3 g = blur_tile_grid(W, lo, hi - lo);
     plan.tileRow0 = lo / (uint32_t)kBlurTileH;
     const int ones = blur_weights_positive(cb) ? 1 : 0;
-    hipLaunchKernelGGL(blur_replay_chain_kernel, dim3(g.x, g.y, (unsigned)n), dim3(512), 0, stream, cb, e, plan, W, H, stamp, ones ? stamp : 0u, ones);
+    constexpr unsigned T = CRY_BLUR_CHAIN_TILES;       // tiles of a row per workgroup
+    hipLaunchKernelGGL(blur_replay_chain_kernel<(int)T>, dim3((g.x + T - 1u) / T, g.y, (unsigned)n), dim3(512u * T), 0, stream, cb, e, plan, W, H, stamp,
+                       ones ? stamp : 0u, ones);
     return hipGetLastError();
 }
 
