@@ -26,6 +26,7 @@ GBUFFER_F16_MASK = 0x7000
 COMM_ID_BYTES = 128
 AA_MAX_SEARCH = 16            # CRYCHIC_AA_MAX_SEARCH: the longest end search of crychic_antialias, in pixels
 FOG_MAX_STEPS = 64            # CRYCHIC_FOG_MAX_STEPS: the most samples crychic_fog takes along a view ray
+SSR_MAX_STEPS = 64            # CRYCHIC_SSR_MAX_STEPS: the most samples crychic_ssr takes along a reflected ray
 DOF_MAX_RADIUS = 8            # CRYCHIC_DOF_MAX_RADIUS: the largest gather radius of crychic_dof, in pixels
 BLOOM_MAX_LEVELS = 8          # CRYCHIC_BLOOM_MAX_LEVELS: the most levels of crychic_bloom's pyramid
 
@@ -119,6 +120,20 @@ class FogParams(C.Structure):
                 p.steps = int(v)
             else:
                 setattr(p, k, float(v))
+        return p
+
+
+class SsrParams(C.Structure):
+    """crychic_ssr_params: the knobs of crychic_ssr (extension); SsrParams.default() = crychic_ssr_default_params."""
+    _fields_ = [("maxDistance", C.c_float), ("thickness", C.c_float), ("bias", C.c_float), ("maxRoughness", C.c_float), ("steps", C.c_uint32),
+                ("edgeFade", C.c_uint32), ("intensity", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @classmethod
+    def default(cls, **fields):
+        p = cls()
+        check(lib.crychic_ssr_default_params(C.byref(p)))
+        for k, v in fields.items():
+            setattr(p, k, int(v) if k in ("steps", "edgeFade", "intensity", "reserved") else float(v))
         return p
 
 
@@ -304,6 +319,8 @@ PROTOTYPES = {
     "crychic_antialias": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(AAParams), _vp]),
     "crychic_fog_default_params": (_i, [_P(FogParams)]),
     "crychic_fog": (_i, [_vp, _P(PassConstants), _vp, _P(_vp), _u32, _vp, _vp, _u32, _u32, _u32, _u32, _P(FogParams), _vp]),
+    "crychic_ssr_default_params": (_i, [_P(SsrParams)]),
+    "crychic_ssr": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _P(SsrParams), _vp]),
     "crychic_dof_default_params": (_i, [_P(DofParams)]),
     "crychic_dof": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(DofParams), _vp]),
     "crychic_decal_from_box": (_i, [_P(_f), _u32, _u32, _f, _f, _P(Decal)]),

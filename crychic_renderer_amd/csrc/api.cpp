@@ -21,6 +21,7 @@
 #include "cube_mips_core.hpp"
 #include "post_aa_core.hpp"
 #include "fog_core.hpp"
+#include "ssr_core.hpp"
 #include "dof_core.hpp"
 #include "bloom_core.hpp"
 #include "taa_core.hpp"
@@ -885,6 +886,72 @@ int crychic_fog(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32
     std::memcpy(&q, &p, sizeof q);
     CRY_HIP(cry::launch_fog(cb->InvViewProj, cb->EyePosW, cb->ShadowTransforms, depth_dev, shadow_dev, shadowDim, in_rgba8_dev, out_rgba8_dev, W, H,
                             row0, rows, q, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(CRYCHIC_SSR_MAX_STEPS == cry::kSsrMaxSteps && CRYCHIC_SSR_REFINE == cry::kSsrRefine && sizeof(crychic_ssr_params) == 32 &&
+                  sizeof(crychic_ssr_params) == sizeof(cry::SsrParams),
+              "ssr_core.hpp mirrors the ABI");
+
+int crychic_ssr_default_params(crychic_ssr_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    *out = crychic_ssr_params{};
+    out->maxDistance = 20.0f; out->thickness = 0.5f; out->bias = 0.02f; out->maxRoughness = 0.75f;
+    out->steps = 32u; out->edgeFade = 32u; out->intensity = 256u;
+    return 0;
+}
+
+int crychic_ssr(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev, const float* g2_dev,
+                const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                uint32_t flags, const crychic_ssr_params* params, void* stream)
+{
+    // every argument is checked before the context is looked at: a refusal needs no device
+    if (!cb || !g0_dev || !g1_dev || !g2_dev || !depth_dev || !in_rgba8_dev || !out_rgba8_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (flags & ~CRYCHIC_GBUFFER_F16_MASK)
+        return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection flags 0x%x: bits outside CRYCHIC_GBUFFER_G0_F16 | G1_F16 | G2_F16", flags);
+    const void* const planes[3] = { g0_dev, g1_dev, g2_dev };
+    for (int k = 0; k < 3; ++k) {
+        const uintptr_t need = (flags & (CRYCHIC_GBUFFER_G0_F16 << k)) ? 8u : 16u;
+        if (reinterpret_cast<uintptr_t>(planes[k]) & (need - 1u))
+            return fail(CRYCHIC_E_INVALID_ARG, "G-buffer plane %d is not %u-byte aligned", k, (unsigned)need);
+    }
+    const uintptr_t s = reinterpret_cast<uintptr_t>(in_rgba8_dev), d = reinterpret_cast<uintptr_t>(out_rgba8_dev);
+    if ((reinterpret_cast<uintptr_t>(depth_dev) | s | d) & 3u)
+        return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection depth and frame planes are not 4-byte aligned");
+    if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
+    if (int rc = check_extent("frame", W, H, false, 0u)) return rc;                   // a one-dimensional grid, at most 2^27 workgroups
+    if (W > (1u << 22) || H > (1u << 22)) return fail(CRYCHIC_E_UNSUPPORTED, "frame %ux%u exceeds 2^22 columns or rows", W, H);
+    if (int rc = check_rows(kFrameRows, row0, rows, H)) return rc;
+    crychic_ssr_params p;
+    crychic_ssr_default_params(&p);
+    if (params) p = *params;
+    const float big = 3.40282347e38f;
+    if (!(p.maxDistance > 0.0f && p.maxDistance <= big))
+        return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection maxDistance %g is not a finite positive number", (double)p.maxDistance);
+    if (!(p.thickness > 0.0f && p.thickness <= big))
+        return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection thickness %g is not a finite positive number", (double)p.thickness);
+    if (!(p.bias >= 0.0f && p.bias < p.thickness))
+        return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection bias %g outside 0 .. thickness %g", (double)p.bias, (double)p.thickness);
+    if (!(p.maxRoughness >= 0.0f && p.maxRoughness <= 1.0f))
+        return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection maxRoughness %g outside 0 .. 1", (double)p.maxRoughness);
+    if (p.steps == 0 || p.steps > CRYCHIC_SSR_MAX_STEPS)
+        return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection steps %u outside 1 .. %d", p.steps, CRYCHIC_SSR_MAX_STEPS);
+    if (p.edgeFade == 0 || p.edgeFade > 1024u) return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection edgeFade %u outside 1 .. 1024", p.edgeFade);
+    if (p.intensity > 256u) return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection intensity %u outside 0 .. 256", p.intensity);
+    if (p.reserved) return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection reserved word must be 0");
+    const float A = cb->Proj[10], B = cb->Proj[11];
+    if (!(A >= -big && A <= big && B >= -big && B <= big) || B == 0.0f)
+        return fail(CRYCHIC_E_INVALID_ARG, "Proj[10] = %g and Proj[11] = %g must be finite and Proj[11] not 0 (viewZ = Proj[11] / (d - Proj[10]))",
+                    (double)A, (double)B);
+    const size_t bytes = (size_t)W * H * 4u;
+    if (ranges_overlap(s, bytes, d, bytes))
+        return fail(CRYCHIC_E_INVALID_ARG, "the screen-space reflection input and output planes overlap (the pass cannot run in place)");
+    if (int rc = bind(ctx)) return rc;
+    cry::SsrParams q;
+    std::memcpy(&q, &p, sizeof q);
+    CRY_HIP(cry::launch_ssr(cb->Proj, cb->ViewProj, cb->InvViewProj, cb->EyePosW, cb->NearZ, g0_dev, g1_dev, g2_dev, depth_dev, in_rgba8_dev,
+                            out_rgba8_dev, W, H, row0, rows, flags, q, (hipStream_t)stream));
     return 0;
 }
 

@@ -100,6 +100,15 @@ hipError_t launch_fog(const float* invViewProj, const float* eye, const float (*
                       const uint32_t* const* maps, uint32_t dim, const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0,
                       uint32_t rows, const FogParams& p, hipStream_t stream);
 
+// ssr.hip: rows [row0, row0 + rows) of the W x H RGBA8 frame `out`: `in` with its own screen-space reflections blended over it, from
+// the D24 plane `depth` and the G-buffer planes (half4 where formatFlags has the plane's CRYCHIC_GBUFFER_G*_F16 bit) (ssr_core.hpp);
+// proj, viewProj, invViewProj, eye and nearZ are the pass constants' fields, read before the call returns.  One launch on `stream`,
+// none for rows == 0.  The caller has checked the pointers, their alignment and overlap, the sizes, the rows, proj and `p`.
+struct SsrParams;
+hipError_t launch_ssr(const float* proj, const float* viewProj, const float* invViewProj, const float* eye, float nearZ, const void* g0,
+                      const void* g1, const void* g2, const uint32_t* depth, const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H,
+                      uint32_t row0, uint32_t rows, uint32_t formatFlags, const SsrParams& p, hipStream_t stream);
+
 // dof.hip: rows [row0, row0 + rows) of the W x H RGBA8 frame `out`: `in` blurred by the circle of confusion of the D24 plane `depth`
 // (dof_core.hpp); proj is the pass constants' Proj, read before the call returns.  One launch on `stream`, none for rows == 0.  The
 // caller has checked the pointers, their alignment and overlap, the sizes, the rows, proj and `p`.

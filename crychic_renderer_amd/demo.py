@@ -1,6 +1,7 @@
 """python -m crychic_renderer_amd.demo [--size WxH] [--out frame.ppm] [--textures DIR] [--cube FILE.dds] [--gbuffer f32|mixed|f16]
                                    [--capture-env X,Y,Z [--capture-dim N]] [--gloss] [--env-ambient] [--env-specular]
                                    [--probe-box X0,Y0,Z0,X1,Y1,Z1] [--aa]
+                                   [--ssr [--ssr-steps N] [--ssr-distance X] [--ssr-max-roughness X]]
                                    [--fog [--fog-density X] [--fog-steps N]]
                                    [--dof [--dof-focus X] [--dof-aperture X] [--dof-radius N]]
                                    [--bloom [--bloom-threshold N] [--bloom-intensity N] [--bloom-levels N]]
@@ -28,6 +29,10 @@ through it (set_cube_map(parallax=True)): a box's reflection in the floor meets 
 camera.
 --aa: the finished frame goes through the post-process anti-aliasing pass (Crychic.antiAliasing = True: crychic_antialias after the
 lighting pass, the deferred path's stand-in for the framework's 4x MSAA switch) and the anti-aliased buffer is what is written.
+--ssr: screen-space reflections of the lit frame (Crychic.ssr: crychic_ssr after the lighting pass, in front of --fog and every other
+stage, into a buffer of its own on which the fog then works): a smooth surface shows what stands on it, blended over the cube-map
+reflection; --ssr-steps (samples along each ray, default 32, at most 64), --ssr-distance (the ray's length in world units, default 20)
+and --ssr-max-roughness (surfaces at or above it do not reflect, default 0.75) set its parameters.
 --fog: volumetric fog with sun shafts through the cascade maps (Crychic.fog: crychic_fog after the lighting pass, in place on the back
 buffer, in front of --aa); --fog-density (default 0.02) and --fog-steps (default 16, at most 64) set its parameters.
 --dof: depth of field from the depth plane (Crychic.depthOfField: crychic_dof after the lighting pass and the fog, in front of --aa);
@@ -72,6 +77,10 @@ def main():
     ap.add_argument("--probe-box", default="", metavar="X0,Y0,Z0,X1,Y1,Z1", help="box-project the captured reflections through this box around "
                                                                                  "the capture position (needs --capture-env and --gloss)")
     ap.add_argument("--aa", action="store_true", help="anti-alias the finished frame (post-process pass) and write the anti-aliased buffer")
+    ap.add_argument("--ssr", action="store_true", help="screen-space reflections of the lit frame, after the lighting pass and in front of the fog")
+    ap.add_argument("--ssr-steps", type=int, default=None, metavar="N", help="samples along each reflected ray, 1 .. 64 (default 32; needs --ssr)")
+    ap.add_argument("--ssr-distance", type=float, default=None, metavar="X", help="length of a reflected ray in world units (default 20; needs --ssr)")
+    ap.add_argument("--ssr-max-roughness", type=float, default=None, metavar="X", help="surfaces at or above this roughness do not reflect, 0 .. 1 (default 0.75; needs --ssr)")
     ap.add_argument("--fog", action="store_true", help="volumetric fog with sun shafts through the cascades, after the lighting pass")
     ap.add_argument("--fog-density", type=float, default=None, metavar="X", help="fog density, 0 .. 16 (default 0.02; needs --fog)")
     ap.add_argument("--fog-steps", type=int, default=None, metavar="N", help="samples along each view ray, 1 .. 64 (default 16; needs --fog)")
@@ -103,6 +112,8 @@ def main():
         ap.error("--dof-focus, --dof-aperture and --dof-radius need --dof")
     if (a.fog_density is not None or a.fog_steps is not None) and not a.fog:
         ap.error("--fog-density and --fog-steps need --fog")
+    if (a.ssr_steps is not None or a.ssr_distance is not None or a.ssr_max_roughness is not None) and not a.ssr:
+        ap.error("--ssr-steps, --ssr-distance and --ssr-max-roughness need --ssr")
     box = None
     if a.probe_box:
         if not (a.capture_env and a.gloss):
@@ -120,7 +131,7 @@ def main():
     W, H = (int(v) for v in a.size.lower().split("x"))
     import torch
     from . import Context, Crychic, LIGHT_SKY, SceneGeometry, check, geometry as g, lib, scene
-    from ._lib import BloomParams, DofParams, FogParams, MotionBlurParams, PassConstants
+    from ._lib import BloomParams, DofParams, FogParams, MotionBlurParams, PassConstants, SsrParams
     ctx = Context(0)
     consts = scene.Constants(W, H, a.shadow_dim)
     tex = g.reference_textures(a.textures) if a.textures else g.procedural_textures(64)
@@ -180,6 +191,9 @@ def main():
         app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient, env_brdf=a.env_specular,
                          parallax=box is not None)
         print("captured the environment at (%g, %g, %g): %d-texel faces, %d levels" % (pos[0], pos[1], pos[2], dim, levels))
+    if a.ssr:
+        knobs = {k: v for k, v in (("steps", a.ssr_steps), ("maxDistance", a.ssr_distance), ("maxRoughness", a.ssr_max_roughness)) if v is not None}
+        app.ssr = SsrParams.default(**knobs) if knobs else True
     if a.fog:
         knobs = {k: v for k, v in (("density", a.fog_density), ("steps", a.fog_steps)) if v is not None}
         app.fog = FogParams.default(**knobs) if knobs else True
@@ -218,7 +232,7 @@ def main():
     torch.cuda.synchronize()
     img = np.ascontiguousarray(app.final_frame().cpu().numpy())
     check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, W, H))
-    chain = (("fog", "fog"), ("temporalAA", "temporal anti-aliasing"), ("depthOfField", "depth of field"), ("motionBlur", "motion blur"),
+    chain = (("ssr", "screen-space reflections"), ("fog", "fog"), ("temporalAA", "temporal anti-aliasing"), ("depthOfField", "depth of field"), ("motionBlur", "motion blur"),
              ("bloom", "bloom"), ("antiAliasing", "anti-aliased"))                   # Draw()'s order
     print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, "".join(", " + text for switch, text in chain if getattr(app, switch)), ctx.device_name))
 

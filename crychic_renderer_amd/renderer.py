@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (AAParams, CrychicError, FogParams, DofParams, BloomParams, TaaParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, FogParams, SsrParams, DofParams, BloomParams, TaaParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -226,6 +226,8 @@ class Crychic:
         self._antiAliasing = None    # antiAliasing, extension: None | True | AAParams -- Draw() of a whole frame runs crychic_antialias into mBackBufferAA
         self.mBackBufferAA = None    # the anti-aliased frame, allocated by the first antialias() that needs it
         self._fog = None             # fog, extension: None | True | FogParams -- Draw() of a whole frame runs crychic_fog in place on mBackBuffer
+        self._ssr = None             # ssr, extension: None | True | SsrParams -- Draw() of a whole frame runs crychic_ssr into mBackBufferSSR, in front of the fog
+        self.mBackBufferSSR = None   # the frame behind the screen-space reflections, allocated by the first screen_space_reflections() that needs it
         self._depthOfField = None    # depthOfField, extension: None | True | DofParams -- Draw() of a whole frame runs crychic_dof into mBackBufferDoF
         self.mBackBufferDoF = None   # the frame behind the depth-of-field pass, allocated by the first depth_of_field() that needs it
         self._bloom = None           # bloom, extension: None | True | BloomParams -- Draw() of a whole frame runs crychic_bloom into mBackBufferBloom
@@ -250,11 +252,12 @@ class Crychic:
             if name == "_temporalAA" and value and not self._temporalAA:
                 self._taaReset = True            # turned on: whatever the history planes hold is stale
             setattr(self, name, value)
-            self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA or self._motionBlur)
+            self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA or self._motionBlur or self._ssr)
         return property(get, put)
 
     antiAliasing = _post_switch("_antiAliasing")
     fog = _post_switch("_fog")
+    ssr = _post_switch("_ssr")
     depthOfField = _post_switch("_depthOfField")
     bloom = _post_switch("_bloom")
     temporalAA = _post_switch("_temporalAA")
@@ -321,7 +324,7 @@ class Crychic:
         the lighting pass in `parts` row ranges that travel while the next is lit (sharding.StripExchange.draw).
         With a switch of the passes behind the lighting pass set (extensions; True, or the pass's parameter struct): a whole frame,
         then the set passes in the order
-            lighting -> fog (in place) -> temporalAA -> depthOfField -> motionBlur -> bloom -> antiAliasing,
+            lighting -> ssr -> fog (in place on the frame it is handed) -> temporalAA -> depthOfField -> motionBlur -> bloom -> antiAliasing,
         each but the fog from the buffer of the nearest set stage in front of it that writes one of its own (mBackBuffer if there is
         none) into its own mBackBuffer*; final_frame() is the last one.  The temporal pass and the motion blur take the matrices of
         set_frame_view_proj (never called: a still camera); the first frame after temporalAA was turned on is a RESET frame.  A strip
@@ -378,7 +381,7 @@ class Crychic:
     def _draw_post_chain(self, row0, rows, shared):
         """Draw() with a switch set: the lighting frame, then one walk along the chain with the frame each stage reads."""
         if shared is not None or row0 != 0 or (rows is not None and rows != self.mClientHeight):
-            what = next(s for s in ("bloom", "motionBlur", "depthOfField", "temporalAA", "fog", "antiAliasing") if getattr(self, s))
+            what = next(s for s in ("bloom", "motionBlur", "depthOfField", "temporalAA", "fog", "antiAliasing", "ssr") if getattr(self, s))
             raise CrychicError(-1, "%s is set: Draw() takes the whole frame on one GPU (the pass is not sharded and does not run behind the "
                                "exchange)" % what)
         self._draw_lighting(0, None, None)
@@ -386,8 +389,10 @@ class Crychic:
         def params(switch, kind):               # a switch holds True or the pass's parameters
             return switch if isinstance(switch, kind) else None
         frame = self.mBackBuffer
+        if self._ssr:
+            frame = self.screen_space_reflections(src=frame, params=params(self._ssr, SsrParams))
         if self._fog:
-            self.apply_fog(params=params(self._fog, FogParams))
+            self.apply_fog(src=frame, params=params(self._fog, FogParams))
         cur, prev = self._taaViewProj           # of the temporal pass and the motion blur
         if cur is None:                         # set_frame_view_proj was never called: a still camera whose constants are not jittered
             cur = prev = tuple(self.mMainPassCB.ViewProj)
@@ -411,7 +416,7 @@ class Crychic:
                              (self._depthOfField, "mBackBufferDoF"), (self._temporalAA, "mBackBufferTAA")):
             if switch:
                 return getattr(self, name)
-        return self.mBackBuffer
+        return self.mBackBufferSSR if self._ssr else self.mBackBuffer
 
     def _pass_frames(self, who, buffer, src, out, any_shape=False):
         """(src, out, H, W) of the pass method `who`: src defaults to mBackBuffer, out to the attribute `buffer` -- allocated, or
@@ -505,6 +510,18 @@ class Crychic:
         check(lib.crychic_dof(self.ctx.handle, C.byref(self.mMainPassCB), self.mDepthStencilBuffer.data_ptr(), _ptr(src), _ptr(out), W, H,
                               int(row0), int(H - row0 if rows is None else rows), None if params is None else C.byref(params),
                               _stream(self.ctx.device)))
+        return out
+
+    def screen_space_reflections(self, src=None, out=None, row0=0, rows=None, params=None):
+        """crychic_ssr on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferSSR, allocated on first use) from
+        `src` (default: mBackBuffer), both (H, W, 4) uint8 tensors of the frame's size, with this frame's G-buffer in its planes'
+        formats, depth plane and pass constants; params: an SsrParams, None = the defaults.  The pass reads any row of `src` and of the
+        depth plane and writes no other byte of `out`; `src` and `out` must not overlap.  Returns `out`."""
+        src, out, H, W = self._pass_frames("screen_space_reflections", "mBackBufferSSR", src, out)
+        g = self.mDeferred.mGBuffer
+        check(lib.crychic_ssr(self.ctx.handle, C.byref(self.mMainPassCB), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), self.mDepthStencilBuffer.data_ptr(),
+                              _ptr(src), _ptr(out), W, H, int(row0), int(H - row0 if rows is None else rows), gbuffer_flags(g),
+                              None if params is None else C.byref(params), _stream(self.ctx.device)))
         return out
 
     def apply_fog(self, src=None, out=None, row0=0, rows=None, params=None):

@@ -166,6 +166,7 @@ public:
         mBackBuffer = FramePlane();
         if (mAntiAliasing) mBackBufferAA = FramePlane();
         if (mDepthOfField) mBackBufferDoF = FramePlane();
+        if (mScreenSpaceReflections) mBackBufferSSR = FramePlane();
         if (mBloom) AllocateBloom();
         if (mTemporalAA) AllocateTemporalAA();                                                      // new history planes: the next frame is a reset frame
         if (mMotionBlur) AllocateMotionBlur();                                                      // the next frame counts as the first: no previous camera
@@ -210,9 +211,9 @@ public:
 
     void Draw(const GameTimer&)  // CRYCHIC.cpp:172-306, deferred branch
     {
-        if ((!mWholeFrame || mComm) && (mAntiAliasing || mFog || mDepthOfField || mBloom || mTemporalAA || mMotionBlur)) {
+        if ((!mWholeFrame || mComm) && (mAntiAliasing || mFog || mDepthOfField || mBloom || mTemporalAA || mMotionBlur || mScreenSpaceReflections)) {
             const char* pass = mAntiAliasing ? "anti-aliasing" : mFog ? "fog" : mDepthOfField ? "depth of field" : mBloom ? "bloom"
-                             : mTemporalAA ? "temporal anti-aliasing" : "motion blur";
+                             : mTemporalAA ? "temporal anti-aliasing" : mMotionBlur ? "motion blur" : "screen-space reflections";
             throw CrychicException(CRYCHIC_E_INVALID_ARG, std::string("CRYCHIC::Draw (") + pass + " takes the whole frame on one GPU: no SetStrip / JoinNode)",
                                    __FILE__, __LINE__);
         }
@@ -284,10 +285,15 @@ public:
                                                                      mCommandList->Stream()));
         // The passes behind the lighting pass, in the chain's order (the comment above SetAntiAliasing).  `frame` is what the next
         // stage reads: the fog works in place on it, every other stage writes a buffer of its own and hands that on.
-        const uint8_t* frame = f.out_rgba8_dev;
+        uint8_t* frame = f.out_rgba8_dev;
         auto bytes = [](const std::unique_ptr<ID3D12Resource>& r) { return static_cast<uint8_t*>(r->Data()); };
+        if (mScreenSpaceReflections) {          // first: the frame is aligned with the depth plane and the G-buffer, the fog lies over both
+            CrychicThrowIfFailed(crychic_ssr(md3dDevice->Ctx(), passCB, f.g0_dev, f.g1_dev, f.g2_dev, f.depth_dev, frame, bytes(mBackBufferSSR), mClientWidth,
+                                             mClientHeight, 0, mClientHeight, f.flags & CRYCHIC_GBUFFER_F16_MASK, &mSsrParams, mCommandList->Stream()));
+            frame = bytes(mBackBufferSSR);
+        }
         if (mFog)
-            CrychicThrowIfFailed(crychic_fog(md3dDevice->Ctx(), passCB, f.depth_dev, f.shadow_dev, f.shadowDim, f.out_rgba8_dev, f.out_rgba8_dev,
+            CrychicThrowIfFailed(crychic_fog(md3dDevice->Ctx(), passCB, f.depth_dev, f.shadow_dev, f.shadowDim, frame, frame,
                                              mClientWidth, mClientHeight, 0, mClientHeight, &mFogParams, mCommandList->Stream()));
         if (mTemporalAA) {                      // blended into the reprojected history while the frame is still aligned with its depth plane
             crychic_taa_params tp = mTaaParams;
@@ -326,12 +332,14 @@ public:
     }
 
     // ---- the passes behind the lighting pass (extensions) -----------------------------------------------------------------------------
-    // Six switches, all off by default (then nothing changes).  With any of them on, Draw takes a whole frame on one GPU -- SetStrip /
+    // Seven switches, all off by default (then nothing changes).  With any of them on, Draw takes a whole frame on one GPU -- SetStrip /
     // JoinNode make it throw, the passes are not sharded -- and issues those that are on behind the lighting pass in the order
-    //     lighting -> fog (in place) -> temporal anti-aliasing -> depth of field -> motion blur -> bloom -> anti-aliasing.
-    // The fog works in place on the back buffer.  Every other stage reads the buffer of the nearest stage in front of it that is on
-    // and writes one (the back buffer if there is none) and writes a buffer of its own, which exists while the stage is on and which
-    // OnResize re-creates; Present writes the last one.  CurrentBackBuffer stays the (fogged) frame without them.  A setter's p == nullptr:
+    //     lighting -> screen-space reflections -> fog (in place) -> temporal anti-aliasing -> depth of field -> motion blur -> bloom -> anti-aliasing.
+    // The fog works in place on the frame it is handed: the reflections' buffer if they are on, the back buffer if not.  Every other
+    // stage reads the buffer of the nearest stage in front of it that is on and writes one (the back buffer if there is none) and
+    // writes a buffer of its own, which exists while the stage is on and which OnResize re-creates; Present writes the last one.
+    // CurrentBackBuffer stays the lit frame without them -- fogged unless the reflections took the fog onto their buffer.  A setter's
+    // p == nullptr:
     // the pass's default parameters; parameters outside their ranges are refused and leave the switch as it was.
 
     // ---- anti-aliasing ------------------------------------------------------------------------------------------------------------
@@ -370,6 +378,29 @@ public:
         mFogParams = q;
     }
     bool Fog() const { return mFog; }
+
+    // ---- screen-space reflections ------------------------------------------------------------------------------------------------------
+    // The lit frame's own reflections from the depth plane and the G-buffer (include/crychic_hip.h crychic_ssr), in front of the fog.
+    void SetScreenSpaceReflections(bool on, const crychic_ssr_params* p = nullptr)
+    {
+        crychic_ssr_params q;
+        CrychicThrowIfFailed(crychic_ssr_default_params(&q));
+        if (p) q = *p;
+        const float big = 3.40282347e38f;
+        if (!(q.maxDistance > 0.0f && q.maxDistance <= big) || !(q.thickness > 0.0f && q.thickness <= big) || !(q.bias >= 0.0f && q.bias < q.thickness) ||
+            !(q.maxRoughness >= 0.0f && q.maxRoughness <= 1.0f) || q.steps == 0 || q.steps > CRYCHIC_SSR_MAX_STEPS || q.edgeFade == 0 || q.edgeFade > 1024u ||
+            q.intensity > 256u || q.reserved)
+            throw CrychicException(CRYCHIC_E_INVALID_ARG,
+                                   "CRYCHIC::SetScreenSpaceReflections (maxDistance and thickness finite and > 0, bias 0 .. thickness, maxRoughness 0 .. 1, "
+                                   "steps 1 .. 64, edgeFade 1 .. 1024, intensity 0 .. 256, reserved 0)", __FILE__, __LINE__);
+        mCommandList->Flush();                                  // a frame in flight may still write the buffer released below
+        mScreenSpaceReflections = on;
+        mSsrParams = q;
+        if (on) mBackBufferSSR = FramePlane();
+        else mBackBufferSSR.reset();
+    }
+    bool ScreenSpaceReflections() const { return mScreenSpaceReflections; }
+    ID3D12Resource* ScreenSpaceReflectionsBackBuffer() { return mBackBufferSSR.get(); }
 
     // ---- depth of field ----------------------------------------------------------------------------------------------------------------
     // A thin-lens blur from the depth plane (include/crychic_hip.h crychic_dof).
@@ -1213,6 +1244,9 @@ private:
     std::unique_ptr<ID3D12Resource> mDecals;  // SetDecals: the device array
     uint32_t mDecalCount = 0;
     std::vector<crychic_texture> mDecalTextures;
+    bool mScreenSpaceReflections = false;     // SetScreenSpaceReflections
+    crychic_ssr_params mSsrParams = {};
+    std::unique_ptr<ID3D12Resource> mBackBufferSSR;  // the frame behind the screen-space reflections, while mScreenSpaceReflections
     bool mDepthOfField = false;               // SetDepthOfField
     crychic_dof_params mDofParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferDoF;  // the frame behind the depth-of-field pass, while mDepthOfField
@@ -1276,7 +1310,7 @@ private:
     ID3D12Resource* FinalFrame() const           // where Draw leaves the finished frame: the buffer of the last stage that is on
     {
         return (mAntiAliasing ? mBackBufferAA : mBloom ? mBackBufferBloom : mMotionBlur ? mBackBufferMB : mDepthOfField ? mBackBufferDoF
-                : mTemporalAA ? mBackBufferTAA : mBackBuffer).get();
+                : mTemporalAA ? mBackBufferTAA : mScreenSpaceReflections ? mBackBufferSSR : mBackBuffer).get();
     }
     std::unique_ptr<ID3D12Resource> mDepthStencilBuffer, mBackBuffer, mCubeMap;
     std::unique_ptr<ID3D12Resource> mPointLights, mSpotLights;   // SetLocalLights

@@ -925,6 +925,82 @@ int crychic_fog(crychic_ctx* ctx, const crychic_pass_constants* cb, const uint32
                 uint32_t shadowDim, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0,
                 uint32_t rows, const crychic_fog_params* params /* NULL = defaults */, void* stream);
 
+/* ---- screen-space reflections of the lit frame (extension) -------------------------------------------------
+ * One pass over the finished RGBA8 frame, a separate call after the lighting pass and before the fog: a pixel whose surface is
+ * smooth enough follows its mirrored view ray across the depth plane and, where the ray meets a surface on screen, blends the
+ * frame's texel there over its own, weighed by the surface's Fresnel term and faded towards the border of the frame and the end of
+ * the ray.  The lighting pass adds its reflection term after the tone map, so the blend is display-referred like that term.  A build
+ * definition: nothing of it is the reference's.  The device, a host build and the checker (tests/ssr_ref) agree bit for bit.
+ *
+ * Float operations are IEEE binary32, each rounded once, in the order written; fma is fused only where written.  rcp, len_from_sq,
+ * dot3, mulcol and d24_to_float are those of crychic_fog; lerpf, saturate, clampf and normalize3 those of crychic_apply_decals;
+ * reflect3(i, n) = (fma(-t, n.x, i.x), fma(-t, n.y, i.y), fma(-t, n.z, i.z)) with t = 2.0f dot3(n, i).  x / w below stands for x rcp(w).
+ *
+ * Host side, once per call, with N = steps:  A = cb->Proj[10], B = cb->Proj[11] in memory order (viewZ = B / (d - A), as in
+ * crychic_dof), both finite and B != 0;  sx = 2.0f / (float)W;  sy = 2.0f / (float)H;  Wf = (float)W;  Hf = (float)H;  hw = Wf 0.5f;
+ * hh = Hf 0.5f;  invN = 1.0f / (float)N;  wmin = cb->NearZ.
+ * Per pixel (px, py), Eye = EyePosW, with in, depth and the G-buffer planes indexed by py W + px:
+ *   1  u = depth & 0xFFFFFF;  rough = G1.w.  If u == 0xFFFFFF (sky) or !(rough < maxRoughness) (so for a NaN too):  out = in.
+ *   2  d = d24_to_float(u);  P = the world point of crychic_fog's steps 2 and 3;  V = normalize3(P - Eye);  Nw = normalize3(G2.xyz);
+ *      R = reflect3(V, Nw);  Q.c = fma(R.c, maxDistance, P.c).
+ *   3  h0[c] = mulcol(P.x, P.y, P.z, 1.0f, ViewProj + 4c), c = 0 .. 3, and h1 likewise of Q.  If h1.w < wmin:
+ *      tt = (h0.w - wmin) rcp(h0.w - h1.w);  md = maxDistance tt;  Q.c = fma(R.c, md, P.c);  h1 again of that Q (once: no second test).
+ *      If !(h0.w > wmin):  out = in.  screen(h) = (fma(h.x / h.w, hw, hw), fma(-(h.y / h.w), hh, hh), h.z / h.w): pixels and NDC
+ *      depth, which is affine along a line of the screen.  s0 = screen(h0);  ds = screen(h1) - s0.  The sample at t is
+ *      x = fma(ds.x, t, s0.x), y = fma(ds.y, t, s0.y), dr = fma(ds.z, t, s0.z);  it is ok iff
+ *      x >= 0 && x < Wf && y >= 0 && y < Hf && dr < 1.0f (false for a NaN), and then its pixel is ((uint32_t)x, (uint32_t)y).
+ *   4  jit as in crychic_fog's step 6 (the same Bayer matrix).  For i = 0 .. N - 1:  t_i = ((float)i + jit) invN.  A sample that is
+ *      not ok ends the ray: no hit.  A sample in (px, py) itself is skipped.
+ *   5  Otherwise, with v the low 24 bits of the sample pixel's depth word and dz = d24_to_float(v):  D = (dr - A) (dz - A);
+ *      n = B (dz - dr);  the sample is a hit iff  v != 0xFFFFFF && dr > dz && bias D <= n && n <= thickness D  -- the test
+ *      bias <= viewZ(dr) - viewZ(dz) <= thickness without a reciprocal per step.  The first hit, at i = I, ends the march.
+ *   6  lo = (I == 0) ? 0.0f : t_(I-1);  hi = t_I;  the hit pixel is t_I's.  CRYCHIC_SSR_REFINE times:  tm = (lo + hi) 0.5f;  if the
+ *      sample at tm is ok, not in (px, py) and passes the test of step 5 on its own pixel:  hi = tm and the hit pixel is tm's;
+ *      else lo = tm.  t_hit = hi;  (hx, hy) the hit pixel;  hit = in[hy W + hx], a point sample.
+ *   7  per channel c of albedo = G1.xyz, with metalness = G0.w:  R0 = lerpf(0.04f, albedo_c, metalness);
+ *      f0 = 1.0f - saturate(dot3(Nw, R));  f2 = f0 f0;  f5 = (f2 f2) f0;  w = (1.0f - rough) fma(1.0f - R0, f5, R0);
+ *      wq = (uint32_t)fma(clampf(w, 0.0f, 1.0f), 65536.0f, 0.5f), 0 .. 65536.  From here on unsigned integers.
+ *   8  e = min(hx, W - 1 - hx, hy, H - 1 - hy);  fe = min(e, E) 65536 / E with E = edgeFade (floor);  tq = (uint32_t)(t_hit 65536.0f);
+ *      fd = min(65536, 4 (65536 - tq));  K = ((((wq fe) >> 16) fd) >> 16) intensity >> 8, the two inner products in 64 bits; 0 .. 65536.
+ *   9  out = (in (65536 - K) + hit K + 32768) >> 16 for R, G, B;  alpha is the pixel's own.  No hit:  out = in.
+ * Known answers: maxRoughness 0, a depth plane of sky or intensity 0 give out == in byte for byte; a frame of one colour stays
+ * that colour under any G-buffer, depth and parameters; alpha is always the pixel's own.
+ * Known limits: the pass reflects only what is on screen and in front; a thin object can fall between two samples; a hit is
+ * weighed by the surface's own Fresnel term and blended OVER the frame, so the cube-map reflection the lighting pass added stays
+ * under the blend and is not removed; the hit colour is not blurred by roughness.
+ *
+ * Parameters: maxDistance (world units, default 20; finite, > 0), thickness (view units, 0.5; finite, > 0), bias (0.02; >= 0 and
+ * below thickness), maxRoughness (0.75; 0 .. 1), steps = N (32; 1 .. CRYCHIC_SSR_MAX_STEPS), edgeFade = E (pixels, 32; 1 .. 1024),
+ * intensity (256; 0 .. 256), reserved (must be 0).  crychic_ssr_default_params fills the defaults (pure host code;
+ * CRYCHIC_E_INVALID_ARG for NULL). */
+#define CRYCHIC_SSR_MAX_STEPS 64
+#define CRYCHIC_SSR_REFINE 4
+typedef struct crychic_ssr_params {
+    float maxDistance;
+    float thickness;
+    float bias;
+    float maxRoughness;
+    uint32_t steps;
+    uint32_t edgeFade;
+    uint32_t intensity;
+    uint32_t reserved;
+} crychic_ssr_params;   /* 32 bytes */
+int crychic_ssr_default_params(crychic_ssr_params* out);
+/* Writes rows [row0, row0 + rows) of out_rgba8_dev and no other byte; reads ANY row of in_rgba8_dev and depth_dev (W x H, D24 in the
+ * low 24 bits) -- the frame, not the row range --, the same rows of the three G-buffer planes, and Proj, ViewProj, InvViewProj, EyePosW
+ * and NearZ of cb (a host pointer, read during the call).  Stitched row ranges therefore equal the whole-frame call byte for byte, for
+ * any row0 and rows; rows == 0 launches nothing.  flags carries only CRYCHIC_GBUFFER_G*_F16 bits: a set bit says that plane's pointer
+ * addresses half4 texels, which widen exactly on read as in the lighting pass, so every format mix equals the call on the widened
+ * planes bit for bit.  in and out must not overlap at all within W * H * 4 bytes: a pixel reads other pixels' texels.  params == NULL
+ * = the defaults.  One launch on `stream`: no allocation, no synchronisation, no host read-back; capturable into a graph.
+ * CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and before anything is enqueued: a NULL plane or cb, a
+ * G-buffer plane that is not 16-byte (half4: 8-byte) aligned, a depth or frame plane that is not 4-byte aligned, W or H of 0, a row
+ * range outside the frame, a parameter outside its range or a non-zero reserved word, unknown flag bits, in and out overlapping, a
+ * non-finite Proj[10] or Proj[11] or Proj[11] == 0.  More than 2^28 pixels, or more than 2^22 columns or rows: CRYCHIC_E_UNSUPPORTED. */
+int crychic_ssr(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev, const float* g2_dev,
+                const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0,
+                uint32_t rows, uint32_t flags, const crychic_ssr_params* params /* NULL = defaults */, void* stream);
+
 /* ---- depth of field from the depth plane (extension) -------------------------------------------------------
  * One pass over the finished RGBA8 frame, a separate call after the lighting pass (and the fog) and before the anti-aliasing: a
  * thin-lens blur.  Every texel has a circle of confusion from its depth; every output pixel gathers the texels of a disc of radius R
