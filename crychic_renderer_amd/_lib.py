@@ -208,6 +208,22 @@ class TaaParams(C.Structure):
         return p
 
 
+class TaaUpscaleParams(C.Structure):
+    """crychic_taa_upscale_params: the knobs of crychic_taa_upscale (extension; the flags are TAA_RESET and TAA_NO_CLAMP);
+    TaaUpscaleParams.default() = crychic_taa_upscale_default_params, any field replaced by its keyword."""
+    _fields_ = [("blend", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 6)]
+
+    @classmethod
+    def default(cls, blend=None, flags=None):
+        p = cls()
+        check(lib.crychic_taa_upscale_default_params(C.byref(p)))
+        if blend is not None:
+            p.blend = int(blend)
+        if flags is not None:
+            p.flags = int(flags)
+        return p
+
+
 class MotionBlurParams(C.Structure):
     """crychic_motion_blur_params: the knobs of crychic_motion_blur (extension); MotionBlurParams.default() =
     crychic_motion_blur_default_params, any field replaced by its keyword."""
@@ -343,6 +359,9 @@ PROTOTYPES = {
     "crychic_motion_blur_gather": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(MotionBlurParams), _vp, _sz, _vp]),
     "crychic_motion_blur": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _u32, _u32, _P(MotionBlurParams), _vp, _sz, _vp]),
     "crychic_taa": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(TaaParams), _vp]),
+    "crychic_taa_upscale_default_params": (_i, [_P(TaaUpscaleParams)]),
+    "crychic_taa_upscale": (_i, [_vp, _P(PassConstants), _vp, _vp, _f, _f, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _u32,
+                                 _P(TaaUpscaleParams), _vp]),
     "crychic_save_ppm":(_i, [C.c_char_p, _vp, _u32, _u32]),
     "crychic_raster_workspace_bytes": (_sz, [C.c_uint64, _u32, _u32]),
     "crychic_raster_status": (_i, [_vp, _vp, _P(_u32)]),

@@ -25,6 +25,7 @@
 #include "dof_core.hpp"
 #include "bloom_core.hpp"
 #include "taa_core.hpp"
+#include "taa_upscale_core.hpp"
 #include "motion_blur_core.hpp"
 #include "decal_core.hpp"
 #include "internal.hpp"
@@ -1253,6 +1254,63 @@ int crychic_taa(crychic_ctx* ctx, const crychic_pass_constants* cb, const float 
     std::memcpy(&q, &p, sizeof q);
     CRY_HIP(cry::launch_taa(cb->InvViewProj, curViewProj, prevViewProj, depth_dev, in_rgba8_dev, reset ? nullptr : history_in_dev, history_out_dev,
                             out_rgba8_dev, W, H, row0, rows, q, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(CRYCHIC_TAA_UPSCALE_RESET == cry::kTaaReset && CRYCHIC_TAA_UPSCALE_NO_CLAMP == cry::kTaaNoClamp && sizeof(crychic_taa_upscale_params) == 32 &&
+              sizeof(crychic_taa_upscale_params) == sizeof(cry::TaaUpscaleParams), "taa_upscale_core.hpp mirrors the ABI");
+
+int crychic_taa_upscale_default_params(crychic_taa_upscale_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    *out = crychic_taa_upscale_params{};
+    out->blend = 102u;
+    return 0;
+}
+
+int crychic_taa_upscale(crychic_ctx* ctx, const crychic_pass_constants* cb, const float curViewProj[16], const float prevViewProj[16], float jx, float jy,
+                        const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, uint32_t Wi, uint32_t Hi, const uint16_t* history_in_dev,
+                        uint16_t* history_out_dev, uint8_t* out_rgba8_dev, uint32_t Wo, uint32_t Ho, uint32_t row0, uint32_t rows,
+                        const crychic_taa_upscale_params* params, void* stream)
+{
+    // every argument is checked before the context is looked at: a refusal needs no device
+    crychic_taa_upscale_params p;
+    crychic_taa_upscale_default_params(&p);
+    if (params) p = *params;
+    if (p.blend == 0u || p.blend > 256u) return fail(CRYCHIC_E_INVALID_ARG, "temporal upsampling blend %u outside 1 .. 256", p.blend);
+    if (p.flags & ~(CRYCHIC_TAA_UPSCALE_RESET | CRYCHIC_TAA_UPSCALE_NO_CLAMP)) return fail(CRYCHIC_E_INVALID_ARG, "temporal upsampling flags 0x%x: unknown bits", p.flags);
+    for (uint32_t r : p.reserved)
+        if (r) return fail(CRYCHIC_E_INVALID_ARG, "temporal upsampling reserved words must be 0");
+    const bool reset = (p.flags & CRYCHIC_TAA_UPSCALE_RESET) != 0u;
+    if (!cb || !curViewProj || !prevViewProj || !depth_dev || !in_rgba8_dev || !history_out_dev || !out_rgba8_dev || (!history_in_dev && !reset))
+        return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    const uintptr_t z = reinterpret_cast<uintptr_t>(depth_dev), s = reinterpret_cast<uintptr_t>(in_rgba8_dev), d = reinterpret_cast<uintptr_t>(out_rgba8_dev);
+    const uintptr_t hi = reinterpret_cast<uintptr_t>(history_in_dev), ho = reinterpret_cast<uintptr_t>(history_out_dev);
+    if ((z | s | d) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "temporal upsampling frame planes are not 4-byte aligned");
+    if ((hi | ho) & 7u) return fail(CRYCHIC_E_INVALID_ARG, "temporal upsampling history planes are not 8-byte aligned");
+    if (Wi == 0 || Hi == 0 || Wo == 0 || Ho == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame sizes %ux%u -> %ux%u must be non-zero", Wi, Hi, Wo, Ho);
+    if (Wo < Wi || (uint64_t)Wo > (uint64_t)cry::kTaaUpscaleMaxRatio * Wi || Ho < Hi || (uint64_t)Ho > (uint64_t)cry::kTaaUpscaleMaxRatio * Hi)
+        return fail(CRYCHIC_E_INVALID_ARG, "temporal upsampling %ux%u -> %ux%u: each ratio must lie in 1 .. 4", Wi, Hi, Wo, Ho);
+    if (int rc = check_extent("output", Wo, Ho, false, 0u)) return rc;                // a one-dimensional grid, at most 2^27 workgroups
+    if (Wo > cry::kTaaMaxSide || Ho > cry::kTaaMaxSide) return fail(CRYCHIC_E_UNSUPPORTED, "output %ux%u: temporal upsampling takes at most 2^22 texels a side", Wo, Ho);
+    if (int rc = check_rows(kFrameRows, row0, rows, Ho)) return rc;
+    if (!std::isfinite(jx) || !std::isfinite(jy) || std::fabs(jx) > 0.5f || std::fabs(jy) > 0.5f)
+        return fail(CRYCHIC_E_INVALID_ARG, "temporal upsampling jitter (%g, %g) must be finite and within 0.5 of zero", (double)jx, (double)jy);
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(cb->InvViewProj[k]) || !std::isfinite(curViewProj[k]) || !std::isfinite(prevViewProj[k]))
+            return fail(CRYCHIC_E_INVALID_ARG, "temporal upsampling: entry %d of InvViewProj, curViewProj or prevViewProj is not finite", k);
+    const size_t ibytes = (size_t)Wi * Hi * 4u, obytes = (size_t)Wo * Ho * 4u, hbytes = crychic_taa_history_bytes(Wo, Ho);
+    if (ranges_overlap(s, ibytes, d, obytes) || ranges_overlap(z, ibytes, d, obytes))
+        return fail(CRYCHIC_E_INVALID_ARG, "the temporal upsampling output plane overlaps an input plane");
+    if (history_in_dev && ranges_overlap(hi, hbytes, ho, hbytes)) return fail(CRYCHIC_E_INVALID_ARG, "the temporal upsampling history planes overlap");
+    for (const uintptr_t h : { hi, ho })
+        if (h && (ranges_overlap(h, hbytes, s, ibytes) || ranges_overlap(h, hbytes, d, obytes) || ranges_overlap(h, hbytes, z, ibytes)))
+            return fail(CRYCHIC_E_INVALID_ARG, "a temporal upsampling history plane overlaps a frame plane");
+    if (int rc = bind(ctx)) return rc;
+    cry::TaaUpscaleParams q;
+    std::memcpy(&q, &p, sizeof q);
+    CRY_HIP(cry::launch_taa_upscale(cb->InvViewProj, curViewProj, prevViewProj, jx, jy, depth_dev, in_rgba8_dev, Wi, Hi, reset ? nullptr : history_in_dev,
+                                    history_out_dev, out_rgba8_dev, Wo, Ho, row0, rows, q, (hipStream_t)stream));
     return 0;
 }
 

@@ -142,6 +142,15 @@ hipError_t launch_taa(const float* invViewProj, const float* curViewProj, const 
                       const uint16_t* historyIn, uint16_t* historyOut, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
                       const TaaParams& p, hipStream_t stream);
 
+// taa_upscale.hip: rows [row0, row0 + rows) of the Wo x Ho RGBA8 frame `out` and of the history plane `historyOut` from the Wi x Hi
+// frame `in`, its D24 plane `depth` and the Wo x Ho history plane `historyIn` (NULL only with the reset flag) (taa_upscale_core.hpp);
+// the three matrices are read before the call returns.  One launch on `stream`, none for rows == 0.  The caller has checked the
+// pointers, their alignment and overlap, the sizes and their ratios, the rows, the matrices, the jitter and `p`.
+struct TaaUpscaleParams;
+hipError_t launch_taa_upscale(const float* invViewProj, const float* curViewProj, const float* prevViewProj, float jx, float jy, const uint32_t* depth,
+                              const uint8_t* in, uint32_t Wi, uint32_t Hi, const uint16_t* historyIn, uint16_t* historyOut, uint8_t* out, uint32_t Wo,
+                              uint32_t Ho, uint32_t row0, uint32_t rows, const TaaUpscaleParams& p, hipStream_t stream);
+
 // motion_blur.hip: launch_motion_blur_velocity fills the velocity plane and the tile plane of `workspace` for the whole W x H frame
 // from the D24 plane `depth` (motion_blur_core.hpp); the three matrices are read before the call returns.  launch_motion_blur_gather
 // writes rows [row0, row0 + rows) of `out` from `in` and the workspace: none for rows == 0.  One launch each on `stream`.  The caller

@@ -5,7 +5,7 @@
                                    [--fog [--fog-density X] [--fog-steps N]]
                                    [--dof [--dof-focus X] [--dof-aperture X] [--dof-radius N]]
                                    [--bloom [--bloom-threshold N] [--bloom-intensity N] [--bloom-levels N]]
-                                   [--taa [--taa-frames N]]
+                                   [--taa [--taa-frames N]] [--taa-upscale WxH [--taa-frames N]]
                                    [--motion-blur [--motion-blur-shutter N] [--motion-blur-samples N] [--motion-blur-pan DX]]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
@@ -44,6 +44,9 @@ most 1024) and --bloom-levels (default 6, at most 8) set its parameters.
 --taa: temporal anti-aliasing (Crychic.temporalAA: crychic_taa after the lighting pass and the fog, in front of --dof, --bloom and
 --aa): --taa-frames frames (default 16) of the still scene are rendered, each with the projection shifted by its sub-pixel jitter
 (crychic_taa_jitter), and blended into the history; the resolved frame of the last one is what the later stages read.
+--taa-upscale WxH: temporal upsampling (Crychic.temporalUpscale: crychic_taa_upscale at --taa's place, not together with --taa, --dof or
+--motion-blur): --taa-frames jittered frames (default 16) of the still scene are rendered at --size and accumulated into a history of
+W x H pixels, each side 1 to 4 times --size's; --bloom and --aa then run at W x H, and the PPM has that size.
 --motion-blur: camera-motion blur (Crychic.motionBlur: crychic_motion_blur behind --dof, in front of --bloom and --aa): the frame is
 drawn as if the camera had stood --motion-blur-pan world units (default 0.5) further along +x one frame earlier, and blurred along the
 velocity that gives each pixel through its depth; --motion-blur-shutter (exposure in 1/256 of the frame interval, default 128, at
@@ -95,7 +98,9 @@ def main():
     ap.add_argument("--bloom-intensity", type=int, default=None, metavar="N", help="strength, 256 = 1.0, 0 .. 1024 (default 128; needs --bloom)")
     ap.add_argument("--bloom-levels", type=int, default=None, metavar="N", help="pyramid levels, 1 .. 8 (default 6; needs --bloom)")
     ap.add_argument("--taa", action="store_true", help="temporal anti-aliasing: jittered frames of the still scene blended into a history")
-    ap.add_argument("--taa-frames", type=int, default=None, metavar="N", help="jittered frames to render (default 16; needs --taa)")
+    ap.add_argument("--taa-upscale", default="", metavar="WxH", help="temporal upsampling: jittered frames of --size accumulated into a W x H history; "
+                                                                     "the frame written has that size (not with --taa, --dof or --motion-blur)")
+    ap.add_argument("--taa-frames", type=int, default=None, metavar="N", help="jittered frames to render (default 16; needs --taa or --taa-upscale)")
     ap.add_argument("--motion-blur", action="store_true", help="camera-motion blur, behind the depth of field and in front of the bloom")
     ap.add_argument("--motion-blur-shutter", type=int, default=None, metavar="N", help="exposure in 1/256 of the frame interval, 0 .. 256 (default 128; needs --motion-blur)")
     ap.add_argument("--motion-blur-samples", type=int, default=None, metavar="N", help="samples along the velocity: 2, 4, 8, 16 or 32 (default 8; needs --motion-blur)")
@@ -104,8 +109,10 @@ def main():
     a = ap.parse_args()
     if (a.motion_blur_shutter is not None or a.motion_blur_samples is not None or a.motion_blur_pan is not None) and not a.motion_blur:
         ap.error("--motion-blur-shutter, --motion-blur-samples and --motion-blur-pan need --motion-blur")
-    if a.taa_frames is not None and not (a.taa and a.taa_frames >= 1):
-        ap.error("--taa-frames takes a positive count and needs --taa")
+    if a.taa_frames is not None and not ((a.taa or a.taa_upscale) and a.taa_frames >= 1):
+        ap.error("--taa-frames takes a positive count and needs --taa or --taa-upscale")
+    if a.taa_upscale and (a.taa or a.dof or a.motion_blur):
+        ap.error("--taa-upscale does not go with --taa, --dof or --motion-blur")
     if (a.bloom_threshold is not None or a.bloom_intensity is not None or a.bloom_levels is not None) and not a.bloom:
         ap.error("--bloom-threshold, --bloom-intensity and --bloom-levels need --bloom")
     if (a.dof_focus is not None or a.dof_aperture is not None or a.dof_radius is not None) and not a.dof:
@@ -129,6 +136,9 @@ def main():
     if a.env_ambient and not (a.cube or a.capture_env):
         ap.error("--env-ambient needs --cube or --capture-env")
     W, H = (int(v) for v in a.size.lower().split("x"))
+    WO, HO = (int(v) for v in a.taa_upscale.lower().split("x")) if a.taa_upscale else (W, H)
+    if not (W <= WO <= 4 * W and H <= HO <= 4 * H):
+        ap.error("--taa-upscale takes a size whose sides are 1 to 4 times --size's")
     import torch
     from . import Context, Crychic, LIGHT_SKY, SceneGeometry, check, geometry as g, lib, scene
     from ._lib import BloomParams, DofParams, FogParams, MotionBlurParams, PassConstants, SsrParams
@@ -209,10 +219,13 @@ def main():
         before = scene.default_camera(W, H)
         before.pos[0] += 0.5 if a.motion_blur_pan is None else a.motion_blur_pan
         prev_view_proj = scene.Constants(W, H, a.shadow_dim, cam=before).pass_cb.ViewProj
-    if a.taa:
+    if a.taa or a.taa_upscale:
         # the still scene under the jitter sequence: the camera planes are rasterised again with each frame's shifted projection, the
         # pass gets the unjittered ViewProj of the same camera for this frame and the previous one
-        app.temporalAA = True
+        if a.taa:
+            app.temporalAA = True
+        else:
+            app.temporalUpscale = (WO, HO)
         jx, jy = C.c_float(), C.c_float()
         frames = a.taa_frames or 16
         for k in range(frames):
@@ -222,7 +235,7 @@ def main():
             camera_passes()
             if prev_view_proj is not None and k == frames - 1:
                 app.set_frame_view_proj(prev_view_proj)
-            app.set_frame_view_proj(consts.pass_cb.ViewProj)
+            app.set_frame_view_proj(consts.pass_cb.ViewProj, jitter=(jx.value, jy.value))
             app.Draw()
     else:
         if prev_view_proj is not None:
@@ -231,10 +244,10 @@ def main():
         app.Draw()
     torch.cuda.synchronize()
     img = np.ascontiguousarray(app.final_frame().cpu().numpy())
-    check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, W, H))
-    chain = (("ssr", "screen-space reflections"), ("fog", "fog"), ("temporalAA", "temporal anti-aliasing"), ("depthOfField", "depth of field"), ("motionBlur", "motion blur"),
+    check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, WO, HO))
+    chain = (("ssr", "screen-space reflections"), ("fog", "fog"), ("temporalAA", "temporal anti-aliasing"), ("temporalUpscale", "temporal upsampling"), ("depthOfField", "depth of field"), ("motionBlur", "motion blur"),
              ("bloom", "bloom"), ("antiAliasing", "anti-aliased"))                   # Draw()'s order
-    print("wrote %s (%dx%d%s) on %s" % (a.out, W, H, "".join(", " + text for switch, text in chain if getattr(app, switch)), ctx.device_name))
+    print("wrote %s (%dx%d%s) on %s" % (a.out, WO, HO, "".join(", " + text for switch, text in chain if getattr(app, switch)), ctx.device_name))
 
 
 if __name__ == "__main__":

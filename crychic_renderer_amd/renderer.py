@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (AAParams, CrychicError, FogParams, SsrParams, DofParams, BloomParams, TaaParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, FogParams, SsrParams, DofParams, BloomParams, TaaParams, TaaUpscaleParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -238,6 +238,11 @@ class Crychic:
         self.mTaaHistory = None      # [history read by the next call, history it writes]: (H, W, 4) int16 planes of 8.8 fixed point, swapped after each call
         self._taaReset = True        # the next Draw() with temporalAA set is a RESET frame: the first, or the first after the switch was turned on
         self._taaViewProj = [None, None]     # set_frame_view_proj: the unjittered ViewProj of this frame and of the previous one
+        self._frameJitter = (0.0, 0.0)       # set_frame_view_proj: the jitter the frame's constants were built with
+        self._temporalUpscale = None  # temporalUpscale, extension: None | (Wo, Ho) | (Wo, Ho, TaaUpscaleParams) -- Draw() of a whole frame runs crychic_taa_upscale into mBackBufferUpscaled
+        self.mBackBufferUpscaled = None      # the resolved (Ho, Wo, 4) frame of the display size, allocated by the first temporal_upscale() that needs it
+        self.mTaaUpscaleHistory = None       # as mTaaHistory, of the display size
+        self._taaUpscaleReset = True         # as _taaReset, for temporalUpscale
         self._motionBlur = None      # motionBlur, extension: None | True | MotionBlurParams -- Draw() of a whole frame runs crychic_motion_blur into mBackBufferMB
         self.mBackBufferMB = None    # the frame behind the motion blur, allocated by the first motion_blur() that needs it
         self.mMotionBlurWorkspace = None     # the velocity and tile planes: crychic_motion_blur_workspace_bytes of the frame, with the first motion_blur()
@@ -251,8 +256,11 @@ class Crychic:
         def put(self, value):
             if name == "_temporalAA" and value and not self._temporalAA:
                 self._taaReset = True            # turned on: whatever the history planes hold is stale
+            if name == "_temporalUpscale" and value and not self._temporalUpscale:
+                self._taaUpscaleReset = True
             setattr(self, name, value)
-            self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA or self._motionBlur or self._ssr)
+            self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA or self._motionBlur or self._ssr
+                              or self._temporalUpscale)
         return property(get, put)
 
     antiAliasing = _post_switch("_antiAliasing")
@@ -262,6 +270,7 @@ class Crychic:
     bloom = _post_switch("_bloom")
     temporalAA = _post_switch("_temporalAA")
     motionBlur = _post_switch("_motionBlur")
+    temporalUpscale = _post_switch("_temporalUpscale")
     del _post_switch
 
     def set_gbuffer_formats(self, formats):
@@ -328,7 +337,11 @@ class Crychic:
         each but the fog from the buffer of the nearest set stage in front of it that writes one of its own (mBackBuffer if there is
         none) into its own mBackBuffer*; final_frame() is the last one.  The temporal pass and the motion blur take the matrices of
         set_frame_view_proj (never called: a still camera); the first frame after temporalAA was turned on is a RESET frame.  A strip
-        or a shared draw then raises CrychicError: these passes are not sharded."""
+        or a shared draw then raises CrychicError: these passes are not sharded.
+        temporalUpscale = (Wo, Ho) or (Wo, Ho, TaaUpscaleParams) puts crychic_taa_upscale at the temporal pass's place: the frame of the
+        client size, rendered with the jitter handed to set_frame_view_proj, is accumulated into a history of Wo x Ho texels, and the
+        bloom and the anti-aliasing behind it run at that size.  Together with temporalAA, depthOfField or motionBlur it raises
+        CrychicError before anything is issued (the last two read a depth plane of the frame's size)."""
         if self._post:
             return self._draw_post_chain(row0, rows, shared)
         return self._draw_lighting(row0, rows, shared)
@@ -381,9 +394,17 @@ class Crychic:
     def _draw_post_chain(self, row0, rows, shared):
         """Draw() with a switch set: the lighting frame, then one walk along the chain with the frame each stage reads."""
         if shared is not None or row0 != 0 or (rows is not None and rows != self.mClientHeight):
-            what = next(s for s in ("bloom", "motionBlur", "depthOfField", "temporalAA", "fog", "antiAliasing", "ssr") if getattr(self, s))
+            what = next(s for s in ("bloom", "motionBlur", "depthOfField", "temporalAA", "fog", "antiAliasing", "ssr", "temporalUpscale") if getattr(self, s))
             raise CrychicError(-1, "%s is set: Draw() takes the whole frame on one GPU (the pass is not sharded and does not run behind the "
                                "exchange)" % what)
+        if self._temporalUpscale:
+            for other in ("temporalAA", "depthOfField", "motionBlur"):
+                if getattr(self, other):
+                    raise CrychicError(-1, "temporalUpscale and %s are both set: %s" % (other, "one temporal pass resolves a frame" if other == "temporalAA"
+                                                                                        else "the pass reads a depth plane of the frame's size, and the frame behind the upsampling has the display's"))
+            up = tuple(self._temporalUpscale)
+            if len(up) not in (2, 3) or (len(up) == 3 and not isinstance(up[2], TaaUpscaleParams)):
+                raise CrychicError(-1, "temporalUpscale takes (Wo, Ho) or (Wo, Ho, TaaUpscaleParams)")
         self._draw_lighting(0, None, None)
 
         def params(switch, kind):               # a switch holds True or the pass's parameters
@@ -401,6 +422,9 @@ class Crychic:
         if self._temporalAA:
             frame = self.temporal_aa(cur, prev, src=frame, reset=self._taaReset, params=params(self._temporalAA, TaaParams))
             self._taaReset = False
+        if self._temporalUpscale:
+            frame = self.temporal_upscale(cur, prev, self._frameJitter, up[:2], src=frame, reset=self._taaUpscaleReset, params=up[2] if len(up) == 3 else None)
+            self._taaUpscaleReset = False
         if self._depthOfField:
             frame = self.depth_of_field(src=frame, params=params(self._depthOfField, DofParams))
         if self._motionBlur:
@@ -413,7 +437,7 @@ class Crychic:
     def final_frame(self):
         """The tensor a Draw() with the switches as they are leaves the finished frame in: the last set stage's buffer."""
         for switch, name in ((self._antiAliasing, "mBackBufferAA"), (self._bloom, "mBackBufferBloom"), (self._motionBlur, "mBackBufferMB"),
-                             (self._depthOfField, "mBackBufferDoF"), (self._temporalAA, "mBackBufferTAA")):
+                             (self._depthOfField, "mBackBufferDoF"), (self._temporalAA, "mBackBufferTAA"), (self._temporalUpscale, "mBackBufferUpscaled")):
             if switch:
                 return getattr(self, name)
         return self.mBackBufferSSR if self._ssr else self.mBackBuffer
@@ -458,13 +482,48 @@ class Crychic:
                                                  need, stream))
         return out
 
-    def set_frame_view_proj(self, view_proj):
+    def set_frame_view_proj(self, view_proj, jitter=(0.0, 0.0)):
         """The UNJITTERED view-projection of the frame about to be drawn (16 floats, stored transposed like the pass constants'
-        ViewProj): what was current becomes the previous frame's.  Draw() with temporalAA set hands both to crychic_taa."""
+        ViewProj): what was current becomes the previous frame's.  Draw() with temporalAA set hands both to crychic_taa.  jitter: the
+        (jx, jy) the frame's constants were built with, which Draw() with temporalUpscale set hands to crychic_taa_upscale."""
         m = tuple(float(v) for v in view_proj)
-        if len(m) != 16:
-            raise CrychicError(-1, "set_frame_view_proj takes 16 floats")
+        j = tuple(float(v) for v in jitter)
+        if len(m) != 16 or len(j) != 2:
+            raise CrychicError(-1, "set_frame_view_proj takes 16 floats and a jitter of 2")
         self._taaViewProj = [m, self._taaViewProj[0]]
+        self._frameJitter = j
+
+    def temporal_upscale(self, cur_view_proj, prev_view_proj, jitter, display_size, src=None, out=None, reset=False, row0=0, rows=None, params=None):
+        """crychic_taa_upscale on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferUpscaled, allocated on
+        first use), an (Ho, Wo, 4) uint8 tensor of display_size = (Wo, Ho), from `src` (default: mBackBuffer), an (H, W, 4) uint8 tensor
+        of the frame's size, with this frame's depth plane and (jittered) pass constants, the two UNJITTERED view-projections (16
+        floats each, stored transposed) and the frame's jitter (jx, jy).  The two history planes mTaaUpscaleHistory, of the display
+        size, are this object's and behave as mTaaHistory does in temporal_aa.  params: a TaaUpscaleParams, None = the defaults.
+        Returns `out`."""
+        src = self.mBackBuffer if src is None else src
+        Wo, Ho = int(display_size[0]), int(display_size[1])
+        if out is None:
+            out = self.mBackBufferUpscaled
+            if out is None or out.shape != (Ho, Wo, 4) or out.device != src.device:
+                out = self.mBackBufferUpscaled = torch.zeros((Ho, Wo, 4), dtype=torch.uint8, device=src.device)
+        H, W = self.mClientHeight, self.mClientWidth
+        if src.dtype != torch.uint8 or out.dtype != torch.uint8 or tuple(src.shape) != (H, W, 4) or tuple(out.shape) != (Ho, Wo, 4) \
+                or not src.is_contiguous() or not out.is_contiguous():
+            raise CrychicError(-1, "temporal_upscale takes a contiguous (H, W, 4) uint8 tensor of the frame's size and one of the display's")
+        hist = self.mTaaUpscaleHistory
+        if hist is None or tuple(hist[0].shape) != (Ho, Wo, 4) or hist[0].device != src.device:
+            self.mTaaUpscaleHistory = [torch.zeros((Ho, Wo, 4), dtype=torch.int16, device=src.device) for _ in range(2)]
+            reset = True
+        p = TaaUpscaleParams.default() if params is None else TaaUpscaleParams.from_buffer_copy(params)
+        if reset:
+            p.flags |= _lib.TAA_RESET
+        cur, prev = (C.c_float * 16)(*cur_view_proj), (C.c_float * 16)(*prev_view_proj)
+        hin, hout = self.mTaaUpscaleHistory
+        check(lib.crychic_taa_upscale(self.ctx.handle, C.byref(self.mMainPassCB), cur, prev, float(jitter[0]), float(jitter[1]),
+                                      self.mDepthStencilBuffer.data_ptr(), _ptr(src), W, H, None if p.flags & _lib.TAA_RESET else _ptr(hin), _ptr(hout),
+                                      _ptr(out), Wo, Ho, int(row0), int(Ho - row0 if rows is None else rows), C.byref(p), _stream(self.ctx.device)))
+        self.mTaaUpscaleHistory = [hout, hin]
+        return out
 
     def temporal_aa(self, cur_view_proj, prev_view_proj, src=None, out=None, reset=False, row0=0, rows=None, params=None):
         """crychic_taa on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferTAA, allocated on first use) from
@@ -490,10 +549,10 @@ class Crychic:
 
     def apply_bloom(self, src=None, out=None, params=None):
         """crychic_bloom on the context's stream: the whole frame `out` (default: mBackBufferBloom, allocated on first use) from `src`
-        (default: mBackBuffer), both (H, W, 4) uint8 tensors of the frame's size; `out` may be `src` itself (in place) and must not
-        overlap it otherwise.  params: a BloomParams, None = the defaults.  The pyramid goes through mBloomWorkspace, allocated on
+        (default: mBackBuffer), both (H, W, 4) uint8 tensors of one shape (the frame's, or the display's behind temporalUpscale); `out`
+        may be `src` itself (in place) and must not overlap it otherwise.  params: a BloomParams, None = the defaults.  The pyramid goes through mBloomWorkspace, allocated on
         first use for the frame's size at BLOOM_MAX_LEVELS levels; afterwards its level k holds U_k.  Returns `out`."""
-        src, out, H, W = self._pass_frames("apply_bloom", "mBackBufferBloom", src, out)
+        src, out, H, W = self._pass_frames("apply_bloom", "mBackBufferBloom", src, out, any_shape=True)
         need = int(lib.crychic_bloom_workspace_bytes(W, H, _lib.BLOOM_MAX_LEVELS))
         if self.mBloomWorkspace is None or self.mBloomWorkspace.numel() != need or self.mBloomWorkspace.device != src.device:
             self.mBloomWorkspace = torch.zeros((need,), dtype=torch.uint8, device=src.device)

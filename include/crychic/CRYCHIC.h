@@ -164,12 +164,13 @@ public:
         mDepthStencilBuffer = FramePlane();
         CrychicHipThrowIfFailed(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(mDepthStencilBuffer->Data()), 0x00FFFFFF, n));
         mBackBuffer = FramePlane();
-        if (mAntiAliasing) mBackBufferAA = FramePlane();
+        if (mAntiAliasing) mBackBufferAA = FinalPlane();
         if (mDepthOfField) mBackBufferDoF = FramePlane();
         if (mScreenSpaceReflections) mBackBufferSSR = FramePlane();
         if (mBloom) AllocateBloom();
         if (mTemporalAA) AllocateTemporalAA();                                                      // new history planes: the next frame is a reset frame
         if (mMotionBlur) AllocateMotionBlur();                                                      // the next frame counts as the first: no previous camera
+        if (mTemporalUpscale) AllocateTemporalUpscale();                                            // the display size stays; the next frame is a reset frame
         mCamera.SetLens(0.25f * 3.1415926535f, AspectRatio(), 1.0f, 100.0f);                       // :114
         if (mSsao) { mSsao->OnResize(mClientWidth, mClientHeight); mSsao->RebuildDescriptors(mDepthStencilBuffer.get()); }
         if (mDeferred) { mDeferred->OnResize(mClientWidth, mClientHeight); mDeferred->BuildDescriptors(); }
@@ -203,7 +204,7 @@ public:
         UpdateCascadeShadowTransform(gt);
         UpdateSpotShadowTransforms();
         UpdatePointShadowTransforms();
-        if (mTemporalAA) CrychicThrowIfFailed(crychic_taa_jitter(mTaaFrameIndex++, &mTaaJitter[0], &mTaaJitter[1]));   // this frame's sub-pixel offset
+        if (mTemporalAA || mTemporalUpscale) CrychicThrowIfFailed(crychic_taa_jitter(mTaaFrameIndex++, &mTaaJitter[0], &mTaaJitter[1]));   // this frame's sub-pixel offset
         UpdateMainPassCB(gt);
         UpdateShadowPassCB(gt);
         UpdateSsaoCB(gt);
@@ -211,12 +212,18 @@ public:
 
     void Draw(const GameTimer&)  // CRYCHIC.cpp:172-306, deferred branch
     {
-        if ((!mWholeFrame || mComm) && (mAntiAliasing || mFog || mDepthOfField || mBloom || mTemporalAA || mMotionBlur || mScreenSpaceReflections)) {
+        if ((!mWholeFrame || mComm) && (mAntiAliasing || mFog || mDepthOfField || mBloom || mTemporalAA || mMotionBlur || mScreenSpaceReflections || mTemporalUpscale)) {
             const char* pass = mAntiAliasing ? "anti-aliasing" : mFog ? "fog" : mDepthOfField ? "depth of field" : mBloom ? "bloom"
-                             : mTemporalAA ? "temporal anti-aliasing" : mMotionBlur ? "motion blur" : "screen-space reflections";
+                             : mTemporalAA ? "temporal anti-aliasing" : mMotionBlur ? "motion blur" : mScreenSpaceReflections ? "screen-space reflections"
+                             : "temporal upsampling";
             throw CrychicException(CRYCHIC_E_INVALID_ARG, std::string("CRYCHIC::Draw (") + pass + " takes the whole frame on one GPU: no SetStrip / JoinNode)",
                                    __FILE__, __LINE__);
         }
+        if (mTemporalUpscale && (mTemporalAA || mDepthOfField || mMotionBlur))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, std::string("CRYCHIC::Draw (temporal upsampling together with ") +
+                                   (mTemporalAA ? "temporal anti-aliasing: one temporal pass resolves a frame)"
+                                    : mDepthOfField ? "depth of field: the pass reads a depth plane of the frame's size)"
+                                    : "motion blur: the pass reads a depth plane of the frame's size)"), __FILE__, __LINE__);
         if (mRunProducerPasses) {
             DrawSceneToShadowMap();                                                                 // :208
             if (mFuseCameraPasses) DrawNormalsDepthAndGBuffer();                                    // :214 + :236 on one rasterisation
@@ -307,6 +314,21 @@ public:
             mTaaReset = false;
             frame = bytes(mBackBufferTAA);
         }
+        uint32_t fw = mClientWidth, fh = mClientHeight;         // the size of `frame`: the display's behind the temporal upsampling
+        if (mTemporalUpscale) {                 // at the temporal pass's place; what follows runs at the display size
+            crychic_taa_upscale_params tp = mTuParams;
+            if (mTuReset) tp.flags |= CRYCHIC_TAA_UPSCALE_RESET;
+            ID3D12Resource* hin = mTuHistory[mTuHistoryIndex].get();
+            ID3D12Resource* hout = mTuHistory[mTuHistoryIndex ^ 1].get();
+            CrychicThrowIfFailed(crychic_taa_upscale(md3dDevice->Ctx(), passCB, mTaaViewProj[0], mTaaViewProj[1], mTaaJitter[0], mTaaJitter[1], f.depth_dev,
+                                                     frame, mClientWidth, mClientHeight, mTuReset ? nullptr : static_cast<const uint16_t*>(hin->Data()),
+                                                     static_cast<uint16_t*>(hout->Data()), bytes(mBackBufferUpscaled), mTuWidth, mTuHeight, 0, mTuHeight, &tp,
+                                                     mCommandList->Stream()));
+            mTuHistoryIndex ^= 1;
+            mTuReset = false;
+            frame = bytes(mBackBufferUpscaled);
+            fw = mTuWidth; fh = mTuHeight;
+        }
         if (mDepthOfField) {
             CrychicThrowIfFailed(crychic_dof(md3dDevice->Ctx(), passCB, f.depth_dev, frame, bytes(mBackBufferDoF), mClientWidth, mClientHeight, 0,
                                              mClientHeight, &mDofParams, mCommandList->Stream()));
@@ -319,12 +341,12 @@ public:
             frame = bytes(mBackBufferMB);
         }
         if (mBloom) {
-            CrychicThrowIfFailed(crychic_bloom(md3dDevice->Ctx(), frame, bytes(mBackBufferBloom), mClientWidth, mClientHeight, &mBloomParams,
+            CrychicThrowIfFailed(crychic_bloom(md3dDevice->Ctx(), frame, bytes(mBackBufferBloom), fw, fh, &mBloomParams,
                                                mBloomWorkspace->Data(), mBloomWorkspace->Bytes(), mCommandList->Stream()));
             frame = bytes(mBackBufferBloom);
         }
         if (mAntiAliasing)
-            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), frame, bytes(mBackBufferAA), mClientWidth, mClientHeight, 0, mClientHeight,
+            CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), frame, bytes(mBackBufferAA), fw, fh, 0, fh,
                                                    &mAAParams, mCommandList->Stream()));
         // :300-305: advance the fence and signal it behind this frame's commands
         mCurrFrameResource->Fence = ++mCurrentFence;
@@ -332,7 +354,7 @@ public:
     }
 
     // ---- the passes behind the lighting pass (extensions) -----------------------------------------------------------------------------
-    // Seven switches, all off by default (then nothing changes).  With any of them on, Draw takes a whole frame on one GPU -- SetStrip /
+    // Eight switches (the temporal upsampling, below, stands at the temporal anti-aliasing's place), all off by default (then nothing changes).  With any of them on, Draw takes a whole frame on one GPU -- SetStrip /
     // JoinNode make it throw, the passes are not sharded -- and issues those that are on behind the lighting pass in the order
     //     lighting -> screen-space reflections -> fog (in place) -> temporal anti-aliasing -> depth of field -> motion blur -> bloom -> anti-aliasing.
     // The fog works in place on the frame it is handed: the reflections' buffer if they are on, the back buffer if not.  Every other
@@ -357,7 +379,7 @@ public:
         mCommandList->Flush();                                  // a frame in flight may still write the buffer released below
         mAntiAliasing = on;
         mAAParams = q;
-        if (on) mBackBufferAA = FramePlane();
+        if (on) mBackBufferAA = FinalPlane();
         else mBackBufferAA.reset();
     }
     bool AntiAliasing() const { return mAntiAliasing; }
@@ -463,6 +485,43 @@ public:
     ID3D12Resource* TemporalAAHistory() { return mTaaHistory[mTaaHistoryIndex].get(); }     // the history the last Draw wrote
     const float* TemporalAAViewProj(int previous) const { return mTaaViewProj[previous ? 1 : 0]; }   // unjittered, of the last Update
     const float* TemporalAAJitter() const { return mTaaJitter; }                            // the last Update's offset in pixels
+
+    // ---- temporal upsampling ----------------------------------------------------------------------------------------------------------
+    // Jittered frames of the client size accumulated into a history of width x height texels (include/crychic_hip.h
+    // crychic_taa_upscale), at the temporal anti-aliasing's place in the chain: Update jitters the constants as it does for that pass,
+    // Draw issues the pass through two history planes of the display size, and the bloom and the anti-aliasing behind it, their buffers
+    // and what Present writes have that size (FinalWidth x FinalHeight).  The first frame after it was turned on, after a change of the
+    // display size and after OnResize is a reset frame; the flag is this pass's own.  Draw throws while the temporal anti-aliasing,
+    // the depth of field or the motion blur is on as well: the last two read a depth plane of the frame's size.
+    void SetTemporalUpscale(uint32_t width, uint32_t height, const crychic_taa_upscale_params* p = nullptr)    // 0 x 0: off
+    {
+        crychic_taa_upscale_params q;
+        CrychicThrowIfFailed(crychic_taa_upscale_default_params(&q));
+        if (p) q = *p;
+        const bool on = width != 0u || height != 0u;
+        if (q.blend == 0u || q.blend > 256u || (q.flags & ~(CRYCHIC_TAA_UPSCALE_RESET | CRYCHIC_TAA_UPSCALE_NO_CLAMP)) ||
+            (q.reserved[0] | q.reserved[1] | q.reserved[2] | q.reserved[3] | q.reserved[4] | q.reserved[5]) ||
+            (on && (width < (uint32_t)mClientWidth || width > 4u * (uint32_t)mClientWidth || height < (uint32_t)mClientHeight || height > 4u * (uint32_t)mClientHeight)))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetTemporalUpscale (each side 1 .. 4 times the client's, blend 1 .. 256, flags RESET | NO_CLAMP, reserved 0)",
+                                   __FILE__, __LINE__);
+        mCommandList->Flush();                                  // a frame in flight may still write the buffers released below
+        const bool was = mTemporalUpscale, resized = width != mTuWidth || height != mTuHeight;
+        mTemporalUpscale = on;
+        mTuParams = q;
+        mTuWidth = width; mTuHeight = height;
+        if (on && (!was || resized)) AllocateTemporalUpscale();
+        if (on && !was) mTaaFrameIndex = 0;
+        if (!on) { mBackBufferUpscaled.reset(); mTuHistory[0].reset(); mTuHistory[1].reset(); }
+        if (was != on || resized) {                             // the stages behind it change their size with it
+            if (mAntiAliasing) mBackBufferAA = FinalPlane();
+            if (mBloom) AllocateBloom();
+        }
+    }
+    bool TemporalUpscale() const { return mTemporalUpscale; }
+    ID3D12Resource* TemporalUpscaleBackBuffer() { return mBackBufferUpscaled.get(); }
+    ID3D12Resource* TemporalUpscaleHistory() { return mTuHistory[mTuHistoryIndex].get(); }  // the history the last Draw wrote
+    uint32_t FinalWidth() const { return mTemporalUpscale ? mTuWidth : (uint32_t)mClientWidth; }      // of FinalFrame
+    uint32_t FinalHeight() const { return mTemporalUpscale ? mTuHeight : (uint32_t)mClientHeight; }
 
     // ---- motion blur ------------------------------------------------------------------------------------------------------------------
     // Camera motion turned into blur (include/crychic_hip.h crychic_motion_blur).  On: Update keeps the unjittered ViewProj of this
@@ -742,10 +801,10 @@ public:
     // that is on, the back buffer if none is -- and write it as PPM.
     void Present(const std::string& path)
     {
-        std::vector<uint8_t> host((size_t)mClientWidth * mClientHeight * 4);
+        std::vector<uint8_t> host((size_t)FinalWidth() * FinalHeight() * 4);
         FinalFrame()->Download(host.data(), host.size(), mCommandList->Stream());
         mCommandList->Flush();
-        CrychicThrowIfFailed(crychic_save_ppm(path.c_str(), host.data(), mClientWidth, mClientHeight));
+        CrychicThrowIfFailed(crychic_save_ppm(path.c_str(), host.data(), FinalWidth(), FinalHeight()));
     }
 
     // ---- planes the producer passes would fill (row f1) + the result ----
@@ -1189,10 +1248,10 @@ private:
             std::memcpy(mMbViewProj[0], &mMainPassCB.ViewProj, 64);
             mMbFirst = false;
         }
-        if (mTemporalAA) {
+        if (mTemporalAA || mTemporalUpscale) {
             // the unjittered ViewProj built above becomes this frame's, what was this frame's the previous one's (its own on a reset
             // frame); then the constants again with the projection shifted by the frame's jitter
-            std::memcpy(mTaaViewProj[1], mTaaReset ? reinterpret_cast<const float*>(&mMainPassCB.ViewProj) : mTaaViewProj[0], 64);
+            std::memcpy(mTaaViewProj[1], (mTemporalAA ? mTaaReset : mTuReset) ? reinterpret_cast<const float*>(&mMainPassCB.ViewProj) : mTaaViewProj[0], 64);
             std::memcpy(mTaaViewProj[0], &mMainPassCB.ViewProj, 64);
             CrychicThrowIfFailed(crychic_update_main_pass_cb_jittered(&mCamera.Raw(), mClientWidth, mClientHeight, st, dirs, mTaaJitter[0], mTaaJitter[1],
                                                                       reinterpret_cast<crychic_pass_constants*>(&mMainPassCB)));
@@ -1211,7 +1270,7 @@ private:
         mSsao->GetOffsetVectors(off);                                                               // :920
         float o[14][4];
         for (int i = 0; i < 14; ++i) { o[i][0] = off[i].x; o[i][1] = off[i].y; o[i][2] = off[i].z; o[i][3] = off[i].w; }
-        if (mTemporalAA)
+        if (mTemporalAA || mTemporalUpscale)
             CrychicThrowIfFailed(crychic_update_ssao_cb_jittered(&mCamera.Raw(), mClientWidth, mClientHeight, o, mTaaJitter[0], mTaaJitter[1],
                                                                  reinterpret_cast<crychic_ssao_constants*>(&ssaoCB)));
         else
@@ -1256,8 +1315,8 @@ private:
     std::unique_ptr<ID3D12Resource> mBloomWorkspace;   // its pyramid: the frame's size at the most levels, so any parameters fit
     void AllocateBloom()
     {
-        mBackBufferBloom = FramePlane();
-        mBloomWorkspace = std::make_unique<ID3D12Resource>(crychic_bloom_workspace_bytes(mClientWidth, mClientHeight, CRYCHIC_BLOOM_MAX_LEVELS),
+        mBackBufferBloom = FinalPlane();
+        mBloomWorkspace = std::make_unique<ID3D12Resource>(crychic_bloom_workspace_bytes(FinalWidth(), FinalHeight(), CRYCHIC_BLOOM_MAX_LEVELS),
                                                            ID3D12Resource::DEFAULT_HEAP);
     }
     bool mTemporalAA = false;                 // SetTemporalAA
@@ -1288,6 +1347,20 @@ private:
         if (on && !was) { AllocateTemporalAA(); mTaaFrameIndex = 0; }
         if (!on) { mBackBufferTAA.reset(); mTaaHistory[0].reset(); mTaaHistory[1].reset(); }
     }
+    bool mTemporalUpscale = false;            // SetTemporalUpscale
+    crychic_taa_upscale_params mTuParams = {};
+    uint32_t mTuWidth = 0, mTuHeight = 0;     // the display size
+    std::unique_ptr<ID3D12Resource> mBackBufferUpscaled;   // the resolved frame of the display size, while mTemporalUpscale
+    std::unique_ptr<ID3D12Resource> mTuHistory[2];     // as mTaaHistory, of the display size
+    int mTuHistoryIndex = 0;
+    bool mTuReset = true;                     // the next frame does not read the history: apart from mTaaReset
+    void AllocateTemporalUpscale()
+    {
+        mBackBufferUpscaled = FinalPlane();
+        for (auto& h : mTuHistory) h = std::make_unique<ID3D12Resource>(crychic_taa_history_bytes(mTuWidth, mTuHeight), ID3D12Resource::DEFAULT_HEAP);
+        mTuHistoryIndex = 0;
+        mTuReset = true;
+    }
     bool mMotionBlur = false;                 // SetMotionBlur
     crychic_motion_blur_params mMbParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferMB;     // the frame behind the motion blur, while mMotionBlur
@@ -1307,10 +1380,14 @@ private:
     {
         return std::make_unique<ID3D12Resource>((size_t)mClientWidth * mClientHeight * 4, ID3D12Resource::DEFAULT_HEAP);
     }
+    std::unique_ptr<ID3D12Resource> FinalPlane() const      // an RGBA8 plane of the finished frame's size: the display's behind the temporal upsampling
+    {
+        return std::make_unique<ID3D12Resource>((size_t)FinalWidth() * FinalHeight() * 4, ID3D12Resource::DEFAULT_HEAP);
+    }
     ID3D12Resource* FinalFrame() const           // where Draw leaves the finished frame: the buffer of the last stage that is on
     {
         return (mAntiAliasing ? mBackBufferAA : mBloom ? mBackBufferBloom : mMotionBlur ? mBackBufferMB : mDepthOfField ? mBackBufferDoF
-                : mTemporalAA ? mBackBufferTAA : mScreenSpaceReflections ? mBackBufferSSR : mBackBuffer).get();
+                : mTemporalAA ? mBackBufferTAA : mTemporalUpscale ? mBackBufferUpscaled : mScreenSpaceReflections ? mBackBufferSSR : mBackBuffer).get();
     }
     std::unique_ptr<ID3D12Resource> mDepthStencilBuffer, mBackBuffer, mCubeMap;
     std::unique_ptr<ID3D12Resource> mPointLights, mSpotLights;   // SetLocalLights

@@ -1314,6 +1314,73 @@ int crychic_taa(crychic_ctx* ctx, const crychic_pass_constants* cb, const float 
                 uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
                 const crychic_taa_params* params /* NULL = defaults */, void* stream);
 
+/* ---- temporal upsampling: jittered frames of the render size into a history of the display size (extension)
+ * crychic_taa_upscale stands where crychic_taa stands (never both): the finished RGBA8 frame of Wi x Hi pixels, rendered with the
+ * frame's jitter, is accumulated into a history of Wo x Ho texels and resolved to an RGBA8 frame of Wo x Ho pixels,
+ * Wi <= Wo <= 4 Wi and Hi <= Ho <= 4 Hi, the two ratios independent.  Each output pixel weighs the current frame by how close one of
+ * its samples fell to the pixel's centre, so that over the jitter sequence every output pixel is fed by samples near it.  A build
+ * definition: nothing of it is the reference's.  The device, a host build and the checker (tests/taa_upscale_ref) agree bit for bit on
+ * both outputs.
+ *
+ * Float operations, matrices, primitives and the history format are those of crychic_taa above; behind the history position
+ * everything is 32-bit unsigned integer arithmetic unless said otherwise.  cb is the frame's own (jittered) constants at Wi x Hi, of
+ * which InvViewProj is read; (jx, jy) is the jitter those constants were built with.
+ * Host-side constants, once per call:  sx = 2.0f / (float)Wi;  sy = 2.0f / (float)Hi;  hw = 0.5f * (float)Wi;  hh = 0.5f * (float)Hi;
+ * rx = (float)Wo / (float)Wi;  ry = (float)Ho / (float)Hi  (one IEEE division each);  xmax = (float)((Wo - 1) 256);
+ * ymax = (float)((Ho - 1) 256);  Jx = (int)floorf(fmaf(jx, 256.0f, 0.5f));  Jy likewise from jy  (-128 .. 128).
+ * Per output pixel (ox, oy):
+ *   1  The pixel's centre in the input frame, in 1/256 texel, texel t's centre at 256 t:
+ *      U = ((2 ox + 1) Wi 256) / (2 Wo) + Jx - 128, the division a floor division of non-negative 64-bit integers; V likewise from oy,
+ *      Hi, Ho and Jy.  (The jittered frame shows at x + jx what the unjittered frame shows at x: the centre (ox + 0.5) Wi / Wo of the
+ *      output pixel is found at that position plus jx, and a position p is p - 0.5 texel centres.)  ui = U >> 8 (arithmetic, -1 at
+ *      the least), fu = U & 255, vi, fv likewise;  tx = clamp((U + 128) >> 8, 0, Wi - 1), ty = clamp((V + 128) >> 8, 0, Hi - 1): the
+ *      NEAREST texel.
+ *   2  c256[k], k = R, G, B: with t00 = in at (clamp(ui, 0, Wi - 1), clamp(vi, 0, Hi - 1)), t10 at (clamp(ui + 1), clamp(vi)), t01 at
+ *      (clamp(ui), clamp(vi + 1)), t11 at (clamp(ui + 1), clamp(vi + 1)), per channel:  top = t00 (256 - fu) + t10 fu;
+ *      bot = t01 (256 - fu) + t11 fu;  c256 = (top (256 - fv) + bot fv + 128) >> 8  (at most 65280).  cA = byte A of the nearest texel.
+ *   3  du = min(fu, 256 - fu);  dX = min(256, (du Wo) / Wi);  dv, dY likewise from fv, Ho, Hi;  conf = ((256 - dX) (256 - dY)) >> 8;
+ *      conf2 = (conf conf) >> 8;  wgt = min(256, (blend conf2) >> 8): the current frame's weight in this pixel.
+ *   4  lo[k] = 256 min, hi[k] = 256 max of channel k = R, G, B over the 3 x 3 texels of `in` at (clamp(tx + i, 0, Wi - 1),
+ *      clamp(ty + j, 0, Hi - 1)), i, j = -1 .. 1.
+ *   5  vx, vy as steps 2 and 3 of crychic_taa give them with px = tx, py = ty, depth[ty Wi + tx] and the constants above, b[3]
+ *      included: a velocity in input pixels.  fxp = ((float)ox - vx rx) 256.0f;  fyp = ((float)oy - vy ry) 256.0f  (one product, one
+ *      difference, one product each).  The pixel HAS HISTORY under step 4's test of crychic_taa with these fxp, fyp, xmax and ymax and
+ *      CRYCHIC_TAA_UPSCALE_RESET, and hv[k] is that step's fetch from the Wo x Ho plane history_in;  hc[k] = min(max(hv[k], lo[k]),
+ *      hi[k]), with CRYCHIC_TAA_UPSCALE_NO_CLAMP hc[k] = hv[k].
+ *   6  with history n[k] = (hc[k] (256 - wgt) + c256[k] wgt + 128) >> 8 (at most 65535); without, n[k] = c256[k].
+ *      history_out[oy Wo + ox] = (n[R], n[G], n[B], 256 cA);  out[oy Wo + ox] = (min((n[k] + 128) >> 8, 255) for R, G, B;  cA).
+ * Known answers.  RESET: history_out == c256 and out == the rounded bilinear frame.  Wo == Wi, Ho == Hi, jx == jy == 0: U = 256 ox,
+ * fu = 0, c256 = 256 c, conf2 = 256, wgt = blend, rx = 1: both outputs are those of crychic_taa with the same blend and flags, byte for
+ * byte.  A constant frame C over a constant history Hc with identical matrices and NO_CLAMP: n = (Hc (256 - wgt) + 256 C wgt + 128) >> 8
+ * with each pixel's own wgt.  Wo == 2 Wi, Ho == 2 Hi, zero jitter: fu, fv are 64 or 192, dX = dY = 128, conf = 64, conf2 = 16 in every
+ * pixel.
+ *
+ * Parameters (32 bytes): blend, the weight in 1/256 of a current sample that falls on the pixel's centre (default 102; 1 .. 256);
+ * flags (CRYCHIC_TAA_UPSCALE_RESET, CRYCHIC_TAA_UPSCALE_NO_CLAMP: the bit values and meanings of the CRYCHIC_TAA_ flags); reserved
+ * (must be 0).  crychic_taa_upscale_default_params fills the defaults (pure host code; CRYCHIC_E_INVALID_ARG for NULL).
+ *
+ * crychic_taa_upscale writes rows [row0, row0 + rows) of out_rgba8_dev and history_out_dev (rows of the OUTPUT) and no other byte; it
+ * reads any texel of in_rgba8_dev, depth_dev and history_in_dev.  Stitched row ranges equal the whole-frame call byte for byte in both
+ * outputs, for any split; rows == 0 launches nothing.  One launch on `stream`: no allocation, no synchronisation, no host read-back;
+ * capturable into a graph.  CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and before anything is enqueued:
+ * a NULL plane (history_in_dev only without RESET), cb or matrix; an RGBA8 or depth plane that is not 4-byte aligned or a history plane
+ * that is not 8-byte aligned; a size of 0; Wo outside Wi .. 4 Wi or Ho outside Hi .. 4 Hi; a row range outside the output; a
+ * non-finite matrix entry or jitter, or a jitter beyond 0.5 in magnitude; blend outside 1 .. 256, an unknown flag bit or a non-zero
+ * reserved word; out overlapping in or depth; history_out overlapping history_in; a history plane overlapping in, out or depth (out
+ * and the histories have Wo x Ho texels, in and depth Wi x Hi).  More than 2^28 output pixels, or Wo or Ho above 2^22: CRYCHIC_E_UNSUPPORTED. */
+#define CRYCHIC_TAA_UPSCALE_RESET CRYCHIC_TAA_RESET
+#define CRYCHIC_TAA_UPSCALE_NO_CLAMP CRYCHIC_TAA_NO_CLAMP
+typedef struct crychic_taa_upscale_params {
+    uint32_t blend;
+    uint32_t flags;
+    uint32_t reserved[6];
+} crychic_taa_upscale_params;   /* 32 bytes */
+int crychic_taa_upscale_default_params(crychic_taa_upscale_params* out);
+int crychic_taa_upscale(crychic_ctx* ctx, const crychic_pass_constants* cb, const float curViewProj[16], const float prevViewProj[16],
+                        float jx, float jy, const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, uint32_t Wi, uint32_t Hi,
+                        const uint16_t* history_in_dev, uint16_t* history_out_dev, uint8_t* out_rgba8_dev, uint32_t Wo, uint32_t Ho,
+                        uint32_t row0, uint32_t rows, const crychic_taa_upscale_params* params /* NULL = defaults */, void* stream);
+
 /* ---- motion blur: depth-reprojected velocity, tile maximum, gather (extension) ---------------------------
  * Camera motion turned into blur of the finished RGBA8 frame.  A separate call behind the depth of field and in front of the bloom and
  * the post-process anti-aliasing; it writes a buffer of its own.  Each pixel's velocity is the reprojection of crychic_taa (steps 2
