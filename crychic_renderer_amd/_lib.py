@@ -26,6 +26,7 @@ GBUFFER_F16_MASK = 0x7000
 COMM_ID_BYTES = 128
 AA_MAX_SEARCH = 16            # CRYCHIC_AA_MAX_SEARCH: the longest end search of crychic_antialias, in pixels
 FOG_MAX_STEPS = 64            # CRYCHIC_FOG_MAX_STEPS: the most samples crychic_fog takes along a view ray
+SKY_MAX_VIEW_STEPS, SKY_MAX_SUN_STEPS = 64, 32      # CRYCHIC_SKY_MAX_VIEW_STEPS, CRYCHIC_SKY_MAX_SUN_STEPS: the marches of crychic_render_sky
 SSR_MAX_STEPS = 64            # CRYCHIC_SSR_MAX_STEPS: the most samples crychic_ssr takes along a reflected ray
 DOF_MAX_RADIUS = 8            # CRYCHIC_DOF_MAX_RADIUS: the largest gather radius of crychic_dof, in pixels
 BLOOM_MAX_LEVELS = 8          # CRYCHIC_BLOOM_MAX_LEVELS: the most levels of crychic_bloom's pyramid
@@ -120,6 +121,27 @@ class FogParams(C.Structure):
                 p.steps = int(v)
             else:
                 setattr(p, k, float(v))
+        return p
+
+
+class SkyParams(C.Structure):
+    """crychic_sky_params: the knobs of crychic_render_sky (extension); SkyParams.default() = crychic_sky_default_params.  sunDir
+    takes an (x, y, z) sequence, towards the sun; the definition normalises it."""
+    _fields_ = [("sunDir", C.c_float * 3), ("altitude", C.c_float), ("sunIntensity", C.c_float), ("exposure", C.c_float),
+                ("sunAngularRadius", C.c_float), ("groundAlbedo", C.c_float), ("viewSteps", C.c_uint32), ("sunSteps", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def default(cls, **fields):
+        p = cls()
+        check(lib.crychic_sky_default_params(C.byref(p)))
+        for k, v in fields.items():
+            if k == "sunDir":
+                p.sunDir = (C.c_float * 3)(*[float(c) for c in v])
+            elif k == "reserved":
+                p.reserved = (C.c_uint32 * 2)(*[int(c) for c in v])
+            else:
+                setattr(p, k, int(v) if k in ("viewSteps", "sunSteps") else float(v))
         return p
 
 
@@ -331,6 +353,9 @@ PROTOTYPES = {
     "crychic_build_env_brdf": (_i, [_vp, _vp, _vp]),
     "crychic_cube_probe_offset": (_sz, [_u32, _u32]),
     "crychic_set_cube_probe_volume": (_i, [_vp, _vp, _P(_f), _P(_f), _P(_f), _vp]),
+    "crychic_sky_default_params": (_i, [_P(SkyParams)]),
+    "crychic_render_sky": (_i, [_vp, _vp, _u32, _u32, _u32, _P(SkyParams), _vp]),
+    "crychic_sky_sun_colour": (_i, [_P(SkyParams), _P(_f)]),
     "crychic_aa_default_params": (_i, [_P(AAParams)]),
     "crychic_antialias": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(AAParams), _vp]),
     "crychic_fog_default_params": (_i, [_P(FogParams)]),

@@ -28,6 +28,7 @@
 #include "taa_upscale_core.hpp"
 #include "motion_blur_core.hpp"
 #include "decal_core.hpp"
+#include "sky_core.hpp"
 #include "internal.hpp"
 
 namespace {
@@ -1444,6 +1445,71 @@ int crychic_set_cube_probe_volume(crychic_ctx* ctx, void* tail_dev, const float 
     if (!cry::probe_volume_valid(pos, boxMin, boxMax))
         return fail(CRYCHIC_E_INVALID_ARG, "probe volume: every value finite and boxMin < pos < boxMax in every component");
     CRY_HIP(cry::launch_cube_probe_volume(tail_dev, pos, boxMin, boxMax, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(CRYCHIC_SKY_MAX_VIEW_STEPS == cry::kSkyMaxViewSteps && CRYCHIC_SKY_MAX_SUN_STEPS == cry::kSkyMaxSunSteps &&
+                  sizeof(crychic_sky_params) == 48 && sizeof(crychic_sky_params) == sizeof(cry::SkyParams),
+              "sky_core.hpp mirrors the ABI");
+
+int crychic_sky_default_params(crychic_sky_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    *out = crychic_sky_params{};
+    out->sunDir[0] = 0.0f; out->sunDir[1] = 0.5f; out->sunDir[2] = -0.8660254f;      // 30 degrees up
+    out->altitude = 0.002f; out->sunIntensity = 20.0f; out->exposure = 2.0f;
+    out->sunAngularRadius = 0.02f; out->groundAlbedo = 0.3f;
+    out->viewSteps = 16u; out->sunSteps = 8u;
+    return 0;
+}
+
+namespace {
+// The parameters of a sky call, with the defaults for NULL; a refusal leaves the message behind.
+int sky_params(const crychic_sky_params* params, cry::SkyParams* q)
+{
+    crychic_sky_params p;
+    crychic_sky_default_params(&p);
+    if (params) p = *params;
+    const auto in = [](float v, float lo, float hi) { return v >= lo && v <= hi; };       // false for NaN
+    for (int c = 0; c < 3; ++c)
+        if (!in(p.sunDir[c], -3.40282347e38f, 3.40282347e38f)) return fail(CRYCHIC_E_INVALID_ARG, "sky sunDir[%d] %g is not finite", c, (double)p.sunDir[c]);
+    if (p.sunDir[0] == 0.0f && p.sunDir[1] == 0.0f && p.sunDir[2] == 0.0f) return fail(CRYCHIC_E_INVALID_ARG, "sky sunDir is the zero vector");
+    if (!in(p.altitude, 0.0f, 50.0f)) return fail(CRYCHIC_E_INVALID_ARG, "sky altitude %g outside 0 .. 50 km", (double)p.altitude);
+    if (!in(p.sunIntensity, 0.0f, 65536.0f)) return fail(CRYCHIC_E_INVALID_ARG, "sky sunIntensity %g outside 0 .. 65536", (double)p.sunIntensity);
+    if (!in(p.exposure, 0.0f, 65536.0f)) return fail(CRYCHIC_E_INVALID_ARG, "sky exposure %g outside 0 .. 65536", (double)p.exposure);
+    if (!in(p.sunAngularRadius, 0.0f, 0.5f)) return fail(CRYCHIC_E_INVALID_ARG, "sky sunAngularRadius %g outside 0 .. 0.5", (double)p.sunAngularRadius);
+    if (!in(p.groundAlbedo, 0.0f, 1.0f)) return fail(CRYCHIC_E_INVALID_ARG, "sky groundAlbedo %g outside 0 .. 1", (double)p.groundAlbedo);
+    if (p.viewSteps == 0 || p.viewSteps > CRYCHIC_SKY_MAX_VIEW_STEPS)
+        return fail(CRYCHIC_E_INVALID_ARG, "sky viewSteps %u outside 1 .. %d", p.viewSteps, CRYCHIC_SKY_MAX_VIEW_STEPS);
+    if (p.sunSteps == 0 || p.sunSteps > CRYCHIC_SKY_MAX_SUN_STEPS)
+        return fail(CRYCHIC_E_INVALID_ARG, "sky sunSteps %u outside 1 .. %d", p.sunSteps, CRYCHIC_SKY_MAX_SUN_STEPS);
+    if (p.reserved[0] | p.reserved[1]) return fail(CRYCHIC_E_INVALID_ARG, "sky reserved words must be 0");
+    std::memcpy(q, &p, sizeof *q);
+    return 0;
+}
+}  // namespace
+
+int crychic_render_sky(crychic_ctx* ctx, uint8_t* cube_dev, uint32_t dim, uint32_t face0, uint32_t faces, const crychic_sky_params* params,
+                       void* stream)
+{
+    // every argument is checked before the context is looked at: a refusal needs no device
+    if (!cube_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (reinterpret_cast<uintptr_t>(cube_dev) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "cube map is not 4-byte aligned");
+    if (dim < 2u || dim > 8192u) return fail(CRYCHIC_E_INVALID_ARG, "cube map face size %u outside 2 .. 8192", dim);
+    if (face0 > 6u || faces > 6u - face0) return fail(CRYCHIC_E_INVALID_ARG, "faces [%u,+%u) outside the six faces", face0, faces);
+    cry::SkyParams q;
+    if (int rc = sky_params(params, &q)) return rc;
+    if (int rc = bind(ctx)) return rc;
+    CRY_HIP(cry::launch_sky(cube_dev, dim, face0, faces, q, (hipStream_t)stream));
+    return 0;
+}
+
+int crychic_sky_sun_colour(const crychic_sky_params* params, float rgb[3])
+{
+    if (!rgb) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    cry::SkyParams q;
+    if (int rc = sky_params(params, &q)) return rc;
+    cry::sky_sun_colour(q, rgb);
     return 0;
 }
 

@@ -85,6 +85,11 @@ hipError_t launch_cube_probe_volume(void* tail, const float pos[3], const float 
 // caller has checked the pointer and its alignment.
 hipError_t launch_env_brdf(void* table, hipStream_t stream);
 
+// sky.hip: level 0 of faces [face0, face0 + faces) of the dim-texel cube map `cube` from the atmosphere of `p` (sky_core.hpp); one
+// launch on `stream`, none for faces == 0.  The caller has checked the pointer, its alignment, dim, the face range and `p`.
+struct SkyParams;
+hipError_t launch_sky(uint8_t* cube, uint32_t dim, uint32_t face0, uint32_t faces, const SkyParams& p, hipStream_t stream);
+
 // post_aa.hip: rows [row0, row0 + rows) of the anti-aliased W x H RGBA8 frame `out` from `in` (post_aa_core.hpp); one launch on
 // `stream`, none for rows == 0.  The caller has checked the pointers, their alignment and overlap, the sizes, the rows and `p`.
 struct PostAaParams;

@@ -55,6 +55,7 @@ most 256) and --motion-blur-samples (2, 4, 8, 16 or 32, default 8) set its param
 glossy puddle with a dent normal map on the floor and a painted ring on the face of a box."""
 import argparse
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -84,6 +85,11 @@ def main():
     ap.add_argument("--ssr-steps", type=int, default=None, metavar="N", help="samples along each reflected ray, 1 .. 64 (default 32; needs --ssr)")
     ap.add_argument("--ssr-distance", type=float, default=None, metavar="X", help="length of a reflected ray in world units (default 20; needs --ssr)")
     ap.add_argument("--ssr-max-roughness", type=float, default=None, metavar="X", help="surfaces at or above this roughness do not reflect, 0 .. 1 (default 0.75; needs --ssr)")
+    ap.add_argument("--sky", action="store_true", help="render the procedural sky (a single-scattering atmosphere) under the sun of Lights[0] "
+                    "into the cube map, with the chain, tail and table that --gloss, --env-ambient and --env-specular ask for")
+    ap.add_argument("--sky-sun-elevation", type=float, default=None, metavar="DEG", help="the sun's elevation over the horizon, along the azimuth "
+                    "of Lights[0] (default: where Lights[0] shines from; needs --sky)")
+    ap.add_argument("--sky-steps", type=int, default=None, metavar="N", help="samples along each view ray, 1 .. 64 (default 16; needs --sky)")
     ap.add_argument("--fog", action="store_true", help="volumetric fog with sun shafts through the cascades, after the lighting pass")
     ap.add_argument("--fog-density", type=float, default=None, metavar="X", help="fog density, 0 .. 16 (default 0.02; needs --fog)")
     ap.add_argument("--fog-steps", type=int, default=None, metavar="N", help="samples along each view ray, 1 .. 64 (default 16; needs --fog)")
@@ -201,6 +207,27 @@ def main():
         app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient, env_brdf=a.env_specular,
                          parallax=box is not None)
         print("captured the environment at (%g, %g, %g): %d-texel faces, %d levels" % (pos[0], pos[1], pos[2], dim, levels))
+    if a.sky:
+        from ._lib import SkyParams
+        knobs = {} if a.sky_steps is None else dict(viewSteps=a.sky_steps)
+        levels = None if a.gloss else 1
+        if levels is None or a.env_ambient or a.env_specular:       # bind a cube map with the flags followSun is to keep
+            chain, dim, levels = app.render_sky(SkyParams.default(**knobs), dim=256, levels=levels, prefilter=a.gloss, irradiance=a.env_ambient,
+                                                env_brdf=a.env_specular)
+            app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient, env_brdf=a.env_specular)
+        if a.sky_sun_elevation is None:
+            app.followSun = SkyParams.default(**knobs) if knobs else True
+            d = app.mMainPassCB.Lights[0].Direction
+            sun = (-d[0], -d[1], -d[2])
+        else:
+            d = app.mMainPassCB.Lights[0].Direction
+            az, el = math.atan2(-d[0], -d[2]), math.radians(a.sky_sun_elevation)
+            sun = (math.cos(el) * math.sin(az), math.sin(el), math.cos(el) * math.cos(az))
+            chain, dim, levels = app.render_sky(SkyParams.default(sunDir=sun, **knobs), dim=256, levels=levels, prefilter=a.gloss,
+                                                irradiance=a.env_ambient, env_brdf=a.env_specular)
+            app.set_cube_map(chain, dim, levels, gloss=a.gloss and levels > 1, ambient_sh=a.env_ambient, env_brdf=a.env_specular)
+        print("procedural sky: sun towards (%.3f, %.3f, %.3f), sun colour %s" % (sun + (tuple(round(c, 3) for c in app.sky_sun_colour(
+            SkyParams.default(sunDir=sun, **knobs))),)))
     if a.ssr:
         knobs = {k: v for k, v in (("steps", a.ssr_steps), ("maxDistance", a.ssr_distance), ("maxRoughness", a.ssr_max_roughness)) if v is not None}
         app.ssr = SsrParams.default(**knobs) if knobs else True

@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (AAParams, CrychicError, FogParams, SsrParams, DofParams, BloomParams, TaaParams, TaaUpscaleParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, FogParams, SkyParams, SsrParams, DofParams, BloomParams, TaaParams, TaaUpscaleParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -220,6 +220,9 @@ class Crychic:
         self._pointHost = None       # host copy of the point lights (the face transforms are built from it)
         self._pointShadow = None     # (PointShadows descriptor, [face pass constants, 6 per light], geometry)
         self._desc = None
+        self._followSun = None       # followSun, extension: None | True | SkyParams -- Draw() keeps a procedural sky bound whose sun is Lights[0]
+        self._skyKey, self._skyChain = None, None    # what the sky in _skyChain, followSun's own chain, was rendered from
+        self.skyRenders = 0          # launches of crychic_render_sky this object has issued (render_sky and followSun)
         # The switches of the passes behind the lighting pass (the properties below): Draw() looks at _post alone, so a frame with none
         # of them set pays one test however many passes there are.
         self._post = False
@@ -341,7 +344,11 @@ class Crychic:
         temporalUpscale = (Wo, Ho) or (Wo, Ho, TaaUpscaleParams) puts crychic_taa_upscale at the temporal pass's place: the frame of the
         client size, rendered with the jitter handed to set_frame_view_proj, is accumulated into a history of Wo x Ho texels, and the
         bloom and the anti-aliasing behind it run at that size.  Together with temporalAA, depthOfField or motionBlur it raises
-        CrychicError before anything is issued (the last two read a depth plane of the frame's size)."""
+        CrychicError before anything is issued (the last two read a depth plane of the frame's size).
+        followSun (extension; True or a SkyParams): in front of all that, the procedural sky is kept bound whose sun is where Lights[0]
+        shines from (render_sky), re-rendered only when that direction or the parameters changed; strips and shared draws included."""
+        if self._followSun is not None:
+            self._follow_sun()
         if self._post:
             return self._draw_post_chain(row0, rows, shared)
         return self._draw_lighting(row0, rows, shared)
@@ -873,6 +880,106 @@ class Crychic:
         if probe_box is not None:       # into the chain that is bound later: the prefiltered one
             self.set_probe_volume(final, dim, levels, pos, probe_box[0], probe_box[1])
         return out, dim, levels
+
+    def render_sky(self, params=None, dim=256, levels=None, prefilter=False, irradiance=False, env_brdf=False, out=None):
+        """Extension: renders the procedural sky -- a single-scattering atmosphere lit by the sun of `params` (a SkyParams; None = the
+        defaults) -- into level 0 of a cube map (crychic_render_sky; include/crychic_hip.h "procedural sky") and builds what
+        capture_environment builds behind a capture, in its order: the mip chain, then with irradiance the SH9 projection of level 0
+        into the environment tail, with env_brdf (needs prefilter=True and more than one level) the environment BRDF table, with
+        prefilter the chain prefiltered by roughness (the box chain lives in a scratch tensor kept with the capture probes).  levels
+        None = the full chain.  out: a uint8 tensor of at least the bytes the options need (geometry.cube_chain_bytes,
+        cube_chain_sh_bytes or cube_chain_env_bytes) that must not overlap the bound cube map (default: a new one).  Returns
+        (chain, dim, levels); binding it is the caller's set_cube_map(chain, dim, levels, ...), as after a capture."""
+        return self._render_sky(params, dim, levels, prefilter, irradiance, env_brdf, out, False)
+
+    def _render_sky(self, params, dim, levels, prefilter, irradiance, env_brdf, out, own):
+        """render_sky; own: `out` is followSun's own chain, which may be the bound one (the sky reads no cube map)."""
+        from .geometry import cube_chain_bytes, cube_chain_env_bytes, cube_chain_sh_bytes, cube_env_brdf_offset, cube_full_levels, cube_sh_offset
+        if env_brdf and not prefilter:
+            raise CrychicError(-1, "render_sky: env_brdf needs prefilter=True (the table weighs a prefiltered chain)")
+        dim = int(dim)
+        if not 2 <= dim <= 8192:
+            raise CrychicError(-1, "render_sky: dim %d (a sky cube map has 2 .. 8192-texel faces)" % dim)
+        full = cube_full_levels(dim)
+        levels = full if levels is None else int(levels)
+        if not 1 <= levels <= full:
+            raise CrychicError(-1, "render_sky: levels %d (1 .. %d for %d-texel faces)" % (levels, full, dim))
+        if env_brdf and levels < 2:
+            raise CrychicError(-1, "render_sky: env_brdf needs a chain (levels > 1)")
+        chain_bytes = cube_chain_bytes(dim, levels)
+        nbytes = cube_chain_env_bytes(dim, levels) if env_brdf else cube_chain_sh_bytes(dim, levels) if irradiance else chain_bytes
+        if out is None:
+            out = torch.empty((nbytes,), device=self.ctx.device, dtype=torch.uint8)
+        elif out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() < nbytes or out.device != self.mBackBuffer.device:
+            raise CrychicError(-1, "render_sky: out must be a contiguous uint8 device tensor of at least %d bytes" % nbytes)
+        src = self.mCubeMap
+        if not own and out.data_ptr() < src.data_ptr() + src.numel() * src.element_size() and src.data_ptr() < out.data_ptr() + nbytes:
+            raise CrychicError(-1, "render_sky: the destination aliases the bound cube map")
+        final = out
+        if prefilter:           # the faces and their box chain go to the scratch chain, the prefiltered chain to `out`
+            out = self._probe_chains.get((dim, levels))
+            if out is None:
+                out = self._probe_chains[(dim, levels)] = torch.empty((chain_bytes,), device=self.ctx.device, dtype=torch.uint8)
+        check(lib.crychic_render_sky(self.ctx.handle, _ptr(out), dim, 0, 6, None if params is None else C.byref(params), _stream(self.ctx.device)))
+        self.skyRenders += 1
+        if levels > 1:
+            self.generate_cube_mips(out, dim, levels)
+        if irradiance:
+            check(lib.crychic_project_cube_sh(self.ctx.handle, _ptr(out), dim, C.c_void_p(final.data_ptr() + cube_sh_offset(dim, levels)),
+                                              _stream(self.ctx.device)))
+        if env_brdf:
+            check(lib.crychic_build_env_brdf(self.ctx.handle, C.c_void_p(final.data_ptr() + cube_env_brdf_offset(dim, levels)),
+                                             _stream(self.ctx.device)))
+        if prefilter:
+            out = self.prefilter_cube_map(out, dim, levels, out=final)
+        return out, dim, levels
+
+    @staticmethod
+    def sky_sun_colour(params=None):
+        """Extension: the colour of the sun's light under the sky of `params` (crychic_sky_sun_colour): three floats, the sun's
+        intensity through the atmosphere along its own ray, zeros when the planet hides it -- what Lights[0].Strength should be so
+        that the light reddens as the sky does.  Host code; needs no device."""
+        rgb = (C.c_float * 3)()
+        check(lib.crychic_sky_sun_colour(None if params is None else C.byref(params), rgb))
+        return tuple(rgb)
+
+    def _follow_sun(self):
+        """Draw() with followSun set: the sun of the sky is where Lights[0] shines from.  If that direction or the parameters are not
+        those of the sky last rendered, or another cube map was bound since, the sky is rendered anew -- with the mips, the prefilter,
+        the SH projection and the table that the flags of the last set_cube_map need -- into a chain of this object's own, which is
+        then bound with those flags."""
+        p = SkyParams.from_buffer_copy(self._followSun) if isinstance(self._followSun, SkyParams) else SkyParams.default()
+        d = self.mMainPassCB.Lights[0].Direction
+        p.sunDir[:] = [-d[0], -d[1], -d[2]]
+        if self.mCubeMapParallax:
+            raise CrychicError(-1, "followSun: a sky has no probe volume (set_cube_map(parallax=True) is bound)")
+        dim, levels = int(self.mCubeMapSize or self.mCubeMap.shape[1]), int(self.mCubeMapLevels)
+        flags = (self.mCubeMapGloss, self.mCubeMapAmbientSH, self.mCubeMapEnvBrdf)
+        key = (bytes(p), dim, levels, flags)
+        if key == self._skyKey and self._skyChain is not None and self.mCubeMap.data_ptr() == self._skyChain.data_ptr():
+            return
+        from .geometry import cube_chain_env_bytes
+        nbytes = cube_chain_env_bytes(dim, levels)      # room for the tail and the table, whatever the flags
+        if self._skyChain is None or self._skyChain.numel() != nbytes:
+            self._skyChain = torch.empty((nbytes,), device=self.ctx.device, dtype=torch.uint8)
+        self._render_sky(p, dim, levels, flags[0], flags[1], flags[2], self._skyChain, True)
+        self.set_cube_map(self._skyChain, dim, levels, gloss=flags[0], ambient_sh=flags[1], env_brdf=flags[2])
+        self._skyKey = key
+
+    @property
+    def followSun(self):
+        """Extension: None | True | SkyParams.  When set, Draw() takes the sky's sunDir from -mMainPassCB.Lights[0].Direction in front
+        of the lighting frame and re-renders the procedural sky (render_sky) whenever the direction or the parameters changed, into a
+        chain of its own, bound with the flags the previous set_cube_map asked for.  Independent of the passes behind the lighting
+        pass and of strips: every rank renders the same deterministic cube.  Unset, Draw issues exactly the calls it issues without it."""
+        return self._followSun
+
+    @followSun.setter
+    def followSun(self, value):
+        if not (value is None or value is True or value is False or isinstance(value, SkyParams)):
+            raise CrychicError(-1, "followSun: None, True or a SkyParams")
+        self._followSun = value or None
+        self._skyKey = None
 
     def release_capture_probes(self):
         """Frees the probe renderers capture_environment keeps (one per (dim, shadow_dim) it was called with)."""

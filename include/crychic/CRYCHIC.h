@@ -230,6 +230,7 @@ public:
             else { DrawNormalsAndDepth(); DrawGBuffer(); }
             if (mDecalCount) ApplyDecals();                                                         // SetDecals: into the fresh G-buffer
         }
+        if (mFollowSun && !mOwner) FollowSun();                                                     // SetProceduralSky: the sky under this frame's sun
         // L: whose cube map, local lights and local-light shadow maps this frame reads -- a capture's probe reads its owner's
         const CRYCHIC& L = mOwner ? *mOwner : *this;
         crychic_frame_desc f = {};
@@ -825,6 +826,7 @@ public:
         mCubeMapHasTable = hasTable;
         mCubeMapHasProbe = false;               // CaptureEnvironment and SetReflectionProbeBox write the volume and say so
         mHaveCapturePos = false;
+        mSkyOf = nullptr;                       // SetProceduralSky: whatever is bound now is not (yet) the sky Draw rendered
     }
     bool CubeMapHasTail() const { return mCubeMapHasTail; }
     bool CubeMapHasTable() const { return mCubeMapHasTable; }
@@ -864,6 +866,81 @@ public:
     // it ran crychic_prefilter_cube_chain over.
     void SetGlossyReflections(bool on) { mGlossyReflections = on; }
     bool GlossyReflections() const { return mGlossyReflections; }
+
+    // Procedural sky (extension: include/crychic_hip.h "procedural sky"; no counterpart: the reference's sky is
+    // a file).  Renders the single-scattering atmosphere of `params` (nullptr = the defaults) into level 0 of a chain of `levels`
+    // levels (0 = the full chain) of `dim`-texel faces (0 = the bound cube map's size, 256 if none is bound) and binds it, shaped like
+    // CaptureEnvironment: the mip chain, and with SetEnvironmentAmbient / SetEnvironmentSpecular / SetGlossyReflections on the SH
+    // projection of level 0, the environment BRDF table and the prefilter, in that order, refused in the same combinations.  The cube
+    // map bound before becomes the next call's destination when its size fits, so a per-frame re-render allocates nothing.
+    void RenderSky(const crychic_sky_params* params = nullptr, UINT dim = 0, UINT levels = 0)
+    {
+        if (dim == 0) dim = mCubeMap ? mCubeMapSize : 256u;
+        uint32_t full = 1;
+        for (UINT m = dim; m > 1u; m >>= 1) ++full;
+        if (full > 15u) full = 15u;
+        if (levels == 0) levels = full;
+        if (dim < 2u || dim > 8192u || levels > full)
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::RenderSky (dim 2 .. 8192; at most floor(log2 dim) + 1 levels)", __FILE__, __LINE__);
+        if (mEnvironmentAmbient && levels > 1u && !mGlossyReflections)
+            throw CrychicException(CRYCHIC_E_UNSUPPORTED, "CRYCHIC::RenderSky (environment ambient with a chain needs glossy reflections)", __FILE__, __LINE__);
+        if (mEnvironmentSpecular && (levels < 2u || !mGlossyReflections))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::RenderSky (environment specular needs glossy reflections and a chain)", __FILE__, __LINE__);
+        const bool gloss = mGlossyReflections && levels > 1u;
+        const size_t chainBytes = crychic_cube_chain_bytes(dim, levels);
+        const size_t boundBytes = mEnvironmentSpecular ? crychic_cube_chain_env_bytes(dim, levels)
+                                : mEnvironmentAmbient ? crychic_cube_chain_sh_bytes(dim, levels) : chainBytes;
+        std::unique_ptr<ID3D12Resource> chain = std::move(mSpareCubeMap);
+        if (!chain || chain->Bytes() != boundBytes) chain = std::make_unique<ID3D12Resource>(boundBytes, ID3D12Resource::DEFAULT_HEAP);
+        if (gloss && (!mCaptureBoxChain || mCaptureBoxChain->Bytes() != chainBytes))
+            mCaptureBoxChain = std::make_unique<ID3D12Resource>(chainBytes, ID3D12Resource::DEFAULT_HEAP);
+        ID3D12Resource* box = gloss ? mCaptureBoxChain.get() : chain.get();
+        crychic_ctx* ctx = md3dDevice->Ctx();
+        CrychicThrowIfFailed(crychic_render_sky(ctx, static_cast<uint8_t*>(box->Data()), dim, 0, 6, params, mCommandList->Stream()));
+        ++mSkyRenders;
+        CrychicThrowIfFailed(crychic_generate_cube_mips(ctx, static_cast<uint8_t*>(box->Data()), dim, levels, mCommandList->Stream()));
+        if (mEnvironmentAmbient)
+            CrychicThrowIfFailed(crychic_project_cube_sh(ctx, static_cast<const uint8_t*>(box->Data()), dim,
+                                                         static_cast<uint8_t*>(chain->Data()) + crychic_cube_sh_offset(dim, levels), mCommandList->Stream()));
+        if (mEnvironmentSpecular)
+            CrychicThrowIfFailed(crychic_build_env_brdf(ctx, static_cast<uint8_t*>(chain->Data()) + crychic_cube_env_brdf_offset(dim, levels),
+                                                        mCommandList->Stream()));
+        if (gloss)
+            CrychicThrowIfFailed(crychic_prefilter_cube_chain(ctx, static_cast<const uint8_t*>(box->Data()), static_cast<uint8_t*>(chain->Data()), dim,
+                                                              levels, mCommandList->Stream()));
+        mCommandList->Flush();                  // frames in flight may still read the cube map bound so far, the next call's destination
+        mSpareCubeMap = std::move(mCubeMap);
+        SetCubeMap(std::move(chain), dim, levels, mEnvironmentAmbient, mEnvironmentSpecular);
+    }
+    // While `follow` is on, Draw takes the sky's sunDir from -mMainPassCB.Lights[0].Direction in front of the lighting frame and, when
+    // the direction or the parameters are not those of the sky it rendered last (or another cube map was bound since), calls
+    // RenderSky(params with that sun, the bound size and levels).  Off, Draw issues exactly the calls it issues without it.
+    void SetProceduralSky(bool follow, const crychic_sky_params* params = nullptr)
+    {
+        crychic_sky_params p;
+        CrychicThrowIfFailed(crychic_sky_default_params(&p));
+        if (params) p = *params;
+        float rgb[3];
+        CrychicThrowIfFailed(crychic_sky_sun_colour(&p, rgb));      // a parameter outside its range is refused here and leaves the switch as it was
+        mSkyParams = p; mFollowSun = follow; mSkyOf = nullptr;
+    }
+    bool ProceduralSky() const { return mFollowSun; }
+    // The angle about +y the next Update turns the three directional lights by.  The reference's own rate is zero (:152), so its
+    // lights stand still; an application that moves its sun sets the angle here, and the shadows, the lighting and -- under
+    // SetProceduralSky -- the sky follow from the same pass constants.
+    void SetLightRotationAngle(float radians) { mLightRotationAngle = radians; }
+    float LightRotationAngle() const { return mLightRotationAngle; }
+    // Draw's part of SetProceduralSky
+    void FollowSun()
+    {
+        const auto& d = mMainPassCB.Lights[0].Direction;
+        const float sun[3] = { -d.x, -d.y, -d.z };
+        if (mSkyOf && mSkyOf == mCubeMap.get() && std::memcmp(sun, mSkyParams.sunDir, sizeof sun) == 0) return;
+        std::memcpy(mSkyParams.sunDir, sun, sizeof sun);
+        RenderSky(&mSkyParams, mCubeMap ? mCubeMapSize : 0u, mCubeMap ? mCubeMapLevels : 1u);
+        mSkyOf = mCubeMap.get();
+    }
+    UINT SkyRenders() const { return mSkyRenders; }     // launches of crychic_render_sky this object has issued
 
     // CRYCHIC::LoadTextures (CRYCHIC.cpp:939-973): the six material textures in heap order (= gTextureMaps indices, :954-959) with the
     // mip chains their files store, and the sky cube map, from `dir` (the reference opens "Textures/...").  The DDS decoding that
@@ -1413,6 +1490,10 @@ private:
     bool mHaveCapturePos = false;                   // the bound cube map is CaptureEnvironment's, taken at mCapturePos
     float mProbeBoxMin[3] = {}, mProbeBoxMax[3] = {}, mCapturePos[3] = {};
     std::unique_ptr<ID3D12Resource> mCaptureBoxChain;   // CaptureEnvironment with glossy reflections: the captured box chain, kept
+    bool mFollowSun = false;                        // SetProceduralSky
+    crychic_sky_params mSkyParams = {};             // SetProceduralSky's, and from the last FollowSun on with the sun it rendered
+    const ID3D12Resource* mSkyOf = nullptr;         // the cube map FollowSun bound last (nullptr: none yet, or the parameters changed)
+    UINT mSkyRenders = 0;
     UINT mClientWidth, mClientHeight;
     float mLightRotationAngle = 0.0f;
     DirectX::XMFLOAT3 mBaseLightDirections[3] = { { 0.57735f, -0.57735f, 0.57735f }, { -0.57735f, -0.57735f, 0.57735f }, { 0.0f, -0.707f, -0.707f } };  // CRYCHIC.h:173-177

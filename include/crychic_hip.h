@@ -809,6 +809,104 @@ size_t crychic_cube_probe_offset(uint32_t dim, uint32_t levels);
 int crychic_set_cube_probe_volume(crychic_ctx* ctx, void* tail_dev, const float pos[3], const float boxMin[3], const float boxMax[3],
                                   void* stream);
 
+/* ---- procedural sky: a single-scattering atmosphere into the cube map (BUILD-DEFINED EXTENSION) ---------- *
+ * The producer of level 0 of a cube map that needs neither a file nor six renders of a scene: one ray per texel through a spherical
+ * atmosphere lit by one sun (Nishita-style single scattering: Rayleigh and Mie, no ozone, no multiple scattering), tone-mapped with
+ * the lighting pass's own operator into RGBA8.  A build definition: nothing of it is the reference's, whose sky.hlsl only samples a
+ * cube.  The device, a host build and the checker (tests/sky_ref) agree bit for bit.
+ *
+ * Float operations are IEEE binary32, each rounded once, in the order written; fma(a, b, c) is the fused a b + c and nothing else is
+ * fused.  rcp, len_from_sq, dot3 and det_exp2 are those of crychic_fog below;  max0(x) = x > 0 ? x : 0 (NaN -> 0);
+ * normalize3(v) = v * rcp(len_from_sq(dot3(v, v))) per component;  pow_inv_gamma is the lighting pass's pinned pow(x, 1 / 2.2)
+ * (SCALE[E] * P(m - 1), gamma_pow.inc);  unorm8(x) = (uint32_t)fma(min(max(x, 0), 1), 255, 0.5).
+ *
+ * Atmosphere, in kilometres.  A planet of radius Rg = 6360 under a shell of radius Rt = 6420.  Rayleigh scattering
+ * betaR = (5.8e-3f, 13.5e-3f, 33.1e-3f) per km with scale height 8; Mie scattering betaM = 21e-3f with extinction 1.1 betaM, scale
+ * height 1.2 and g = 0.76.  The binary32 constants derived from them (nearest to the decimal written):
+ *   Rg2 = 40449600 (exact);  invRg = 0.000157232702;  nHR = -0.180336878 (-log2(e) / 8);  nHM = -1.20224583 (-log2(e) / 1.2);
+ *   tauR = (0.00836763065, 0.0194763839, 0.0477532074) (betaR log2(e));  tauM = 0.0333262533 (1.1 betaM log2(e));
+ *   phaseR = 0.0596831031 (3 / (16 pi));  phaseM = 0.0195609424 (3 (1 - g^2) / (8 pi (2 + g^2)));  -2 g = -1.52;  1 + g^2 = 1.5776;
+ *   invPi = 0.318309873.
+ * Positions are carried as q = r^2 - Rg^2 (r the distance from the planet's centre), never as r, so that no height is the
+ * difference of two numbers near 6400:   height(q) = q * rcp(len_from_sq(q + Rg2) + Rg).
+ *
+ * Host-side constants, once per call (double where written; every double operation is IEEE binary64, rounded once, in the order
+ * written), with Nv = viewSteps, Ns = sunSteps, alt = altitude:
+ *   len = sqrt(x x + y y + z z) of sunDir in double (left to right);  S = ((float)(x / len), (float)(y / len), (float)(z / len))
+ *   r0 = 6360.0f + alt (binary32);  a0 = (float)(alt (12720.0 + alt));  cT = (float)((60.0 - alt) (12780.0 + alt));  r0Sy = r0 S.y
+ *   invNv = 1.0f / (float)Nv;  invNv2 = invNv invNv;  invNs, invNs2 alike;  rd = rcp((float)dim)
+ *   a2 = sunAngularRadius^2 in double;  cosDisc = (float)(1.0 - a2 (0.5 - a2 / 24.0));  groundK = (groundAlbedo invPi) sunIntensity
+ * The observer stands at (0, r0, 0): +Y is up, as in the scene.
+ *
+ * Samples.  Both marches put sample i of N at the middle, in u, of the i-th of N equal intervals of u in [0, 1], with the distance
+ * along the ray t = L u^2: denser near the start of the ray, where the air is densest for every ray that climbs.
+ *   u_i = ((float)i + 0.5f) invN;   t_i = L (u_i u_i);   dt_i = L ((float)(2 i + 1) invN2)        (L the length of the ray's segment)
+ *
+ * blocked(q, bs) = bs < 0 && fma(bs, bs, -q) >= 0      -- the planet stands between the point (q, bs = P . S) and the sun
+ * to_shell(c, b):  sq = len_from_sq(fma(b, b, c));  b >= 0 ? c rcp(sq + b) : sq - b      -- c = Rt^2 - r^2 >= 0, b = P . direction
+ * sun_depth(q, bs, c), the sun march from a point:  L = to_shell(c, bs);  twob = bs + bs;  dR = dM = 0;  for j = 0 .. Ns - 1, with
+ *   (s, ds) = sample j of Ns over L:  h = height(fma(s, s + twob, q));  dR = fma(det_exp2(h nHR), ds, dR);
+ *   dM = fma(det_exp2(h nHM), ds, dM).
+ * trans_c(dR, dM) = det_exp2(-fma(tauR_c, dR, tauM dM)), c = R, G, B.
+ *
+ * Texel (x, y) of face f of a dim-texel cube map:
+ *   1  s = (float)(2 x + 1) rd - 1.0f;  t = (float)(2 y + 1) rd - 1.0f;  the direction of the texel centre is the prefilter's table
+ *      (crychic_prefilter_cube_chain step 1): +X (1, -t, -s), -X (-1, -t, s), +Y (s, 1, t), -Y (s, -1, -t), +Z (s, -t, 1),
+ *      -Z (-s, -t, -1);  v = normalize3 of it;  mu = dot3(v, S).
+ *   2  b = r0 v.y;  twob = b + b;  dg = fma(b, b, -a0);  ground = b < 0 && dg >= 0;
+ *      tEnd = ground ? a0 rcp(len_from_sq(dg) - b) : to_shell(cT, b).
+ *   3  vR = vM = 0, sR_c = sM_c = 0.  For i = 0 .. Nv - 1, with (t, dt) = sample i of Nv over tEnd:
+ *        w = t (t + twob);  q = a0 + w;  h = height(q);  rhoR = det_exp2(h nHR) dt;  rhoM = det_exp2(h nHM) dt;
+ *        mR = fma(0.5f, rhoR, vR);  mM = fma(0.5f, rhoM, vM);  vR = vR + rhoR;  vM = vM + rhoM;
+ *        bs = fma(t, mu, r0Sy);  a sample with blocked(q, bs) contributes nothing more (this is what makes twilight and night);
+ *        otherwise  D = sun_depth(q, bs, max0(cT - w));  for each c:  T = trans_c(mR + D.dR, mM + D.dM);
+ *        sR_c = fma(T, rhoR, sR_c);  sM_c = fma(T, rhoM, sM_c).
+ *   4  m1 = fma(mu, mu, 1.0f);  phR = phaseR m1;  xg = fma(-1.52f, mu, 1.5776f);  phM = (phaseM m1) rcp(xg len_from_sq(xg))
+ *      (Cornette-Shanks);  L_c = sunIntensity fma(phR betaR_c, sR_c, (phM betaM) sM_c).
+ *   5  disc = !ground && mu >= cosDisc.  If ground or disc:  w = tEnd (tEnd + twob);  q = max0(a0 + w);  bs = fma(tEnd, mu, r0Sy);
+ *      Tv_c = trans_c(vR, vM) (the whole view ray).  If ground && bs > 0 (the sun is above the ground point's horizon):
+ *      D = sun_depth(q, bs, max0(cT - w));  L_c = L_c + ((groundK (bs invRg)) trans_c(D.dR, D.dM)) Tv_c.
+ *      If disc:  L_c = fma(sunIntensity, Tv_c, L_c).
+ *   6  e = L_c exposure;  byte_c = unorm8(pow_inv_gamma(e rcp(e + 1.0f)));  the texel is R | G << 8 | B << 16 | 255 << 24.
+ * Every quantity is finite for parameters inside their ranges, so there is no NaN case.
+ *
+ * crychic_sky_sun_colour: zeros if blocked(a0, r0Sy); otherwise D = sun_depth(a0, r0Sy, cT) and rgb_c = sunIntensity trans_c(D.dR, D.dM).
+ * Known answers: a sun 30 degrees below the horizon gives the sun colour (0, 0, 0) and every texel (0, 0, 0, 255); for a sun at the
+ * zenith and altitude 0 the sun colour is sunIntensity exp(-(betaR_c 8 + 1.1 betaM 1.2)) up to the quadrature and the 60 km shell.
+ *
+ * Parameters: sunDir (towards the sun; any finite non-zero vector, normalised by the definition; default (0, 0.5, -0.8660254): 30
+ * degrees up), altitude (0.002 km; 0 .. 50), sunIntensity (20; 0 .. 65536), exposure (2; 0 .. 65536), sunAngularRadius (0.02 rad;
+ * 0 .. 0.5), groundAlbedo (0.3; 0 .. 1), viewSteps (16; 1 .. CRYCHIC_SKY_MAX_VIEW_STEPS), sunSteps (8; 1 .. CRYCHIC_SKY_MAX_SUN_STEPS),
+ * reserved (must be 0).  crychic_sky_default_params fills the defaults (pure host code; CRYCHIC_E_INVALID_ARG for NULL). */
+#define CRYCHIC_SKY_MAX_VIEW_STEPS 64
+#define CRYCHIC_SKY_MAX_SUN_STEPS 32
+typedef struct crychic_sky_params {
+    float sunDir[3];
+    float altitude;
+    float sunIntensity;
+    float exposure;
+    float sunAngularRadius;
+    float groundAlbedo;
+    uint32_t viewSteps;
+    uint32_t sunSteps;
+    uint32_t reserved[2];
+} crychic_sky_params;   /* 48 bytes */
+int crychic_sky_default_params(crychic_sky_params* out);
+/* Writes level 0 of faces [face0, face0 + faces) of the cube map at cube_dev (6 x dim x dim RGBA8, faces +X, -X, +Y, -Y, +Z, -Z; face
+ * f starts at cube_dev + f dim dim 4) and no other byte; it reads no device memory.  A texel depends on nothing but (f, x, y, dim) and
+ * the parameters, so any split of the six faces stitches to the whole call byte for byte; faces == 0 is valid and launches nothing.
+ * params == NULL = the defaults.  One launch on `stream`: no allocation, no synchronisation, no host read-back; capturable into a
+ * graph.  CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and before anything is enqueued: a NULL cube_dev
+ * or one that is not 4-byte aligned, dim outside 2 .. 8192, a face range outside the six faces, a parameter that is not finite or
+ * outside its range, a zero sunDir, a non-zero reserved word. */
+int crychic_render_sky(crychic_ctx* ctx, uint8_t* cube_dev, uint32_t dim, uint32_t face0, uint32_t faces,
+                       const crychic_sky_params* params /* NULL = defaults */, void* stream);
+/* The colour of the sun's light at the observer (above): the transmittance of the sun's own ray times sunIntensity, zeros when the
+ * planet hides the sun.  Pure host code, the host build of the functions the kernel marches with: an integrator sets
+ * Lights[0].Strength from it, so that the light reddens as the sky does.  params == NULL = the defaults.  CRYCHIC_E_INVALID_ARG for a
+ * NULL rgb or a parameter crychic_render_sky refuses. */
+int crychic_sky_sun_colour(const crychic_sky_params* params /* NULL = defaults */, float rgb[3]);
+
 /* ---- post-process anti-aliasing of the back buffer (extension) ------------------------------------------
  * The reference's framework smooths edges with 4x MSAA (Common/d3dApp.cpp:190-191, :367, :518), which does not compose with a
  * deferred G-buffer; this is the deferred path's stand-in: one pass over the finished RGBA8 frame, a separate call after the
