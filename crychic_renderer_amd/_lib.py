@@ -30,6 +30,7 @@ SKY_MAX_VIEW_STEPS, SKY_MAX_SUN_STEPS = 64, 32      # CRYCHIC_SKY_MAX_VIEW_STEPS
 SSR_MAX_STEPS = 64            # CRYCHIC_SSR_MAX_STEPS: the most samples crychic_ssr takes along a reflected ray
 DOF_MAX_RADIUS = 8            # CRYCHIC_DOF_MAX_RADIUS: the largest gather radius of crychic_dof, in pixels
 BLOOM_MAX_LEVELS = 8          # CRYCHIC_BLOOM_MAX_LEVELS: the most levels of crychic_bloom's pyramid
+GRADE_MAX_N = 33              # CRYCHIC_GRADE_MAX_N: the largest table of crychic_grade (33 x 33 x 33 entries: 143 748 bytes of LDS)
 
 
 class Light(C.Structure):
@@ -211,6 +212,27 @@ class BloomParams(C.Structure):
         return p
 
 
+class GradeParams(C.Structure):
+    """crychic_grade_params: an ASC CDL (slope, offset, power per channel) and a saturation, what crychic_grade_build_lut makes a
+    table of (extension); GradeParams.default() = crychic_grade_default_params -- the identity --, any field replaced by its keyword
+    (slope, offset and power: one number for all three channels, or three)."""
+    _fields_ = [("slope", C.c_float * 3), ("offset", C.c_float * 3), ("power", C.c_float * 3), ("saturation", C.c_float)]
+
+    @classmethod
+    def default(cls, slope=None, offset=None, power=None, saturation=None):
+        p = cls()
+        check(lib.crychic_grade_default_params(C.byref(p)))
+        for name, v in (("slope", slope), ("offset", offset), ("power", power)):
+            if v is not None:
+                getattr(p, name)[:] = [float(v)] * 3 if isinstance(v, (int, float)) else [float(c) for c in v]
+        if saturation is not None:
+            p.saturation = float(saturation)
+        return p
+
+
+assert C.sizeof(GradeParams) == 40
+
+
 TAA_RESET, TAA_NO_CLAMP = 1, 2               # CRYCHIC_TAA_RESET, CRYCHIC_TAA_NO_CLAMP
 
 
@@ -372,6 +394,10 @@ PROTOTYPES = {
     "crychic_bloom_pyramid": (_i, [_vp, _vp, _u32, _u32, _P(BloomParams), _vp, _sz, _vp]),
     "crychic_bloom_composite": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(BloomParams), _vp, _sz, _vp]),
     "crychic_bloom": (_i, [_vp, _vp, _vp, _u32, _u32, _P(BloomParams), _vp, _sz, _vp]),
+    "crychic_grade_default_params": (_i, [_P(GradeParams)]),
+    "crychic_grade_build_lut": (_i, [_P(GradeParams), _u32, _vp, _sz]),
+    "crychic_load_cube_lut": (_i, [C.c_char_p, _vp, _sz, _P(C.c_uint32)]),
+    "crychic_grade": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u32, _vp]),
     "crychic_taa_jitter": (_i, [_u32, _P(_f), _P(_f)]),
     "crychic_update_main_pass_cb_jittered": (_i, [_P(Camera), _u32, _u32, _vp, _vp, _f, _f, _P(PassConstants)]),
     "crychic_update_ssao_cb_jittered": (_i, [_P(Camera), _u32, _u32, _vp, _f, _f, _P(SsaoConstants)]),

@@ -24,6 +24,7 @@
 #include "ssr_core.hpp"
 #include "dof_core.hpp"
 #include "bloom_core.hpp"
+#include "grade_core.hpp"
 #include "taa_core.hpp"
 #include "taa_upscale_core.hpp"
 #include "motion_blur_core.hpp"
@@ -1201,6 +1202,68 @@ int crychic_bloom(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rg
     if (int rc = bind(ctx)) return rc;
     CRY_HIP(cry::launch_bloom_pyramid(in_rgba8_dev, W, H, q, workspace_dev, (hipStream_t)stream));
     CRY_HIP(cry::launch_bloom_composite(in_rgba8_dev, out_rgba8_dev, W, H, 0u, H, q, workspace_dev, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(CRYCHIC_GRADE_MAX_N == cry::kGradeMaxN && sizeof(crychic_grade_params) == 40 && sizeof(crychic_grade_params) == sizeof(cry::GradeParams),
+              "grade_core.hpp mirrors the ABI");
+static_assert(4u * CRYCHIC_GRADE_MAX_N * CRYCHIC_GRADE_MAX_N * CRYCHIC_GRADE_MAX_N <= cry::kGradeLdsPerCu, "the largest table fits one compute unit's LDS");
+
+int crychic_grade_default_params(crychic_grade_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    for (int c = 0; c < 3; ++c) { out->slope[c] = 1.0f; out->offset[c] = 0.0f; out->power[c] = 1.0f; }
+    out->saturation = 1.0f;
+    return 0;
+}
+
+namespace {
+int check_grade_n(uint32_t N)
+{
+    if (N < 2u || N > CRYCHIC_GRADE_MAX_N) return fail(CRYCHIC_E_INVALID_ARG, "colour grade table size %u outside 2 .. %d", N, CRYCHIC_GRADE_MAX_N);
+    return 0;
+}
+}  // namespace
+
+int crychic_grade_build_lut(const crychic_grade_params* params, uint32_t N, uint8_t* lut_rgba8, size_t capacityBytes)
+{
+    if (!lut_rgba8) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (int rc = check_grade_n(N)) return rc;
+    if (capacityBytes < (size_t)4u * N * N * N) return fail(CRYCHIC_E_INVALID_ARG, "the colour grade table has %zu bytes, size %u needs %zu", capacityBytes, N, (size_t)4u * N * N * N);
+    crychic_grade_params p;
+    crychic_grade_default_params(&p);
+    if (params) p = *params;
+    // !(lo <= v && v <= hi) refuses a NaN with everything else outside the range
+    for (int c = 0; c < 3; ++c) {
+        if (!(p.slope[c] >= 0.0f && p.slope[c] <= 16.0f)) return fail(CRYCHIC_E_INVALID_ARG, "colour grade slope[%d] %g outside 0 .. 16", c, (double)p.slope[c]);
+        if (!(p.offset[c] >= -4.0f && p.offset[c] <= 4.0f)) return fail(CRYCHIC_E_INVALID_ARG, "colour grade offset[%d] %g outside -4 .. 4", c, (double)p.offset[c]);
+        if (!(p.power[c] >= 0.0625f && p.power[c] <= 16.0f)) return fail(CRYCHIC_E_INVALID_ARG, "colour grade power[%d] %g outside 1/16 .. 16", c, (double)p.power[c]);
+    }
+    if (!(p.saturation >= 0.0f && p.saturation <= 4.0f)) return fail(CRYCHIC_E_INVALID_ARG, "colour grade saturation %g outside 0 .. 4", (double)p.saturation);
+    cry::GradeParams q;
+    memcpy(&q, &p, sizeof q);
+    cry::grade_build_lut(q, N, lut_rgba8);
+    return 0;
+}
+
+int crychic_grade(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                  const uint8_t* lut_rgba8_dev, uint32_t N, void* stream)
+{
+    // every argument is checked before the context is looked at: a refusal needs no device
+    if (!in_rgba8_dev || !out_rgba8_dev || !lut_rgba8_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
+    if (int rc = check_extent("frame", W, H, false, 0u)) return rc;
+    if (int rc = check_rows(kFrameRows, row0, rows, H)) return rc;
+    if (int rc = check_grade_n(N)) return rc;
+    const uintptr_t s = reinterpret_cast<uintptr_t>(in_rgba8_dev), d = reinterpret_cast<uintptr_t>(out_rgba8_dev), l = reinterpret_cast<uintptr_t>(lut_rgba8_dev);
+    if ((s | d) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "colour grade planes are not 4-byte aligned");
+    if (l & 3u) return fail(CRYCHIC_E_INVALID_ARG, "the colour grade table is not 4-byte aligned");
+    const size_t bytes = (size_t)W * H * 4u;
+    if (s != d && ranges_overlap(s, bytes, d, bytes))
+        return fail(CRYCHIC_E_INVALID_ARG, "the colour grade input and output planes overlap (in place takes the same address)");
+    if (ranges_overlap(l, (size_t)4u * N * N * N, d, bytes)) return fail(CRYCHIC_E_INVALID_ARG, "the colour grade table overlaps the output plane");
+    if (int rc = bind(ctx)) return rc;
+    CRY_HIP(cry::launch_grade(in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, lut_rgba8_dev, N, (hipStream_t)stream));
     return 0;
 }
 

@@ -3,7 +3,9 @@
 // or uncompressed 32-bit masks, decoded on the host to the R8G8B8A8 mip-0 image the G-buffer pass samples.
 // Block decompression follows the D3D10 BC1/BC3 definition with 5:6:5 -> 8:8:8 bit replication and round-to-nearest
 // integer interpolation ((2a + b + 1) / 3, (wa*a + wb*b + 3) / 7); D3D leaves the low bits of these to the hardware.
+#include <cmath>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <vector>
@@ -260,6 +262,110 @@ extern "C" int crychic_load_dds_rgba8_mips(const char* path, uint8_t* rgba8, siz
 {
     if (!mipLevels) return CRYCHIC_E_INVALID_ARG;
     return load_dds(path, rgba8, capacityBytes, width, height, mipLevels, true);
+}
+
+// ---- .cube colour grade tables (crychic_grade; the format and the refusals: include/crychic_hip.h) -----------------------------------
+namespace {
+
+constexpr size_t kCubeMaxLine = 1023;
+
+// The next line of `in` without its LF or CRLF into line[0 .. kCubeMaxLine], NUL-terminated.  1: a line; 0: the end of the file;
+// -1: a line longer than kCubeMaxLine bytes or one that holds a NUL byte (no text file does).
+int cube_next_line(std::streambuf* in, char* line)
+{
+    size_t n = 0;
+    bool any = false;
+    for (;;) {
+        const int c = in->sbumpc();
+        if (c == std::char_traits<char>::eof()) break;
+        any = true;
+        if (c == '\n') break;
+        if (c == 0 || n == kCubeMaxLine) return -1;
+        line[n++] = (char)c;
+    }
+    if (n > 0 && line[n - 1] == '\r') --n;
+    line[n] = 0;
+    return any ? 1 : 0;
+}
+
+// float_to_unorm8 of csrc/devmath.hpp, restated: this file is built without the device headers
+uint8_t cube_unorm8(float x) { return (uint8_t)(uint32_t)std::fmaf(std::fmin(std::fmax(x, 0.0f), 1.0f), 255.0f, 0.5f); }
+
+bool cube_blank(char c) { return c == ' ' || c == '\t'; }
+
+// Exactly `want` finite numbers, separated by blanks, fill the rest of the line at `s`.
+bool cube_numbers(const char* s, int want, float* v)
+{
+    for (int k = 0; k < want; ++k) {
+        while (cube_blank(*s)) ++s;
+        if (!*s) return false;
+        char* end = nullptr;
+        v[k] = std::strtof(s, &end);
+        if (end == s || (*end && !cube_blank(*end)) || !std::isfinite(v[k])) return false;
+        s = end;
+    }
+    while (cube_blank(*s)) ++s;
+    return *s == 0;
+}
+
+int load_cube(const char* path, uint8_t* lut, size_t capacityBytes, uint32_t* N)
+{
+    if (!path || !N) return CRYCHIC_E_INVALID_ARG;
+    std::ifstream file(path, std::ios::binary);
+    if (!file) return CRYCHIC_E_INVALID_ARG;
+    char line[kCubeMaxLine + 1];
+    uint32_t n = 0;
+    size_t rows = 0, want = 0;
+    for (;;) {
+        const int got = cube_next_line(file.rdbuf(), line);
+        if (got < 0) return CRYCHIC_E_INVALID_ARG;
+        if (got == 0) break;
+        const char* s = line;
+        while (cube_blank(*s)) ++s;
+        if (!*s || *s == '#') continue;
+        if ((*s >= 'A' && *s <= 'Z') || (*s >= 'a' && *s <= 'z') || *s == '_') {
+            size_t k = 0;
+            while (s[k] && !cube_blank(s[k])) ++k;
+            if (rows) return CRYCHIC_E_INVALID_ARG;                 // a keyword behind the first row of data
+            float v[3];
+            if (k == 5 && !std::memcmp(s, "TITLE", 5)) continue;
+            if (k == 11 && !std::memcmp(s, "LUT_3D_SIZE", 11)) {
+                if (n || !cube_numbers(s + k, 1, v)) return CRYCHIC_E_INVALID_ARG;
+                if (!(v[0] >= 2.0f && v[0] <= (float)CRYCHIC_GRADE_MAX_N) || v[0] != (float)(uint32_t)v[0]) return CRYCHIC_E_UNSUPPORTED;
+                n = (uint32_t)v[0];
+                want = (size_t)n * n * n;
+                continue;
+            }
+            const bool lo = k == 10 && !std::memcmp(s, "DOMAIN_MIN", 10), hi = k == 10 && !std::memcmp(s, "DOMAIN_MAX", 10);
+            if (lo || hi) {
+                if (!cube_numbers(s + k, 3, v)) return CRYCHIC_E_INVALID_ARG;
+                const float d = lo ? 0.0f : 1.0f;
+                if (v[0] != d || v[1] != d || v[2] != d) return CRYCHIC_E_UNSUPPORTED;
+                continue;
+            }
+            return CRYCHIC_E_UNSUPPORTED;                           // LUT_1D_SIZE and every keyword this loader does not know
+        }
+        float v[3];
+        if (!n || !cube_numbers(s, 3, v) || rows == want) return CRYCHIC_E_INVALID_ARG;
+        if (lut) {
+            if (capacityBytes < 4 * want) return CRYCHIC_E_INVALID_ARG;
+            uint8_t* e = lut + 4 * rows;
+            for (int c = 0; c < 3; ++c) e[c] = cube_unorm8(v[c]);
+            e[3] = 255u;
+        }
+        ++rows;
+    }
+    if (!n || rows != want) return CRYCHIC_E_INVALID_ARG;
+    if (lut && capacityBytes < 4 * want) return CRYCHIC_E_INVALID_ARG;
+    *N = n;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int crychic_load_cube_lut(const char* path, uint8_t* lut_rgba8, size_t capacityBytes, uint32_t* N)
+{
+    return load_cube(path, lut_rgba8, capacityBytes, N);
 }
 
 // Present stand-in: the reference hands the back buffer to the swap chain (CRYCHIC.cpp:294-297); a

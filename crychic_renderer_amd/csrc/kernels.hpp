@@ -166,6 +166,12 @@ hipError_t launch_motion_blur_velocity(const float* invViewProj, const float* cu
 hipError_t launch_motion_blur_gather(const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const MotionBlurParams& p,
                                      const void* workspace, hipStream_t stream);
 
+// grade.hip: rows [row0, row0 + rows) of the W x H RGBA8 frame `out`: `in` through the N x N x N table `lut` of device memory
+// (grade_core.hpp); in == out is in place.  One launch on `stream` with 4 N^3 bytes of LDS, none for rows == 0; a launch the runtime
+// refuses comes back as its error code.  The caller has checked the pointers, their alignment and overlap, the sizes, the rows and N.
+hipError_t launch_grade(const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const uint8_t* lut, uint32_t N,
+                        hipStream_t stream);
+
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
 struct Texture;

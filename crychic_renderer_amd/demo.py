@@ -7,6 +7,7 @@
                                    [--bloom [--bloom-threshold N] [--bloom-intensity N] [--bloom-levels N]]
                                    [--taa [--taa-frames N]] [--taa-upscale WxH [--taa-frames N]]
                                    [--motion-blur [--motion-blur-shutter N] [--motion-blur-samples N] [--motion-blur-pan DX]]
+                                   [--grade-cube FILE.cube | --grade-slope R,G,B --grade-offset R,G,B --grade-power R,G,B --grade-saturation X]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
 (HIP rasteriser), SSAO + blur, deferred lighting + sky -- and writes it as PPM (the headless stand-in for Present).
@@ -52,7 +53,11 @@ drawn as if the camera had stood --motion-blur-pan world units (default 0.5) fur
 velocity that gives each pixel through its depth; --motion-blur-shutter (exposure in 1/256 of the frame interval, default 128, at
 most 256) and --motion-blur-samples (2, 4, 8, 16 or 32, default 8) set its parameters.  With --taa the last frame is the one that moved.
 --decals: deferred decals between the G-buffer pass and the lighting pass (Crychic.set_decals / apply_decals: crychic_apply_decals): a
-glossy puddle with a dent normal map on the floor and a painted ring on the face of a box."""
+glossy puddle with a dent normal map on the floor and a painted ring on the face of a box.
+--grade-cube FILE.cube, or any of --grade-slope, --grade-offset, --grade-power (R,G,B or one number for all three) and
+--grade-saturation: the colour grade (Crychic.colourGrade: crychic_grade behind --bloom, in front of --aa): the frame's look through a
+3D table, loaded from an Adobe / Resolve .cube file or built from an ASC CDL with a saturation at 33 x 33 x 33 entries.
+--grade-saturation 0 writes a grey frame."""
 import argparse
 import ctypes as C
 import math
@@ -112,7 +117,23 @@ def main():
     ap.add_argument("--motion-blur-samples", type=int, default=None, metavar="N", help="samples along the velocity: 2, 4, 8, 16 or 32 (default 8; needs --motion-blur)")
     ap.add_argument("--motion-blur-pan", type=float, default=None, metavar="DX", help="the previous camera's displacement along +x in world units (default 0.5; "
                                                                                       "needs --motion-blur)")
+    ap.add_argument("--grade-cube", default="", metavar="FILE.cube", help="colour grade through the 3D table of a .cube file, behind the bloom and in front of --aa")
+    ap.add_argument("--grade-slope", default="", metavar="R,G,B", help="colour grade: the ASC CDL's slope, 0 .. 16 (default 1)")
+    ap.add_argument("--grade-offset", default="", metavar="R,G,B", help="colour grade: the ASC CDL's offset, -4 .. 4 (default 0)")
+    ap.add_argument("--grade-power", default="", metavar="R,G,B", help="colour grade: the ASC CDL's power, 1/16 .. 16 (default 1)")
+    ap.add_argument("--grade-saturation", type=float, default=None, metavar="X", help="colour grade: saturation, 0 .. 4 (default 1)")
     a = ap.parse_args()
+    grade = {}
+    for name, text in (("slope", a.grade_slope), ("offset", a.grade_offset), ("power", a.grade_power)):
+        if text:
+            v = [float(x) for x in text.split(",")]
+            if len(v) not in (1, 3):
+                ap.error("--grade-%s takes R,G,B or one number" % name)
+            grade[name] = v * 3 if len(v) == 1 else v
+    if a.grade_saturation is not None:
+        grade["saturation"] = a.grade_saturation
+    if a.grade_cube and grade:
+        ap.error("--grade-cube does not go with --grade-slope, --grade-offset, --grade-power or --grade-saturation")
     if (a.motion_blur_shutter is not None or a.motion_blur_samples is not None or a.motion_blur_pan is not None) and not a.motion_blur:
         ap.error("--motion-blur-shutter, --motion-blur-samples and --motion-blur-pan need --motion-blur")
     if a.taa_frames is not None and not ((a.taa or a.taa_upscale) and a.taa_frames >= 1):
@@ -238,6 +259,11 @@ def main():
         app.depthOfField = DofParams.default(focus=a.dof_focus, aperture=a.dof_aperture, radius=a.dof_radius)
     if a.bloom:
         app.bloom = BloomParams.default(threshold=a.bloom_threshold, intensity=a.bloom_intensity, levels=a.bloom_levels)
+    if a.grade_cube:
+        app.colourGrade = a.grade_cube
+    elif grade:
+        from ._lib import GradeParams
+        app.colourGrade = GradeParams.default(**grade)
     if a.aa:
         app.antiAliasing = True
     prev_view_proj = None
@@ -273,8 +299,9 @@ def main():
     img = np.ascontiguousarray(app.final_frame().cpu().numpy())
     check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, WO, HO))
     chain = (("ssr", "screen-space reflections"), ("fog", "fog"), ("temporalAA", "temporal anti-aliasing"), ("temporalUpscale", "temporal upsampling"), ("depthOfField", "depth of field"), ("motionBlur", "motion blur"),
-             ("bloom", "bloom"), ("antiAliasing", "anti-aliased"))                   # Draw()'s order
-    print("wrote %s (%dx%d%s) on %s" % (a.out, WO, HO, "".join(", " + text for switch, text in chain if getattr(app, switch)), ctx.device_name))
+             ("bloom", "bloom"), ("colourGrade", "colour grade"), ("antiAliasing", "anti-aliased"))                   # Draw()'s order
+    print("wrote %s (%dx%d%s) on %s" % (a.out, WO, HO, "".join(", " + text for switch, text in chain if getattr(app, switch) is not None and getattr(app, switch) is not False),
+                                        ctx.device_name))
 
 
 if __name__ == "__main__":

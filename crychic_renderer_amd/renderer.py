@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (AAParams, CrychicError, FogParams, SkyParams, SsrParams, DofParams, BloomParams, TaaParams, TaaUpscaleParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, FogParams, SkyParams, SsrParams, DofParams, BloomParams, GradeParams, TaaParams, TaaUpscaleParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -249,6 +249,9 @@ class Crychic:
         self._motionBlur = None      # motionBlur, extension: None | True | MotionBlurParams -- Draw() of a whole frame runs crychic_motion_blur into mBackBufferMB
         self.mBackBufferMB = None    # the frame behind the motion blur, allocated by the first motion_blur() that needs it
         self.mMotionBlurWorkspace = None     # the velocity and tile planes: crychic_motion_blur_workspace_bytes of the frame, with the first motion_blur()
+        self._colourGrade = None     # colourGrade, extension: None | GradeParams | (N, N, N, 4) uint8 array | path of a .cube file -- Draw() of a whole frame runs crychic_grade into mBackBufferGrade
+        self.mBackBufferGrade = None  # the graded frame, allocated by the first colour_grade() that needs it
+        self.mGradeLut = None        # the table colourGrade was given, built or loaded and uploaded once by the assignment: an (N, N, N, 4) uint8 device tensor, [blue][green][red]
         self.mDecals, self.mDecalCount = None, 0                             # set_decals, extension: the device array of Decal structs
         self._decalTextures, self._decalTextureCount, self._decalKeep = None, 0, []     # the host texture table and the chains it points into
 
@@ -262,9 +265,12 @@ class Crychic:
             if name == "_temporalUpscale" and value and not self._temporalUpscale:
                 self._taaUpscaleReset = True
             setattr(self, name, value)
-            self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA or self._motionBlur or self._ssr
-                              or self._temporalUpscale)
+            self._update_post()
         return property(get, put)
+
+    def _update_post(self):
+        self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA or self._motionBlur or self._ssr
+                          or self._temporalUpscale or self._colourGrade is not None)
 
     antiAliasing = _post_switch("_antiAliasing")
     fog = _post_switch("_fog")
@@ -274,6 +280,41 @@ class Crychic:
     temporalAA = _post_switch("_temporalAA")
     motionBlur = _post_switch("_motionBlur")
     temporalUpscale = _post_switch("_temporalUpscale")
+
+    @property
+    def colourGrade(self):
+        return self._colourGrade
+
+    @colourGrade.setter
+    def colourGrade(self, value):
+        """None | a GradeParams (crychic_grade_build_lut at GRADE_MAX_N) | an (N, N, N, 4) uint8 array or tensor indexed [blue][green][red]
+        | the path of a .cube file (crychic_load_cube_lut): the table is built or loaded and uploaded here, once."""
+        self.mGradeLut = None if value is None else self.grade_lut(value)
+        self._colourGrade = value
+        self._update_post()
+
+    def grade_lut(self, value):
+        """The (N, N, N, 4) uint8 device tensor of a table given as colourGrade takes it."""
+        if isinstance(value, GradeParams):
+            N = _lib.GRADE_MAX_N
+            buf = (C.c_uint8 * (4 * N ** 3))()
+            check(lib.crychic_grade_build_lut(C.byref(value), N, buf, len(buf)))
+        elif isinstance(value, (str, bytes)) or hasattr(value, "__fspath__"):
+            import os
+            path = os.fsencode(value)
+            n = C.c_uint32()
+            buf = (C.c_uint8 * (4 * _lib.GRADE_MAX_N ** 3))()
+            rc = lib.crychic_load_cube_lut(path, buf, len(buf), C.byref(n))
+            if rc < 0:
+                raise CrychicError(rc, "crychic_load_cube_lut refuses %r" % (value,))
+            N = int(n.value)
+        else:
+            t = value if isinstance(value, torch.Tensor) else torch.tensor(value)      # a copy: the caller's array may be read-only
+            if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 4 or not (t.shape[0] == t.shape[1] == t.shape[2]) \
+                    or not 2 <= t.shape[0] <= _lib.GRADE_MAX_N:
+                raise CrychicError(-1, "a colour grade table is an (N, N, N, 4) uint8 array, 2 <= N <= %d" % _lib.GRADE_MAX_N)
+            return t.to(self.ctx.device).contiguous().clone()
+        return torch.frombuffer(buf, dtype=torch.uint8, count=4 * N ** 3).reshape(N, N, N, 4).to(self.ctx.device)
     del _post_switch
 
     def set_gbuffer_formats(self, formats):
@@ -336,7 +377,7 @@ class Crychic:
         the lighting pass in `parts` row ranges that travel while the next is lit (sharding.StripExchange.draw).
         With a switch of the passes behind the lighting pass set (extensions; True, or the pass's parameter struct): a whole frame,
         then the set passes in the order
-            lighting -> ssr -> fog (in place on the frame it is handed) -> temporalAA -> depthOfField -> motionBlur -> bloom -> antiAliasing,
+            lighting -> ssr -> fog (in place on the frame it is handed) -> temporalAA -> depthOfField -> motionBlur -> bloom -> colourGrade -> antiAliasing,
         each but the fog from the buffer of the nearest set stage in front of it that writes one of its own (mBackBuffer if there is
         none) into its own mBackBuffer*; final_frame() is the last one.  The temporal pass and the motion blur take the matrices of
         set_frame_view_proj (never called: a still camera); the first frame after temporalAA was turned on is a RESET frame.  A strip
@@ -401,7 +442,8 @@ class Crychic:
     def _draw_post_chain(self, row0, rows, shared):
         """Draw() with a switch set: the lighting frame, then one walk along the chain with the frame each stage reads."""
         if shared is not None or row0 != 0 or (rows is not None and rows != self.mClientHeight):
-            what = next(s for s in ("bloom", "motionBlur", "depthOfField", "temporalAA", "fog", "antiAliasing", "ssr", "temporalUpscale") if getattr(self, s))
+            what = next(s for s in ("bloom", "motionBlur", "depthOfField", "temporalAA", "fog", "antiAliasing", "ssr", "temporalUpscale", "colourGrade")
+                        if (getattr(self, s) is not None if s == "colourGrade" else getattr(self, s)))
             raise CrychicError(-1, "%s is set: Draw() takes the whole frame on one GPU (the pass is not sharded and does not run behind the "
                                "exchange)" % what)
         if self._temporalUpscale:
@@ -438,12 +480,14 @@ class Crychic:
             frame = self.motion_blur(cur, prev, src=frame, params=params(self._motionBlur, MotionBlurParams))
         if self._bloom:
             frame = self.apply_bloom(src=frame, params=params(self._bloom, BloomParams))
+        if self._colourGrade is not None:
+            frame = self.colour_grade(src=frame)
         if self._antiAliasing:
             self.antialias(src=frame, params=params(self._antiAliasing, AAParams))
 
     def final_frame(self):
         """The tensor a Draw() with the switches as they are leaves the finished frame in: the last set stage's buffer."""
-        for switch, name in ((self._antiAliasing, "mBackBufferAA"), (self._bloom, "mBackBufferBloom"), (self._motionBlur, "mBackBufferMB"),
+        for switch, name in ((self._antiAliasing, "mBackBufferAA"), (self._colourGrade is not None, "mBackBufferGrade"), (self._bloom, "mBackBufferBloom"), (self._motionBlur, "mBackBufferMB"),
                              (self._depthOfField, "mBackBufferDoF"), (self._temporalAA, "mBackBufferTAA"), (self._temporalUpscale, "mBackBufferUpscaled")):
             if switch:
                 return getattr(self, name)
@@ -565,6 +609,19 @@ class Crychic:
             self.mBloomWorkspace = torch.zeros((need,), dtype=torch.uint8, device=src.device)
         check(lib.crychic_bloom(self.ctx.handle, _ptr(src), _ptr(out), W, H, None if params is None else C.byref(params),
                                 _ptr(self.mBloomWorkspace), need, _stream(self.ctx.device)))
+        return out
+
+    def colour_grade(self, src=None, out=None, lut=None, row0=0, rows=None):
+        """crychic_grade on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferGrade, allocated on first use)
+        from `src` (default: mBackBuffer), both (H, W, 4) uint8 tensors of one shape (the frame's, or the display's behind
+        temporalUpscale), through the table `lut` (default: mGradeLut, what colourGrade was given; otherwise anything colourGrade
+        takes, uploaded for this call).  `out` may be `src` itself (in place) and must not overlap it otherwise.  Returns `out`."""
+        src, out, H, W = self._pass_frames("colour_grade", "mBackBufferGrade", src, out, any_shape=True)
+        table = self.mGradeLut if lut is None else self.grade_lut(lut)
+        if table is None:
+            raise CrychicError(-1, "colour_grade needs a table: set colourGrade or pass lut")
+        check(lib.crychic_grade(self.ctx.handle, _ptr(src), _ptr(out), W, H, int(row0), int(H - row0 if rows is None else rows), _ptr(table),
+                                int(table.shape[0]), _stream(self.ctx.device)))
         return out
 
     def depth_of_field(self, src=None, out=None, row0=0, rows=None, params=None):

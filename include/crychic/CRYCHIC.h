@@ -168,6 +168,7 @@ public:
         if (mDepthOfField) mBackBufferDoF = FramePlane();
         if (mScreenSpaceReflections) mBackBufferSSR = FramePlane();
         if (mBloom) AllocateBloom();
+        if (mColourGrade) mBackBufferGrade = FinalPlane();
         if (mTemporalAA) AllocateTemporalAA();                                                      // new history planes: the next frame is a reset frame
         if (mMotionBlur) AllocateMotionBlur();                                                      // the next frame counts as the first: no previous camera
         if (mTemporalUpscale) AllocateTemporalUpscale();                                            // the display size stays; the next frame is a reset frame
@@ -212,10 +213,10 @@ public:
 
     void Draw(const GameTimer&)  // CRYCHIC.cpp:172-306, deferred branch
     {
-        if ((!mWholeFrame || mComm) && (mAntiAliasing || mFog || mDepthOfField || mBloom || mTemporalAA || mMotionBlur || mScreenSpaceReflections || mTemporalUpscale)) {
+        if ((!mWholeFrame || mComm) && (mAntiAliasing || mFog || mDepthOfField || mBloom || mTemporalAA || mMotionBlur || mScreenSpaceReflections || mTemporalUpscale || mColourGrade)) {
             const char* pass = mAntiAliasing ? "anti-aliasing" : mFog ? "fog" : mDepthOfField ? "depth of field" : mBloom ? "bloom"
                              : mTemporalAA ? "temporal anti-aliasing" : mMotionBlur ? "motion blur" : mScreenSpaceReflections ? "screen-space reflections"
-                             : "temporal upsampling";
+                             : mTemporalUpscale ? "temporal upsampling" : "colour grade";
             throw CrychicException(CRYCHIC_E_INVALID_ARG, std::string("CRYCHIC::Draw (") + pass + " takes the whole frame on one GPU: no SetStrip / JoinNode)",
                                    __FILE__, __LINE__);
         }
@@ -346,6 +347,11 @@ public:
                                                mBloomWorkspace->Data(), mBloomWorkspace->Bytes(), mCommandList->Stream()));
             frame = bytes(mBackBufferBloom);
         }
+        if (mColourGrade) {                     // the look, in front of the anti-aliasing: its luma test sees graded colours
+            CrychicThrowIfFailed(crychic_grade(md3dDevice->Ctx(), frame, bytes(mBackBufferGrade), fw, fh, 0, fh, bytes(mGradeLut), mGradeN,
+                                               mCommandList->Stream()));
+            frame = bytes(mBackBufferGrade);
+        }
         if (mAntiAliasing)
             CrychicThrowIfFailed(crychic_antialias(md3dDevice->Ctx(), frame, bytes(mBackBufferAA), fw, fh, 0, fh,
                                                    &mAAParams, mCommandList->Stream()));
@@ -355,9 +361,9 @@ public:
     }
 
     // ---- the passes behind the lighting pass (extensions) -----------------------------------------------------------------------------
-    // Eight switches (the temporal upsampling, below, stands at the temporal anti-aliasing's place), all off by default (then nothing changes).  With any of them on, Draw takes a whole frame on one GPU -- SetStrip /
+    // Nine switches (the temporal upsampling, below, stands at the temporal anti-aliasing's place), all off by default (then nothing changes).  With any of them on, Draw takes a whole frame on one GPU -- SetStrip /
     // JoinNode make it throw, the passes are not sharded -- and issues those that are on behind the lighting pass in the order
-    //     lighting -> screen-space reflections -> fog (in place) -> temporal anti-aliasing -> depth of field -> motion blur -> bloom -> anti-aliasing.
+    //     lighting -> screen-space reflections -> fog (in place) -> temporal anti-aliasing -> depth of field -> motion blur -> bloom -> colour grade -> anti-aliasing.
     // The fog works in place on the frame it is handed: the reflections' buffer if they are on, the back buffer if not.  Every other
     // stage reads the buffer of the nearest stage in front of it that is on and writes one (the back buffer if there is none) and
     // writes a buffer of its own, which exists while the stage is on and which OnResize re-creates; Present writes the last one.
@@ -468,6 +474,44 @@ public:
     bool Bloom() const { return mBloom; }
     ID3D12Resource* BloomBackBuffer() { return mBackBufferBloom.get(); }
 
+    // ---- colour grade -------------------------------------------------------------------------------------------------------------------
+    // The frame's look through a 3D table, between the bloom and the anti-aliasing (include/crychic_hip.h crychic_grade): the table of
+    // an ASC CDL with a saturation, built at CRYCHIC_GRADE_MAX_N (SetColourGrade), a caller's table of N x N x N entries
+    // (SetColourGradeLut) or a .cube file (LoadColourGradeLut).  The setter builds or loads the table and uploads it once; Draw issues
+    // crychic_grade alone.  nullptr turns the stage off; what is refused leaves it as it was.
+    void SetColourGrade(const crychic_grade_params* p)
+    {
+        if (!p) { SetColourGradeLut(nullptr, 0); return; }
+        std::vector<uint8_t> lut((size_t)4 * CRYCHIC_GRADE_MAX_N * CRYCHIC_GRADE_MAX_N * CRYCHIC_GRADE_MAX_N);
+        CrychicThrowIfFailed(crychic_grade_build_lut(p, CRYCHIC_GRADE_MAX_N, lut.data(), lut.size()));
+        SetColourGradeLut(lut.data(), CRYCHIC_GRADE_MAX_N);
+    }
+    void SetColourGradeLut(const uint8_t* lut, uint32_t N)
+    {
+        if (lut && (N < 2u || N > CRYCHIC_GRADE_MAX_N))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetColourGradeLut (N 2 .. 33)", __FILE__, __LINE__);
+        mCommandList->Flush();                                  // a frame in flight may still read the table and write the buffer
+        mColourGrade = lut != nullptr;
+        if (!lut) { mGradeLut.reset(); mBackBufferGrade.reset(); mGradeN = 0; return; }
+        const size_t n = (size_t)4 * N * N * N;
+        mGradeLut = std::make_unique<ID3D12Resource>(n, ID3D12Resource::DEFAULT_HEAP);
+        mGradeLut->Upload(lut, n, mCommandList->Stream());
+        mGradeN = N;
+        mBackBufferGrade = FinalPlane();
+        mCommandList->Flush();                                  // the caller's table may go once this returns
+    }
+    void LoadColourGradeLut(const char* path)
+    {
+        std::vector<uint8_t> lut((size_t)4 * CRYCHIC_GRADE_MAX_N * CRYCHIC_GRADE_MAX_N * CRYCHIC_GRADE_MAX_N);
+        uint32_t N = 0;
+        const int rc = crychic_load_cube_lut(path, lut.data(), lut.size(), &N);
+        if (rc < 0) throw CrychicException(rc, "CRYCHIC::LoadColourGradeLut (crychic_load_cube_lut refuses the file)", __FILE__, __LINE__);
+        SetColourGradeLut(lut.data(), N);
+    }
+    bool ColourGrade() const { return mColourGrade; }
+    uint32_t ColourGradeSize() const { return mGradeN; }
+    ID3D12Resource* ColourGradeBackBuffer() { return mBackBufferGrade.get(); }
+
     // ---- temporal anti-aliasing ---------------------------------------------------------------------------------------------------------
     // Jittered frames blended into a reprojected history (include/crychic_hip.h crychic_taa).  On: Update shifts the projection of the
     // main pass and SSAO constants by the frame's sub-pixel offset (crychic_taa_jitter of a running frame index) and keeps the
@@ -516,6 +560,7 @@ public:
         if (was != on || resized) {                             // the stages behind it change their size with it
             if (mAntiAliasing) mBackBufferAA = FinalPlane();
             if (mBloom) AllocateBloom();
+            if (mColourGrade) mBackBufferGrade = FinalPlane();
         }
     }
     bool TemporalUpscale() const { return mTemporalUpscale; }
@@ -1396,6 +1441,10 @@ private:
         mBloomWorkspace = std::make_unique<ID3D12Resource>(crychic_bloom_workspace_bytes(FinalWidth(), FinalHeight(), CRYCHIC_BLOOM_MAX_LEVELS),
                                                            ID3D12Resource::DEFAULT_HEAP);
     }
+    bool mColourGrade = false;                // SetColourGrade / SetColourGradeLut / LoadColourGradeLut
+    uint32_t mGradeN = 0;
+    std::unique_ptr<ID3D12Resource> mGradeLut;         // the table, uploaded by the setter
+    std::unique_ptr<ID3D12Resource> mBackBufferGrade;  // the graded frame, while mColourGrade
     bool mTemporalAA = false;                 // SetTemporalAA
     crychic_taa_params mTaaParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferTAA;    // the resolved frame, while mTemporalAA
@@ -1463,7 +1512,7 @@ private:
     }
     ID3D12Resource* FinalFrame() const           // where Draw leaves the finished frame: the buffer of the last stage that is on
     {
-        return (mAntiAliasing ? mBackBufferAA : mBloom ? mBackBufferBloom : mMotionBlur ? mBackBufferMB : mDepthOfField ? mBackBufferDoF
+        return (mAntiAliasing ? mBackBufferAA : mColourGrade ? mBackBufferGrade : mBloom ? mBackBufferBloom : mMotionBlur ? mBackBufferMB : mDepthOfField ? mBackBufferDoF
                 : mTemporalAA ? mBackBufferTAA : mTemporalUpscale ? mBackBufferUpscaled : mScreenSpaceReflections ? mBackBufferSSR : mBackBuffer).get();
     }
     std::unique_ptr<ID3D12Resource> mDepthStencilBuffer, mBackBuffer, mCubeMap;

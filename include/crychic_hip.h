@@ -1558,6 +1558,70 @@ int crychic_motion_blur(crychic_ctx* ctx, const crychic_pass_constants* cb, cons
                         const crychic_motion_blur_params* params /* NULL = defaults */, void* workspace_dev, size_t workspace_bytes,
                         void* stream);
 
+/* ---- colour grading: a 3D look-up table, tetrahedral interpolation (extension) ----------------------------
+ * The last look of the finished RGBA8 frame: every texel's (R, G, B) is looked up in a table of N x N x N colours.  A separate call
+ * behind the bloom and in front of the anti-aliasing; every texel is independent, so the pass takes row ranges and may run in place.
+ * A build definition: nothing of it is the reference's.  The device, a host build and the checker (tests/grade_ref) agree on every
+ * byte.
+ *
+ * The table.  2 <= N <= CRYCHIC_GRADE_MAX_N; N^3 entries of 4 bytes; entry (i, j, k) -- i along red, j along green, k along blue,
+ * the order of a .cube file -- lies at byte 4 (i + N (j + N k)).  Its bytes are R, G, B and one byte that is never looked at.
+ *
+ * Applying it.  All arithmetic is unsigned 32-bit, every division is the exact floor.  For a frame texel (R, G, B, A) and each of
+ * its three channel values v:  p = v (N - 1);  i = min(p / 255, N - 2);  f = p - 255 i.  So 0 <= f <= 255, and v = 255 gives
+ * i = N - 2 with f = 255: the last cell, at its far end.  Order the three fractions f1 >= f2 >= f3 and call their axes a1, a2, a3.
+ * With V0 = (iR, iG, iB), V1 = V0 + e(a1), V2 = V1 + e(a2), V3 = V0 + (1, 1, 1) and L[V] the entry at V, for c = R, G, B:
+ *   out_c = ((255 - f1) L[V0]_c + (f1 - f2) L[V1]_c + (f2 - f3) L[V2]_c + f3 L[V3]_c + 127) / 255
+ * (the four weights add up to 255, so the numerator is at most 255 * 255 + 127 = 65 152), and the output's alpha is A.  Where two
+ * fractions are equal the vertex that depends on their order has the weight 0: every order gives the same byte, and an
+ * implementation may break ties as it likes.  Every vertex lies inside the table because i <= N - 2.
+ * Known answers: a table with L(i, j, k) = (255 i, 255 j, 255 k) / (N - 1) leaves the frame as it is when N - 1 divides 255; a
+ * table of N = 2 that is white at (1, 1, 1) alone gives min(R, G, B) in every channel (trilinear interpolation would give
+ * R G B / 255^2).
+ *
+ * crychic_grade: rows [row0, row0 + rows) of out_rgba8_dev from the same rows of in_rgba8_dev and the table lut_rgba8_dev (device
+ * memory, 4 N^3 bytes, only read), and no other byte; rows == 0 launches nothing.  in == out exactly is allowed (in place); any
+ * other overlap is refused.  One launch on `stream`: each workgroup copies the table into 4 N^3 bytes of LDS (143 748 bytes at
+ * N = 33, which the 160 KiB of a gfx950 compute unit hold) and walks the row range with a grid stride.  The planes need 4-byte
+ * alignment only; where both are 16-byte aligned alike the pass moves 16 bytes per lane.  No allocation, no synchronisation, no host
+ * read-back; capturable into a graph.  CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and before
+ * anything is enqueued: a NULL plane or table; a plane or table that is not 4-byte aligned; W or H of 0; a row range outside the
+ * frame; N outside 2 .. CRYCHIC_GRADE_MAX_N; in and out overlapping without being equal; the table overlapping out.  More than 2^28
+ * pixels: CRYCHIC_E_UNSUPPORTED.
+ *
+ * crychic_grade_build_lut (pure host code): the table of size N of an ASC CDL with a saturation, into lut_rgba8 (capacityBytes
+ * >= 4 N^3; the fourth byte of every entry is 255).  Parameters: slope (default 1; 0 .. 16), offset (default 0; -4 .. 4), power
+ * (default 1; 1/16 .. 16) per channel, saturation (default 1; 0 .. 4).  In binary32 with the primitives of csrc/devmath.hpp, fused
+ * exactly where fma is written, for entry (iR, iG, iB) and c = R, G, B:
+ *   x_c = divf(i_c, N - 1);  y_c = min(max(fma(x_c, slope_c, offset_c), 0), 1);  z_c = det_pow(y_c, power_c), and z_c = y_c where
+ *   power_c == 1;  luma = fma(0.0722, z_B, fma(0.7152, z_G, 0.2126 z_R));  w_c = fma(saturation, z_c - luma, luma), and w_c = z_c
+ *   where saturation == 1;  byte_c = float_to_unorm8(w_c) = (uint32_t) fma(min(max(w_c, 0), 1), 255, 0.5).
+ * At y_c = 0 det_pow gives 0 whatever the power: black stays black.  The two exceptions make the defaults the identity table
+ * unorm8(i / (N - 1)) byte for byte.  CRYCHIC_E_INVALID_ARG: a NULL pointer, N outside its range, a capacity below 4 N^3, a
+ * parameter that is not finite or outside its range.
+ *
+ * crychic_load_cube_lut (pure host code): the table of an Adobe / Resolve .cube text file into lut_rgba8, *N its size; with
+ * lut_rgba8 == NULL only *N is written.  Lines end in LF or CRLF and are at most 1023 bytes long.  Accepted: empty lines, lines
+ * starting with '#', TITLE (ignored), DOMAIN_MIN 0 0 0, DOMAIN_MAX 1 1 1, LUT_3D_SIZE N, in any order in front of the data; then
+ * exactly N^3 rows of three numbers, red fastest, each stored as float_to_unorm8 of its binary32 value (the fourth byte 255).
+ * CRYCHIC_E_UNSUPPORTED: LUT_1D_SIZE, any other keyword, a domain other than 0 .. 1, N outside 2 .. CRYCHIC_GRADE_MAX_N.
+ * CRYCHIC_E_INVALID_ARG: a NULL path or N, a file that cannot be read, no LUT_3D_SIZE in front of the data or two of them, too few
+ * or too many rows, a number that does not parse or is not finite, a row of other than three numbers, a keyword behind the first row,
+ * a line longer than 1023 bytes or holding a NUL byte, a capacity below 4 N^3.  A line that starts with a letter is a keyword line: a
+ * row that starts with "nan" or "inf" is refused as an unknown keyword. */
+#define CRYCHIC_GRADE_MAX_N 33
+typedef struct crychic_grade_params {
+    float slope[3];
+    float offset[3];
+    float power[3];
+    float saturation;
+} crychic_grade_params;   /* 40 bytes */
+int crychic_grade_default_params(crychic_grade_params* out);
+int crychic_grade_build_lut(const crychic_grade_params* params /* NULL = defaults */, uint32_t N, uint8_t* lut_rgba8, size_t capacityBytes);
+int crychic_load_cube_lut(const char* path, uint8_t* lut_rgba8, size_t capacityBytes, uint32_t* N);
+int crychic_grade(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0,
+                  uint32_t rows, const uint8_t* lut_rgba8_dev, uint32_t N, void* stream);
+
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
  * of 2 rows (half-res alignment); the last rank takes the remainder. */
