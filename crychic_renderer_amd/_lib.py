@@ -160,6 +160,28 @@ class SsrParams(C.Structure):
         return p
 
 
+SSR_GLOSS_MAX_LEVELS = 8       # CRYCHIC_SSR_GLOSS_MAX_LEVELS: the most levels, the frame included, of crychic_ssr_pyramid
+
+
+class SsrGlossParams(C.Structure):
+    """crychic_ssr_gloss_params: the cone of crychic_ssr_glossy (extension); SsrGlossParams.default() = crychic_ssr_gloss_default_params."""
+    _fields_ = [("coneScale", C.c_float), ("levels", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def default(cls, **fields):
+        p = cls()
+        check(lib.crychic_ssr_gloss_default_params(C.byref(p)))
+        for k, v in fields.items():
+            if k == "reserved":
+                p.reserved = (C.c_uint32 * 2)(*[int(c) for c in v])
+            else:
+                setattr(p, k, int(v) if k == "levels" else float(v))
+        return p
+
+
+assert C.sizeof(SsrGlossParams) == 16
+
+
 class DofParams(C.Structure):
     """crychic_dof_params: the knobs of crychic_dof (extension); DofParams.default() = crychic_dof_default_params, with focus, aperture
     and radius as short names of focusDistance, aperture and maxRadius."""
@@ -384,6 +406,12 @@ PROTOTYPES = {
     "crychic_fog": (_i, [_vp, _P(PassConstants), _vp, _P(_vp), _u32, _vp, _vp, _u32, _u32, _u32, _u32, _P(FogParams), _vp]),
     "crychic_ssr_default_params": (_i, [_P(SsrParams)]),
     "crychic_ssr": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _P(SsrParams), _vp]),
+    "crychic_ssr_gloss_default_params": (_i, [_P(SsrGlossParams)]),
+    "crychic_ssr_pyramid_bytes": (_sz, [_u32, _u32, _u32]),
+    "crychic_ssr_pyramid_offset": (_sz, [_u32, _u32, _u32, _u32]),
+    "crychic_ssr_pyramid": (_i, [_vp, _vp, _u32, _u32, _u32, _vp, _sz, _vp]),
+    "crychic_ssr_glossy": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _u32, _u32, _u32, _u32, _u32, _P(SsrParams),
+                                _P(SsrGlossParams), _vp]),
     "crychic_dof_default_params": (_i, [_P(DofParams)]),
     "crychic_dof": (_i, [_vp, _P(PassConstants), _vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(DofParams), _vp]),
     "crychic_decal_from_box": (_i, [_P(_f), _u32, _u32, _f, _f, _P(Decal)]),

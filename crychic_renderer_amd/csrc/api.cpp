@@ -22,6 +22,7 @@
 #include "post_aa_core.hpp"
 #include "fog_core.hpp"
 #include "ssr_core.hpp"
+#include "ssr_gloss_core.hpp"
 #include "dof_core.hpp"
 #include "bloom_core.hpp"
 #include "grade_core.hpp"
@@ -905,11 +906,14 @@ int crychic_ssr_default_params(crychic_ssr_params* out)
     return 0;
 }
 
-int crychic_ssr(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev, const float* g2_dev,
-                const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
-                uint32_t flags, const crychic_ssr_params* params, void* stream)
+namespace {
+
+// What crychic_ssr and crychic_ssr_glossy check alike, before the context is looked at: a refusal needs no device.  Fills `q` with the
+// parameters in force.
+int ssr_check(const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev, const float* g2_dev, const uint32_t* depth_dev,
+              const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, uint32_t flags,
+              const crychic_ssr_params* params, cry::SsrParams& q)
 {
-    // every argument is checked before the context is looked at: a refusal needs no device
     if (!cb || !g0_dev || !g1_dev || !g2_dev || !depth_dev || !in_rgba8_dev || !out_rgba8_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
     if (flags & ~CRYCHIC_GBUFFER_F16_MASK)
         return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection flags 0x%x: bits outside CRYCHIC_GBUFFER_G0_F16 | G1_F16 | G2_F16", flags);
@@ -950,11 +954,95 @@ int crychic_ssr(crychic_ctx* ctx, const crychic_pass_constants* cb, const float*
     const size_t bytes = (size_t)W * H * 4u;
     if (ranges_overlap(s, bytes, d, bytes))
         return fail(CRYCHIC_E_INVALID_ARG, "the screen-space reflection input and output planes overlap (the pass cannot run in place)");
-    if (int rc = bind(ctx)) return rc;
-    cry::SsrParams q;
     std::memcpy(&q, &p, sizeof q);
+    return 0;
+}
+
+}  // namespace
+
+int crychic_ssr(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev, const float* g2_dev,
+                const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                uint32_t flags, const crychic_ssr_params* params, void* stream)
+{
+    cry::SsrParams q;
+    if (int rc = ssr_check(cb, g0_dev, g1_dev, g2_dev, depth_dev, in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, flags, params, q)) return rc;
+    if (int rc = bind(ctx)) return rc;
     CRY_HIP(cry::launch_ssr(cb->Proj, cb->ViewProj, cb->InvViewProj, cb->EyePosW, cb->NearZ, g0_dev, g1_dev, g2_dev, depth_dev, in_rgba8_dev,
                             out_rgba8_dev, W, H, row0, rows, flags, q, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(CRYCHIC_SSR_GLOSS_MAX_LEVELS == cry::kSsrGlossMaxLevels && sizeof(crychic_ssr_gloss_params) == 16 &&
+                  sizeof(crychic_ssr_gloss_params) == sizeof(cry::SsrGlossParams),
+              "ssr_gloss_core.hpp mirrors the ABI");
+
+int crychic_ssr_gloss_default_params(crychic_ssr_gloss_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    *out = crychic_ssr_gloss_params{};
+    out->coneScale = 0.0f; out->levels = 6u;       // 0: profiles/ssr_gloss_quality.txt
+    return 0;
+}
+
+size_t crychic_ssr_pyramid_bytes(uint32_t W, uint32_t H, uint32_t levels) { return cry::ssr_pyramid_plan(W, H, levels).bytes; }
+size_t crychic_ssr_pyramid_offset(uint32_t W, uint32_t H, uint32_t levels, uint32_t k)
+{
+    const cry::SsrPyramidPlan plan = cry::ssr_pyramid_plan(W, H, levels);
+    return k >= 1u && k <= plan.nEff ? plan.off[k] : 0u;
+}
+
+namespace {
+
+// What the two entries check of a pyramid's workspace, the frame's size already checked: `other` is the plane it must not overlap.
+int ssr_pyramid_check(uint32_t W, uint32_t H, uint32_t levels, const void* workspace, size_t workspaceBytes, const void* other)
+{
+    if (levels == 0u || levels > CRYCHIC_SSR_GLOSS_MAX_LEVELS)
+        return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection pyramid levels %u outside 1 .. %d", levels, CRYCHIC_SSR_GLOSS_MAX_LEVELS);
+    const size_t need = crychic_ssr_pyramid_bytes(W, H, levels);
+    if (need && !workspace) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    const uintptr_t w = reinterpret_cast<uintptr_t>(workspace);
+    if (w & 15u) return fail(CRYCHIC_E_INVALID_ARG, "the screen-space reflection pyramid is not 16-byte aligned");
+    if (workspaceBytes < need)
+        return fail(CRYCHIC_E_INVALID_ARG, "the screen-space reflection pyramid has %zu bytes, %ux%u with %u levels needs %zu", workspaceBytes, W, H, levels, need);
+    if (need && ranges_overlap(w, need, reinterpret_cast<uintptr_t>(other), (size_t)W * H * 4u))
+        return fail(CRYCHIC_E_INVALID_ARG, "the screen-space reflection pyramid overlaps a plane");
+    return 0;
+}
+
+}  // namespace
+
+int crychic_ssr_pyramid(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint32_t W, uint32_t H, uint32_t levels, void* workspace_dev, size_t workspace_bytes,
+                        void* stream)
+{
+    if (!in_rgba8_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (reinterpret_cast<uintptr_t>(in_rgba8_dev) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "the frame plane is not 4-byte aligned");
+    if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
+    if (int rc = check_extent("frame", W, H, false, 0u)) return rc;                   // one-dimensional grids, at most 2^18 workgroups
+    if (int rc = ssr_pyramid_check(W, H, levels, workspace_dev, workspace_bytes, in_rgba8_dev)) return rc;
+    if (int rc = bind(ctx)) return rc;
+    CRY_HIP(cry::launch_ssr_pyramid(in_rgba8_dev, W, H, levels, workspace_dev, (hipStream_t)stream));
+    return 0;
+}
+
+int crychic_ssr_glossy(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev, const float* g2_dev,
+                       const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, const void* pyramid_dev, size_t pyramid_bytes, uint8_t* out_rgba8_dev,
+                       uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, uint32_t flags, const crychic_ssr_params* params,
+                       const crychic_ssr_gloss_params* gloss, void* stream)
+{
+    cry::SsrParams q;
+    if (int rc = ssr_check(cb, g0_dev, g1_dev, g2_dev, depth_dev, in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, flags, params, q)) return rc;
+    crychic_ssr_gloss_params g;
+    crychic_ssr_gloss_default_params(&g);
+    if (gloss) g = *gloss;
+    if (!(g.coneScale >= 0.0f && g.coneScale <= 16.0f))
+        return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection coneScale %g outside 0 .. 16", (double)g.coneScale);
+    if (g.reserved[0] | g.reserved[1]) return fail(CRYCHIC_E_INVALID_ARG, "screen-space reflection gloss reserved words must be 0");
+    if (int rc = ssr_pyramid_check(W, H, g.levels, pyramid_dev, pyramid_bytes, out_rgba8_dev)) return rc;
+    if (int rc = bind(ctx)) return rc;
+    cry::SsrGlossParams gq;
+    std::memcpy(&gq, &g, sizeof gq);
+    CRY_HIP(cry::launch_ssr_glossy(cb->Proj, cb->ViewProj, cb->InvViewProj, cb->EyePosW, cb->NearZ, g0_dev, g1_dev, g2_dev, depth_dev, in_rgba8_dev,
+                                   pyramid_dev, out_rgba8_dev, W, H, row0, rows, flags, q, gq, (hipStream_t)stream));
     return 0;
 }
 

@@ -114,6 +114,17 @@ hipError_t launch_ssr(const float* proj, const float* viewProj, const float* inv
                       const void* g1, const void* g2, const uint32_t* depth, const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H,
                       uint32_t row0, uint32_t rows, uint32_t formatFlags, const SsrParams& p, hipStream_t stream);
 
+// ssr_pyramid.hip: levels 1 .. n_eff of the pyramid of the W x H RGBA8 frame `in` into `workspace` (ssr_pyramid_core.hpp): n_eff
+// launches on `stream`, one behind the other, none for n_eff == 0.  ssr_gloss.hip: launch_ssr with the hit colour from that pyramid
+// (`pyramid`: the workspace, built with g.levels) by the cone of `g` (ssr_gloss_core.hpp); one launch, none for rows == 0.  The caller
+// has checked what launch_ssr's has, and `levels`, `g`, the workspace's alignment, size and overlap.
+struct SsrGlossParams;
+hipError_t launch_ssr_pyramid(const uint8_t* in, uint32_t W, uint32_t H, uint32_t levels, void* workspace, hipStream_t stream);
+hipError_t launch_ssr_glossy(const float* proj, const float* viewProj, const float* invViewProj, const float* eye, float nearZ, const void* g0,
+                             const void* g1, const void* g2, const uint32_t* depth, const uint8_t* in, const void* pyramid, uint8_t* out, uint32_t W,
+                             uint32_t H, uint32_t row0, uint32_t rows, uint32_t formatFlags, const SsrParams& p, const SsrGlossParams& g,
+                             hipStream_t stream);
+
 // dof.hip: rows [row0, row0 + rows) of the W x H RGBA8 frame `out`: `in` blurred by the circle of confusion of the D24 plane `depth`
 // (dof_core.hpp); proj is the pass constants' Proj, read before the call returns.  One launch on `stream`, none for rows == 0.  The
 // caller has checked the pointers, their alignment and overlap, the sizes, the rows, proj and `p`.

@@ -110,10 +110,19 @@ CRY_HD bool ssr_hit(const SsrArgs& a, float dr, uint32_t word)
     return w24 != 0x00FFFFFFu && dr > ds && a.bias * D <= num && num <= a.thickness * D;
 }
 
+// The hit colour of crychic_ssr, the end of step 6: a point sample of the frame.  A policy of ssr_pixel: called once by every lane that
+// reaches step 7 (`hit`: the lane has a hit; otherwise hitIdx is 0 and the colour is not used), it returns the hit's texel, R, G and B
+// in the low three bytes.  crychic_ssr_glossy's policy is in ssr_gloss_core.hpp.
+struct SsrPointHit {
+    template <class Any>
+    CRY_HD uint32_t operator()(const SsrArgs& a, uint32_t, uint32_t, uint32_t hitIdx, float, bool, Any) const { return a.in[hitIdx]; }
+};
+
 // One pixel of the frame.  `any`: a vote over the lanes that run together (the device: the wavefront's active lanes; the host: the
-// lane's own predicate).  It only skips work whose result would be what it already is; no result depends on it.
-template <class Any>
-CRY_HD void ssr_pixel(const SsrArgs& a, uint32_t px, uint32_t py, Any any)
+// lane's own predicate).  It only skips work whose result would be what it already is; no result depends on it.  `colour`: the hit
+// colour's policy.
+template <class Any, class HitColour>
+CRY_HD void ssr_pixel(const SsrArgs& a, uint32_t px, uint32_t py, Any any, const HitColour& colour)
 {
     const uint32_t at = py * a.W + px;                         // below 2^28
     const uint32_t texel = a.in[at];
@@ -193,7 +202,7 @@ CRY_HD void ssr_pixel(const SsrArgs& a, uint32_t px, uint32_t py, Any any)
     tHit = tHi;
     // steps 7 to 9: integers from here on
     const f4a G0 = gbuffer_load(a.g0, at, a.h0);
-    const uint32_t src = a.in[hitIdx];
+    const uint32_t src = colour(a, px, py, hitIdx, rough, hit, any);
     const float f0 = 1.0f - saturate(dot3(Nw, R));
     const float f2 = f0 * f0;
     const float f5 = (f2 * f2) * f0;
@@ -219,5 +228,8 @@ CRY_HD void ssr_pixel(const SsrArgs& a, uint32_t px, uint32_t py, Any any)
     }
     a.out[at] = hit ? o : texel;
 }
+
+template <class Any>
+CRY_HD void ssr_pixel(const SsrArgs& a, uint32_t px, uint32_t py, Any any) { ssr_pixel(a, px, py, any, SsrPointHit{}); }
 
 }  // namespace cry

@@ -1,7 +1,8 @@
 """python -m crychic_renderer_amd.demo [--size WxH] [--out frame.ppm] [--textures DIR] [--cube FILE.dds] [--gbuffer f32|mixed|f16]
                                    [--capture-env X,Y,Z [--capture-dim N]] [--gloss] [--env-ambient] [--env-specular]
                                    [--probe-box X0,Y0,Z0,X1,Y1,Z1] [--aa]
-                                   [--ssr [--ssr-steps N] [--ssr-distance X] [--ssr-max-roughness X]]
+                                   [--ssr [--ssr-steps N] [--ssr-distance X] [--ssr-max-roughness X]
+                                          [--ssr-gloss [--ssr-cone X] [--ssr-levels N]]]
                                    [--fog [--fog-density X] [--fog-steps N]]
                                    [--dof [--dof-focus X] [--dof-aperture X] [--dof-radius N]]
                                    [--bloom [--bloom-threshold N] [--bloom-intensity N] [--bloom-levels N]]
@@ -34,6 +35,10 @@ lighting pass, the deferred path's stand-in for the framework's 4x MSAA switch) 
 stage, into a buffer of its own on which the fog then works): a smooth surface shows what stands on it, blended over the cube-map
 reflection; --ssr-steps (samples along each ray, default 32, at most 64), --ssr-distance (the ray's length in world units, default 20)
 and --ssr-max-roughness (surfaces at or above it do not reflect, default 0.75) set its parameters.
+--ssr-gloss (needs --ssr; experimental): the hit colour comes from a blurred pyramid of the lit frame, at the level whose texel is as
+wide as the reflection cone at the hit (Crychic.ssrGloss: crychic_ssr_pyramid and crychic_ssr_glossy in place of crychic_ssr);
+--ssr-cone (the cone's width per unit of roughness, 0 .. 16; the default 0 is the sharp pass, 0.7 a measured starting point) and
+--ssr-levels (the pyramid's levels, the frame counted, 1 .. 8, default 6) set its parameters.
 --fog: volumetric fog with sun shafts through the cascade maps (Crychic.fog: crychic_fog after the lighting pass, in place on the back
 buffer, in front of --aa); --fog-density (default 0.02) and --fog-steps (default 16, at most 64) set its parameters.
 --dof: depth of field from the depth plane (Crychic.depthOfField: crychic_dof after the lighting pass and the fog, in front of --aa);
@@ -90,6 +95,9 @@ def main():
     ap.add_argument("--ssr-steps", type=int, default=None, metavar="N", help="samples along each reflected ray, 1 .. 64 (default 32; needs --ssr)")
     ap.add_argument("--ssr-distance", type=float, default=None, metavar="X", help="length of a reflected ray in world units (default 20; needs --ssr)")
     ap.add_argument("--ssr-max-roughness", type=float, default=None, metavar="X", help="surfaces at or above this roughness do not reflect, 0 .. 1 (default 0.75; needs --ssr)")
+    ap.add_argument("--ssr-gloss", action="store_true", help="experimental: the hit colour from a blurred pyramid of the lit frame, by the reflection cone (needs --ssr)")
+    ap.add_argument("--ssr-cone", type=float, default=None, metavar="X", help="the cone's width per unit of roughness, 0 .. 16 (default 0: the sharp pass; needs --ssr-gloss)")
+    ap.add_argument("--ssr-levels", type=int, default=None, metavar="N", help="levels of the pyramid, the frame counted, 1 .. 8 (default 6; needs --ssr-gloss)")
     ap.add_argument("--sky", action="store_true", help="render the procedural sky (a single-scattering atmosphere) under the sun of Lights[0] "
                     "into the cube map, with the chain, tail and table that --gloss, --env-ambient and --env-specular ask for")
     ap.add_argument("--sky-sun-elevation", type=float, default=None, metavar="DEG", help="the sun's elevation over the horizon, along the azimuth "
@@ -146,6 +154,9 @@ def main():
         ap.error("--dof-focus, --dof-aperture and --dof-radius need --dof")
     if (a.fog_density is not None or a.fog_steps is not None) and not a.fog:
         ap.error("--fog-density and --fog-steps need --fog")
+    ap_gloss = a.ssr_gloss or a.ssr_cone is not None or a.ssr_levels is not None
+    if ap_gloss and not (a.ssr and a.ssr_gloss):
+        ap.error("--ssr-gloss needs --ssr; --ssr-cone and --ssr-levels need --ssr-gloss")
     if (a.ssr_steps is not None or a.ssr_distance is not None or a.ssr_max_roughness is not None) and not a.ssr:
         ap.error("--ssr-steps, --ssr-distance and --ssr-max-roughness need --ssr")
     box = None
@@ -252,6 +263,10 @@ def main():
     if a.ssr:
         knobs = {k: v for k, v in (("steps", a.ssr_steps), ("maxDistance", a.ssr_distance), ("maxRoughness", a.ssr_max_roughness)) if v is not None}
         app.ssr = SsrParams.default(**knobs) if knobs else True
+        if a.ssr_gloss:
+            from ._lib import SsrGlossParams
+            knobs = {k: v for k, v in (("coneScale", a.ssr_cone), ("levels", a.ssr_levels)) if v is not None}
+            app.ssrGloss = SsrGlossParams.default(**knobs) if knobs else True
     if a.fog:
         knobs = {k: v for k, v in (("density", a.fog_density), ("steps", a.fog_steps)) if v is not None}
         app.fog = FogParams.default(**knobs) if knobs else True

@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (AAParams, CrychicError, FogParams, SkyParams, SsrParams, DofParams, BloomParams, GradeParams, TaaParams, TaaUpscaleParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, FogParams, SkyParams, SsrParams, SsrGlossParams, DofParams, BloomParams, GradeParams, TaaParams, TaaUpscaleParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -231,6 +231,8 @@ class Crychic:
         self._fog = None             # fog, extension: None | True | FogParams -- Draw() of a whole frame runs crychic_fog in place on mBackBuffer
         self._ssr = None             # ssr, extension: None | True | SsrParams -- Draw() of a whole frame runs crychic_ssr into mBackBufferSSR, in front of the fog
         self.mBackBufferSSR = None   # the frame behind the screen-space reflections, allocated by the first screen_space_reflections() that needs it
+        self._ssrGloss = None        # ssrGloss, extension: None | True | SsrGlossParams -- with ssr set, Draw() runs crychic_ssr_pyramid and crychic_ssr_glossy in place of crychic_ssr
+        self.mSsrPyramid = None      # the lit frame's pyramid: crychic_ssr_pyramid_bytes of the frame at the most levels, with the first ssr_pyramid()
         self._depthOfField = None    # depthOfField, extension: None | True | DofParams -- Draw() of a whole frame runs crychic_dof into mBackBufferDoF
         self.mBackBufferDoF = None   # the frame behind the depth-of-field pass, allocated by the first depth_of_field() that needs it
         self._bloom = None           # bloom, extension: None | True | BloomParams -- Draw() of a whole frame runs crychic_bloom into mBackBufferBloom
@@ -269,12 +271,13 @@ class Crychic:
         return property(get, put)
 
     def _update_post(self):
-        self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA or self._motionBlur or self._ssr
+        self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA or self._motionBlur or self._ssr or self._ssrGloss
                           or self._temporalUpscale or self._colourGrade is not None)
 
     antiAliasing = _post_switch("_antiAliasing")
     fog = _post_switch("_fog")
     ssr = _post_switch("_ssr")
+    ssrGloss = _post_switch("_ssrGloss")
     depthOfField = _post_switch("_depthOfField")
     bloom = _post_switch("_bloom")
     temporalAA = _post_switch("_temporalAA")
@@ -377,7 +380,7 @@ class Crychic:
         the lighting pass in `parts` row ranges that travel while the next is lit (sharding.StripExchange.draw).
         With a switch of the passes behind the lighting pass set (extensions; True, or the pass's parameter struct): a whole frame,
         then the set passes in the order
-            lighting -> ssr -> fog (in place on the frame it is handed) -> temporalAA -> depthOfField -> motionBlur -> bloom -> colourGrade -> antiAliasing,
+            lighting -> ssr (with ssrGloss: the lit frame's pyramid and the glossy variant) -> fog (in place on the frame it is handed) -> temporalAA -> depthOfField -> motionBlur -> bloom -> colourGrade -> antiAliasing,
         each but the fog from the buffer of the nearest set stage in front of it that writes one of its own (mBackBuffer if there is
         none) into its own mBackBuffer*; final_frame() is the last one.  The temporal pass and the motion blur take the matrices of
         set_frame_view_proj (never called: a still camera); the first frame after temporalAA was turned on is a RESET frame.  A strip
@@ -442,10 +445,12 @@ class Crychic:
     def _draw_post_chain(self, row0, rows, shared):
         """Draw() with a switch set: the lighting frame, then one walk along the chain with the frame each stage reads."""
         if shared is not None or row0 != 0 or (rows is not None and rows != self.mClientHeight):
-            what = next(s for s in ("bloom", "motionBlur", "depthOfField", "temporalAA", "fog", "antiAliasing", "ssr", "temporalUpscale", "colourGrade")
+            what = next(s for s in ("bloom", "motionBlur", "depthOfField", "temporalAA", "fog", "antiAliasing", "ssr", "temporalUpscale", "colourGrade", "ssrGloss")
                         if (getattr(self, s) is not None if s == "colourGrade" else getattr(self, s)))
             raise CrychicError(-1, "%s is set: Draw() takes the whole frame on one GPU (the pass is not sharded and does not run behind the "
                                "exchange)" % what)
+        if self._ssrGloss and not self._ssr:
+            raise CrychicError(-1, "ssrGloss is set and ssr is not: the glossy lookup is a variant of the screen-space reflections")
         if self._temporalUpscale:
             for other in ("temporalAA", "depthOfField", "motionBlur"):
                 if getattr(self, other):
@@ -460,7 +465,12 @@ class Crychic:
             return switch if isinstance(switch, kind) else None
         frame = self.mBackBuffer
         if self._ssr:
-            frame = self.screen_space_reflections(src=frame, params=params(self._ssr, SsrParams))
+            if self._ssrGloss:
+                gloss = params(self._ssrGloss, SsrGlossParams) or SsrGlossParams.default()
+                self.ssr_pyramid(src=frame, levels=gloss.levels)
+                frame = self.screen_space_reflections(src=frame, params=params(self._ssr, SsrParams), gloss=gloss)
+            else:
+                frame = self.screen_space_reflections(src=frame, params=params(self._ssr, SsrParams))
         if self._fog:
             self.apply_fog(src=frame, params=params(self._fog, FogParams))
         cur, prev = self._taaViewProj           # of the temporal pass and the motion blur
@@ -635,13 +645,37 @@ class Crychic:
                               _stream(self.ctx.device)))
         return out
 
-    def screen_space_reflections(self, src=None, out=None, row0=0, rows=None, params=None):
+    def ssr_pyramid(self, src=None, levels=None):
+        """crychic_ssr_pyramid on the context's stream: levels 1 .. n_eff of the pyramid of `src` (default: mBackBuffer; an (H, W, 4)
+        uint8 tensor of the frame's size) into mSsrPyramid, allocated on first use for the frame's size at SSR_GLOSS_MAX_LEVELS levels;
+        levels: 1 .. SSR_GLOSS_MAX_LEVELS, the frame counted, None = the default of SsrGlossParams.  Returns mSsrPyramid."""
+        src, _, H, W = self._pass_frames("ssr_pyramid", None, src, None)
+        levels = SsrGlossParams.default().levels if levels is None else int(levels)
+        need = int(lib.crychic_ssr_pyramid_bytes(W, H, _lib.SSR_GLOSS_MAX_LEVELS))
+        if self.mSsrPyramid is None or self.mSsrPyramid.numel() != max(need, 16) or self.mSsrPyramid.device != src.device:
+            self.mSsrPyramid = torch.zeros((max(need, 16),), dtype=torch.uint8, device=src.device)
+        check(lib.crychic_ssr_pyramid(self.ctx.handle, _ptr(src), W, H, levels, _ptr(self.mSsrPyramid), self.mSsrPyramid.numel(),
+                                      _stream(self.ctx.device)))
+        return self.mSsrPyramid
+
+    def screen_space_reflections(self, src=None, out=None, row0=0, rows=None, params=None, gloss=None):
         """crychic_ssr on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferSSR, allocated on first use) from
         `src` (default: mBackBuffer), both (H, W, 4) uint8 tensors of the frame's size, with this frame's G-buffer in its planes'
         formats, depth plane and pass constants; params: an SsrParams, None = the defaults.  The pass reads any row of `src` and of the
-        depth plane and writes no other byte of `out`; `src` and `out` must not overlap.  Returns `out`."""
+        depth plane and writes no other byte of `out`; `src` and `out` must not overlap.  Returns `out`.
+        gloss: None, or True or an SsrGlossParams for crychic_ssr_glossy in its place, which reads the hit colour from mSsrPyramid:
+        what ssr_pyramid(src, levels=gloss.levels) left there, the caller's to issue first."""
         src, out, H, W = self._pass_frames("screen_space_reflections", "mBackBufferSSR", src, out)
         g = self.mDeferred.mGBuffer
+        if gloss is not None:
+            if self.mSsrPyramid is None:
+                raise CrychicError(-1, "screen_space_reflections(gloss=...) reads mSsrPyramid: call ssr_pyramid() first")
+            gp = gloss if isinstance(gloss, SsrGlossParams) else None
+            check(lib.crychic_ssr_glossy(self.ctx.handle, C.byref(self.mMainPassCB), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
+                                         self.mDepthStencilBuffer.data_ptr(), _ptr(src), _ptr(self.mSsrPyramid), self.mSsrPyramid.numel(), _ptr(out), W,
+                                         H, int(row0), int(H - row0 if rows is None else rows), gbuffer_flags(g),
+                                         None if params is None else C.byref(params), None if gp is None else C.byref(gp), _stream(self.ctx.device)))
+            return out
         check(lib.crychic_ssr(self.ctx.handle, C.byref(self.mMainPassCB), _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), self.mDepthStencilBuffer.data_ptr(),
                               _ptr(src), _ptr(out), W, H, int(row0), int(H - row0 if rows is None else rows), gbuffer_flags(g),
                               None if params is None else C.byref(params), _stream(self.ctx.device)))

@@ -167,6 +167,7 @@ public:
         if (mAntiAliasing) mBackBufferAA = FinalPlane();
         if (mDepthOfField) mBackBufferDoF = FramePlane();
         if (mScreenSpaceReflections) mBackBufferSSR = FramePlane();
+        if (mSsrGloss) AllocateSsrPyramid();
         if (mBloom) AllocateBloom();
         if (mColourGrade) mBackBufferGrade = FinalPlane();
         if (mTemporalAA) AllocateTemporalAA();                                                      // new history planes: the next frame is a reset frame
@@ -220,6 +221,9 @@ public:
             throw CrychicException(CRYCHIC_E_INVALID_ARG, std::string("CRYCHIC::Draw (") + pass + " takes the whole frame on one GPU: no SetStrip / JoinNode)",
                                    __FILE__, __LINE__);
         }
+        if (mSsrGloss && !mScreenSpaceReflections)
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::Draw (SetScreenSpaceReflectionGloss is on and SetScreenSpaceReflections is not)", __FILE__,
+                                   __LINE__);
         if (mTemporalUpscale && (mTemporalAA || mDepthOfField || mMotionBlur))
             throw CrychicException(CRYCHIC_E_INVALID_ARG, std::string("CRYCHIC::Draw (temporal upsampling together with ") +
                                    (mTemporalAA ? "temporal anti-aliasing: one temporal pass resolves a frame)"
@@ -296,7 +300,14 @@ public:
         // stage reads: the fog works in place on it, every other stage writes a buffer of its own and hands that on.
         uint8_t* frame = f.out_rgba8_dev;
         auto bytes = [](const std::unique_ptr<ID3D12Resource>& r) { return static_cast<uint8_t*>(r->Data()); };
-        if (mScreenSpaceReflections) {          // first: the frame is aligned with the depth plane and the G-buffer, the fog lies over both
+        if (mScreenSpaceReflections && mSsrGloss) {         // the glossy variant: the lit frame's pyramid, then the pass that reads it
+            CrychicThrowIfFailed(crychic_ssr_pyramid(md3dDevice->Ctx(), frame, mClientWidth, mClientHeight, mSsrGlossParams.levels, mSsrPyramid->Data(),
+                                                     mSsrPyramid->Bytes(), mCommandList->Stream()));
+            CrychicThrowIfFailed(crychic_ssr_glossy(md3dDevice->Ctx(), passCB, f.g0_dev, f.g1_dev, f.g2_dev, f.depth_dev, frame, mSsrPyramid->Data(),
+                                                    mSsrPyramid->Bytes(), bytes(mBackBufferSSR), mClientWidth, mClientHeight, 0, mClientHeight,
+                                                    f.flags & CRYCHIC_GBUFFER_F16_MASK, &mSsrParams, &mSsrGlossParams, mCommandList->Stream()));
+            frame = bytes(mBackBufferSSR);
+        } else if (mScreenSpaceReflections) {   // first: the frame is aligned with the depth plane and the G-buffer, the fog lies over both
             CrychicThrowIfFailed(crychic_ssr(md3dDevice->Ctx(), passCB, f.g0_dev, f.g1_dev, f.g2_dev, f.depth_dev, frame, bytes(mBackBufferSSR), mClientWidth,
                                              mClientHeight, 0, mClientHeight, f.flags & CRYCHIC_GBUFFER_F16_MASK, &mSsrParams, mCommandList->Stream()));
             frame = bytes(mBackBufferSSR);
@@ -363,7 +374,7 @@ public:
     // ---- the passes behind the lighting pass (extensions) -----------------------------------------------------------------------------
     // Nine switches (the temporal upsampling, below, stands at the temporal anti-aliasing's place), all off by default (then nothing changes).  With any of them on, Draw takes a whole frame on one GPU -- SetStrip /
     // JoinNode make it throw, the passes are not sharded -- and issues those that are on behind the lighting pass in the order
-    //     lighting -> screen-space reflections -> fog (in place) -> temporal anti-aliasing -> depth of field -> motion blur -> bloom -> colour grade -> anti-aliasing.
+    //     lighting -> screen-space reflections (with SetScreenSpaceReflectionGloss: the frame's pyramid and the glossy variant) -> fog (in place) -> temporal anti-aliasing -> depth of field -> motion blur -> bloom -> colour grade -> anti-aliasing.
     // The fog works in place on the frame it is handed: the reflections' buffer if they are on, the back buffer if not.  Every other
     // stage reads the buffer of the nearest stage in front of it that is on and writes one (the back buffer if there is none) and
     // writes a buffer of its own, which exists while the stage is on and which OnResize re-creates; Present writes the last one.
@@ -430,6 +441,26 @@ public:
     }
     bool ScreenSpaceReflections() const { return mScreenSpaceReflections; }
     ID3D12Resource* ScreenSpaceReflectionsBackBuffer() { return mBackBufferSSR.get(); }
+    // EXPERIMENTAL.  With SetScreenSpaceReflections on too, Draw issues crychic_ssr_pyramid and crychic_ssr_glossy in place of crychic_ssr:
+    // the hit colour comes from the level of the lit frame's pyramid that is as wide as the reflection cone at the hit
+    // (include/crychic_hip.h).  The default coneScale is 0, the sharp pass: the caller chooses the cone.  On without
+    // SetScreenSpaceReflections, Draw throws before it issues anything.
+    void SetScreenSpaceReflectionGloss(bool on, const crychic_ssr_gloss_params* p = nullptr)
+    {
+        crychic_ssr_gloss_params q;
+        CrychicThrowIfFailed(crychic_ssr_gloss_default_params(&q));
+        if (p) q = *p;
+        if (!(q.coneScale >= 0.0f && q.coneScale <= 16.0f) || q.levels == 0 || q.levels > CRYCHIC_SSR_GLOSS_MAX_LEVELS || q.reserved[0] || q.reserved[1])
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetScreenSpaceReflectionGloss (coneScale 0 .. 16, levels 1 .. 8, reserved 0)", __FILE__,
+                                   __LINE__);
+        mCommandList->Flush();                                  // a frame in flight may still read the pyramid released below
+        mSsrGloss = on;
+        mSsrGlossParams = q;
+        if (on) AllocateSsrPyramid();
+        else mSsrPyramid.reset();
+    }
+    bool ScreenSpaceReflectionGloss() const { return mSsrGloss; }
+    ID3D12Resource* ScreenSpaceReflectionPyramid() { return mSsrPyramid.get(); }
 
     // ---- depth of field ----------------------------------------------------------------------------------------------------------------
     // A thin-lens blur from the depth plane (include/crychic_hip.h crychic_dof).
@@ -1428,6 +1459,14 @@ private:
     bool mScreenSpaceReflections = false;     // SetScreenSpaceReflections
     crychic_ssr_params mSsrParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferSSR;  // the frame behind the screen-space reflections, while mScreenSpaceReflections
+    bool mSsrGloss = false;                   // SetScreenSpaceReflectionGloss
+    crychic_ssr_gloss_params mSsrGlossParams = {};
+    std::unique_ptr<ID3D12Resource> mSsrPyramid;     // the lit frame's pyramid: the frame's size at the most levels, so any parameters fit
+    void AllocateSsrPyramid()
+    {
+        const size_t need = crychic_ssr_pyramid_bytes(mClientWidth, mClientHeight, CRYCHIC_SSR_GLOSS_MAX_LEVELS);
+        mSsrPyramid = std::make_unique<ID3D12Resource>(need < 16 ? 16 : need, ID3D12Resource::DEFAULT_HEAP);
+    }
     bool mDepthOfField = false;               // SetDepthOfField
     crychic_dof_params mDofParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferDoF;  // the frame behind the depth-of-field pass, while mDepthOfField

@@ -1099,6 +1099,79 @@ int crychic_ssr(crychic_ctx* ctx, const crychic_pass_constants* cb, const float*
                 const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0,
                 uint32_t rows, uint32_t flags, const crychic_ssr_params* params /* NULL = defaults */, void* stream);
 
+/* ---- glossy screen-space reflections: a blurred pyramid of the lit frame and a cone lookup (extension) ------
+ * crychic_ssr takes the hit colour as a point sample whatever the surface's roughness.  crychic_ssr_pyramid builds a binomial
+ * pyramid of the finished RGBA8 frame; crychic_ssr_glossy is crychic_ssr with the hit colour fetched from the level whose texel is as
+ * wide as the reflection cone at the hit.  A build definition: nothing of it is the reference's.  The device, a host build and the
+ * checker (tests/ssr_gloss_ref) agree bit for bit.
+ *
+ * The pyramid, all unsigned 32-bit integers.  Level 0 is the frame itself and is never copied.  W_k = (W_(k-1) + 1) >> 1, H_k
+ * likewise (the bloom's sizes).  `levels` counts level 0: 1 .. CRYCHIC_SSR_GLOSS_MAX_LEVELS.  n_eff, the highest level built, is the
+ * smaller of levels - 1 and the first k with W_k == H_k == 1 (0 for a 1 x 1 frame): levels = 1 builds nothing.  A texel is RGBA8 and
+ * all four channels are filtered alike.  Level k + 1 from level k is the bloom's 4 x 4 binomial (1, 3, 3, 1) x (1, 3, 3, 1):
+ * destination (x, y) reads source columns 2x - 1 .. 2x + 2 and rows 2y - 1 .. 2y + 2, each coordinate clamped to the source level's
+ * edge;  sum = the 16 products (at most 64 * 255);  v = (sum + 32) >> 6 per channel.
+ * Workspace: levels 1 .. n_eff back to back, each starting on a 16-byte boundary; level k is W_k x H_k texels of 4 bytes, row-major.
+ * crychic_ssr_pyramid_bytes is the end of level n_eff (0 when n_eff is 0), crychic_ssr_pyramid_offset the start of level k (0 for
+ * k = 0 or k > n_eff, as for W or H of 0 or levels outside 1 .. CRYCHIC_SSR_GLOSS_MAX_LEVELS); both are pure host code.
+ * Known answers: a frame of one colour has that colour in every texel of every level; transposing the frame transposes every
+ * level; a frame whose columns alternate 0 and 255 has 128 in every level-1 texel whose four source columns are unclamped
+ * ((4 * 8 * 255 + 32) >> 6); on a frame affine in x and y a level-k texel whose level-0 support (4 * 2^k - 3 columns and rows about
+ * its centre) lies inside the frame is within k / 2 of the affine value at its centre.
+ *
+ * The glossy pass.  Steps 1 to 6 of crychic_ssr stand: the same ray, the same hit pixel (hx, hy), the same t_hit.  Steps 7 to 9
+ * stand too.  Between them only the source of `hit` changes; rough is step 1's, len_from_sq crychic_fog's, det_log2
+ * crychic_apply_decals':
+ *   6a  dx = (float)hx - (float)px;  dy = (float)hy - (float)py;  Lpx = len_from_sq(fma(dx, dx, dy dy));
+ *       r = (coneScale rough) Lpx  -- the lighting pass's lobe is NDF_GGX with a = roughness, not squared (section 15), so the cone's
+ *       tangent goes with rough; the cone's length is taken as the ray's length on the screen;
+ *       lam = r > 1.0f ? det_log2(r) : 0.0f (a NaN gives 0);  lam = lam < (float)n_eff ? lam : (float)n_eff;
+ *       lq = (uint32_t)fma(lam, 256.0f, 0.5f);  k = lq >> 8;  f = lq & 255 (0 when k == n_eff, since lq <= 256 n_eff).
+ *   6b  integers only.  fetch(k), along x:  T = ((2 hx + 1) 128) >> k;  U = max(T, 128) - 128  -- (hx + 1/2) / 2^k - 1/2 in 1/256
+ *       texel, clamped at 0;  x0 = min(U >> 8, W_k - 1);  x1 = min(x0 + 1, W_k - 1);  fx = U & 255;  y0, y1, fy likewise from hy and
+ *       H_k.  Per channel, with cXY the level's texel (xX, yY):  top = c00 (256 - fx) + c10 fx;  bot = c01 (256 - fx) + c11 fx;
+ *       v_k = (top (256 - fy) + bot fy + 32768) >> 16.  At k = 0 this is in[hy W + hx] exactly.
+ *       hit_c = f == 0 ? v_k : (v_k (256 - f) + v_(k+1) f + 128) >> 8.
+ * The pyramid is always that of the whole frame `in`, built with the same W, H and levels.
+ * Known answers: coneScale 0, levels 1, or a G1 plane with roughness 0 everywhere each give crychic_ssr's output byte for byte on
+ * any input; a frame of one colour stays that colour; alpha is always the pixel's own.
+ * Known limit: the pyramid blurs across depth edges, so a rough floor's reflection of a box can pick up some floor colour.
+ *
+ * Parameters: coneScale (finite, 0 .. 16; default 0, the sharp pass: the measurement that was to set it, tests/ssr_gloss_quality.py,
+ * leaves no pixel to measure at any roughness of its grid (profiles/ssr_gloss_quality.txt), so the pass is EXPERIMENTAL and the
+ * caller chooses the cone), levels (6; 1 .. CRYCHIC_SSR_GLOSS_MAX_LEVELS), reserved (must be 0).  crychic_ssr_gloss_default_params fills the defaults (pure host code;
+ * CRYCHIC_E_INVALID_ARG for NULL). */
+#define CRYCHIC_SSR_GLOSS_MAX_LEVELS 8
+typedef struct crychic_ssr_gloss_params {
+    float coneScale;
+    uint32_t levels;
+    uint32_t reserved[2];
+} crychic_ssr_gloss_params;   /* 16 bytes */
+int crychic_ssr_gloss_default_params(crychic_ssr_gloss_params* out);
+size_t crychic_ssr_pyramid_bytes(uint32_t W, uint32_t H, uint32_t levels);
+size_t crychic_ssr_pyramid_offset(uint32_t W, uint32_t H, uint32_t levels, uint32_t k);
+/* crychic_ssr_pyramid: after it level k of workspace_dev holds level k of in_rgba8_dev's pyramid for k = 1 .. n_eff; no other byte
+ * of the workspace is written (not the gaps between levels either) and in_rgba8_dev is only read.  n_eff launches on `stream`, one
+ * behind the other; no allocation, no synchronisation, no host read-back; capturable into a graph.  workspace_dev may be NULL only
+ * where crychic_ssr_pyramid_bytes(W, H, levels) is 0 (nothing is launched then).
+ * CRYCHIC_E_INVALID_ARG with a message, checked before the context is used and before anything is enqueued: a NULL plane or (where
+ * bytes are needed) workspace; a plane that is not 4-byte aligned or a workspace that is not 16-byte aligned; W or H of 0; levels
+ * outside its range; workspace_bytes below crychic_ssr_pyramid_bytes(W, H, levels); a workspace (its first
+ * crychic_ssr_pyramid_bytes bytes) overlapping the plane.  More than 2^28 pixels: CRYCHIC_E_UNSUPPORTED. */
+int crychic_ssr_pyramid(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint32_t W, uint32_t H, uint32_t levels, void* workspace_dev,
+                        size_t workspace_bytes, void* stream);
+/* crychic_ssr_glossy: crychic_ssr's contract in every word -- the planes it reads and writes, the row range (stitched ranges equal
+ * the whole frame; the pyramid is always of the whole frame), flags, params, its refusals -- with two more arguments: pyramid_dev,
+ * what crychic_ssr_pyramid(in_rgba8_dev, W, H, gloss->levels) left (only read; any texel of it), and gloss (NULL = the defaults).
+ * Refused besides, with CRYCHIC_E_INVALID_ARG: a coneScale that is not finite or outside 0 .. 16, levels outside its range, a
+ * non-zero reserved word, a NULL pyramid where bytes are needed, a pyramid that is not 16-byte aligned, pyramid_bytes below
+ * crychic_ssr_pyramid_bytes(W, H, levels), a pyramid overlapping out_rgba8_dev.  One launch. */
+int crychic_ssr_glossy(crychic_ctx* ctx, const crychic_pass_constants* cb, const float* g0_dev, const float* g1_dev,
+                       const float* g2_dev, const uint32_t* depth_dev, const uint8_t* in_rgba8_dev, const void* pyramid_dev,
+                       size_t pyramid_bytes, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                       uint32_t flags, const crychic_ssr_params* params /* NULL = defaults */,
+                       const crychic_ssr_gloss_params* gloss /* NULL = defaults */, void* stream);
+
 /* ---- depth of field from the depth plane (extension) -------------------------------------------------------
  * One pass over the finished RGBA8 frame, a separate call after the lighting pass (and the fog) and before the anti-aliasing: a
  * thin-lens blur.  Every texel has a circle of confusion from its depth; every output pixel gathers the texels of a disc of radius R
