@@ -30,6 +30,7 @@ SKY_MAX_VIEW_STEPS, SKY_MAX_SUN_STEPS = 64, 32      # CRYCHIC_SKY_MAX_VIEW_STEPS
 SSR_MAX_STEPS = 64            # CRYCHIC_SSR_MAX_STEPS: the most samples crychic_ssr takes along a reflected ray
 DOF_MAX_RADIUS = 8            # CRYCHIC_DOF_MAX_RADIUS: the largest gather radius of crychic_dof, in pixels
 BLOOM_MAX_LEVELS = 8          # CRYCHIC_BLOOM_MAX_LEVELS: the most levels of crychic_bloom's pyramid
+SHARPEN_MAX_STRENGTH, SHARPEN_MAX_LIMIT = 256, 3584      # CRYCHIC_SHARPEN_MAX_STRENGTH, CRYCHIC_SHARPEN_MAX_LIMIT (Q12) of crychic_sharpen
 GRADE_MAX_N = 33              # CRYCHIC_GRADE_MAX_N: the largest table of crychic_grade (33 x 33 x 33 entries: 143 748 bytes of LDS)
 
 
@@ -255,6 +256,24 @@ class GradeParams(C.Structure):
 assert C.sizeof(GradeParams) == 40
 
 
+class SharpenParams(C.Structure):
+    """crychic_sharpen_params: the knobs of crychic_sharpen (extension); SharpenParams.default() = crychic_sharpen_default_params, any
+    field replaced by its keyword."""
+    _fields_ = [("strength", C.c_uint32), ("limit", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+    @classmethod
+    def default(cls, strength=None, limit=None):
+        p = cls()
+        check(lib.crychic_sharpen_default_params(C.byref(p)))
+        for name, v in (("strength", strength), ("limit", limit)):
+            if v is not None:
+                setattr(p, name, int(v))
+        return p
+
+
+assert C.sizeof(SharpenParams) == 16
+
+
 TAA_RESET, TAA_NO_CLAMP = 1, 2               # CRYCHIC_TAA_RESET, CRYCHIC_TAA_NO_CLAMP
 
 
@@ -426,6 +445,8 @@ PROTOTYPES = {
     "crychic_grade_build_lut": (_i, [_P(GradeParams), _u32, _vp, _sz]),
     "crychic_load_cube_lut": (_i, [C.c_char_p, _vp, _sz, _P(C.c_uint32)]),
     "crychic_grade": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u32, _vp]),
+    "crychic_sharpen_default_params": (_i, [_P(SharpenParams)]),
+    "crychic_sharpen": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _P(SharpenParams), _vp]),
     "crychic_taa_jitter": (_i, [_u32, _P(_f), _P(_f)]),
     "crychic_update_main_pass_cb_jittered": (_i, [_P(Camera), _u32, _u32, _vp, _vp, _f, _f, _P(PassConstants)]),
     "crychic_update_ssao_cb_jittered": (_i, [_P(Camera), _u32, _u32, _vp, _f, _f, _P(SsaoConstants)]),

@@ -13,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libcrychic_hip.so")
-SOURCES = ["kernels.hip", "light_general.hip", "raster.hip", "cube_mips.hip", "cube_prefilter.hip", "cube_sh.hip", "env_brdf.hip", "sky.hip", "post_aa.hip", "fog.hip", "ssr.hip", "ssr_pyramid.hip", "ssr_gloss.hip", "dof.hip", "bloom.hip", "taa.hip", "taa_upscale.hip", "motion_blur.hip", "decal.hip", "grade.hip", "api.cpp", "comm.cpp", "host_constants.cpp", "host_geometry.cpp", "host_textures.cpp"]
-HEADERS = ["devmath.hpp", "gamma_pow.inc", "ssao_core.hpp", "blur_tiles.hpp", "light_core.hpp", "light_bind.hpp", "light_tiles.hpp", "dispatch_order.hpp", "raster_core.hpp", "cube_mips_core.hpp", "cube_prefilter_core.hpp", "cube_sh_core.hpp", "env_brdf_core.hpp", "sky_core.hpp", "post_aa_core.hpp", "fog_core.hpp", "ssr_core.hpp", "ssr_pyramid_core.hpp", "ssr_gloss_core.hpp", "dof_core.hpp", "bloom_core.hpp", "taa_core.hpp", "taa_upscale_core.hpp", "motion_blur_core.hpp", "decal_core.hpp", "grade_core.hpp", "kernels.hpp", "internal.hpp"]
+SOURCES = ["kernels.hip", "light_general.hip", "raster.hip", "cube_mips.hip", "cube_prefilter.hip", "cube_sh.hip", "env_brdf.hip", "sky.hip", "post_aa.hip", "fog.hip", "ssr.hip", "ssr_pyramid.hip", "ssr_gloss.hip", "dof.hip", "bloom.hip", "taa.hip", "taa_upscale.hip", "motion_blur.hip", "decal.hip", "grade.hip", "sharpen.hip", "api.cpp", "comm.cpp", "host_constants.cpp", "host_geometry.cpp", "host_textures.cpp"]
+HEADERS = ["devmath.hpp", "gamma_pow.inc", "ssao_core.hpp", "blur_tiles.hpp", "light_core.hpp", "light_bind.hpp", "light_tiles.hpp", "dispatch_order.hpp", "raster_core.hpp", "cube_mips_core.hpp", "cube_prefilter_core.hpp", "cube_sh_core.hpp", "env_brdf_core.hpp", "sky_core.hpp", "post_aa_core.hpp", "fog_core.hpp", "ssr_core.hpp", "ssr_pyramid_core.hpp", "ssr_gloss_core.hpp", "dof_core.hpp", "bloom_core.hpp", "taa_core.hpp", "taa_upscale_core.hpp", "motion_blur_core.hpp", "decal_core.hpp", "grade_core.hpp", "sharpen_core.hpp", "kernels.hpp", "internal.hpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math",
          # the SLP vectoriser packs scalar fp32 pairs into v_pk_* plus the v_mov that pairs their registers: measured 5 % slower
          # lighting / blur (profiles/r01_e_relaxed_math_probe.json); the SSAO tap loop is packed by hand where it pays

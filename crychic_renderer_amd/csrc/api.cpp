@@ -26,6 +26,7 @@
 #include "dof_core.hpp"
 #include "bloom_core.hpp"
 #include "grade_core.hpp"
+#include "sharpen_core.hpp"
 #include "taa_core.hpp"
 #include "taa_upscale_core.hpp"
 #include "motion_blur_core.hpp"
@@ -1352,6 +1353,41 @@ int crychic_grade(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rg
     if (ranges_overlap(l, (size_t)4u * N * N * N, d, bytes)) return fail(CRYCHIC_E_INVALID_ARG, "the colour grade table overlaps the output plane");
     if (int rc = bind(ctx)) return rc;
     CRY_HIP(cry::launch_grade(in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, lut_rgba8_dev, N, (hipStream_t)stream));
+    return 0;
+}
+
+static_assert(CRYCHIC_SHARPEN_MAX_STRENGTH == cry::kSharpenMaxStrength && CRYCHIC_SHARPEN_MAX_LIMIT == cry::kSharpenMaxLimit &&
+              sizeof(crychic_sharpen_params) == 16 && sizeof(crychic_sharpen_params) == sizeof(cry::SharpenParams), "sharpen_core.hpp mirrors the ABI");
+
+int crychic_sharpen_default_params(crychic_sharpen_params* out)
+{
+    if (!out) return fail(CRYCHIC_E_INVALID_ARG, "out is null");
+    out->strength = CRYCHIC_SHARPEN_DEFAULT_STRENGTH; out->limit = CRYCHIC_SHARPEN_DEFAULT_LIMIT;
+    out->reserved[0] = out->reserved[1] = 0u;
+    return 0;
+}
+
+int crychic_sharpen(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows,
+                    const crychic_sharpen_params* params, void* stream)
+{
+    // every argument is checked before the context is looked at: a refusal needs no device
+    if (!in_rgba8_dev || !out_rgba8_dev) return fail(CRYCHIC_E_INVALID_ARG, "null argument");
+    if (W == 0 || H == 0) return fail(CRYCHIC_E_INVALID_ARG, "frame size %ux%u must be non-zero", W, H);
+    if (int rc = check_extent("frame", W, H, false, 0u)) return rc;
+    if (int rc = check_rows(kFrameRows, row0, rows, H)) return rc;
+    crychic_sharpen_params p;
+    crychic_sharpen_default_params(&p);
+    if (params) p = *params;
+    if (p.strength > CRYCHIC_SHARPEN_MAX_STRENGTH) return fail(CRYCHIC_E_INVALID_ARG, "sharpening strength %u outside 0 .. %d", p.strength, CRYCHIC_SHARPEN_MAX_STRENGTH);
+    if (p.limit > CRYCHIC_SHARPEN_MAX_LIMIT) return fail(CRYCHIC_E_INVALID_ARG, "sharpening limit %u outside 0 .. %d", p.limit, CRYCHIC_SHARPEN_MAX_LIMIT);
+    if (p.reserved[0] | p.reserved[1]) return fail(CRYCHIC_E_INVALID_ARG, "sharpening reserved words must be 0");
+    const uintptr_t s = reinterpret_cast<uintptr_t>(in_rgba8_dev), d = reinterpret_cast<uintptr_t>(out_rgba8_dev);
+    if ((s | d) & 3u) return fail(CRYCHIC_E_INVALID_ARG, "sharpening planes are not 4-byte aligned");
+    const size_t bytes = (size_t)W * H * 4u;
+    if (ranges_overlap(s, bytes, d, bytes)) return fail(CRYCHIC_E_INVALID_ARG, "the sharpening input and output planes overlap (the pass cannot run in place)");
+    if (int rc = bind(ctx)) return rc;
+    const cry::SharpenParams q = { p.strength, p.limit, { 0u, 0u } };
+    CRY_HIP(cry::launch_sharpen(in_rgba8_dev, out_rgba8_dev, W, H, row0, rows, q, (hipStream_t)stream));
     return 0;
 }
 

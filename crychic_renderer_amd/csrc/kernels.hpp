@@ -183,6 +183,14 @@ hipError_t launch_motion_blur_gather(const uint8_t* in, uint8_t* out, uint32_t W
 hipError_t launch_grade(const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const uint8_t* lut, uint32_t N,
                         hipStream_t stream);
 
+// sharpen.hip: rows [row0, row0 + rows) of the W x H RGBA8 frame `out` from `in` sharpened (sharpen_core.hpp); neighbours are clamped
+// to the frame, not to the rows.  One launch on `stream`, none for rows == 0: the wide kernel where W is a multiple of 4 and both
+// planes are 16-byte aligned, the narrow one otherwise.  The caller has checked the pointers, their alignment and overlap, the sizes,
+// the rows and the parameters.
+struct SharpenParams;
+hipError_t launch_sharpen(const uint8_t* in, uint8_t* out, uint32_t W, uint32_t H, uint32_t row0, uint32_t rows, const SharpenParams& p,
+                          hipStream_t stream);
+
 // ---- producer passes (raster.hip) ----
 struct crychic_pass_constants_viewproj { float m[16]; };   // one transposed 4x4 passed by value in the kernarg segment
 struct Texture;

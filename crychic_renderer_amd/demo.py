@@ -8,6 +8,7 @@
                                    [--bloom [--bloom-threshold N] [--bloom-intensity N] [--bloom-levels N]]
                                    [--taa [--taa-frames N]] [--taa-upscale WxH [--taa-frames N]]
                                    [--motion-blur [--motion-blur-shutter N] [--motion-blur-samples N] [--motion-blur-pan DX]]
+                                   [--sharpen [--sharpen-strength N]]
                                    [--grade-cube FILE.cube | --grade-slope R,G,B --grade-offset R,G,B --grade-power R,G,B --grade-saturation X]
 
 Renders one frame of the reference's live scene entirely on the GPU -- 4 shadow cascades, view normals + depth, G-buffer
@@ -62,7 +63,10 @@ glossy puddle with a dent normal map on the floor and a painted ring on the face
 --grade-cube FILE.cube, or any of --grade-slope, --grade-offset, --grade-power (R,G,B or one number for all three) and
 --grade-saturation: the colour grade (Crychic.colourGrade: crychic_grade behind --bloom, in front of --aa): the frame's look through a
 3D table, loaded from an Adobe / Resolve .cube file or built from an ASC CDL with a saturation at 33 x 33 x 33 entries.
---grade-saturation 0 writes a grey frame."""
+--grade-saturation 0 writes a grey frame.
+--sharpen: contrast-adaptive sharpening (Crychic.sharpening: crychic_sharpen directly behind --taa or --taa-upscale, then at the display
+size, and in front of --dof); --sharpen-strength (0 .. 256, default: the measured one of crychic_sharpen_default_params) sets how much
+of the limited weight is used."""
 import argparse
 import ctypes as C
 import math
@@ -125,6 +129,8 @@ def main():
     ap.add_argument("--motion-blur-samples", type=int, default=None, metavar="N", help="samples along the velocity: 2, 4, 8, 16 or 32 (default 8; needs --motion-blur)")
     ap.add_argument("--motion-blur-pan", type=float, default=None, metavar="DX", help="the previous camera's displacement along +x in world units (default 0.5; "
                                                                                       "needs --motion-blur)")
+    ap.add_argument("--sharpen", action="store_true", help="contrast-adaptive sharpening behind the temporal stage, in front of --dof")
+    ap.add_argument("--sharpen-strength", type=int, default=None, metavar="N", help="0 .. 256 (default: the pass's; needs --sharpen)")
     ap.add_argument("--grade-cube", default="", metavar="FILE.cube", help="colour grade through the 3D table of a .cube file, behind the bloom and in front of --aa")
     ap.add_argument("--grade-slope", default="", metavar="R,G,B", help="colour grade: the ASC CDL's slope, 0 .. 16 (default 1)")
     ap.add_argument("--grade-offset", default="", metavar="R,G,B", help="colour grade: the ASC CDL's offset, -4 .. 4 (default 0)")
@@ -142,6 +148,8 @@ def main():
         grade["saturation"] = a.grade_saturation
     if a.grade_cube and grade:
         ap.error("--grade-cube does not go with --grade-slope, --grade-offset, --grade-power or --grade-saturation")
+    if a.sharpen_strength is not None and not a.sharpen:
+        ap.error("--sharpen-strength needs --sharpen")
     if (a.motion_blur_shutter is not None or a.motion_blur_samples is not None or a.motion_blur_pan is not None) and not a.motion_blur:
         ap.error("--motion-blur-shutter, --motion-blur-samples and --motion-blur-pan need --motion-blur")
     if a.taa_frames is not None and not ((a.taa or a.taa_upscale) and a.taa_frames >= 1):
@@ -274,6 +282,9 @@ def main():
         app.depthOfField = DofParams.default(focus=a.dof_focus, aperture=a.dof_aperture, radius=a.dof_radius)
     if a.bloom:
         app.bloom = BloomParams.default(threshold=a.bloom_threshold, intensity=a.bloom_intensity, levels=a.bloom_levels)
+    if a.sharpen:
+        from ._lib import SharpenParams
+        app.sharpening = SharpenParams.default(strength=a.sharpen_strength)
     if a.grade_cube:
         app.colourGrade = a.grade_cube
     elif grade:
@@ -313,7 +324,7 @@ def main():
     torch.cuda.synchronize()
     img = np.ascontiguousarray(app.final_frame().cpu().numpy())
     check(lib.crychic_save_ppm(a.out.encode(), img.ctypes.data, WO, HO))
-    chain = (("ssr", "screen-space reflections"), ("fog", "fog"), ("temporalAA", "temporal anti-aliasing"), ("temporalUpscale", "temporal upsampling"), ("depthOfField", "depth of field"), ("motionBlur", "motion blur"),
+    chain = (("ssr", "screen-space reflections"), ("fog", "fog"), ("temporalAA", "temporal anti-aliasing"), ("temporalUpscale", "temporal upsampling"), ("sharpening", "sharpened"), ("depthOfField", "depth of field"), ("motionBlur", "motion blur"),
              ("bloom", "bloom"), ("colourGrade", "colour grade"), ("antiAliasing", "anti-aliased"))                   # Draw()'s order
     print("wrote %s (%dx%d%s) on %s" % (a.out, WO, HO, "".join(", " + text for switch, text in chain if getattr(app, switch) is not None and getattr(app, switch) is not False),
                                         ctx.device_name))

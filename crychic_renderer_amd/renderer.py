@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import (AAParams, CrychicError, FogParams, SkyParams, SsrParams, SsrGlossParams, DofParams, BloomParams, GradeParams, TaaParams, TaaUpscaleParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
+from ._lib import (AAParams, CrychicError, FogParams, SkyParams, SsrParams, SsrGlossParams, DofParams, BloomParams, GradeParams, SharpenParams, TaaParams, TaaUpscaleParams, MotionBlurParams, DrawItem, FrameDesc, Light, PassConstants, PassTimes, PointShadows, SpotShadows, SsaoConstants, Texture,
                    check, lib)
 
 
@@ -248,6 +248,8 @@ class Crychic:
         self.mBackBufferUpscaled = None      # the resolved (Ho, Wo, 4) frame of the display size, allocated by the first temporal_upscale() that needs it
         self.mTaaUpscaleHistory = None       # as mTaaHistory, of the display size
         self._taaUpscaleReset = True         # as _taaReset, for temporalUpscale
+        self._sharpening = None      # sharpening, extension: None | True | SharpenParams -- Draw() of a whole frame runs crychic_sharpen into mBackBufferSharp, behind the temporal stage
+        self.mBackBufferSharp = None  # the sharpened frame, allocated by the first sharpen_frame() that needs it
         self._motionBlur = None      # motionBlur, extension: None | True | MotionBlurParams -- Draw() of a whole frame runs crychic_motion_blur into mBackBufferMB
         self.mBackBufferMB = None    # the frame behind the motion blur, allocated by the first motion_blur() that needs it
         self.mMotionBlurWorkspace = None     # the velocity and tile planes: crychic_motion_blur_workspace_bytes of the frame, with the first motion_blur()
@@ -272,7 +274,7 @@ class Crychic:
 
     def _update_post(self):
         self._post = bool(self._fog or self._antiAliasing or self._depthOfField or self._bloom or self._temporalAA or self._motionBlur or self._ssr or self._ssrGloss
-                          or self._temporalUpscale or self._colourGrade is not None)
+                          or self._temporalUpscale or self._colourGrade is not None or self._sharpening)
 
     antiAliasing = _post_switch("_antiAliasing")
     fog = _post_switch("_fog")
@@ -283,6 +285,7 @@ class Crychic:
     temporalAA = _post_switch("_temporalAA")
     motionBlur = _post_switch("_motionBlur")
     temporalUpscale = _post_switch("_temporalUpscale")
+    sharpening = _post_switch("_sharpening")
 
     @property
     def colourGrade(self):
@@ -380,14 +383,14 @@ class Crychic:
         the lighting pass in `parts` row ranges that travel while the next is lit (sharding.StripExchange.draw).
         With a switch of the passes behind the lighting pass set (extensions; True, or the pass's parameter struct): a whole frame,
         then the set passes in the order
-            lighting -> ssr (with ssrGloss: the lit frame's pyramid and the glossy variant) -> fog (in place on the frame it is handed) -> temporalAA -> depthOfField -> motionBlur -> bloom -> colourGrade -> antiAliasing,
+            lighting -> ssr (with ssrGloss: the lit frame's pyramid and the glossy variant) -> fog (in place on the frame it is handed) -> temporalAA -> sharpening -> depthOfField -> motionBlur -> bloom -> colourGrade -> antiAliasing,
         each but the fog from the buffer of the nearest set stage in front of it that writes one of its own (mBackBuffer if there is
         none) into its own mBackBuffer*; final_frame() is the last one.  The temporal pass and the motion blur take the matrices of
         set_frame_view_proj (never called: a still camera); the first frame after temporalAA was turned on is a RESET frame.  A strip
         or a shared draw then raises CrychicError: these passes are not sharded.
         temporalUpscale = (Wo, Ho) or (Wo, Ho, TaaUpscaleParams) puts crychic_taa_upscale at the temporal pass's place: the frame of the
         client size, rendered with the jitter handed to set_frame_view_proj, is accumulated into a history of Wo x Ho texels, and the
-        bloom and the anti-aliasing behind it run at that size.  Together with temporalAA, depthOfField or motionBlur it raises
+        sharpening, the bloom, the colour grade and the anti-aliasing behind it run at that size.  Together with temporalAA, depthOfField or motionBlur it raises
         CrychicError before anything is issued (the last two read a depth plane of the frame's size).
         followSun (extension; True or a SkyParams): in front of all that, the procedural sky is kept bound whose sun is where Lights[0]
         shines from (render_sky), re-rendered only when that direction or the parameters changed; strips and shared draws included."""
@@ -445,7 +448,7 @@ class Crychic:
     def _draw_post_chain(self, row0, rows, shared):
         """Draw() with a switch set: the lighting frame, then one walk along the chain with the frame each stage reads."""
         if shared is not None or row0 != 0 or (rows is not None and rows != self.mClientHeight):
-            what = next(s for s in ("bloom", "motionBlur", "depthOfField", "temporalAA", "fog", "antiAliasing", "ssr", "temporalUpscale", "colourGrade", "ssrGloss")
+            what = next(s for s in ("bloom", "motionBlur", "depthOfField", "temporalAA", "fog", "antiAliasing", "ssr", "temporalUpscale", "colourGrade", "ssrGloss", "sharpening")
                         if (getattr(self, s) is not None if s == "colourGrade" else getattr(self, s)))
             raise CrychicError(-1, "%s is set: Draw() takes the whole frame on one GPU (the pass is not sharded and does not run behind the "
                                "exchange)" % what)
@@ -484,6 +487,8 @@ class Crychic:
         if self._temporalUpscale:
             frame = self.temporal_upscale(cur, prev, self._frameJitter, up[:2], src=frame, reset=self._taaUpscaleReset, params=up[2] if len(up) == 3 else None)
             self._taaUpscaleReset = False
+        if self._sharpening:                    # directly behind the temporal stage, at its place when there is none
+            frame = self.sharpen_frame(src=frame, params=params(self._sharpening, SharpenParams))
         if self._depthOfField:
             frame = self.depth_of_field(src=frame, params=params(self._depthOfField, DofParams))
         if self._motionBlur:
@@ -498,7 +503,7 @@ class Crychic:
     def final_frame(self):
         """The tensor a Draw() with the switches as they are leaves the finished frame in: the last set stage's buffer."""
         for switch, name in ((self._antiAliasing, "mBackBufferAA"), (self._colourGrade is not None, "mBackBufferGrade"), (self._bloom, "mBackBufferBloom"), (self._motionBlur, "mBackBufferMB"),
-                             (self._depthOfField, "mBackBufferDoF"), (self._temporalAA, "mBackBufferTAA"), (self._temporalUpscale, "mBackBufferUpscaled")):
+                             (self._depthOfField, "mBackBufferDoF"), (self._sharpening, "mBackBufferSharp"), (self._temporalAA, "mBackBufferTAA"), (self._temporalUpscale, "mBackBufferUpscaled")):
             if switch:
                 return getattr(self, name)
         return self.mBackBufferSSR if self._ssr else self.mBackBuffer
@@ -632,6 +637,15 @@ class Crychic:
             raise CrychicError(-1, "colour_grade needs a table: set colourGrade or pass lut")
         check(lib.crychic_grade(self.ctx.handle, _ptr(src), _ptr(out), W, H, int(row0), int(H - row0 if rows is None else rows), _ptr(table),
                                 int(table.shape[0]), _stream(self.ctx.device)))
+        return out
+
+    def sharpen_frame(self, src=None, out=None, row0=0, rows=None, params=None):
+        """crychic_sharpen on the context's stream: rows [row0, row0 + rows) of `out` (default: mBackBufferSharp, allocated on first use)
+        from `src` (default: mBackBuffer), both (H, W, 4) uint8 tensors of one shape (the frame's, or the display's behind
+        temporalUpscale).  params: a SharpenParams, None = the defaults.  `src` and `out` must not overlap.  Returns `out`."""
+        src, out, H, W = self._pass_frames("sharpen_frame", "mBackBufferSharp", src, out, any_shape=True)
+        check(lib.crychic_sharpen(self.ctx.handle, _ptr(src), _ptr(out), W, H, int(row0), int(H - row0 if rows is None else rows),
+                                  C.byref(params) if params is not None else None, _stream(self.ctx.device)))
         return out
 
     def depth_of_field(self, src=None, out=None, row0=0, rows=None, params=None):

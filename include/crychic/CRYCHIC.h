@@ -170,6 +170,7 @@ public:
         if (mSsrGloss) AllocateSsrPyramid();
         if (mBloom) AllocateBloom();
         if (mColourGrade) mBackBufferGrade = FinalPlane();
+        if (mSharpening) mBackBufferSharp = FinalPlane();
         if (mTemporalAA) AllocateTemporalAA();                                                      // new history planes: the next frame is a reset frame
         if (mMotionBlur) AllocateMotionBlur();                                                      // the next frame counts as the first: no previous camera
         if (mTemporalUpscale) AllocateTemporalUpscale();                                            // the display size stays; the next frame is a reset frame
@@ -214,10 +215,10 @@ public:
 
     void Draw(const GameTimer&)  // CRYCHIC.cpp:172-306, deferred branch
     {
-        if ((!mWholeFrame || mComm) && (mAntiAliasing || mFog || mDepthOfField || mBloom || mTemporalAA || mMotionBlur || mScreenSpaceReflections || mTemporalUpscale || mColourGrade)) {
+        if ((!mWholeFrame || mComm) && (mAntiAliasing || mFog || mDepthOfField || mBloom || mTemporalAA || mMotionBlur || mScreenSpaceReflections || mTemporalUpscale || mColourGrade || mSharpening)) {
             const char* pass = mAntiAliasing ? "anti-aliasing" : mFog ? "fog" : mDepthOfField ? "depth of field" : mBloom ? "bloom"
                              : mTemporalAA ? "temporal anti-aliasing" : mMotionBlur ? "motion blur" : mScreenSpaceReflections ? "screen-space reflections"
-                             : mTemporalUpscale ? "temporal upsampling" : "colour grade";
+                             : mTemporalUpscale ? "temporal upsampling" : mColourGrade ? "colour grade" : "sharpening";
             throw CrychicException(CRYCHIC_E_INVALID_ARG, std::string("CRYCHIC::Draw (") + pass + " takes the whole frame on one GPU: no SetStrip / JoinNode)",
                                    __FILE__, __LINE__);
         }
@@ -342,6 +343,10 @@ public:
             frame = bytes(mBackBufferUpscaled);
             fw = mTuWidth; fh = mTuHeight;
         }
+        if (mSharpening) {                      // what the history fetch softened, before the blurs, the bloom and the edge pass work on it
+            CrychicThrowIfFailed(crychic_sharpen(md3dDevice->Ctx(), frame, bytes(mBackBufferSharp), fw, fh, 0, fh, &mSharpenParams, mCommandList->Stream()));
+            frame = bytes(mBackBufferSharp);
+        }
         if (mDepthOfField) {
             CrychicThrowIfFailed(crychic_dof(md3dDevice->Ctx(), passCB, f.depth_dev, frame, bytes(mBackBufferDoF), mClientWidth, mClientHeight, 0,
                                              mClientHeight, &mDofParams, mCommandList->Stream()));
@@ -372,9 +377,9 @@ public:
     }
 
     // ---- the passes behind the lighting pass (extensions) -----------------------------------------------------------------------------
-    // Nine switches (the temporal upsampling, below, stands at the temporal anti-aliasing's place), all off by default (then nothing changes).  With any of them on, Draw takes a whole frame on one GPU -- SetStrip /
+    // Ten switches (the temporal upsampling, below, stands at the temporal anti-aliasing's place), all off by default (then nothing changes).  With any of them on, Draw takes a whole frame on one GPU -- SetStrip /
     // JoinNode make it throw, the passes are not sharded -- and issues those that are on behind the lighting pass in the order
-    //     lighting -> screen-space reflections (with SetScreenSpaceReflectionGloss: the frame's pyramid and the glossy variant) -> fog (in place) -> temporal anti-aliasing -> depth of field -> motion blur -> bloom -> colour grade -> anti-aliasing.
+    //     lighting -> screen-space reflections (with SetScreenSpaceReflectionGloss: the frame's pyramid and the glossy variant) -> fog (in place) -> temporal anti-aliasing -> sharpening -> depth of field -> motion blur -> bloom -> colour grade -> anti-aliasing.
     // The fog works in place on the frame it is handed: the reflections' buffer if they are on, the back buffer if not.  Every other
     // stage reads the buffer of the nearest stage in front of it that is on and writes one (the back buffer if there is none) and
     // writes a buffer of its own, which exists while the stage is on and which OnResize re-creates; Present writes the last one.
@@ -543,6 +548,26 @@ public:
     uint32_t ColourGradeSize() const { return mGradeN; }
     ID3D12Resource* ColourGradeBackBuffer() { return mBackBufferGrade.get(); }
 
+    // ---- sharpening --------------------------------------------------------------------------------------------------------------------
+    // A contrast-adaptive sharpening of the frame directly behind the temporal stage -- the temporal anti-aliasing or the temporal
+    // upsampling, then at the display size -- and in front of the depth of field (include/crychic_hip.h crychic_sharpen); it stands at
+    // that place when neither is on.
+    void SetSharpening(bool on, const crychic_sharpen_params* p = nullptr)
+    {
+        crychic_sharpen_params q;
+        CrychicThrowIfFailed(crychic_sharpen_default_params(&q));
+        if (p) q = *p;
+        if (q.strength > CRYCHIC_SHARPEN_MAX_STRENGTH || q.limit > CRYCHIC_SHARPEN_MAX_LIMIT || (q.reserved[0] | q.reserved[1]))
+            throw CrychicException(CRYCHIC_E_INVALID_ARG, "CRYCHIC::SetSharpening (strength 0 .. 256, limit 0 .. 3584, reserved 0)", __FILE__, __LINE__);
+        mCommandList->Flush();                                  // a frame in flight may still write the buffer released below
+        mSharpening = on;
+        mSharpenParams = q;
+        if (on) mBackBufferSharp = FinalPlane();
+        else mBackBufferSharp.reset();
+    }
+    bool Sharpening() const { return mSharpening; }
+    ID3D12Resource* SharpenedBackBuffer() { return mBackBufferSharp.get(); }
+
     // ---- temporal anti-aliasing ---------------------------------------------------------------------------------------------------------
     // Jittered frames blended into a reprojected history (include/crychic_hip.h crychic_taa).  On: Update shifts the projection of the
     // main pass and SSAO constants by the frame's sub-pixel offset (crychic_taa_jitter of a running frame index) and keeps the
@@ -592,6 +617,7 @@ public:
             if (mAntiAliasing) mBackBufferAA = FinalPlane();
             if (mBloom) AllocateBloom();
             if (mColourGrade) mBackBufferGrade = FinalPlane();
+            if (mSharpening) mBackBufferSharp = FinalPlane();
         }
     }
     bool TemporalUpscale() const { return mTemporalUpscale; }
@@ -1484,6 +1510,9 @@ private:
     uint32_t mGradeN = 0;
     std::unique_ptr<ID3D12Resource> mGradeLut;         // the table, uploaded by the setter
     std::unique_ptr<ID3D12Resource> mBackBufferGrade;  // the graded frame, while mColourGrade
+    bool mSharpening = false;                 // SetSharpening
+    crychic_sharpen_params mSharpenParams = {};
+    std::unique_ptr<ID3D12Resource> mBackBufferSharp;  // the sharpened frame, while mSharpening
     bool mTemporalAA = false;                 // SetTemporalAA
     crychic_taa_params mTaaParams = {};
     std::unique_ptr<ID3D12Resource> mBackBufferTAA;    // the resolved frame, while mTemporalAA
@@ -1552,7 +1581,7 @@ private:
     ID3D12Resource* FinalFrame() const           // where Draw leaves the finished frame: the buffer of the last stage that is on
     {
         return (mAntiAliasing ? mBackBufferAA : mColourGrade ? mBackBufferGrade : mBloom ? mBackBufferBloom : mMotionBlur ? mBackBufferMB : mDepthOfField ? mBackBufferDoF
-                : mTemporalAA ? mBackBufferTAA : mTemporalUpscale ? mBackBufferUpscaled : mScreenSpaceReflections ? mBackBufferSSR : mBackBuffer).get();
+                : mSharpening ? mBackBufferSharp : mTemporalAA ? mBackBufferTAA : mTemporalUpscale ? mBackBufferUpscaled : mScreenSpaceReflections ? mBackBufferSSR : mBackBuffer).get();
     }
     std::unique_ptr<ID3D12Resource> mDepthStencilBuffer, mBackBuffer, mCubeMap;
     std::unique_ptr<ID3D12Resource> mPointLights, mSpotLights;   // SetLocalLights

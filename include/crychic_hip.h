@@ -1695,6 +1695,54 @@ int crychic_load_cube_lut(const char* path, uint8_t* lut_rgba8, size_t capacityB
 int crychic_grade(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0,
                   uint32_t rows, const uint8_t* lut_rgba8_dev, uint32_t N, void* stream);
 
+/* ---- sharpening: a contrast-adaptive negative-lobe cross filter (extension) -----------------------------------
+ * What the temporal passes' bilinear history fetch softened, put back: a separate call directly behind crychic_taa or
+ * crychic_taa_upscale and in front of the depth of field.  A build definition: nothing of it is the reference's.  It uses 32-bit
+ * integers only, every division is the exact floor of non-negative operands; the device, a host build, the checker
+ * (tests/sharpen_ref) and a numpy restatement agree on every byte.
+ *
+ * For the pixel e at (x, y) the neighbours are b = (x, y - 1), d = (x - 1, y), f = (x + 1, y), h = (x, y + 1), their coordinates
+ * clamped to the frame [0, W - 1] x [0, H - 1] -- not to the row range of the call.  Per channel c = R, G, B on the bytes:
+ *   mn_c = min(b, d, e, f, h)      mx_c = max(b, d, e, f, h)
+ *   q_c  = min( mx_c == 0   ? 0 : (mn_c << 12) / mx_c,
+ *               mn_c == 255 ? 0 : ((255 - mx_c) << 12) / (255 - mn_c) )
+ *   a    = min(q_R, q_G, q_B, limit)
+ *   t    = (a * strength) >> 8
+ *   S_c  = b_c + d_c + f_c + h_c
+ *   num_c = 16384 * e_c - t * S_c          den = 4 * (4096 - t)
+ *   out_c = (num_c + den / 2) / den        out_A = e_A
+ * This is the filter (e - w S) / (1 - 4 w) with one weight w = t / 16384 for the three channels; the limiter q holds w to what the
+ * local minimum and maximum leave room for, so num_c >= 0 and out_c <= 255 always and the definition has no clamp.  Known answers:
+ * strength 0 or limit 0 return the input's bytes; so does a flat neighbourhood at any strength, and a pixel with a 0 or a 255 in
+ * the cross of any of its channels (that channel's q is 0); a centre of 200 in a ring of 100 at strength 256 and the default limit gives
+ * q = 1453, t = 1453 and 255 in each channel.
+ *
+ * Parameters: strength 0 .. CRYCHIC_SHARPEN_MAX_STRENGTH (256: the whole of the limited weight), limit 0 ..
+ * CRYCHIC_SHARPEN_MAX_LIMIT (Q12; the default 3072 is 4 w <= 0.75, that is w <= 0.1875), two reserved words that must be 0.
+ * crychic_sharpen_default_params: strength CRYCHIC_SHARPEN_DEFAULT_STRENGTH -- what tests/sharpen_quality.py measured
+ * (profiles/sharpen_quality.txt) --, limit 3072.
+ *
+ * crychic_sharpen: rows [row0, row0 + rows) of out_rgba8_dev from in_rgba8_dev (rows row0 - 1 .. row0 + rows of it, clamped), and no
+ * other byte; rows == 0 launches nothing; ranges stitch to the whole-frame result.  One launch on `stream`, no LDS: where W is a
+ * multiple of 4 and both planes are 16-byte aligned a lane moves 16 bytes per load and store and takes the pixels beside its four
+ * from the neighbouring lanes; any other width or 4-byte alignment takes a slower kernel of one pixel per lane and is never refused.
+ * No allocation, no synchronisation, no host read-back; capturable into a graph.  CRYCHIC_E_INVALID_ARG with a message, checked
+ * before the context is used and before anything is enqueued: a NULL plane; a plane that is not 4-byte aligned; W or H of 0; a row
+ * range outside the frame; strength or limit outside its range; a reserved word that is not 0; in and out overlapping in any way
+ * (the pass reads neighbours: it cannot run in place).  More than 2^28 pixels: CRYCHIC_E_UNSUPPORTED. */
+#define CRYCHIC_SHARPEN_MAX_STRENGTH 256
+#define CRYCHIC_SHARPEN_MAX_LIMIT 3584
+#define CRYCHIC_SHARPEN_DEFAULT_STRENGTH 96
+#define CRYCHIC_SHARPEN_DEFAULT_LIMIT 3072
+typedef struct crychic_sharpen_params {
+    uint32_t strength;
+    uint32_t limit;
+    uint32_t reserved[2];
+} crychic_sharpen_params;   /* 16 bytes */
+int crychic_sharpen_default_params(crychic_sharpen_params* out);
+int crychic_sharpen(crychic_ctx* ctx, const uint8_t* in_rgba8_dev, uint8_t* out_rgba8_dev, uint32_t W, uint32_t H, uint32_t row0,
+                    uint32_t rows, const crychic_sharpen_params* params /* NULL = defaults */, void* stream);
+
 /* ---- multi-GPU strip plan (pure host arithmetic) ---------------------------------------------- */
 /* Full-res rows [*row0, *row0 + *rows) owned by `rank` of `nranks` for an H-row frame: strips are multiples
  * of 2 rows (half-res alignment); the last rank takes the remainder. */
